@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- MPC receding-horizon steps/s of the HIP path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config {2,3,4,5}]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config {2,3,4,5}] [--dump-outputs DIR]
 
 `--gpus N` (N > 1) started plainly spawns its own N ranks (one per GPU, `python -m torch.distributed.run`, rendezvous on
 127.0.0.1) BEFORE this process imports torch or touches a GPU, relays their output and exits with their code; started
@@ -18,7 +18,11 @@ Weak scaling: every rank owns the same number of egos, no collective on the solv
 all-gathered once at the end (RCCL all-gather; the job's only exchange).  With N > 1 and the default config the line also
 carries `extra`: the per-rank shares of configs 4 and 5 measured in the same job (same protocol).
 
-Prints ONE JSON line (rank 0).  `value` = egos x ticks / wall time (max over ranks).
+Prints ONE JSON line (rank 0).  `value` = egos x ticks / wall time (max over ranks); `ms_per_step` = wall time of the K timed
+ticks / K.
+`--dump-outputs DIR` : after the timed ticks, what they computed in the last one is written as DIR/<name>.npy (float64, one row
+                 per ego; `_rank<r>` appended to the names when N > 1): see dump_outputs().  The egos and routes are seeded, so
+                 the same arguments give the same inputs on every run and two builds can be compared array by array.
 `roofline`     : the dominant kernel against the fp64 peak (the path is bound by single-wave fp64 issue latency, not by HBM
                  and not by MFMA throughput: SURVEY D6); `roofline_hbm` carries the algorithmic-bytes-vs-HBM figure.
 `cpu_baseline` : the CPU oracle (a C port of the reference path; the reference's cvxpy/ECOS stack cannot be installed)
@@ -37,6 +41,7 @@ sys.path.insert(0, REPO)
 
 FP64_PEAK_TFLOPS = 78.6   # MI355X fp64 vector == fp64 matrix peak
 HBM_PEAK_GBS = 8000.0     # /opt/skills/guides/MI355X_MICROARCH.md
+DUMP_CAP_BYTES = 64 << 20  # --dump-outputs: at most this much in all (a seeded sample of egos beyond it)
 
 # The workloads (CONFIGS, OBSTACLE_SPECS, route tables, ego batches, loop objects) live in the package's workloads.py: ONE
 # definition shared with tests/test_gpu_bench_workloads.py, which checks these very egos and routes against the oracle.
@@ -102,6 +107,8 @@ def parse_args(argv=None):
                     help="skip the second, shorter run of the same workload under the other respawn rule (reported beside the headline)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=14.0)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last tick as DIR/<name>.npy (see dump_outputs())")
     return ap.parse_args(argv)
 
 
@@ -177,14 +184,15 @@ def main():
         pkg._cabi.check(eng.lib.jsim_mpc_iter_totals(eng._ctx, eng.B, tot.ctypes.data, 1 if reset else 0), eng._ctx, "jsim_mpc_iter_totals")
         return tot
 
-    def run_workload(cfg_id, B, T, K, W, mode, tpl, respawn):
+    def run_workload(cfg_id, B, T, K, W, mode, tpl, respawn, dump_dir=None):
         """W untimed ticks, then EXACTLY K timed ticks bracketed by barrier + synchronize; returns the figures of this rank
-        (elapsed = max over ranks)."""
+        (elapsed = max over ranks).  dump_dir: write the last timed tick's outputs there (dump_outputs())."""
         cfg = CONFIGS[cfg_id]
         routes = route_table(cfg["multi_lane"])
         batch = WL.ego_batch(routes, B, T, rank=rank)
         eng, x0 = WL.make_engine(routes, batch, T, device)
-        sc, loop = WL.make_loop(cfg_id, eng, x0, hist_cap=K + W + 64, routes=routes, batch=batch, respawn=respawn)
+        # the history holds every tick up to the last timed one (the untimed first launch is `tpl` ticks long at most)
+        sc, loop = WL.make_loop(cfg_id, eng, x0, hist_cap=K + W + 64 + max(tpl, 0), routes=routes, batch=batch, respawn=respawn)
         if sc is not None:
             tick, run = sc.tick, sc.run
             mode = "fused" if mode == "graph" else mode
@@ -263,6 +271,14 @@ def main():
                           # evidence in the data itself: rank blocks of the gathered tensor that arrived non-empty
                           "rank_blocks_with_data": int((hist_all.reshape(world, -1).abs().sum(dim=1) > 0).sum().item()),
                           "ms": float(gev[0].elapsed_time(gev[1]))}
+        if dump_dir:
+            # what the last timed tick left for a caller (read before the untimed launches below change it): the controls it
+            # applied (from the recorded history), the plant state after it, the MPC solution / warm start, status, index, path
+            last = int(loop.tick_counter.item()) - 1
+            assert 0 <= last < loop.hist_cap, (last, loop.hist_cap)
+            dump_outputs(dump_dir, {"controls": loop.hist[last], "state": loop.x0, "oa": eng.oa, "od": eng.od,
+                                    "status": eng.status, "target_ind": eng.target_ind, "path_len": eng.path_len},
+                         suffix=f"_rank{rank}" if world > 1 else "")
         eng_cut_last = (eng.path_len < eng.full_len).sum() if sc is not None else None
         elapsed = torch.tensor([t1 - t0], dtype=torch.float64, device="cpu" if rehearsal else device)
         if world > 1:
@@ -307,7 +323,7 @@ def main():
     cfg = CONFIGS[args.config]
     B = args.batch or cfg["batch"]
     T = args.horizon or cfg["horizon"]
-    main_res = run_workload(args.config, B, T, K, W, args.mode, args.ticks_per_launch, args.respawn)
+    main_res = run_workload(args.config, B, T, K, W, args.mode, args.ticks_per_launch, args.respawn, dump_dir=args.dump_outputs)
     other = None
     if args.mode == "fused" and not args.no_respawn_start:
         # the same workload and kernels under the OTHER respawn rule, a shorter run of the same protocol: the default rule keeps
@@ -404,6 +420,33 @@ def main():
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
+
+
+def dump_outputs(out_dir, arrays, cap_bytes=DUMP_CAP_BYTES, seed=0, suffix=""):
+    """Write `arrays` (name -> tensor or array, first axis = ego) as out_dir/<name><suffix>.npy in float64 (integer arrays
+    convert exactly).  Beyond `cap_bytes` in all, the same fixed seeded sample of egos (ascending) is written from every array,
+    and its indices as ego_index<suffix>.npy.  Returns the file names written."""
+    import numpy as np
+    out = {}
+    for name, a in arrays.items():
+        if hasattr(a, "detach"):
+            a = a.detach().cpu().numpy()
+        out[name] = np.ascontiguousarray(a, dtype=np.float64)
+    n = {a.shape[0] for a in out.values()}
+    assert len(n) == 1, {k: a.shape for k, a in out.items()}
+    n = n.pop()
+    total = sum(a.nbytes for a in out.values())
+    if total > cap_bytes:
+        per_ego = total // max(n, 1) + 8                 # + its entry in ego_index
+        keep = np.sort(np.random.default_rng(seed).choice(n, size=max(1, cap_bytes // per_ego), replace=False))
+        out = {k: np.ascontiguousarray(a[keep]) for k, a in out.items()}
+        out["ego_index"] = keep.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    names = []
+    for name, a in out.items():
+        names.append(f"{name}{suffix}.npy")
+        np.save(os.path.join(out_dir, names[-1]), a)
+    return names
 
 
 def straggler_stats(totals, K):

@@ -2,6 +2,7 @@
 """Fixtures of stage S4 AS THE REFERENCE ASSEMBLES IT: tests/golden/ref_qp_T{13,20,30,40}.npz + ref_qp_sweep.json.
 
 Run in the build container only (needs /root/reference):    python tests/golden/make_golden_refqp.py [T ...]
+                                                           python tests/golden/make_golden_refqp.py live
 
 What runs.  The reference's `lib.mpc` is imported from /root/reference/main with tests/golden/cvxpy_recorder.py registered as
 `cvxpy` (the real cvxpy / ECOS are not installed, pinned or fetchable: SURVEY.md D5), and for every case the reference's own
@@ -26,7 +27,7 @@ Cases: the 54 G3 cases of make_golden_qp.py (every constraint family active, the
 start) + 96 more seeded random egos (truncated paths, 30 % near the path end).
 
 Checked here, before anything is written (the same checks are tests: tests/test_ref_qp_cpu.py on the fixtures,
-tests/test_ref_qp_live.py on fresh cases when /root/reference is present):
+tests/test_ref_qp_live.py on the seeded cases of ref_qp_live_T*.npz, which `live` writes):
   * the oracle's condensed (H, g, G, h) equal the emitted problem after GENERIC elimination of x through A z = b
     (tests/qp_sparse_numpy.condense) to <= 1e-12 relative (g: 1e-11), row for row in the emitted order;
   * the oracle's status, target_ind, xref equal the reference's bit for bit; u*, predicted states <= 1e-8; active sets equal.
@@ -55,6 +56,7 @@ for p in (REPO, os.path.join(REPO, "oracle"), os.path.join(REPO, "tests"), HERE)
 TS = (13, 20, 30, 40)
 N_EXTRA = 96
 N_SWEEP = 1000
+LIVE, LIVE_SEED = ((13, 120), (20, 100), (30, 70), (40, 50)), 9000      # (horizon, egos) of ref_qp_live_T*.npz
 DL, DT = 0.083, 0.2
 
 
@@ -150,6 +152,36 @@ def coo(M):
     return i.astype(np.int16), j.astype(np.int16), M[i, j]
 
 
+def save_fixture(path, cases, recs, outs):
+    """Write one horizon's cases in the ref_qp_T*.npz layout (read back by tests/refqp_tools.py)."""
+    src_eq, src_in = recs[0]["eq_src"], recs[0]["in_src"]
+    assert all(np.array_equal(r["eq_src"], src_eq) and np.array_equal(r["in_src"], src_in) for r in recs)
+    parts = {k: [coo(r[k]) for r in recs] for k in ("P", "A", "G")}
+    save = {}
+    for k, lst in parts.items():
+        save[f"{k}_ptr"] = np.cumsum([0] + [len(t[2]) for t in lst]).astype(np.int64)
+        save[f"{k}_i"] = np.concatenate([t[0] for t in lst]); save[f"{k}_j"] = np.concatenate([t[1] for t in lst])
+        save[f"{k}_v"] = np.concatenate([t[2] for t in lst])
+    kk = lambda name: np.array([r["kkt"][name] if r["kkt"] else 0.0 for r in recs])
+    np.savez_compressed(
+        path,
+        x0=np.array([c[0] for c in cases]), path_id=np.array([c[1] for c in cases], dtype=np.int32),
+        path_len=np.array([c[2] for c in cases], dtype=np.int32), target_ind_in=np.array([c[3] for c in cases], dtype=np.int64),
+        speed=np.array([c[4] for c in cases]), oa_in=np.array([c[5] for c in cases]), od_in=np.array([c[6] for c in cases]),
+        degenerate=np.array([o["degenerate"] for o in outs]), tight=np.array([o["tight"] for o in outs]),
+        active=np.array([o["active"] for o in outs]),
+        n_z=np.int64(recs[0]["n"]), eq_src=src_eq, in_src=src_in, q=np.array([r["q"] for r in recs]), c0=np.array([r["c0"] for r in recs]),
+        b=np.array([r["b"] for r in recs]), h=np.array([r["h"] for r in recs]), **save,
+        status=np.array([o["status"] for o in outs], dtype=np.int32), di=np.array([o["di"] for o in outs]),
+        ai=np.array([o["ai"] for o in outs]), di_kept=np.array([o["di_kept"] for o in outs]),
+        target_ind_out=np.array([o["target_ind"] for o in outs], dtype=np.int64), xref=np.array([o["xref"] for o in outs]),
+        oa=np.array([o["oa"] for o in outs]), od=np.array([o["od"] for o in outs]), ox=np.array([o["ox"] for o in outs]),
+        oy=np.array([o["oy"] for o in outs]), ov=np.array([o["ov"] for o in outs]), oyaw=np.array([o["oyaw"] for o in outs]),
+        lam=np.array([o["lam"] for o in outs]),
+        kkt_stationarity=kk("stationarity"), kkt_primal_eq=kk("primal_eq"), kkt_primal_in=kk("primal_in"), kkt_dual_min=kk("dual_min"),
+        du_ipm_vs_polish=kk("du_ipm"))
+
+
 def main():
     if not os.path.isdir(REF_MAIN):
         raise SystemExit("reference not present; these fixtures can only be generated in the build container")
@@ -186,33 +218,8 @@ def main():
                 out["tight"], out["degenerate"], out["active"] = np.zeros(8 * T, dtype=bool), False, np.zeros(8 * T, dtype=bool)
             recs.append(r); outs.append(out); figs.append(f)
         n = len(cases)
-        src_eq, src_in = recs[0]["eq_src"], recs[0]["in_src"]
-        assert all(np.array_equal(r["eq_src"], src_eq) and np.array_equal(r["in_src"], src_in) for r in recs)
-        parts = {k: [coo(r[k]) for r in recs] for k in ("P", "A", "G")}
-        save = {}
-        for k, lst in parts.items():
-            save[f"{k}_ptr"] = np.cumsum([0] + [len(t[2]) for t in lst]).astype(np.int64)
-            save[f"{k}_i"] = np.concatenate([t[0] for t in lst]); save[f"{k}_j"] = np.concatenate([t[1] for t in lst])
-            save[f"{k}_v"] = np.concatenate([t[2] for t in lst])
+        save_fixture(os.path.join(HERE, f"ref_qp_T{T}.npz"), cases, recs, outs)
         solved = np.array([o["status"] == 0 for o in outs])
-        kk = lambda name: np.array([r["kkt"][name] if r["kkt"] else 0.0 for r in recs])
-        np.savez_compressed(
-            os.path.join(HERE, f"ref_qp_T{T}.npz"),
-            x0=np.array([c[0] for c in cases]), path_id=np.array([c[1] for c in cases], dtype=np.int32),
-            path_len=np.array([c[2] for c in cases], dtype=np.int32), target_ind_in=np.array([c[3] for c in cases], dtype=np.int64),
-            speed=np.array([c[4] for c in cases]), oa_in=np.array([c[5] for c in cases]), od_in=np.array([c[6] for c in cases]),
-            degenerate=np.array([o["degenerate"] for o in outs]), tight=np.array([o["tight"] for o in outs]),
-            active=np.array([o["active"] for o in outs]),
-            n_z=np.int64(recs[0]["n"]), eq_src=src_eq, in_src=src_in, q=np.array([r["q"] for r in recs]), c0=np.array([r["c0"] for r in recs]),
-            b=np.array([r["b"] for r in recs]), h=np.array([r["h"] for r in recs]), **save,
-            status=np.array([o["status"] for o in outs], dtype=np.int32), di=np.array([o["di"] for o in outs]),
-            ai=np.array([o["ai"] for o in outs]), di_kept=np.array([o["di_kept"] for o in outs]),
-            target_ind_out=np.array([o["target_ind"] for o in outs], dtype=np.int64), xref=np.array([o["xref"] for o in outs]),
-            oa=np.array([o["oa"] for o in outs]), od=np.array([o["od"] for o in outs]), ox=np.array([o["ox"] for o in outs]),
-            oy=np.array([o["oy"] for o in outs]), ov=np.array([o["ov"] for o in outs]), oyaw=np.array([o["oyaw"] for o in outs]),
-            lam=np.array([o["lam"] for o in outs]),
-            kkt_stationarity=kk("stationarity"), kkt_primal_eq=kk("primal_eq"), kkt_primal_in=kk("primal_in"), kkt_dual_min=kk("dual_min"),
-            du_ipm_vs_polish=kk("du_ipm"))
         mx = lambda name: max(f.get(name, 0.0) for f in figs)
         print(f"T={T}: {n} cases ({int(solved.sum())} solved, {int((~solved).sum())} infeasible); oracle vs the reference's emitted problem: "
               f"dH {mx('dH'):.1e} dg {mx('dg'):.1e} dG {mx('dG'):.1e} dh {mx('dh'):.1e}; vs its outputs: du {mx('du'):.1e} dx {mx('dx'):.1e} "
@@ -249,5 +256,43 @@ def main():
         json.dump(old, f, indent=1, sort_keys=True)
 
 
+def main_live():
+    """tests/golden/ref_qp_live_T*.npz: the reference's step on the seeded egos of tests/test_ref_qp_live.py (cases no other
+    fixture holds), compared with the oracle under that test's bars before anything is written."""
+    if not os.path.isdir(REF_MAIN):
+        raise SystemExit("reference not present; these fixtures can only be generated in the build container")
+    import oracle_py as O
+    import qp_sparse_numpy as QS
+    O.build()
+    pkg = importlib.import_module("av-simulation-at-intersections_amd")
+    routes = pkg.synth.make_route_table()
+    for r_ in routes:
+        pkg.synth.smooth_yaw_inplace(r_[:, 2])
+    for T, n in LIVE:
+        refmpc, rec = import_reference(T)
+        from lib.car_dimensions import BicycleModelDimensions
+        from lib.simulation import State
+        car = BicycleModelDimensions()
+        b = pkg.synth.make_ego_batch(routes, n, T, seed=LIVE_SEED + T, truncate=True, near_end_frac=0.25)
+        cases = [(b.x0[i].copy(), int(b.path_id[i]), int(b.path_len[i]), int(b.target_ind[i]), float(b.speed[i]), b.oa[i].copy(),
+                  b.od[i].copy(), "live") for i in range(n)]
+        recs, outs, figs = [], [], []
+        for c in cases:
+            r, out = reference_step(refmpc, rec, car, State, routes[c[1]], c)
+            figs.append(compare_with_oracle(O, QS, pkg, T, routes[c[1]], c, r, out))
+            if out["status"] != 0:
+                out["tight"], out["degenerate"], out["active"] = np.zeros(8 * T, dtype=bool), False, np.zeros(8 * T, dtype=bool)
+            recs.append(r); outs.append(out)
+        mx = lambda k: max(f.get(k, 0.0) for f in figs)
+        assert all(f["status_equal"] and f["target_equal"] and f["xref_equal"] for f in figs)
+        assert mx("dH") <= 1e-12 and mx("dG") <= 1e-12 and mx("dh") <= 1e-12 and mx("dg") <= 1e-11
+        assert mx("du") <= 1e-8 and mx("dx") <= 1e-8
+        save_fixture(os.path.join(HERE, f"ref_qp_live_T{T}.npz"), cases, recs, outs)
+        print(f"T={T}: {n} live cases, {sum('du' in f for f in figs)} solved, du {mx('du'):.1e} dx {mx('dx'):.1e}")
+
+
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:2] == ["live"]:
+        main_live()
+    else:
+        main()

@@ -230,3 +230,23 @@ def test_bench_line_fields():
     assert abs(j["roofline"]["algorithmic_flops_per_launch"] / flops - 1.0) < 2e-3 and j["roofline"]["ticks_per_launch"] == 20
     spec_src = open(os.path.join(REPO, "bench.py")).read()
     assert 'mpc_step_reg4_kernel<{T}, {pre}>' in spec_src and "reg2" not in spec_src
+
+
+def test_bench_dump_outputs_are_reproducible(tmp_path):
+    """`python bench.py --dump-outputs DIR`: the last timed tick's controls, state, solution, status, index and path of every
+    ego as float64 .npy files; two runs with the same arguments write identical arrays."""
+    runs = []
+    for d in ("a", "b"):
+        out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "20", "--warmup", "3", "--no-cpu-baseline",
+                              "--no-respawn-start", "--dump-outputs", str(tmp_path / d)], capture_output=True, text=True, timeout=900)
+        assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
+        j = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith('{"metric"')][0])
+        assert j["steps"] == 20 and j["ms_per_step"] > 0
+        runs.append({f[:-4]: np.load(tmp_path / d / f) for f in sorted(os.listdir(tmp_path / d))})
+    a, b = runs
+    B, T = j["config"]["egos_per_gpu"], j["config"]["horizon"]
+    shapes = {"controls": (B, 2), "state": (B, 4), "oa": (B, T), "od": (B, T), "status": (B,), "target_ind": (B,), "path_len": (B,)}
+    assert {k: v.shape for k, v in a.items()} == shapes and all(v.dtype == np.float64 for v in a.values())
+    assert all(np.isfinite(v).all() for v in a.values()) and np.abs(a["controls"]).max() > 0
+    for k in shapes:
+        assert np.array_equal(a[k], b[k]), k

@@ -349,3 +349,32 @@ def test_bench_line_helpers():
     assert bench.latest_pmc_summary(2, 100) == pm and bench.latest_pmc_summary(2, 37) == pm
     d = json.load(open(pm))
     assert "FETCH_SIZE" in d and "WRITE_SIZE" in d and d.get("commit", "?") != "?"
+
+
+def test_bench_dump_outputs_writes_float64_and_a_seeded_sample_beyond_the_cap(tmp_path):
+    """bench.py --dump-outputs: every array as <name>.npy in float64 (integers exact); beyond the cap the same seeded egos of
+    every array, ascending, with their indices, identical from call to call."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod3", os.path.join(REPO, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    assert bench.parse_args(["--dump-outputs", "d"]).dump_outputs == "d" and bench.parse_args([]).dump_outputs is None
+    B = 1000
+    arrays = {"state": np.arange(B * 4, dtype=np.float64).reshape(B, 4), "status": np.arange(B, dtype=np.int32) % 3,
+              "target_ind": np.arange(B, dtype=np.int64) * 7}
+    names = bench.dump_outputs(str(tmp_path / "all"), arrays, suffix="_rank1")
+    assert sorted(names) == ["state_rank1.npy", "status_rank1.npy", "target_ind_rank1.npy"]
+    for k, a in arrays.items():
+        got = np.load(tmp_path / "all" / f"{k}_rank1.npy")
+        assert got.dtype == np.float64 and np.array_equal(got, a)
+    cap = 10_000
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), arrays, cap_bytes=cap)
+    idx = np.load(tmp_path / "s1" / "ego_index.npy")
+    assert np.array_equal(idx, np.load(tmp_path / "s2" / "ego_index.npy")) and np.all(np.diff(idx) > 0)
+    total = 0
+    for k, a in arrays.items():
+        got = np.load(tmp_path / "s1" / f"{k}.npy")
+        assert got.dtype == np.float64 and np.array_equal(got, a[idx.astype(np.int64)])
+        total += got.nbytes
+    assert len(idx) == cap // (6 * 8 + 8) and total + idx.nbytes <= cap          # 6 values + the index entry per ego
