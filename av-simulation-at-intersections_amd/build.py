@@ -6,6 +6,12 @@ import os
 import shutil
 import subprocess
 
+if __package__:
+    from . import config, isa_exec_check
+else:                                      # run as a script: python av-simulation-at-intersections_amd/build.py
+    import config
+    import isa_exec_check
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(_HERE, "csrc", "jsim_mpc.hip")
 INC = os.path.join(os.path.dirname(_HERE), "include")
@@ -40,19 +46,14 @@ def needs_build() -> bool:
     if not os.path.exists(LIB):
         return True
     csrc = os.path.join(_HERE, "csrc")
-    deps = [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith((".hip", ".inc"))] + [os.path.join(INC, "jsim_mpc.h")]
+    deps = [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith((".hip", ".inc", ".h"))] + [os.path.join(INC, "jsim_mpc.h")]
     return os.path.getmtime(LIB) < max(os.path.getmtime(d) for d in deps)
 
 
 def check_isa(asm_path: str) -> None:
     """The build-time guard of DESIGN.md section 5, fact 6: refuse a library in which a vector instruction sits in a join
-    block in front of that block's exec restore (tools/isa_exec_check.py explains the pattern and how it miscomputes)."""
-    import importlib.util
-    tool = os.path.join(os.path.dirname(_HERE), "tools", "isa_exec_check.py")
-    spec = importlib.util.spec_from_file_location("jsim_isa_exec_check", tool)
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    findings = mod.check(asm_path)
+    block in front of that block's exec restore (isa_exec_check.py explains the pattern and how it miscomputes)."""
+    findings = isa_exec_check.check(asm_path)
     if findings:
         lines = [f"{k[:70]} block {b}: {len(ins)} vector instruction(s) in front of the exec restore at {asm_path}:{ln}"
                  for k, b, ln, ins in findings]
@@ -60,14 +61,14 @@ def check_isa(asm_path: str) -> None:
                            "restore (lanes outside the mask keep stale values; DESIGN.md section 5, fact 6):\n  " + "\n  ".join(lines))
 
 
-KERNEL_TUS = (13, 15, 16, 20, 25, 30, 32, 40)   # one translation unit per horizon with a register kernel (csrc/jsim_mpc.hip, JSIM_KERNEL_TU)
+KERNEL_TUS = tuple(sorted({row[1] for row in config.REG_VARIANTS}))   # one translation unit per horizon with a register kernel (JSIM_KERNEL_TU)
 ASM_NAME = "jsim_mpc-hip-amdgcn-amd-amdhsa-gfx950.s"
 
 
 def _build_split(hipcc: str, extra, obj_dir: str, tmp_lib: str, verbose: bool) -> None:
     """The library from nine translation units compiled in parallel: csrc/jsim_mpc.hip once per horizon (-DJSIM_KERNEL_TU=T: that
-    horizon's register kernels, explicitly instantiated) and once for everything else (-DJSIM_SPLIT_BUILD: the same kernels declared
-    `extern template`), then one link.  Every unit's device listing goes through the ISA guard; the listings are concatenated into
+    horizon's rows of csrc/reg_variants.h, explicitly instantiated) and once for everything else (-DJSIM_SPLIT_BUILD: the same
+    kernels declared `extern template`), then one link.  Every unit's device listing goes through the ISA guard; the listings are concatenated into
     the path the one-unit build leaves its listing at (tests and tools read that file)."""
     flags = [f for f in HIPCC_FLAGS if f != "-shared"]
     units = [("main", ["-DJSIM_SPLIT_BUILD"])] + [(f"T{t}", [f"-DJSIM_KERNEL_TU={t}"]) for t in KERNEL_TUS]
@@ -106,7 +107,7 @@ def _build_split(hipcc: str, extra, obj_dir: str, tmp_lib: str, verbose: bool) -
 
 def build(force: bool = False, verbose: bool = False) -> str:
     if force or needs_build():
-        extra = os.environ.get("JSIM_HIPCC_EXTRA", "").split()   # diagnostic builds (-DJSIM_STAMPS, -DJSIM_DEV_ONLY_T40, ...)
+        extra = os.environ.get("JSIM_HIPCC_EXTRA", "").split()   # diagnostic builds (-DJSIM_STAMPS, -DJSIM_DEV_ONLY_T=40, -DJSIM_DEV_NO_REG, ...)
         out = os.environ.get("JSIM_LIB_OUT", LIB)
         obj_dir = OBJ_DIR if out == LIB else os.path.join(os.path.dirname(os.path.abspath(out)), "obj")
         os.makedirs(obj_dir, exist_ok=True)

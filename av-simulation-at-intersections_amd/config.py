@@ -10,12 +10,25 @@ from typing import List, Optional
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 DEFAULT_CONFIG_PATH = os.path.join(_HERE, "mpc_config.json")
-# Horizons with a register-resident kernel in libjsim_mpc.so (csrc/jsim_mpc.hip: JSIM_ONE_WAVE_HORIZONS / JSIM_FOUR_WAVE_HORIZONS; a
-# CPU test compares the lists).  Any other T <= 48 runs on the LDS kernel: same results, 4-6 x slower.
-ONE_WAVE_HORIZONS = (13, 15, 16, 20, 25, 30)
-FOUR_WAVE_HORIZONS = (32, 40)
-HELP_HORIZONS = (13, 15, 16, 20, 25)     # one-wave horizons with the three-helper-wavefronts form, taken for batches of up to 256 egos
-HELP_PRE_HORIZONS = (13, 20)             # ... those whose scenario-loop form (the glue inside the launch) has helpers, too
+# The register-resident kernels of libjsim_mpc.so, (W, T, PRE, WPE, HELP) per instantiation: csrc/reg_variants.h's table, which
+# explains the columns (a CPU test compiles the header and compares).  Any other T <= 48 runs on the LDS kernel: same results, 4-6 x
+# slower.
+REG_VARIANTS = (
+    (1, 13, True, 1, False), (1, 13, False, 2, False), (1, 13, False, 1, True), (1, 13, True, 1, True),
+    (1, 15, True, 1, False), (1, 15, False, 1, False), (1, 15, False, 1, True),
+    (1, 16, True, 1, False), (1, 16, False, 1, False), (1, 16, False, 1, True),
+    (1, 20, True, 1, False), (1, 20, False, 1, False), (1, 20, False, 2, False), (1, 20, False, 1, True), (1, 20, True, 1, True),
+    (1, 25, True, 1, False), (1, 25, False, 1, False), (1, 25, False, 1, True),
+    (1, 30, True, 1, False), (1, 30, False, 1, False),
+    (4, 32, True, 1, False), (4, 32, False, 1, False),
+    (4, 40, True, 1, False), (4, 40, False, 1, False),
+)
+ONE_WAVE_HORIZONS = tuple(sorted({T for W, T, _, _, _ in REG_VARIANTS if W == 1}))
+FOUR_WAVE_HORIZONS = tuple(sorted({T for W, T, _, _, _ in REG_VARIANTS if W == 4}))
+# one-wave horizons with the three-helper-wavefronts form, taken for batches of up to one ego per CU (256 egos on an MI355X) ...
+HELP_HORIZONS = tuple(sorted({T for W, T, PRE, _, HELP in REG_VARIANTS if HELP and not PRE}))
+# ... and those whose scenario-loop form (the glue inside the launch) has helpers, too
+HELP_PRE_HORIZONS = tuple(sorted({T for W, T, PRE, _, HELP in REG_VARIANTS if HELP and PRE}))
 
 
 def deg2rad(x: float) -> float:

@@ -1075,161 +1075,57 @@ __global__ __launch_bounds__(64) void mpc_step_kernel(const KP Pin)
 #include "reg_common.inc"
 #include "mpc_step_reg4.inc"
 
-// Horizons with a register-resident kernel.  One wavefront per ego: every row stored for 13 <= T <= 20 (3T+1 <= 63 lanes), virtual
-// speed rows for 21 <= T <= 31; four wavefronts per ego (two lanes per row) for T = 32 and 40 (half rows in panels of eight).  The
-// kernels are templates on T, fully unrolled -- a horizon is fast if it is in one of these lists (7 s of compile time per
-// instantiation) and runs on the LDS kernel otherwise (any T <= 48; 4-6 x slower: tools/dev/horizon_ab.py).  BASELINE.json's
-// configurations use 13 (the reference's stock horizon), 20, 30 and 40; the others are there so that a horizon near them does not
-// fall off that cliff.  Mirrored by config.ONE_WAVE_HORIZONS / FOUR_WAVE_HORIZONS / HELP_HORIZONS (tests/test_host_cpu.py compares them).
-#define JSIM_ONE_WAVE_HORIZONS(X) X(13) X(15) X(16) X(20) X(25) X(30)
-#define JSIM_FOUR_WAVE_HORIZONS(X) X(32) X(40)
-// one-wave horizons that also have the form with three helper wavefronts per ego, taken at B <= 256 (one ego per CU at most).  Measured
-// at 256 egos, closed loop (tools/dev/help_ab13.py): T = 13 +8 %, 15 +6 %, 16 +11 %, 20 +11-14 %, 25 +6 %; T = 30 LOSES 2 % (448
-// registers, 72 KB of LDS: handing 61 rows of 60 doubles over costs what the helpers save) and is left out.
-#define JSIM_HELP_HORIZONS(X) X(13) X(15) X(16) X(20) X(25)
-// ... and those whose form with the loop glue inside the launch (PRE) has helpers too: the reference's stock horizon and the headline's.
-// (T = 16 with PRE and helpers is a build the ISA guard refuses -- vector code in front of a join block's exec restore, section 5 fact 6 of
-// DESIGN.md -- and is not instantiated.)
-#define JSIM_HELP_PRE_HORIZONS(X) X(13) X(20)
+#include "reg_variants.h"
 
 // ---- Split build (build.py's default: one translation unit per horizon, compiled in parallel -- 3 minutes of one core otherwise).
-// -DJSIM_KERNEL_TU=<T>: this file up to here plus the explicit instantiations of horizon T's register kernels, nothing else.
-// -DJSIM_SPLIT_BUILD  : the rest of the library, with those instantiations declared `extern template` (their host stubs and code
-//                       objects come from the kernel translation units).  Neither: everything in one unit, as before.
-// The `#if` lists below repeat the three horizon lists above (tests/test_host_cpu.py compares them).
+// -DJSIM_KERNEL_TU=<T>: this file up to here plus the explicit instantiations of horizon T's rows of reg_variants.h, nothing else.
+// -DJSIM_SPLIT_BUILD  : the rest of the library, with every row declared `extern template` (their host stubs and code objects come
+//                       from the kernel translation units).  Neither: everything in one unit.
+#define JSIM_REG_KERNEL_1(T, PRE, WPE, HELP) mpc_step_reg_kernel<T, PRE, WPE, HELP>
+#define JSIM_REG_KERNEL_4(T, PRE, WPE, HELP) mpc_step_reg4_kernel<T, PRE>
+#define JSIM_REG_KERNEL(W, T, PRE, WPE, HELP) JSIM_CAT(JSIM_REG_KERNEL_, W)(T, PRE, WPE, HELP)
 #define JSIM_REG_ARGS const KP, const TickP, const PreK
 #if defined(JSIM_KERNEL_TU)
-#if JSIM_KERNEL_TU == 32 || JSIM_KERNEL_TU == 40                                                            /* four-wave horizons */
-template __global__ void mpc_step_reg4_kernel<JSIM_KERNEL_TU, true>(JSIM_REG_ARGS);
-template __global__ void mpc_step_reg4_kernel<JSIM_KERNEL_TU, false>(JSIM_REG_ARGS);
-#elif JSIM_KERNEL_TU == 13 || JSIM_KERNEL_TU == 15 || JSIM_KERNEL_TU == 16 || JSIM_KERNEL_TU == 20 || JSIM_KERNEL_TU == 25 || JSIM_KERNEL_TU == 30   /* one-wave horizons */
-template __global__ void mpc_step_reg_kernel<JSIM_KERNEL_TU, true, 1, false>(JSIM_REG_ARGS);
-template __global__ void mpc_step_reg_kernel<JSIM_KERNEL_TU, false, (JSIM_KERNEL_TU == 13 ? 2 : 1), false>(JSIM_REG_ARGS);
-#if JSIM_KERNEL_TU == 20
-template __global__ void mpc_step_reg_kernel<20, false, 2, false>(JSIM_REG_ARGS);
-#endif
-#if JSIM_KERNEL_TU == 13 || JSIM_KERNEL_TU == 15 || JSIM_KERNEL_TU == 16 || JSIM_KERNEL_TU == 20 || JSIM_KERNEL_TU == 25                            /* helper-wavefront horizons */
-template __global__ void mpc_step_reg_kernel<JSIM_KERNEL_TU, false, 1, true>(JSIM_REG_ARGS);
-#endif
-#if JSIM_KERNEL_TU == 13 || JSIM_KERNEL_TU == 20                                                                                                    /* helper-wavefront horizons with the glue */
-template __global__ void mpc_step_reg_kernel<JSIM_KERNEL_TU, true, 1, true>(JSIM_REG_ARGS);
-#endif
-#else
+#define JSIM_X(w, t, p, e, h) + (t == JSIM_KERNEL_TU)
+#if (0 JSIM_REG_VARIANTS(JSIM_X)) == 0
 #error "JSIM_KERNEL_TU: not a horizon with a register kernel"
 #endif
+#undef JSIM_X
+#define JSIM_X(w, t, p, e, h) template __global__ void JSIM_REG_KERNEL(w, t, p, e, h)(JSIM_REG_ARGS);
+JSIM_CAT(JSIM_REG_ROW_, JSIM_KERNEL_TU)(JSIM_X)
+#undef JSIM_X
 #else /* !JSIM_KERNEL_TU: the library proper */
 #if defined(JSIM_SPLIT_BUILD)
-#define JSIM_X(t) extern template __global__ void mpc_step_reg_kernel<t, true, 1, false>(JSIM_REG_ARGS); \
-                  extern template __global__ void mpc_step_reg_kernel<t, false, (t == 13 ? 2 : 1), false>(JSIM_REG_ARGS);
-JSIM_ONE_WAVE_HORIZONS(JSIM_X)
-#undef JSIM_X
-extern template __global__ void mpc_step_reg_kernel<20, false, 2, false>(JSIM_REG_ARGS);
-#define JSIM_X(t) extern template __global__ void mpc_step_reg_kernel<t, false, 1, true>(JSIM_REG_ARGS);
-JSIM_HELP_HORIZONS(JSIM_X)
-#undef JSIM_X
-#define JSIM_X(t) extern template __global__ void mpc_step_reg_kernel<t, true, 1, true>(JSIM_REG_ARGS);
-JSIM_HELP_PRE_HORIZONS(JSIM_X)
-#undef JSIM_X
-#define JSIM_X(t) extern template __global__ void mpc_step_reg4_kernel<t, true>(JSIM_REG_ARGS); \
-                  extern template __global__ void mpc_step_reg4_kernel<t, false>(JSIM_REG_ARGS);
-JSIM_FOUR_WAVE_HORIZONS(JSIM_X)
+#define JSIM_X(w, t, p, e, h) extern template __global__ void JSIM_REG_KERNEL(w, t, p, e, h)(JSIM_REG_ARGS);
+JSIM_REG_VARIANTS(JSIM_X)
 #undef JSIM_X
 #endif
-#if defined(JSIM_DEV_NO_REG)
-static bool has_reg_kernel(int) { return false; }
-#elif defined(JSIM_DEV_ONLY_T40)
-static bool has_reg_kernel(int T) { return T == 40; }
-#elif defined(JSIM_DEV_ONLY_T30)
-static bool has_reg_kernel(int T) { return T == 30; }
-#elif defined(JSIM_DEV_ONLY_T20)
-static bool has_reg_kernel(int T) { return T == 20; }
-#else
-static bool has_reg_kernel(int T)
+
+static int device_cu_count()
 {
-#define JSIM_X(t) if (T == t) return true;
-    JSIM_ONE_WAVE_HORIZONS(JSIM_X) JSIM_FOUR_WAVE_HORIZONS(JSIM_X)
-#undef JSIM_X
-    return false;
+    static int cus[64];   // per device id, 0 = not asked yet
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
+    if (cus[dev] == 0) {
+        int n = 0;
+        cus[dev] = (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0) ? n : 256;
+    }
+    return cus[dev];
 }
-#endif
-static bool has_fused_glue(int T) { return has_reg_kernel(T); }
 
 static void launch_reg(int T, int B, hipStream_t s, const KP &P, const TickP &K, const PreK *Q = nullptr)
 {
     static const PreK none = {};
-    // more egos than SIMDs (256 CUs x 4): the T = 20 form built for two waves per SIMD (mpc_step_reg.inc, WPE)
-    static const int w2_min_b = [] { const char *e = getenv("JSIM_W2_MIN_B"); return e ? atoi(e) : 1025; }();
-    // at most one ego per CU: the form with three helper wavefronts per ego (mpc_step_reg.inc, HELP) -- it needs a CU to itself (four
-    // wavefronts of 270-350 registers), so the default threshold is the device's CU count (256 on an MI355X in SPX mode)
-    static const int help_env_b = [] { const char *e = getenv("JSIM_HELP_MAX_B"); return e ? atoi(e) : -1; }();
-    int help_max_b = help_env_b;
-    if (help_max_b < 0) {
-        static int cus[64];   // per device id, 0 = not asked yet
-        int dev = 0;
-        help_max_b = 256;
-        if (hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64) {
-            if (cus[dev] == 0) {
-                int n = 0;
-                cus[dev] = (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0) ? n : 256;
-            }
-            help_max_b = cus[dev];
-        }
+    static const int w2_min_b = reg_w2_min_b(getenv("JSIM_W2_MIN_B"));
+    static const char *const help_env = getenv("JSIM_HELP_MAX_B");
+    const RegVariant v = select_reg_variant(T, B, Q != nullptr, reg_help_max_b(help_env, device_cu_count()), w2_min_b);
+#define JSIM_X(w, t, p, e, h)                                                                                                    \
+    if (v == RegVariant{w, t, p, e, h}) {                                                                                        \
+        hipLaunchKernelGGL((JSIM_REG_KERNEL(w, t, p, e, h)), dim3(B), dim3(v.threads()), 0, s, P, K, Q ? *Q : none);             \
+        return;                                                                                                                  \
     }
-#if defined(JSIM_DEV_NO_REG) /* development builds of the planner / glue: no register kernel is instantiated */
-    (void)T; (void)B; (void)s; (void)P; (void)K; (void)Q; (void)none; (void)w2_min_b; (void)help_max_b;
-    return;
-#elif defined(JSIM_DEV_ONLY_T40) /* development builds: only the T = 40 kernel is instantiated (seconds instead of minutes to compile) */
-    if (T == 40) {
-        if (Q) hipLaunchKernelGGL((mpc_step_reg4_kernel<40, true>), dim3(B), dim3(256), 0, s, P, K, *Q);
-        else hipLaunchKernelGGL((mpc_step_reg4_kernel<40, false>), dim3(B), dim3(256), 0, s, P, K, none);
-    }
-    return;
-#elif defined(JSIM_DEV_ONLY_T30) /* development builds: only the T = 30 one-wave kernel */
-    if (T == 30) {
-        if (Q) hipLaunchKernelGGL((mpc_step_reg_kernel<30, true, 1>), dim3(B), dim3(64), 0, s, P, K, *Q);
-        else hipLaunchKernelGGL((mpc_step_reg_kernel<30, false, 1>), dim3(B), dim3(64), 0, s, P, K, none);
-    }
-    return;
-#elif defined(JSIM_DEV_ONLY_T20) /* development builds: only the T = 20 one-wave kernels */
-    if (T == 20) {
-        if (Q) hipLaunchKernelGGL((mpc_step_reg_kernel<20, true, 1>), dim3(B), dim3(64), 0, s, P, K, *Q);
-        else if (B <= help_max_b) hipLaunchKernelGGL((mpc_step_reg_kernel<20, false, 1, true>), dim3(B), dim3(256), 0, s, P, K, none);
-        else if (B >= w2_min_b) hipLaunchKernelGGL((mpc_step_reg_kernel<20, false, 2>), dim3(B), dim3(64), 0, s, P, K, none);
-        else hipLaunchKernelGGL((mpc_step_reg_kernel<20, false, 1>), dim3(B), dim3(64), 0, s, P, K, none);
-    }
-    return;
-#else
-    if (Q) { // the loop glue inside the launch
-        if (B <= help_max_b) { // (with helper wavefronts, like the plain closed loop below)
-#define JSIM_X(t) if (T == t) { hipLaunchKernelGGL((mpc_step_reg_kernel<t, true, 1, true>), dim3(B), dim3(256), 0, s, P, K, *Q); return; }
-            JSIM_HELP_PRE_HORIZONS(JSIM_X)
+    JSIM_REG_VARIANTS(JSIM_X)
 #undef JSIM_X
-        }
-#define JSIM_X(t) if (T == t) { hipLaunchKernelGGL((mpc_step_reg_kernel<t, true, 1>), dim3(B), dim3(64), 0, s, P, K, *Q); return; }
-        JSIM_ONE_WAVE_HORIZONS(JSIM_X)
-#undef JSIM_X
-#define JSIM_X(t) if (T == t) { hipLaunchKernelGGL((mpc_step_reg4_kernel<t, true>), dim3(B), dim3(256), 0, s, P, K, *Q); return; }
-        JSIM_FOUR_WAVE_HORIZONS(JSIM_X)
-#undef JSIM_X
-        return;
-    }
-    // register budgets (WPE): T = 13 fits 256 registers without scratch -- two waves per SIMD at every batch size; T = 20 has a
-    // 256-register form for batches above one ego per SIMD; every other horizon one wave per SIMD
-    // at most one ego per CU: three helper wavefronts per ego (mpc_step_reg.inc, HELP) -- every one-wave horizon
-    if (B <= help_max_b) {
-#define JSIM_X(t) if (T == t) { hipLaunchKernelGGL((mpc_step_reg_kernel<t, false, 1, true>), dim3(B), dim3(256), 0, s, P, K, none); return; }
-        JSIM_HELP_HORIZONS(JSIM_X)
-#undef JSIM_X
-    }
-    if (T == 13) { hipLaunchKernelGGL((mpc_step_reg_kernel<13, false, 2>), dim3(B), dim3(64), 0, s, P, K, none); return; }
-    if (T == 20 && B >= w2_min_b) { hipLaunchKernelGGL((mpc_step_reg_kernel<20, false, 2>), dim3(B), dim3(64), 0, s, P, K, none); return; }
-#define JSIM_X(t) if (T == t && t != 13) { hipLaunchKernelGGL((mpc_step_reg_kernel<t, false, (t == 13 ? 2 : 1)>), dim3(B), dim3(64), 0, s, P, K, none); return; }
-    JSIM_ONE_WAVE_HORIZONS(JSIM_X)
-#undef JSIM_X
-#define JSIM_X(t) if (T == t) { hipLaunchKernelGGL((mpc_step_reg4_kernel<t, false>), dim3(B), dim3(256), 0, s, P, K, none); return; }
-    JSIM_FOUR_WAVE_HORIZONS(JSIM_X)
-#undef JSIM_X
-#endif
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -2291,7 +2187,7 @@ extern "C" int jsim_loop_run_scenario(jsim_ctx *ctx, int32_t B, int32_t n_ticks,
     if (speed_cutoff && !ctx->cv_cut)
         return fail(ctx, -22, "jsim_loop_run_scenario: the speed-cut-off glue needs jsim_mpc_set_speed_cutoff first");
     int32_t *const glue_out = speed_cutoff ? const_cast<int32_t *>(ctx->cv_cut) : path_len; // where the cut-off index goes
-    if (!ctx->use_reg_kernel || !has_fused_glue(c.T) || c.max_iter > 1 || (ctx->cv_cut && !speed_cutoff)) {
+    if (!ctx->use_reg_kernel || !has_reg_kernel(c.T) || c.max_iter > 1 || (ctx->cv_cut && !speed_cutoff)) {
         // tick by tick, as ScenarioLoop.tick does
         for (int k = 0; k < n_ticks; ++k) {
             int rc = jsim_loop_obstacles(ctx, n_obs, obs_state, obs_param, obs_get, 0, stream);

@@ -5,15 +5,18 @@ Bars: path indices / target_ind / reaches_end / status bit-exact; rollout and re
 condensed (H, g) <= 1e-9 relative; control sequence u* <= 1e-4 abs (north_star; observed ~1e-9);
 active-constraint indices identical.
 """
+import importlib
+
 import numpy as np
 import pytest
 import torch
 
-from conftest import load_golden
+from conftest import PKG_NAME, load_golden
 from gpu_helpers import kkt_check
 
 pytestmark = pytest.mark.gpu
 TS = (13, 20, 30, 40)
+CFG = importlib.import_module(PKG_NAME + ".config")
 U_TOL = 1e-4  # north_star tolerance on u*
 
 
@@ -61,7 +64,7 @@ def test_stages_vs_reference_golden(pkg, routes, T):
     assert feas.sum() > 60
 
 
-@pytest.mark.parametrize("T", TS + (15, 16, 25, 32))     # every horizon with a register kernel (config.ONE_WAVE / FOUR_WAVE_HORIZONS)
+@pytest.mark.parametrize("T", CFG.ONE_WAVE_HORIZONS + CFG.FOUR_WAVE_HORIZONS)     # every horizon with a register kernel
 def test_step_vs_oracle(pkg, oracle, routes, T):
     B = 192 if T <= 20 else 96
     batch = pkg.synth.make_ego_batch(routes, B, T, seed=0, truncate=True, near_end_frac=0.2)
@@ -273,7 +276,7 @@ def test_fused_ticks_equal_single_ticks(pkg, routes, T):
     assert int(l1.n_respawn.item()) == int(l2.n_respawn.item()) > 0
 
 
-@pytest.mark.parametrize("T", (13, 20, 15, 16, 25))     # config.HELP_HORIZONS
+@pytest.mark.parametrize("T", CFG.HELP_HORIZONS)
 def test_helper_wavefronts_change_nothing(pkg, routes, T):
     """Up to 256 egos run on the kernel with three helper wavefronts per ego (mpc_step_reg_kernel<T, false, 1, true>: the scan of S1,
     tile rows of H, g and J = L^-T are done by the helpers), larger batches on the one-wave kernel.  Same operations in the same

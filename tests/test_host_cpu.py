@@ -304,7 +304,7 @@ def test_plan_routes_argument_errors_without_gpu(pkg):
     assert call(cc_off_=bad) == -22 and b"cc_off" in lib.jsim_last_error(None)
 
 
-def test_bench_line_helpers():
+def test_bench_pure_helpers():
     """bench.py's pure pieces: the kernel launch_reg dispatches per (T, scenario, B), the straggler
     statistic from per-ego iteration totals, the flop / byte formulas of SURVEY 8d, the newest committed PMC summary."""
     import importlib.util
@@ -322,20 +322,6 @@ def test_bench_line_helpers():
     assert bench.kernel_name(24, False, 8) == "mpc_step_kernel" and bench.kernel_name(48, False, 8) == "mpc_step_kernel"
     assert bench.waves_per_ego(bench.kernel_name(20, False, 256)) == "1 + 3 helper" and bench.waves_per_ego(bench.kernel_name(20, True, 256)) == "1 + 3 helper" and bench.waves_per_ego(bench.kernel_name(20, True, 4096)) == 1
     assert bench.waves_per_ego(bench.kernel_name(40, False, 8)) == 4 and bench.waves_per_ego(bench.kernel_name(20, False, 4096)) == 1
-    src = open(os.path.join(REPO, "av-simulation-at-intersections_amd", "csrc", "jsim_mpc.hip")).read()
-    assert "return e ? atoi(e) : 1025;" in src and "hipDeviceAttributeMultiprocessorCount" in src   # the dispatch thresholds kernel_name() mirrors (256 CUs)
-    # the horizon lists kernel_name() reads are the library's own
-    import re
-    cfg = importlib.import_module("av-simulation-at-intersections_amd.config")
-    for macro, lst in (("JSIM_ONE_WAVE_HORIZONS", cfg.ONE_WAVE_HORIZONS), ("JSIM_FOUR_WAVE_HORIZONS", cfg.FOUR_WAVE_HORIZONS), ("JSIM_HELP_HORIZONS", cfg.HELP_HORIZONS), ("JSIM_HELP_PRE_HORIZONS", cfg.HELP_PRE_HORIZONS)):
-        line = re.search(r"#define %s\(X\)(.*)" % macro, src).group(1)
-        assert tuple(int(t) for t in re.findall(r"X\((\d+)\)", line)) == tuple(lst), macro
-    # the split build's per-horizon units: the `#if JSIM_KERNEL_TU == ..` lists and build.py's unit list repeat the same horizons
-    for tag, lst in (("four-wave horizons", cfg.FOUR_WAVE_HORIZONS), ("one-wave horizons", cfg.ONE_WAVE_HORIZONS), ("helper-wavefront horizons */", cfg.HELP_HORIZONS), ("helper-wavefront horizons with the glue", cfg.HELP_PRE_HORIZONS)):
-        line = [ln for ln in src.splitlines() if ln.startswith(("#if JSIM_KERNEL_TU ==", "#elif JSIM_KERNEL_TU ==")) and tag in ln]
-        assert len(line) == 1 and tuple(int(t) for t in re.findall(r"JSIM_KERNEL_TU == (\d+)", line[0])) == tuple(lst), tag
-    build_mod = importlib.import_module("av-simulation-at-intersections_amd.build")
-    assert tuple(build_mod.KERNEL_TUS) == tuple(sorted(cfg.ONE_WAVE_HORIZONS + cfg.FOUR_WAVE_HORIZONS))
     mean, s = bench.straggler_stats(np.array([100, 100, 100, 700], dtype=np.uint64), 10)
     assert mean == 25.0 and s == {"max_ego_iters_per_tick": 70.0, "slowest_over_mean": 2.8, "egos_above_3x_mean": 0}
     mean, s = bench.straggler_stats(np.array([10] * 99 + [1000], dtype=np.uint64), 10)
@@ -349,6 +335,60 @@ def test_bench_line_helpers():
     assert bench.latest_pmc_summary(2, 100) == pm and bench.latest_pmc_summary(2, 37) == pm
     d = json.load(open(pm))
     assert "FETCH_SIZE" in d and "WRITE_SIZE" in d and d.get("commit", "?") != "?"
+
+
+REG_DRIVER = r"""
+#include <cstdio>
+#include <initializer_list>
+#include "reg_variants.h"
+int main()
+{
+#define X(w, t, p, e, h) std::printf("row %d %d %d %d %d\n", w, t, (int)p, e, (int)h);
+    JSIM_REG_VARIANTS(X)
+    for (int T = 1; T <= 48; ++T)
+        for (int B : {1, 8, 255, 256, 257, 1024, 1025, 4096})
+            for (bool pre : {false, true}) {
+                const RegVariant v = select_reg_variant(T, B, pre, 256, 1025);
+                std::printf("select %d %d %d %d %d %d %d %d\n", T, B, (int)pre, v.W, v.T, (int)v.PRE, v.WPE, (int)v.HELP);
+            }
+    std::printf("defaults %d %d %d %d\n", reg_w2_min_b(nullptr), reg_help_max_b(nullptr, 256), reg_help_max_b("-1", 80), reg_help_max_b("0", 80));
+}
+"""
+
+
+def test_reg_variant_table_and_dispatch(tmp_path):
+    """csrc/reg_variants.h compiled for the host: its table is config.REG_VARIANTS, every (T, B, PRE) launch_reg can see takes the
+    kernel bench.kernel_name() names (at its 256 CUs and the default thresholds), and the split build has one unit per horizon."""
+    import importlib.util
+    import shutil
+    spec = importlib.util.spec_from_file_location("bench_mod4", os.path.join(REPO, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    cfg = importlib.import_module("av-simulation-at-intersections_amd.config")
+    build_mod = importlib.import_module("av-simulation-at-intersections_amd.build")
+    csrc = os.path.join(REPO, "av-simulation-at-intersections_amd", "csrc")
+    cxx = next(c for c in (shutil.which("c++"), "/opt/rocm/llvm/bin/clang++") if c and os.path.exists(c))
+    (tmp_path / "driver.cpp").write_text(REG_DRIVER)
+    exe = str(tmp_path / "driver")
+    subprocess.run([cxx, "-std=c++17", "-Wall", "-Werror", "-I", csrc, str(tmp_path / "driver.cpp"), "-o", exe], check=True)
+    out = [ln.split() for ln in subprocess.run([exe], check=True, capture_output=True, text=True).stdout.splitlines()]
+    rows = tuple((int(w), int(t), bool(int(p)), int(e), bool(int(h))) for tag, w, t, p, e, h in (ln for ln in out if ln[0] == "row"))
+    assert rows == cfg.REG_VARIANTS and len(rows) == 24
+    assert build_mod.KERNEL_TUS == tuple(sorted({t for _, t, _, _, _ in rows})) == tuple(sorted(cfg.ONE_WAVE_HORIZONS + cfg.FOUR_WAVE_HORIZONS))
+
+    def name(w, t, pre, wpe, help_):
+        p = "true" if pre else "false"
+        return ("mpc_step_kernel" if w == 0 else f"mpc_step_reg4_kernel<{t}, {p}>" if w == 4 else
+                f"mpc_step_reg_kernel<{t}, {p}, {wpe}" + (", true>" if help_ else ">"))
+    sel = [ln[1:] for ln in out if ln[0] == "select"]
+    assert len(sel) == 48 * 8 * 2
+    for T, B, pre, w, t, p, e, h in ((int(x) for x in ln) for ln in sel):
+        assert w == 0 or (t == T and p == pre)
+        assert name(w, T, pre, e, h) == bench.kernel_name(T, bool(pre), B), (T, B, pre)
+    # the thresholds' defaults, which kernel_name() assumes: JSIM_W2_MIN_B 1025, JSIM_HELP_MAX_B the CU count (unset or negative)
+    assert [ln[1:] for ln in out if ln[0] == "defaults"] == [["1025", "256", "80", "0"]]
+    src = open(os.path.join(csrc, "jsim_mpc.hip")).read()
+    assert "hipDeviceAttributeMultiprocessorCount" in src and 'reg_help_max_b(help_env, device_cu_count())' in src
 
 
 def test_bench_dump_outputs_writes_float64_and_a_seeded_sample_beyond_the_cap(tmp_path):

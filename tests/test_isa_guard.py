@@ -1,20 +1,18 @@
-"""The build-time ISA guard (tools/isa_exec_check.py, wired into build.py): the pattern that made round 2's T = 30 build
+"""The build-time ISA guard (the package's isa_exec_check.py, wired into build.py): the pattern that made round 2's T = 30 build
 attribute multipliers to the wrong rows -- a vector copy in a JOIN block in front of that block's exec restore -- is found in a
 minimal reproduction of the failing listing, legitimate shapes (a then-block whose tail holds the merged restore, an
 out-of-line then-block, a divergent loop's exit) are not flagged, and the library build() produced has no finding."""
-import importlib.util
+import importlib
 import os
+import re
 
 import pytest
 
-from conftest import REPO
+from conftest import PKG_NAME
 
 
 def _tool():
-    spec = importlib.util.spec_from_file_location("isa_exec_check", os.path.join(REPO, "tools", "isa_exec_check.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
+    return importlib.import_module(PKG_NAME + ".isa_exec_check")
 
 
 BAD = """
@@ -128,15 +126,11 @@ def test_shipped_library_has_no_finding(pkg):
         pytest.skip("no device listing (library not built in this tree: build() writes it)")
     T = _tool()
     assert T.check(asm) == []
-    names = set(T.kernels(asm))
-    for k in ("_Z19mpc_step_reg_kernelILi13ELb0ELi2ELb0EEv2KP5TickP4PreK", "_Z19mpc_step_reg_kernelILi20ELb0ELi1ELb0EEv2KP5TickP4PreK",
-              "_Z19mpc_step_reg_kernelILi20ELb0ELi1ELb1EEv2KP5TickP4PreK", "_Z19mpc_step_reg_kernelILi13ELb0ELi1ELb1EEv2KP5TickP4PreK",
-              "_Z19mpc_step_reg_kernelILi25ELb0ELi1ELb1EEv2KP5TickP4PreK", "_Z19mpc_step_reg_kernelILi13ELb1ELi1ELb1EEv2KP5TickP4PreK",
-              "_Z19mpc_step_reg_kernelILi20ELb1ELi1ELb1EEv2KP5TickP4PreK",      # (three helper wavefronts per ego, B <= 256)
-              "_Z19mpc_step_reg_kernelILi20ELb0ELi2ELb0EEv2KP5TickP4PreK", "_Z19mpc_step_reg_kernelILi30ELb1ELi1ELb0EEv2KP5TickP4PreK",
-              "_Z19mpc_step_reg_kernelILi25ELb0ELi1ELb0EEv2KP5TickP4PreK", "_Z20mpc_step_reg4_kernelILi32ELb1EEv2KP5TickP4PreK",
-              "_Z20mpc_step_reg4_kernelILi40ELb0EEv2KP5TickP4PreK"):
-        assert k in names, k                      # the listing really is the library's: every dispatched kernel is in it
+    # the listing really is the library's: its register kernels are exactly the rows of csrc/reg_variants.h (config.REG_VARIANTS)
+    want = {f"_Z20mpc_step_reg4_kernelILi{t}ELb{int(p)}EEv2KP5TickP4PreK" if w == 4 else
+            f"_Z19mpc_step_reg_kernelILi{t}ELb{int(p)}ELi{e}ELb{int(h)}EEv2KP5TickP4PreK" for w, t, p, e, h in pkg.config.REG_VARIANTS}
+    assert len(want) == 24
+    assert {k for k in T.kernels(asm) if re.match(r"_Z\d+mpc_step_reg4?_kernel", k)} == want
     # and the guard refuses to install: a listing with the pattern raises
     bad = os.path.join(os.path.dirname(asm), "_guard_selftest.s")
     open(bad, "w").write(BAD)
