@@ -35,6 +35,7 @@ EXPORTS = (
     "jsim_loop_set_geometry", "jsim_loop_set_obstacle_geometry", "jsim_loop_predict_obstacles", "jsim_loop_pre_tick",
     "jsim_mpc_set_path_speed", "jsim_mpc_set_speed_cutoff", "jsim_mpc_update_cfg", "jsim_mpc_set_ego_config", "jsim_loop_obstacles",
     "jsim_mpc_xref_deviation_goal", "jsim_loop_run_scenario",
+    "jsim_loop_set_groups", "jsim_loop_predict_egos", "jsim_loop_run_interacting",
     "jsim_comm_unique_id", "jsim_comm_init", "jsim_mpc_gather", "jsim_comm_destroy", "jsim_plan_routes",
 )
 
@@ -105,6 +106,12 @@ def load() -> C.CDLL:
     lib.jsim_loop_run_scenario.argtypes = ([vp, i32, i32] + [vp] * 19 + [i32, vp, vp, i32, vp] +
                                            # traj_idx prev_len col_flag pre_status  window margin n_obs state param get  n_steps speed_cutoff stream
                                            [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, i32, i32, vp])
+    lib.jsim_loop_set_groups.restype = C.c_int
+    lib.jsim_loop_set_groups.argtypes = [vp, i32, i32, vp]
+    lib.jsim_loop_predict_egos.restype = C.c_int
+    lib.jsim_loop_predict_egos.argtypes = [vp, i32, vp, vp, i32, vp, vp]
+    lib.jsim_loop_run_interacting.restype = C.c_int
+    lib.jsim_loop_run_interacting.argtypes = lib.jsim_loop_run_scenario.argtypes
     lib.jsim_mpc_xref_deviation_goal.restype = C.c_int
     lib.jsim_mpc_xref_deviation_goal.argtypes = [vp, i32] + [vp] * 9
     lib.jsim_comm_unique_id.restype = C.c_int

@@ -256,3 +256,77 @@ class ScenarioLoop:
             1 if pre.mode == "speed_cutoff" else 0, eng._stream()), eng._ctx,
             "jsim_loop_run_scenario")
         pre.n_obs = ob.n
+
+
+MAX_GROUP = 8          # JSIM_MAX_OBS: the obstacles of an ego are the scripted ones plus its group mates
+
+
+def group_offsets(B: int, group_off=None, group_sizes=None) -> np.ndarray:
+    """The group layout of InteractingLoop as offsets [n_groups + 1] (int32): group_off itself, or the running sum of
+    group_sizes.  Raises ValueError unless exactly one is given, the groups cover 0..B contiguously and each has 1..8 egos."""
+    if (group_off is None) == (group_sizes is None):
+        raise ValueError("pass exactly one of group_off and group_sizes")
+    if group_sizes is not None:
+        sizes = np.asarray(group_sizes).reshape(-1)
+        if sizes.size == 0 or not np.issubdtype(sizes.dtype, np.integer):
+            raise ValueError("group_sizes must be a non-empty sequence of integers")
+        off = np.concatenate([[0], np.cumsum(sizes)])
+    else:
+        off = np.asarray(group_off).reshape(-1)
+        if off.size < 2 or not np.issubdtype(off.dtype, np.integer):
+            raise ValueError("group_off must hold n_groups + 1 >= 2 integers")
+    sizes = np.diff(off)
+    if off[0] != 0 or off[-1] != B:
+        raise ValueError(f"the groups must cover egos 0..{B}: offsets run {off[0]}..{off[-1]}")
+    if sizes.min() < 1 or sizes.max() > MAX_GROUP:
+        raise ValueError(f"every group needs 1..{MAX_GROUP} egos (sizes {sizes.min()}..{sizes.max()})")
+    return off.astype(np.int32)
+
+
+class InteractingLoop:
+    """Several automated vehicles at one intersection that react to each other (main/scenarios/interactive_mpc.py:117-190):
+    ScenarioLoop's tick, where the obstacles of an ego are the scripted vehicles (spec order) and then the OTHER egos of its
+    group (ascending batch index), every ego predicted like an obstacle from its tick-start state with a = 0 and the steering
+    it applied last tick.  A tick is a Jacobi step: all egos solve, then all advance.  Groups are contiguous batch ranges
+    (group_off [n_groups + 1], or group_sizes), 1..8 egos each; n_obs + largest group - 1 <= 8.  Egos in different groups
+    never affect each other; a group of one ego is ScenarioLoop.  Only the truncate glue, only obstacles of the ego's shape."""
+
+    def __init__(self, engine: BatchedMPC, x0: torch.Tensor, group_off=None, obstacle_specs=(), hist_cap: int = 0,
+                 max_age: int = 0, frame_window: int = 20, group_sizes=None):
+        off = group_offsets(engine.B, group_off, group_sizes)        # before any device work
+        n_obs = len(obstacle_specs)
+        if n_obs + int(np.diff(off).max()) - 1 > MAX_GROUP:
+            raise ValueError(f"{n_obs} scripted obstacles + the largest group ({int(np.diff(off).max())}) - 1 > {MAX_GROUP}")
+        self.group_off = off
+        self.loop = ClosedLoop(engine, x0, hist_cap=hist_cap, max_age=max_age)
+        self.pre = PreTick(engine, frame_window=frame_window)
+        self.obst = ScriptedObstacles(engine, list(obstacle_specs))
+        eng = engine
+        _cabi.check(eng.lib.jsim_loop_set_groups(eng._ctx, eng.B, len(off) - 1, off.ctypes.data_as(C.c_void_p)), eng._ctx,
+                    "jsim_loop_set_groups")
+
+    def pred_egos(self) -> torch.Tensor:
+        """[B, n_steps, 3] (x, y, yaw): every ego's prediction from its current state, as the next tick will make it."""
+        eng = self.loop.eng
+        pred = torch.zeros(eng.B, self.pre.n_steps, 3, dtype=torch.float64, device=eng.device)
+        _cabi.check(eng.lib.jsim_loop_predict_egos(eng._ctx, eng.B, _ptr(self.loop.x0), _ptr(eng.di_ai), self.pre.n_steps,
+                                                   _ptr(pred), eng._stream()), eng._ctx, "jsim_loop_predict_egos")
+        return pred
+
+    def tick(self):
+        self.run(1)
+
+    def run(self, n_ticks: int):
+        """n_ticks ticks in one call (jsim_loop_run_interacting; separate launches per tick)."""
+        loop, pre, ob, eng = self.loop, self.pre, self.obst, self.loop.eng
+        eng._check_x0(loop.x0)
+        _cabi.check(eng.lib.jsim_loop_run_interacting(
+            eng._ctx, eng.B, int(n_ticks), _ptr(loop.x0), _ptr(eng.path_id), _ptr(eng.path_len), _ptr(eng.speed),
+            _ptr(eng.target_ind), _ptr(eng.oa), _ptr(eng.od), _ptr(eng.ox), _ptr(eng.oy), _ptr(eng.ov), _ptr(eng.oyaw),
+            _ptr(eng.xref), _ptr(eng.active_mask), _ptr(eng.status), _ptr(eng.n_iter), _ptr(eng.di_ai),
+            _ptr(loop.x0_spawn), _ptr(loop.target_spawn), _ptr(loop.age), loop.max_age, _ptr(loop.hist),
+            _ptr(loop.tick_counter), loop.hist_cap, _ptr(loop.n_respawn), _ptr(pre.traj_idx), _ptr(pre.prev_len),
+            _ptr(pre.col_flag), _ptr(pre.status), pre.frame_window, pre.margin, ob.n, _ptr(ob.state) if ob.n else None,
+            _ptr(ob.param) if ob.n else None, _ptr(ob.get_buf) if ob.n else None, pre.n_steps, 0, eng._stream()), eng._ctx,
+            "jsim_loop_run_interacting")
+        pre.n_obs = ob.n

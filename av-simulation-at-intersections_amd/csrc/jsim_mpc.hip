@@ -1283,6 +1283,12 @@ struct jsim_ctx {
     double2 *d_pcc;
     double2 *d_pred_cc;
     int pred_n_obs, pred_n_steps;
+    // interacting egos (jsim_loop_set_groups, jsim_loop_run_interacting): groups and the egos' own predictions
+    int *d_group_of, *d_group_off; // [group_B], [n_groups + 1]
+    int group_B, n_groups, group_max;
+    double2 *d_ego_cc;             // [B][n_steps][2] ..
+    double4 *d_ego_bc;             // .. [B], sized on first use (ego_pred_cap elements of d_ego_cc)
+    size_t ego_pred_cap, ego_bc_cap;
     double *d_pcv;          // speed reference per path point (mpc_with_speed variant) or NULL
     const int *cv_cut;      // caller-owned device array [B] or NULL
     size_t lds_bytes;
@@ -1418,6 +1424,10 @@ extern "C" void jsim_mpc_destroy(jsim_ctx *ctx)
     if (ctx->d_pred_all) (void)hipFree(ctx->d_pred_all);
     if (ctx->d_bc_all) (void)hipFree(ctx->d_bc_all);
     if (ctx->d_pred_bc) (void)hipFree(ctx->d_pred_bc);
+    if (ctx->d_group_of) (void)hipFree(ctx->d_group_of);
+    if (ctx->d_group_off) (void)hipFree(ctx->d_group_off);
+    if (ctx->d_ego_cc) (void)hipFree(ctx->d_ego_cc);
+    if (ctx->d_ego_bc) (void)hipFree(ctx->d_ego_bc);
     if (ctx->d_order) (void)hipFree(ctx->d_order);
     if (ctx->d_work) (void)hipFree(ctx->d_work);
     if (ctx->d_iters) (void)hipFree(ctx->d_iters);
@@ -2267,6 +2277,158 @@ extern "C" int jsim_loop_run_scenario(jsim_ctx *ctx, int32_t B, int32_t n_ticks,
     if (int rc_ = prepare_iter_totals(ctx, B, s, K)) return rc_;
     launch_reg(c.T, B, s, P, K, &Q);
     if (tick) hipLaunchKernelGGL(tick_add_kernel, dim3(1), dim3(1), 0, s, tick, n_ticks);
+    HIP_TRY(ctx, hipGetLastError());
+    return 0;
+}
+
+// ---- Interacting egos: the obstacles of an ego are the scripted vehicles and the other egos of its group ----
+extern "C" int jsim_loop_set_groups(jsim_ctx *ctx, int32_t B, int32_t n_groups, const int32_t *group_off)
+{
+    if (!ctx) return fail(nullptr, -22, "jsim_loop_set_groups: null ctx");
+    DeviceGuard dev_guard(ctx->device);
+    JSIM_GUARD_OK(ctx);
+    if (n_groups < 0 || B < 0) return fail(ctx, -22, "jsim_loop_set_groups: B=%d n_groups=%d", B, n_groups);
+    if (n_groups > 0) {
+        if (!group_off) return fail(ctx, -22, "jsim_loop_set_groups: null group_off");
+        if (group_off[0] != 0 || group_off[n_groups] != B)
+            return fail(ctx, -22, "jsim_loop_set_groups: group_off must run from 0 to B=%d (got %d .. %d)", B, group_off[0],
+                        group_off[n_groups]);
+        for (int g = 0; g < n_groups; ++g) {
+            const int n = group_off[g + 1] - group_off[g];
+            if (n < 1 || n > JSIM_MAX_OBS)
+                return fail(ctx, -22, "jsim_loop_set_groups: group %d has %d egos (1..%d)", g, n, JSIM_MAX_OBS);
+        }
+    }
+    if (ctx->d_group_of) (void)hipFree(ctx->d_group_of);
+    if (ctx->d_group_off) (void)hipFree(ctx->d_group_off);
+    ctx->d_group_of = nullptr; ctx->d_group_off = nullptr;
+    ctx->group_B = 0; ctx->n_groups = 0; ctx->group_max = 0;
+    if (n_groups == 0) return 0;
+    std::vector<int> of((size_t)B);
+    int gmax = 0;
+    for (int g = 0; g < n_groups; ++g) {
+        for (int b = group_off[g]; b < group_off[g + 1]; ++b) of[b] = g;
+        gmax = std::max(gmax, group_off[g + 1] - group_off[g]);
+    }
+    HIP_TRY(ctx, hipMalloc(&ctx->d_group_of, sizeof(int) * B));
+    HIP_TRY(ctx, hipMalloc(&ctx->d_group_off, sizeof(int) * (n_groups + 1)));
+    HIP_TRY(ctx, hipMemcpy(ctx->d_group_of, of.data(), sizeof(int) * B, hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemcpy(ctx->d_group_off, group_off, sizeof(int) * (n_groups + 1), hipMemcpyHostToDevice));
+    ctx->group_B = B; ctx->n_groups = n_groups; ctx->group_max = gmax;
+    return 0;
+}
+
+// the egos' predictions (circle centres, bounding circles), sized on first use like d_pred_all
+static int ensure_ego_pred(jsim_ctx *ctx, int B, int n_steps)
+{
+    const size_t need = (size_t)B * n_steps * 2;
+    if (need > ctx->ego_pred_cap) {
+        if (ctx->d_ego_cc) (void)hipFree(ctx->d_ego_cc);
+        ctx->d_ego_cc = nullptr; ctx->ego_pred_cap = 0;
+        HIP_TRY(ctx, hipMalloc(&ctx->d_ego_cc, sizeof(double2) * need));
+        ctx->ego_pred_cap = need;
+    }
+    if ((size_t)B > ctx->ego_bc_cap) {
+        if (ctx->d_ego_bc) (void)hipFree(ctx->d_ego_bc);
+        ctx->d_ego_bc = nullptr; ctx->ego_bc_cap = 0;
+        HIP_TRY(ctx, hipMalloc(&ctx->d_ego_bc, sizeof(double4) * B));
+        ctx->ego_bc_cap = B;
+    }
+    return 0;
+}
+
+static void launch_ego_predict(jsim_ctx *ctx, int B, const double *x0, const double *di_ai, int n_steps, double *pred, hipStream_t s)
+{
+    EgoPredP P = {B, n_steps, ctx->cfg.dt, ctx->cfg.L, ctx->cc0, ctx->cc1, x0, di_ai, pred, ctx->d_ego_cc, ctx->d_ego_bc};
+    hipLaunchKernelGGL(ego_predict_kernel, dim3((B + 63) / 64), dim3(64), 0, s, P);   // one wave per block: spread over the CUs
+}
+
+extern "C" int jsim_loop_predict_egos(jsim_ctx *ctx, int32_t B, const double *x0, const double *di_ai, int32_t n_steps,
+                                      double *pred, void *stream)
+{
+    if (!ctx) return fail(nullptr, -22, "jsim_loop_predict_egos: null ctx");
+    DeviceGuard dev_guard(ctx->device);
+    JSIM_GUARD_OK(ctx);
+    if (!ctx->have_geom) return fail(ctx, -22, "jsim_loop_predict_egos: jsim_loop_set_geometry has not been called");
+    if (B < 0 || n_steps < 1 || n_steps > JSIM_MAX_PRED)
+        return fail(ctx, -22, "jsim_loop_predict_egos: B=%d, n_steps=%d (max %d)", B, n_steps, JSIM_MAX_PRED);
+    if (B == 0) return 0;
+    if (!x0 || !di_ai) return fail(ctx, -22, "jsim_loop_predict_egos: null device pointer");
+    if (int rc = ensure_ego_pred(ctx, B, n_steps)) return rc;
+    launch_ego_predict(ctx, B, x0, di_ai, n_steps, pred, (hipStream_t)stream);
+    HIP_TRY(ctx, hipGetLastError());
+    return 0;
+}
+
+// n_ticks Jacobi ticks of interacting egos (main/scenarios/interactive_mpc.py:117-190), each as separate launches: scripted
+// obstacles get() -> their prediction -> every ego's prediction from the tick-start states -> glue per ego against the scripted
+// obstacles, then its group mates -> MPC.step -> plant, history, goal / respawn -> glue reset of respawned egos -> obstacles
+// step().  Arguments as jsim_loop_run_scenario; groups from jsim_loop_set_groups.
+extern "C" int jsim_loop_run_interacting(jsim_ctx *ctx, int32_t B, int32_t n_ticks, double *x0, const int32_t *path_id,
+                                         int32_t *path_len, const double *speed, int64_t *target_ind, double *oa, double *od,
+                                         double *ox, double *oy, double *ov, double *oyaw, double *xref, uint32_t *active_mask,
+                                         int32_t *status, int32_t *n_iter, double *di_ai, const double *x0_spawn,
+                                         const int64_t *target_spawn, int32_t *age, int32_t max_age, double *hist, int32_t *tick,
+                                         int32_t hist_cap, uint64_t *n_respawn, int64_t *traj_idx, int32_t *prev_path_len,
+                                         int32_t *col_flag, int32_t *pre_status, int32_t frame_window, int32_t margin,
+                                         int32_t n_obs, double *obs_state, const double *obs_param, double *obs_get,
+                                         int32_t n_steps, int32_t speed_cutoff, void *stream)
+{
+    if (!ctx) return fail(nullptr, -22, "jsim_loop_run_interacting: null ctx");
+    DeviceGuard dev_guard(ctx->device);
+    JSIM_GUARD_OK(ctx);
+    if (B < 0 || n_ticks < 0 || frame_window < 0 || frame_window > 32 || margin < 0)
+        return fail(ctx, -22, "jsim_loop_run_interacting: bad argument");
+    if (speed_cutoff) return fail(ctx, -22, "jsim_loop_run_interacting: only the truncate glue is supported (speed_cutoff = 1)");
+    if (ctx->have_ogeom)
+        return fail(ctx, -22, "jsim_loop_run_interacting: egos cannot be mixed with obstacles of another shape "
+                              "(jsim_loop_set_obstacle_geometry has been called)");
+    if (ctx->n_groups == 0 || ctx->group_B != B)
+        return fail(ctx, -22, "jsim_loop_run_interacting: no groups set for B=%d (jsim_loop_set_groups)", B);
+    if (n_obs < 0 || n_steps < 1 || n_steps > JSIM_MAX_PRED || n_obs + ctx->group_max - 1 > JSIM_MAX_OBS)
+        return fail(ctx, -22, "jsim_loop_run_interacting: n_obs=%d + largest group %d - 1 > %d, or n_steps=%d (max %d)", n_obs,
+                    ctx->group_max, JSIM_MAX_OBS, n_steps, JSIM_MAX_PRED);
+    if (B == 0 || n_ticks == 0) return 0;
+    if (!x0 || !path_id || !path_len || !speed || !target_ind || !oa || !od || !status || !di_ai || !x0_spawn || !target_spawn ||
+        !age || !traj_idx || !prev_path_len || !col_flag || !pre_status)
+        return fail(ctx, -22, "jsim_loop_run_interacting: a required device pointer is null");
+    if (n_obs > 0 && (!obs_state || !obs_param || !obs_get)) return fail(ctx, -22, "jsim_loop_run_interacting: null obstacle pointer");
+    if (hist && !tick) return fail(ctx, -22, "jsim_loop_run_interacting: hist needs a device tick counter");
+    if (!ctx->d_pxy || !ctx->d_pcc || !ctx->have_geom) return fail(ctx, -22, "jsim_loop_run_interacting: paths / geometry not set");
+    if (int rc = ensure_ego_pred(ctx, B, n_steps)) return rc;
+    const jsim_cfg &c = ctx->cfg;
+    hipStream_t s = (hipStream_t)stream;
+    PreP P;
+    memset(&P, 0, sizeof(P));
+    P.B = B; P.n_obs = n_obs; P.n_steps = n_steps; P.frame_window = frame_window; P.margin = margin;
+    P.dt = c.dt; P.max_accel = c.max_accel; P.max_speed = c.max_speed; P.thr = ctx->col_radius + ctx->ocol_radius;
+    P.thr_sq = jsim_sqrt_threshold(P.thr);
+    P.pxy = ctx->d_pxy; P.pcc = ctx->d_pcc; P.poff = ctx->d_poff; P.pred_cc = ctx->d_pred_cc; P.pred_bc = ctx->d_pred_bc;
+    P.x0 = x0; P.path_id = path_id; P.traj_idx = (long long *)traj_idx; P.prev_path_len = prev_path_len; P.path_len = path_len;
+    P.col_flag = col_flag; P.status = pre_status;
+    const GroupP G = {ctx->d_group_of, ctx->d_group_off, ctx->d_ego_cc, ctx->d_ego_bc, n_obs};
+    for (int k = 0; k < n_ticks; ++k) {
+        int rc = jsim_loop_obstacles(ctx, n_obs, obs_state, obs_param, obs_get, 0, stream);
+        if (rc) return rc;
+        ctx->pred_n_obs = n_obs; ctx->pred_n_steps = n_steps;
+        if (n_obs > 0) {
+            ObsP OP = {n_obs, n_steps, c.dt, ctx->oL, ctx->occ0, ctx->occ1, obs_get, nullptr, ctx->d_pred_cc, ctx->d_pred_bc};
+            hipLaunchKernelGGL(obstacle_predict_kernel, dim3(1), dim3(64), 0, s, OP);
+        }
+        launch_ego_predict(ctx, B, x0, di_ai, n_steps, nullptr, s);
+        hipLaunchKernelGGL(group_pre_tick_kernel, dim3(B), dim3(64), 0, s, P, G);
+        HIP_TRY(ctx, hipGetLastError());
+        HIP_TRY(ctx, hipMemcpyAsync(prev_path_len, path_len, sizeof(int32_t) * B, hipMemcpyDeviceToDevice, s));
+        rc = launch_step(ctx, B, x0, path_id, path_len, speed, target_ind, oa, od, ox, oy, ov, oyaw, xref, active_mask, status,
+                         n_iter, nullptr, nullptr, nullptr, nullptr, nullptr, stream);
+        if (rc) return rc;
+        rc = jsim_loop_advance(ctx, B, x0, oa, od, status, di_ai, target_ind, path_id, path_len, x0_spawn, target_spawn, age,
+                               max_age, hist, tick, hist_cap, n_respawn, stream);
+        if (rc) return rc;
+        hipLaunchKernelGGL(glue_reset_kernel, dim3((B + 255) / 256), dim3(256), 0, s, B, age, (long long *)traj_idx, prev_path_len);
+        rc = jsim_loop_obstacles(ctx, n_obs, obs_state, obs_param, obs_get, 1, stream);
+        if (rc) return rc;
+    }
     HIP_TRY(ctx, hipGetLastError());
     return 0;
 }

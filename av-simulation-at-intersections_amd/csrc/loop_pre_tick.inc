@@ -111,8 +111,10 @@ struct PreScratch {
 // BLOCK: the caller's workgroup has several wavefronts that all run this function on the same scratch (the four-wave T = 40 kernel):
 // its phases are separated by workgroup barriers.  Otherwise ONE wavefront runs it -- alone in its workgroup or beside helper
 // wavefronts that must not be woken -- and what it hands from lane to lane through LDS only needs the compiler's order kept.
+// OCC_READY: the caller has already put the P.n_obs obstacles' circle centres into W.occ (group_pre_tick_kernel gathers
+// scripted obstacles and group mates there) and pred_cc is not read.
 #define JSIM_PRE_SYNC() do { if (BLOCK) __syncthreads(); else { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); } } while (0)
-template <bool BLOCK = false>
+template <bool BLOCK = false, bool OCC_READY = false>
 __device__ __forceinline__ PreOut jsim_pre_tick_ego(const PreP &P, const double2 *pred_cc, const double4 *pred_bc, PreScratch &W, int lane, int ego,
                                                     long long off, int M, double sx, double sy, double sv, long long idx0,
                                                     int prev)
@@ -127,7 +129,8 @@ __device__ __forceinline__ PreOut jsim_pre_tick_ego(const PreP &P, const double2
     int status = JSIM_OK;
 
     // obstacle circle centres -> LDS
-    for (int e = lane; e < P.n_obs * P.n_steps * 2; e += 64) occ[e] = pred_cc[e];
+    if (!OCC_READY)
+        for (int e = lane; e < P.n_obs * P.n_steps * 2; e += 64) occ[e] = pred_cc[e];
     stepbuf[lane] = 0.0;
 
     // ---- progress index (mpc_intersection.py:106-109): nearest index in direction on the FULL path
@@ -370,6 +373,112 @@ __global__ __launch_bounds__(64) void loop_pre_tick_kernel(PreP P)
     if (lane != 0) return;
     P.status[ego] = o.status;
     if (o.status != JSIM_OK) return; // the reference raised: the ego's loop state stays as it was
+    P.traj_idx[ego] = o.idx;
+    P.path_len[ego] = o.path_len;
+    P.col_flag[ego] = o.col;
+    if (o.col && P.col_xy) { P.col_xy[2 * ego] = o.cx; P.col_xy[2 * ego + 1] = o.cy; }
+    if (P.first_idx) P.first_idx[ego] = o.first;
+}
+#endif
+
+// ---- Interacting egos (main/scenarios/interactive_mpc.py:117-190): the obstacles of an ego are the scripted vehicles and
+//      the OTHER egos of its group (contiguous batch range group_off[g] .. group_off[g + 1]), every ego predicted like an
+//      obstacle from its tick-start state: MovingObstaclesPrediction(x, y, v, yaw, a = 0, steering = the delta it applied
+//      last tick).
+struct EgoPredP {
+    int B, n_steps;
+    double dt, L, cc0, cc1;
+    const double *x0;    // [B][4] (x, y, v, yaw)
+    const double *di_ai; // [B][2] (delta, a) applied last tick (0 before the first step and after a respawn)
+    double *pred;        // [B][n_steps][3] (x, y, yaw); may be NULL
+    double2 *pred_cc;    // [B][n_steps][2] circle centres
+    double4 *pred_bc;    // [B] bounding circles, as obstacle_predict_kernel
+};
+
+// One thread per ego over the whole batch, 64 per block (each thread is a serial chain of n_steps fp64 sin / cos: one wave per
+// CU rather than four to a block).  The arithmetic is obstacle_predict_kernel's, operation for operation, so an ego
+// predicted here equals its (x, y, v, yaw, 0, delta) tuple run through that kernel bit for bit.
+#ifndef JSIM_KERNEL_TU /* (a kernel translation unit of the split build holds the register kernels only) */
+__global__ __launch_bounds__(64) void ego_predict_kernel(EgoPredP P)
+{
+    const int o = blockIdx.x * blockDim.x + threadIdx.x;
+    if (o >= P.B) return;
+    double2 *pcc = P.pred_cc;
+    double bx0 = INFINITY, bx1 = -INFINITY, by0 = INFINITY, by1 = -INFINITY;
+    double x = P.x0[4 * o], y = P.x0[4 * o + 1], v = P.x0[4 * o + 2], yaw = P.x0[4 * o + 3];
+    const double a = 0.0, st = P.di_ai[2 * o];
+    const double tn = tan(st);
+    for (int i = 0; i < P.n_steps; ++i) {
+        x += v * cos(yaw) * P.dt;
+        y += v * sin(yaw) * P.dt;
+        v += a * P.dt;
+        yaw += (v / P.L) * tn * P.dt;
+        const size_t k = (size_t)o * P.n_steps + i;
+        if (P.pred) { P.pred[3 * k] = x; P.pred[3 * k + 1] = y; P.pred[3 * k + 2] = yaw; }
+        const double c = cos(yaw), s = sin(yaw);
+        pcc[2 * k] = double2{c * P.cc0 - s * 0.0 + x, s * P.cc0 + c * 0.0 + y};
+        pcc[2 * k + 1] = double2{c * P.cc1 - s * 0.0 + x, s * P.cc1 + c * 0.0 + y};
+        for (int b = 0; b < 2; ++b) {
+            const double2 q = pcc[2 * k + b];
+            bx0 = fmin(bx0, q.x); bx1 = fmax(bx1, q.x); by0 = fmin(by0, q.y); by1 = fmax(by1, q.y);
+        }
+    }
+    const double mx = 0.5 * (bx0 + bx1), my = 0.5 * (by0 + by1);
+    double r = 0.0;
+    for (int i = 0; i < 2 * P.n_steps; ++i) {
+        const double2 q = pcc[(size_t)o * P.n_steps * 2 + i];
+        const double dx = q.x - mx, dy = q.y - my;
+        r = fmax(r, sqrt(dx * dx + dy * dy));
+    }
+    P.pred_bc[o] = double4{mx, my, r * (1.0 + 1e-9) + 1e-9, 0.0};
+}
+#endif
+
+struct GroupP {
+    const int *group_of;     // [B] group of each ego
+    const int *group_off;    // [n_groups + 1]
+    const double2 *ego_cc;   // [B][n_steps][2] (ego_predict_kernel)
+    const double4 *ego_bc;   // [B]
+    int n_scripted;          // scripted obstacles in P.pred_cc / P.pred_bc (P.n_obs is ignored)
+};
+
+// loop_pre_tick_kernel for interacting egos: one wavefront per ego gathers the scripted predictions, then those of its group
+// mates in ascending batch index (skipping itself), into the LDS view jsim_pre_tick_ego reads, and runs the same glue.
+#ifndef JSIM_KERNEL_TU /* (a kernel translation unit of the split build holds the register kernels only) */
+__global__ __launch_bounds__(64) void group_pre_tick_kernel(PreP P, GroupP G)
+{
+    __shared__ PreScratch W;
+    __shared__ double4 bc[JSIM_MAX_OBS];
+    constexpr bool BLOCK = false;
+    const int lane = threadIdx.x;
+    const int ego = blockIdx.x;
+    if (ego >= P.B) return;
+    const int g = G.group_of[ego];
+    const int g0 = G.group_off[g], n_mates = G.group_off[g + 1] - g0 - 1;
+    const int ns = G.n_scripted, per = P.n_steps * 2;
+    for (int e = lane; e < ns * per; e += 64) W.occ[e] = P.pred_cc[e];
+    for (int m = 0; m < n_mates; ++m) {
+        const int j = g0 + m + (g0 + m >= ego ? 1 : 0);
+        const double2 *src = G.ego_cc + (size_t)j * per;
+        double2 *dst = W.occ + (size_t)(ns + m) * per;
+        for (int e = lane; e < per; e += 64) dst[e] = src[e];
+    }
+    if (lane < ns) bc[lane] = P.pred_bc[lane];
+    else if (lane < ns + n_mates) {
+        const int m = lane - ns;
+        bc[lane] = G.ego_bc[g0 + m + (g0 + m >= ego ? 1 : 0)];
+    }
+    JSIM_PRE_SYNC();
+    PreP Q = P;
+    Q.n_obs = ns + n_mates;
+    const int pid = P.path_id[ego];
+    const long long off = P.poff[pid];
+    const int M = (int)(P.poff[pid + 1] - off);
+    const PreOut o = jsim_pre_tick_ego<false, true>(Q, nullptr, bc, W, lane, ego, off, M, P.x0[4 * ego], P.x0[4 * ego + 1],
+                                                     P.x0[4 * ego + 2], P.traj_idx[ego], P.prev_path_len[ego]);
+    if (lane != 0) return;
+    P.status[ego] = o.status;
+    if (o.status != JSIM_OK) return; // the ego's loop state stays as it was
     P.traj_idx[ego] = o.idx;
     P.path_len[ego] = o.path_len;
     P.col_flag[ego] = o.col;

@@ -107,3 +107,30 @@ def make_loop(cfg_id: int, eng: BatchedMPC, x0: torch.Tensor, hist_cap: int, rou
     elif respawn != "initial":
         raise ValueError(f"unknown respawn rule {respawn!r}")
     return sc, loop
+
+
+def interacting_batch(routes, G: int, T: int, seed: int = 0) -> Tuple[S.EgoBatch, np.ndarray]:
+    """G groups of 4 interacting egos (InteractingLoop), one group per intersection: the four approaches of intersection()
+    (start_pos 1..4; routes = route_table(False), ordered start_pos x turn_indicator), each ego turning left or going straight
+    (seeded), so that the routes of a group cross in the middle.  Every ego starts on its route at a seeded offset within its
+    first quarter, heading along it at a seeded speed, with a cold controller.  Returns (batch, group_sizes)."""
+    if len(routes) != 12:
+        raise ValueError("routes must be the 12 routes of intersection() (route_table(multi_lane=False))")
+    rng = np.random.default_rng(seed)
+    B = 4 * G
+    path_id = np.zeros(B, dtype=np.int32)
+    x0 = np.zeros((B, 4))
+    target_ind = np.zeros(B, dtype=np.int64)
+    for g in range(G):
+        for k in range(4):
+            b = 4 * g + k
+            turn = int(rng.integers(1, 3))                 # 1: left, 2: straight
+            path_id[b] = 3 * k + (turn - 1)
+            r = routes[path_id[b]]
+            s = int(rng.integers(0, len(r) // 4))
+            x0[b] = (r[s, 0], r[s, 1], rng.uniform(0.0, 0.5 * S.SPEED), r[s, 2])
+            target_ind[b] = s
+    path_len = np.array([len(routes[p]) for p in path_id], dtype=np.int32)
+    batch = S.EgoBatch(x0=x0, path_id=path_id, path_len=path_len, target_ind=target_ind, speed=np.full(B, S.SPEED),
+                       oa=np.zeros((B, T)), od=np.zeros((B, T)))
+    return batch, np.full(G, 4, dtype=np.int64)

@@ -195,6 +195,31 @@ int jsim_loop_pre_tick(jsim_ctx *ctx, int32_t B, const double *x0, const int32_t
                        int32_t *first_idx, int32_t *status, int32_t frame_window, int32_t margin,
                        int32_t *dbg_res_idx /*[B][320]*/, int32_t *dbg_n_res, void *stream);
 
+/* ---- Interacting egos: several automated vehicles at one intersection that react to each other
+ * (main/scenarios/interactive_mpc.py:117-190).  The obstacles of an ego are the scripted vehicles (spec order) and then the
+ * OTHER egos of its group (ascending batch index); egos in different groups never affect each other.
+ * jsim_loop_set_groups: group_off [n_groups + 1] (HOST) cuts the batch into contiguous groups, group_off[0] = 0,
+ *   group_off[n_groups] = B, 1..8 egos per group.  n_groups = 0 clears the groups.
+ * jsim_loop_predict_egos: every ego predicted like an obstacle, MovingObstaclesPrediction(x, y, v, yaw, a = 0,
+ *   steering = di_ai[b][0]) with the ego's wheelbase and circles -- bit for bit what jsim_loop_predict_obstacles gives for
+ *   that tuple.  x0 [B][4], di_ai [B][2]; pred [B][n_steps][3] = (x, y, yaw) or NULL.
+ * jsim_loop_run_interacting: n_ticks Jacobi ticks (every prediction from the tick-start states), arguments as
+ *   jsim_loop_run_scenario: obstacles get() -> their prediction -> the egos' prediction -> glue per ego -> MPC.step -> plant,
+ *   history, goal / respawn -> glue reset of respawned egos -> obstacles step().  Separate launches per tick.  Refused (-22):
+ *   no groups for this B, n_obs + (largest group - 1) > 8, speed_cutoff != 0, or after jsim_loop_set_obstacle_geometry
+ *   (the collision rows have one distance threshold).  A group of one ego gives jsim_loop_run_scenario's results. */
+int jsim_loop_set_groups(jsim_ctx *ctx, int32_t B, int32_t n_groups, const int32_t *group_off);
+int jsim_loop_predict_egos(jsim_ctx *ctx, int32_t B, const double *x0, const double *di_ai, int32_t n_steps, double *pred,
+                           void *stream);
+int jsim_loop_run_interacting(jsim_ctx *ctx, int32_t B, int32_t n_ticks, double *x0, const int32_t *path_id, int32_t *path_len,
+                              const double *speed, int64_t *target_ind, double *oa, double *od, double *ox, double *oy,
+                              double *ov, double *oyaw, double *xref, uint32_t *active_mask, int32_t *status, int32_t *n_iter,
+                              double *di_ai, const double *x0_spawn, const int64_t *target_spawn, int32_t *age, int32_t max_age,
+                              double *hist, int32_t *tick, int32_t hist_cap, uint64_t *n_respawn, int64_t *traj_idx,
+                              int32_t *prev_path_len, int32_t *col_flag, int32_t *pre_status, int32_t frame_window,
+                              int32_t margin, int32_t n_obs, double *obs_state, const double *obs_param, double *obs_get,
+                              int32_t n_steps, int32_t speed_cutoff, void *stream);
+
 /* n_ticks consecutive closed-loop ticks, each = jsim_mpc_step followed by jsim_loop_advance, with identical results.
  * For the horizons that have the fused register-resident kernel (T = 13, 20) this is ONE launch in which every
  * wavefront runs all n_ticks for its own ego (egos are independent, so none waits for the slowest solve of a tick);

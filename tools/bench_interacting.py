@@ -1,0 +1,60 @@
+#!/usr/bin/env python3
+"""Interacting egos (InteractingLoop, jsim_loop_run_interacting) at scale: G groups of 4 egos on the four approaches of
+intersection() (workloads.interacting_batch, default 1024 groups = 4096 egos), FRAME_WINDOW = 20, no scripted obstacles.
+For each horizon: ego-steps/s over `ticks` device-synchronised ticks after a warm-up, for the interacting loop and, beside it,
+the same egos in singleton groups (no interaction), plus how many ego-ticks were cut by a group mate.  One JSON line per
+horizon.
+
+    python tools/bench_interacting.py [--groups 1024] [--ticks 100] [--warmup 10] [--horizons 13 20]
+"""
+import argparse
+import importlib
+import json
+import os
+import sys
+import time
+
+import torch
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+pkg = importlib.import_module("av-simulation-at-intersections_amd")
+W = pkg.workloads
+
+
+def timed(routes, G, T, sizes_of, ticks, warmup):
+    batch, sizes = W.interacting_batch(routes, G, T, seed=1)
+    eng, x0 = W.make_engine(routes, batch, T, "cuda:0")
+    il = pkg.InteractingLoop(eng, x0, group_sizes=sizes_of(sizes, eng.B), max_age=W.MAX_AGE)
+    il.run(warmup)
+    torch.cuda.synchronize()
+    cut = torch.zeros((), dtype=torch.int64, device=eng.device)
+    t0 = time.perf_counter()
+    for _ in range(ticks):
+        il.tick()
+        cut += il.pre.col_flag.sum()
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    return eng.B * ticks / dt, dt / ticks * 1e3, int(cut.item()), int((eng.status != 0).sum().item())
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--groups", type=int, default=1024)
+    ap.add_argument("--ticks", type=int, default=100)
+    ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--horizons", type=int, nargs="+", default=[13, 20])
+    a = ap.parse_args()
+    routes = W.route_table(False)[0]
+    for T in a.horizons:
+        r_i = timed(routes, a.groups, T, lambda s, B: s, a.ticks, a.warmup)
+        r_s = timed(routes, a.groups, T, lambda s, B: [1] * B, a.ticks, a.warmup)
+        print(json.dumps({"T": T, "egos": 4 * a.groups, "groups": a.groups, "ticks": a.ticks,
+                          "interacting_ego_steps_per_s": round(r_i[0]), "interacting_ms_per_tick": round(r_i[1], 4),
+                          "interacting_cut_ego_ticks": r_i[2], "interacting_failed_solves_last_tick": r_i[3],
+                          "singleton_ego_steps_per_s": round(r_s[0]), "singleton_ms_per_tick": round(r_s[1], 4),
+                          "singleton_cut_ego_ticks": r_s[2]}), flush=True)
+
+
+if __name__ == "__main__":
+    main()
