@@ -47,18 +47,21 @@ class ClosedLoop:
             _ptr(self.target_spawn), _ptr(self.age), self.max_age, _ptr(self.hist), _ptr(self.tick_counter),
             self.hist_cap, _ptr(self.n_respawn), eng._stream()), eng._ctx, "jsim_loop_advance")
 
+    def _loop_args(self):
+        """Checks x0; returns the step and advance buffers the multi-tick entry points take after (ctx, B, n_ticks)."""
+        eng = self.eng
+        eng._check_x0(self.x0)
+        return (_ptr(self.x0), _ptr(eng.path_id), _ptr(eng.path_len), _ptr(eng.speed), _ptr(eng.target_ind), _ptr(eng.oa),
+                _ptr(eng.od), _ptr(eng.ox), _ptr(eng.oy), _ptr(eng.ov), _ptr(eng.oyaw), _ptr(eng.xref), _ptr(eng.active_mask),
+                _ptr(eng.status), _ptr(eng.n_iter), _ptr(eng.di_ai), _ptr(self.x0_spawn), _ptr(self.target_spawn),
+                _ptr(self.age), self.max_age, _ptr(self.hist), _ptr(self.tick_counter), self.hist_cap, _ptr(self.n_respawn))
+
     def run(self, n_ticks: int):
         """n_ticks ticks in one call (jsim_mpc_run_ticks): for T = 13 / 20 a single launch in which each wavefront
         advances its own ego n_ticks times -- same results as n_ticks x tick(), without per-tick synchronisation."""
         eng = self.eng
-        eng._check_x0(self.x0)
-        _cabi.check(eng.lib.jsim_mpc_run_ticks(
-            eng._ctx, eng.B, int(n_ticks), _ptr(self.x0), _ptr(eng.path_id), _ptr(eng.path_len), _ptr(eng.speed),
-            _ptr(eng.target_ind), _ptr(eng.oa), _ptr(eng.od), _ptr(eng.ox), _ptr(eng.oy), _ptr(eng.ov), _ptr(eng.oyaw),
-            _ptr(eng.xref), _ptr(eng.active_mask), _ptr(eng.status), _ptr(eng.n_iter), _ptr(eng.di_ai),
-            _ptr(self.x0_spawn), _ptr(self.target_spawn), _ptr(self.age), self.max_age, _ptr(self.hist),
-            _ptr(self.tick_counter), self.hist_cap, _ptr(self.n_respawn), eng._stream()), eng._ctx,
-            "jsim_mpc_run_ticks")
+        _cabi.check(eng.lib.jsim_mpc_run_ticks(eng._ctx, eng.B, int(n_ticks), *self._loop_args(), eng._stream()), eng._ctx,
+                    "jsim_mpc_run_ticks")
 
     # ---- hipGraph: a launch-bound inner loop (two short kernels per tick) replayed without host work
     def capture(self, ticks: int):
@@ -222,6 +225,8 @@ class ScenarioLoop:
     obstacle get() -> prediction -> progress index / resample / collision / cut-off -> MPC.step -> plant, history, goal ->
     obstacle step()."""
 
+    _ENTRY = "jsim_loop_run_scenario"
+
     def __init__(self, engine: BatchedMPC, x0: torch.Tensor, obstacle_specs, hist_cap: int = 0, max_age: int = 0,
                  frame_window: int = 10, mode: str = "truncate"):
         self.loop = ClosedLoop(engine, x0, hist_cap=hist_cap, max_age=max_age)
@@ -242,19 +247,13 @@ class ScenarioLoop:
         """n_ticks ticks in one call (jsim_loop_run_scenario).  With a register kernel (config.ONE_WAVE_HORIZONS / FOUR_WAVE_HORIZONS) and MAX_ITER = 1
         three launches -- the scripted obstacles rolled forward n_ticks ticks, their predictions for every
         tick, and one fused launch in which each ego's wavefront does glue + solve + plant n_ticks times.  Same results as
-        n_ticks x tick()."""
+        n_ticks x tick().  (InteractingLoop.run: the same arguments to jsim_loop_run_interacting.)"""
         loop, pre, ob, eng = self.loop, self.pre, self.obst, self.loop.eng
-        eng._check_x0(loop.x0)
-        _cabi.check(eng.lib.jsim_loop_run_scenario(
-            eng._ctx, eng.B, int(n_ticks), _ptr(loop.x0), _ptr(eng.path_id), _ptr(eng.path_len), _ptr(eng.speed),
-            _ptr(eng.target_ind), _ptr(eng.oa), _ptr(eng.od), _ptr(eng.ox), _ptr(eng.oy), _ptr(eng.ov), _ptr(eng.oyaw),
-            _ptr(eng.xref), _ptr(eng.active_mask), _ptr(eng.status), _ptr(eng.n_iter), _ptr(eng.di_ai),
-            _ptr(loop.x0_spawn), _ptr(loop.target_spawn), _ptr(loop.age), loop.max_age, _ptr(loop.hist),
-            _ptr(loop.tick_counter), loop.hist_cap, _ptr(loop.n_respawn), _ptr(pre.traj_idx), _ptr(pre.prev_len),
-            _ptr(pre.col_flag), _ptr(pre.status), pre.frame_window, pre.margin, ob.n, _ptr(ob.state) if ob.n else None,
+        _cabi.check(getattr(eng.lib, self._ENTRY)(
+            eng._ctx, eng.B, int(n_ticks), *loop._loop_args(), _ptr(pre.traj_idx), _ptr(pre.prev_len), _ptr(pre.col_flag),
+            _ptr(pre.status), pre.frame_window, pre.margin, ob.n, _ptr(ob.state) if ob.n else None,
             _ptr(ob.param) if ob.n else None, _ptr(ob.get_buf) if ob.n else None, pre.n_steps,
-            1 if pre.mode == "speed_cutoff" else 0, eng._stream()), eng._ctx,
-            "jsim_loop_run_scenario")
+            1 if pre.mode == "speed_cutoff" else 0, eng._stream()), eng._ctx, self._ENTRY)
         pre.n_obs = ob.n
 
 
@@ -289,7 +288,11 @@ class InteractingLoop:
     group (ascending batch index), every ego predicted like an obstacle from its tick-start state with a = 0 and the steering
     it applied last tick.  A tick is a Jacobi step: all egos solve, then all advance.  Groups are contiguous batch ranges
     (group_off [n_groups + 1], or group_sizes), 1..8 egos each; n_obs + largest group - 1 <= 8.  Egos in different groups
-    never affect each other; a group of one ego is ScenarioLoop.  Only the truncate glue, only obstacles of the ego's shape."""
+    never affect each other; a group of one ego is ScenarioLoop.  Only the truncate glue, only obstacles of the ego's shape.
+    run(n_ticks): n_ticks ticks in one call (jsim_loop_run_interacting; separate launches per tick)."""
+
+    _ENTRY = "jsim_loop_run_interacting"
+    run = ScenarioLoop.run
 
     def __init__(self, engine: BatchedMPC, x0: torch.Tensor, group_off=None, obstacle_specs=(), hist_cap: int = 0,
                  max_age: int = 0, frame_window: int = 20, group_sizes=None):
@@ -315,18 +318,3 @@ class InteractingLoop:
 
     def tick(self):
         self.run(1)
-
-    def run(self, n_ticks: int):
-        """n_ticks ticks in one call (jsim_loop_run_interacting; separate launches per tick)."""
-        loop, pre, ob, eng = self.loop, self.pre, self.obst, self.loop.eng
-        eng._check_x0(loop.x0)
-        _cabi.check(eng.lib.jsim_loop_run_interacting(
-            eng._ctx, eng.B, int(n_ticks), _ptr(loop.x0), _ptr(eng.path_id), _ptr(eng.path_len), _ptr(eng.speed),
-            _ptr(eng.target_ind), _ptr(eng.oa), _ptr(eng.od), _ptr(eng.ox), _ptr(eng.oy), _ptr(eng.ov), _ptr(eng.oyaw),
-            _ptr(eng.xref), _ptr(eng.active_mask), _ptr(eng.status), _ptr(eng.n_iter), _ptr(eng.di_ai),
-            _ptr(loop.x0_spawn), _ptr(loop.target_spawn), _ptr(loop.age), loop.max_age, _ptr(loop.hist),
-            _ptr(loop.tick_counter), loop.hist_cap, _ptr(loop.n_respawn), _ptr(pre.traj_idx), _ptr(pre.prev_len),
-            _ptr(pre.col_flag), _ptr(pre.status), pre.frame_window, pre.margin, ob.n, _ptr(ob.state) if ob.n else None,
-            _ptr(ob.param) if ob.n else None, _ptr(ob.get_buf) if ob.n else None, pre.n_steps, 0, eng._stream()), eng._ctx,
-            "jsim_loop_run_interacting")
-        pre.n_obs = ob.n

@@ -1261,49 +1261,66 @@ __global__ __launch_bounds__(256) void deviation_goal_kernel(GoalP P, const doub
 // ---------------------------------------------------------------------------------------------------
 // C-ABI
 // ---------------------------------------------------------------------------------------------------
+// A device array the context owns: reserve() only ever grows it (dropping the old contents when it does); freed with the context.
+template <class T> struct DevArray {
+    T *p = nullptr;
+    size_t cap = 0; // elements
+    DevArray() = default;
+    DevArray(const DevArray &) = delete;
+    DevArray &operator=(const DevArray &) = delete;
+    ~DevArray() { release(); }
+    operator T *() const { return p; }
+    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
+    hipError_t reserve(size_t n, bool *grew = nullptr)
+    {
+        if (grew) *grew = n > cap;
+        if (n <= cap) return hipSuccess;
+        release();
+        const hipError_t e = hipMalloc(&p, sizeof(T) * n);
+        if (e == hipSuccess) cap = n; else p = nullptr;
+        return e;
+    }
+};
+
 struct jsim_ctx {
-    jsim_cfg cfg;
-    int device;
-    double2 *d_pxy;
-    double *d_pyaw;
-    long long *d_poff;
-    int n_paths;
-    long long n_points;
+    jsim_cfg cfg{};
+    int device = 0;
+    DevArray<double2> d_pxy;
+    DevArray<double> d_pyaw;
+    DevArray<long long> d_poff;
+    int n_paths = 0;
+    long long n_points = 0;
     // per-vehicle loop glue (row f1): host copy of the paths, car circle geometry, per-point circle centres, predictions
-    double *h_cx, *h_cy, *h_cyaw;
-    int have_geom;
-    double cc0, cc1, col_radius;
-    double *d_get_all;     // [ticks][n_obs][6]  obstacle get() tuples of a fused scenario run
-    double2 *d_pred_all;   // [ticks][n_obs][n_steps][2]
-    double4 *d_bc_all;     // [ticks][n_obs] bounding circles of the predictions
-    double4 *d_pred_bc;    // [JSIM_MAX_OBS] of the current single-tick prediction
-    size_t get_all_cap, pred_all_cap; // in elements
-    double occ0, occ1, ocol_radius, oL; // the obstacles' circles / wheelbase (jsim_loop_set_obstacle_geometry); default: the ego's
-    int have_ogeom;
-    double2 *d_pcc;
-    double2 *d_pred_cc;
-    int pred_n_obs, pred_n_steps;
+    double *h_cx = nullptr, *h_cy = nullptr, *h_cyaw = nullptr;
+    int have_geom = 0;
+    double cc0 = 0, cc1 = 0, col_radius = 0;
+    DevArray<double> d_get_all;    // [ticks][n_obs][6]  obstacle get() tuples of a fused scenario run
+    DevArray<double2> d_pred_all;  // [ticks][n_obs][n_steps][2]
+    DevArray<double4> d_bc_all;    // [ticks][n_obs] bounding circles of the predictions
+    DevArray<double4> d_pred_bc;   // [JSIM_MAX_OBS] of the current single-tick prediction
+    double occ0 = 0, occ1 = 0, ocol_radius = 0, oL = 0; // the obstacles' circles / wheelbase (jsim_loop_set_obstacle_geometry); default: the ego's
+    int have_ogeom = 0;
+    DevArray<double2> d_pcc;
+    DevArray<double2> d_pred_cc;
+    int pred_n_obs = 0, pred_n_steps = 0;
     // interacting egos (jsim_loop_set_groups, jsim_loop_run_interacting): groups and the egos' own predictions
-    int *d_group_of, *d_group_off; // [group_B], [n_groups + 1]
-    int group_B, n_groups, group_max;
-    double2 *d_ego_cc;             // [B][n_steps][2] ..
-    double4 *d_ego_bc;             // .. [B], sized on first use (ego_pred_cap elements of d_ego_cc)
-    size_t ego_pred_cap, ego_bc_cap;
-    double *d_pcv;          // speed reference per path point (mpc_with_speed variant) or NULL
-    const int *cv_cut;      // caller-owned device array [B] or NULL
-    size_t lds_bytes;
-    const double *d_pe; // per-ego weights / limits (caller-owned device array) or NULL
-    void *comm;         // ncclComm_t of jsim_comm_init (RCCL), or NULL
-    int *d_order;       // launch order of the fused closed-loop launches (prepare_launch_order) ..
-    unsigned *d_work;   // .. and the per-ego iteration count of the previous launch it is derived from
-    unsigned long long *d_iters; // per-ego running totals of active-set iterations over the fused launches (jsim_mpc_iter_totals)
-    int iters_cap;
-    int order_cap;
-    int order_mode;     // 0: from the environment (default on), 1: on, -1: off (jsim_mpc_set_launch_order)
-    int use_reg_kernel; // 1: register-resident fast path available for this T (and not disabled)
-    int dbg_max_gi;
-    long long *dbg_clk; // diagnostic builds only
-    char err[512];
+    DevArray<int> d_group_of, d_group_off; // [group_B], [n_groups + 1]
+    int group_B = 0, n_groups = 0, group_max = 0;
+    DevArray<double2> d_ego_cc;    // [B][n_steps][2]
+    DevArray<double4> d_ego_bc;    // [B]
+    DevArray<double> d_pcv;        // speed reference per path point (mpc_with_speed variant) or NULL
+    const int *cv_cut = nullptr;   // caller-owned device array [B] or NULL
+    size_t lds_bytes = 0;
+    const double *d_pe = nullptr;  // per-ego weights / limits (caller-owned device array) or NULL
+    void *comm = nullptr;          // ncclComm_t of jsim_comm_init (RCCL), or NULL
+    DevArray<int> d_order;         // launch order of the fused closed-loop launches (prepare_launch_order) ..
+    DevArray<unsigned> d_work;     // .. and the per-ego iteration count of the previous launch it is derived from
+    DevArray<unsigned long long> d_iters; // per-ego running totals of active-set iterations over the fused launches (jsim_mpc_iter_totals)
+    int order_mode = 0;      // 0: from the environment (default on), 1: on, -1: off (jsim_mpc_set_launch_order)
+    int use_reg_kernel = 0;  // 1: register-resident fast path available for this T (and not disabled)
+    int dbg_max_gi = 0;
+    long long *dbg_clk = nullptr; // diagnostic builds only
+    char err[512] = "";
 };
 
 static thread_local char g_err[512] = "";
@@ -1384,7 +1401,6 @@ extern "C" int jsim_mpc_create(const jsim_cfg *cfg, int device_id, jsim_ctx **ou
     HIP_TRY(nullptr, hipFuncSetAttribute((const void *)mpc_step_kernel<2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     jsim_ctx *c = new (std::nothrow) jsim_ctx();
     if (!c) return fail(nullptr, -12, "jsim_mpc_create: out of memory");
-    memset(c, 0, sizeof(*c));
     c->cfg = *cfg;
     c->device = device_id;
     c->lds_bytes = lds_bytes;
@@ -1401,15 +1417,9 @@ extern "C" int jsim_mpc_create(const jsim_cfg *cfg, int device_id, jsim_ctx **ou
 
 static void free_paths(jsim_ctx *c)
 {
-    if (c->d_pxy) (void)hipFree(c->d_pxy);
-    if (c->d_pyaw) (void)hipFree(c->d_pyaw);
-    if (c->d_poff) (void)hipFree(c->d_poff);
-    if (c->d_pcc) (void)hipFree(c->d_pcc);
-    if (c->d_pcv) (void)hipFree(c->d_pcv);
-    c->d_pcv = nullptr;
+    c->d_pxy.release(); c->d_pyaw.release(); c->d_poff.release(); c->d_pcc.release(); c->d_pcv.release();
     delete[] c->h_cx; delete[] c->h_cy; delete[] c->h_cyaw;
-    c->h_cx = c->h_cy = c->h_cyaw = nullptr; c->d_pcc = nullptr;
-    c->d_pxy = nullptr; c->d_pyaw = nullptr; c->d_poff = nullptr;
+    c->h_cx = c->h_cy = c->h_cyaw = nullptr;
     c->n_paths = 0; c->n_points = 0;
 }
 
@@ -1419,19 +1429,7 @@ extern "C" void jsim_mpc_destroy(jsim_ctx *ctx)
     if (ctx->comm) (void)jsim_comm_destroy(ctx);
     DeviceGuard dev_guard(ctx->device);   // (a failed switch still frees: hipFree takes the pointers' own device)
     free_paths(ctx);
-    if (ctx->d_pred_cc) (void)hipFree(ctx->d_pred_cc);
-    if (ctx->d_get_all) (void)hipFree(ctx->d_get_all);
-    if (ctx->d_pred_all) (void)hipFree(ctx->d_pred_all);
-    if (ctx->d_bc_all) (void)hipFree(ctx->d_bc_all);
-    if (ctx->d_pred_bc) (void)hipFree(ctx->d_pred_bc);
-    if (ctx->d_group_of) (void)hipFree(ctx->d_group_of);
-    if (ctx->d_group_off) (void)hipFree(ctx->d_group_off);
-    if (ctx->d_ego_cc) (void)hipFree(ctx->d_ego_cc);
-    if (ctx->d_ego_bc) (void)hipFree(ctx->d_ego_bc);
-    if (ctx->d_order) (void)hipFree(ctx->d_order);
-    if (ctx->d_work) (void)hipFree(ctx->d_work);
-    if (ctx->d_iters) (void)hipFree(ctx->d_iters);
-    delete ctx;
+    delete ctx;                           // the device arrays, while the guard still holds the context's device
 }
 
 // circle centres of every path point (lib/trajectories.py:11-55 with the two body-axis circles of
@@ -1446,8 +1444,8 @@ static int upload_circle_centres(jsim_ctx *ctx)
         h[2 * i].x = c * ctx->cc0 - s * 0.0 + ctx->h_cx[i];     h[2 * i].y = s * ctx->cc0 + c * 0.0 + ctx->h_cy[i];
         h[2 * i + 1].x = c * ctx->cc1 - s * 0.0 + ctx->h_cx[i]; h[2 * i + 1].y = s * ctx->cc1 + c * 0.0 + ctx->h_cy[i];
     }
-    if (ctx->d_pcc) { (void)hipFree(ctx->d_pcc); ctx->d_pcc = nullptr; }
-    HIP_TRY(ctx, hipMalloc(&ctx->d_pcc, sizeof(double2) * 2 * N));
+    ctx->d_pcc.release();
+    HIP_TRY(ctx, ctx->d_pcc.reserve(2 * N));
     HIP_TRY(ctx, hipMemcpy(ctx->d_pcc, h.data(), sizeof(double2) * 2 * N, hipMemcpyHostToDevice));
     return 0;
 }
@@ -1468,9 +1466,9 @@ extern "C" int jsim_mpc_set_paths(jsim_ctx *ctx, const double *cx, const double 
     double2 *h = new (std::nothrow) double2[N];
     if (!h) return fail(ctx, -12, "jsim_mpc_set_paths: out of host memory");
     for (long long i = 0; i < N; ++i) { h[i].x = cx[i]; h[i].y = cy[i]; }
-    hipError_t e = hipMalloc(&ctx->d_pxy, sizeof(double2) * N);
-    if (e == hipSuccess) e = hipMalloc(&ctx->d_pyaw, sizeof(double) * N);
-    if (e == hipSuccess) e = hipMalloc(&ctx->d_poff, sizeof(long long) * (n_paths + 1));
+    hipError_t e = ctx->d_pxy.reserve(N);
+    if (e == hipSuccess) e = ctx->d_pyaw.reserve(N);
+    if (e == hipSuccess) e = ctx->d_poff.reserve(n_paths + 1);
     if (e == hipSuccess) e = hipMemcpy(ctx->d_pxy, h, sizeof(double2) * N, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(ctx->d_pyaw, cyaw, sizeof(double) * N, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(ctx->d_poff, path_off, sizeof(long long) * (n_paths + 1), hipMemcpyHostToDevice);
@@ -1485,9 +1483,50 @@ extern "C" int jsim_mpc_set_paths(jsim_ctx *ctx, const double *cx, const double 
     return 0;
 }
 
-static void fill_kp(const jsim_ctx *ctx, int32_t B, KP &P)
+// The closed-loop entry points' arguments, packed once per call: jsim_mpc_step's buffers (x0 is written by the advance only,
+// path_len by the glue only), jsim_loop_advance's own, and those of the glue and the scripted obstacles (jsim_loop_run_scenario).
+struct StepBufs {
+    double *x0; const int32_t *path_id, *path_len; const double *speed; int64_t *target_ind;
+    double *oa, *od, *ox, *oy, *ov, *oyaw, *xref; uint32_t *active_mask; int32_t *status, *n_iter;
+};
+struct AdvanceBufs {
+    double *di_ai; const double *x0_spawn; const int64_t *target_spawn; int32_t *age, max_age;
+    double *hist; int32_t *tick, hist_cap; uint64_t *n_respawn;
+};
+struct GlueBufs {
+    int64_t *traj_idx; int32_t *prev_path_len, *col_flag, *pre_status, frame_window, margin, n_obs;
+    double *obs_state; const double *obs_param; double *obs_get; int32_t n_steps, speed_cutoff;
+};
+
+static int check_step(jsim_ctx *ctx, const char *fn, const StepBufs &S)
+{
+    if (!S.x0 || !S.path_id || !S.path_len || !S.speed || !S.target_ind || !S.oa || !S.od || !S.status)
+        return fail(ctx, -22, "%s: a required device pointer is null", fn);
+    if (!ctx->d_pxy) return fail(ctx, -22, "%s: jsim_mpc_set_paths has not been called", fn);
+    if (ctx->cfg.max_iter > 1 && !S.ov)
+        return fail(ctx, -22, "%s: MAX_ITER=%d needs the ov buffer (the next pass's travel distances)", fn, ctx->cfg.max_iter);
+    return 0;
+}
+
+static int check_advance(jsim_ctx *ctx, const char *fn, const AdvanceBufs &A)
+{
+    if (!A.di_ai || !A.x0_spawn || !A.target_spawn || !A.age) return fail(ctx, -22, "%s: a required device pointer is null", fn);
+    if (A.hist && !A.tick) return fail(ctx, -22, "%s: hist needs a device tick counter", fn);
+    return 0;
+}
+
+static int check_glue(jsim_ctx *ctx, const char *fn, const GlueBufs &G)
+{
+    if (!G.traj_idx || !G.prev_path_len || !G.col_flag || !G.pre_status) return fail(ctx, -22, "%s: a required device pointer is null", fn);
+    if (G.n_obs > 0 && (!G.obs_state || !G.obs_param || !G.obs_get)) return fail(ctx, -22, "%s: null obstacle pointer", fn);
+    if (!ctx->d_pxy || !ctx->d_pcc || !ctx->have_geom) return fail(ctx, -22, "%s: paths / geometry not set", fn);
+    return 0;
+}
+
+static KP fill_kp(const jsim_ctx *ctx, int32_t B, const StepBufs &S)
 {
     const jsim_cfg &c = ctx->cfg;
+    KP P;
     memset(&P, 0, sizeof(P));
     P.T = c.T; P.n = jsim_nvar(c.T, c.nx == 5); P.ld = jsim_ld(P.n); P.B = B;
     P.jerkw = c.jerk_weight;
@@ -1499,6 +1538,34 @@ static void fill_kp(const jsim_ctx *ctx, int32_t B, KP &P)
     P.vmax_plant = c.max_speed; P.vmin = c.min_speed; P.vref_min = c.min_ref_speed;
     P.pxy = ctx->d_pxy; P.pyaw = ctx->d_pyaw; P.poff = ctx->d_poff;
     P.pcv = ctx->d_pcv; P.cv_cut = ctx->cv_cut; P.pe = ctx->d_pe;
+    P.x0 = S.x0; P.path_id = S.path_id; P.path_len = S.path_len; P.speed = S.speed;
+    P.target_ind = (long long *)S.target_ind; P.oa = S.oa; P.od = S.od; P.ox = S.ox; P.oy = S.oy; P.ov = S.ov; P.oyaw = S.oyaw;
+    P.xref = S.xref; P.amask = S.active_mask; P.status = S.status; P.n_iter = S.n_iter;
+    P.dbg_clk = ctx->dbg_clk; P.dbg_max_gi = ctx->dbg_max_gi;
+    return P;
+}
+
+// the largest double x with sqrt(x) <= thr (IEEE sqrt is correctly rounded and monotone): comparing a squared distance with it
+// decides exactly what comparing its square root with thr decides
+static double jsim_sqrt_threshold(double thr)
+{
+    double x = thr * thr;
+    while (std::sqrt(x) > thr) x = std::nextafter(x, 0.0);
+    while (std::sqrt(std::nextafter(x, INFINITY)) <= thr) x = std::nextafter(x, INFINITY);
+    return x;
+}
+
+// the glue's launch constants and the context's tables and single-tick predictions; the per-ego pointers are the caller's
+static PreP fill_prep(const jsim_ctx *ctx, int B, int n_obs, int n_steps, int frame_window, int margin)
+{
+    const jsim_cfg &c = ctx->cfg;
+    PreP P;
+    memset(&P, 0, sizeof(P));
+    P.B = B; P.n_obs = n_obs; P.n_steps = n_steps; P.frame_window = frame_window; P.margin = margin;
+    P.dt = c.dt; P.max_accel = c.max_accel; P.max_speed = c.max_speed; P.thr = ctx->col_radius + ctx->ocol_radius; // min_distance: 2 * radius, or car radius + bicycle radius
+    P.thr_sq = jsim_sqrt_threshold(P.thr);
+    P.pxy = ctx->d_pxy; P.pcc = ctx->d_pcc; P.poff = ctx->d_poff; P.pred_cc = ctx->d_pred_cc; P.pred_bc = ctx->d_pred_bc;
+    return P;
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -1535,15 +1602,10 @@ static int prepare_launch_order(jsim_ctx *ctx, int B, hipStream_t s, TickP &K)
     K.order = nullptr; K.work = nullptr;
     const bool on = ctx->order_mode ? ctx->order_mode > 0 : (bool)enabled;
     if (!on || B < 512 || B > 65536) return 0; // fewer egos than slots: all start at once; beyond: O(B^2) ranking not worth it
-    if (ctx->order_cap < B) {
-        if (ctx->d_order) (void)hipFree(ctx->d_order);
-        if (ctx->d_work) (void)hipFree(ctx->d_work);
-        ctx->d_order = nullptr; ctx->d_work = nullptr; ctx->order_cap = 0;
-        HIP_TRY(ctx, hipMalloc(&ctx->d_order, sizeof(int) * (size_t)B));
-        HIP_TRY(ctx, hipMalloc(&ctx->d_work, sizeof(unsigned) * (size_t)B));
-        ctx->order_cap = B;
-        HIP_TRY(ctx, hipMemsetAsync(ctx->d_work, 0, sizeof(unsigned) * (size_t)B, s));
-    }
+    bool grew;
+    HIP_TRY(ctx, ctx->d_order.reserve(B));
+    HIP_TRY(ctx, ctx->d_work.reserve(B, &grew));
+    if (grew) HIP_TRY(ctx, hipMemsetAsync(ctx->d_work, 0, sizeof(unsigned) * (size_t)B, s));
     hipLaunchKernelGGL(launch_order_kernel, dim3((B + 255) / 256), dim3(256), 0, s, ctx->d_work, B, ctx->d_order);
     HIP_TRY(ctx, hipMemsetAsync(ctx->d_work, 0, sizeof(unsigned) * (size_t)B, s));
     K.order = ctx->d_order; K.work = ctx->d_work;
@@ -1554,13 +1616,9 @@ static int prepare_launch_order(jsim_ctx *ctx, int B, hipStream_t s, TickP &K)
 static int prepare_iter_totals(jsim_ctx *ctx, int B, hipStream_t s, TickP &K)
 {
     K.iters = nullptr;
-    if (ctx->iters_cap < B) {
-        if (ctx->d_iters) (void)hipFree(ctx->d_iters);
-        ctx->d_iters = nullptr; ctx->iters_cap = 0;
-        HIP_TRY(ctx, hipMalloc(&ctx->d_iters, sizeof(unsigned long long) * (size_t)B));
-        ctx->iters_cap = B;
-        HIP_TRY(ctx, hipMemsetAsync(ctx->d_iters, 0, sizeof(unsigned long long) * (size_t)B, s));
-    }
+    bool grew;
+    HIP_TRY(ctx, ctx->d_iters.reserve(B, &grew));
+    if (grew) HIP_TRY(ctx, hipMemsetAsync(ctx->d_iters, 0, sizeof(unsigned long long) * (size_t)B, s));
     K.iters = ctx->d_iters;
     return 0;
 }
@@ -1570,10 +1628,10 @@ extern "C" int jsim_mpc_iter_totals(jsim_ctx *ctx, int32_t B, uint64_t *totals, 
     if (!ctx) return fail(nullptr, -22, "jsim_mpc_iter_totals: null ctx");
     DeviceGuard dev_guard(ctx->device);
     JSIM_GUARD_OK(ctx);
-    if (B <= 0 || B > ctx->iters_cap) return fail(ctx, -22, "jsim_mpc_iter_totals: B=%d, but the fused launches of this context had at most %d egos", B, ctx->iters_cap);
+    if (B <= 0 || (size_t)B > ctx->d_iters.cap) return fail(ctx, -22, "jsim_mpc_iter_totals: B=%d, but the fused launches of this context had at most %d egos", B, (int)ctx->d_iters.cap);
     HIP_TRY(ctx, hipDeviceSynchronize());
     if (totals) HIP_TRY(ctx, hipMemcpy(totals, ctx->d_iters, sizeof(uint64_t) * (size_t)B, hipMemcpyDeviceToHost));
-    if (reset) HIP_TRY(ctx, hipMemset(ctx->d_iters, 0, sizeof(unsigned long long) * (size_t)ctx->iters_cap));
+    if (reset) HIP_TRY(ctx, hipMemset(ctx->d_iters, 0, sizeof(unsigned long long) * ctx->d_iters.cap));
     return 0;
 }
 
@@ -1589,53 +1647,30 @@ extern "C" int jsim_mpc_get_launch_order(jsim_ctx *ctx, int32_t B, int32_t *orde
     if (!ctx) return fail(nullptr, -22, "jsim_mpc_get_launch_order: null ctx");
     DeviceGuard dev_guard(ctx->device);
     JSIM_GUARD_OK(ctx);
-    if (B <= 0 || B > ctx->order_cap) return fail(ctx, -22, "jsim_mpc_get_launch_order: B=%d, but the last ordered launch had %d egos", B, ctx->order_cap);
+    if (B <= 0 || (size_t)B > ctx->d_work.cap) // (d_work is reserved after d_order)
+        return fail(ctx, -22, "jsim_mpc_get_launch_order: B=%d, but the last ordered launch had %d egos", B, (int)ctx->d_work.cap);
     HIP_TRY(ctx, hipDeviceSynchronize());
     if (order) HIP_TRY(ctx, hipMemcpy(order, ctx->d_order, sizeof(int32_t) * (size_t)B, hipMemcpyDeviceToHost));
     if (work) HIP_TRY(ctx, hipMemcpy(work, ctx->d_work, sizeof(uint32_t) * (size_t)B, hipMemcpyDeviceToHost));
     return 0;
 }
 
-static int launch_step(jsim_ctx *ctx, int32_t B, const double *x0, const int32_t *path_id, const int32_t *path_len,
-                       const double *speed, int64_t *target_ind, double *oa, double *od, double *ox, double *oy,
-                       double *ov, double *oyaw, double *xref, uint32_t *active_mask, int32_t *status, int32_t *n_iter,
-                       double *xbar, int64_t *ref_idx, double *H, double *g, double *lam, void *stream)
+// MPC.step for the batch: one launch per linearisation pass (_iterative_linear_mpc_control, main/lib/mpc.py:231-236)
+static void launch_step(const jsim_ctx *ctx, KP &P, hipStream_t s)
 {
-    if (!ctx) return fail(nullptr, -22, "jsim_mpc_step: null ctx");
-    DeviceGuard dev_guard(ctx->device);
-    JSIM_GUARD_OK(ctx);
-    if (B < 0) return fail(ctx, -22, "jsim_mpc_step: B=%d", B);
-    if (B == 0) return 0;
-    if (!x0 || !path_id || !path_len || !speed || !target_ind || !oa || !od || !status)
-        return fail(ctx, -22, "jsim_mpc_step: a required device pointer is null");
-    if (!ctx->d_pxy) return fail(ctx, -22, "jsim_mpc_step: jsim_mpc_set_paths has not been called");
     const jsim_cfg &c = ctx->cfg;
-    KP P;
-    fill_kp(ctx, B, P);
-    P.x0 = x0; P.path_id = path_id; P.path_len = path_len; P.speed = speed;
-    P.target_ind = (long long *)target_ind; P.oa = oa; P.od = od; P.ox = ox; P.oy = oy; P.ov = ov; P.oyaw = oyaw;
-    P.xref = xref; P.amask = active_mask; P.status = status; P.n_iter = n_iter;
-    P.dbg_xbar = xbar; P.dbg_idx = (long long *)ref_idx; P.dbg_H = H; P.dbg_g = g; P.dbg_lam = lam;
-    P.dbg_clk = ctx->dbg_clk;
-    P.dbg_max_gi = ctx->dbg_max_gi;
-
-    const size_t lds_bytes = ctx->lds_bytes;
-    hipStream_t s = (hipStream_t)stream;
     TickP K;
     memset(&K, 0, sizeof(K));
     K.n_ticks = 1; // plain MPC.step: one tick, no plant/bookkeeping
-    if (c.max_iter > 1 && !ov) return fail(ctx, -22, "jsim_mpc_step: MAX_ITER=%d needs the ov buffer (the next pass's travel distances)", c.max_iter);
-    for (int pass = 0; pass < c.max_iter; ++pass) { // _iterative_linear_mpc_control, main/lib/mpc.py:231-236: one launch per pass
+    for (int pass = 0; pass < c.max_iter; ++pass) {
         P.pass = pass;
-        if (ctx->use_reg_kernel) launch_reg(c.T, B, s, P, K);
+        if (ctx->use_reg_kernel) launch_reg(c.T, P.B, s, P, K);
         else if (c.nx == 5) {
-            if (P.n <= 64) hipLaunchKernelGGL((mpc_step_kernel<1, true>), dim3(B), dim3(64), lds_bytes, s, P);
-            else hipLaunchKernelGGL((mpc_step_kernel<2, true>), dim3(B), dim3(64), lds_bytes, s, P);
-        } else if (P.n <= 64) hipLaunchKernelGGL((mpc_step_kernel<1, false>), dim3(B), dim3(64), lds_bytes, s, P);
-        else hipLaunchKernelGGL((mpc_step_kernel<2, false>), dim3(B), dim3(64), lds_bytes, s, P);
+            if (P.n <= 64) hipLaunchKernelGGL((mpc_step_kernel<1, true>), dim3(P.B), dim3(64), ctx->lds_bytes, s, P);
+            else hipLaunchKernelGGL((mpc_step_kernel<2, true>), dim3(P.B), dim3(64), ctx->lds_bytes, s, P);
+        } else if (P.n <= 64) hipLaunchKernelGGL((mpc_step_kernel<1, false>), dim3(P.B), dim3(64), ctx->lds_bytes, s, P);
+        else hipLaunchKernelGGL((mpc_step_kernel<2, false>), dim3(P.B), dim3(64), ctx->lds_bytes, s, P);
     }
-    HIP_TRY(ctx, hipGetLastError());
-    return 0;
 }
 
 extern "C" int jsim_mpc_step(jsim_ctx *ctx, int32_t B, const double *x0, const int32_t *path_id,
@@ -1643,8 +1678,8 @@ extern "C" int jsim_mpc_step(jsim_ctx *ctx, int32_t B, const double *x0, const i
                              double *od, double *ox, double *oy, double *ov, double *oyaw, double *xref,
                              uint32_t *active_mask, int32_t *status, int32_t *n_iter, void *stream)
 {
-    return launch_step(ctx, B, x0, path_id, path_len, speed, target_ind, oa, od, ox, oy, ov, oyaw, xref, active_mask,
-                       status, n_iter, nullptr, nullptr, nullptr, nullptr, nullptr, stream);
+    return jsim_mpc_step_debug(ctx, B, x0, path_id, path_len, speed, target_ind, oa, od, ox, oy, ov, oyaw, xref, active_mask,
+                               status, n_iter, nullptr, nullptr, nullptr, nullptr, nullptr, stream);
 }
 
 extern "C" int jsim_mpc_step_debug(jsim_ctx *ctx, int32_t B, const double *x0, const int32_t *path_id,
@@ -1653,8 +1688,19 @@ extern "C" int jsim_mpc_step_debug(jsim_ctx *ctx, int32_t B, const double *x0, c
                                    uint32_t *active_mask, int32_t *status, int32_t *n_iter, double *xbar,
                                    int64_t *ref_idx, double *H, double *g, double *lam, void *stream)
 {
-    return launch_step(ctx, B, x0, path_id, path_len, speed, target_ind, oa, od, ox, oy, ov, oyaw, xref, active_mask,
-                       status, n_iter, xbar, ref_idx, H, g, lam, stream);
+    if (!ctx) return fail(nullptr, -22, "jsim_mpc_step: null ctx");
+    DeviceGuard dev_guard(ctx->device);
+    JSIM_GUARD_OK(ctx);
+    if (B < 0) return fail(ctx, -22, "jsim_mpc_step: B=%d", B);
+    if (B == 0) return 0;
+    const StepBufs S = {const_cast<double *>(x0), path_id, path_len, speed, target_ind, oa, od, ox, oy, ov, oyaw, xref,
+                        active_mask, status, n_iter};
+    if (int rc = check_step(ctx, "jsim_mpc_step", S)) return rc;
+    KP P = fill_kp(ctx, B, S);
+    P.dbg_xbar = xbar; P.dbg_idx = (long long *)ref_idx; P.dbg_H = H; P.dbg_g = g; P.dbg_lam = lam;
+    launch_step(ctx, P, (hipStream_t)stream);
+    HIP_TRY(ctx, hipGetLastError());
+    return 0;
 }
 
 extern "C" int jsim_plant_step(jsim_ctx *ctx, int32_t B, double *x0, const double *oa, const double *od,
@@ -1693,6 +1739,18 @@ extern "C" int jsim_mpc_xref_deviation_goal(jsim_ctx *ctx, int32_t B, const doub
     return 0;
 }
 
+// plant, history, goal / respawn, then the device tick counter
+static void launch_advance(const jsim_ctx *ctx, int B, const StepBufs &S, const AdvanceBufs &A, hipStream_t s)
+{
+    const jsim_cfg &c = ctx->cfg;
+    LoopP P = {B, c.T, A.max_age > 0 ? A.max_age : 0x7fffffff, c.dt, c.L, c.max_steer, c.max_speed, c.min_speed,
+               c.max_decel, c.goal_dis, c.stop_speed, ctx->d_pxy, ctx->d_poff, ctx->d_pe};
+    hipLaunchKernelGGL(loop_advance_kernel, dim3((B + 255) / 256), dim3(256), 0, s, P, S.x0, S.oa, S.od, S.status, A.di_ai,
+                       (long long *)S.target_ind, S.path_id, S.path_len, A.x0_spawn, (const long long *)A.target_spawn, A.age,
+                       A.hist, A.tick, A.hist_cap, (unsigned long long *)A.n_respawn);
+    if (A.tick) hipLaunchKernelGGL(tick_increment_kernel, dim3(1), dim3(1), 0, s, A.tick);
+}
+
 extern "C" int jsim_loop_advance(jsim_ctx *ctx, int32_t B, double *x0, double *oa, double *od, const int32_t *status,
                                  double *di_ai, int64_t *target_ind, const int32_t *path_id, const int32_t *path_len,
                                  const double *x0_spawn, const int64_t *target_spawn, int32_t *age, int32_t max_age,
@@ -1703,18 +1761,15 @@ extern "C" int jsim_loop_advance(jsim_ctx *ctx, int32_t B, double *x0, double *o
     JSIM_GUARD_OK(ctx);
     if (B < 0) return fail(ctx, -22, "jsim_loop_advance: B=%d", B);
     if (B == 0) return 0;
-    if (!x0 || !oa || !od || !status || !di_ai || !target_ind || !path_id || !path_len || !x0_spawn || !target_spawn || !age)
-        return fail(ctx, -22, "jsim_loop_advance: null device pointer");
-    if (hist && !tick) return fail(ctx, -22, "jsim_loop_advance: hist needs a device tick counter");
+    if (!x0 || !oa || !od || !status || !target_ind || !path_id || !path_len)
+        return fail(ctx, -22, "jsim_loop_advance: a required device pointer is null");
+    const AdvanceBufs A = {di_ai, x0_spawn, target_spawn, age, max_age, hist, tick, hist_cap, n_respawn};
+    if (int rc = check_advance(ctx, "jsim_loop_advance", A)) return rc;
     if (!ctx->d_pxy) return fail(ctx, -22, "jsim_loop_advance: no paths set");
-    const jsim_cfg &c = ctx->cfg;
-    LoopP P = {B, c.T, max_age > 0 ? max_age : 0x7fffffff, c.dt, c.L, c.max_steer, c.max_speed, c.min_speed,
-               c.max_decel, c.goal_dis, c.stop_speed, ctx->d_pxy, ctx->d_poff, ctx->d_pe};
-    hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(loop_advance_kernel, dim3((B + 255) / 256), dim3(256), 0, s, P, x0, oa, od, status, di_ai,
-                       (long long *)target_ind, path_id, path_len, x0_spawn, (const long long *)target_spawn, age, hist,
-                       tick, hist_cap, (unsigned long long *)n_respawn);
-    if (tick) hipLaunchKernelGGL(tick_increment_kernel, dim3(1), dim3(1), 0, s, tick);
+    StepBufs S = {}; // (the advance reads status)
+    S.x0 = x0; S.path_id = path_id; S.path_len = path_len; S.target_ind = target_ind; S.oa = oa; S.od = od;
+    S.status = const_cast<int32_t *>(status);
+    launch_advance(ctx, B, S, A, (hipStream_t)stream);
     HIP_TRY(ctx, hipGetLastError());
     return 0;
 }
@@ -1728,57 +1783,6 @@ extern "C" int jsim_debug_set_clock_buffer(jsim_ctx *ctx, long long *dev_buf)
     return 0;
 }
 #endif
-
-extern "C" int jsim_mpc_run_ticks(jsim_ctx *ctx, int32_t B, int32_t n_ticks, double *x0, const int32_t *path_id,
-                                  const int32_t *path_len, const double *speed, int64_t *target_ind, double *oa,
-                                  double *od, double *ox, double *oy, double *ov, double *oyaw, double *xref,
-                                  uint32_t *active_mask, int32_t *status, int32_t *n_iter, double *di_ai,
-                                  const double *x0_spawn, const int64_t *target_spawn, int32_t *age, int32_t max_age,
-                                  double *hist, int32_t *tick, int32_t hist_cap, uint64_t *n_respawn, void *stream)
-{
-    if (!ctx) return fail(nullptr, -22, "jsim_mpc_run_ticks: null ctx");
-    DeviceGuard dev_guard(ctx->device);
-    JSIM_GUARD_OK(ctx);
-    if (B < 0 || n_ticks < 0) return fail(ctx, -22, "jsim_mpc_run_ticks: B=%d n_ticks=%d", B, n_ticks);
-    if (B == 0 || n_ticks == 0) return 0;
-    if (!x0 || !path_id || !path_len || !speed || !target_ind || !oa || !od || !status || !di_ai || !x0_spawn ||
-        !target_spawn || !age)
-        return fail(ctx, -22, "jsim_mpc_run_ticks: a required device pointer is null");
-    if (hist && !tick) return fail(ctx, -22, "jsim_mpc_run_ticks: hist needs a device tick counter");
-    if (!ctx->d_pxy) return fail(ctx, -22, "jsim_mpc_run_ticks: jsim_mpc_set_paths has not been called");
-    const jsim_cfg &c = ctx->cfg;
-    hipStream_t s = (hipStream_t)stream;
-    if (!ctx->use_reg_kernel || c.max_iter > 1) {
-        // horizons without the fused register kernel, or several linearisation passes per step: the same ticks as separate launches
-        for (int k = 0; k < n_ticks; ++k) {
-            int rc = launch_step(ctx, B, x0, path_id, path_len, speed, target_ind, oa, od, ox, oy, ov, oyaw, xref,
-                                 active_mask, status, n_iter, nullptr, nullptr, nullptr, nullptr, nullptr, stream);
-            if (rc) return rc;
-            rc = jsim_loop_advance(ctx, B, x0, oa, od, status, di_ai, target_ind, path_id, path_len, x0_spawn,
-                                   target_spawn, age, max_age, hist, tick, hist_cap, n_respawn, stream);
-            if (rc) return rc;
-        }
-        return 0;
-    }
-    KP P;
-    fill_kp(ctx, B, P);
-    P.x0 = x0; P.path_id = path_id; P.path_len = path_len; P.speed = speed;
-    P.target_ind = (long long *)target_ind; P.oa = oa; P.od = od; P.ox = ox; P.oy = oy; P.ov = ov; P.oyaw = oyaw;
-    P.xref = xref; P.amask = active_mask; P.status = status; P.n_iter = n_iter;
-    P.dbg_clk = nullptr; P.dbg_max_gi = ctx->dbg_max_gi;
-    TickP K;
-    memset(&K, 0, sizeof(K));
-    K.n_ticks = n_ticks; K.advance = 1; K.max_age = max_age > 0 ? max_age : 0x7fffffff; K.hist_cap = hist_cap;
-    K.max_decel = c.max_decel; K.goal_dis = c.goal_dis; K.stop_speed = c.stop_speed;
-    K.x0w = x0; K.di_ai = di_ai; K.x0_spawn = x0_spawn; K.target_spawn = (const long long *)target_spawn; K.age = age;
-    K.hist = hist; K.tick = tick; K.n_respawn = (unsigned long long *)n_respawn;
-    if (int rc_ = prepare_launch_order(ctx, B, s, K)) return rc_;
-    if (int rc_ = prepare_iter_totals(ctx, B, s, K)) return rc_;
-    launch_reg(c.T, B, s, P, K);
-    if (tick) hipLaunchKernelGGL(tick_add_kernel, dim3(1), dim3(1), 0, s, tick, n_ticks);
-    HIP_TRY(ctx, hipGetLastError());
-    return 0;
-}
 
 // ---------------------------------------------------------------------------------------------------
 // The job's one exchange: all-gather of the per-rank result blocks over RCCL (xGMI).  Egos are independent
@@ -2021,16 +2025,6 @@ extern "C" int jsim_plan_routes(int device_id, int32_t n_routes, const double *s
     return 0;
 }
 
-// the largest double x with sqrt(x) <= thr (IEEE sqrt is correctly rounded and monotone): comparing a squared distance with it
-// decides exactly what comparing its square root with thr decides
-static double jsim_sqrt_threshold(double thr)
-{
-    double x = thr * thr;
-    while (std::sqrt(x) > thr) x = std::nextafter(x, 0.0);
-    while (std::sqrt(std::nextafter(x, INFINITY)) <= thr) x = std::nextafter(x, INFINITY);
-    return x;
-}
-
 extern "C" int jsim_loop_set_geometry(jsim_ctx *ctx, double cc_front, double cc_rear, double radius)
 {
     if (!ctx) return fail(nullptr, -22, "jsim_loop_set_geometry: null ctx");
@@ -2039,8 +2033,8 @@ extern "C" int jsim_loop_set_geometry(jsim_ctx *ctx, double cc_front, double cc_
     if (!(radius > 0)) return fail(ctx, -22, "jsim_loop_set_geometry: radius must be positive");
     ctx->cc0 = cc_front; ctx->cc1 = cc_rear; ctx->col_radius = radius; ctx->have_geom = 1;
     if (!ctx->have_ogeom) { ctx->occ0 = cc_front; ctx->occ1 = cc_rear; ctx->ocol_radius = radius; ctx->oL = ctx->cfg.L; }
-    if (!ctx->d_pred_cc) HIP_TRY(ctx, hipMalloc(&ctx->d_pred_cc, sizeof(double2) * JSIM_MAX_OBS * JSIM_MAX_PRED * 2));
-    if (!ctx->d_pred_bc) HIP_TRY(ctx, hipMalloc(&ctx->d_pred_bc, sizeof(double4) * JSIM_MAX_OBS));
+    HIP_TRY(ctx, ctx->d_pred_cc.reserve(JSIM_MAX_OBS * JSIM_MAX_PRED * 2));
+    HIP_TRY(ctx, ctx->d_pred_bc.reserve(JSIM_MAX_OBS));
     return upload_circle_centres(ctx);
 }
 
@@ -2052,6 +2046,19 @@ extern "C" int jsim_loop_set_obstacle_geometry(jsim_ctx *ctx, double cc_front, d
     if (!(radius > 0) || !(wheelbase > 0)) return fail(ctx, -22, "jsim_loop_set_obstacle_geometry: radius and wheelbase must be positive");
     ctx->occ0 = cc_front; ctx->occ1 = cc_rear; ctx->ocol_radius = radius; ctx->oL = wheelbase; ctx->have_ogeom = 1;
     return 0;
+}
+
+// obstacle_predict_kernel on n_ticks consecutive ticks' get() tuples (one block per tick)
+static void launch_obstacle_predict(const jsim_ctx *ctx, int n_obs, int n_steps, const double *get, double *pred, double2 *pred_cc,
+                                    double4 *pred_bc, int n_ticks, hipStream_t s)
+{
+    const ObsP P = {n_obs, n_steps, ctx->cfg.dt, ctx->oL, ctx->occ0, ctx->occ1, get, pred, pred_cc, pred_bc};
+    hipLaunchKernelGGL(obstacle_predict_kernel, dim3(n_ticks), dim3(64), 0, s, P);
+}
+
+static ObsStepP obstacle_step_p(const jsim_ctx *ctx, int n_obs, int do_step, double *state, const double *param, double *get)
+{
+    return ObsStepP{n_obs, do_step, ctx->have_ogeom ? ctx->oL : ctx->cfg.L, state, param, get};
 }
 
 extern "C" int jsim_loop_predict_obstacles(jsim_ctx *ctx, int32_t n_obs, const double *obst, int32_t n_steps, double *pred,
@@ -2066,8 +2073,7 @@ extern "C" int jsim_loop_predict_obstacles(jsim_ctx *ctx, int32_t n_obs, const d
     ctx->pred_n_obs = n_obs; ctx->pred_n_steps = n_steps;
     if (n_obs == 0) return 0;
     if (!obst || !pred) return fail(ctx, -22, "jsim_loop_predict_obstacles: null device pointer");
-    ObsP P = {n_obs, n_steps, ctx->cfg.dt, ctx->oL, ctx->occ0, ctx->occ1, obst, pred, ctx->d_pred_cc, ctx->d_pred_bc};
-    hipLaunchKernelGGL(obstacle_predict_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, P);
+    launch_obstacle_predict(ctx, n_obs, n_steps, obst, pred, ctx->d_pred_cc, ctx->d_pred_bc, 1, (hipStream_t)stream);
     HIP_TRY(ctx, hipGetLastError());
     return 0;
 }
@@ -2086,13 +2092,7 @@ extern "C" int jsim_loop_pre_tick(jsim_ctx *ctx, int32_t B, const double *x0, co
         return fail(ctx, -22, "jsim_loop_pre_tick: null device pointer");
     if (!ctx->d_pxy || !ctx->d_pcc) return fail(ctx, -22, "jsim_loop_pre_tick: paths / geometry not set");
     if (dbg_res_idx && !dbg_n_res) return fail(ctx, -22, "jsim_loop_pre_tick: dbg_res_idx needs dbg_n_res");
-    const jsim_cfg &c = ctx->cfg;
-    PreP P;
-    memset(&P, 0, sizeof(P));
-    P.B = B; P.n_obs = ctx->pred_n_obs; P.n_steps = ctx->pred_n_steps; P.frame_window = frame_window; P.margin = margin;
-    P.dt = c.dt; P.max_accel = c.max_accel; P.max_speed = c.max_speed; P.thr = ctx->col_radius + ctx->ocol_radius; // min_distance: 2 * radius, or car radius + bicycle radius
-    P.thr_sq = jsim_sqrt_threshold(P.thr);
-    P.pxy = ctx->d_pxy; P.pcc = ctx->d_pcc; P.poff = ctx->d_poff; P.pred_cc = ctx->d_pred_cc; P.pred_bc = ctx->d_pred_bc;
+    PreP P = fill_prep(ctx, B, ctx->pred_n_obs, ctx->pred_n_steps, frame_window, margin);
     P.x0 = x0; P.path_id = path_id; P.traj_idx = (long long *)traj_idx; P.prev_path_len = prev_path_len; P.path_len = path_len;
     P.col_flag = col_flag; P.col_xy = col_xy; P.first_idx = first_idx; P.status = status;
     P.dbg_res_idx = dbg_res_idx; P.dbg_n_res = dbg_n_res;
@@ -2107,10 +2107,10 @@ extern "C" int jsim_mpc_set_path_speed(jsim_ctx *ctx, const double *cv)
     if (!ctx) return fail(nullptr, -22, "jsim_mpc_set_path_speed: null ctx");
     DeviceGuard dev_guard(ctx->device);
     JSIM_GUARD_OK(ctx);
-    if (ctx->d_pcv) { (void)hipFree(ctx->d_pcv); ctx->d_pcv = nullptr; }
+    ctx->d_pcv.release();
     if (!cv) return 0; // back to the plain controller (no speed reference)
     if (ctx->n_points <= 0) return fail(ctx, -22, "jsim_mpc_set_path_speed: call jsim_mpc_set_paths first");
-    HIP_TRY(ctx, hipMalloc(&ctx->d_pcv, sizeof(double) * ctx->n_points));
+    HIP_TRY(ctx, ctx->d_pcv.reserve(ctx->n_points));
     HIP_TRY(ctx, hipMemcpy(ctx->d_pcv, cv, sizeof(double) * ctx->n_points, hipMemcpyHostToDevice));
     return 0;
 }
@@ -2151,8 +2151,8 @@ extern "C" int jsim_loop_obstacles(jsim_ctx *ctx, int32_t n_obs, double *state, 
     if (n_obs < 0 || n_obs > JSIM_MAX_OBS) return fail(ctx, -22, "jsim_loop_obstacles: n_obs=%d (max %d)", n_obs, JSIM_MAX_OBS);
     if (n_obs == 0) return 0;
     if (!state || !param) return fail(ctx, -22, "jsim_loop_obstacles: null device pointer");
-    ObsStepP P = {n_obs, do_step ? 1 : 0, ctx->have_ogeom ? ctx->oL : ctx->cfg.L, state, param, get};
-    hipLaunchKernelGGL(obstacle_step_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, P);
+    hipLaunchKernelGGL(obstacle_step_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream,
+                       obstacle_step_p(ctx, n_obs, do_step ? 1 : 0, state, param, get));
     HIP_TRY(ctx, hipGetLastError());
     return 0;
 }
@@ -2162,6 +2162,124 @@ __global__ __launch_bounds__(256) void glue_reset_kernel(int B, const int *age, 
 {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b < B && age[b] == 0) { traj_idx[b] = 0; prev_len[b] = -1; }
+}
+
+// the egos' predictions (circle centres, bounding circles), sized on first use
+static int ensure_ego_pred(jsim_ctx *ctx, int B, int n_steps)
+{
+    HIP_TRY(ctx, ctx->d_ego_cc.reserve((size_t)B * n_steps * 2));
+    HIP_TRY(ctx, ctx->d_ego_bc.reserve(B));
+    return 0;
+}
+
+static void launch_ego_predict(jsim_ctx *ctx, int B, const double *x0, const double *di_ai, int n_steps, double *pred, hipStream_t s)
+{
+    EgoPredP P = {B, n_steps, ctx->cfg.dt, ctx->cfg.L, ctx->cc0, ctx->cc1, x0, di_ai, pred, ctx->d_ego_cc, ctx->d_ego_bc};
+    hipLaunchKernelGGL(ego_predict_kernel, dim3((B + 63) / 64), dim3(64), 0, s, P);   // one wave per block: spread over the CUs
+}
+
+// where the glue's cut-off index goes: the controller's speed cut-off (jsim_mpc_set_speed_cutoff), or the path length
+static int32_t *glue_out(const jsim_ctx *ctx, const StepBufs &S, const GlueBufs &G)
+{
+    return const_cast<int32_t *>(G.speed_cutoff ? ctx->cv_cut : S.path_len);
+}
+
+enum class Glue { none, scripted, interacting };
+
+// n_ticks ticks as separate launches, the calls the tick() methods of closed_loop.py make.  With a glue (G): scripted obstacles
+// get() -> their prediction -> [interacting: every ego's prediction from the tick-start states ->] glue per ego against the
+// scripted obstacles [, then its group mates] -> previous path length -> MPC.step -> plant, history, goal / respawn -> glue reset
+// of respawned egos -> obstacles step().  Without one: MPC.step -> plant, history, goal / respawn.
+static int run_host_ticks(jsim_ctx *ctx, int B, int n_ticks, const StepBufs &S, const AdvanceBufs &A, const GlueBufs *G,
+                          Glue kind, hipStream_t s)
+{
+    KP P = fill_kp(ctx, B, S);
+    PreP Q = {};
+    GroupP GP = {};
+    if (G) {
+        Q = fill_prep(ctx, B, G->n_obs, G->n_steps, G->frame_window, G->margin);
+        Q.x0 = S.x0; Q.path_id = S.path_id; Q.traj_idx = (long long *)G->traj_idx; Q.prev_path_len = G->prev_path_len;
+        Q.path_len = glue_out(ctx, S, *G); Q.col_flag = G->col_flag; Q.status = G->pre_status;
+        GP = GroupP{ctx->d_group_of, ctx->d_group_off, ctx->d_ego_cc, ctx->d_ego_bc, G->n_obs};
+    }
+    auto obstacles = [&](int do_step) { // get(), or get() then step()
+        if (G->n_obs > 0)
+            hipLaunchKernelGGL(obstacle_step_kernel, dim3(1), dim3(64), 0, s,
+                               obstacle_step_p(ctx, G->n_obs, do_step, G->obs_state, G->obs_param, G->obs_get));
+    };
+    for (int k = 0; k < n_ticks; ++k) {
+        if (G) {
+            obstacles(0);
+            ctx->pred_n_obs = G->n_obs; ctx->pred_n_steps = G->n_steps;
+            if (G->n_obs > 0)
+                launch_obstacle_predict(ctx, G->n_obs, G->n_steps, G->obs_get, nullptr, ctx->d_pred_cc, ctx->d_pred_bc, 1, s);
+            if (kind == Glue::interacting) {
+                launch_ego_predict(ctx, B, S.x0, A.di_ai, G->n_steps, nullptr, s);
+                hipLaunchKernelGGL(group_pre_tick_kernel, dim3(B), dim3(64), 0, s, Q, GP);
+            } else {
+                hipLaunchKernelGGL(loop_pre_tick_kernel, dim3(B), dim3(64), 0, s, Q);
+            }
+            // the previous tmp_trajectory: the truncated path, or always the full one (mpc_intersection_new_ref.py:131)
+            HIP_TRY(ctx, hipMemcpyAsync(G->prev_path_len, S.path_len, sizeof(int32_t) * B, hipMemcpyDeviceToDevice, s));
+        }
+        launch_step(ctx, P, s);
+        launch_advance(ctx, B, S, A, s);
+        if (G) {
+            hipLaunchKernelGGL(glue_reset_kernel, dim3((B + 255) / 256), dim3(256), 0, s, B, A.age, (long long *)G->traj_idx,
+                               G->prev_path_len);
+            obstacles(1);
+        }
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    return 0;
+}
+
+// The fused K-tick register kernel runs the ticks when the horizon has one, MAX_ITER is 1, and a registered speed cut-off is
+// the glue's own output; otherwise run_host_ticks does.
+static bool fused_ticks(const jsim_ctx *ctx, const GlueBufs *G)
+{
+    return ctx->use_reg_kernel && ctx->cfg.max_iter == 1 && !(G && ctx->cv_cut && !G->speed_cutoff);
+}
+
+// One fused launch of n_ticks ticks: each ego's wavefront runs [glue (Q) ->] MPC.step -> plant, history, goal / respawn.
+static int launch_fused(jsim_ctx *ctx, int B, int n_ticks, const StepBufs &S, const AdvanceBufs &A, const PreK *Q, hipStream_t s)
+{
+    const jsim_cfg &c = ctx->cfg;
+    KP P = fill_kp(ctx, B, S);
+    P.dbg_clk = nullptr;
+    TickP K;
+    memset(&K, 0, sizeof(K));
+    K.n_ticks = n_ticks; K.advance = 1; K.max_age = A.max_age > 0 ? A.max_age : 0x7fffffff; K.hist_cap = A.hist_cap;
+    K.max_decel = c.max_decel; K.goal_dis = c.goal_dis; K.stop_speed = c.stop_speed;
+    K.x0w = S.x0; K.di_ai = A.di_ai; K.x0_spawn = A.x0_spawn; K.target_spawn = (const long long *)A.target_spawn; K.age = A.age;
+    K.hist = A.hist; K.tick = A.tick; K.n_respawn = (unsigned long long *)A.n_respawn;
+    if (int rc = prepare_launch_order(ctx, B, s, K)) return rc;
+    if (int rc = prepare_iter_totals(ctx, B, s, K)) return rc;
+    launch_reg(c.T, B, s, P, K, Q);
+    if (A.tick) hipLaunchKernelGGL(tick_add_kernel, dim3(1), dim3(1), 0, s, A.tick, n_ticks);
+    HIP_TRY(ctx, hipGetLastError());
+    return 0;
+}
+
+extern "C" int jsim_mpc_run_ticks(jsim_ctx *ctx, int32_t B, int32_t n_ticks, double *x0, const int32_t *path_id,
+                                  const int32_t *path_len, const double *speed, int64_t *target_ind, double *oa,
+                                  double *od, double *ox, double *oy, double *ov, double *oyaw, double *xref,
+                                  uint32_t *active_mask, int32_t *status, int32_t *n_iter, double *di_ai,
+                                  const double *x0_spawn, const int64_t *target_spawn, int32_t *age, int32_t max_age,
+                                  double *hist, int32_t *tick, int32_t hist_cap, uint64_t *n_respawn, void *stream)
+{
+    const char *const F = "jsim_mpc_run_ticks";
+    if (!ctx) return fail(nullptr, -22, "%s: null ctx", F);
+    DeviceGuard dev_guard(ctx->device);
+    JSIM_GUARD_OK(ctx);
+    if (B < 0 || n_ticks < 0) return fail(ctx, -22, "%s: B=%d n_ticks=%d", F, B, n_ticks);
+    if (B == 0 || n_ticks == 0) return 0;
+    const StepBufs S = {x0, path_id, path_len, speed, target_ind, oa, od, ox, oy, ov, oyaw, xref, active_mask, status, n_iter};
+    const AdvanceBufs A = {di_ai, x0_spawn, target_spawn, age, max_age, hist, tick, hist_cap, n_respawn};
+    if (int rc = check_step(ctx, F, S)) return rc;
+    if (int rc = check_advance(ctx, F, A)) return rc;
+    if (!fused_ticks(ctx, nullptr)) return run_host_ticks(ctx, B, n_ticks, S, A, nullptr, Glue::none, (hipStream_t)stream);
+    return launch_fused(ctx, B, n_ticks, S, A, nullptr, (hipStream_t)stream);
 }
 
 // The whole scenario loop (main/scenarios/mpc_intersection.py:99-163) for n_ticks ticks.  With a one-wave register kernel and
@@ -2178,107 +2296,45 @@ extern "C" int jsim_loop_run_scenario(jsim_ctx *ctx, int32_t B, int32_t n_ticks,
                                       int32_t n_obs, double *obs_state, const double *obs_param, double *obs_get,
                                       int32_t n_steps, int32_t speed_cutoff, void *stream)
 {
-    if (!ctx) return fail(nullptr, -22, "jsim_loop_run_scenario: null ctx");
+    const char *const F = "jsim_loop_run_scenario";
+    if (!ctx) return fail(nullptr, -22, "%s: null ctx", F);
     DeviceGuard dev_guard(ctx->device);
     JSIM_GUARD_OK(ctx);
-    if (B < 0 || n_ticks < 0 || frame_window < 0 || frame_window > 32 || margin < 0)
-        return fail(ctx, -22, "jsim_loop_run_scenario: bad argument");
+    if (B < 0 || n_ticks < 0 || frame_window < 0 || frame_window > 32 || margin < 0) return fail(ctx, -22, "%s: bad argument", F);
     if (B == 0 || n_ticks == 0) return 0;
-    if (!x0 || !path_id || !path_len || !speed || !target_ind || !oa || !od || !status || !di_ai || !x0_spawn || !target_spawn ||
-        !age || !traj_idx || !prev_path_len || !col_flag || !pre_status)
-        return fail(ctx, -22, "jsim_loop_run_scenario: a required device pointer is null");
+    const StepBufs S = {x0, path_id, path_len, speed, target_ind, oa, od, ox, oy, ov, oyaw, xref, active_mask, status, n_iter};
+    const AdvanceBufs A = {di_ai, x0_spawn, target_spawn, age, max_age, hist, tick, hist_cap, n_respawn};
+    const GlueBufs G = {traj_idx, prev_path_len, col_flag, pre_status, frame_window, margin, n_obs, obs_state, obs_param, obs_get,
+                        n_steps, speed_cutoff};
+    if (int rc = check_step(ctx, F, S)) return rc;
+    if (int rc = check_advance(ctx, F, A)) return rc;
     if (n_obs < 0 || n_obs > JSIM_MAX_OBS || n_steps < 1 || n_steps > JSIM_MAX_PRED)
-        return fail(ctx, -22, "jsim_loop_run_scenario: n_obs=%d (max %d), n_steps=%d (max %d)", n_obs, JSIM_MAX_OBS, n_steps, JSIM_MAX_PRED);
-    if (n_obs > 0 && (!obs_state || !obs_param || !obs_get)) return fail(ctx, -22, "jsim_loop_run_scenario: null obstacle pointer");
-    if (hist && !tick) return fail(ctx, -22, "jsim_loop_run_scenario: hist needs a device tick counter");
-    if (!ctx->d_pxy || !ctx->d_pcc || !ctx->have_geom) return fail(ctx, -22, "jsim_loop_run_scenario: paths / geometry not set");
-    const jsim_cfg &c = ctx->cfg;
+        return fail(ctx, -22, "%s: n_obs=%d (max %d), n_steps=%d (max %d)", F, n_obs, JSIM_MAX_OBS, n_steps, JSIM_MAX_PRED);
+    if (int rc = check_glue(ctx, F, G)) return rc;
+    if (speed_cutoff && !ctx->cv_cut) return fail(ctx, -22, "%s: the speed-cut-off glue needs jsim_mpc_set_speed_cutoff first", F);
     hipStream_t s = (hipStream_t)stream;
-    if (speed_cutoff && !ctx->cv_cut)
-        return fail(ctx, -22, "jsim_loop_run_scenario: the speed-cut-off glue needs jsim_mpc_set_speed_cutoff first");
-    int32_t *const glue_out = speed_cutoff ? const_cast<int32_t *>(ctx->cv_cut) : path_len; // where the cut-off index goes
-    if (!ctx->use_reg_kernel || !has_reg_kernel(c.T) || c.max_iter > 1 || (ctx->cv_cut && !speed_cutoff)) {
-        // tick by tick, as ScenarioLoop.tick does
-        for (int k = 0; k < n_ticks; ++k) {
-            int rc = jsim_loop_obstacles(ctx, n_obs, obs_state, obs_param, obs_get, 0, stream);
-            if (rc) return rc;
-            ctx->pred_n_obs = n_obs; ctx->pred_n_steps = n_steps;
-            if (n_obs > 0) {
-                ObsP OP = {n_obs, n_steps, c.dt, ctx->oL, ctx->occ0, ctx->occ1, obs_get, nullptr, ctx->d_pred_cc, ctx->d_pred_bc};
-                hipLaunchKernelGGL(obstacle_predict_kernel, dim3(1), dim3(64), 0, s, OP);
-            }
-            rc = jsim_loop_pre_tick(ctx, B, x0, path_id, traj_idx, prev_path_len, glue_out, col_flag, nullptr, nullptr, pre_status,
-                                    frame_window, margin, nullptr, nullptr, stream);
-            if (rc) return rc;
-            // the previous tmp_trajectory: the truncated path, or always the full one (mpc_intersection_new_ref.py:131)
-            HIP_TRY(ctx, hipMemcpyAsync(prev_path_len, path_len, sizeof(int32_t) * B, hipMemcpyDeviceToDevice, s));
-            rc = launch_step(ctx, B, x0, path_id, path_len, speed, target_ind, oa, od, ox, oy, ov, oyaw, xref, active_mask, status,
-                             n_iter, nullptr, nullptr, nullptr, nullptr, nullptr, stream);
-            if (rc) return rc;
-            rc = jsim_loop_advance(ctx, B, x0, oa, od, status, di_ai, target_ind, path_id, path_len, x0_spawn, target_spawn, age,
-                                   max_age, hist, tick, hist_cap, n_respawn, stream);
-            if (rc) return rc;
-            hipLaunchKernelGGL(glue_reset_kernel, dim3((B + 255) / 256), dim3(256), 0, s, B, age, (long long *)traj_idx, prev_path_len);
-            rc = jsim_loop_obstacles(ctx, n_obs, obs_state, obs_param, obs_get, 1, stream);
-            if (rc) return rc;
-        }
-        return 0;
-    }
+    if (!fused_ticks(ctx, &G)) return run_host_ticks(ctx, B, n_ticks, S, A, &G, Glue::scripted, s);
     // obstacles: n_ticks ticks of get() tuples, then every tick's prediction
-    const size_t need_get = (size_t)n_ticks * (n_obs > 0 ? n_obs : 1) * 6;
-    const size_t need_pred = (size_t)n_ticks * (n_obs > 0 ? n_obs : 1) * n_steps * 2;
-    if (need_get > ctx->get_all_cap) {
-        if (ctx->d_get_all) (void)hipFree(ctx->d_get_all);
-        ctx->d_get_all = nullptr; ctx->get_all_cap = 0;
-        HIP_TRY(ctx, hipMalloc(&ctx->d_get_all, sizeof(double) * need_get));
-        ctx->get_all_cap = need_get;
-    }
-    if (need_pred > ctx->pred_all_cap) {
-        if (ctx->d_pred_all) (void)hipFree(ctx->d_pred_all);
-        ctx->d_pred_all = nullptr; ctx->pred_all_cap = 0;
-        HIP_TRY(ctx, hipMalloc(&ctx->d_pred_all, sizeof(double2) * need_pred));
-        ctx->pred_all_cap = need_pred;
-        if (ctx->d_bc_all) (void)hipFree(ctx->d_bc_all);
-        ctx->d_bc_all = nullptr;
-        HIP_TRY(ctx, hipMalloc(&ctx->d_bc_all, sizeof(double4) * (need_pred / ((size_t)n_steps * 2))));
-    }
+    const size_t obs_ticks = (size_t)n_ticks * (n_obs > 0 ? n_obs : 1);
+    HIP_TRY(ctx, ctx->d_get_all.reserve(obs_ticks * 6));
+    HIP_TRY(ctx, ctx->d_pred_all.reserve(obs_ticks * n_steps * 2));
+    HIP_TRY(ctx, ctx->d_bc_all.reserve(obs_ticks));
     if (n_obs > 0) {
-        ObsStepP SP = {n_obs, 1, ctx->have_ogeom ? ctx->oL : c.L, obs_state, obs_param, nullptr};
-        hipLaunchKernelGGL(obstacle_rollout_kernel, dim3(1), dim3(64), 0, s, SP, n_ticks, ctx->d_get_all);
-        ObsP OP = {n_obs, n_steps, c.dt, ctx->oL, ctx->occ0, ctx->occ1, ctx->d_get_all, nullptr, ctx->d_pred_all, ctx->d_bc_all};
-        hipLaunchKernelGGL(obstacle_predict_kernel, dim3(n_ticks), dim3(64), 0, s, OP);
+        hipLaunchKernelGGL(obstacle_rollout_kernel, dim3(1), dim3(64), 0, s, obstacle_step_p(ctx, n_obs, 1, obs_state, obs_param, nullptr),
+                           n_ticks, ctx->d_get_all);
+        launch_obstacle_predict(ctx, n_obs, n_steps, ctx->d_get_all, nullptr, ctx->d_pred_all, ctx->d_bc_all, n_ticks, s);
         // the last get() tuples, as after n_ticks host ticks
         HIP_TRY(ctx, hipMemcpyAsync(obs_get, ctx->d_get_all + (size_t)(n_ticks - 1) * n_obs * 6, sizeof(double) * n_obs * 6,
                                     hipMemcpyDeviceToDevice, s));
     }
     ctx->pred_n_obs = n_obs; ctx->pred_n_steps = n_steps;
-    KP P;
-    fill_kp(ctx, B, P);
-    P.x0 = x0; P.path_id = path_id; P.path_len = path_len; P.speed = speed;
-    P.target_ind = (long long *)target_ind; P.oa = oa; P.od = od; P.ox = ox; P.oy = oy; P.ov = ov; P.oyaw = oyaw;
-    P.xref = xref; P.amask = active_mask; P.status = status; P.n_iter = n_iter;
-    P.dbg_clk = nullptr; P.dbg_max_gi = ctx->dbg_max_gi;
-    TickP K;
-    memset(&K, 0, sizeof(K));
-    K.n_ticks = n_ticks; K.advance = 1; K.max_age = max_age > 0 ? max_age : 0x7fffffff; K.hist_cap = hist_cap;
-    K.max_decel = c.max_decel; K.goal_dis = c.goal_dis; K.stop_speed = c.stop_speed;
-    K.x0w = x0; K.di_ai = di_ai; K.x0_spawn = x0_spawn; K.target_spawn = (const long long *)target_spawn; K.age = age;
-    K.hist = hist; K.tick = tick; K.n_respawn = (unsigned long long *)n_respawn;
     PreK Q;
     memset(&Q, 0, sizeof(Q));
-    Q.pre.B = B; Q.pre.n_obs = n_obs; Q.pre.n_steps = n_steps; Q.pre.frame_window = frame_window; Q.pre.margin = margin;
-    Q.pre.dt = c.dt; Q.pre.max_accel = c.max_accel; Q.pre.max_speed = c.max_speed; Q.pre.thr = ctx->col_radius + ctx->ocol_radius;
-    Q.pre.thr_sq = jsim_sqrt_threshold(Q.pre.thr);
-    Q.pre.pxy = ctx->d_pxy; Q.pre.pcc = ctx->d_pcc; Q.pre.poff = ctx->d_poff;
+    Q.pre = fill_prep(ctx, B, n_obs, n_steps, frame_window, margin);
     Q.pred_cc_all = ctx->d_pred_all; Q.pred_bc_all = ctx->d_bc_all; Q.traj_idx = (long long *)traj_idx; Q.prev_len = prev_path_len; Q.path_len_out = path_len;
     Q.col_flag = col_flag; Q.pre_status = pre_status;
-    Q.speed_cutoff = speed_cutoff ? 1 : 0; Q.cut_io = glue_out;
-    if (int rc_ = prepare_launch_order(ctx, B, s, K)) return rc_;
-    if (int rc_ = prepare_iter_totals(ctx, B, s, K)) return rc_;
-    launch_reg(c.T, B, s, P, K, &Q);
-    if (tick) hipLaunchKernelGGL(tick_add_kernel, dim3(1), dim3(1), 0, s, tick, n_ticks);
-    HIP_TRY(ctx, hipGetLastError());
-    return 0;
+    Q.speed_cutoff = speed_cutoff ? 1 : 0; Q.cut_io = glue_out(ctx, S, G);
+    return launch_fused(ctx, B, n_ticks, S, A, &Q, s);
 }
 
 // ---- Interacting egos: the obstacles of an ego are the scripted vehicles and the other egos of its group ----
@@ -2299,9 +2355,7 @@ extern "C" int jsim_loop_set_groups(jsim_ctx *ctx, int32_t B, int32_t n_groups, 
                 return fail(ctx, -22, "jsim_loop_set_groups: group %d has %d egos (1..%d)", g, n, JSIM_MAX_OBS);
         }
     }
-    if (ctx->d_group_of) (void)hipFree(ctx->d_group_of);
-    if (ctx->d_group_off) (void)hipFree(ctx->d_group_off);
-    ctx->d_group_of = nullptr; ctx->d_group_off = nullptr;
+    ctx->d_group_of.release(); ctx->d_group_off.release();
     ctx->group_B = 0; ctx->n_groups = 0; ctx->group_max = 0;
     if (n_groups == 0) return 0;
     std::vector<int> of((size_t)B);
@@ -2310,37 +2364,12 @@ extern "C" int jsim_loop_set_groups(jsim_ctx *ctx, int32_t B, int32_t n_groups, 
         for (int b = group_off[g]; b < group_off[g + 1]; ++b) of[b] = g;
         gmax = std::max(gmax, group_off[g + 1] - group_off[g]);
     }
-    HIP_TRY(ctx, hipMalloc(&ctx->d_group_of, sizeof(int) * B));
-    HIP_TRY(ctx, hipMalloc(&ctx->d_group_off, sizeof(int) * (n_groups + 1)));
+    HIP_TRY(ctx, ctx->d_group_of.reserve(B));
+    HIP_TRY(ctx, ctx->d_group_off.reserve(n_groups + 1));
     HIP_TRY(ctx, hipMemcpy(ctx->d_group_of, of.data(), sizeof(int) * B, hipMemcpyHostToDevice));
     HIP_TRY(ctx, hipMemcpy(ctx->d_group_off, group_off, sizeof(int) * (n_groups + 1), hipMemcpyHostToDevice));
     ctx->group_B = B; ctx->n_groups = n_groups; ctx->group_max = gmax;
     return 0;
-}
-
-// the egos' predictions (circle centres, bounding circles), sized on first use like d_pred_all
-static int ensure_ego_pred(jsim_ctx *ctx, int B, int n_steps)
-{
-    const size_t need = (size_t)B * n_steps * 2;
-    if (need > ctx->ego_pred_cap) {
-        if (ctx->d_ego_cc) (void)hipFree(ctx->d_ego_cc);
-        ctx->d_ego_cc = nullptr; ctx->ego_pred_cap = 0;
-        HIP_TRY(ctx, hipMalloc(&ctx->d_ego_cc, sizeof(double2) * need));
-        ctx->ego_pred_cap = need;
-    }
-    if ((size_t)B > ctx->ego_bc_cap) {
-        if (ctx->d_ego_bc) (void)hipFree(ctx->d_ego_bc);
-        ctx->d_ego_bc = nullptr; ctx->ego_bc_cap = 0;
-        HIP_TRY(ctx, hipMalloc(&ctx->d_ego_bc, sizeof(double4) * B));
-        ctx->ego_bc_cap = B;
-    }
-    return 0;
-}
-
-static void launch_ego_predict(jsim_ctx *ctx, int B, const double *x0, const double *di_ai, int n_steps, double *pred, hipStream_t s)
-{
-    EgoPredP P = {B, n_steps, ctx->cfg.dt, ctx->cfg.L, ctx->cc0, ctx->cc1, x0, di_ai, pred, ctx->d_ego_cc, ctx->d_ego_bc};
-    hipLaunchKernelGGL(ego_predict_kernel, dim3((B + 63) / 64), dim3(64), 0, s, P);   // one wave per block: spread over the CUs
 }
 
 extern "C" int jsim_loop_predict_egos(jsim_ctx *ctx, int32_t B, const double *x0, const double *di_ai, int32_t n_steps,
@@ -2360,10 +2389,8 @@ extern "C" int jsim_loop_predict_egos(jsim_ctx *ctx, int32_t B, const double *x0
     return 0;
 }
 
-// n_ticks Jacobi ticks of interacting egos (main/scenarios/interactive_mpc.py:117-190), each as separate launches: scripted
-// obstacles get() -> their prediction -> every ego's prediction from the tick-start states -> glue per ego against the scripted
-// obstacles, then its group mates -> MPC.step -> plant, history, goal / respawn -> glue reset of respawned egos -> obstacles
-// step().  Arguments as jsim_loop_run_scenario; groups from jsim_loop_set_groups.
+// n_ticks Jacobi ticks of interacting egos (main/scenarios/interactive_mpc.py:117-190), each as separate launches
+// (run_host_ticks).  Arguments as jsim_loop_run_scenario; groups from jsim_loop_set_groups.
 extern "C" int jsim_loop_run_interacting(jsim_ctx *ctx, int32_t B, int32_t n_ticks, double *x0, const int32_t *path_id,
                                          int32_t *path_len, const double *speed, int64_t *target_ind, double *oa, double *od,
                                          double *ox, double *oy, double *ov, double *oyaw, double *xref, uint32_t *active_mask,
@@ -2374,62 +2401,27 @@ extern "C" int jsim_loop_run_interacting(jsim_ctx *ctx, int32_t B, int32_t n_tic
                                          int32_t n_obs, double *obs_state, const double *obs_param, double *obs_get,
                                          int32_t n_steps, int32_t speed_cutoff, void *stream)
 {
-    if (!ctx) return fail(nullptr, -22, "jsim_loop_run_interacting: null ctx");
+    const char *const F = "jsim_loop_run_interacting";
+    if (!ctx) return fail(nullptr, -22, "%s: null ctx", F);
     DeviceGuard dev_guard(ctx->device);
     JSIM_GUARD_OK(ctx);
-    if (B < 0 || n_ticks < 0 || frame_window < 0 || frame_window > 32 || margin < 0)
-        return fail(ctx, -22, "jsim_loop_run_interacting: bad argument");
-    if (speed_cutoff) return fail(ctx, -22, "jsim_loop_run_interacting: only the truncate glue is supported (speed_cutoff = 1)");
+    if (B < 0 || n_ticks < 0 || frame_window < 0 || frame_window > 32 || margin < 0) return fail(ctx, -22, "%s: bad argument", F);
+    if (speed_cutoff) return fail(ctx, -22, "%s: only the truncate glue is supported (speed_cutoff = 1)", F);
     if (ctx->have_ogeom)
-        return fail(ctx, -22, "jsim_loop_run_interacting: egos cannot be mixed with obstacles of another shape "
-                              "(jsim_loop_set_obstacle_geometry has been called)");
-    if (ctx->n_groups == 0 || ctx->group_B != B)
-        return fail(ctx, -22, "jsim_loop_run_interacting: no groups set for B=%d (jsim_loop_set_groups)", B);
+        return fail(ctx, -22, "%s: egos cannot be mixed with obstacles of another shape (jsim_loop_set_obstacle_geometry has been called)", F);
+    if (ctx->n_groups == 0 || ctx->group_B != B) return fail(ctx, -22, "%s: no groups set for B=%d (jsim_loop_set_groups)", F, B);
     if (n_obs < 0 || n_steps < 1 || n_steps > JSIM_MAX_PRED || n_obs + ctx->group_max - 1 > JSIM_MAX_OBS)
-        return fail(ctx, -22, "jsim_loop_run_interacting: n_obs=%d + largest group %d - 1 > %d, or n_steps=%d (max %d)", n_obs,
-                    ctx->group_max, JSIM_MAX_OBS, n_steps, JSIM_MAX_PRED);
+        return fail(ctx, -22, "%s: n_obs=%d + largest group %d - 1 > %d, or n_steps=%d (max %d)", F, n_obs, ctx->group_max,
+                    JSIM_MAX_OBS, n_steps, JSIM_MAX_PRED);
     if (B == 0 || n_ticks == 0) return 0;
-    if (!x0 || !path_id || !path_len || !speed || !target_ind || !oa || !od || !status || !di_ai || !x0_spawn || !target_spawn ||
-        !age || !traj_idx || !prev_path_len || !col_flag || !pre_status)
-        return fail(ctx, -22, "jsim_loop_run_interacting: a required device pointer is null");
-    if (n_obs > 0 && (!obs_state || !obs_param || !obs_get)) return fail(ctx, -22, "jsim_loop_run_interacting: null obstacle pointer");
-    if (hist && !tick) return fail(ctx, -22, "jsim_loop_run_interacting: hist needs a device tick counter");
-    if (!ctx->d_pxy || !ctx->d_pcc || !ctx->have_geom) return fail(ctx, -22, "jsim_loop_run_interacting: paths / geometry not set");
+    const StepBufs S = {x0, path_id, path_len, speed, target_ind, oa, od, ox, oy, ov, oyaw, xref, active_mask, status, n_iter};
+    const AdvanceBufs A = {di_ai, x0_spawn, target_spawn, age, max_age, hist, tick, hist_cap, n_respawn};
+    const GlueBufs G = {traj_idx, prev_path_len, col_flag, pre_status, frame_window, margin, n_obs, obs_state, obs_param, obs_get,
+                        n_steps, speed_cutoff};
+    if (int rc = check_step(ctx, F, S)) return rc;
+    if (int rc = check_advance(ctx, F, A)) return rc;
+    if (int rc = check_glue(ctx, F, G)) return rc;
     if (int rc = ensure_ego_pred(ctx, B, n_steps)) return rc;
-    const jsim_cfg &c = ctx->cfg;
-    hipStream_t s = (hipStream_t)stream;
-    PreP P;
-    memset(&P, 0, sizeof(P));
-    P.B = B; P.n_obs = n_obs; P.n_steps = n_steps; P.frame_window = frame_window; P.margin = margin;
-    P.dt = c.dt; P.max_accel = c.max_accel; P.max_speed = c.max_speed; P.thr = ctx->col_radius + ctx->ocol_radius;
-    P.thr_sq = jsim_sqrt_threshold(P.thr);
-    P.pxy = ctx->d_pxy; P.pcc = ctx->d_pcc; P.poff = ctx->d_poff; P.pred_cc = ctx->d_pred_cc; P.pred_bc = ctx->d_pred_bc;
-    P.x0 = x0; P.path_id = path_id; P.traj_idx = (long long *)traj_idx; P.prev_path_len = prev_path_len; P.path_len = path_len;
-    P.col_flag = col_flag; P.status = pre_status;
-    const GroupP G = {ctx->d_group_of, ctx->d_group_off, ctx->d_ego_cc, ctx->d_ego_bc, n_obs};
-    for (int k = 0; k < n_ticks; ++k) {
-        int rc = jsim_loop_obstacles(ctx, n_obs, obs_state, obs_param, obs_get, 0, stream);
-        if (rc) return rc;
-        ctx->pred_n_obs = n_obs; ctx->pred_n_steps = n_steps;
-        if (n_obs > 0) {
-            ObsP OP = {n_obs, n_steps, c.dt, ctx->oL, ctx->occ0, ctx->occ1, obs_get, nullptr, ctx->d_pred_cc, ctx->d_pred_bc};
-            hipLaunchKernelGGL(obstacle_predict_kernel, dim3(1), dim3(64), 0, s, OP);
-        }
-        launch_ego_predict(ctx, B, x0, di_ai, n_steps, nullptr, s);
-        hipLaunchKernelGGL(group_pre_tick_kernel, dim3(B), dim3(64), 0, s, P, G);
-        HIP_TRY(ctx, hipGetLastError());
-        HIP_TRY(ctx, hipMemcpyAsync(prev_path_len, path_len, sizeof(int32_t) * B, hipMemcpyDeviceToDevice, s));
-        rc = launch_step(ctx, B, x0, path_id, path_len, speed, target_ind, oa, od, ox, oy, ov, oyaw, xref, active_mask, status,
-                         n_iter, nullptr, nullptr, nullptr, nullptr, nullptr, stream);
-        if (rc) return rc;
-        rc = jsim_loop_advance(ctx, B, x0, oa, od, status, di_ai, target_ind, path_id, path_len, x0_spawn, target_spawn, age,
-                               max_age, hist, tick, hist_cap, n_respawn, stream);
-        if (rc) return rc;
-        hipLaunchKernelGGL(glue_reset_kernel, dim3((B + 255) / 256), dim3(256), 0, s, B, age, (long long *)traj_idx, prev_path_len);
-        rc = jsim_loop_obstacles(ctx, n_obs, obs_state, obs_param, obs_get, 1, stream);
-        if (rc) return rc;
-    }
-    HIP_TRY(ctx, hipGetLastError());
-    return 0;
+    return run_host_ticks(ctx, B, n_ticks, S, A, &G, Glue::interacting, (hipStream_t)stream);
 }
 #endif /* !JSIM_KERNEL_TU */
