@@ -220,20 +220,77 @@ class ScriptedObstacles:
         return self.get_buf[: self.n]
 
 
+MAX_OBS = 8            # JSIM_MAX_OBS: obstacles one ego's glue can hold (scripted vehicles, then group mates)
+
+
+def traffic_layout(B: int, sets, traffic_of, group_off=None):
+    """The traffic-set layout of jsim_loop_set_traffic as (set_of [B], obs_off [n_sets + 1]), int32 host arrays.  sets: a list of
+    per-set spec lists (0..8 vehicles each, ScriptedObstacles' dicts); traffic_of: the set of every ego ([B]), or with group_off
+    ([n_groups + 1], InteractingLoop) the set of every group, expanded to its egos.  Raises ValueError on a wrong length, a set
+    index out of range, a set of more than 8 vehicles, or (groups) a set's vehicles + the group mates exceeding 8."""
+    sets = [list(st) for st in sets]
+    if not sets:
+        raise ValueError("need at least one traffic set")
+    sizes = np.array([len(st) for st in sets], dtype=np.int64)
+    if sizes.max() > MAX_OBS:
+        raise ValueError(f"traffic set {int(sizes.argmax())} has {int(sizes.max())} vehicles (max {MAX_OBS})")
+    tof = np.asarray(traffic_of).reshape(-1)
+    n_units = B if group_off is None else len(group_off) - 1
+    if tof.size != n_units or (tof.size and not np.issubdtype(tof.dtype, np.integer)):
+        raise ValueError(f"traffic_of must hold {n_units} set indices ({'one per group' if group_off is not None else 'one per ego'}), "
+                         f"got {tof.size}")
+    if tof.size and (tof.min() < 0 or tof.max() >= len(sets)):
+        raise ValueError(f"traffic_of holds set indices {tof.min()}..{tof.max()}, but there are {len(sets)} sets")
+    if group_off is not None:
+        gs = np.diff(np.asarray(group_off))
+        over = sizes[tof] + gs - 1 > MAX_OBS
+        if over.any():
+            g = int(np.argmax(over))
+            raise ValueError(f"group {g}: {int(sizes[tof[g]])} vehicles of set {int(tof[g])} + {int(gs[g]) - 1} group mates > {MAX_OBS}")
+        tof = np.repeat(tof, gs)
+    obs_off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)
+    return tof.astype(np.int32), obs_off
+
+
+def _register_traffic(engine: BatchedMPC, set_of, obs_off, chunk_ticks: int = 0):
+    """jsim_loop_set_traffic (set_of None: clear the context's layout)."""
+    if set_of is None:
+        _cabi.check(engine.lib.jsim_loop_set_traffic(engine._ctx, engine.B, 0, None, None, 0), engine._ctx, "jsim_loop_set_traffic")
+        engine.traffic_layout = None
+        return
+    _cabi.check(engine.lib.jsim_loop_set_traffic(engine._ctx, engine.B, len(obs_off) - 1, set_of.ctypes.data_as(C.c_void_p),
+                                                 obs_off.ctypes.data_as(C.c_void_p), int(chunk_ticks)), engine._ctx,
+                "jsim_loop_set_traffic")
+    engine.traffic_layout = (set_of, obs_off)
+
+
 class ScenarioLoop:
     """The reference scenario loop for a batch, entirely on the device (main/scenarios/mpc_intersection.py:99-163):
     obstacle get() -> prediction -> progress index / resample / collision / cut-off -> MPC.step -> plant, history, goal ->
-    obstacle step()."""
+    obstacle step().
+
+    traffic_of ([B] set indices): every ego meets its own scripted vehicles -- obstacle_specs is then a list of traffic sets
+    (per-set spec lists, traffic_layout), all of whose vehicles step every tick; ego e's results are those of a ScenarioLoop
+    whose obstacle_specs are set traffic_of[e], bit for bit.  chunk_ticks: ticks per fused launch (0: from a 512 MiB budget)."""
 
     _ENTRY = "jsim_loop_run_scenario"
 
     def __init__(self, engine: BatchedMPC, x0: torch.Tensor, obstacle_specs, hist_cap: int = 0, max_age: int = 0,
-                 frame_window: int = 10, mode: str = "truncate"):
+                 frame_window: int = 10, mode: str = "truncate", traffic_of=None, chunk_ticks: int = 0):
+        layout = None
+        if traffic_of is not None:
+            layout = traffic_layout(engine.B, obstacle_specs, traffic_of)         # before any device work
+            obstacle_specs = [sp for st in obstacle_specs for sp in st]
         self.loop = ClosedLoop(engine, x0, hist_cap=hist_cap, max_age=max_age)
         self.pre = PreTick(engine, frame_window=frame_window, mode=mode)
         self.obst = ScriptedObstacles(engine, obstacle_specs)
+        self.traffic = layout
+        _register_traffic(engine, *(layout if layout else (None, None)), chunk_ticks)
 
     def tick(self):
+        if self.traffic is not None:             # the vehicles of all sets: the gridded kernels of run()
+            self.run(1)
+            return
         g = self.obst.get(step=False)
         self.pre.predict(g)
         self.pre.run(self.loop.x0)
@@ -257,7 +314,7 @@ class ScenarioLoop:
         pre.n_obs = ob.n
 
 
-MAX_GROUP = 8          # JSIM_MAX_OBS: the obstacles of an ego are the scripted ones plus its group mates
+MAX_GROUP = MAX_OBS    # the obstacles of an ego are the scripted ones plus its group mates
 
 
 def group_offsets(B: int, group_off=None, group_sizes=None) -> np.ndarray:
@@ -289,24 +346,33 @@ class InteractingLoop:
     it applied last tick.  A tick is a Jacobi step: all egos solve, then all advance.  Groups are contiguous batch ranges
     (group_off [n_groups + 1], or group_sizes), 1..8 egos each; n_obs + largest group - 1 <= 8.  Egos in different groups
     never affect each other; a group of one ego is ScenarioLoop.  Only the truncate glue, only obstacles of the ego's shape.
-    run(n_ticks): n_ticks ticks in one call (jsim_loop_run_interacting; separate launches per tick)."""
+    run(n_ticks): n_ticks ticks in one call (jsim_loop_run_interacting; separate launches per tick).
+    traffic_of ([n_groups] set indices): every group meets its own scripted vehicles -- obstacle_specs is then a list of traffic
+    sets (traffic_layout); the vehicles of a group's set + the group - 1 <= 8, per group."""
 
     _ENTRY = "jsim_loop_run_interacting"
     run = ScenarioLoop.run
 
     def __init__(self, engine: BatchedMPC, x0: torch.Tensor, group_off=None, obstacle_specs=(), hist_cap: int = 0,
-                 max_age: int = 0, frame_window: int = 20, group_sizes=None):
+                 max_age: int = 0, frame_window: int = 20, group_sizes=None, traffic_of=None):
         off = group_offsets(engine.B, group_off, group_sizes)        # before any device work
-        n_obs = len(obstacle_specs)
-        if n_obs + int(np.diff(off).max()) - 1 > MAX_GROUP:
-            raise ValueError(f"{n_obs} scripted obstacles + the largest group ({int(np.diff(off).max())}) - 1 > {MAX_GROUP}")
+        layout = None
+        if traffic_of is not None:
+            layout = traffic_layout(engine.B, obstacle_specs, traffic_of, group_off=off)
+            obstacle_specs = [sp for st in obstacle_specs for sp in st]
+        else:
+            n_obs = len(obstacle_specs)
+            if n_obs + int(np.diff(off).max()) - 1 > MAX_GROUP:
+                raise ValueError(f"{n_obs} scripted obstacles + the largest group ({int(np.diff(off).max())}) - 1 > {MAX_GROUP}")
         self.group_off = off
         self.loop = ClosedLoop(engine, x0, hist_cap=hist_cap, max_age=max_age)
         self.pre = PreTick(engine, frame_window=frame_window)
         self.obst = ScriptedObstacles(engine, list(obstacle_specs))
+        self.traffic = layout
         eng = engine
         _cabi.check(eng.lib.jsim_loop_set_groups(eng._ctx, eng.B, len(off) - 1, off.ctypes.data_as(C.c_void_p)), eng._ctx,
                     "jsim_loop_set_groups")
+        _register_traffic(engine, *(layout if layout else (None, None)))
 
     def pred_egos(self) -> torch.Tensor:
         """[B, n_steps, 3] (x, y, yaw): every ego's prediction from its current state, as the next tick will make it."""

@@ -1305,7 +1305,12 @@ struct jsim_ctx {
     int pred_n_obs = 0, pred_n_steps = 0;
     // interacting egos (jsim_loop_set_groups, jsim_loop_run_interacting): groups and the egos' own predictions
     DevArray<int> d_group_of, d_group_off; // [group_B], [n_groups + 1]
+    std::vector<int> h_group_off;          // host copy (the traffic checks of jsim_loop_run_interacting)
     int group_B = 0, n_groups = 0, group_max = 0;
+    // traffic sets (jsim_loop_set_traffic): ego -> set, set -> its vehicles in the [total] obstacle tables; host copies to validate
+    DevArray<int> d_set_of, d_obs_off;     // [traffic_B], [n_sets + 1]
+    std::vector<int> h_set_of, h_obs_off;
+    int traffic_B = 0, n_sets = 0, traffic_chunk = 0; // traffic_chunk: ticks per fused launch, 0 = from JSIM_TRAFFIC_BUDGET
     DevArray<double2> d_ego_cc;    // [B][n_steps][2]
     DevArray<double4> d_ego_bc;    // [B]
     DevArray<double> d_pcv;        // speed reference per path point (mpc_with_speed variant) or NULL
@@ -2056,6 +2061,21 @@ static void launch_obstacle_predict(const jsim_ctx *ctx, int n_obs, int n_steps,
     hipLaunchKernelGGL(obstacle_predict_kernel, dim3(n_ticks), dim3(64), 0, s, P);
 }
 
+// obstacle_predict_grid_kernel: every (tick, vehicle) of the n_obs vehicles of all traffic sets, n_ticks consecutive ticks
+static void launch_obstacle_predict_grid(const jsim_ctx *ctx, int n_obs, int n_steps, const double *get, double2 *pred_cc,
+                                         double4 *pred_bc, int n_ticks, hipStream_t s)
+{
+    const ObsP P = {n_obs, n_steps, ctx->cfg.dt, ctx->oL, ctx->occ0, ctx->occ1, get, nullptr, pred_cc, pred_bc};
+    hipLaunchKernelGGL(obstacle_predict_grid_kernel, dim3((n_obs + 63) / 64, n_ticks), dim3(64), 0, s, P);
+}
+
+// the registered traffic layout as the glue kernels take it (both NULL without one)
+static TrafficP traffic_p(const jsim_ctx *ctx)
+{
+    if (ctx->n_sets == 0) return TrafficP{nullptr, nullptr};
+    return TrafficP{ctx->d_set_of, ctx->d_obs_off};
+}
+
 static ObsStepP obstacle_step_p(const jsim_ctx *ctx, int n_obs, int do_step, double *state, const double *param, double *get)
 {
     return ObsStepP{n_obs, do_step, ctx->have_ogeom ? ctx->oL : ctx->cfg.L, state, param, get};
@@ -2096,7 +2116,7 @@ extern "C" int jsim_loop_pre_tick(jsim_ctx *ctx, int32_t B, const double *x0, co
     P.x0 = x0; P.path_id = path_id; P.traj_idx = (long long *)traj_idx; P.prev_path_len = prev_path_len; P.path_len = path_len;
     P.col_flag = col_flag; P.col_xy = col_xy; P.first_idx = first_idx; P.status = status;
     P.dbg_res_idx = dbg_res_idx; P.dbg_n_res = dbg_n_res;
-    hipLaunchKernelGGL(loop_pre_tick_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, P);
+    hipLaunchKernelGGL(loop_pre_tick_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, P, TrafficP{});
     HIP_TRY(ctx, hipGetLastError());
     return 0;
 }
@@ -2196,28 +2216,39 @@ static int run_host_ticks(jsim_ctx *ctx, int B, int n_ticks, const StepBufs &S, 
     KP P = fill_kp(ctx, B, S);
     PreP Q = {};
     GroupP GP = {};
+    const TrafficP X = G ? traffic_p(ctx) : TrafficP{};
+    const bool grid = X.set_of != nullptr; // traffic sets: all sets' vehicles step and are predicted by the gridded kernels
+    if (grid) {
+        HIP_TRY(ctx, ctx->d_pred_all.reserve((size_t)std::max(G->n_obs, 1) * G->n_steps * 2));
+        HIP_TRY(ctx, ctx->d_bc_all.reserve(std::max(G->n_obs, 1)));
+    }
     if (G) {
         Q = fill_prep(ctx, B, G->n_obs, G->n_steps, G->frame_window, G->margin);
         Q.x0 = S.x0; Q.path_id = S.path_id; Q.traj_idx = (long long *)G->traj_idx; Q.prev_path_len = G->prev_path_len;
         Q.path_len = glue_out(ctx, S, *G); Q.col_flag = G->col_flag; Q.status = G->pre_status;
+        if (grid) { Q.pred_cc = ctx->d_pred_all; Q.pred_bc = ctx->d_bc_all; }
         GP = GroupP{ctx->d_group_of, ctx->d_group_off, ctx->d_ego_cc, ctx->d_ego_bc, G->n_obs};
     }
     auto obstacles = [&](int do_step) { // get(), or get() then step()
-        if (G->n_obs > 0)
-            hipLaunchKernelGGL(obstacle_step_kernel, dim3(1), dim3(64), 0, s,
-                               obstacle_step_p(ctx, G->n_obs, do_step, G->obs_state, G->obs_param, G->obs_get));
+        if (G->n_obs == 0) return;
+        const ObsStepP O = obstacle_step_p(ctx, G->n_obs, do_step, G->obs_state, G->obs_param, G->obs_get);
+        if (grid) hipLaunchKernelGGL(obstacle_step_grid_kernel, dim3((G->n_obs + 63) / 64), dim3(64), 0, s, O);
+        else hipLaunchKernelGGL(obstacle_step_kernel, dim3(1), dim3(64), 0, s, O);
     };
     for (int k = 0; k < n_ticks; ++k) {
         if (G) {
             obstacles(0);
-            ctx->pred_n_obs = G->n_obs; ctx->pred_n_steps = G->n_steps;
-            if (G->n_obs > 0)
-                launch_obstacle_predict(ctx, G->n_obs, G->n_steps, G->obs_get, nullptr, ctx->d_pred_cc, ctx->d_pred_bc, 1, s);
+            // (traffic sets: no single-tick prediction of at most JSIM_MAX_OBS obstacles is left for jsim_loop_pre_tick)
+            ctx->pred_n_obs = grid ? 0 : G->n_obs; ctx->pred_n_steps = G->n_steps;
+            if (G->n_obs > 0) {
+                if (grid) launch_obstacle_predict_grid(ctx, G->n_obs, G->n_steps, G->obs_get, ctx->d_pred_all, ctx->d_bc_all, 1, s);
+                else launch_obstacle_predict(ctx, G->n_obs, G->n_steps, G->obs_get, nullptr, ctx->d_pred_cc, ctx->d_pred_bc, 1, s);
+            }
             if (kind == Glue::interacting) {
                 launch_ego_predict(ctx, B, S.x0, A.di_ai, G->n_steps, nullptr, s);
-                hipLaunchKernelGGL(group_pre_tick_kernel, dim3(B), dim3(64), 0, s, Q, GP);
+                hipLaunchKernelGGL(group_pre_tick_kernel, dim3(B), dim3(64), 0, s, Q, GP, X);
             } else {
-                hipLaunchKernelGGL(loop_pre_tick_kernel, dim3(B), dim3(64), 0, s, Q);
+                hipLaunchKernelGGL(loop_pre_tick_kernel, dim3(B), dim3(64), 0, s, Q, X);
             }
             // the previous tmp_trajectory: the truncated path, or always the full one (mpc_intersection_new_ref.py:131)
             HIP_TRY(ctx, hipMemcpyAsync(G->prev_path_len, S.path_len, sizeof(int32_t) * B, hipMemcpyDeviceToDevice, s));
@@ -2282,9 +2313,32 @@ extern "C" int jsim_mpc_run_ticks(jsim_ctx *ctx, int32_t B, int32_t n_ticks, dou
     return launch_fused(ctx, B, n_ticks, S, A, nullptr, (hipStream_t)stream);
 }
 
+// Traffic sets: the fused scenario run lays out every tick's predictions of all sets' vehicles up front, total x n_steps x 32 B
+// per tick (plus 80 B per vehicle of get() tuples and bounding circles) -- 4096 egos x 4 vehicles x 35 steps: 19 MB a tick.  It
+// splits n_ticks into fused launches of at most this many bytes of tables each, unless jsim_loop_set_traffic forced a chunk.
+#define JSIM_TRAFFIC_BUDGET (512ull << 20)
+
+static int traffic_chunk_ticks(const jsim_ctx *ctx, int n_obs, int n_steps, int n_ticks)
+{
+    if (ctx->traffic_chunk > 0) return std::min(ctx->traffic_chunk, n_ticks);
+    const unsigned long long per_tick = (unsigned long long)std::max(n_obs, 1) * ((unsigned long long)n_steps * 32 + 32 + 48);
+    return (int)std::max(1ull, std::min((unsigned long long)n_ticks, JSIM_TRAFFIC_BUDGET / per_tick));
+}
+
+// A registered traffic layout must be the run's: the same B, and n_obs = all sets' vehicles
+static int check_traffic(jsim_ctx *ctx, const char *fn, int B, int n_obs)
+{
+    if (ctx->traffic_B != B)
+        return fail(ctx, -22, "%s: the traffic layout (jsim_loop_set_traffic) is for B=%d, not B=%d", fn, ctx->traffic_B, B);
+    if (n_obs != ctx->h_obs_off[ctx->n_sets])
+        return fail(ctx, -22, "%s: n_obs=%d, but the traffic sets hold %d vehicles", fn, n_obs, ctx->h_obs_off[ctx->n_sets]);
+    return 0;
+}
+
 // The whole scenario loop (main/scenarios/mpc_intersection.py:99-163) for n_ticks ticks.  With a one-wave register kernel and
 // one linearisation pass it is THREE launches: the scripted obstacles rolled forward n_ticks ticks (they do not depend on the
-// egos), their predictions for every tick, and the fused K-tick kernel with the loop glue inside each ego's tick loop.
+// egos), their predictions for every tick, and the fused K-tick kernel with the loop glue inside each ego's tick loop.  With
+// traffic sets, the same three by the gridded obstacle kernels, per chunk of traffic_chunk_ticks ticks.
 // Otherwise the same ticks as the separate calls a host loop would make.
 extern "C" int jsim_loop_run_scenario(jsim_ctx *ctx, int32_t B, int32_t n_ticks, double *x0, const int32_t *path_id,
                                       int32_t *path_len, const double *speed, int64_t *target_ind, double *oa, double *od,
@@ -2308,33 +2362,48 @@ extern "C" int jsim_loop_run_scenario(jsim_ctx *ctx, int32_t B, int32_t n_ticks,
                         n_steps, speed_cutoff};
     if (int rc = check_step(ctx, F, S)) return rc;
     if (int rc = check_advance(ctx, F, A)) return rc;
-    if (n_obs < 0 || n_obs > JSIM_MAX_OBS || n_steps < 1 || n_steps > JSIM_MAX_PRED)
+    const bool traffic = ctx->n_sets > 0;
+    if (n_steps < 1 || n_steps > JSIM_MAX_PRED || (traffic ? n_obs < 0 : (n_obs < 0 || n_obs > JSIM_MAX_OBS)))
         return fail(ctx, -22, "%s: n_obs=%d (max %d), n_steps=%d (max %d)", F, n_obs, JSIM_MAX_OBS, n_steps, JSIM_MAX_PRED);
+    if (traffic)
+        if (int rc = check_traffic(ctx, F, B, n_obs)) return rc;
     if (int rc = check_glue(ctx, F, G)) return rc;
     if (speed_cutoff && !ctx->cv_cut) return fail(ctx, -22, "%s: the speed-cut-off glue needs jsim_mpc_set_speed_cutoff first", F);
     hipStream_t s = (hipStream_t)stream;
     if (!fused_ticks(ctx, &G)) return run_host_ticks(ctx, B, n_ticks, S, A, &G, Glue::scripted, s);
-    // obstacles: n_ticks ticks of get() tuples, then every tick's prediction
-    const size_t obs_ticks = (size_t)n_ticks * (n_obs > 0 ? n_obs : 1);
+    // obstacles: a chunk's ticks of get() tuples, then every tick's prediction, then the chunk's fused launch; the obstacle
+    // state and obs_get carry over from chunk to chunk (without traffic sets: one chunk)
+    const int chunk = traffic ? traffic_chunk_ticks(ctx, n_obs, n_steps, n_ticks) : n_ticks;
+    const size_t obs_ticks = (size_t)chunk * (n_obs > 0 ? n_obs : 1);
     HIP_TRY(ctx, ctx->d_get_all.reserve(obs_ticks * 6));
     HIP_TRY(ctx, ctx->d_pred_all.reserve(obs_ticks * n_steps * 2));
     HIP_TRY(ctx, ctx->d_bc_all.reserve(obs_ticks));
-    if (n_obs > 0) {
-        hipLaunchKernelGGL(obstacle_rollout_kernel, dim3(1), dim3(64), 0, s, obstacle_step_p(ctx, n_obs, 1, obs_state, obs_param, nullptr),
-                           n_ticks, ctx->d_get_all);
-        launch_obstacle_predict(ctx, n_obs, n_steps, ctx->d_get_all, nullptr, ctx->d_pred_all, ctx->d_bc_all, n_ticks, s);
-        // the last get() tuples, as after n_ticks host ticks
-        HIP_TRY(ctx, hipMemcpyAsync(obs_get, ctx->d_get_all + (size_t)(n_ticks - 1) * n_obs * 6, sizeof(double) * n_obs * 6,
-                                    hipMemcpyDeviceToDevice, s));
-    }
-    ctx->pred_n_obs = n_obs; ctx->pred_n_steps = n_steps;
+    ctx->pred_n_obs = traffic ? 0 : n_obs; ctx->pred_n_steps = n_steps;
     PreK Q;
     memset(&Q, 0, sizeof(Q));
     Q.pre = fill_prep(ctx, B, n_obs, n_steps, frame_window, margin);
     Q.pred_cc_all = ctx->d_pred_all; Q.pred_bc_all = ctx->d_bc_all; Q.traj_idx = (long long *)traj_idx; Q.prev_len = prev_path_len; Q.path_len_out = path_len;
     Q.col_flag = col_flag; Q.pre_status = pre_status;
     Q.speed_cutoff = speed_cutoff ? 1 : 0; Q.cut_io = glue_out(ctx, S, G);
-    return launch_fused(ctx, B, n_ticks, S, A, &Q, s);
+    Q.traffic = traffic_p(ctx);
+    for (int k0 = 0; k0 < n_ticks; k0 += chunk) {
+        const int nk = std::min(chunk, n_ticks - k0);
+        if (n_obs > 0) {
+            const ObsStepP O = obstacle_step_p(ctx, n_obs, 1, obs_state, obs_param, nullptr);
+            if (traffic) {
+                hipLaunchKernelGGL(obstacle_rollout_grid_kernel, dim3((n_obs + 63) / 64), dim3(64), 0, s, O, nk, ctx->d_get_all);
+                launch_obstacle_predict_grid(ctx, n_obs, n_steps, ctx->d_get_all, ctx->d_pred_all, ctx->d_bc_all, nk, s);
+            } else {
+                hipLaunchKernelGGL(obstacle_rollout_kernel, dim3(1), dim3(64), 0, s, O, nk, ctx->d_get_all);
+                launch_obstacle_predict(ctx, n_obs, n_steps, ctx->d_get_all, nullptr, ctx->d_pred_all, ctx->d_bc_all, nk, s);
+            }
+            // the last get() tuples, as after nk host ticks
+            HIP_TRY(ctx, hipMemcpyAsync(obs_get, ctx->d_get_all + (size_t)(nk - 1) * n_obs * 6, sizeof(double) * n_obs * 6,
+                                        hipMemcpyDeviceToDevice, s));
+        }
+        if (int rc = launch_fused(ctx, B, nk, S, A, &Q, s)) return rc;
+    }
+    return 0;
 }
 
 // ---- Interacting egos: the obstacles of an ego are the scripted vehicles and the other egos of its group ----
@@ -2355,7 +2424,7 @@ extern "C" int jsim_loop_set_groups(jsim_ctx *ctx, int32_t B, int32_t n_groups, 
                 return fail(ctx, -22, "jsim_loop_set_groups: group %d has %d egos (1..%d)", g, n, JSIM_MAX_OBS);
         }
     }
-    ctx->d_group_of.release(); ctx->d_group_off.release();
+    ctx->d_group_of.release(); ctx->d_group_off.release(); ctx->h_group_off.clear();
     ctx->group_B = 0; ctx->n_groups = 0; ctx->group_max = 0;
     if (n_groups == 0) return 0;
     std::vector<int> of((size_t)B);
@@ -2368,7 +2437,42 @@ extern "C" int jsim_loop_set_groups(jsim_ctx *ctx, int32_t B, int32_t n_groups, 
     HIP_TRY(ctx, ctx->d_group_off.reserve(n_groups + 1));
     HIP_TRY(ctx, hipMemcpy(ctx->d_group_of, of.data(), sizeof(int) * B, hipMemcpyHostToDevice));
     HIP_TRY(ctx, hipMemcpy(ctx->d_group_off, group_off, sizeof(int) * (n_groups + 1), hipMemcpyHostToDevice));
+    ctx->h_group_off.assign(group_off, group_off + n_groups + 1);
     ctx->group_B = B; ctx->n_groups = n_groups; ctx->group_max = gmax;
+    return 0;
+}
+
+// ---- Traffic sets: each ego meets the scripted vehicles of its own set ----
+extern "C" int jsim_loop_set_traffic(jsim_ctx *ctx, int32_t B, int32_t n_sets, const int32_t *set_of, const int32_t *obs_off,
+                                     int32_t chunk_ticks)
+{
+    const char *const F = "jsim_loop_set_traffic";
+    if (!ctx) return fail(nullptr, -22, "%s: null ctx", F);
+    DeviceGuard dev_guard(ctx->device);
+    JSIM_GUARD_OK(ctx);
+    if (B < 0 || n_sets < 0 || chunk_ticks < 0) return fail(ctx, -22, "%s: B=%d n_sets=%d chunk_ticks=%d", F, B, n_sets, chunk_ticks);
+    if (n_sets > 0) {
+        if (!obs_off || (B > 0 && !set_of)) return fail(ctx, -22, "%s: null set_of / obs_off", F);
+        if (obs_off[0] != 0) return fail(ctx, -22, "%s: obs_off must start at 0 (got %d)", F, obs_off[0]);
+        for (int k = 0; k < n_sets; ++k) {
+            const long long n = (long long)obs_off[k + 1] - obs_off[k];
+            if (n < 0) return fail(ctx, -22, "%s: obs_off decreases at set %d (%d -> %d)", F, k, obs_off[k], obs_off[k + 1]);
+            if (n > JSIM_MAX_OBS) return fail(ctx, -22, "%s: set %d has %lld vehicles (max %d)", F, k, n, JSIM_MAX_OBS);
+        }
+        for (int b = 0; b < B; ++b)
+            if (set_of[b] < 0 || set_of[b] >= n_sets)
+                return fail(ctx, -22, "%s: set_of[%d] = %d is not a set (0..%d)", F, b, set_of[b], n_sets - 1);
+    }
+    ctx->d_set_of.release(); ctx->d_obs_off.release(); ctx->h_set_of.clear(); ctx->h_obs_off.clear();
+    ctx->traffic_B = 0; ctx->n_sets = 0; ctx->traffic_chunk = 0;
+    if (n_sets == 0) return 0;
+    HIP_TRY(ctx, ctx->d_set_of.reserve(std::max(B, 1)));
+    HIP_TRY(ctx, ctx->d_obs_off.reserve(n_sets + 1));
+    if (B > 0) HIP_TRY(ctx, hipMemcpy(ctx->d_set_of, set_of, sizeof(int) * B, hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemcpy(ctx->d_obs_off, obs_off, sizeof(int) * (n_sets + 1), hipMemcpyHostToDevice));
+    ctx->h_set_of.assign(set_of, set_of + B);
+    ctx->h_obs_off.assign(obs_off, obs_off + n_sets + 1);
+    ctx->traffic_B = B; ctx->n_sets = n_sets; ctx->traffic_chunk = chunk_ticks;
     return 0;
 }
 
@@ -2410,9 +2514,24 @@ extern "C" int jsim_loop_run_interacting(jsim_ctx *ctx, int32_t B, int32_t n_tic
     if (ctx->have_ogeom)
         return fail(ctx, -22, "%s: egos cannot be mixed with obstacles of another shape (jsim_loop_set_obstacle_geometry has been called)", F);
     if (ctx->n_groups == 0 || ctx->group_B != B) return fail(ctx, -22, "%s: no groups set for B=%d (jsim_loop_set_groups)", F, B);
-    if (n_obs < 0 || n_steps < 1 || n_steps > JSIM_MAX_PRED || n_obs + ctx->group_max - 1 > JSIM_MAX_OBS)
+    const bool traffic = ctx->n_sets > 0;
+    if (n_obs < 0 || n_steps < 1 || n_steps > JSIM_MAX_PRED || (!traffic && n_obs + ctx->group_max - 1 > JSIM_MAX_OBS))
         return fail(ctx, -22, "%s: n_obs=%d + largest group %d - 1 > %d, or n_steps=%d (max %d)", F, n_obs, ctx->group_max,
                     JSIM_MAX_OBS, n_steps, JSIM_MAX_PRED);
+    if (traffic) { // one set per group, and its vehicles + the group mates fit the glue's obstacle table
+        if (int rc = check_traffic(ctx, F, B, n_obs)) return rc;
+        for (int g = 0; g < ctx->n_groups; ++g) {
+            const int b0 = ctx->h_group_off[g], b1 = ctx->h_group_off[g + 1], set = ctx->h_set_of[b0];
+            for (int b = b0 + 1; b < b1; ++b)
+                if (ctx->h_set_of[b] != set)
+                    return fail(ctx, -22, "%s: group %d mixes traffic sets (ego %d: set %d, ego %d: set %d)", F, g, b0, set, b,
+                                ctx->h_set_of[b]);
+            const int n = ctx->h_obs_off[set + 1] - ctx->h_obs_off[set];
+            if (n + (b1 - b0) - 1 > JSIM_MAX_OBS)
+                return fail(ctx, -22, "%s: group %d: %d vehicles of set %d + %d group mates > %d", F, g, n, set, b1 - b0 - 1,
+                            JSIM_MAX_OBS);
+        }
+    }
     if (B == 0 || n_ticks == 0) return 0;
     const StepBufs S = {x0, path_id, path_len, speed, target_ind, oa, od, ox, oy, ov, oyaw, xref, active_mask, status, n_iter};
     const AdvanceBufs A = {di_ai, x0_spawn, target_spawn, age, max_age, hist, tick, hist_cap, n_respawn};

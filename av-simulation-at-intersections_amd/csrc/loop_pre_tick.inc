@@ -27,14 +27,14 @@ struct ObsP {
     // blockIdx.x = tick of a K-tick batch: obst, pred_cc and pred_bc advance by one tick's worth per block (pred is per call only)
 };
 
-// lib/moving_obstacles_prediction.py:21-47 (yaw uses the UPDATED speed), circle centres lib/trajectories.py:11-37
-#ifndef JSIM_KERNEL_TU /* (a kernel translation unit of the split build holds the register kernels only) */
-__global__ __launch_bounds__(64) void obstacle_predict_kernel(ObsP P)
+// lib/moving_obstacles_prediction.py:21-47 (yaw uses the UPDATED speed), circle centres lib/trajectories.py:11-37.  Obstacle o
+// of tick t: obst, pred_cc and pred_bc advance by one tick's worth (P.n_obs obstacles) per tick, pred is per call only.  The
+// body of obstacle_predict_kernel and of its gridded counterpart obstacle_predict_grid_kernel: the same arithmetic, operation
+// for operation.
+__device__ __forceinline__ void obstacle_predict_one(const ObsP &P, int o, int t)
 {
-    const int o = threadIdx.x;
-    if (o >= P.n_obs) return;
-    const double *ob = P.obst + (size_t)blockIdx.x * P.n_obs * 6;
-    double2 *pcc = P.pred_cc + (size_t)blockIdx.x * P.n_obs * P.n_steps * 2;
+    const double *ob = P.obst + (size_t)t * P.n_obs * 6;
+    double2 *pcc = P.pred_cc + (size_t)t * P.n_obs * P.n_steps * 2;
     double bx0 = INFINITY, bx1 = -INFINITY, by0 = INFINITY, by1 = -INFINITY;
     double x = ob[6 * o], y = ob[6 * o + 1], v = ob[6 * o + 2], yaw = ob[6 * o + 3];
     const double a = ob[6 * o + 4], st = ob[6 * o + 5];
@@ -62,10 +62,45 @@ __global__ __launch_bounds__(64) void obstacle_predict_kernel(ObsP P)
             const double dx = q.x - mx, dy = q.y - my;
             r = fmax(r, sqrt(dx * dx + dy * dy));
         }
-        P.pred_bc[(size_t)blockIdx.x * P.n_obs + o] = double4{mx, my, r * (1.0 + 1e-9) + 1e-9, 0.0};
+        P.pred_bc[(size_t)t * P.n_obs + o] = double4{mx, my, r * (1.0 + 1e-9) + 1e-9, 0.0};
     }
 }
+
+#ifndef JSIM_KERNEL_TU /* (a kernel translation unit of the split build holds the register kernels only) */
+// one block per tick, one thread per obstacle (n_obs <= JSIM_MAX_OBS)
+__global__ __launch_bounds__(64) void obstacle_predict_kernel(ObsP P)
+{
+    const int o = threadIdx.x;
+    if (o >= P.n_obs) return;
+    obstacle_predict_one(P, o, blockIdx.x);
+}
+
+// The vehicles of all traffic sets (jsim_loop_set_traffic), P.n_obs = their total: grid (ceil(total / 64), ticks), one thread
+// per (tick, vehicle).  Each thread is a serial chain of n_steps fp64 sin / cos, like ego_predict_kernel: one wave per block.
+__global__ __launch_bounds__(64) void obstacle_predict_grid_kernel(ObsP P)
+{
+    const int o = blockIdx.x * 64 + threadIdx.x;
+    if (o >= P.n_obs) return;
+    obstacle_predict_one(P, o, blockIdx.y);
+}
 #endif
+
+// Traffic sets (jsim_loop_set_traffic): the scripted vehicles of all sets sit in one [total] table, set s at obs_off[s] ..
+// obs_off[s + 1]; each ego reads its own set's slice.  set_of == NULL: no layout, every ego reads all n_obs vehicles.
+struct TrafficP {
+    const int *set_of;  // [B] traffic set of each ego
+    const int *obs_off; // [n_sets + 1]
+};
+
+struct ObsSlice { int first, n; };
+
+__device__ __forceinline__ ObsSlice traffic_slice(const TrafficP &X, int ego, int n_obs)
+{
+    if (!X.set_of) return ObsSlice{0, n_obs};
+    const int s = X.set_of[ego];
+    const int o0 = X.obs_off[s];
+    return ObsSlice{o0, X.obs_off[s + 1] - o0};
+}
 
 struct PreP {
     int B, n_obs, n_steps, frame_window, margin;
@@ -359,7 +394,8 @@ __device__ __forceinline__ PreOut jsim_pre_tick_ego(const PreP &P, const double2
 }
 
 #ifndef JSIM_KERNEL_TU /* (a kernel translation unit of the split build holds the register kernels only) */
-__global__ __launch_bounds__(64) void loop_pre_tick_kernel(PreP P)
+// X: the ego reads its traffic set's slice of P.pred_cc / P.pred_bc (P.n_obs = all sets' vehicles), or all of them
+__global__ __launch_bounds__(64) void loop_pre_tick_kernel(PreP P, TrafficP X)
 {
     __shared__ PreScratch W;
     const int lane = threadIdx.x;
@@ -368,8 +404,11 @@ __global__ __launch_bounds__(64) void loop_pre_tick_kernel(PreP P)
     const int pid = P.path_id[ego];
     const long long off = P.poff[pid];
     const int M = (int)(P.poff[pid + 1] - off);
-    const PreOut o = jsim_pre_tick_ego(P, P.pred_cc, P.pred_bc, W, lane, ego, off, M, P.x0[4 * ego], P.x0[4 * ego + 1], P.x0[4 * ego + 2],
-                                       P.traj_idx[ego], P.prev_path_len[ego]);
+    const ObsSlice sl = traffic_slice(X, ego, P.n_obs);
+    PreP Q = P;
+    Q.n_obs = sl.n;
+    const PreOut o = jsim_pre_tick_ego(Q, P.pred_cc + (size_t)sl.first * P.n_steps * 2, P.pred_bc + sl.first, W, lane, ego, off, M,
+                                       P.x0[4 * ego], P.x0[4 * ego + 1], P.x0[4 * ego + 2], P.traj_idx[ego], P.prev_path_len[ego]);
     if (lane != 0) return;
     P.status[ego] = o.status;
     if (o.status != JSIM_OK) return; // the reference raised: the ego's loop state stays as it was
@@ -439,13 +478,14 @@ struct GroupP {
     const int *group_off;    // [n_groups + 1]
     const double2 *ego_cc;   // [B][n_steps][2] (ego_predict_kernel)
     const double4 *ego_bc;   // [B]
-    int n_scripted;          // scripted obstacles in P.pred_cc / P.pred_bc (P.n_obs is ignored)
+    int n_scripted;          // scripted obstacles in P.pred_cc / P.pred_bc (P.n_obs is ignored); with traffic sets: all sets' vehicles
 };
 
 // loop_pre_tick_kernel for interacting egos: one wavefront per ego gathers the scripted predictions, then those of its group
-// mates in ascending batch index (skipping itself), into the LDS view jsim_pre_tick_ego reads, and runs the same glue.
+// mates in ascending batch index (skipping itself), into the LDS view jsim_pre_tick_ego reads, and runs the same glue.  The
+// scripted ones are its traffic set's (X), or all G.n_scripted without a layout.
 #ifndef JSIM_KERNEL_TU /* (a kernel translation unit of the split build holds the register kernels only) */
-__global__ __launch_bounds__(64) void group_pre_tick_kernel(PreP P, GroupP G)
+__global__ __launch_bounds__(64) void group_pre_tick_kernel(PreP P, GroupP G, TrafficP X)
 {
     __shared__ PreScratch W;
     __shared__ double4 bc[JSIM_MAX_OBS];
@@ -455,15 +495,17 @@ __global__ __launch_bounds__(64) void group_pre_tick_kernel(PreP P, GroupP G)
     if (ego >= P.B) return;
     const int g = G.group_of[ego];
     const int g0 = G.group_off[g], n_mates = G.group_off[g + 1] - g0 - 1;
-    const int ns = G.n_scripted, per = P.n_steps * 2;
-    for (int e = lane; e < ns * per; e += 64) W.occ[e] = P.pred_cc[e];
+    const ObsSlice sl = traffic_slice(X, ego, G.n_scripted);
+    const int ns = sl.n, per = P.n_steps * 2;
+    const double2 *scc = P.pred_cc + (size_t)sl.first * per;
+    for (int e = lane; e < ns * per; e += 64) W.occ[e] = scc[e];
     for (int m = 0; m < n_mates; ++m) {
         const int j = g0 + m + (g0 + m >= ego ? 1 : 0);
         const double2 *src = G.ego_cc + (size_t)j * per;
         double2 *dst = W.occ + (size_t)(ns + m) * per;
         for (int e = lane; e < per; e += 64) dst[e] = src[e];
     }
-    if (lane < ns) bc[lane] = P.pred_bc[lane];
+    if (lane < ns) bc[lane] = P.pred_bc[sl.first + lane];
     else if (lane < ns + n_mates) {
         const int m = lane - ns;
         bc[lane] = G.ego_bc[g0 + m + (g0 + m >= ego ? 1 : 0)];
@@ -575,6 +617,29 @@ __global__ __launch_bounds__(64) void obstacle_step_kernel(ObsStepP P)
 __global__ __launch_bounds__(64) void obstacle_rollout_kernel(ObsStepP P, int n_ticks, double *get_all)
 {
     const int o = threadIdx.x;
+    if (o >= P.n_obs) return;
+    for (int k = 0; k < n_ticks; ++k) {
+        ObsStepP Q = P;
+        Q.do_step = 0; Q.get = get_all + (size_t)k * P.n_obs * 6;
+        obstacle_step_one(Q, o);
+        Q.do_step = 1; Q.get = nullptr;
+        obstacle_step_one(Q, o);
+    }
+}
+
+// The gridded counterparts for the vehicles of all traffic sets (P.n_obs = their total, tens of thousands): one thread per
+// vehicle over ceil(total / 64) blocks, the same obstacle_step_one.  obstacle_step_grid_kernel is obstacle_step_kernel (one
+// get() or get() + step() per call), obstacle_rollout_grid_kernel is obstacle_rollout_kernel.
+__global__ __launch_bounds__(64) void obstacle_step_grid_kernel(ObsStepP P)
+{
+    const int o = blockIdx.x * 64 + threadIdx.x;
+    if (o >= P.n_obs) return;
+    obstacle_step_one(P, o);
+}
+
+__global__ __launch_bounds__(64) void obstacle_rollout_grid_kernel(ObsStepP P, int n_ticks, double *get_all)
+{
+    const int o = blockIdx.x * 64 + threadIdx.x;
     if (o >= P.n_obs) return;
     for (int k = 0; k < n_ticks; ++k) {
         ObsStepP Q = P;

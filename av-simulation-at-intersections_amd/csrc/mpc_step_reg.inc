@@ -251,6 +251,7 @@ struct PreK {
     int *cut_io;                //    the controller's speed cut-off [B] in/out (what jsim_mpc_set_speed_cutoff registered)
     int *col_flag;              // [B] out
     int *pre_status;            // [B] out
+    TrafficP traffic;           // traffic sets: pre.n_obs is all sets' vehicles, each ego reads its set's slice (set_of NULL: all)
 };
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -456,7 +457,10 @@ void mpc_step_reg_kernel(const KP Pin, const TickP K, const PreK Q)
     // PRE: the glue's per-ego loop state
     long long pre_idx = 0;
     int pre_prev = -1, pre_col = 0, pre_st = JSIM_OK, Mfull = 0, pre_cut = -1;
+    ObsSlice pre_obs = {0, 0};   // the ego's slice of the obstacle tables: its traffic set, or all of them
     if (PRE) {
+        pre_obs = traffic_slice(Q.traffic, ego, Q.pre.n_obs);
+        pre_obs.first = uni(pre_obs.first); pre_obs.n = uni(pre_obs.n);
         pre_idx = Q.traj_idx[ego];
         pre_prev = Q.prev_len[ego];
         Mfull = (int)(P.poff[pid + 1] - off);
@@ -545,8 +549,10 @@ void mpc_step_reg_kernel(const KP Pin, const TickP K, const PreK Q)
     LANE_FENCE();
     if (PRE) {
         PreScratch &W = *reinterpret_cast<PreScratch *>(HL);
-        const PreOut o = jsim_pre_tick_ego(Q.pre, Q.pred_cc_all + (size_t)tk * Q.pre.n_obs * Q.pre.n_steps * 2,
-                                           Q.pred_bc_all + (size_t)tk * Q.pre.n_obs, W, lane, ego,
+        PreP pre = Q.pre;
+        pre.n_obs = pre_obs.n;
+        const PreOut o = jsim_pre_tick_ego(pre, Q.pred_cc_all + ((size_t)tk * Q.pre.n_obs + pre_obs.first) * Q.pre.n_steps * 2,
+                                           Q.pred_bc_all + (size_t)tk * Q.pre.n_obs + pre_obs.first, W, lane, ego,
                                            off, Mfull, sx, sy, sv, pre_idx, pre_prev);
         pre_st = o.status;
         if (o.status == JSIM_OK) {

@@ -65,6 +65,9 @@ class CabiGather:
         if world is None:
             world = dist.get_world_size(group) if dist.is_initialized() else 1
         self.rank, self.world = int(rank), int(world)
+        if getattr(engine, "traffic_layout", None) is not None and self.world > 1:
+            raise ValueError("a traffic-set layout (ScenarioLoop / InteractingLoop traffic_of) is not sharded across ranks: "
+                             "give every rank its own engine, batch and layout")
         lib = engine.lib
         if unique_id is None:
             buf = (C.c_char * 128)()

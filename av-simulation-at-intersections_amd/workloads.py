@@ -134,3 +134,29 @@ def interacting_batch(routes, G: int, T: int, seed: int = 0) -> Tuple[S.EgoBatch
     batch = S.EgoBatch(x0=x0, path_id=path_id, path_len=path_len, target_ind=target_ind, speed=np.full(B, S.SPEED),
                        oa=np.zeros((B, T)), od=np.zeros((B, T)))
     return batch, np.full(G, 4, dtype=np.int64)
+
+
+def traffic_batch(n: int, seed: int = 0, n_sets: Optional[int] = None, vehicles: int = 4, empty: float = 0.05,
+                  roundabout: float = 0.1) -> Tuple[List[List[dict]], np.ndarray]:
+    """Traffic sets for n egos (ScenarioLoop) or n groups (InteractingLoop), drawn with `seed`: (sets, traffic_of).  n_sets sets
+    (default: one per ego or group, traffic_of = 0..n-1; otherwise traffic_of is drawn uniformly).  A set is empty with
+    probability `empty`; else, with probability `roundabout`, 2 roundabout vehicles (direction +-1, turning, 25 km/h, offset
+    in [1, 4] s: main/scenarios/mpc_roundabout.py:49-50); else `vehicles` T-intersection vehicles like OBSTACLE_SPECS: direction
+    +-1, offset in [0.5, 5] s, 20-30 km/h, turning on or off (main/scenarios/mpc_intersection.py:46-49, the offsets 2 / 4 there,
+    1 in mpc_intersection_new_ref.py)."""
+    rng = np.random.default_rng(seed)
+    m = n if n_sets is None else int(n_sets)
+    sets: List[List[dict]] = []
+    for _ in range(m):
+        u = rng.uniform()
+        if u < empty:
+            sets.append([])
+        elif u < empty + roundabout:
+            sets.append([dict(kind="roundabout", direction=d, turning=True, speed=25 / 3.6, offset=float(rng.uniform(1.0, 4.0)))
+                         for d in (1, -1)])
+        else:
+            sets.append([dict(direction=int(rng.choice((1, -1))), turning=bool(rng.integers(0, 2)),
+                              speed=float(rng.uniform(20.0, 30.0)) / 3.6, offset=float(rng.uniform(0.5, 5.0)))
+                         for _ in range(vehicles)])
+    traffic_of = np.arange(n, dtype=np.int64) if n_sets is None else rng.integers(0, m, n)
+    return sets, traffic_of

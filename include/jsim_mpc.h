@@ -220,6 +220,20 @@ int jsim_loop_run_interacting(jsim_ctx *ctx, int32_t B, int32_t n_ticks, double 
                               int32_t margin, int32_t n_obs, double *obs_state, const double *obs_param, double *obs_get,
                               int32_t n_steps, int32_t speed_cutoff, void *stream);
 
+/* ---- Traffic sets: each ego of a batch meets its own scripted vehicles (the reference's studies vary offsets, speeds, turning
+ * and kind of the traffic: main/scenarios/mpc_intersection.py, mpc_intersection_new_ref.py, mpc_roundabout.py).
+ * jsim_loop_set_traffic: set_of [B] (HOST) gives each ego its set, obs_off [n_sets + 1] (HOST) the sets' vehicles in the
+ *   obstacle tables: set s is vehicles obs_off[s] .. obs_off[s + 1] - 1, obs_off[0] = 0, non-decreasing, 0..8 per set.
+ *   n_sets = 0 clears the layout.  chunk_ticks: ticks per fused launch of jsim_loop_run_scenario, 0 = as many as fit a
+ *   512 MiB budget of precomputed predictions (total x n_steps x 32 B per tick, plus 80 B per vehicle).  Refused (-22), the
+ *   previous layout kept: set_of out of range, obs_off not starting at 0 or decreasing, a set of more than 8 vehicles.
+ *   While a layout is registered, n_obs of jsim_loop_run_scenario / jsim_loop_run_interacting is the TOTAL obs_off[n_sets]
+ *   (obs_state, obs_param, obs_get [total][4 | 8 | 6]); they refuse (-22) another B or total, and jsim_loop_run_interacting
+ *   refuses a group whose egos have different sets or whose set's vehicles + group mates exceed 8.  All vehicles of all sets
+ *   step once per tick.  Ego e's results equal those of a run in which set set_of[e] is the shared obstacles, bit for bit. */
+int jsim_loop_set_traffic(jsim_ctx *ctx, int32_t B, int32_t n_sets, const int32_t *set_of, const int32_t *obs_off,
+                          int32_t chunk_ticks);
+
 /* n_ticks consecutive closed-loop ticks, each = jsim_mpc_step followed by jsim_loop_advance, with identical results.
  * For the horizons that have the fused register-resident kernel (T = 13, 20) this is ONE launch in which every
  * wavefront runs all n_ticks for its own ego (egos are independent, so none waits for the slowest solve of a tick);
