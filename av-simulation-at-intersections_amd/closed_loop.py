@@ -4,6 +4,7 @@ bookkeeping launch per tick, nothing leaving the device between ticks."""
 from __future__ import annotations
 
 import ctypes as C
+import warnings
 from typing import Optional
 
 import numpy as np
@@ -11,17 +12,96 @@ import torch
 
 import math
 
-from . import _cabi
+from . import _cabi, history
 from .batched import BatchedMPC, _ptr
+
+
+class Recorder:
+    """The device History recorder of a loop (jsim_loop_set_recorder): every tick of every ego -- state after the plant step
+    (before a respawn), applied (delta, a), xref deviation, flags -- and the scripted vehicles' get() tuples, written by the loop's
+    kernels into [cap] tick slots (slot = the loop's device tick counter; ticks beyond cap are dropped).  The engine's context
+    holds one recorder: the one of the loop constructed last on it; an earlier one is marked `superseded` and warns when read.
+
+    histories(b): lib.simulation.History objects, one per episode of ego b; obstacle_positions(): the scripts'
+    obstacles_positions; episodes(): per-ego episode counts, lengths and ends.  These synchronise (device -> host copies)."""
+
+    def __init__(self, loop: "ClosedLoop", cap: int, n_obs: int = 0):
+        eng = loop.eng
+        if cap < 1:
+            raise ValueError("record must be a positive number of ticks")
+        self.loop, self.cap, self.n_obs = loop, int(cap), int(n_obs)
+        dev = eng.device
+        self.rec = torch.zeros(self.cap, eng.B, 7, dtype=torch.float64, device=dev)
+        self.flags = torch.zeros(self.cap, eng.B, dtype=torch.int32, device=dev)
+        # one row more than registered: the slot host ticks of ScenarioLoop write beyond cap (dropped)
+        self._obs = torch.zeros(self.cap + 1, self.n_obs, 6, dtype=torch.float64, device=dev) if self.n_obs > 0 else None
+        self.obs = self._obs[: self.cap] if self._obs is not None else None
+        self.x0_first = loop.x0.clone()
+        self.superseded = False          # set when a later loop on the same engine registers its own recorder (or none)
+        _register_recorder(eng, self)
+
+    def _record_obstacles(self, get: torch.Tensor):
+        """Host ticks of ScenarioLoop: this tick's get() tuples (ahead of step()) to the slot of the tick just advanced."""
+        k = (self.loop.tick_counter.to(torch.int64) - 1).clamp_(0, self.cap)
+        self._obs.index_copy_(0, k, get.unsqueeze(0))
+
+    @property
+    def ticks_run(self) -> int:
+        return int(self.loop.tick_counter.item())
+
+    @property
+    def overflow(self) -> bool:
+        """True once more ticks ran than the recorder holds (the later ones were dropped)."""
+        return history.recorded_ticks(self.ticks_run, self.cap)[1]
+
+    def _n(self) -> int:
+        if self.superseded:
+            warnings.warn("a later loop on this engine replaced this recorder: its records stopped at that point",
+                          RuntimeWarning, stacklevel=3)
+        n, over = history.recorded_ticks(self.ticks_run, self.cap)
+        if over:
+            warnings.warn(f"the recorder holds {self.cap} ticks, {self.ticks_run} ran: the last {self.ticks_run - self.cap} are not "
+                          "recorded", RuntimeWarning, stacklevel=3)
+        return n
+
+    def histories(self, b: int):
+        n = self._n()
+        eng = self.loop.eng
+        return history.ego_histories(self.rec[:n, b].cpu().numpy(), self.flags[:n, b].cpu().numpy(), eng.dt,
+                                     self.x0_first[b].cpu().numpy(), self.loop.x0_spawn[b].cpu().numpy())
+
+    def obstacle_positions(self):
+        n = self._n()
+        return history.obstacle_positions(self.obs[:n].cpu().numpy() if self.obs is not None else None)
+
+    def episodes(self):
+        return history.episodes(self.flags[: self._n()].cpu().numpy())
+
+
+def _register_recorder(engine: BatchedMPC, rec: Optional[Recorder]):
+    """jsim_loop_set_recorder (None: clear).  The engine keeps the registered buffers alive; the recorder it replaces is marked
+    superseded."""
+    old = getattr(engine, "_recorder", None)
+    if old is not None and old is not rec:
+        old.superseded = True
+    if rec is None:
+        _cabi.check(engine.lib.jsim_loop_set_recorder(engine._ctx, engine.B, 0, None, None, 0, None), engine._ctx,
+                    "jsim_loop_set_recorder")
+    else:
+        _cabi.check(engine.lib.jsim_loop_set_recorder(engine._ctx, engine.B, rec.cap, _ptr(rec.rec), _ptr(rec.flags), rec.n_obs,
+                                                      _ptr(rec.obs) if rec.obs is not None else None), engine._ctx,
+                    "jsim_loop_set_recorder")
+    engine._recorder = rec
 
 
 class ClosedLoop:
     """tick(): jsim_mpc_step then jsim_loop_advance (plant, history, respawn of finished egos).
 
     hist_cap: ticks of (di, ai) history kept on the device ([hist_cap, B, 2]); max_age: safety respawn
-    after that many ticks (<= 0: only MPC.is_goal ends an ego's run)."""
+    after that many ticks (<= 0: only MPC.is_goal ends an ego's run); record: ticks of the full History kept on the device
+    (`recorder`, a Recorder; 0: none)."""
 
-    def __init__(self, engine: BatchedMPC, x0: torch.Tensor, hist_cap: int = 0, max_age: int = 0):
+    def __init__(self, engine: BatchedMPC, x0: torch.Tensor, hist_cap: int = 0, max_age: int = 0, record: int = 0):
         self.eng = engine
         eng = engine
         eng._check_x0(x0)
@@ -37,6 +117,11 @@ class ClosedLoop:
         self.n_respawn = torch.zeros(1, dtype=torch.int64, device=dev)
         self._graph: Optional[torch.cuda.CUDAGraph] = None
         self._graph_ticks = 0
+        self.recorder: Optional[Recorder] = None
+        if getattr(eng, "_recorder", None) is not None:
+            _register_recorder(eng, None)            # an earlier loop's recorder on this engine stops recording
+        if record:
+            self.recorder = Recorder(self, record)
 
     def tick(self):
         eng = self.eng
@@ -271,12 +356,13 @@ class ScenarioLoop:
 
     traffic_of ([B] set indices): every ego meets its own scripted vehicles -- obstacle_specs is then a list of traffic sets
     (per-set spec lists, traffic_layout), all of whose vehicles step every tick; ego e's results are those of a ScenarioLoop
-    whose obstacle_specs are set traffic_of[e], bit for bit.  chunk_ticks: ticks per fused launch (0: from a 512 MiB budget)."""
+    whose obstacle_specs are set traffic_of[e], bit for bit.  chunk_ticks: ticks per fused launch (0: from a 512 MiB budget).
+    record: ticks of the full History kept on the device, the vehicles' get() tuples included (`recorder`; 0: none)."""
 
     _ENTRY = "jsim_loop_run_scenario"
 
     def __init__(self, engine: BatchedMPC, x0: torch.Tensor, obstacle_specs, hist_cap: int = 0, max_age: int = 0,
-                 frame_window: int = 10, mode: str = "truncate", traffic_of=None, chunk_ticks: int = 0):
+                 frame_window: int = 10, mode: str = "truncate", traffic_of=None, chunk_ticks: int = 0, record: int = 0):
         layout = None
         if traffic_of is not None:
             layout = traffic_layout(engine.B, obstacle_specs, traffic_of)         # before any device work
@@ -286,6 +372,12 @@ class ScenarioLoop:
         self.obst = ScriptedObstacles(engine, obstacle_specs)
         self.traffic = layout
         _register_traffic(engine, *(layout if layout else (None, None)), chunk_ticks)
+        if record:
+            self.loop.recorder = Recorder(self.loop, record, n_obs=self.obst.n)
+
+    @property
+    def recorder(self) -> Optional[Recorder]:
+        return self.loop.recorder
 
     def tick(self):
         if self.traffic is not None:             # the vehicles of all sets: the gridded kernels of run()
@@ -298,7 +390,10 @@ class ScenarioLoop:
         resp = self.loop.age == 0                    # respawned this tick: the glue starts over like for a new run
         self.pre.traj_idx.masked_fill_(resp, 0)
         self.pre.prev_len.masked_fill_(resp, -1)
-        self.obst.get(step=True)
+        g = self.obst.get(step=True)
+        rec = self.loop.recorder
+        if rec is not None and rec.n_obs:
+            rec._record_obstacles(g)
 
     def run(self, n_ticks: int):
         """n_ticks ticks in one call (jsim_loop_run_scenario).  With a register kernel (config.ONE_WAVE_HORIZONS / FOUR_WAVE_HORIZONS) and MAX_ITER = 1
@@ -348,13 +443,14 @@ class InteractingLoop:
     never affect each other; a group of one ego is ScenarioLoop.  Only the truncate glue, only obstacles of the ego's shape.
     run(n_ticks): n_ticks ticks in one call (jsim_loop_run_interacting; separate launches per tick).
     traffic_of ([n_groups] set indices): every group meets its own scripted vehicles -- obstacle_specs is then a list of traffic
-    sets (traffic_layout); the vehicles of a group's set + the group - 1 <= 8, per group."""
+    sets (traffic_layout); the vehicles of a group's set + the group - 1 <= 8, per group.
+    record: ticks of the full History kept on the device (`recorder`, as ScenarioLoop's); the egos are recorded like any other."""
 
     _ENTRY = "jsim_loop_run_interacting"
     run = ScenarioLoop.run
 
     def __init__(self, engine: BatchedMPC, x0: torch.Tensor, group_off=None, obstacle_specs=(), hist_cap: int = 0,
-                 max_age: int = 0, frame_window: int = 20, group_sizes=None, traffic_of=None):
+                 max_age: int = 0, frame_window: int = 20, group_sizes=None, traffic_of=None, record: int = 0):
         off = group_offsets(engine.B, group_off, group_sizes)        # before any device work
         layout = None
         if traffic_of is not None:
@@ -373,6 +469,10 @@ class InteractingLoop:
         _cabi.check(eng.lib.jsim_loop_set_groups(eng._ctx, eng.B, len(off) - 1, off.ctypes.data_as(C.c_void_p)), eng._ctx,
                     "jsim_loop_set_groups")
         _register_traffic(engine, *(layout if layout else (None, None)))
+        if record:
+            self.loop.recorder = Recorder(self.loop, record, n_obs=self.obst.n)
+
+    recorder = ScenarioLoop.recorder
 
     def pred_egos(self) -> torch.Tensor:
         """[B, n_steps, 3] (x, y, yaw): every ego's prediction from its current state, as the next tick will make it."""

@@ -109,6 +109,34 @@ __device__ __forceinline__ void jsim_apply_ego_cfg(KPT &P, const double *pe, int
     P.dmax = w[12] * dt; P.amax = w[13]; P.amin = w[14];
 }
 
+// MPC.get_current_xref_deviation (main/lib/mpc.py:305-312) from the reference point rp = (cx, cy)[target_ind], its yaw and
+// (ox[0], oy[0]).  One definition for jsim_mpc_xref_deviation_goal and the recorder: the same operations in the same order (the
+// build contracts nothing, -ffp-contract=off), so every kernel that records it gives that entry's value bit for bit.
+__device__ __forceinline__ double jsim_xref_deviation(double2 rp, double ryaw, double ox0, double oy0)
+{
+    const double yp = ryaw + M_PI / 2;
+    const double dx = rp.x - ox0, dy = rp.y - oy0;
+    const double a = cos(yp) * dx, c = sin(yp) * dy;
+    return sqrt(a * a + c * c);
+}
+
+// One History record of jsim_loop_set_recorder, written by one lane: slot k (< cap) of ego b, flags = JSIM_REC_* bits.  The
+// deviation goes first, before the plant step (the register kernels would otherwise carry it through the step's sin / cos / tan).
+template <class DP>
+__device__ __forceinline__ void jsim_rec_store_dev(DP rec, int k, int B, int b, double dev)
+{
+    rec[7 * ((size_t)k * B + b) + 6] = dev;
+}
+template <class DP, class IP>
+__device__ __forceinline__ void jsim_rec_store(DP rec, IP flags, int k, int B, int b, double x, double y, double yaw, double v,
+                                               double di, double ai, int fl)
+{
+    const size_t r = (size_t)k * B + b;
+    rec[7 * r] = x; rec[7 * r + 1] = y; rec[7 * r + 2] = yaw; rec[7 * r + 3] = v;
+    rec[7 * r + 4] = di; rec[7 * r + 5] = ai;
+    flags[r] = fl;
+}
+
 // ---------------------------------------------------------------------------------------------------
 // wave-level helpers (64 lanes)
 // ---------------------------------------------------------------------------------------------------
@@ -1162,6 +1190,14 @@ __global__ __launch_bounds__(256) void plant_step_kernel(PlantP P, double *x0, c
 // Closed-loop bookkeeping of the per-vehicle loop for a batch (main/scenarios/mpc_intersection.py:99-163):
 // (di, ai) selection + plant step as above, history record, and replacement of finished egos -- the loop's
 // `if mpc.is_goal(state): break` (:101) becomes "respawn at the ego's spawn state with a cold controller".
+// The recorder of jsim_loop_set_recorder as the kernels see it: rec == NULL records nothing.  The path yaw is for the deviation.
+struct RecP {
+    double *rec;   // [cap][B][JSIM_REC_FIELDS]
+    int *flags;    // [cap][B]
+    int cap;
+    const double *pyaw;
+};
+
 struct LoopP {
     int B, T, max_age;
     double dt, L, smax, vmax, vmin, max_decel, goal_dis, stop_speed;
@@ -1175,7 +1211,7 @@ __global__ __launch_bounds__(256) void loop_advance_kernel(LoopP P, double *x0, 
                                                            const int *path_id, const int *path_len,
                                                            const double *x0_spawn, const long long *target_spawn,
                                                            int *age, double *hist, int *tick, int hist_cap,
-                                                           unsigned long long *n_respawn)
+                                                           unsigned long long *n_respawn, RecP R)
 {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= P.B) return;
@@ -1204,7 +1240,18 @@ __global__ __launch_bounds__(256) void loop_advance_kernel(LoopP P, double *x0, 
     bool isgoal = hypot(x - g.x, y - g.y) <= P.goal_dis;
     long long df = ti - (long long)path_len[b];
     if ((df < 0 ? -df : df) >= 5) isgoal = false;
-    const bool done = (isgoal && fabs(v) <= P.stop_speed) || (age[b] + 1 >= P.max_age);
+    const bool goal = isgoal && fabs(v) <= P.stop_speed, aged = age[b] + 1 >= P.max_age;
+    const bool done = goal || aged;
+    if (R.rec) { // the History record: state after the plant step, ahead of the respawn; the solve's ox[0], oy[0] is x0's pose
+        const int k = *tick;
+        if (k < R.cap) {
+            const bool ok = status[b] == JSIM_OK;
+            jsim_rec_store_dev(R.rec, k, P.B, b,
+                               ok ? jsim_xref_deviation(P.pxy[off + ti], R.pyaw[off + ti], x0[4 * b], x0[4 * b + 1]) : __builtin_nan(""));
+            jsim_rec_store(R.rec, R.flags, k, P.B, b, x, y, th, v, di, ai,
+                           (ok ? 0 : JSIM_REC_FAILED) | (goal ? JSIM_REC_GOAL : 0) | (aged ? JSIM_REC_AGE : 0));
+        }
+    }
     if (done) {
         x = x0_spawn[4 * b]; y = x0_spawn[4 * b + 1]; v = x0_spawn[4 * b + 2]; th = x0_spawn[4 * b + 3];
         target_ind[b] = target_spawn[b];
@@ -1240,13 +1287,8 @@ __global__ __launch_bounds__(256) void deviation_goal_kernel(GoalP P, const doub
     const long long off = P.poff[path_id[b]];
     const long long full = P.poff[path_id[b] + 1] - off;
     const long long ti = target_ind[b];
-    if (deviation) {
-        const double2 rp = P.pxy[off + ti];
-        const double yp = P.pyaw[off + ti] + M_PI / 2;
-        const double dx = rp.x - ox[(size_t)b * (P.T + 1)], dy = rp.y - oy[(size_t)b * (P.T + 1)];
-        const double a = cos(yp) * dx, c = sin(yp) * dy;
-        deviation[b] = sqrt(a * a + c * c);
-    }
+    if (deviation)
+        deviation[b] = jsim_xref_deviation(P.pxy[off + ti], P.pyaw[off + ti], ox[(size_t)b * (P.T + 1)], oy[(size_t)b * (P.T + 1)]);
     if (is_goal) {
         const double2 g = P.pxy[off + full - 1]; // goal = last point of the path given to MPC.__init__
         const double d = hypot(x0[4 * b] - g.x, x0[4 * b + 1] - g.y);
@@ -1311,6 +1353,10 @@ struct jsim_ctx {
     DevArray<int> d_set_of, d_obs_off;     // [traffic_B], [n_sets + 1]
     std::vector<int> h_set_of, h_obs_off;
     int traffic_B = 0, n_sets = 0, traffic_chunk = 0; // traffic_chunk: ticks per fused launch, 0 = from JSIM_TRAFFIC_BUDGET
+    // the History recorder (jsim_loop_set_recorder): caller-owned device buffers, rec_cap = 0: none
+    double *rec = nullptr, *rec_obs = nullptr;
+    int32_t *rec_flags = nullptr;
+    int rec_B = 0, rec_cap = 0, rec_n_obs = 0;
     DevArray<double2> d_ego_cc;    // [B][n_steps][2]
     DevArray<double4> d_ego_bc;    // [B]
     DevArray<double> d_pcv;        // speed reference per path point (mpc_with_speed variant) or NULL
@@ -1517,6 +1563,18 @@ static int check_advance(jsim_ctx *ctx, const char *fn, const AdvanceBufs &A)
 {
     if (!A.di_ai || !A.x0_spawn || !A.target_spawn || !A.age) return fail(ctx, -22, "%s: a required device pointer is null", fn);
     if (A.hist && !A.tick) return fail(ctx, -22, "%s: hist needs a device tick counter", fn);
+    return 0;
+}
+
+// A registered recorder must be the run's: the same B and a device tick counter (its slots); n_obs >= 0: the run's scripted
+// vehicles, which a recorder of obstacle tuples must hold
+static int check_recorder(jsim_ctx *ctx, const char *fn, int B, const int32_t *tick, int n_obs)
+{
+    if (!ctx->rec) return 0;
+    if (ctx->rec_B != B) return fail(ctx, -22, "%s: the recorder (jsim_loop_set_recorder) is for B=%d, not B=%d", fn, ctx->rec_B, B);
+    if (!tick) return fail(ctx, -22, "%s: the recorder needs a device tick counter", fn);
+    if (n_obs >= 0 && ctx->rec_obs && ctx->rec_n_obs != n_obs)
+        return fail(ctx, -22, "%s: the recorder holds %d vehicles, the run has n_obs=%d", fn, ctx->rec_n_obs, n_obs);
     return 0;
 }
 
@@ -1750,9 +1808,10 @@ static void launch_advance(const jsim_ctx *ctx, int B, const StepBufs &S, const 
     const jsim_cfg &c = ctx->cfg;
     LoopP P = {B, c.T, A.max_age > 0 ? A.max_age : 0x7fffffff, c.dt, c.L, c.max_steer, c.max_speed, c.min_speed,
                c.max_decel, c.goal_dis, c.stop_speed, ctx->d_pxy, ctx->d_poff, ctx->d_pe};
+    const RecP R = {ctx->rec, ctx->rec_flags, ctx->rec_cap, ctx->d_pyaw};
     hipLaunchKernelGGL(loop_advance_kernel, dim3((B + 255) / 256), dim3(256), 0, s, P, S.x0, S.oa, S.od, S.status, A.di_ai,
                        (long long *)S.target_ind, S.path_id, S.path_len, A.x0_spawn, (const long long *)A.target_spawn, A.age,
-                       A.hist, A.tick, A.hist_cap, (unsigned long long *)A.n_respawn);
+                       A.hist, A.tick, A.hist_cap, (unsigned long long *)A.n_respawn, R);
     if (A.tick) hipLaunchKernelGGL(tick_increment_kernel, dim3(1), dim3(1), 0, s, A.tick);
 }
 
@@ -1770,6 +1829,7 @@ extern "C" int jsim_loop_advance(jsim_ctx *ctx, int32_t B, double *x0, double *o
         return fail(ctx, -22, "jsim_loop_advance: a required device pointer is null");
     const AdvanceBufs A = {di_ai, x0_spawn, target_spawn, age, max_age, hist, tick, hist_cap, n_respawn};
     if (int rc = check_advance(ctx, "jsim_loop_advance", A)) return rc;
+    if (int rc = check_recorder(ctx, "jsim_loop_advance", B, tick, -1)) return rc;
     if (!ctx->d_pxy) return fail(ctx, -22, "jsim_loop_advance: no paths set");
     StepBufs S = {}; // (the advance reads status)
     S.x0 = x0; S.path_id = path_id; S.path_len = path_len; S.target_ind = target_ind; S.oa = oa; S.od = od;
@@ -2078,7 +2138,16 @@ static TrafficP traffic_p(const jsim_ctx *ctx)
 
 static ObsStepP obstacle_step_p(const jsim_ctx *ctx, int n_obs, int do_step, double *state, const double *param, double *get)
 {
-    return ObsStepP{n_obs, do_step, ctx->have_ogeom ? ctx->oL : ctx->cfg.L, state, param, get};
+    return ObsStepP{n_obs, do_step, ctx->have_ogeom ? ctx->oL : ctx->cfg.L, state, param, get, nullptr, nullptr, 0};
+}
+
+// the same, with the recorder's obstacle tuples (when one is registered) at the slots of the device tick counter
+static ObsStepP obstacle_step_rec_p(const jsim_ctx *ctx, int n_obs, int do_step, double *state, const double *param, double *get,
+                                    const int32_t *tick)
+{
+    ObsStepP O = obstacle_step_p(ctx, n_obs, do_step, state, param, get);
+    if (ctx->rec_obs) { O.rec = ctx->rec_obs; O.tick = tick; O.rec_cap = ctx->rec_cap; }
+    return O;
 }
 
 extern "C" int jsim_loop_predict_obstacles(jsim_ctx *ctx, int32_t n_obs, const double *obst, int32_t n_steps, double *pred,
@@ -2231,7 +2300,7 @@ static int run_host_ticks(jsim_ctx *ctx, int B, int n_ticks, const StepBufs &S, 
     }
     auto obstacles = [&](int do_step) { // get(), or get() then step()
         if (G->n_obs == 0) return;
-        const ObsStepP O = obstacle_step_p(ctx, G->n_obs, do_step, G->obs_state, G->obs_param, G->obs_get);
+        const ObsStepP O = obstacle_step_rec_p(ctx, G->n_obs, do_step, G->obs_state, G->obs_param, G->obs_get, A.tick);
         if (grid) hipLaunchKernelGGL(obstacle_step_grid_kernel, dim3((G->n_obs + 63) / 64), dim3(64), 0, s, O);
         else hipLaunchKernelGGL(obstacle_step_kernel, dim3(1), dim3(64), 0, s, O);
     };
@@ -2284,6 +2353,7 @@ static int launch_fused(jsim_ctx *ctx, int B, int n_ticks, const StepBufs &S, co
     K.max_decel = c.max_decel; K.goal_dis = c.goal_dis; K.stop_speed = c.stop_speed;
     K.x0w = S.x0; K.di_ai = A.di_ai; K.x0_spawn = A.x0_spawn; K.target_spawn = (const long long *)A.target_spawn; K.age = A.age;
     K.hist = A.hist; K.tick = A.tick; K.n_respawn = (unsigned long long *)A.n_respawn;
+    K.rec = ctx->rec; K.rec_flags = ctx->rec_flags; K.rec_cap = ctx->rec_cap;
     if (int rc = prepare_launch_order(ctx, B, s, K)) return rc;
     if (int rc = prepare_iter_totals(ctx, B, s, K)) return rc;
     launch_reg(c.T, B, s, P, K, Q);
@@ -2309,6 +2379,7 @@ extern "C" int jsim_mpc_run_ticks(jsim_ctx *ctx, int32_t B, int32_t n_ticks, dou
     const AdvanceBufs A = {di_ai, x0_spawn, target_spawn, age, max_age, hist, tick, hist_cap, n_respawn};
     if (int rc = check_step(ctx, F, S)) return rc;
     if (int rc = check_advance(ctx, F, A)) return rc;
+    if (int rc = check_recorder(ctx, F, B, tick, -1)) return rc;
     if (!fused_ticks(ctx, nullptr)) return run_host_ticks(ctx, B, n_ticks, S, A, nullptr, Glue::none, (hipStream_t)stream);
     return launch_fused(ctx, B, n_ticks, S, A, nullptr, (hipStream_t)stream);
 }
@@ -2362,6 +2433,7 @@ extern "C" int jsim_loop_run_scenario(jsim_ctx *ctx, int32_t B, int32_t n_ticks,
                         n_steps, speed_cutoff};
     if (int rc = check_step(ctx, F, S)) return rc;
     if (int rc = check_advance(ctx, F, A)) return rc;
+    if (int rc = check_recorder(ctx, F, B, tick, n_obs)) return rc;
     const bool traffic = ctx->n_sets > 0;
     if (n_steps < 1 || n_steps > JSIM_MAX_PRED || (traffic ? n_obs < 0 : (n_obs < 0 || n_obs > JSIM_MAX_OBS)))
         return fail(ctx, -22, "%s: n_obs=%d (max %d), n_steps=%d (max %d)", F, n_obs, JSIM_MAX_OBS, n_steps, JSIM_MAX_PRED);
@@ -2389,7 +2461,7 @@ extern "C" int jsim_loop_run_scenario(jsim_ctx *ctx, int32_t B, int32_t n_ticks,
     for (int k0 = 0; k0 < n_ticks; k0 += chunk) {
         const int nk = std::min(chunk, n_ticks - k0);
         if (n_obs > 0) {
-            const ObsStepP O = obstacle_step_p(ctx, n_obs, 1, obs_state, obs_param, nullptr);
+            const ObsStepP O = obstacle_step_rec_p(ctx, n_obs, 1, obs_state, obs_param, nullptr, tick);
             if (traffic) {
                 hipLaunchKernelGGL(obstacle_rollout_grid_kernel, dim3((n_obs + 63) / 64), dim3(64), 0, s, O, nk, ctx->d_get_all);
                 launch_obstacle_predict_grid(ctx, n_obs, n_steps, ctx->d_get_all, ctx->d_pred_all, ctx->d_bc_all, nk, s);
@@ -2476,6 +2548,26 @@ extern "C" int jsim_loop_set_traffic(jsim_ctx *ctx, int32_t B, int32_t n_sets, c
     return 0;
 }
 
+// ---- The History recorder: the loop entry points write each ego's per-tick record where the state lives ----
+extern "C" int jsim_loop_set_recorder(jsim_ctx *ctx, int32_t B, int32_t cap, double *rec, int32_t *flags, int32_t n_obs,
+                                      double *obs_rec)
+{
+    const char *const F = "jsim_loop_set_recorder";
+    // (the argument checks come first: they need no context and no device)
+    if (B < 0 || cap < 0 || n_obs < 0) return fail(ctx, -22, "%s: B=%d cap=%d n_obs=%d", F, B, cap, n_obs);
+    if (cap > 0 && (!rec || !flags)) return fail(ctx, -22, "%s: cap=%d needs the rec and flags buffers", F, cap);
+    if (!ctx) return fail(nullptr, -22, "%s: null ctx", F);
+    if (n_obs == 0) obs_rec = nullptr; // (no vehicles recorded)
+    if (cap > 0 && obs_rec && ctx->n_sets > 0 && n_obs != ctx->h_obs_off[ctx->n_sets])
+        return fail(ctx, -22, "%s: n_obs=%d, but the traffic sets hold %d vehicles", F, n_obs, ctx->h_obs_off[ctx->n_sets]);
+    ctx->rec = nullptr; ctx->rec_flags = nullptr; ctx->rec_obs = nullptr;
+    ctx->rec_B = 0; ctx->rec_cap = 0; ctx->rec_n_obs = 0;
+    if (cap == 0) return 0;
+    ctx->rec = rec; ctx->rec_flags = flags; ctx->rec_cap = cap; ctx->rec_B = B;
+    if (obs_rec) { ctx->rec_obs = obs_rec; ctx->rec_n_obs = n_obs; }
+    return 0;
+}
+
 extern "C" int jsim_loop_predict_egos(jsim_ctx *ctx, int32_t B, const double *x0, const double *di_ai, int32_t n_steps,
                                       double *pred, void *stream)
 {
@@ -2539,6 +2631,7 @@ extern "C" int jsim_loop_run_interacting(jsim_ctx *ctx, int32_t B, int32_t n_tic
                         n_steps, speed_cutoff};
     if (int rc = check_step(ctx, F, S)) return rc;
     if (int rc = check_advance(ctx, F, A)) return rc;
+    if (int rc = check_recorder(ctx, F, B, tick, n_obs)) return rc;
     if (int rc = check_glue(ctx, F, G)) return rc;
     if (int rc = ensure_ego_pred(ctx, B, n_steps)) return rc;
     return run_host_ticks(ctx, B, n_ticks, S, A, &G, Glue::interacting, (hipStream_t)stream);

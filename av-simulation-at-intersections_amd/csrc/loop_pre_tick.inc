@@ -541,6 +541,11 @@ struct ObsStepP {
     double *state;        // [n_obs][4]  xc, yc, theta, counter
     const double *param;  // [n_obs][8]  direction (+-1), turning (0/1), speed, offset (<= 0: none), x_turn, dt, kind, initial_speed
     double *get;          // [n_obs][6]  x, y, v, yaw, a, steer  (state BEFORE the step, like o.get() ahead of o.step())
+    // the recorder (jsim_loop_set_recorder), NULL: none -- the get() tuples ahead of each step() go to rec [rec_cap][n_obs][6],
+    // slot = the device tick counter (+ the tick of a rollout), as the scripts' obstacles_positions keep them
+    double *rec;
+    const int *tick;
+    int rec_cap;
 };
 
 __device__ __forceinline__ double obstacle_steer(double dir, double turning, double xc, double theta, double x_turn)
@@ -602,12 +607,31 @@ __device__ __forceinline__ void obstacle_step_one(const ObsStepP &P, int o)
     P.state[4 * o + 2] = th; // also without a step: the roundabout rule may have rewritten the heading
 }
 
+// The recorder's slot of the tick dk ticks after the counter's, or NULL (no recorder, or beyond its capacity)
+__device__ __forceinline__ double *obstacle_rec_slot(const ObsStepP &P, int dk)
+{
+    if (!P.rec) return nullptr;
+    const int k = *P.tick + dk;
+    return (k >= 0 && k < P.rec_cap) ? P.rec + (size_t)k * P.n_obs * 6 : nullptr;
+}
+
+// a host tick's get() + step() call, the last launch of the tick: its get() tuple to the recorder's slot of the tick (the
+// advance has already counted it)
+__device__ __forceinline__ void obstacle_record(const ObsStepP &P, int o)
+{
+    if (!P.do_step || !P.get) return;
+    double *r = obstacle_rec_slot(P, -1);
+    if (r)
+        for (int j = 0; j < 6; ++j) r[6 * o + j] = P.get[6 * o + j];
+}
+
 #ifndef JSIM_KERNEL_TU /* (a kernel translation unit of the split build holds the register kernels only) */
 __global__ __launch_bounds__(64) void obstacle_step_kernel(ObsStepP P)
 {
     const int o = threadIdx.x;
     if (o >= P.n_obs) return;
     obstacle_step_one(P, o);
+    obstacle_record(P, o);
 }
 #endif
 
@@ -622,7 +646,7 @@ __global__ __launch_bounds__(64) void obstacle_rollout_kernel(ObsStepP P, int n_
         ObsStepP Q = P;
         Q.do_step = 0; Q.get = get_all + (size_t)k * P.n_obs * 6;
         obstacle_step_one(Q, o);
-        Q.do_step = 1; Q.get = nullptr;
+        Q.do_step = 1; Q.get = obstacle_rec_slot(P, k);
         obstacle_step_one(Q, o);
     }
 }
@@ -635,6 +659,7 @@ __global__ __launch_bounds__(64) void obstacle_step_grid_kernel(ObsStepP P)
     const int o = blockIdx.x * 64 + threadIdx.x;
     if (o >= P.n_obs) return;
     obstacle_step_one(P, o);
+    obstacle_record(P, o);
 }
 
 __global__ __launch_bounds__(64) void obstacle_rollout_grid_kernel(ObsStepP P, int n_ticks, double *get_all)
@@ -645,7 +670,7 @@ __global__ __launch_bounds__(64) void obstacle_rollout_grid_kernel(ObsStepP P, i
         ObsStepP Q = P;
         Q.do_step = 0; Q.get = get_all + (size_t)k * P.n_obs * 6;
         obstacle_step_one(Q, o);
-        Q.do_step = 1; Q.get = nullptr;
+        Q.do_step = 1; Q.get = obstacle_rec_slot(P, k);
         obstacle_step_one(Q, o);
     }
 }

@@ -197,7 +197,7 @@ __host__ __device__ static inline size_t jsim_reg_lds_doubles(int T)
 // respawn }.  Egos never wait for each other, the controller state (pose, remembered path index, warm start,
 // previous steer) stays in registers between ticks.  n_ticks = 1 with advance = 0 is the plain MPC.step.
 struct TickP {
-    int n_ticks, advance, max_age, hist_cap;
+    int n_ticks, advance, max_age, hist_cap, rec_cap;
     double max_decel, goal_dis, stop_speed;
     double *x0w;
     double *di_ai;
@@ -205,6 +205,8 @@ struct TickP {
     const long long *target_spawn;
     int *age;
     double *hist;
+    double *rec;   // the History recorder (jsim_loop_set_recorder): [rec_cap][B][JSIM_REC_FIELDS], flags [rec_cap][B]; NULL: none
+    int *rec_flags;
     const int *tick;
     unsigned long long *n_respawn;
     // launch order (jsim_mpc.hip, launch_order_kernel): workgroup b solves ego order[b] -- the egos that needed the most
@@ -1590,6 +1592,10 @@ void mpc_step_reg_kernel(const KP Pin, const TickP K, const PreK Q)
             const int k = hist_base + tk;
             if (k < K.hist_cap) { K.hist[((size_t)k * P.B + ego) * 2] = di; K.hist[((size_t)k * P.B + ego) * 2 + 1] = ai; }
         }
+        // the recorder's xref deviation: the solve's ox[0], oy[0] is the tick-start pose (sx, sy), target_ind is s0
+        if (K.rec && lane == 0 && *K.tick + tk < K.rec_cap) // (the counter is read where it is needed: no register holds it)
+            jsim_rec_store_dev(K.rec, *K.tick + tk, P.B, ego,
+                               status == JSIM_OK ? jsim_xref_deviation(P.pxy[off + s0], P.pyaw[off + s0], sx, sy) : __builtin_nan(""));
         // Simulation.step (main/lib/simulation.py:35-47)
         double dc = (P.smax < di) ? P.smax : di;
         dc = (-P.smax > dc) ? -P.smax : dc;
@@ -1605,6 +1611,13 @@ void mpc_step_reg_kernel(const KP Pin, const TickP K, const PreK Q)
         long long df = s0 - M;
         if ((df < 0 ? -df : df) >= 5) isgoal = false;
         const bool done = (isgoal && fabs(sv) <= K.stop_speed) || (age + 1 >= K.max_age);
+        if (K.rec && lane == 0) { // the History record: the new state ahead of the respawn
+            const int k = *K.tick + tk;
+            if (k < K.rec_cap)
+                jsim_rec_store(K.rec, K.rec_flags, k, P.B, ego, sx, sy, syaw, sv, di, ai,
+                               (status == JSIM_OK ? 0 : JSIM_REC_FAILED) | (isgoal && fabs(sv) <= K.stop_speed ? JSIM_REC_GOAL : 0) |
+                                   (age + 1 >= K.max_age ? JSIM_REC_AGE : 0));
+        }
         if (done) {
             sx = K.x0_spawn[4 * ego]; sy = K.x0_spawn[4 * ego + 1]; sv = K.x0_spawn[4 * ego + 2]; syaw = K.x0_spawn[4 * ego + 3];
             s0 = K.target_spawn[ego];

@@ -137,7 +137,7 @@ __global__ __launch_bounds__(256, JSIM_REG4_MINW) void mpc_step_reg4_kernel(cons
     double di_prev = advance ? gp(Kv.di_ai)[2 * ego] : 0.0;
     double ai_last = advance ? gp(Kv.di_ai)[2 * ego + 1] : 0.0;
     int age = advance ? uni(gp(Kv.age)[ego]) : 0;
-    const int hist_base = (advance && Kv.hist) ? uni(*gp(Kv.tick)) : 0;
+    const int hist_base = (advance && (Kv.hist || Kv.rec)) ? uni(*gp(Kv.tick)) : 0;
     double2 goal_xy = double2{0.0, 0.0};
     if (advance) { const jsim_d2v gq = ((JSIM_GAS const jsim_d2v *)Pv.pxy)[gp(Pv.poff)[pid + 1] - 1]; goal_xy = double2{uni(gq.x), uni(gq.y)}; }
 
@@ -1311,6 +1311,13 @@ __global__ __launch_bounds__(256, JSIM_REG4_MINW) void mpc_step_reg4_kernel(cons
             const int k = hist_base + tk;
             if (k < Kv.hist_cap) { gp(Kv.hist)[((size_t)k * Pv.B + ego) * 2] = di; gp(Kv.hist)[((size_t)k * Pv.B + ego) * 2 + 1] = ai; }
         }
+        // the recorder's xref deviation: the solve's ox[0], oy[0] is the tick-start pose (sx, sy), target_ind is s0
+        if (Kv.rec && gl == 0 && hist_base + tk < Kv.rec_cap) {
+            const jsim_d2v rq = ((JSIM_GAS const jsim_d2v *)Pv.pxy)[off + s0];
+            jsim_rec_store_dev(gp(Kv.rec), hist_base + tk, Pv.B, ego,
+                               status == JSIM_OK ? jsim_xref_deviation(double2{rq.x, rq.y}, gp(Pv.pyaw)[off + s0], sx, sy)
+                                                 : __builtin_nan(""));
+        }
         double dc = (Pv.smax < di) ? Pv.smax : di;
         dc = (-Pv.smax > dc) ? -Pv.smax : dc;
         const double xd = sv * cos(syaw), yd = sv * sin(syaw), thd = (sv / Pv.L) * tan(dc);
@@ -1322,7 +1329,14 @@ __global__ __launch_bounds__(256, JSIM_REG4_MINW) void mpc_step_reg4_kernel(cons
         long long df = s0 - M;
         if ((df < 0 ? -df : df) >= 5) isgoal = false;
         // (uniform, but decided by vector compares: without the broadcast `age` and everything reset below live in vector registers)
-        const bool done = uni((int)((isgoal && fabs(sv) <= Kv.stop_speed) || (age + 1 >= Kv.max_age))) != 0;
+        const bool goal = isgoal && fabs(sv) <= Kv.stop_speed, aged = age + 1 >= Kv.max_age;
+        const bool done = uni((int)(goal || aged)) != 0;
+        if (Kv.rec && gl == 0) { // the History record: the new state ahead of the respawn
+            const int k = hist_base + tk;
+            if (k < Kv.rec_cap)
+                jsim_rec_store(gp(Kv.rec), gp(Kv.rec_flags), k, Pv.B, ego, sx, sy, syaw, sv, di, ai,
+                               (status == JSIM_OK ? 0 : JSIM_REC_FAILED) | (goal ? JSIM_REC_GOAL : 0) | (aged ? JSIM_REC_AGE : 0));
+        }
         if (done) {
             sx = gp(Kv.x0_spawn)[4 * ego]; sy = gp(Kv.x0_spawn)[4 * ego + 1]; sv = gp(Kv.x0_spawn)[4 * ego + 2]; syaw = gp(Kv.x0_spawn)[4 * ego + 3];
             s0 = gp(Kv.target_spawn)[ego];

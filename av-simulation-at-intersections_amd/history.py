@@ -1,0 +1,99 @@
+"""Per-tick History of every ego, as the reference's scenario scripts keep it (lib.simulation.History,
+main/lib/simulation.py:50-88, and `obstacles_positions`, main/scenarios/mpc_intersection.py:95-96,159-161), rebuilt from what
+the device recorder wrote (jsim_loop_set_recorder): rec [n][B][7] = x, y, yaw, v, delta, a, xref_deviation per tick, flags
+[n][B] (FAILED / GOAL / AGE bits), obs [n][n_obs][6] = the scripted vehicles' get() tuples.  Pure numpy: the host-side half of
+the recorder, testable without a device."""
+from __future__ import annotations
+
+from typing import List, Optional
+
+import numpy as np
+
+FIELDS = ("x", "y", "yaw", "v", "delta", "a", "xref_deviation")
+FAILED, GOAL, AGE = 1, 2, 4              # JSIM_REC_* of include/jsim_mpc.h
+END_RUNNING, END_GOAL, END_AGE = 0, 1, 2  # how an episode ended (episodes())
+
+
+class History:
+    """lib.simulation.History's fields and meaning: Python float lists x, y, yaw, v, t, delta, a, xref_deviation; t grows by
+    repeated `+ sample_time` from 0 (the first entry is at t = sample_time), as History.store does it."""
+
+    def __init__(self, sample_time: float):
+        self.x: List[float] = []
+        self.y: List[float] = []
+        self.yaw: List[float] = []
+        self.v: List[float] = []
+        self.t: List[float] = []
+        self.delta: List[float] = []
+        self.a: List[float] = []
+        self.xref_deviation: List[float] = []
+        self._sample_time = sample_time
+
+    def store(self, x: float, y: float, yaw: float, v: float, a: float, delta: float, xref_deviation: float):
+        self.x.append(float(x))
+        self.y.append(float(y))
+        self.yaw.append(float(yaw))
+        self.v.append(float(v))
+        self.t.append(self.get_current_time() + self._sample_time)
+        self.delta.append(float(delta))
+        self.a.append(float(a))
+        self.xref_deviation.append(float(xref_deviation))
+
+    def get_current_time(self) -> float:
+        return self.t[-1] if len(self.t) > 0 else 0.
+
+    def __len__(self):
+        return len(self.x)
+
+
+def episode_bounds(flags_b: np.ndarray):
+    """Episodes of one ego from its flags [n]: a list of (first tick, end tick (exclusive), END_*).  An episode ends with the
+    record whose GOAL or AGE bit is set (the ego respawns after it); the last one is still running (END_RUNNING), and has no
+    ticks yet when the last record ended the one before.  A tick with both bits counts as GOAL."""
+    f = np.asarray(flags_b).reshape(-1)
+    out, start = [], 0
+    for k in np.flatnonzero(f & (GOAL | AGE)):
+        out.append((start, int(k) + 1, END_GOAL if f[k] & GOAL else END_AGE))
+        start = int(k) + 1
+    out.append((start, f.size, END_RUNNING))      # the running one (just respawned: its spawn entry only)
+    return out
+
+
+def ego_histories(rec_b: np.ndarray, flags_b: np.ndarray, dt: float, x0_first, x0_spawn) -> List[History]:
+    """One History per episode of one ego.  rec_b [n][7], flags_b [n]: the ego's recorded ticks; x0_first / x0_spawn: its state at
+    the first recorded tick's start and its respawn state, both in the MPC's order (x, y, v, yaw).  Each History starts with the
+    episode's spawn entry (a = delta = xref_deviation = 0, HistorySimulation.__init__), then one entry per tick."""
+    rec_b = np.asarray(rec_b, dtype=np.float64).reshape(-1, 7)
+    out = []
+    for e, (k0, k1, _) in enumerate(episode_bounds(flags_b)):
+        s = np.asarray(x0_first if e == 0 else x0_spawn, dtype=np.float64).reshape(4)
+        h = History(dt)
+        h.store(s[0], s[1], s[3], s[2], 0.0, 0.0, 0.0)
+        for r in rec_b[k0:k1].tolist():
+            h.store(r[0], r[1], r[2], r[3], r[5], r[4], r[6])
+        out.append(h)
+    return out
+
+
+def episodes(flags: np.ndarray):
+    """Per ego (flags [n][B]): dict count [B] (episodes), ticks (B arrays: ticks per episode), end (B arrays of END_*)."""
+    f = np.asarray(flags).reshape(np.shape(flags)[0], -1)
+    ticks, end = [], []
+    for b in range(f.shape[1]):
+        eb = episode_bounds(f[:, b])
+        ticks.append(np.array([k1 - k0 for k0, k1, _ in eb], dtype=np.int64))
+        end.append(np.array([x for _, _, x in eb], dtype=np.int8))
+    return {"count": np.array([len(t) for t in ticks], dtype=np.int64), "ticks": ticks, "end": end}
+
+
+def obstacle_positions(obs: Optional[np.ndarray], first_tick: int = 0):
+    """The scripts' obstacles_positions from obs [n][n_obs][6]: per vehicle, the list of (i, get() tuple) of every tick i."""
+    if obs is None:
+        return []
+    obs = np.asarray(obs, dtype=np.float64)
+    return [[(first_tick + i, tuple(obs[i, o].tolist())) for i in range(obs.shape[0])] for o in range(obs.shape[1])]
+
+
+def recorded_ticks(ticks_run: int, cap: int):
+    """(ticks held by a recorder of capacity cap after ticks_run ticks, whether ticks were dropped)."""
+    return min(int(ticks_run), int(cap)), int(ticks_run) > int(cap)

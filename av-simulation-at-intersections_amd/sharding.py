@@ -68,6 +68,7 @@ class CabiGather:
         if getattr(engine, "traffic_layout", None) is not None and self.world > 1:
             raise ValueError("a traffic-set layout (ScenarioLoop / InteractingLoop traffic_of) is not sharded across ranks: "
                              "give every rank its own engine, batch and layout")
+        self._refuse_recorder()
         lib = engine.lib
         if unique_id is None:
             buf = (C.c_char * 128)()
@@ -86,8 +87,16 @@ class CabiGather:
         idbuf = C.create_string_buffer(unique_id, 128)
         _cabi.check(lib.jsim_comm_init(engine._ctx, C.cast(idbuf, C.c_void_p), self.world, self.rank), engine._ctx, "jsim_comm_init")
 
+    def _refuse_recorder(self):
+        """A History recorder is not sharded across ranks -- checked when the gather is built and again at every gather (a loop
+        with record= may be constructed on the engine afterwards)."""
+        if getattr(self.eng, "_recorder", None) is not None and self.world > 1:
+            raise ValueError("a History recorder (ClosedLoop / ScenarioLoop / InteractingLoop record=) is not sharded across "
+                             "ranks: give every rank its own engine, batch and recorder")
+
     def gather_rows(self, local: torch.Tensor, B: int) -> torch.Tensor:
         """All-gather per-ego rows [b_local, ...] into [B, ...] in rank order (ragged shards are padded to the largest)."""
+        self._refuse_recorder()
         sizes = shard_sizes(B, self.world)
         per = max(sizes)
         if local.shape[0] != sizes[self.rank]:

@@ -234,6 +234,23 @@ int jsim_loop_run_interacting(jsim_ctx *ctx, int32_t B, int32_t n_ticks, double 
 int jsim_loop_set_traffic(jsim_ctx *ctx, int32_t B, int32_t n_sets, const int32_t *set_of, const int32_t *obs_off,
                           int32_t chunk_ticks);
 
+/* ---- Per-tick History of every ego (lib.simulation.History, main/lib/simulation.py:50-88, and the scripts' obstacles_positions,
+ * main/scenarios/mpc_intersection.py:166-177), recorded by the loop entry points where the state lives.
+ * jsim_loop_set_recorder: caller-owned DEVICE buffers; cap = 0 clears.  While registered, jsim_loop_advance, jsim_mpc_run_ticks,
+ *   jsim_loop_run_scenario and jsim_loop_run_interacting write slot k = the device tick counter of the tick (the one hist uses;
+ *   slots k >= cap are dropped, the counter keeps counting):
+ *   rec [cap][B][7] = x, y, yaw, v after the plant step and before any respawn (History's field order), the applied delta and a,
+ *     and xref_deviation = what jsim_mpc_xref_deviation_goal gives for that tick's ox[0], oy[0], target_ind (NaN when the solve
+ *     failed);
+ *   flags [cap][B] = JSIM_REC_* bits;
+ *   obs_rec [cap][n_obs][6] (NULL / n_obs = 0: not recorded) = the scripted vehicles' get() tuples of the tick, ahead of their
+ *     step() -- all vehicles of a traffic layout.
+ *   Refused (-22), nothing changed: B < 0, cap < 0, n_obs < 0, cap > 0 with a null rec / flags, or an obs_rec whose n_obs is not
+ *   the registered traffic layout's total.  The loop entry points refuse (-22) a run while
+ *   a recorder is registered for another B, a run without a tick counter, and (scenario / interacting, obs_rec given) another n_obs. */
+enum { JSIM_REC_FIELDS = 7, JSIM_REC_FAILED = 1, JSIM_REC_GOAL = 2, JSIM_REC_AGE = 4 };
+int jsim_loop_set_recorder(jsim_ctx *ctx, int32_t B, int32_t cap, double *rec, int32_t *flags, int32_t n_obs, double *obs_rec);
+
 /* n_ticks consecutive closed-loop ticks, each = jsim_mpc_step followed by jsim_loop_advance, with identical results.
  * For the horizons that have the fused register-resident kernel (T = 13, 20) this is ONE launch in which every
  * wavefront runs all n_ticks for its own ego (egos are independent, so none waits for the slowest solve of a tick);

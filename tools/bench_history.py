@@ -1,0 +1,60 @@
+#!/usr/bin/env python3
+"""The cost of the device History recorder at config 3's shape: 4096 egos, T = 30, the scenario loop with four scripted vehicles
+(workloads.OBSTACLE_SPECS), fused ScenarioLoop.run launches -- with the recorder off (record = 0) and on (record = warmup + ticks,
+every tick recorded).  The two are run alternately `rounds` times on fresh loops; prints one JSON line per run (ego-steps/s over
+`ticks` device-synchronised ticks after `warmup` ticks) and a summary line with the medians and the relative cost.
+
+    python3 tools/bench_history.py [--egos 4096] [--horizon 30] [--ticks 60] [--warmup 10] [--rounds 3]
+"""
+import argparse
+import importlib
+import json
+import os
+import statistics
+import sys
+import time
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--egos", type=int, default=4096)
+    ap.add_argument("--horizon", type=int, default=30)
+    ap.add_argument("--ticks", type=int, default=60)
+    ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--rounds", type=int, default=3)
+    a = ap.parse_args()
+    import torch
+    pkg = importlib.import_module("av-simulation-at-intersections_amd")
+    W = pkg.workloads
+    routes = W.route_table(False)[0]
+    T, B = a.horizon, a.egos
+    batch = W.ego_batch(routes, B, T)
+    rate = {0: [], 1: []}
+    for _ in range(a.rounds):
+        for on in (0, 1):
+            eng, x0 = W.make_engine(routes, batch, T, "cuda:0")
+            loop = pkg.ScenarioLoop(eng, x0, W.OBSTACLE_SPECS, max_age=W.MAX_AGE, record=(a.warmup + a.ticks) if on else 0)
+            loop.run(a.warmup)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            loop.run(a.ticks)
+            torch.cuda.synchronize()
+            dt = time.perf_counter() - t0
+            rate[on].append(B * a.ticks / dt)
+            line = {"record": bool(on), "egos": B, "T": T, "ticks": a.ticks, "ego_steps_per_s": round(rate[on][-1]),
+                    "ms_per_tick": round(dt / a.ticks * 1e3, 4)}
+            if on:
+                r = loop.recorder
+                line["recorded_bytes"] = int(r.rec.numel() * 8 + r.flags.numel() * 4 + r.obs.numel() * 8)
+                line["respawns_recorded"] = int(((r.flags & 6) != 0).sum().item())
+            print(json.dumps(line), flush=True)
+            del loop, eng
+    off, on = statistics.median(rate[0]), statistics.median(rate[1])
+    print(json.dumps({"summary": True, "median_off": round(off), "median_on": round(on), "cost_pct": round((off / on - 1) * 100, 2)}))
+
+
+if __name__ == "__main__":
+    main()
