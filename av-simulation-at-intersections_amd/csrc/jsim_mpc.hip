@@ -1268,6 +1268,13 @@ __global__ __launch_bounds__(256) void loop_advance_kernel(LoopP P, double *x0, 
 __global__ void tick_increment_kernel(int *tick) { *tick += 1; }
 __global__ void tick_add_kernel(int *tick, int n) { *tick += n; }
 
+// host ticks: this tick's active-set iterations (summed over the linearisation passes) onto the running totals
+__global__ __launch_bounds__(256) void iters_add_kernel(int B, const int *n_iter, unsigned long long *iters)
+{
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b < B) iters[b] += (unsigned long long)n_iter[b];
+}
+
 struct GoalP {
     int B, T;
     double goal_dis, stop_speed;
@@ -1366,7 +1373,8 @@ struct jsim_ctx {
     void *comm = nullptr;          // ncclComm_t of jsim_comm_init (RCCL), or NULL
     DevArray<int> d_order;         // launch order of the fused closed-loop launches (prepare_launch_order) ..
     DevArray<unsigned> d_work;     // .. and the per-ego iteration count of the previous launch it is derived from
-    DevArray<unsigned long long> d_iters; // per-ego running totals of active-set iterations over the fused launches (jsim_mpc_iter_totals)
+    DevArray<unsigned long long> d_iters; // per-ego running totals of active-set iterations over the closed-loop ticks (jsim_mpc_iter_totals)
+    DevArray<int32_t> d_n_iter;           // host ticks without a caller's n_iter: the tick's counts for d_iters
     int order_mode = 0;      // 0: from the environment (default on), 1: on, -1: off (jsim_mpc_set_launch_order)
     int use_reg_kernel = 0;  // 1: register-resident fast path available for this T (and not disabled)
     int dbg_max_gi = 0;
@@ -1675,14 +1683,13 @@ static int prepare_launch_order(jsim_ctx *ctx, int B, hipStream_t s, TickP &K)
     return 0;
 }
 
-// Per-ego running totals of active-set iterations, added to by every fused launch (one 8-byte update per ego and tick).
-static int prepare_iter_totals(jsim_ctx *ctx, int B, hipStream_t s, TickP &K)
+// Per-ego running totals of active-set iterations, added to by every closed-loop tick: inside the fused launches (one 8-byte update
+// per ego and tick), after each MPC step of run_host_ticks.  Sized on first use, cleared when they grow.
+static int prepare_iter_totals(jsim_ctx *ctx, int B, hipStream_t s)
 {
-    K.iters = nullptr;
     bool grew;
     HIP_TRY(ctx, ctx->d_iters.reserve(B, &grew));
     if (grew) HIP_TRY(ctx, hipMemsetAsync(ctx->d_iters, 0, sizeof(unsigned long long) * (size_t)B, s));
-    K.iters = ctx->d_iters;
     return 0;
 }
 
@@ -1691,7 +1698,7 @@ extern "C" int jsim_mpc_iter_totals(jsim_ctx *ctx, int32_t B, uint64_t *totals, 
     if (!ctx) return fail(nullptr, -22, "jsim_mpc_iter_totals: null ctx");
     DeviceGuard dev_guard(ctx->device);
     JSIM_GUARD_OK(ctx);
-    if (B <= 0 || (size_t)B > ctx->d_iters.cap) return fail(ctx, -22, "jsim_mpc_iter_totals: B=%d, but the fused launches of this context had at most %d egos", B, (int)ctx->d_iters.cap);
+    if (B <= 0 || (size_t)B > ctx->d_iters.cap) return fail(ctx, -22, "jsim_mpc_iter_totals: B=%d, but the closed-loop runs of this context had at most %d egos", B, (int)ctx->d_iters.cap);
     HIP_TRY(ctx, hipDeviceSynchronize());
     if (totals) HIP_TRY(ctx, hipMemcpy(totals, ctx->d_iters, sizeof(uint64_t) * (size_t)B, hipMemcpyDeviceToHost));
     if (reset) HIP_TRY(ctx, hipMemset(ctx->d_iters, 0, sizeof(unsigned long long) * ctx->d_iters.cap));
@@ -2304,6 +2311,12 @@ static int run_host_ticks(jsim_ctx *ctx, int B, int n_ticks, const StepBufs &S, 
         if (grid) hipLaunchKernelGGL(obstacle_step_grid_kernel, dim3((G->n_obs + 63) / 64), dim3(64), 0, s, O);
         else hipLaunchKernelGGL(obstacle_step_kernel, dim3(1), dim3(64), 0, s, O);
     };
+    // every tick's iteration counts go onto the totals (jsim_mpc_iter_totals): the caller's n_iter, or the context's own
+    if (int rc = prepare_iter_totals(ctx, B, s)) return rc;
+    if (!P.n_iter) {
+        HIP_TRY(ctx, ctx->d_n_iter.reserve(B));
+        P.n_iter = ctx->d_n_iter;
+    }
     for (int k = 0; k < n_ticks; ++k) {
         if (G) {
             obstacles(0);
@@ -2323,6 +2336,7 @@ static int run_host_ticks(jsim_ctx *ctx, int B, int n_ticks, const StepBufs &S, 
             HIP_TRY(ctx, hipMemcpyAsync(G->prev_path_len, S.path_len, sizeof(int32_t) * B, hipMemcpyDeviceToDevice, s));
         }
         launch_step(ctx, P, s);
+        hipLaunchKernelGGL(iters_add_kernel, dim3((B + 255) / 256), dim3(256), 0, s, B, P.n_iter, ctx->d_iters.p);
         launch_advance(ctx, B, S, A, s);
         if (G) {
             hipLaunchKernelGGL(glue_reset_kernel, dim3((B + 255) / 256), dim3(256), 0, s, B, A.age, (long long *)G->traj_idx,
@@ -2355,7 +2369,8 @@ static int launch_fused(jsim_ctx *ctx, int B, int n_ticks, const StepBufs &S, co
     K.hist = A.hist; K.tick = A.tick; K.n_respawn = (unsigned long long *)A.n_respawn;
     K.rec = ctx->rec; K.rec_flags = ctx->rec_flags; K.rec_cap = ctx->rec_cap;
     if (int rc = prepare_launch_order(ctx, B, s, K)) return rc;
-    if (int rc = prepare_iter_totals(ctx, B, s, K)) return rc;
+    if (int rc = prepare_iter_totals(ctx, B, s)) return rc;
+    K.iters = ctx->d_iters;
     launch_reg(c.T, B, s, P, K, Q);
     if (A.tick) hipLaunchKernelGGL(tick_add_kernel, dim3(1), dim3(1), 0, s, A.tick, n_ticks);
     HIP_TRY(ctx, hipGetLastError());

@@ -272,10 +272,13 @@ int jsim_mpc_run_ticks(jsim_ctx *ctx, int32_t B, int32_t n_ticks, double *x0, co
 int jsim_mpc_set_launch_order(jsim_ctx *ctx, int32_t enabled);
 int jsim_mpc_get_launch_order(jsim_ctx *ctx, int32_t B, int32_t *order, uint32_t *work);
 
-/* Per-ego running totals of active-set iterations of the fused launches (jsim_mpc_run_ticks, jsim_loop_run_scenario) since the
- * last reset.  No reference counterpart (the reference never sees its solver's iterations, main/lib/mpc.py:196-199); this is
- * the measurement hook bench.py takes mean iterations, algorithmic flops and the straggler statistic of the TIMED launches from.
- * Copies totals [B] to a HOST array (may be NULL) and, with reset != 0, clears them; it synchronises. */
+/* Per-ego running totals of active-set iterations since the last reset, over every tick run through jsim_mpc_run_ticks,
+ * jsim_loop_run_scenario and jsim_loop_run_interacting: fused launches and separate launches per tick alike (no register kernel,
+ * MAX_ITER > 1 with a tick's count summed over its passes, JSIM_FORCE_LDS_KERNEL, the interacting glue).  Single steps
+ * (jsim_mpc_step) do not count.  No reference counterpart (the reference never sees its solver's iterations,
+ * main/lib/mpc.py:196-199); this is the measurement hook bench.py takes mean iterations, algorithmic flops and the straggler
+ * statistic of the TIMED launches from.  Copies totals [B] to a HOST array (may be NULL) and, with reset != 0, clears them; it
+ * synchronises. */
 int jsim_mpc_iter_totals(jsim_ctx *ctx, int32_t B, uint64_t *totals, int32_t reset);
 
 /* ---- the route planner: A* over motion primitives, a batch of route queries at once ----

@@ -1,6 +1,54 @@
 """Shared pieces of the GPU parity tests (tests/test_gpu_*.py)."""
+import importlib
+
 import numpy as np
 import torch
+
+from conftest import PKG_NAME
+
+REG_VARIANTS = importlib.import_module(PKG_NAME + ".config").REG_VARIANTS
+_CABI = importlib.import_module(PKG_NAME + "._cabi")
+W2_MIN_B = 1025          # launch_reg's JSIM_W2_MIN_B default (csrc/reg_variants.h); the tests never set it, nor JSIM_HELP_MAX_B
+
+
+def variant_id(row):
+    """A readable test id for a row (W, T, PRE, WPE, HELP) of config.REG_VARIANTS: w1-T15-pre-wpe1, w1-T20-wpe1-help."""
+    W, T, pre, wpe, help_ = row
+    return f"w{W}-T{T}" + ("-pre" if pre else "") + f"-wpe{wpe}" + ("-help" if help_ else "")
+
+
+def variant_batches(row, cu):
+    """The batch sizes at which launch_reg takes `row` (select_reg_variant with JSIM_HELP_MAX_B = cu, the device's CU count, and
+    JSIM_W2_MIN_B = 1025), each at a boundary where the dispatch changes: HELP rows at B = cu, the last size with one ego per CU;
+    one-wave rows without helpers at cu + 1, the first size without them, and below the two-waves-per-SIMD threshold at 1024 where
+    that horizon has a two-wave form; that form at cu + 1 where it is the horizon's only one-wave form, else at 1025; the four-wave
+    rows at an odd size.  tests/test_host_cpu.py checks the dispatch lands on every row at every size returned here."""
+    W, T, pre, wpe, help_ = row
+    w1 = (1, T, pre, 1, False) in REG_VARIANTS
+    if help_:
+        return (cu,)
+    if W == 1 and wpe == 2:
+        return (W2_MIN_B,) if w1 else (cu + 1,)
+    if W == 1:
+        return (cu + 1, W2_MIN_B - 1) if (1, T, pre, 2, False) in REG_VARIANTS else (cu + 1,)
+    return (97,)
+
+
+def variant_batch(row, cu):
+    """The first of variant_batches(row, cu)."""
+    return variant_batches(row, cu)[0]
+
+
+def cu_count():
+    """The CU count of device 0: launch_reg's HELP threshold."""
+    return torch.cuda.get_device_properties(0).multi_processor_count
+
+
+def iter_totals(eng, reset=False):
+    """jsim_mpc_iter_totals of an engine's context: the per-ego active-set iterations of its closed-loop runs (int64 [B])."""
+    tot = np.zeros(eng.B, dtype=np.uint64)
+    _CABI.check(eng.lib.jsim_mpc_iter_totals(eng._ctx, eng.B, tot.ctypes.data, 1 if reset else 0), eng._ctx, "jsim_mpc_iter_totals")
+    return tot.astype(np.int64)
 
 
 def engine(pkg, routes, batch, T, **kw):

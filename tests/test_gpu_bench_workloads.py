@@ -232,6 +232,21 @@ def test_bench_line_fields():
     assert 'mpc_step_reg4_kernel<{T}, {pre}>' in spec_src and "reg2" not in spec_src
 
 
+def test_bench_on_a_horizon_without_a_register_kernel():
+    """`python bench.py --horizon 24`: no register kernel, so the fused mode's closed loop runs as separate launches per tick
+    inside jsim_mpc_run_ticks -- which count into jsim_mpc_iter_totals like the fused launches do, so the line has its
+    iteration figures and names the LDS-resident kernel."""
+    out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--horizon", "24", "--steps", "5", "--warmup", "2",
+                          "--no-cpu-baseline"], capture_output=True, text=True, timeout=900)
+    assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
+    j = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith('{"metric"')][0])
+    cfg = j["config"]
+    assert cfg["horizon"] == 24 and "jsim_mpc_iter_totals" in cfg["iters_source"] and cfg["mean_active_set_iters"] > 0
+    s = cfg["straggler"]
+    assert s["max_ego_iters_per_tick"] >= cfg["mean_active_set_iters"] and s["slowest_over_mean"] >= 1.0
+    assert j["roofline"]["kernel"] == "mpc_step_kernel"
+
+
 def test_bench_dump_outputs_are_reproducible(tmp_path):
     """`python bench.py --dump-outputs DIR`: the last timed tick's controls, state, solution, status, index and path of every
     ego as float64 .npy files; two runs with the same arguments write identical arrays."""

@@ -122,6 +122,31 @@ def test_singleton_groups_equal_the_scenario_loop(pkg, W, iroutes, T, with_obsta
     print(f"singleton groups, T = {T}, {len(specs)} scripted obstacles: {n_cut} ego-ticks with a cut-off")
 
 
+def test_interacting_run_counts_every_tick_into_the_iteration_totals(pkg, W, iroutes):
+    """jsim_loop_run_interacting runs separate launches per tick; jsim_mpc_iter_totals after run(K) is the per-tick n_iter of
+    K x tick() added up, and both loops end bit-identical."""
+    T, K = 13, 20
+    batch, sizes = W.interacting_batch(iroutes, 6, T, seed=7)
+    loops = []
+    for _ in range(2):
+        eng, x0 = _engine(pkg, W, iroutes, batch, T)
+        loops.append((eng, pkg.InteractingLoop(eng, x0, group_sizes=sizes, obstacle_specs=W.OBSTACLE_SPECS[:2], hist_cap=K,
+                                               max_age=W.MAX_AGE)))
+    (e1, l1), (e2, l2) = loops
+    iters = torch.zeros(e1.B, dtype=torch.int64, device=e1.device)
+    for _ in range(K):
+        l1.tick()
+        iters += e1.n_iter
+    l2.run(K)
+    torch.cuda.synchronize()
+    a, b = _state(e1, l1.loop, l1.pre), _state(e2, l2.loop, l2.pre)
+    for key in a:
+        assert torch.equal(a[key], b[key]), key
+    tot = np.zeros(e2.B, dtype=np.uint64)
+    pkg._cabi.check(e2.lib.jsim_mpc_iter_totals(e2._ctx, e2.B, tot.ctypes.data, 0), e2._ctx, "jsim_mpc_iter_totals")
+    assert np.array_equal(tot.astype(np.int64), iters.cpu().numpy()) and int(iters.sum()) > 0
+
+
 def test_groups_are_isolated(pkg, W, iroutes):
     """Perturbing the spawn states of group 1 changes nothing in groups 0 and 2, bit for bit (and does change group 1)."""
     T, K = 13, 30

@@ -12,12 +12,38 @@ import pytest
 import torch
 
 from conftest import PKG_NAME, load_golden
-from gpu_helpers import kkt_check
+from gpu_helpers import cu_count, iter_totals, kkt_check, variant_batches, variant_id
 
 pytestmark = pytest.mark.gpu
 TS = (13, 20, 30, 40)
 CFG = importlib.import_module(PKG_NAME + ".config")
 U_TOL = 1e-4  # north_star tolerance on u*
+# The register kernels by row of config.REG_VARIANTS (W, T, PRE, WPE, HELP), each run at the batch size where launch_reg takes it
+# (gpu_helpers.variant_batches, checked against the dispatch by tests/test_host_cpu.py): a new row is tested without a list to edit.
+# Beside them the tests keep their horizon-keyed cases (ids: the horizon), at the fixed batch sizes they were written with.
+NON_PRE_ROWS = tuple(r for r in CFG.REG_VARIANTS if not r[2])
+PRE_ROWS = tuple(r for r in CFG.REG_VARIANTS if r[2])
+HELP_ROWS = tuple(r for r in CFG.REG_VARIANTS if r[4])
+
+
+def _rows(rows, every_batch=False):
+    """pytest params (T, size) of rows: size = (row, k), k indexing variant_batches(row, cu) (every boundary size with every_batch,
+    else the first)."""
+    return [pytest.param(r[1], (r, k), id=variant_id(r) + (f"-b{k}" if k else ""))
+            for r in rows for k in range(len(variant_batches(r, 256)) if every_batch else 1)]
+
+
+def _horizons(Ts, B):
+    """pytest params (T, size) of the horizon-keyed cases: size = a fixed batch size (an int, or B(T)), whatever kernel it takes."""
+    return [pytest.param(T, B(T) if callable(B) else B, id=str(T)) for T in Ts]
+
+
+def _batch(size):
+    """The batch size of a case: the fixed size, or variant_batches(row, this device's CU count)[k]."""
+    if isinstance(size, int):
+        return size
+    row, k = size
+    return variant_batches(row, cu_count())[k]
 
 
 def _engine(pkg, routes, batch, T):
@@ -34,11 +60,11 @@ def _debug_bufs(eng):
             "H": torch.zeros(B, 2 * T, 2 * T, **f), "g": torch.zeros(B, 2 * T, **f), "lam": torch.zeros(B, 8 * T, **f)}
 
 
-def _oracle_batch(oracle, pkg, routes, batch, T, **kw):
+def _oracle_batch(oracle, pkg, routes, batch, T, n_threads=1, **kw):
     p = oracle.make_params(T=T, **kw)
     cx, cy, cyaw, off = pkg.synth.pack_paths(routes)
     return p, oracle.mpc_step_batch(p, batch.x0, batch.path_id, batch.path_len, batch.speed, cx, cy, cyaw, off,
-                                    batch.target_ind, batch.oa, batch.od)
+                                    batch.target_ind, batch.oa, batch.od, n_threads=n_threads)
 
 
 @pytest.mark.parametrize("T", TS)
@@ -64,17 +90,25 @@ def test_stages_vs_reference_golden(pkg, routes, T):
     assert feas.sum() > 60
 
 
-@pytest.mark.parametrize("T", CFG.ONE_WAVE_HORIZONS + CFG.FOUR_WAVE_HORIZONS)     # every horizon with a register kernel
-def test_step_vs_oracle(pkg, oracle, routes, T):
-    B = 192 if T <= 20 else 96
+@pytest.mark.parametrize("T,size", _horizons(CFG.ONE_WAVE_HORIZONS + CFG.FOUR_WAVE_HORIZONS, lambda T: 192 if T <= 20 else 96) +
+                         _rows(NON_PRE_ROWS, every_batch=True))      # every horizon and every single-step register kernel
+def test_step_vs_oracle(pkg, oracle, routes, T, size):
+    """One step of every register kernel without the loop glue, at a batch size where the dispatch takes it, against the oracle:
+    indices, status and xref bit-exact, u* within 1e-7, active sets bit-exact, the condensed QP of a dozen egos; planted among
+    the egos: infeasible starts (the owner's early exits), two and three path points left (no scan; the HELP scan's shortest),
+    the last point of the path."""
+    B = _batch(size)
     batch = pkg.synth.make_ego_batch(routes, B, T, seed=0, truncate=True, near_end_frac=0.2)
     batch.x0[5, 2] = 9.5       # v0 > speed  -> infeasible constant row (reference failure path)
     batch.x0[6, 2] = -5.5      # v0 < MIN_SPEED
+    batch.path_len[7:9] = np.minimum(batch.path_len[7:9], batch.target_ind[7:9] + [2, 3])   # two / three points left
+    batch.target_ind[9] = batch.path_len[9] - 1             # on the last point
+    assert np.array_equal(batch.path_len[7:10] - batch.target_ind[7:10], [2, 3, 1])
     eng = _engine(pkg, routes, batch, T)
     dbg = _debug_bufs(eng)
     eng.solve(torch.from_numpy(batch.x0).to(eng.device), debug=dbg)
     torch.cuda.synchronize()
-    p, ref = _oracle_batch(oracle, pkg, routes, batch, T)
+    p, ref = _oracle_batch(oracle, pkg, routes, batch, T, n_threads=16)
     st = eng.status.cpu().numpy()
     assert np.array_equal(st, ref["status"])
     assert st[5] == 1 and st[6] == 1
@@ -93,7 +127,7 @@ def test_step_vs_oracle(pkg, oracle, routes, T):
     # same sequence of active-set decisions for (nearly) every ego; a near-tie between two violated rows
     # may be ordered differently by last-ulp differences and still ends in the same optimum / active set
     same = eng.n_iter.cpu().numpy() == ref["n_iter"]
-    print(f"T={T}: n_iter identical for {same.mean() * 100:.1f}% of egos; max|du|={err_u:.2e}; "
+    print(f"T={T} B={B}: n_iter identical for {same.mean() * 100:.1f}% of egos; max|du|={err_u:.2e}; "
           f"mean n_iter={ref['n_iter'][ok].mean():.1f} max={ref['n_iter'].max()}")
     assert same.mean() >= 0.9
     # condensed QP of a few egos against the oracle's dense build
@@ -250,20 +284,24 @@ def test_plant_and_goal_kernels(pkg, oracle, routes):
     assert np.array_equal(goal.cpu().numpy()[inr], goal_rows[inr, 4].astype(bool))
 
 
-@pytest.mark.parametrize("T", (13, 20, 30, 40, 25, 16, 32, 24))
-def test_fused_ticks_equal_single_ticks(pkg, routes, T):
+@pytest.mark.parametrize("T,size", _horizons((13, 20, 30, 40, 25, 16, 32, 24), 96) + _rows(NON_PRE_ROWS))
+def test_fused_ticks_equal_single_ticks(pkg, routes, T, size):
     """jsim_mpc_run_ticks (one launch, every wavefront -- or four wavefronts at T = 32 / 40 -- runs K ticks of its
-    own ego) must reproduce K x (jsim_mpc_step + jsim_loop_advance) bit for bit: same history, same final state, same
-    respawn count.  T = 24 exercises the multi-launch fallback of the same entry point (no fused kernel)."""
-    B, K = 96, (60 if T <= 30 else 30)
+    own ego) must reproduce K x (jsim_mpc_step + jsim_loop_advance) bit for bit on every register kernel at a batch size that
+    takes it: same history, device History records, final state, ages, respawn count (max_age forces respawns), and the
+    iteration totals (jsim_mpc_iter_totals) are the per-tick iteration counts added up.  T = 24 exercises the multi-launch
+    fallback of the same entry point (no fused kernel)."""
+    B, K = _batch(size), (60 if T <= 30 else 30)
     batch = pkg.synth.make_ego_batch(routes, B, T, seed=11, near_end_frac=0.5)
     def make():
         eng = _engine(pkg, routes, batch, T)
         x0 = torch.from_numpy(batch.x0).to(eng.device)
-        return eng, pkg.ClosedLoop(eng, x0, hist_cap=K, max_age=45)
+        return eng, pkg.ClosedLoop(eng, x0, hist_cap=K, max_age=25, record=K)
     e1, l1 = make()
+    iters = torch.zeros(B, dtype=torch.int64, device=e1.device)
     for _ in range(K):
         l1.tick()
+        iters += e1.n_iter
     e2, l2 = make()
     l2.run(K // 2 - 5); l2.run(K - (K // 2 - 5))
     torch.cuda.synchronize()
@@ -272,8 +310,10 @@ def test_fused_ticks_equal_single_ticks(pkg, routes, T):
     assert torch.equal(l1.x0, l2.x0)
     for name in ("oa", "od", "ox", "oy", "ov", "oyaw", "xref", "target_ind", "status", "n_iter", "active_mask", "di_ai"):
         assert torch.equal(getattr(e1, name), getattr(e2, name)), name
+    assert torch.equal(l1.recorder.rec, l2.recorder.rec) and torch.equal(l1.recorder.flags, l2.recorder.flags)
     assert torch.equal(l1.age, l2.age)
-    assert int(l1.n_respawn.item()) == int(l2.n_respawn.item()) > 0
+    assert int(l1.n_respawn.item()) == int(l2.n_respawn.item()) >= B
+    assert np.array_equal(iter_totals(e2), iters.cpu().numpy()) and int(iters.sum()) > 0
 
 
 @pytest.mark.parametrize("T", CFG.HELP_HORIZONS)
@@ -312,14 +352,15 @@ def test_helper_wavefronts_change_nothing(pkg, routes, T):
     assert torch.equal(s1.status, s2.status[:B1]) and (s1.status == 1).sum().item() >= 2
 
 
-@pytest.mark.parametrize("T", (13, 20))
-def test_garbage_states_neither_stall_nor_leak(pkg, routes, T):
-    """Egos whose state is garbage (NaN, inf, 1e200) beside sane ones, on the kernel with helper wavefronts: the helpers wait for the
-    owner's columns by polling LDS, so whatever the owner's arithmetic turns into must still release them (a bounded wait that runs
-    out costs a quarter of a second per column) -- the closed loop finishes promptly, and the sane egos' results are those of a batch
-    without the garbage."""
+@pytest.mark.parametrize("T,size", _horizons((13, 20), 96) + _rows(HELP_ROWS))
+def test_garbage_states_neither_stall_nor_leak(pkg, routes, T, size):
+    """Egos whose state is garbage (NaN, inf, 1e200) beside sane ones, on every kernel with helper wavefronts (PRE: the fused
+    scenario loop): the helpers wait for the owner's columns by polling LDS, so whatever the owner's arithmetic turns into must
+    still release them (a bounded wait that runs out costs a quarter of a second per column) -- the closed loop finishes promptly,
+    and the sane egos' results are those of a batch without the garbage."""
     import time
-    B, K = 96, 12
+    pre = not isinstance(size, int) and size[0][2]
+    B, K = _batch(size), 12
     clean = pkg.synth.make_ego_batch(routes, B, T, seed=31, truncate=True)
     dirty = pkg.synth.EgoBatch(**{k: getattr(clean, k).copy() for k in ("x0", "path_id", "path_len", "target_ind", "speed", "oa", "od")})
     bad = [3, 17, 40, 41]
@@ -331,10 +372,16 @@ def test_garbage_states_neither_stall_nor_leak(pkg, routes, T):
     out = []
     for b in (clean, dirty):
         eng = _engine(pkg, routes, b, T)
-        loop = pkg.ClosedLoop(eng, torch.from_numpy(b.x0).to(eng.device), hist_cap=K, max_age=400)
-        loop.run(1); torch.cuda.synchronize()
+        x0 = torch.from_numpy(b.x0).to(eng.device)
+        if pre:
+            sc = pkg.ScenarioLoop(eng, x0, SCENARIO_SPECS, hist_cap=K, max_age=400)
+            loop, run = sc.loop, sc.run
+        else:
+            loop = pkg.ClosedLoop(eng, x0, hist_cap=K, max_age=400)
+            run = loop.run
+        run(1); torch.cuda.synchronize()
         t0 = time.perf_counter()
-        loop.run(K - 1)
+        run(K - 1)
         torch.cuda.synchronize()
         out.append((eng, loop, time.perf_counter() - t0))
     (e1, l1, t1), (e2, l2, t2) = out
@@ -369,6 +416,32 @@ def test_lds_kernel_and_register_kernel_agree(pkg, oracle, routes, T, monkeypatc
         assert np.abs(eng.od.cpu().numpy() - ref["od"])[ok].max() <= (1e-8 if T <= 20 else 1e-7)
     assert float((e_reg.oa - e_lds.oa).abs().max()) <= (1e-8 if T <= 20 else 1e-7)
     assert torch.equal(e_reg.xref, e_lds.xref)
+
+
+@pytest.mark.parametrize("kind", ("closed", "scenario"))
+def test_iteration_totals_with_the_lds_kernel_forced(pkg, routes, kind, monkeypatch):
+    """JSIM_FORCE_LDS_KERNEL=1 (read at jsim_mpc_create) sends T = 20, which has register kernels, through separate launches per
+    tick: ClosedLoop.run / ScenarioLoop.run still count every tick into jsim_mpc_iter_totals, and reset clears the totals."""
+    T, B, K = 20, 97, 12
+    batch = pkg.synth.make_ego_batch(routes, B, T, seed=9, truncate=True, near_end_frac=0.3)
+    monkeypatch.setenv("JSIM_FORCE_LDS_KERNEL", "1")
+    engs = [_engine(pkg, routes, batch, T) for _ in range(2)]
+    monkeypatch.delenv("JSIM_FORCE_LDS_KERNEL")
+    loops = []
+    for eng in engs:
+        x0 = torch.from_numpy(batch.x0).to(eng.device)
+        loops.append(pkg.ClosedLoop(eng, x0, hist_cap=K, max_age=7) if kind == "closed" else
+                     pkg.ScenarioLoop(eng, x0, SCENARIO_SPECS, hist_cap=K, max_age=7))
+    iters = torch.zeros(B, dtype=torch.int64, device=engs[0].device)
+    for _ in range(K):
+        loops[0].tick()
+        iters += engs[0].n_iter
+    loops[1].run(K)
+    torch.cuda.synchronize()
+    hist = [lp.hist if kind == "closed" else lp.loop.hist for lp in loops]
+    assert torch.equal(hist[0], hist[1]) and torch.equal(engs[0].n_iter, engs[1].n_iter)
+    assert np.array_equal(iter_totals(engs[1], reset=True), iters.cpu().numpy()) and int(iters.sum()) > 0
+    assert not iter_totals(engs[1]).any()
 
 
 def test_pre_tick_vs_reference_golden(pkg, routes):
@@ -572,37 +645,60 @@ def test_nearest_index_on_self_approaching_paths(pkg, oracle, T):
     np.testing.assert_array_equal(eng.xref.cpu().numpy()[use], ref["xref"][use])
 
 
-@pytest.mark.parametrize("T,max_age", ((13, 0), (20, 0), (30, 0), (40, 0), (25, 0), (20, 5), (40, 5), (25, 5), (32, 0), (16, 5), (24, 0), (24, 5)))
-def test_fused_scenario_loop_equals_tick_by_tick(pkg, routes, T, max_age):
+SCENARIO_SPECS = [dict(direction=1, turning=False, speed=25 / 3.6, offset=None), dict(direction=-1, turning=True, speed=20 / 3.6, offset=1.0),
+                  dict(kind="roundabout", direction=1, turning=True, speed=15 / 3.6, offset=2.0)]
+# the speed-cut-off glue on one row of each kernel family: one wave, one wave with helpers, four waves
+SPEED_CUTOFF_ROWS = ((1, 20, True, 1, False), (1, 13, True, 1, True), (4, 40, True, 1, False))
+SCENARIO_CASES = ([pytest.param(T, 48, "truncate", a, id=f"{T}-{a}")          # the horizon-keyed cases, 48 egos
+                   for T, a in ((13, 0), (20, 0), (30, 0), (40, 0), (25, 0), (20, 5), (40, 5), (25, 5), (32, 0), (16, 5), (24, 0), (24, 5))] +
+                  [pytest.param(r[1], (r, 0), "truncate", a, id=f"{variant_id(r)}-age{a}") for r in PRE_ROWS for a in (0, 5)] +
+                  [pytest.param(r[1], (r, 0), "speed_cutoff", 5, id=f"{variant_id(r)}-speed-cutoff") for r in SPEED_CUTOFF_ROWS])
+
+
+@pytest.mark.parametrize("T,size,mode,max_age", SCENARIO_CASES)
+def test_fused_scenario_loop_equals_tick_by_tick(pkg, routes, T, size, mode, max_age):
     """The whole scenario loop -- obstacles, prediction, progress index / resample / collision / cut-off, MPC step, plant,
     goal -- for K ticks in one call (jsim_loop_run_scenario: three launches for the horizons with a register kernel, the glue inside
     each ego's tick loop; tick-by-tick launches inside the same call for T = 24, which has none) against the same ticks
-    driven from the host: every buffer bit-identical."""
-    B, K1, K2 = 48, 7, 9
-    specs = [dict(direction=1, turning=False, speed=25 / 3.6, offset=None), dict(direction=-1, turning=True, speed=20 / 3.6, offset=1.0),
-             dict(kind="roundabout", direction=1, turning=True, speed=15 / 3.6, offset=2.0)]
-    outs = []
+    driven from the host: every buffer and every History record bit-identical, and the iteration totals are the host ticks'
+    counts added up.  Every PRE kernel at a batch size that takes it; the host ticks run the glue kernel and the single-step
+    kernel of the same batch size, which test_step_vs_oracle compares with the oracle."""
+    B, K1, K2 = _batch(size), 7, 9
+    kw = {}
+    if mode == "speed_cutoff":
+        m = pkg.mpc_with_speed
+        kw = dict(config=m.config, cv=[np.full(len(r), m.MAX_SPEED) for r in routes])
+    outs, iters = [], []
     for fused in (False, True):
         batch = pkg.synth.make_ego_batch(routes, B, T, seed=17)
-        eng = _engine(pkg, routes, batch, T)
+        eng = pkg.BatchedMPC(routes, batch.path_id, dl=pkg.synth.DL, T=T, speed=batch.speed, device="cuda:0", smooth=False, **kw)
+        eng.load_state(batch.target_ind, batch.oa, batch.od, batch.path_len)
         x0 = torch.from_numpy(batch.x0).to(eng.device)
-        sc = pkg.ScenarioLoop(eng, x0, specs, hist_cap=K1 + K2, max_age=max_age)   # max_age = 5: every ego respawns, twice
-        if fused:
+        sc = pkg.ScenarioLoop(eng, x0, SCENARIO_SPECS, hist_cap=K1 + K2, max_age=max_age, mode=mode, record=K1 + K2)
+        if fused:                                         # max_age = 5: every ego respawns, twice
             sc.run(K1); sc.run(K2)
+            iters.append(iter_totals(eng))
         else:
+            n = torch.zeros(B, dtype=torch.int64, device=eng.device)
             for _ in range(K1 + K2):
                 sc.tick()
+                n += eng.n_iter
+            iters.append(n.cpu().numpy())
         torch.cuda.synchronize()
-        outs.append(dict(x0=sc.loop.x0.clone(), path_len=eng.path_len.clone(), traj_idx=sc.pre.traj_idx.clone(),
+        out = eng.path_len if mode == "truncate" else sc.pre.cut
+        outs.append(dict(x0=sc.loop.x0.clone(), path_len=eng.path_len.clone(), cut=out.clone(), traj_idx=sc.pre.traj_idx.clone(),
                          prev_len=sc.pre.prev_len.clone(), col=sc.pre.col_flag.clone(), pst=sc.pre.status.clone(),
                          oa=eng.oa.clone(), od=eng.od.clone(), tind=eng.target_ind.clone(), status=eng.status.clone(),
                          hist=sc.loop.hist.clone(), obs=sc.obst.state.clone(), get=sc.obst.get_buf.clone(), di_ai=eng.di_ai.clone(),
-                         age=sc.loop.age.clone(), tick=sc.loop.tick_counter.clone()))
+                         age=sc.loop.age.clone(), tick=sc.loop.tick_counter.clone(), rec=sc.recorder.rec.clone(),
+                         flags=sc.recorder.flags.clone(), rec_obs=sc.recorder.obs.clone()))
     a, b = outs
     for k in a:
         assert torch.equal(a[k], b[k]), k
-    assert int((a["col"] != 0).sum()) > 0 and int((a["path_len"].cpu() < torch.from_numpy(batch.path_len)).sum()) > 0
+    assert np.array_equal(iters[0], iters[1]) and iters[0].sum() > 0
+    assert int((a["col"] != 0).sum()) > 0 and int((a["cut"] < eng.full_len).sum()) > 0
     assert int((a["pst"] != 0).sum()) == 0     # the glue never lost its footing (respawned egos restart their progress index)
+    assert (int(((a["flags"] & 6) != 0).sum()) >= B) == (max_age == 5)
 
 
 @pytest.mark.parametrize("T,K,B", ((40, 12, 64), (20, 25, 64), (40, 25, 256)))
@@ -736,13 +832,13 @@ def test_config1_on_the_real_route_planned_and_driven_on_the_device(pkg):
     print(f"config 1 on the reference's planned route: {K} ticks, {n_cut} with a cut-off, max control difference {d_ctrl:.2e}")
 
 
-@pytest.mark.parametrize("T", (30, 40, 25, 32))
-def test_large_working_sets_on_the_long_horizon_kernels(pkg, oracle, routes, T):
+@pytest.mark.parametrize("T,size", _horizons((30, 40, 25, 32), 64) + _rows([r for r in NON_PRE_ROWS if r[1] in (30, 40, 25, 32)]))
+def test_large_working_sets_on_the_long_horizon_kernels(pkg, oracle, routes, T, size):
     """Tight limits (0.05 m/s^2, 0.4 deg/s steer rate) make most of the 8T rows bind: the working set outgrows one
     wavefront's 64 lanes at T = 40 -- the only way to reach working-set positions 64+ of the four-wave kernel
     (mpc_step_reg4_kernel<40>) and the long Givens sweeps of drops in the one-wave T = 30 kernel from a test.  Compared with the
-    oracle under the same configuration."""
-    B = 64
+    oracle under the same configuration, on every kernel of these horizons."""
+    B = _batch(size)
     cfg = pkg.MPCConfig.from_json()
     cfg.MAX_ACCEL, cfg.MAX_DECEL, cfg.MAX_DSTEER = 0.05, -0.05, 0.4
     batch = pkg.synth.make_ego_batch(routes, B, T, seed=5, truncate=False, near_end_frac=0.0)
@@ -752,25 +848,28 @@ def test_large_working_sets_on_the_long_horizon_kernels(pkg, oracle, routes, T):
     eng.load_state(batch.target_ind, batch.oa, batch.od, batch.path_len)
     eng.solve(torch.from_numpy(batch.x0).to(eng.device))
     torch.cuda.synchronize()
-    p, ref = _oracle_batch(oracle, pkg, routes, batch, T, config={"MAX_ACCEL": 0.05, "MAX_DECEL": -0.05, "MAX_DSTEER": 0.4})
+    p, ref = _oracle_batch(oracle, pkg, routes, batch, T, n_threads=16,
+                           config={"MAX_ACCEL": 0.05, "MAX_DECEL": -0.05, "MAX_DSTEER": 0.4})
     st = eng.status.cpu().numpy()
     assert np.array_equal(st, ref["status"])
     ok = st == 0
     assert ok.sum() >= B // 2
     nact = np.unpackbits(ref["active_mask"].view(np.uint8), axis=1).sum(axis=1)
-    print(f"T={T}: active rows per ego: mean {nact[ok].mean():.1f}, max {nact[ok].max()}; n_iter max {ref['n_iter'].max()}")
+    print(f"T={T} B={B}: active rows per ego: mean {nact[ok].mean():.1f}, max {nact[ok].max()}; n_iter max {ref['n_iter'].max()}")
     assert nact[ok].max() > (64 if T == 40 else 40 if T == 30 else 32)
     assert np.abs(eng.oa.cpu().numpy() - ref["oa"])[ok].max() <= 1e-6
     assert np.abs(eng.od.cpu().numpy() - ref["od"])[ok].max() <= 1e-6
     assert np.array_equal(eng.active_mask.cpu().numpy().view(np.uint32)[ok], ref["active_mask"][ok])
 
 
-@pytest.mark.parametrize("T", (20, 30, 40, 16, 25, 32))
-def test_speed_rows_in_the_working_set(pkg, oracle, routes, T):
+@pytest.mark.parametrize("T,size", _horizons((20, 30, 40, 16, 25, 32), 96) +
+                         _rows([r for r in NON_PRE_ROWS if r[1] in (20, 30, 40, 16, 25, 32)]))
+def test_speed_rows_in_the_working_set(pkg, oracle, routes, T, size):
     """Egos that start at (or within 0.3 m/s of) a low speed limit with an accelerating warm start: the v_t <= speed rows
     fill the working set.  T = 30 is the case that matters: its one-wave kernel keeps NO speed rows -- it evaluates them
-    as prefix sums over the acceleration lanes and forms a row in LDS only when it enters (mpc_step_reg.inc, VS)."""
-    B = 96
+    as prefix sums over the acceleration lanes and forms a row in LDS only when it enters (mpc_step_reg.inc, VS).  Every kernel
+    of these horizons."""
+    B = _batch(size)
     batch = pkg.synth.make_ego_batch(routes, B, T, seed=11)
     rng = np.random.default_rng(5)
     batch.speed[:] = rng.uniform(1.0, 8.0, B)
@@ -780,7 +879,7 @@ def test_speed_rows_in_the_working_set(pkg, oracle, routes, T):
     eng = _engine(pkg, routes, batch, T)
     eng.solve(torch.from_numpy(batch.x0).to(eng.device))
     torch.cuda.synchronize()
-    _, ref = _oracle_batch(oracle, pkg, routes, batch, T)
+    _, ref = _oracle_batch(oracle, pkg, routes, batch, T, n_threads=16)
     st = eng.status.cpu().numpy()
     assert np.array_equal(st, ref["status"])
     ok = st == 0
@@ -790,7 +889,7 @@ def test_speed_rows_in_the_working_set(pkg, oracle, routes, T):
     vu = np.zeros(B, dtype=int)
     for cid in range(2 * T - 2, 3 * T - 1):          # canonical ids of the v_t <= speed rows
         vu += (mk[:, cid >> 5] >> (cid & 31)) & 1
-    print(f"T={T}: active speed rows per ego: mean {vu[ok].mean():.1f}, max {vu.max()}")
+    print(f"T={T} B={B}: active speed rows per ego: mean {vu[ok].mean():.1f}, max {vu.max()}")
     assert (vu[ok] >= 3).mean() > 0.5 and vu.max() >= T // 3, (vu.mean(), vu.max())
     err = max(np.abs(eng.oa.cpu().numpy() - ref["oa"])[ok].max(), np.abs(eng.od.cpu().numpy() - ref["od"])[ok].max())
     assert err <= 1e-7, err
@@ -800,7 +899,7 @@ def test_speed_rows_in_the_working_set(pkg, oracle, routes, T):
     # (0.9); the horizons added in round 3 report theirs (T = 16: 0.885 on the first run, same kernel code as T = 20) under a bar
     # that still catches a systematically different pivoting rule.
     same = (eng.n_iter.cpu().numpy() == ref["n_iter"]).mean()
-    print(f"T={T}: identical iteration counts {same:.3f}")
+    print(f"T={T} B={B}: identical iteration counts {same:.3f}")
     assert same >= (0.9 if T in TS else 0.8)
 
 
@@ -837,7 +936,8 @@ def test_long_horizon_kernels_at_scale_and_deterministic(pkg, oracle, routes, T,
 def test_max_iter_relinearisation_passes(pkg, oracle, routes, T):
     """MAX_ITER > 1 (main/lib/mpc.py:231-236): every pass re-selects the reference window with the previous pass's
     predicted speeds, rolls out the previous solution and solves again.  Three passes against the oracle's three passes;
-    a closed loop with two passes per tick through jsim_mpc_run_ticks equals the same ticks one by one."""
+    a closed loop with two passes per tick through jsim_mpc_run_ticks equals the same ticks one by one, and its iteration totals
+    are theirs added up."""
     from dataclasses import replace
     B = 96 if T <= 20 else 48
     cfg = replace(pkg.MPCConfig.from_json(), T=T, MAX_ITER=3)
@@ -867,12 +967,16 @@ def test_max_iter_relinearisation_passes(pkg, oracle, routes, T):
         e.load_state(batch.target_ind, batch.oa, batch.od, batch.path_len)
         return e, pkg.ClosedLoop(e, torch.from_numpy(batch.x0).to(e.device), hist_cap=K, max_age=40)
     e1, l1 = make()
+    iters = torch.zeros(B, dtype=torch.int64, device=e1.device)
     for _ in range(K):
         l1.tick()
+        iters += e1.n_iter
     e2, l2 = make()
     l2.run(K)
     torch.cuda.synchronize()
     assert torch.equal(l1.hist, l2.hist) and torch.equal(l1.x0, l2.x0) and torch.equal(e1.n_iter, e2.n_iter)
+    # the separate launches per tick count into jsim_mpc_iter_totals too, each tick's count summed over its passes
+    assert np.array_equal(iter_totals(e2), iters.cpu().numpy()) and int(iters.sum()) > 0
 
 
 def test_scripted_roundabout_and_arterial_obstacles(pkg, routes):

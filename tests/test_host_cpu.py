@@ -341,8 +341,14 @@ REG_DRIVER = r"""
 #include <cstdio>
 #include <initializer_list>
 #include "reg_variants.h"
-int main()
+#include <cstdlib>
+int main(int argc, char **argv)
 {
+    for (int i = 1; i + 3 < argc; i += 4) { // queries T B PRE CU: the row a launch takes on a device of CU compute units
+        const int T = std::atoi(argv[i]), B = std::atoi(argv[i + 1]), pre = std::atoi(argv[i + 2]), cu = std::atoi(argv[i + 3]);
+        const RegVariant v = select_reg_variant(T, B, pre != 0, cu, 1025);
+        std::printf("pick %d %d %d %d %d %d %d %d %d\n", T, B, pre, cu, v.W, v.T, (int)v.PRE, v.WPE, (int)v.HELP);
+    }
 #define X(w, t, p, e, h) std::printf("row %d %d %d %d %d\n", w, t, (int)p, e, (int)h);
     JSIM_REG_VARIANTS(X)
     for (int T = 1; T <= 48; ++T)
@@ -358,7 +364,8 @@ int main()
 
 def test_reg_variant_table_and_dispatch(tmp_path):
     """csrc/reg_variants.h compiled for the host: its table is config.REG_VARIANTS, every (T, B, PRE) launch_reg can see takes the
-    kernel bench.kernel_name() names (at its 256 CUs and the default thresholds), and the split build has one unit per horizon."""
+    kernel bench.kernel_name() names (at its 256 CUs and the default thresholds), the split build has one unit per horizon, and
+    the batch size the GPU tests run each row at (gpu_helpers.variant_batches) takes exactly that row."""
     import importlib.util
     import shutil
     spec = importlib.util.spec_from_file_location("bench_mod4", os.path.join(REPO, "bench.py"))
@@ -389,6 +396,20 @@ def test_reg_variant_table_and_dispatch(tmp_path):
     assert [ln[1:] for ln in out if ln[0] == "defaults"] == [["1025", "256", "80", "0"]]
     src = open(os.path.join(csrc, "jsim_mpc.hip")).read()
     assert "hipDeviceAttributeMultiprocessorCount" in src and 'reg_help_max_b(help_env, device_cu_count())' in src
+    # the GPU tests' batch sizes (gpu_helpers.variant_batches, parametrized from config.REG_VARIANTS) land on their row, on an
+    # MI355X's 256 CUs and on devices with fewer and more
+    import gpu_helpers
+    queries = [(row, B, cu) for row in cfg.REG_VARIANTS for cu in (256, 80, 304) for B in gpu_helpers.variant_batches(row, cu)]
+    args = [str(int(x)) for (_, T, pre, _, _), B, cu in queries for x in (T, B, pre, cu)]
+    picks = [tuple(int(x) for x in ln.split()[1:]) for ln in subprocess.run([exe] + args, check=True, capture_output=True,
+                                                                            text=True).stdout.splitlines() if ln.startswith("pick")]
+    assert len(picks) == len(queries) >= 3 * len(cfg.REG_VARIANTS)
+    for (row, B, cu), (T, b, pre, c, w, t, p, e, h) in zip(queries, picks):
+        assert (T, b, bool(pre), c) == (row[1], B, row[2], cu)
+        assert (w, t, bool(p), e, bool(h)) == row, (gpu_helpers.variant_id(row), B, cu)
+    assert {B for row in cfg.REG_VARIANTS for B in gpu_helpers.variant_batches(row, 256)} == {97, 256, 257, 1024, 1025}
+    assert [gpu_helpers.variant_id(r) for r in cfg.REG_VARIANTS[:5]] == ["w1-T13-pre-wpe1", "w1-T13-wpe2", "w1-T13-wpe1-help",
+                                                                          "w1-T13-pre-wpe1-help", "w1-T15-pre-wpe1"]
 
 
 def test_bench_dump_outputs_writes_float64_and_a_seeded_sample_beyond_the_cap(tmp_path):
