@@ -280,6 +280,55 @@ def mpc_step_batch(p, x0, path_id, path_len, speed, cx, cy, cyaw, path_off, targ
     return out
 
 
+def mpc_step_batch_per_config(params_list, which, x0, path_id, path_len, speed, cx, cy, cyaw, path_off, target_ind, oa, od,
+                              n_threads=1, cv=None, cv_cut=None):
+    """mpc_step_batch for a batch whose ego b has the configuration params_list[which[b]] (the per-ego table of
+    jsim_mpc_set_ego_config): one mpc_step_batch call per distinct configuration on that configuration's egos, the results
+    scattered back into [B][..] arrays.  All configurations share T and NX."""
+    which = np.asarray(which, dtype=np.int64).reshape(-1)
+    x0 = _c(x0); B = x0.shape[0]
+    if which.shape[0] != B:
+        raise ValueError("which must hold one configuration index per ego")
+    ks = np.unique(which)
+    if ks.size == 0:
+        raise ValueError("an empty batch has no configuration")
+    if len({(params_list[k].T, params_list[k].nx) for k in ks}) != 1:
+        raise ValueError("the configurations of one batch share T and NX")
+    path_id = _c(path_id, np.int32); path_len = _c(path_len, np.int32); speed = _c(speed)
+    target_ind = _c(target_ind, np.int64); oa = _c(oa); od = _c(od)
+    cv_cut = _c(cv_cut, np.int32) if cv_cut is not None else None
+    out = None
+    for k in ks:
+        sel = np.flatnonzero(which == k)
+        r = mpc_step_batch(params_list[k], x0[sel], path_id[sel], path_len[sel], speed[sel], cx, cy, cyaw, path_off, target_ind[sel],
+                           oa[sel], od[sel], n_threads=n_threads, cv=cv, cv_cut=None if cv_cut is None else cv_cut[sel])
+        if out is None:
+            out = {name: np.zeros((B,) + a.shape[1:], dtype=a.dtype) for name, a in r.items()}
+        for name, a in r.items():
+            out[name][sel] = a
+    return out
+
+
+def closed_loop_per_config(params_list, which, state, cx, cy, cyaw, path_off, n_ticks, max_age=0, n_threads=1, record=True):
+    """closed_loop for a batch whose ego b has the configuration params_list[which[b]]: one closed_loop call per distinct
+    configuration on that configuration's egos (egos are independent), `state` updated in place, the counts added up."""
+    which = np.asarray(which, dtype=np.int64).reshape(-1)
+    B = state["x0"].shape[0]
+    hist = np.zeros((n_ticks, B, 2)) if record else None
+    tot = {"n_respawn": 0, "n_iter_sum": 0, "n_fail": 0}
+    for k in np.unique(which):
+        sel = np.flatnonzero(which == k)
+        sub = {name: np.ascontiguousarray(a[sel]) for name, a in state.items()}
+        r = closed_loop(params_list[k], sub, cx, cy, cyaw, path_off, n_ticks, max_age=max_age, n_threads=n_threads, record=record)
+        for name, a in sub.items():
+            state[name][sel] = a
+        if record:
+            hist[:, sel] = r["hist"]
+        for name in tot:
+            tot[name] += r[name]
+    return dict(tot, hist=hist)
+
+
 def closed_loop(p, state, cx, cy, cyaw, path_off, n_ticks, max_age=0, n_threads=1, record=True):
     """n_ticks closed-loop ticks (MPC.step -> plant -> goal / respawn) for every ego, IN PLACE on `state`, a dict of C-contiguous
     arrays: x0 [B,4], path_id, path_len (int32), speed, target_ind (int64), oa, od [B,T], di_ai [B,2], x0_spawn, target_spawn,

@@ -6,7 +6,8 @@ import torch
 
 from conftest import PKG_NAME
 
-REG_VARIANTS = importlib.import_module(PKG_NAME + ".config").REG_VARIANTS
+_CONFIG = importlib.import_module(PKG_NAME + ".config")
+REG_VARIANTS = _CONFIG.REG_VARIANTS
 _CABI = importlib.import_module(PKG_NAME + "._cabi")
 W2_MIN_B = 1025          # launch_reg's JSIM_W2_MIN_B default (csrc/reg_variants.h); the tests never set it, nor JSIM_HELP_MAX_B
 
@@ -71,9 +72,119 @@ def oracle_batch(oracle, pkg, routes, batch, T, n_threads=1, **kw):
                                     batch.target_ind, batch.oa, batch.od, n_threads=n_threads)
 
 
-def kkt_check(eng, batch, dbg):
+# ------------------------------------------------------------------------------------------------
+# The per-ego table (BatchedMPC.set_ego_configs / jsim_mpc_set_ego_config): inputs shared by tests/test_gpu_ego_config.py and
+# tests/test_ego_config_cpu.py, which proves on the oracle alone that these inputs keep the comparisons meaningful.
+# ------------------------------------------------------------------------------------------------
+EGO_CFG_SEED, EGO_BATCH_SEED = 17, 4                  # the draws of test_per_ego_weights_one_batch
+# planted egos, next to each other so that a row read one off shows: two twins (same state, path and warm start, very different
+# rows), an ego that fails (v0 > speed) whose row brakes with -3.7, a row with tight limits beside a loose one
+PLANT_TWINS, PLANT_FAIL, PLANT_TIGHT, PLANT_LOOSE = (10, 11), 12, 13, 14
+PLANT_EGOS = PLANT_TWINS + (PLANT_FAIL, PLANT_TIGHT, PLANT_LOOSE)
+PLANT_DECEL = -3.7
+ORACLE_KEYS = ("NX", "w_perp", "w_para", "R", "Rd", "Q_v_yaw", "Qf", "GOAL_DIS", "STOP_SPEED", "MAX_ITER", "MAX_DSTEER", "MAX_ACCEL",
+               "MAX_DECEL", "JERK_WEIGHT")
+
+
+def ego_config_pool(T, n=12, seed=EGO_CFG_SEED, base=None):
+    """n distinct MPCConfigs of horizon T, drawn as test_per_ego_weights_one_batch draws them (same ranges); everything the table
+    does not carry stays `base`'s (default: the stock JSON)."""
+    from dataclasses import replace
+    rng = np.random.default_rng(seed)
+    base = base if base is not None else _CONFIG.MPCConfig.from_json()
+    return [replace(base, T=T, w_perp=float(rng.uniform(5, 40)), w_para=float(rng.uniform(0.5, 3)),
+                    R=[float(rng.uniform(0.005, 0.2)), float(rng.uniform(0.005, 0.05))],
+                    Rd=[float(rng.uniform(0.005, 10)), float(rng.uniform(0.5, 10))],
+                    Q_v_yaw=[float(rng.choice([0.0, 2.0])), float(rng.uniform(0.1, 1.0))],
+                    Qf=[float(rng.uniform(0.5, 2)), float(rng.uniform(0.5, 2)), 0.0, float(rng.uniform(0.2, 1.0))],
+                    MAX_DSTEER=float(rng.uniform(10, 60)), MAX_ACCEL=float(rng.uniform(0.5, 3)),
+                    MAX_DECEL=float(-rng.uniform(3, 10))) for _ in range(n)]
+
+
+def ego_config_table(pool, B, seed=EGO_CFG_SEED, plant=True):
+    """(cfgs, which): ego b solves with cfgs[b], a seeded pick from `pool`; egos with equal which[b] share a configuration, so the
+    oracle side can group them.  plant: the rows of PLANT_EGOS are replaced by the planted ones (which >= len(pool))."""
+    from dataclasses import replace
+    rng = np.random.default_rng(seed + 1000)
+    which = rng.integers(0, len(pool), size=B).astype(np.int64)
+    cfgs = [pool[k] for k in which]
+    if plant:
+        assert B > max(PLANT_EGOS)
+        a, b = PLANT_TWINS
+        planted = {a: replace(cfgs[a], MAX_ACCEL=0.5, w_perp=5.0), b: replace(cfgs[a], MAX_ACCEL=3.0, w_perp=40.0),
+                   PLANT_FAIL: replace(cfgs[PLANT_FAIL], MAX_DECEL=PLANT_DECEL),
+                   PLANT_TIGHT: replace(cfgs[PLANT_TIGHT], MAX_ACCEL=0.05, MAX_DSTEER=0.4),
+                   PLANT_LOOSE: replace(cfgs[PLANT_LOOSE], MAX_ACCEL=3.0, MAX_DSTEER=60.0)}
+        for k, (e, c) in enumerate(sorted(planted.items())):
+            cfgs[e], which[e] = c, len(pool) + k
+    return cfgs, which
+
+
+def plant_ego_states(routes, batch):
+    """The states that go with the planted rows, in place: the twins share one state, path and warm start -- slow, early on an
+    untruncated path with an accelerating warm start, so that MAX_ACCEL binds; so do the tight and the loose ego, off their path and
+    turned away from it, so that the steering limits matter too; PLANT_FAIL starts above its speed limit."""
+    for (a, b), lat, dyaw in ((PLANT_TWINS, 0.0, 0.0), ((PLANT_TIGHT, PLANT_LOOSE), 0.3, 0.1)):
+        r = routes[int(batch.path_id[a])]
+        s = len(r) // 6
+        batch.x0[a] = (r[s, 0] - lat * np.sin(r[s, 2]), r[s, 1] + lat * np.cos(r[s, 2]), 2.0, r[s, 2] + dyaw)
+        batch.target_ind[a], batch.path_len[a] = max(s - 3, 0), len(r)
+        batch.oa[a] = 1.0
+        for name in ("x0", "path_id", "path_len", "target_ind", "speed", "oa", "od"):
+            getattr(batch, name)[b] = getattr(batch, name)[a]
+    batch.x0[PLANT_FAIL, 2] = 9.5                       # v0 > speed: the reference's failure path, as test_step_vs_oracle plants it
+    return batch
+
+
+def ego_config_case(synth, routes, T, B, base=None, plant=True, **batch_kw):
+    """The inputs of one per-ego case, on the GPU and on the CPU alike: (batch, cfgs, which) from the draws of
+    test_per_ego_weights_one_batch (config seed 17, batch seed 4, truncated paths, a fifth of the egos near their path's end)."""
+    kw = dict(seed=EGO_BATCH_SEED, truncate=True, near_end_frac=0.2)
+    kw.update(batch_kw)
+    batch = synth.make_ego_batch(routes, B, T, **kw)
+    cfgs, which = ego_config_table(ego_config_pool(T, base=base), B, plant=plant)
+    if plant:
+        plant_ego_states(routes, batch)
+    return batch, cfgs, which
+
+
+def ego_config_rows(cfgs, reserved=0.0):
+    """The [B, 16] array of include/jsim_mpc.h for cfgs, slot 15 (`reserved`) set to `reserved`."""
+    return np.array([[c.w_perp, c.w_para, c.R[0], c.R[1], c.Rd[0], c.Rd[1], c.Q_v_yaw[0], c.Q_v_yaw[1], c.Qf[0], c.Qf[1], c.Qf[2],
+                      c.Qf[3], c.max_dsteer_rad, c.MAX_ACCEL, c.MAX_DECEL, reserved] for c in cfgs], dtype=np.float64)
+
+
+def oracle_params(oracle, cfg, T=None):
+    """oracle.make_params for an MPCConfig: every key the oracle takes from a configuration."""
+    return oracle.make_params(T=cfg.T if T is None else T, config={k: getattr(cfg, k) for k in ORACLE_KEYS})
+
+
+def oracle_params_list(oracle, cfgs, which):
+    """One OrcParams per distinct configuration, indexed by `which` (gaps, if any, stay None)."""
+    out = [None] * (int(np.max(which)) + 1)
+    for b, k in enumerate(which):
+        if out[k] is None:
+            out[k] = oracle_params(oracle, cfgs[b])
+    return out
+
+
+def oracle_batch_per_config(oracle, synth, routes, batch, cfgs, which, n_threads=16, **kw):
+    """(params_list, oracle.mpc_step_batch_per_config(..)) of a batch: every ego by the oracle with its own configuration."""
+    ps = oracle_params_list(oracle, cfgs, which)
+    cx, cy, cyaw, off = synth.pack_paths(routes)
+    return ps, oracle.mpc_step_batch_per_config(ps, which, batch.x0, batch.path_id, batch.path_len, batch.speed, cx, cy, cyaw, off,
+                                                batch.target_ind, batch.oa, batch.od, n_threads=n_threads, **kw)
+
+
+def n_active(mask):
+    """Active rows per ego of an active-mask array [B, MW] (uint32 words)."""
+    return np.unpackbits(np.ascontiguousarray(mask).view(np.uint8), axis=1).sum(axis=1)
+
+
+def kkt_check(eng, batch, dbg, cfgs=None):
     """Size-independent property: the u* the kernel returned satisfies the KKT conditions of the condensed QP the kernel built
-    (strictly convex => that IS the optimum), multipliers >= 0, complementary, active bits <=> positive multipliers."""
+    (strictly convex => that IS the optimum), multipliers >= 0, complementary, active bits <=> positive multipliers.
+    cfgs: the per-ego configurations of a run with a table (set_ego_configs) -- the limits of ego b are then cfgs[b]'s."""
     B, T = eng.B, eng.T
     st = eng.status
     ok = st == 0
@@ -92,13 +203,15 @@ def kkt_check(eng, batch, dbg):
         G[4 * T + t, 2 * t] = 1; G[5 * T + t, 2 * t] = -1
         G[6 * T + 2 * t, 2 * t + 1] = 1; G[6 * T + 2 * t + 1, 2 * t + 1] = -1
     c = eng.config
+    per = [c] * B if cfgs is None else cfgs
+    col = lambda f: torch.tensor([f(e) for e in per], dtype=torch.float64, device=eng.device)[:, None]
     h = torch.zeros(B, m, dtype=torch.float64, device=eng.device)
     x0 = torch.from_numpy(batch.x0).to(eng.device)
-    h[:, :2 * T - 2] = c.max_dsteer_rad * eng.dt
+    h[:, :2 * T - 2] = col(lambda e: e.max_dsteer_rad * eng.dt)
     h[:, 2 * T - 2:3 * T - 1] = (eng.speed - x0[:, 2])[:, None]
     h[:, 3 * T - 1:4 * T] = (x0[:, 2] - c.MIN_SPEED)[:, None]
-    h[:, 4 * T:5 * T] = c.MAX_ACCEL
-    h[:, 5 * T:6 * T] = -c.MAX_DECEL
+    h[:, 4 * T:5 * T] = col(lambda e: e.MAX_ACCEL)
+    h[:, 5 * T:6 * T] = col(lambda e: -e.MAX_DECEL)
     h[:, 6 * T:] = c.MAX_STEER_RAD
     stat = torch.einsum("bij,bj->bi", H, u) + dbg["g"] + lam @ G
     scale = dbg["g"].abs().amax(dim=1).clamp(min=1.0)

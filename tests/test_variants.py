@@ -153,9 +153,11 @@ def test_sensitivity_dropin_rereads_its_json(pkg, oracle, routes, tmp_path, monk
 @pytest.mark.parametrize("T", (20, 30, 40, 24))
 def test_per_ego_weights_one_batch(pkg, oracle, routes, T):
     """A sensitivity sweep as one launch: every ego of the batch carries its own weights and limits
-    (jsim_mpc_set_ego_config).  T = 20 / 30 / 40 / 24 = the one-wave kernel with resident and with virtual speed
-    rows, the four-wave kernel and the LDS kernel.  Each ego against the oracle run
-    with that ego's parameters; switching the table off restores the engine's configuration."""
+    (jsim_mpc_set_ego_config).  At B = 48 -- at most one ego per CU -- T = 20 runs the one-wave kernel with helper wavefronts
+    (mpc_step_reg_kernel<20, false, 1, true>, resident speed rows), T = 30 the one-wave kernel with virtual speed rows
+    (<30, false, 1>, which has no helper form), T = 40 the four-wave kernel (mpc_step_reg4_kernel<40, false>) and T = 24 the LDS
+    kernel.  Each ego against the oracle run with that ego's parameters; switching the table off restores the engine's
+    configuration.  Every other register kernel, the boundary batch sizes and the loops: tests/test_gpu_ego_config.py."""
     from dataclasses import replace
     B = 48
     rng = np.random.default_rng(17)
