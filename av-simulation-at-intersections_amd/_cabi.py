@@ -36,7 +36,7 @@ EXPORTS = (
     "jsim_mpc_set_path_speed", "jsim_mpc_set_speed_cutoff", "jsim_mpc_update_cfg", "jsim_mpc_set_ego_config", "jsim_loop_obstacles",
     "jsim_mpc_xref_deviation_goal", "jsim_loop_run_scenario",
     "jsim_loop_set_groups", "jsim_loop_predict_egos", "jsim_loop_run_interacting",
-    "jsim_loop_set_traffic", "jsim_loop_set_recorder",
+    "jsim_loop_set_traffic", "jsim_loop_set_recorder", "jsim_loop_set_vehicle_shapes",
     "jsim_comm_unique_id", "jsim_comm_init", "jsim_mpc_gather", "jsim_comm_destroy", "jsim_plan_routes",
 )
 
@@ -111,6 +111,8 @@ def load() -> C.CDLL:
     lib.jsim_loop_set_groups.argtypes = [vp, i32, i32, vp]
     lib.jsim_loop_set_traffic.restype = C.c_int
     lib.jsim_loop_set_traffic.argtypes = [vp, i32, i32, vp, vp, i32]
+    lib.jsim_loop_set_vehicle_shapes.restype = C.c_int
+    lib.jsim_loop_set_vehicle_shapes.argtypes = [vp, i32, vp]
     lib.jsim_loop_set_recorder.restype = C.c_int
     lib.jsim_loop_set_recorder.argtypes = [vp, i32, i32, vp, vp, i32, vp]
     lib.jsim_loop_predict_egos.restype = C.c_int

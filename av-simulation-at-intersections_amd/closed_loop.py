@@ -179,6 +179,52 @@ def car_circles(L: float = 2.86, width: float = 2.0, extra_length: float = 0.64)
     return width / (2 ** .5), (L / 2 + offset, L / 2 - offset)
 
 
+DIMS_KEYS = ("L", "width", "extra_length")
+
+
+def vehicle_shape(dims=None, L: float = 2.86, width: float = 2.0, extra_length: float = 0.64):
+    """One row of the shape table of jsim_loop_set_vehicle_shapes, (cc_front, cc_rear, radius, wheelbase), from the fields of
+    `obstacle_dims`: dims = dict(L=..., width=..., extra_length=...) (any missing key: the keyword's value) through car_circles.
+    Raises ValueError on an unknown key or a size that is not positive (extra_length: negative)."""
+    if dims is not None:
+        unknown = sorted(set(dims) - set(DIMS_KEYS))
+        if unknown:
+            raise ValueError(f"unknown dims key(s) {unknown}: a vehicle's dims holds {list(DIMS_KEYS)}")
+        L, width, extra_length = (float(dims.get(k, d)) for k, d in zip(DIMS_KEYS, (L, width, extra_length)))
+    if not (L > 0 and width > 0 and extra_length >= 0 and math.isfinite(L + width + extra_length)):
+        raise ValueError(f"a vehicle's L and width must be positive and its extra_length not negative (L={L}, width={width}, "
+                         f"extra_length={extra_length})")
+    radius, (c0, c1) = car_circles(L, width, extra_length)
+    return (c0, c1, radius, L)
+
+
+def shape_table(specs, default_shape):
+    """The [n, 4] float64 shape table of a flat list of vehicle specs, or None when no spec carries `dims` (nothing to
+    register).  A vehicle without dims has default_shape (a vehicle_shape row)."""
+    specs = list(specs)
+    rows = [vehicle_shape(s["dims"]) if s.get("dims") is not None else None for s in specs]
+    if all(r is None for r in rows):
+        return None
+    return np.array([default_shape if r is None else r for r in rows], dtype=np.float64).reshape(len(specs), 4)
+
+
+def _register_shapes(engine: BatchedMPC, table):
+    """jsim_loop_set_vehicle_shapes (table None: clear the context's table, when it has one)."""
+    if table is None:
+        if getattr(engine, "vehicle_shapes", None) is not None:
+            _cabi.check(engine.lib.jsim_loop_set_vehicle_shapes(engine._ctx, 0, None), engine._ctx, "jsim_loop_set_vehicle_shapes")
+        engine.vehicle_shapes = None
+        return
+    table = np.ascontiguousarray(table, dtype=np.float64)
+    if table.ndim != 2 or table.shape[1] != 4 or table.shape[0] < 1:
+        raise ValueError("a shape table is [n >= 1, 4]: (cc_front, cc_rear, radius, wheelbase) per vehicle")
+    if not (np.isfinite(table).all() and (table[:, 2:] > 0).all()):
+        raise ValueError("a shape table needs finite circle offsets and positive radii and wheelbases")
+    _cabi.check(engine.lib.jsim_loop_set_vehicle_shapes(engine._ctx, table.shape[0], table.ctypes.data_as(C.c_void_p)),
+                engine._ctx, "jsim_loop_set_vehicle_shapes")
+    engine.vehicle_shapes = table
+
+
 class PreTick:
     """The loop glue ahead of MPC.step (main/scenarios/mpc_intersection.py:104-143) for the whole batch: progress index,
     ego-path resampling, obstacle prediction, collision check, cut-off -> writes the engine's `path_len`, i.e. the batched
@@ -207,12 +253,16 @@ class PreTick:
         self.frame_window = int(frame_window)
         self.n_steps = int(math.ceil(time_horizon / eng.dt - 1e-9))          # len(np.arange(0, horizon, dt))
         self.margin = int(margin_factor) * int(math.ceil(self.radius / eng.dl))   # EXTRA_CUTOFF_MARGIN, :88-89
+        # the shape of a vehicle without dims of its own in a loop's table: obstacle_dims if given, else the ego's shape
+        self.default_shape = (c0, c1, self.radius, float(eng.L))
+        _register_shapes(eng, None)                          # an earlier loop's table on this engine does not carry over
         _cabi.check(eng.lib.jsim_loop_set_geometry(eng._ctx, c0, c1, self.radius), eng._ctx, "jsim_loop_set_geometry")
         if obstacle_dims is not None:
             oL = float(obstacle_dims["L"])
             orad, (o0, o1) = car_circles(oL, float(obstacle_dims.get("width", 2.0)), float(obstacle_dims.get("extra_length", 0.64)))
             _cabi.check(eng.lib.jsim_loop_set_obstacle_geometry(eng._ctx, o0, o1, orad, oL), eng._ctx,
                         "jsim_loop_set_obstacle_geometry")
+            self.default_shape = (o0, o1, orad, oL)
         dev, B = eng.device, eng.B
         self.traj_idx = torch.zeros(B, dtype=torch.int64, device=dev)
         self.prev_len = torch.full((B,), -1, dtype=torch.int32, device=dev)   # tmp_trajectory is None
@@ -230,11 +280,20 @@ class PreTick:
             self.cut = eng.cv_cut                        # the buffer the controller reads; updated in place every tick
         self.predict(torch.zeros(0, 6, dtype=torch.float64, device=dev))
 
-    def predict(self, obst: torch.Tensor):
-        """obst: device float64 [n_obs, 6] = (x, y, v, yaw, a, steer) per obstacle, as MovingObstacle*.get() returns."""
+    def predict(self, obst: torch.Tensor, shapes=None):
+        """obst: device float64 [n_obs, 6] = (x, y, v, yaw, a, steer) per obstacle, as MovingObstacle*.get() returns.
+        shapes: [n_obs, 4] rows (vehicle_shape) -- each obstacle predicted and tested with its own circles and wheelbase;
+        registered when it differs from the engine's table and kept for later calls (None: the table stays as it is)."""
         eng = self.eng
         if not (obst.is_cuda and obst.dtype == torch.float64 and obst.dim() == 2 and obst.shape[1] == 6 and obst.is_contiguous()):
             raise ValueError("obst must be a contiguous float64 device tensor [n_obs, 6]")
+        if shapes is not None:
+            shapes = np.asarray(shapes, dtype=np.float64)
+            if shapes.shape != (int(obst.shape[0]), 4):
+                raise ValueError(f"shapes must be [n_obs = {int(obst.shape[0])}, 4], got {shapes.shape}")
+            cur = getattr(eng, "vehicle_shapes", None)
+            if cur is None or cur.shape != shapes.shape or not np.array_equal(cur, shapes):
+                _register_shapes(eng, shapes)
         self.n_obs = int(obst.shape[0])
         self.pred = torch.zeros(max(self.n_obs, 1), self.n_steps, 3, dtype=torch.float64, device=eng.device)
         _cabi.check(eng.lib.jsim_loop_predict_obstacles(eng._ctx, self.n_obs, _ptr(obst) if self.n_obs else None,
@@ -267,6 +326,11 @@ class ScriptedObstacles:
     KINDS = {"t_intersection": 0.0, "roundabout": 1.0, "arterial": 2.0}
 
     def __init__(self, engine: BatchedMPC, specs, dt: Optional[float] = None):
+        """A spec may carry dims=dict(L=..., width=..., extra_length=...): the vehicle's own shape (vehicle_shape; `shapes`
+        holds each vehicle's row or None).  The loops register the table (shape_table); a caller that steps the vehicles itself
+        passes it to PreTick.predict(shapes=...)."""
+        specs = list(specs)
+        self.shapes = [vehicle_shape(s["dims"]) if s.get("dims") is not None else None for s in specs]
         self.eng = engine
         dt = engine.dt if dt is None else dt
         st, pr = [], []
@@ -357,7 +421,9 @@ class ScenarioLoop:
     traffic_of ([B] set indices): every ego meets its own scripted vehicles -- obstacle_specs is then a list of traffic sets
     (per-set spec lists, traffic_layout), all of whose vehicles step every tick; ego e's results are those of a ScenarioLoop
     whose obstacle_specs are set traffic_of[e], bit for bit.  chunk_ticks: ticks per fused launch (0: from a 512 MiB budget).
-    record: ticks of the full History kept on the device, the vehicles' get() tuples included (`recorder`; 0: none)."""
+    record: ticks of the full History kept on the device, the vehicles' get() tuples included (`recorder`; 0: none).
+    A spec with dims=dict(L=..., width=..., extra_length=...) gives that vehicle its own shape (vehicle_shape): a car and a
+    cyclist in one loop, or per set.  Vehicles without dims have the ego's shape; no dims anywhere: no table is registered."""
 
     _ENTRY = "jsim_loop_run_scenario"
 
@@ -367,11 +433,16 @@ class ScenarioLoop:
         if traffic_of is not None:
             layout = traffic_layout(engine.B, obstacle_specs, traffic_of)         # before any device work
             obstacle_specs = [sp for st in obstacle_specs for sp in st]
+        obstacle_specs = list(obstacle_specs)
+        shape_table(obstacle_specs, vehicle_shape())                              # validates every dims, before any device work
         self.loop = ClosedLoop(engine, x0, hist_cap=hist_cap, max_age=max_age)
         self.pre = PreTick(engine, frame_window=frame_window, mode=mode)
         self.obst = ScriptedObstacles(engine, obstacle_specs)
         self.traffic = layout
         _register_traffic(engine, *(layout if layout else (None, None)), chunk_ticks)
+        shapes = self.shapes = shape_table(obstacle_specs, self.pre.default_shape)   # no dims: the glue's default shape
+        if shapes is not None:
+            _register_shapes(engine, shapes)
         if record:
             self.loop.recorder = Recorder(self.loop, record, n_obs=self.obst.n)
 
@@ -440,7 +511,8 @@ class InteractingLoop:
     group (ascending batch index), every ego predicted like an obstacle from its tick-start state with a = 0 and the steering
     it applied last tick.  A tick is a Jacobi step: all egos solve, then all advance.  Groups are contiguous batch ranges
     (group_off [n_groups + 1], or group_sizes), 1..8 egos each; n_obs + largest group - 1 <= 8.  Egos in different groups
-    never affect each other; a group of one ego is ScenarioLoop.  Only the truncate glue, only obstacles of the ego's shape.
+    never affect each other; a group of one ego is ScenarioLoop.  Only the truncate glue.  Scripted vehicles have the ego's shape
+    unless their spec carries dims= (a cyclist beside the egos); the group mates always have the ego's.
     run(n_ticks): n_ticks ticks in one call (jsim_loop_run_interacting; separate launches per tick).
     traffic_of ([n_groups] set indices): every group meets its own scripted vehicles -- obstacle_specs is then a list of traffic
     sets (traffic_layout); the vehicles of a group's set + the group - 1 <= 8, per group.
@@ -460,6 +532,8 @@ class InteractingLoop:
             n_obs = len(obstacle_specs)
             if n_obs + int(np.diff(off).max()) - 1 > MAX_GROUP:
                 raise ValueError(f"{n_obs} scripted obstacles + the largest group ({int(np.diff(off).max())}) - 1 > {MAX_GROUP}")
+        obstacle_specs = list(obstacle_specs)
+        shape_table(obstacle_specs, vehicle_shape())                              # validates every dims, before any device work
         self.group_off = off
         self.loop = ClosedLoop(engine, x0, hist_cap=hist_cap, max_age=max_age)
         self.pre = PreTick(engine, frame_window=frame_window)
@@ -469,6 +543,9 @@ class InteractingLoop:
         _cabi.check(eng.lib.jsim_loop_set_groups(eng._ctx, eng.B, len(off) - 1, off.ctypes.data_as(C.c_void_p)), eng._ctx,
                     "jsim_loop_set_groups")
         _register_traffic(engine, *(layout if layout else (None, None)))
+        shapes = self.shapes = shape_table(obstacle_specs, self.pre.default_shape)   # no dims: the glue's default shape
+        if shapes is not None:
+            _register_shapes(engine, shapes)
         if record:
             self.loop.recorder = Recorder(self.loop, record, n_obs=self.obst.n)
 

@@ -1349,6 +1349,12 @@ struct jsim_ctx {
     DevArray<double4> d_pred_bc;   // [JSIM_MAX_OBS] of the current single-tick prediction
     double occ0 = 0, occ1 = 0, ocol_radius = 0, oL = 0; // the obstacles' circles / wheelbase (jsim_loop_set_obstacle_geometry); default: the ego's
     int have_ogeom = 0;
+    // per-vehicle shapes (jsim_loop_set_vehicle_shapes): (cc0, cc1, radius, L) of each scripted vehicle and its (thr, thr_sq)
+    // against the egos' radius; n_shapes = 0: none, the global obstacle geometry above holds for all
+    DevArray<double4> d_shapes;    // [n_shapes]
+    DevArray<double2> d_othr;      // [n_shapes]
+    std::vector<double> h_shapes;  // host copy [n_shapes][4] (the thresholds follow jsim_loop_set_geometry)
+    int n_shapes = 0;
     DevArray<double2> d_pcc;
     DevArray<double2> d_pred_cc;
     int pred_n_obs = 0, pred_n_steps = 0;
@@ -1636,6 +1642,7 @@ static PreP fill_prep(const jsim_ctx *ctx, int B, int n_obs, int n_steps, int fr
     P.dt = c.dt; P.max_accel = c.max_accel; P.max_speed = c.max_speed; P.thr = ctx->col_radius + ctx->ocol_radius; // min_distance: 2 * radius, or car radius + bicycle radius
     P.thr_sq = jsim_sqrt_threshold(P.thr);
     P.pxy = ctx->d_pxy; P.pcc = ctx->d_pcc; P.poff = ctx->d_poff; P.pred_cc = ctx->d_pred_cc; P.pred_bc = ctx->d_pred_bc;
+    P.othr = ctx->n_shapes > 0 ? ctx->d_othr.p : nullptr;
     return P;
 }
 
@@ -2097,6 +2104,30 @@ extern "C" int jsim_plan_routes(int device_id, int32_t n_routes, const double *s
     return 0;
 }
 
+// the shape table's (thr, thr_sq) rows: check_collision_moving_bicycle's min_distance = the egos' radius + the vehicle's own
+static int upload_shape_thresholds(jsim_ctx *ctx)
+{
+    if (ctx->n_shapes == 0) return 0;
+    std::vector<double2> th((size_t)ctx->n_shapes);
+    for (int i = 0; i < ctx->n_shapes; ++i) {
+        const double thr = ctx->col_radius + ctx->h_shapes[4 * (size_t)i + 2];
+        th[i] = double2{thr, jsim_sqrt_threshold(thr)};
+    }
+    HIP_TRY(ctx, hipDeviceSynchronize()); // launches in flight on any stream may still read the table that is replaced
+    HIP_TRY(ctx, ctx->d_othr.reserve(ctx->n_shapes));
+    HIP_TRY(ctx, hipMemcpy(ctx->d_othr, th.data(), sizeof(double2) * ctx->n_shapes, hipMemcpyHostToDevice));
+    return 0;
+}
+
+// A registered shape table must be the call's: one row per scripted vehicle (a call without vehicles passes)
+static int check_shapes(jsim_ctx *ctx, const char *fn, int n_obs)
+{
+    if (ctx->n_shapes > 0 && n_obs > 0 && n_obs != ctx->n_shapes)
+        return fail(ctx, -22, "%s: n_obs=%d, but the shape table (jsim_loop_set_vehicle_shapes) holds %d vehicles", fn, n_obs,
+                    ctx->n_shapes);
+    return 0;
+}
+
 extern "C" int jsim_loop_set_geometry(jsim_ctx *ctx, double cc_front, double cc_rear, double radius)
 {
     if (!ctx) return fail(nullptr, -22, "jsim_loop_set_geometry: null ctx");
@@ -2107,6 +2138,7 @@ extern "C" int jsim_loop_set_geometry(jsim_ctx *ctx, double cc_front, double cc_
     if (!ctx->have_ogeom) { ctx->occ0 = cc_front; ctx->occ1 = cc_rear; ctx->ocol_radius = radius; ctx->oL = ctx->cfg.L; }
     HIP_TRY(ctx, ctx->d_pred_cc.reserve(JSIM_MAX_OBS * JSIM_MAX_PRED * 2));
     HIP_TRY(ctx, ctx->d_pred_bc.reserve(JSIM_MAX_OBS));
+    if (int rc = upload_shape_thresholds(ctx)) return rc;
     return upload_circle_centres(ctx);
 }
 
@@ -2120,11 +2152,43 @@ extern "C" int jsim_loop_set_obstacle_geometry(jsim_ctx *ctx, double cc_front, d
     return 0;
 }
 
+// ---- Per-vehicle shapes: each scripted vehicle is predicted, stepped and tested with its own circles and wheelbase ----
+extern "C" int jsim_loop_set_vehicle_shapes(jsim_ctx *ctx, int32_t n, const double *shapes)
+{
+    const char *const F = "jsim_loop_set_vehicle_shapes";
+    if (!ctx) return fail(nullptr, -22, "%s: null ctx", F);
+    DeviceGuard dev_guard(ctx->device);
+    JSIM_GUARD_OK(ctx);
+    if (n < 0) return fail(ctx, -22, "%s: n=%d", F, n);
+    if (n > 0) {
+        if (!shapes) return fail(ctx, -22, "%s: null shapes", F);
+        if (!ctx->have_geom) return fail(ctx, -22, "%s: jsim_loop_set_geometry has not been called", F);
+        for (int i = 0; i < n; ++i)
+            if (!(shapes[4 * (size_t)i + 2] > 0) || !(shapes[4 * (size_t)i + 3] > 0) || !std::isfinite(shapes[4 * (size_t)i]) ||
+                !std::isfinite(shapes[4 * (size_t)i + 1]))
+                return fail(ctx, -22, "%s: vehicle %d: radius and wheelbase must be positive, the circle offsets finite", F, i);
+    }
+    if (n == 0) { ctx->n_shapes = 0; ctx->h_shapes.clear(); return 0; }
+    // (the device copies are written before the table is switched: a failed upload leaves the context without one; launches
+    // in flight on any stream may still read the table that is replaced: they finish first)
+    HIP_TRY(ctx, hipDeviceSynchronize());
+    ctx->n_shapes = 0;
+    static_assert(sizeof(double4) == 4 * sizeof(double), "a shape row is one double4");
+    HIP_TRY(ctx, ctx->d_shapes.reserve(n));
+    HIP_TRY(ctx, hipMemcpy(ctx->d_shapes, shapes, sizeof(double4) * n, hipMemcpyHostToDevice));
+    ctx->h_shapes.assign(shapes, shapes + 4 * (size_t)n);
+    ctx->n_shapes = n;
+    if (int rc = upload_shape_thresholds(ctx)) { ctx->n_shapes = 0; return rc; }
+    return 0;
+}
+
+static const double4 *shapes_p(const jsim_ctx *ctx) { return ctx->n_shapes > 0 ? ctx->d_shapes.p : nullptr; }
+
 // obstacle_predict_kernel on n_ticks consecutive ticks' get() tuples (one block per tick)
 static void launch_obstacle_predict(const jsim_ctx *ctx, int n_obs, int n_steps, const double *get, double *pred, double2 *pred_cc,
                                     double4 *pred_bc, int n_ticks, hipStream_t s)
 {
-    const ObsP P = {n_obs, n_steps, ctx->cfg.dt, ctx->oL, ctx->occ0, ctx->occ1, get, pred, pred_cc, pred_bc};
+    const ObsP P = {n_obs, n_steps, ctx->cfg.dt, ctx->oL, ctx->occ0, ctx->occ1, get, pred, pred_cc, pred_bc, shapes_p(ctx)};
     hipLaunchKernelGGL(obstacle_predict_kernel, dim3(n_ticks), dim3(64), 0, s, P);
 }
 
@@ -2132,7 +2196,7 @@ static void launch_obstacle_predict(const jsim_ctx *ctx, int n_obs, int n_steps,
 static void launch_obstacle_predict_grid(const jsim_ctx *ctx, int n_obs, int n_steps, const double *get, double2 *pred_cc,
                                          double4 *pred_bc, int n_ticks, hipStream_t s)
 {
-    const ObsP P = {n_obs, n_steps, ctx->cfg.dt, ctx->oL, ctx->occ0, ctx->occ1, get, nullptr, pred_cc, pred_bc};
+    const ObsP P = {n_obs, n_steps, ctx->cfg.dt, ctx->oL, ctx->occ0, ctx->occ1, get, nullptr, pred_cc, pred_bc, shapes_p(ctx)};
     hipLaunchKernelGGL(obstacle_predict_grid_kernel, dim3((n_obs + 63) / 64, n_ticks), dim3(64), 0, s, P);
 }
 
@@ -2145,7 +2209,7 @@ static TrafficP traffic_p(const jsim_ctx *ctx)
 
 static ObsStepP obstacle_step_p(const jsim_ctx *ctx, int n_obs, int do_step, double *state, const double *param, double *get)
 {
-    return ObsStepP{n_obs, do_step, ctx->have_ogeom ? ctx->oL : ctx->cfg.L, state, param, get, nullptr, nullptr, 0};
+    return ObsStepP{n_obs, do_step, ctx->have_ogeom ? ctx->oL : ctx->cfg.L, state, param, get, nullptr, nullptr, 0, shapes_p(ctx)};
 }
 
 // the same, with the recorder's obstacle tuples (when one is registered) at the slots of the device tick counter
@@ -2166,6 +2230,7 @@ extern "C" int jsim_loop_predict_obstacles(jsim_ctx *ctx, int32_t n_obs, const d
     if (!ctx->have_geom) return fail(ctx, -22, "jsim_loop_predict_obstacles: jsim_loop_set_geometry has not been called");
     if (n_obs < 0 || n_obs > JSIM_MAX_OBS || n_steps < 1 || n_steps > JSIM_MAX_PRED)
         return fail(ctx, -22, "jsim_loop_predict_obstacles: n_obs=%d (max %d), n_steps=%d (max %d)", n_obs, JSIM_MAX_OBS, n_steps, JSIM_MAX_PRED);
+    if (int rc = check_shapes(ctx, "jsim_loop_predict_obstacles", n_obs)) return rc;
     ctx->pred_n_obs = n_obs; ctx->pred_n_steps = n_steps;
     if (n_obs == 0) return 0;
     if (!obst || !pred) return fail(ctx, -22, "jsim_loop_predict_obstacles: null device pointer");
@@ -2188,6 +2253,7 @@ extern "C" int jsim_loop_pre_tick(jsim_ctx *ctx, int32_t B, const double *x0, co
         return fail(ctx, -22, "jsim_loop_pre_tick: null device pointer");
     if (!ctx->d_pxy || !ctx->d_pcc) return fail(ctx, -22, "jsim_loop_pre_tick: paths / geometry not set");
     if (dbg_res_idx && !dbg_n_res) return fail(ctx, -22, "jsim_loop_pre_tick: dbg_res_idx needs dbg_n_res");
+    if (int rc = check_shapes(ctx, "jsim_loop_pre_tick", ctx->pred_n_obs)) return rc;
     PreP P = fill_prep(ctx, B, ctx->pred_n_obs, ctx->pred_n_steps, frame_window, margin);
     P.x0 = x0; P.path_id = path_id; P.traj_idx = (long long *)traj_idx; P.prev_path_len = prev_path_len; P.path_len = path_len;
     P.col_flag = col_flag; P.col_xy = col_xy; P.first_idx = first_idx; P.status = status;
@@ -2246,6 +2312,7 @@ extern "C" int jsim_loop_obstacles(jsim_ctx *ctx, int32_t n_obs, double *state, 
     JSIM_GUARD_OK(ctx);
     if (n_obs < 0 || n_obs > JSIM_MAX_OBS) return fail(ctx, -22, "jsim_loop_obstacles: n_obs=%d (max %d)", n_obs, JSIM_MAX_OBS);
     if (n_obs == 0) return 0;
+    if (int rc = check_shapes(ctx, "jsim_loop_obstacles", n_obs)) return rc;
     if (!state || !param) return fail(ctx, -22, "jsim_loop_obstacles: null device pointer");
     hipLaunchKernelGGL(obstacle_step_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream,
                        obstacle_step_p(ctx, n_obs, do_step ? 1 : 0, state, param, get));
@@ -2303,7 +2370,8 @@ static int run_host_ticks(jsim_ctx *ctx, int B, int n_ticks, const StepBufs &S, 
         Q.x0 = S.x0; Q.path_id = S.path_id; Q.traj_idx = (long long *)G->traj_idx; Q.prev_path_len = G->prev_path_len;
         Q.path_len = glue_out(ctx, S, *G); Q.col_flag = G->col_flag; Q.status = G->pre_status;
         if (grid) { Q.pred_cc = ctx->d_pred_all; Q.pred_bc = ctx->d_bc_all; }
-        GP = GroupP{ctx->d_group_of, ctx->d_group_off, ctx->d_ego_cc, ctx->d_ego_bc, G->n_obs};
+        const double mate_thr = 2.0 * ctx->col_radius; // check_collision_moving_cars between two egos
+        GP = GroupP{ctx->d_group_of, ctx->d_group_off, ctx->d_ego_cc, ctx->d_ego_bc, G->n_obs, mate_thr, jsim_sqrt_threshold(mate_thr)};
     }
     auto obstacles = [&](int do_step) { // get(), or get() then step()
         if (G->n_obs == 0) return;
@@ -2454,6 +2522,7 @@ extern "C" int jsim_loop_run_scenario(jsim_ctx *ctx, int32_t B, int32_t n_ticks,
         return fail(ctx, -22, "%s: n_obs=%d (max %d), n_steps=%d (max %d)", F, n_obs, JSIM_MAX_OBS, n_steps, JSIM_MAX_PRED);
     if (traffic)
         if (int rc = check_traffic(ctx, F, B, n_obs)) return rc;
+    if (int rc = check_shapes(ctx, F, n_obs)) return rc;
     if (int rc = check_glue(ctx, F, G)) return rc;
     if (speed_cutoff && !ctx->cv_cut) return fail(ctx, -22, "%s: the speed-cut-off glue needs jsim_mpc_set_speed_cutoff first", F);
     hipStream_t s = (hipStream_t)stream;
@@ -2618,7 +2687,7 @@ extern "C" int jsim_loop_run_interacting(jsim_ctx *ctx, int32_t B, int32_t n_tic
     JSIM_GUARD_OK(ctx);
     if (B < 0 || n_ticks < 0 || frame_window < 0 || frame_window > 32 || margin < 0) return fail(ctx, -22, "%s: bad argument", F);
     if (speed_cutoff) return fail(ctx, -22, "%s: only the truncate glue is supported (speed_cutoff = 1)", F);
-    if (ctx->have_ogeom)
+    if (ctx->have_ogeom && ctx->n_shapes == 0) // (a shape table gives the scripted vehicles their own thresholds beside the mates')
         return fail(ctx, -22, "%s: egos cannot be mixed with obstacles of another shape (jsim_loop_set_obstacle_geometry has been called)", F);
     if (ctx->n_groups == 0 || ctx->group_B != B) return fail(ctx, -22, "%s: no groups set for B=%d (jsim_loop_set_groups)", F, B);
     const bool traffic = ctx->n_sets > 0;
@@ -2639,6 +2708,7 @@ extern "C" int jsim_loop_run_interacting(jsim_ctx *ctx, int32_t B, int32_t n_tic
                             JSIM_MAX_OBS);
         }
     }
+    if (int rc = check_shapes(ctx, F, n_obs)) return rc;
     if (B == 0 || n_ticks == 0) return 0;
     const StepBufs S = {x0, path_id, path_len, speed, target_ind, oa, od, ox, oy, ov, oyaw, xref, active_mask, status, n_iter};
     const AdvanceBufs A = {di_ai, x0_spawn, target_spawn, age, max_age, hist, tick, hist_cap, n_respawn};

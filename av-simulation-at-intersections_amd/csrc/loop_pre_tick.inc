@@ -25,6 +25,7 @@ struct ObsP {
     double4 *pred_bc;   // [n_obs] (x, y, r, -): a circle around ALL predicted circle centres of the obstacle (inflated beyond
                         // rounding): an ego whose own circles stay clear of it skips the obstacle's collision rows
     // blockIdx.x = tick of a K-tick batch: obst, pred_cc and pred_bc advance by one tick's worth per block (pred is per call only)
+    const double4 *shape; // [n_obs] (cc0, cc1, radius, L) of each vehicle (jsim_loop_set_vehicle_shapes), NULL: L, cc0, cc1 above for all
 };
 
 // lib/moving_obstacles_prediction.py:21-47 (yaw uses the UPDATED speed), circle centres lib/trajectories.py:11-37.  Obstacle o
@@ -39,16 +40,19 @@ __device__ __forceinline__ void obstacle_predict_one(const ObsP &P, int o, int t
     double x = ob[6 * o], y = ob[6 * o + 1], v = ob[6 * o + 2], yaw = ob[6 * o + 3];
     const double a = ob[6 * o + 4], st = ob[6 * o + 5];
     const double tn = tan(st);
+    // the vehicle's own wheelbase and circle offsets, or the launch's for all
+    double L = P.L, cc0 = P.cc0, cc1 = P.cc1;
+    if (P.shape) { const double4 sh = P.shape[o]; cc0 = sh.x; cc1 = sh.y; L = sh.w; }
     for (int i = 0; i < P.n_steps; ++i) {
         x += v * cos(yaw) * P.dt;
         y += v * sin(yaw) * P.dt;
         v += a * P.dt;
-        yaw += (v / P.L) * tn * P.dt;
+        yaw += (v / L) * tn * P.dt;
         const size_t k = (size_t)o * P.n_steps + i;
         if (P.pred) { P.pred[3 * k] = x; P.pred[3 * k + 1] = y; P.pred[3 * k + 2] = yaw; }
         const double c = cos(yaw), s = sin(yaw);
-        pcc[2 * k] = double2{c * P.cc0 - s * 0.0 + x, s * P.cc0 + c * 0.0 + y};
-        pcc[2 * k + 1] = double2{c * P.cc1 - s * 0.0 + x, s * P.cc1 + c * 0.0 + y};
+        pcc[2 * k] = double2{c * cc0 - s * 0.0 + x, s * cc0 + c * 0.0 + y};
+        pcc[2 * k + 1] = double2{c * cc1 - s * 0.0 + x, s * cc1 + c * 0.0 + y};
         for (int b = 0; b < 2; ++b) {
             const double2 q = pcc[2 * k + b];
             bx0 = fmin(bx0, q.x); bx1 = fmax(bx1, q.x); by0 = fmin(by0, q.y); by1 = fmax(by1, q.y);
@@ -122,6 +126,9 @@ struct PreP {
     int *status;              // out
     int *dbg_res_idx;         // [B][JSIM_MAX_RES] kept indices (may be NULL)
     int *dbg_n_res;           // [B]
+    // per-vehicle shapes (jsim_loop_set_vehicle_shapes): (thr, thr_sq) of each of the n_obs vehicles -- ego radius + its own
+    // radius -- in the order of pred_cc / pred_bc; NULL: thr / thr_sq above for all
+    const double2 *othr;
 };
 
 // What one tick of the glue decides for one ego.  status != JSIM_OK: nothing else is valid (the reference raised / the
@@ -138,6 +145,7 @@ struct PreScratch {
     double2 occ[JSIM_MAX_OBS * JSIM_MAX_PRED * 2];
     double stepbuf[128]; // [0, 64): zeros; [64, 128): the point-to-point distances of the current chunk
     int olist[JSIM_MAX_OBS]; // the obstacles whose bounding circle comes within reach of the ego's resampled path
+    double2 othr[JSIM_MAX_OBS]; // (thr, thr_sq) of each of the ego's obstacles: its slice of PreP.othr, or PreP.thr / thr_sq
 };
 
 // One wavefront = one ego.  pred_cc: this tick's obstacle circle centres [n_obs][n_steps][2]; (sx, sy, sv): the ego's pose;
@@ -146,11 +154,12 @@ struct PreScratch {
 // BLOCK: the caller's workgroup has several wavefronts that all run this function on the same scratch (the four-wave T = 40 kernel):
 // its phases are separated by workgroup barriers.  Otherwise ONE wavefront runs it -- alone in its workgroup or beside helper
 // wavefronts that must not be woken -- and what it hands from lane to lane through LDS only needs the compiler's order kept.
-// OCC_READY: the caller has already put the P.n_obs obstacles' circle centres into W.occ (group_pre_tick_kernel gathers
-// scripted obstacles and group mates there) and pred_cc is not read.
+// OCC_READY: the caller has already put the P.n_obs obstacles' circle centres into W.occ and their thresholds into W.othr
+// (group_pre_tick_kernel gathers scripted obstacles and group mates there); pred_cc and othr are not read.
+// othr: the ego's slice of P.othr (its obstacles' own thresholds), or NULL: P.thr / P.thr_sq for every obstacle.
 #define JSIM_PRE_SYNC() do { if (BLOCK) __syncthreads(); else { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); } } while (0)
 template <bool BLOCK = false, bool OCC_READY = false>
-__device__ __forceinline__ PreOut jsim_pre_tick_ego(const PreP &P, const double2 *pred_cc, const double4 *pred_bc, PreScratch &W, int lane, int ego,
+__device__ __forceinline__ PreOut jsim_pre_tick_ego(const PreP &P, const double2 *pred_cc, const double4 *pred_bc, const double2 *othr_g, PreScratch &W, int lane, int ego,
                                                     long long off, int M, double sx, double sy, double sv, long long idx0,
                                                     int prev)
 {
@@ -159,13 +168,16 @@ __device__ __forceinline__ PreOut jsim_pre_tick_ego(const PreP &P, const double2
     double2 *const occ = W.occ;
     double *const stepbuf = W.stepbuf;
     const int *const olist = W.olist;
+    const double2 *const othr = W.othr;
     PreOut out;
     out.status = JSIM_OK; out.idx = (int)idx0; out.path_len = M; out.col = 0; out.first = -1; out.cx = 0.0; out.cy = 0.0;
     int status = JSIM_OK;
 
-    // obstacle circle centres -> LDS
-    if (!OCC_READY)
+    // obstacle circle centres and thresholds -> LDS
+    if (!OCC_READY) {
         for (int e = lane; e < P.n_obs * P.n_steps * 2; e += 64) occ[e] = pred_cc[e];
+        if (lane < P.n_obs) W.othr[lane] = othr_g ? othr_g[lane] : double2{P.thr, P.thr_sq};
+    }
     stepbuf[lane] = 0.0;
 
     // ---- progress index (mpc_intersection.py:106-109): nearest index in direction on the FULL path
@@ -294,7 +306,7 @@ __device__ __forceinline__ PreOut jsim_pre_tick_ego(const PreP &P, const double2
         if (lane < P.n_obs) {
             const double4 bc = pred_bc[lane];
             const double dx = bc.x - emx, dy = bc.y - emy;
-            near = sqrt(dx * dx + dy * dy) - bc.z - er <= P.thr;
+            near = sqrt(dx * dx + dy * dy) - bc.z - er <= othr[lane].x;
         }
         const unsigned long long nm = __ballot(near);
         na = __popcll(nm);
@@ -320,6 +332,7 @@ __device__ __forceinline__ PreOut jsim_pre_tick_ego(const PreP &P, const double2
                 const int o = olist[ao - a * na];
                 const int offk = kk - w;
                 const double2 *oc = &occ[(size_t)o * Pn * 2 + b];
+                const double thr_sq = othr[o].y;  // the obstacle's own threshold: one LDS read per row slot
                 for (int fl = 0; fl < fcnt; ++fl) {
                     const int f = f0 + fl;
                     const int fa = f < n_res - 1 ? f : n_res - 1;
@@ -329,7 +342,7 @@ __device__ __forceinline__ PreOut jsim_pre_tick_ego(const PreP &P, const double2
                     const double2 pa = ecc[fa][a];
                     const double2 po = oc[2 * j];
                     const double dx = pa.x - po.x, dy = pa.y - po.y;
-                    if (dx * dx + dy * dy <= P.thr_sq) { // == (sqrt(dx*dx + dy*dy) <= thr), without the square root
+                    if (dx * dx + dy * dy <= thr_sq) { // == (sqrt(dx*dx + dy*dy) <= thr), without the square root
                         const long long key = ((long long)(fl * R + rr) << 32) | ((long long)o << 16) | ((long long)j << 1) | b;
                         if (key < best) best = key;
                     }
@@ -355,6 +368,7 @@ __device__ __forceinline__ PreOut jsim_pre_tick_ego(const PreP &P, const double2
     if (!any_hit) return out;
     // ---- first point of the detailed path whose front (then rear) circle touches that obstacle circle (:111-118)
     const double2 hp = occ[((size_t)hit_o * P.n_steps + hit_j) * 2 + hit_b];
+    const double hthr = othr[hit_o].x;
     int first = 0;
     {
         bool found = false;
@@ -363,7 +377,7 @@ __device__ __forceinline__ PreOut jsim_pre_tick_ego(const PreP &P, const double2
             for (int i = lane; i < n; i += 64) {
                 const double2 c = dcc[2 * i + a];
                 const double dx = hp.x - c.x, dy = hp.y - c.y;
-                if (sqrt(dx * dx + dy * dy) <= P.thr && i < bi) bi = i;
+                if (sqrt(dx * dx + dy * dy) <= hthr && i < bi) bi = i;
             }
             double bd = (double)bi;
             int dummy = lane;
@@ -407,7 +421,8 @@ __global__ __launch_bounds__(64) void loop_pre_tick_kernel(PreP P, TrafficP X)
     const ObsSlice sl = traffic_slice(X, ego, P.n_obs);
     PreP Q = P;
     Q.n_obs = sl.n;
-    const PreOut o = jsim_pre_tick_ego(Q, P.pred_cc + (size_t)sl.first * P.n_steps * 2, P.pred_bc + sl.first, W, lane, ego, off, M,
+    const PreOut o = jsim_pre_tick_ego(Q, P.pred_cc + (size_t)sl.first * P.n_steps * 2, P.pred_bc + sl.first,
+                                       P.othr ? P.othr + sl.first : nullptr, W, lane, ego, off, M,
                                        P.x0[4 * ego], P.x0[4 * ego + 1], P.x0[4 * ego + 2], P.traj_idx[ego], P.prev_path_len[ego]);
     if (lane != 0) return;
     P.status[ego] = o.status;
@@ -479,11 +494,13 @@ struct GroupP {
     const double2 *ego_cc;   // [B][n_steps][2] (ego_predict_kernel)
     const double4 *ego_bc;   // [B]
     int n_scripted;          // scripted obstacles in P.pred_cc / P.pred_bc (P.n_obs is ignored); with traffic sets: all sets' vehicles
+    double mate_thr, mate_thr_sq; // the ego / ego threshold (2 * the egos' radius) of the group mates' rows
 };
 
 // loop_pre_tick_kernel for interacting egos: one wavefront per ego gathers the scripted predictions, then those of its group
 // mates in ascending batch index (skipping itself), into the LDS view jsim_pre_tick_ego reads, and runs the same glue.  The
-// scripted ones are its traffic set's (X), or all G.n_scripted without a layout.
+// scripted ones are its traffic set's (X), or all G.n_scripted without a layout; their thresholds are the shape table's
+// (P.othr) or P.thr, the mates' the ego / ego one.
 #ifndef JSIM_KERNEL_TU /* (a kernel translation unit of the split build holds the register kernels only) */
 __global__ __launch_bounds__(64) void group_pre_tick_kernel(PreP P, GroupP G, TrafficP X)
 {
@@ -505,10 +522,13 @@ __global__ __launch_bounds__(64) void group_pre_tick_kernel(PreP P, GroupP G, Tr
         double2 *dst = W.occ + (size_t)(ns + m) * per;
         for (int e = lane; e < per; e += 64) dst[e] = src[e];
     }
-    if (lane < ns) bc[lane] = P.pred_bc[sl.first + lane];
-    else if (lane < ns + n_mates) {
+    if (lane < ns) {
+        bc[lane] = P.pred_bc[sl.first + lane];
+        W.othr[lane] = P.othr ? P.othr[sl.first + lane] : double2{P.thr, P.thr_sq};
+    } else if (lane < ns + n_mates) {
         const int m = lane - ns;
         bc[lane] = G.ego_bc[g0 + m + (g0 + m >= ego ? 1 : 0)];
+        W.othr[lane] = double2{G.mate_thr, G.mate_thr_sq};
     }
     JSIM_PRE_SYNC();
     PreP Q = P;
@@ -516,7 +536,7 @@ __global__ __launch_bounds__(64) void group_pre_tick_kernel(PreP P, GroupP G, Tr
     const int pid = P.path_id[ego];
     const long long off = P.poff[pid];
     const int M = (int)(P.poff[pid + 1] - off);
-    const PreOut o = jsim_pre_tick_ego<false, true>(Q, nullptr, bc, W, lane, ego, off, M, P.x0[4 * ego], P.x0[4 * ego + 1],
+    const PreOut o = jsim_pre_tick_ego<false, true>(Q, nullptr, bc, nullptr, W, lane, ego, off, M, P.x0[4 * ego], P.x0[4 * ego + 1],
                                                      P.x0[4 * ego + 2], P.traj_idx[ego], P.prev_path_len[ego]);
     if (lane != 0) return;
     P.status[ego] = o.status;
@@ -537,7 +557,7 @@ __global__ __launch_bounds__(64) void group_pre_tick_kernel(PreP P, GroupP G, Tr
 // steer) is written for the prediction kernel.  One thread per obstacle.
 struct ObsStepP {
     int n_obs, do_step;
-    double L;
+    double L;             // wheelbase of every vehicle without a shape table
     double *state;        // [n_obs][4]  xc, yc, theta, counter
     const double *param;  // [n_obs][8]  direction (+-1), turning (0/1), speed, offset (<= 0: none), x_turn, dt, kind, initial_speed
     double *get;          // [n_obs][6]  x, y, v, yaw, a, steer  (state BEFORE the step, like o.get() ahead of o.step())
@@ -546,6 +566,7 @@ struct ObsStepP {
     double *rec;
     const int *tick;
     int rec_cap;
+    const double4 *shape; // [n_obs] (cc0, cc1, radius, L) of each vehicle (jsim_loop_set_vehicle_shapes), NULL: L above for all
 };
 
 __device__ __forceinline__ double obstacle_steer(double dir, double turning, double xc, double theta, double x_turn)
@@ -600,7 +621,8 @@ __device__ __forceinline__ void obstacle_step_one(const ObsStepP &P, int o)
         P.get[6 * o + 5] = steer;
     }
     if (P.do_step) { // Bicycle.step (main/bicycle/main.py:28-41), then counter += 1
-        const double xd = v * cos(th), yd = v * sin(th), thd = (v / P.L) * tan(steer);
+        const double L = P.shape ? P.shape[o].w : P.L;
+        const double xd = v * cos(th), yd = v * sin(th), thd = (v / L) * tan(steer);
         xc += xd * dt; yc += yd * dt; th += thd * dt;
         P.state[4 * o] = xc; P.state[4 * o + 1] = yc; P.state[4 * o + 3] = cnt + 1.0;
     }

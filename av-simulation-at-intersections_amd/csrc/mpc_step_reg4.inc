@@ -115,9 +115,11 @@ __global__ __launch_bounds__(256, JSIM_REG4_MINW) void mpc_step_reg4_kernel(cons
     long long pre_idx = 0;
     int pre_prev = -1, pre_col = 0, pre_st = JSIM_OK, Mfull = 0, pre_cut = -1;
     ObsSlice pre_obs = {0, 0};   // the ego's slice of the obstacle tables: its traffic set, or all of them
+    const double2 *pre_othr = nullptr; // .. and of the per-vehicle thresholds (NULL: no shape table)
     if (PRE) {
         pre_obs = traffic_slice(Q.traffic, ego, Q.pre.n_obs);
         pre_obs.first = uni(pre_obs.first); pre_obs.n = uni(pre_obs.n);
+        if (Q.pre.othr) pre_othr = Q.pre.othr + pre_obs.first;
         pre_idx = Q.traj_idx[ego];
         pre_prev = Q.prev_len[ego];
         Mfull = (int)(gp(Pv.poff)[pid + 1] - off);
@@ -154,7 +156,7 @@ __global__ __launch_bounds__(256, JSIM_REG4_MINW) void mpc_step_reg4_kernel(cons
         PreP pre = Q.pre;
         pre.n_obs = pre_obs.n;
         const PreOut o = jsim_pre_tick_ego<true>(pre, Q.pred_cc_all + ((size_t)tk * Q.pre.n_obs + pre_obs.first) * Q.pre.n_steps * 2,
-                                           Q.pred_bc_all + (size_t)tk * Q.pre.n_obs + pre_obs.first, W, lane, ego,
+                                           Q.pred_bc_all + (size_t)tk * Q.pre.n_obs + pre_obs.first, pre_othr, W, lane, ego,
                                            off, Mfull, sx, sy, sv, pre_idx, pre_prev);
         pre_st = o.status;
         if (o.status == JSIM_OK) {

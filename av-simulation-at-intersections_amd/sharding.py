@@ -68,6 +68,9 @@ class CabiGather:
         if getattr(engine, "traffic_layout", None) is not None and self.world > 1:
             raise ValueError("a traffic-set layout (ScenarioLoop / InteractingLoop traffic_of) is not sharded across ranks: "
                              "give every rank its own engine, batch and layout")
+        if getattr(engine, "vehicle_shapes", None) is not None and self.world > 1:
+            raise ValueError("a vehicle shape table (dims= in an obstacle spec, PreTick.predict(shapes=...)) is not sharded across "
+                             "ranks: give every rank its own engine, batch and table")
         self._refuse_recorder()
         lib = engine.lib
         if unique_id is None:

@@ -182,6 +182,25 @@ int jsim_loop_run_scenario(jsim_ctx *ctx, int32_t B, int32_t n_ticks, double *x0
  * main/lib/collision_avoidance.py:126-166 (min_distance = car radius + bicycle radius, same row order).  Without this call
  * the obstacles have the ego's geometry (check_collision_moving_cars). */
 int jsim_loop_set_obstacle_geometry(jsim_ctx *ctx, double cc_front, double cc_rear, double radius, double wheelbase);
+/* ---- Per-vehicle shapes: a car AND a cyclist in one loop.  The reference has two collision checks,
+ * check_collision_moving_cars (main/lib/collision_avoidance.py:85-124) and check_collision_moving_bicycle
+ * (main/lib/collision_avoidance.py:126-165), which differ in the obstacle's circles and in min_distance = car radius + the obstacle's radius, and one prediction,
+ * main/lib/moving_obstacles_prediction.py:21-47, which takes the obstacle's wheelbase and circles from its car_dimensions.
+ * jsim_loop_set_vehicle_shapes: shapes [n][4] (HOST) = (cc_front, cc_rear, radius, wheelbase) of each scripted vehicle -- the
+ *   arguments of jsim_loop_set_obstacle_geometry -- in the order of the obstacle tables: [n_obs] of a shared obstacle list, or
+ *   the [total] flat order of jsim_loop_set_traffic.  Vehicle i is predicted and stepped with its own wheelbase, its circle
+ *   centres use its own offsets, and an ego circle touches one of its circles when sqrt(dx^2 + dy^2) <= ego radius + radius_i
+ *   -- in the bounding-circle prune, the pair table and the first touching point of the detailed path alike.  Row order,
+ *   first-hit rule, cut-off and margin are unchanged.  n = 0 clears the table: every vehicle has the global obstacle geometry
+ *   again.  Needs jsim_loop_set_geometry first (the thresholds follow a later call of it).  Registering a table (and that
+ *   later call) waits for the device to finish what is in flight, on every stream, before the device copies are replaced.
+ *   Refused (-22), the previous table kept: a radius or wheelbase that is not positive, an offset that is not finite.
+ *   While a table is registered, jsim_loop_obstacles, jsim_loop_predict_obstacles, jsim_loop_pre_tick, jsim_loop_run_scenario
+ *   and jsim_loop_run_interacting refuse (-22) an n_obs (a total, with a traffic layout) other than n; a call without any
+ *   obstacle (n_obs = 0) passes.  jsim_loop_run_interacting runs scripted vehicles of any shape beside the group mates, which
+ *   keep the ego's shape and the ego / ego threshold; without a table it still refuses after jsim_loop_set_obstacle_geometry.
+ *   A table in which every row is the global geometry changes no result bit. */
+int jsim_loop_set_vehicle_shapes(jsim_ctx *ctx, int32_t n, const double *shapes /* host, [n][4] */);
 /* Scripted obstacle vehicles of main/lib/moving_obstacles.py -- MovingObstacleTIntersection (:166-232, kind 0),
  * MovingObstacleRoundabout (:28-124, kind 1), MovingObstacleArterial (:126-164, kind 2): state [n_obs][4] = (xc, yc, theta,
  * counter) in/out, param [n_obs][8] = (direction +-1, turning 0/1, speed, offset seconds (<= 0: none), x_turn, dt, kind,
@@ -207,7 +226,7 @@ int jsim_loop_pre_tick(jsim_ctx *ctx, int32_t B, const double *x0, const int32_t
  *   jsim_loop_run_scenario: obstacles get() -> their prediction -> the egos' prediction -> glue per ego -> MPC.step -> plant,
  *   history, goal / respawn -> glue reset of respawned egos -> obstacles step().  Separate launches per tick.  Refused (-22):
  *   no groups for this B, n_obs + (largest group - 1) > 8, speed_cutoff != 0, or after jsim_loop_set_obstacle_geometry
- *   (the collision rows have one distance threshold).  A group of one ego gives jsim_loop_run_scenario's results. */
+ *   without a shape table (jsim_loop_set_vehicle_shapes: then the collision rows have one distance threshold).  A group of one ego gives jsim_loop_run_scenario's results. */
 int jsim_loop_set_groups(jsim_ctx *ctx, int32_t B, int32_t n_groups, const int32_t *group_off);
 int jsim_loop_predict_egos(jsim_ctx *ctx, int32_t B, const double *x0, const double *di_ai, int32_t n_steps, double *pred,
                            void *stream);
