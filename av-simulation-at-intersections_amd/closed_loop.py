@@ -4,13 +4,12 @@ bookkeeping launch per tick, nothing leaving the device between ticks."""
 from __future__ import annotations
 
 import ctypes as C
+import math
 import warnings
 from typing import Optional
 
 import numpy as np
 import torch
-
-import math
 
 from . import _cabi, history
 from .batched import BatchedMPC, _ptr
@@ -81,7 +80,7 @@ class Recorder:
 def _register_recorder(engine: BatchedMPC, rec: Optional[Recorder]):
     """jsim_loop_set_recorder (None: clear).  The engine keeps the registered buffers alive; the recorder it replaces is marked
     superseded."""
-    old = getattr(engine, "_recorder", None)
+    old = engine._recorder
     if old is not None and old is not rec:
         old.superseded = True
     if rec is None:
@@ -102,8 +101,7 @@ class ClosedLoop:
     (`recorder`, a Recorder; 0: none)."""
 
     def __init__(self, engine: BatchedMPC, x0: torch.Tensor, hist_cap: int = 0, max_age: int = 0, record: int = 0):
-        self.eng = engine
-        eng = engine
+        eng = self.eng = engine
         eng._check_x0(x0)
         self.x0 = x0
         dev = eng.device
@@ -118,19 +116,22 @@ class ClosedLoop:
         self._graph: Optional[torch.cuda.CUDAGraph] = None
         self._graph_ticks = 0
         self.recorder: Optional[Recorder] = None
-        if getattr(eng, "_recorder", None) is not None:
+        if eng._recorder is not None:
             _register_recorder(eng, None)            # an earlier loop's recorder on this engine stops recording
         if record:
             self.recorder = Recorder(self, record)
 
+    def _advance_args(self):
+        """What tick() passes to jsim_loop_advance after (ctx, B)."""
+        eng = self.eng
+        return (_ptr(self.x0), _ptr(eng.oa), _ptr(eng.od), _ptr(eng.status), _ptr(eng.di_ai), _ptr(eng.target_ind),
+                _ptr(eng.path_id), _ptr(eng.path_len), _ptr(self.x0_spawn), _ptr(self.target_spawn), _ptr(self.age), self.max_age,
+                _ptr(self.hist), _ptr(self.tick_counter), self.hist_cap, _ptr(self.n_respawn), eng._stream())
+
     def tick(self):
         eng = self.eng
         eng.solve(self.x0)
-        _cabi.check(eng.lib.jsim_loop_advance(
-            eng._ctx, eng.B, _ptr(self.x0), _ptr(eng.oa), _ptr(eng.od), _ptr(eng.status), _ptr(eng.di_ai),
-            _ptr(eng.target_ind), _ptr(eng.path_id), _ptr(eng.path_len), _ptr(self.x0_spawn),
-            _ptr(self.target_spawn), _ptr(self.age), self.max_age, _ptr(self.hist), _ptr(self.tick_counter),
-            self.hist_cap, _ptr(self.n_respawn), eng._stream()), eng._ctx, "jsim_loop_advance")
+        _cabi.check(eng.lib.jsim_loop_advance(eng._ctx, eng.B, *self._advance_args()), eng._ctx, "jsim_loop_advance")
 
     def _loop_args(self):
         """Checks x0; returns the step and advance buffers the multi-tick entry points take after (ctx, B, n_ticks)."""
@@ -211,7 +212,7 @@ def shape_table(specs, default_shape):
 def _register_shapes(engine: BatchedMPC, table):
     """jsim_loop_set_vehicle_shapes (table None: clear the context's table, when it has one)."""
     if table is None:
-        if getattr(engine, "vehicle_shapes", None) is not None:
+        if engine.vehicle_shapes is not None:
             _cabi.check(engine.lib.jsim_loop_set_vehicle_shapes(engine._ctx, 0, None), engine._ctx, "jsim_loop_set_vehicle_shapes")
         engine.vehicle_shapes = None
         return
@@ -247,8 +248,7 @@ class PreTick:
         if mode == "speed_cutoff" and engine.cv is None:
             raise ValueError("mode='speed_cutoff' needs an engine with a speed reference (cv)")
         self.mode = mode
-        self.eng = engine
-        eng = engine
+        eng = self.eng = engine
         self.radius, (c0, c1) = car_circles(eng.L, car_width, extra_length)
         self.frame_window = int(frame_window)
         self.n_steps = int(math.ceil(time_horizon / eng.dt - 1e-9))          # len(np.arange(0, horizon, dt))
@@ -291,7 +291,7 @@ class PreTick:
             shapes = np.asarray(shapes, dtype=np.float64)
             if shapes.shape != (int(obst.shape[0]), 4):
                 raise ValueError(f"shapes must be [n_obs = {int(obst.shape[0])}, 4], got {shapes.shape}")
-            cur = getattr(eng, "vehicle_shapes", None)
+            cur = eng.vehicle_shapes
             if cur is None or cur.shape != shapes.shape or not np.array_equal(cur, shapes):
                 _register_shapes(eng, shapes)
         self.n_obs = int(obst.shape[0])
@@ -413,7 +413,56 @@ def _register_traffic(engine: BatchedMPC, set_of, obs_off, chunk_ticks: int = 0)
     engine.traffic_layout = (set_of, obs_off)
 
 
-class ScenarioLoop:
+class _GlueLoop:
+    """What ScenarioLoop and InteractingLoop share: construction, run() and the recorder.  The loop constructed last on an engine
+    owns its context's tables: ClosedLoop and PreTick clear an earlier recorder and shape table, the rest is registered here."""
+
+    def __init__(self, engine: BatchedMPC, x0: torch.Tensor, obstacle_specs, hist_cap, max_age, frame_window, mode, traffic_of,
+                 chunk_ticks, record, group_off=None):
+        layout = None
+        if traffic_of is not None:
+            layout = traffic_layout(engine.B, obstacle_specs, traffic_of, group_off=group_off)   # before any device work
+            obstacle_specs = [sp for st in obstacle_specs for sp in st]
+        obstacle_specs = list(obstacle_specs)
+        shape_table(obstacle_specs, vehicle_shape())                              # validates every dims, before any device work
+        self.loop = ClosedLoop(engine, x0, hist_cap=hist_cap, max_age=max_age)
+        self.pre = PreTick(engine, frame_window=frame_window, mode=mode)
+        self.obst = ScriptedObstacles(engine, obstacle_specs)
+        self.traffic = layout
+        self._register_groups()
+        _register_traffic(engine, *(layout if layout else (None, None)), chunk_ticks)
+        shapes = self.shapes = shape_table(obstacle_specs, self.pre.default_shape)   # no dims: the glue's default shape
+        if shapes is not None:
+            _register_shapes(engine, shapes)
+        if record:
+            self.loop.recorder = Recorder(self.loop, record, n_obs=self.obst.n)      # last: it records obst.n vehicles
+
+    def _register_groups(self):
+        """Only InteractingLoop has groups."""
+
+    @property
+    def recorder(self) -> Optional[Recorder]:
+        return self.loop.recorder
+
+    def _run_args(self, n_obs: Optional[int] = None, speed_cutoff: Optional[int] = None):
+        """What run() passes to the entry point after (ctx, B, n_ticks); n_obs / speed_cutoff: a value other than the loop's own."""
+        loop, pre, ob = self.loop, self.pre, self.obst
+        if speed_cutoff is None:
+            speed_cutoff = 1 if pre.mode == "speed_cutoff" else 0
+        return (*loop._loop_args(), _ptr(pre.traj_idx), _ptr(pre.prev_len), _ptr(pre.col_flag), _ptr(pre.status), pre.frame_window,
+                pre.margin, ob.n if n_obs is None else n_obs, _ptr(ob.state) if ob.n else None, _ptr(ob.param) if ob.n else None,
+                _ptr(ob.get_buf) if ob.n else None, pre.n_steps, speed_cutoff, loop.eng._stream())
+
+    def run(self, n_ticks: int):
+        """n_ticks ticks in one call (_ENTRY), same results as n_ticks x tick().  jsim_loop_run_scenario with a register kernel
+        (config.ONE_WAVE_HORIZONS / FOUR_WAVE_HORIZONS) and MAX_ITER = 1: three launches -- the scripted obstacles rolled forward
+        n_ticks ticks, their predictions for every tick, one fused launch of n_ticks x (glue + solve + plant) per wavefront."""
+        eng, lib = self.loop.eng, self.loop.eng.lib
+        _cabi.check(getattr(lib, self._ENTRY)(eng._ctx, eng.B, int(n_ticks), *self._run_args()), eng._ctx, self._ENTRY)
+        self.pre.n_obs = self.obst.n
+
+
+class ScenarioLoop(_GlueLoop):
     """The reference scenario loop for a batch, entirely on the device (main/scenarios/mpc_intersection.py:99-163):
     obstacle get() -> prediction -> progress index / resample / collision / cut-off -> MPC.step -> plant, history, goal ->
     obstacle step().
@@ -429,26 +478,7 @@ class ScenarioLoop:
 
     def __init__(self, engine: BatchedMPC, x0: torch.Tensor, obstacle_specs, hist_cap: int = 0, max_age: int = 0,
                  frame_window: int = 10, mode: str = "truncate", traffic_of=None, chunk_ticks: int = 0, record: int = 0):
-        layout = None
-        if traffic_of is not None:
-            layout = traffic_layout(engine.B, obstacle_specs, traffic_of)         # before any device work
-            obstacle_specs = [sp for st in obstacle_specs for sp in st]
-        obstacle_specs = list(obstacle_specs)
-        shape_table(obstacle_specs, vehicle_shape())                              # validates every dims, before any device work
-        self.loop = ClosedLoop(engine, x0, hist_cap=hist_cap, max_age=max_age)
-        self.pre = PreTick(engine, frame_window=frame_window, mode=mode)
-        self.obst = ScriptedObstacles(engine, obstacle_specs)
-        self.traffic = layout
-        _register_traffic(engine, *(layout if layout else (None, None)), chunk_ticks)
-        shapes = self.shapes = shape_table(obstacle_specs, self.pre.default_shape)   # no dims: the glue's default shape
-        if shapes is not None:
-            _register_shapes(engine, shapes)
-        if record:
-            self.loop.recorder = Recorder(self.loop, record, n_obs=self.obst.n)
-
-    @property
-    def recorder(self) -> Optional[Recorder]:
-        return self.loop.recorder
+        super().__init__(engine, x0, obstacle_specs, hist_cap, max_age, frame_window, mode, traffic_of, chunk_ticks, record)
 
     def tick(self):
         if self.traffic is not None:             # the vehicles of all sets: the gridded kernels of run()
@@ -465,19 +495,6 @@ class ScenarioLoop:
         rec = self.loop.recorder
         if rec is not None and rec.n_obs:
             rec._record_obstacles(g)
-
-    def run(self, n_ticks: int):
-        """n_ticks ticks in one call (jsim_loop_run_scenario).  With a register kernel (config.ONE_WAVE_HORIZONS / FOUR_WAVE_HORIZONS) and MAX_ITER = 1
-        three launches -- the scripted obstacles rolled forward n_ticks ticks, their predictions for every
-        tick, and one fused launch in which each ego's wavefront does glue + solve + plant n_ticks times.  Same results as
-        n_ticks x tick().  (InteractingLoop.run: the same arguments to jsim_loop_run_interacting.)"""
-        loop, pre, ob, eng = self.loop, self.pre, self.obst, self.loop.eng
-        _cabi.check(getattr(eng.lib, self._ENTRY)(
-            eng._ctx, eng.B, int(n_ticks), *loop._loop_args(), _ptr(pre.traj_idx), _ptr(pre.prev_len), _ptr(pre.col_flag),
-            _ptr(pre.status), pre.frame_window, pre.margin, ob.n, _ptr(ob.state) if ob.n else None,
-            _ptr(ob.param) if ob.n else None, _ptr(ob.get_buf) if ob.n else None, pre.n_steps,
-            1 if pre.mode == "speed_cutoff" else 0, eng._stream()), eng._ctx, self._ENTRY)
-        pre.n_obs = ob.n
 
 
 MAX_GROUP = MAX_OBS    # the obstacles of an ego are the scripted ones plus its group mates
@@ -505,7 +522,7 @@ def group_offsets(B: int, group_off=None, group_sizes=None) -> np.ndarray:
     return off.astype(np.int32)
 
 
-class InteractingLoop:
+class InteractingLoop(_GlueLoop):
     """Several automated vehicles at one intersection that react to each other (main/scenarios/interactive_mpc.py:117-190):
     ScenarioLoop's tick, where the obstacles of an ego are the scripted vehicles (spec order) and then the OTHER egos of its
     group (ascending batch index), every ego predicted like an obstacle from its tick-start state with a = 0 and the steering
@@ -519,37 +536,20 @@ class InteractingLoop:
     record: ticks of the full History kept on the device (`recorder`, as ScenarioLoop's); the egos are recorded like any other."""
 
     _ENTRY = "jsim_loop_run_interacting"
-    run = ScenarioLoop.run
 
     def __init__(self, engine: BatchedMPC, x0: torch.Tensor, group_off=None, obstacle_specs=(), hist_cap: int = 0,
                  max_age: int = 0, frame_window: int = 20, group_sizes=None, traffic_of=None, record: int = 0):
-        off = group_offsets(engine.B, group_off, group_sizes)        # before any device work
-        layout = None
-        if traffic_of is not None:
-            layout = traffic_layout(engine.B, obstacle_specs, traffic_of, group_off=off)
-            obstacle_specs = [sp for st in obstacle_specs for sp in st]
-        else:
-            n_obs = len(obstacle_specs)
-            if n_obs + int(np.diff(off).max()) - 1 > MAX_GROUP:
-                raise ValueError(f"{n_obs} scripted obstacles + the largest group ({int(np.diff(off).max())}) - 1 > {MAX_GROUP}")
-        obstacle_specs = list(obstacle_specs)
-        shape_table(obstacle_specs, vehicle_shape())                              # validates every dims, before any device work
-        self.group_off = off
-        self.loop = ClosedLoop(engine, x0, hist_cap=hist_cap, max_age=max_age)
-        self.pre = PreTick(engine, frame_window=frame_window)
-        self.obst = ScriptedObstacles(engine, list(obstacle_specs))
-        self.traffic = layout
-        eng = engine
+        off = self.group_off = group_offsets(engine.B, group_off, group_sizes)        # before any device work
+        n_obs, big = len(obstacle_specs), int(np.diff(off).max())
+        if traffic_of is None and n_obs + big - 1 > MAX_GROUP:
+            raise ValueError(f"{n_obs} scripted obstacles + the largest group ({big}) - 1 > {MAX_GROUP}")
+        super().__init__(engine, x0, obstacle_specs, hist_cap, max_age, frame_window, "truncate", traffic_of, 0, record,
+                         group_off=off)
+
+    def _register_groups(self):
+        eng, off = self.loop.eng, self.group_off
         _cabi.check(eng.lib.jsim_loop_set_groups(eng._ctx, eng.B, len(off) - 1, off.ctypes.data_as(C.c_void_p)), eng._ctx,
                     "jsim_loop_set_groups")
-        _register_traffic(engine, *(layout if layout else (None, None)))
-        shapes = self.shapes = shape_table(obstacle_specs, self.pre.default_shape)   # no dims: the glue's default shape
-        if shapes is not None:
-            _register_shapes(engine, shapes)
-        if record:
-            self.loop.recorder = Recorder(self.loop, record, n_obs=self.obst.n)
-
-    recorder = ScenarioLoop.recorder
 
     def pred_egos(self) -> torch.Tensor:
         """[B, n_steps, 3] (x, y, yaw): every ego's prediction from its current state, as the next tick will make it."""

@@ -83,8 +83,16 @@ def ego_batch(routes, B: int, T: int, rank: int = 0) -> S.EgoBatch:
     return S.make_ego_batch(routes, B, T, seed=1 + rank, truncate=False)
 
 
-def make_engine(routes, batch: S.EgoBatch, T: int, device) -> Tuple[BatchedMPC, torch.Tensor]:
-    eng = BatchedMPC(routes, batch.path_id, dl=S.DL, T=T, speed=batch.speed, device=device, smooth=False)
+def make_engine(routes, batch: S.EgoBatch, T: int, device, mode: str = "truncate") -> Tuple[BatchedMPC, torch.Tensor]:
+    """(engine, x0 on its device).  mode="speed_cutoff": the mpc_with_speed engine with the full-speed reference on every route, for
+    the loops' speed-cut-off glue."""
+    kw = {}
+    if mode == "speed_cutoff":
+        from . import mpc_with_speed as m
+        kw = dict(config=m.config, cv=[np.full(len(r), m.MAX_SPEED) for r in routes])
+    elif mode != "truncate":
+        raise ValueError("mode must be 'truncate' or 'speed_cutoff'")
+    eng = BatchedMPC(routes, batch.path_id, dl=S.DL, T=T, speed=batch.speed, device=device, smooth=False, **kw)
     eng.load_state(batch.target_ind, batch.oa, batch.od, batch.path_len)
     return eng, torch.from_numpy(batch.x0).to(eng.device)
 

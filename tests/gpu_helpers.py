@@ -1,7 +1,9 @@
 """Shared pieces of the GPU parity tests (tests/test_gpu_*.py)."""
+import dataclasses
 import importlib
 
 import numpy as np
+import pytest
 import torch
 
 from conftest import PKG_NAME
@@ -52,15 +54,76 @@ def iter_totals(eng, reset=False):
     return tot.astype(np.int64)
 
 
+# ------------------------------------------------------------------------------------------------
+# The closed loops (ClosedLoop / ScenarioLoop / InteractingLoop): workload fixtures, engines, and snapshots of everything a loop
+# leaves on the device.  A test module takes the fixtures by importing them.
+# ------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def W(pkg):
+    return importlib.import_module(PKG_NAME + ".workloads")
+
+
+@pytest.fixture(scope="module")
+def iroutes(W):
+    return W.route_table(False)[0]
+
+
+def sub_batch(batch, idx):
+    """The egos idx of an EgoBatch."""
+    return dataclasses.replace(batch, **{f.name: getattr(batch, f.name)[idx] for f in dataclasses.fields(batch)})
+
+
+def loop_engine(pkg, routes, batch, T, mode="truncate"):
+    """(engine, x0) for a loop of glue `mode` on device 0: workloads.make_engine."""
+    return pkg.workloads.make_engine(routes, batch, T, "cuda:0", mode=mode)
+
+
+def loop_state(loop, idx=None, exclude=()):
+    """Clones of every per-ego buffer of a ScenarioLoop / InteractingLoop (rows idx): loop, glue and engine buffers, the predicted
+    states, the speed cut-off when the glue has one, the history, and the recorder's records when one is attached."""
+    eng, cl, pre = loop.loop.eng, loop.loop, loop.pre
+    d = dict(x0=cl.x0, path_len=eng.path_len, target_ind=eng.target_ind, traj_idx=pre.traj_idx, prev_len=pre.prev_len,
+             col_flag=pre.col_flag, pre_status=pre.status, status=eng.status, oa=eng.oa, od=eng.od, di_ai=eng.di_ai, age=cl.age,
+             ox=eng.ox, oy=eng.oy, ov=eng.ov, oyaw=eng.oyaw)
+    if pre.cut is not None:
+        d["cut"] = pre.cut
+    if idx is not None:
+        d = {k: v.index_select(0, idx) for k, v in d.items()}
+    by_tick = dict(hist=cl.hist)                                  # [ticks, B, ...]
+    if loop.recorder is not None:
+        by_tick.update(rec=loop.recorder.rec, rec_flags=loop.recorder.flags)
+    d.update({k: v if idx is None else v.index_select(1, idx) for k, v in by_tick.items() if v is not None})
+    return {k: v.clone() for k, v in d.items() if k not in exclude}
+
+
+def obstacle_state(loop, lo=0, hi=None):
+    """Clones of the scripted vehicles lo..hi of a loop: states, get() tuples, and the recorder's tuples when it keeps them."""
+    hi = loop.obst.n if hi is None else hi
+    d = dict(state=loop.obst.state[lo:hi], get=loop.obst.get_buf[lo:hi])
+    if loop.recorder is not None and loop.recorder.obs is not None:
+        d["rec_obs"] = loop.recorder.obs[:, lo:hi]
+    return {k: v.clone() for k, v in d.items()}
+
+
+def assert_state_equal(a, b, what):
+    assert a.keys() == b.keys()
+    for k in a:
+        assert torch.equal(a[k], b[k]), (what, k)
+
+
 def engine(pkg, routes, batch, T, **kw):
     eng = pkg.BatchedMPC(routes, batch.path_id, dl=pkg.synth.DL, T=T, speed=batch.speed, device="cuda:0", smooth=False, **kw)
     eng.load_state(batch.target_ind, batch.oa, batch.od, batch.path_len)
     return eng
 
 
-def debug_bufs(eng):
+def debug_bufs(eng, n=None):
+    """The debug outputs of BatchedMPC.solve; with n (the QP's variables: 2T, 2T + 1 for the acceleration-state variant) only the
+    condensed QP and its multipliers."""
     B, T = eng.B, eng.T
     f = dict(dtype=torch.float64, device=eng.device)
+    if n is not None:
+        return {"H": torch.zeros(B, n, n, **f), "g": torch.zeros(B, n, **f), "lam": torch.zeros(B, 8 * T, **f)}
     return {"xbar": torch.zeros(B, 4, T + 1, **f), "ref_idx": torch.zeros(B, T + 1, dtype=torch.int64, device=eng.device),
             "H": torch.zeros(B, 2 * T, 2 * T, **f), "g": torch.zeros(B, 2 * T, **f), "lam": torch.zeros(B, 8 * T, **f)}
 

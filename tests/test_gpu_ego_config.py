@@ -29,8 +29,8 @@ import pytest
 import torch
 
 from conftest import PKG_NAME
-from gpu_helpers import (PLANT_DECEL, PLANT_EGOS, PLANT_FAIL, PLANT_LOOSE, PLANT_TIGHT, PLANT_TWINS, cu_count, ego_config_case,
-                         ego_config_pool, ego_config_rows, ego_config_table, iter_totals, kkt_check, n_active,
+from gpu_helpers import (PLANT_DECEL, PLANT_EGOS, PLANT_FAIL, PLANT_LOOSE, PLANT_TIGHT, PLANT_TWINS, cu_count, debug_bufs,
+                         ego_config_case, ego_config_pool, ego_config_rows, ego_config_table, engine, iter_totals, kkt_check, n_active,
                          oracle_batch_per_config, oracle_params_list, variant_batches, variant_id)
 
 pytestmark = pytest.mark.gpu
@@ -87,18 +87,6 @@ def _base(pkg, kind, T):
     return replace(src[kind](), T=T)
 
 
-def _engine(pkg, routes, batch, T, base, **kw):
-    eng = pkg.BatchedMPC(routes, batch.path_id, dl=pkg.synth.DL, T=T, speed=batch.speed, device="cuda:0", smooth=False, config=base, **kw)
-    eng.load_state(batch.target_ind, batch.oa, batch.od, batch.path_len)
-    return eng
-
-
-def _debug_bufs(eng, n):
-    B, T = eng.B, eng.T
-    f = dict(dtype=torch.float64, device=eng.device)
-    return {"H": torch.zeros(B, n, n, **f), "g": torch.zeros(B, n, **f), "lam": torch.zeros(B, 8 * T, **f)}
-
-
 def _snap(eng, **more):
     out = {k: getattr(eng, k).clone() for k in NAMES}
     out.update({k: v.clone() for k, v in more.items()})
@@ -133,9 +121,9 @@ def test_step_against_oracle_with_table(pkg, oracle, routes, T, size, kind):
     x0 = torch.from_numpy(batch.x0).cuda()
     runs = []
     for table in (cfgs, ego_config_rows(cfgs, reserved=np.nan)):           # the list form (reserved = 0.0), the array form
-        eng = _engine(pkg, routes, batch, T, base)
+        eng = engine(pkg, routes, batch, T, config=base)
         eng.set_ego_configs(table)
-        dbg = _debug_bufs(eng, n)
+        dbg = debug_bufs(eng, n)
         eng.solve(x0, debug=dbg)
         torch.cuda.synchronize()
         runs.append((eng, dbg))
@@ -207,7 +195,7 @@ def test_table_of_context_rows_changes_nothing(pkg, routes, T, size, kind):
     x0 = torch.from_numpy(batch.x0).cuda()
     steps, loops = [], []
     for table in (None, [ctx] * B):
-        eng = _engine(pkg, routes, batch, T, ctx)
+        eng = engine(pkg, routes, batch, T, config=ctx)
         eng.set_ego_configs(table)
         eng.solve(x0)
         torch.cuda.synchronize()
@@ -237,7 +225,7 @@ def test_row_b_means_ego_b(pkg, routes, T, size, kind):
     B, base = _batch(size), _base(pkg, kind, T)
     batch, cfgs, _ = ego_config_case(pkg.synth, routes, T, B, base=base)
     x0 = torch.from_numpy(batch.x0).cuda()
-    eng = _engine(pkg, routes, batch, T, base)
+    eng = engine(pkg, routes, batch, T, config=base)
     eng.set_ego_configs(cfgs)
     eng.solve(x0)
     torch.cuda.synchronize()
@@ -246,7 +234,7 @@ def test_row_b_means_ego_b(pkg, routes, T, size, kind):
     egos = list(PLANT_EGOS) + [int(e) for e in np.random.default_rng(T).choice(others, 3, replace=False)]
     n_diff = 0
     for e in egos:
-        one = _engine(pkg, routes, batch, T, cfgs[e])
+        one = engine(pkg, routes, batch, T, config=cfgs[e])
         one.solve(x0)
         torch.cuda.synchronize()
         got = _snap(one)
@@ -281,7 +269,7 @@ def test_fused_ticks_equal_single_ticks_with_table(pkg, routes, T, size, kind):
     base = _base(pkg, kind, T)
     batch, cfgs, _ = ego_config_case(pkg.synth, routes, T, B, base=base, truncate=False, near_end_frac=0.5)
     def make():
-        eng = _engine(pkg, routes, batch, T, base)
+        eng = engine(pkg, routes, batch, T, config=base)
         eng.set_ego_configs(cfgs)
         return eng, pkg.ClosedLoop(eng, torch.from_numpy(batch.x0).cuda(), hist_cap=K, max_age=5, record=K)
     e1, l1 = make()
@@ -313,7 +301,7 @@ def test_fused_scenario_loop_equals_tick_by_tick_with_table(pkg, routes, T, size
     states, iters = [], []
     for fused in (False, True):
         batch, cfgs, _ = ego_config_case(pkg.synth, routes, T, B, base=base, seed=17, truncate=False, near_end_frac=0.1)
-        eng = _engine(pkg, routes, batch, T, base, **kw)
+        eng = engine(pkg, routes, batch, T, config=base, **kw)
         eng.set_ego_configs(cfgs)
         sc = pkg.ScenarioLoop(eng, torch.from_numpy(batch.x0).cuda(), SCENARIO_SPECS, hist_cap=K1 + K2, max_age=5, mode=mode, record=K1 + K2)
         if fused:
@@ -351,7 +339,7 @@ def test_interacting_loop_with_table(pkg):
     cfgs, _ = ego_config_table(ego_config_pool(T, base=base), batch.x0.shape[0])
     states = []
     for mode in ("ticks", "run", "no table"):
-        eng = _engine(pkg, iroutes, batch, T, base)
+        eng = engine(pkg, iroutes, batch, T, config=base)
         eng.set_ego_configs(None if mode == "no table" else cfgs)
         il = pkg.InteractingLoop(eng, torch.from_numpy(batch.x0).cuda(), group_sizes=sizes, hist_cap=K, max_age=7, frame_window=20, record=K)
         if mode == "ticks":
@@ -374,7 +362,7 @@ def test_max_iter_passes_with_table(pkg, oracle, routes, T):
     B = 96 if T <= 20 else 48
     base = replace(_base(pkg, "stock", T), MAX_ITER=3)
     batch, cfgs, which = ego_config_case(pkg.synth, routes, T, B, base=base)
-    eng = _engine(pkg, routes, batch, T, base)
+    eng = engine(pkg, routes, batch, T, config=base)
     eng.set_ego_configs(cfgs)
     eng.solve(torch.from_numpy(batch.x0).cuda())
     torch.cuda.synchronize()
@@ -402,7 +390,7 @@ def test_path_speed_reference_with_table(pkg, oracle, routes):
     batch, cfgs, which = ego_config_case(pkg.synth, routes, T, B, base=base, seed=9, near_end_frac=0.3)
     cut = np.where(np.random.default_rng(3).random(B) < 0.6, np.random.default_rng(4).integers(0, 720, size=B), -1).astype(np.int32)
     cvs = [np.full(len(r), m.MAX_SPEED) for r in routes]
-    eng = _engine(pkg, routes, batch, T, base, cv=cvs)
+    eng = engine(pkg, routes, batch, T, config=base, cv=cvs)
     eng.set_speed_cutoff(cut)
     eng.set_ego_configs(cfgs)
     eng.solve(torch.from_numpy(batch.x0).cuda())
@@ -434,7 +422,7 @@ def test_launch_order_with_table(pkg, routes, T, B, pre):
     cfgs, _ = ego_config_table(pool, B)
     out = []
     for enabled in (False, True):
-        eng = _engine(pkg, routes, batch, T, base)
+        eng = engine(pkg, routes, batch, T, config=base)
         eng.set_ego_configs(cfgs)
         pkg._cabi.check(eng.lib.jsim_mpc_set_launch_order(eng._ctx, 1 if enabled else 0), eng._ctx)
         x0 = torch.from_numpy(batch.x0).cuda()
@@ -470,7 +458,7 @@ def test_visited_states_against_oracle_with_table(pkg, oracle, routes, T, size, 
     every ego and tick.  T = 20 at B = CU count (helpers) and one more, T = 40."""
     B, base = _batch(size), _base(pkg, kind, T)
     batch, cfgs, which = ego_config_case(pkg.synth, routes, T, B, base=base, **VISITED_BATCH)
-    eng = _engine(pkg, routes, batch, T, base)
+    eng = engine(pkg, routes, batch, T, config=base)
     eng.set_ego_configs(cfgs)
     loop = pkg.ClosedLoop(eng, torch.from_numpy(batch.x0).cuda(), max_age=70)
     ps = oracle_params_list(oracle, cfgs, which)
@@ -504,7 +492,7 @@ def test_set_ego_configs_surface(pkg, routes):
     T, B, K = 20, 64, 6
     base = _base(pkg, "stock", T)
     batch, cfgs, _ = ego_config_case(pkg.synth, routes, T, B, base=base, truncate=False)
-    eng = _engine(pkg, routes, batch, T, base)
+    eng = engine(pkg, routes, batch, T, config=base)
     rows = ego_config_rows(cfgs)
     for bad in (rows[:-1], rows[:, :15], np.zeros((B, 17)), cfgs[:-1], torch.zeros(B + 1, 16, dtype=torch.float64)):
         with pytest.raises(ValueError):
@@ -521,7 +509,7 @@ def test_set_ego_configs_surface(pkg, routes):
     eng.set_ego_configs(other)
     loop.run(K)
     torch.cuda.synchronize()
-    e2 = _engine(pkg, routes, batch, T, base)
+    e2 = engine(pkg, routes, batch, T, config=base)
     e2.load_state(mid["tind"], mid["oa"], mid["od"])
     e2.di_ai.copy_(mid["di_ai"])
     e2.set_ego_configs(other)
@@ -530,7 +518,7 @@ def test_set_ego_configs_surface(pkg, routes):
     l2.run(K)
     torch.cuda.synchronize()
     assert _eq(l2.hist[:K], loop.hist[K:2 * K]) and _eq(l2.x0, loop.x0)
-    e3 = _engine(pkg, routes, batch, T, base)                   # ... and differs from going on with the old table
+    e3 = engine(pkg, routes, batch, T, config=base)                   # ... and differs from going on with the old table
     e3.set_ego_configs(cfgs)
     l3 = pkg.ClosedLoop(e3, torch.from_numpy(batch.x0).cuda(), hist_cap=2 * K, max_age=400)
     l3.run(2 * K)
@@ -545,14 +533,14 @@ def test_sharded_table(pkg, routes):
     T, B, world = 20, 96, 2
     base = _base(pkg, "stock", T)
     batch, cfgs, _ = ego_config_case(pkg.synth, routes, T, B, base=base)
-    whole = _engine(pkg, routes, batch, T, base)
+    whole = engine(pkg, routes, batch, T, config=base)
     whole.set_ego_configs(cfgs)
     whole.solve(torch.from_numpy(batch.x0).cuda())
     parts = []
     for rank in range(world):
         lo, hi = pkg.sharding.shard_range(B, rank, world)
         sub = pkg.synth.EgoBatch(**{k: getattr(batch, k)[lo:hi].copy() for k in ("x0", "path_id", "path_len", "target_ind", "speed", "oa", "od")})
-        eng = _engine(pkg, routes, sub, T, base)
+        eng = engine(pkg, routes, sub, T, config=base)
         eng.set_ego_configs(cfgs[lo:hi])
         eng.solve(torch.from_numpy(sub.x0).cuda())
         g = pkg.sharding.CabiGather(eng, rank=0, world=1)

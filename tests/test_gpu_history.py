@@ -2,25 +2,14 @@
 reference's own History on its loops (tests/golden/loop_real_T13.npz, loop_interact_T13.npz), fused launches against host ticks
 record for record on every kind of kernel that records, the fields against independent sources, no change to any other output,
 and graph replay."""
-import importlib
-
 import numpy as np
 import pytest
 import torch
 
-from conftest import PKG_NAME, load_golden
+from conftest import load_golden
+from gpu_helpers import W, iroutes, loop_engine  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def W(pkg):
-    return importlib.import_module(PKG_NAME + ".workloads")
-
-
-@pytest.fixture(scope="module")
-def iroutes(W):
-    return W.route_table(False)[0]
 
 
 def _rec(r):
@@ -96,13 +85,7 @@ def test_history_of_the_reference_intersection_loop(pkg):
 
 def _scenario(pkg, W, iroutes, T, B, K, mode="truncate", traffic=False, chunk=0):
     batch = W.ego_batch(iroutes, B, T, rank=2)
-    kw = {}
-    if mode == "speed_cutoff":
-        m = pkg.mpc_with_speed
-        kw = dict(config=m.config, cv=[np.full(len(r), m.MAX_SPEED) for r in iroutes])
-    eng = pkg.BatchedMPC(iroutes, batch.path_id, dl=pkg.synth.DL, T=T, speed=batch.speed, device="cuda:0", smooth=False, **kw)
-    eng.load_state(batch.target_ind, batch.oa, batch.od, batch.path_len)
-    x0 = torch.from_numpy(batch.x0).to(eng.device)
+    eng, x0 = loop_engine(pkg, iroutes, batch, T, mode)
     if traffic:
         sets, tof = W.traffic_batch(B, seed=5, n_sets=6)
         return pkg.ScenarioLoop(eng, x0, sets, hist_cap=K, max_age=60, frame_window=20, mode=mode, traffic_of=tof,
@@ -142,7 +125,7 @@ def test_traffic_chunks_record_for_record(pkg, W, iroutes):
 
 def _closed(pkg, W, iroutes, T, B, K, record=0, max_age=40):
     batch = W.ego_batch(iroutes, B, T, rank=1)
-    eng, x0 = W.make_engine(iroutes, batch, T, "cuda:0")
+    eng, x0 = loop_engine(pkg, iroutes, batch, T)
     return pkg.ClosedLoop(eng, x0, hist_cap=K, max_age=max_age, record=record)
 
 
@@ -174,7 +157,7 @@ def test_fields_from_independent_sources(pkg, W, iroutes):
         eng.solve(loop.x0)
         dev, _ = eng.xref_deviation_and_goal(loop.x0)
         devs.append(torch.where(eng.status == 0, dev, torch.full_like(dev, float("nan"))))
-        pkg._cabi.check(eng.lib.jsim_loop_advance(*_advance_args(loop)), eng._ctx, "jsim_loop_advance")
+        pkg._cabi.check(eng.lib.jsim_loop_advance(eng._ctx, eng.B, *loop._advance_args()), eng._ctx, "jsim_loop_advance")
         respawned = (loop.recorder.flags[k] & 6) != 0
         assert torch.equal(loop.recorder.rec[k][~respawned][:, [0, 1, 3, 2]], loop.x0[~respawned]), k
     torch.cuda.synchronize()
@@ -189,14 +172,6 @@ def test_fields_from_independent_sources(pkg, W, iroutes):
     assert int(failed.sum().item()) >= 8 and torch.equal(failed, torch.isnan(dev_rec))
     assert int(((r.flags & 6) != 0).sum().item()) == int(loop.n_respawn.item()) > 0
     assert int(((r.flags & 4) != 0).sum().item()) > 0
-
-
-def _advance_args(loop):
-    _ptr = importlib.import_module(PKG_NAME + ".batched")._ptr
-    eng = loop.eng
-    return (eng._ctx, eng.B, _ptr(loop.x0), _ptr(eng.oa), _ptr(eng.od), _ptr(eng.status), _ptr(eng.di_ai), _ptr(eng.target_ind),
-            _ptr(eng.path_id), _ptr(eng.path_len), _ptr(loop.x0_spawn), _ptr(loop.target_spawn), _ptr(loop.age), loop.max_age,
-            _ptr(loop.hist), _ptr(loop.tick_counter), loop.hist_cap, _ptr(loop.n_respawn), eng._stream())
 
 
 @pytest.mark.parametrize("kind", ("closed", "scenario"))

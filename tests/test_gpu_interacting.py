@@ -2,35 +2,21 @@
 interactive_mpc loop replayed tick by tick, singleton groups against ScenarioLoop, isolation of groups, the ego predictor
 against the obstacle predictor, the glue at scale against the numpy oracle, and the refusals."""
 import ctypes
-import importlib
 
 import numpy as np
 import pytest
 import torch
 
-from conftest import PKG_NAME, load_golden
+from conftest import load_golden
+from gpu_helpers import W, assert_state_equal, iroutes, iter_totals, loop_engine, loop_state  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def W(pkg):
-    return importlib.import_module(PKG_NAME + ".workloads")
-
-
-@pytest.fixture(scope="module")
-def iroutes(W):
-    return W.route_table(False)[0]
 
 
 @pytest.fixture(scope="module")
 def LO(oracle):
     import loop_oracle
     return loop_oracle
-
-
-def _engine(pkg, W, routes, batch, T):
-    return W.make_engine(routes, batch, T, "cuda:0")
 
 
 def test_interacting_reference_loop_planned_and_driven_on_the_device(pkg):
@@ -91,13 +77,6 @@ def test_interacting_reference_loop_planned_and_driven_on_the_device(pkg):
           f"max control difference {d_ctrl:.2e}, max prediction difference {worst_pred:.2e}")
 
 
-def _state(eng, loop, pre):
-    return dict(x0=loop.x0.clone(), hist=loop.hist.clone(), path_len=eng.path_len.clone(), status=eng.status.clone(),
-                target_ind=eng.target_ind.clone(), oa=eng.oa.clone(), od=eng.od.clone(), traj_idx=pre.traj_idx.clone(),
-                prev_len=pre.prev_len.clone(), col_flag=pre.col_flag.clone(), pre_status=pre.status.clone(),
-                age=loop.age.clone(), di_ai=eng.di_ai.clone())
-
-
 @pytest.mark.parametrize("with_obstacles", (False, True))
 @pytest.mark.parametrize("T", (13, 20))
 def test_singleton_groups_equal_the_scenario_loop(pkg, W, iroutes, T, with_obstacles):
@@ -105,17 +84,15 @@ def test_singleton_groups_equal_the_scenario_loop(pkg, W, iroutes, T, with_obsta
     batch, _ = W.interacting_batch(iroutes, 8, T, seed=3)
     specs = W.OBSTACLE_SPECS if with_obstacles else []
     K = 40
-    eng_a, x0a = _engine(pkg, W, iroutes, batch, T)
+    eng_a, x0a = loop_engine(pkg, iroutes, batch, T)
     sc = pkg.ScenarioLoop(eng_a, x0a, specs, hist_cap=K, max_age=W.MAX_AGE, frame_window=20)
-    eng_b, x0b = _engine(pkg, W, iroutes, batch, T)
+    eng_b, x0b = loop_engine(pkg, iroutes, batch, T)
     il = pkg.InteractingLoop(eng_b, x0b, group_sizes=[1] * eng_b.B, obstacle_specs=specs, hist_cap=K, max_age=W.MAX_AGE)
     n_cut = 0
     for _ in range(K):
         sc.tick()
         il.tick()
-        a, b = _state(eng_a, sc.loop, sc.pre), _state(eng_b, il.loop, il.pre)
-        for key in a:
-            assert torch.equal(a[key], b[key]), key
+        assert_state_equal(loop_state(sc), loop_state(il), "singleton groups")
         n_cut += int(il.pre.col_flag.sum().item())
     assert torch.equal(sc.obst.state, il.obst.state)
     assert with_obstacles or n_cut == 0                         # a group of one has nothing to meet but scripted vehicles
@@ -129,7 +106,7 @@ def test_interacting_run_counts_every_tick_into_the_iteration_totals(pkg, W, iro
     batch, sizes = W.interacting_batch(iroutes, 6, T, seed=7)
     loops = []
     for _ in range(2):
-        eng, x0 = _engine(pkg, W, iroutes, batch, T)
+        eng, x0 = loop_engine(pkg, iroutes, batch, T)
         loops.append((eng, pkg.InteractingLoop(eng, x0, group_sizes=sizes, obstacle_specs=W.OBSTACLE_SPECS[:2], hist_cap=K,
                                                max_age=W.MAX_AGE)))
     (e1, l1), (e2, l2) = loops
@@ -139,12 +116,8 @@ def test_interacting_run_counts_every_tick_into_the_iteration_totals(pkg, W, iro
         iters += e1.n_iter
     l2.run(K)
     torch.cuda.synchronize()
-    a, b = _state(e1, l1.loop, l1.pre), _state(e2, l2.loop, l2.pre)
-    for key in a:
-        assert torch.equal(a[key], b[key]), key
-    tot = np.zeros(e2.B, dtype=np.uint64)
-    pkg._cabi.check(e2.lib.jsim_mpc_iter_totals(e2._ctx, e2.B, tot.ctypes.data, 0), e2._ctx, "jsim_mpc_iter_totals")
-    assert np.array_equal(tot.astype(np.int64), iters.cpu().numpy()) and int(iters.sum()) > 0
+    assert_state_equal(loop_state(l1), loop_state(l2), "run(K) against K ticks")
+    assert np.array_equal(iter_totals(e2), iters.cpu().numpy()) and int(iters.sum()) > 0
 
 
 def test_groups_are_isolated(pkg, W, iroutes):
@@ -153,14 +126,14 @@ def test_groups_are_isolated(pkg, W, iroutes):
     batch, sizes = W.interacting_batch(iroutes, 3, T, seed=5)
     runs = []
     for perturb in (False, True):
-        eng, x0 = _engine(pkg, W, iroutes, batch, T)
+        eng, x0 = loop_engine(pkg, iroutes, batch, T)
         if perturb:
             x0[4:8, 2] += 0.5
             x0[4:8, 0] += 0.05
         il = pkg.InteractingLoop(eng, x0, group_sizes=sizes, hist_cap=K, max_age=W.MAX_AGE)
         il.run(K)
         torch.cuda.synchronize()
-        runs.append(_state(eng, il.loop, il.pre))
+        runs.append(loop_state(il))
     a, b = runs
     keep = torch.tensor([0, 1, 2, 3, 8, 9, 10, 11], device=a["x0"].device)
     for key in a:
@@ -172,7 +145,7 @@ def test_groups_are_isolated(pkg, W, iroutes):
 def test_ego_prediction_equals_the_obstacle_prediction(pkg, W, iroutes):
     """jsim_loop_predict_egos on (x0, di_ai) == jsim_loop_predict_obstacles on the tuples (x, y, v, yaw, 0, delta), bit for bit."""
     batch, sizes = W.interacting_batch(iroutes, 6, 13, seed=7)
-    eng, x0 = _engine(pkg, W, iroutes, batch, 13)
+    eng, x0 = loop_engine(pkg, iroutes, batch, 13)
     il = pkg.InteractingLoop(eng, x0, group_sizes=sizes)
     rng = np.random.default_rng(2)
     eng.di_ai[:, 0] = torch.from_numpy(rng.uniform(-0.6, 0.6, eng.B)).to(eng.device)
@@ -193,7 +166,7 @@ def test_interacting_glue_at_scale_against_the_oracle(pkg, W, iroutes, LO):
     the numpy glue give the same path length, collision flag and progress index; most cuts come from group mates."""
     G, T, K = 64, 13, 20
     batch, sizes = W.interacting_batch(iroutes, G, T, seed=11)
-    eng, x0 = _engine(pkg, W, iroutes, batch, T)
+    eng, x0 = loop_engine(pkg, iroutes, batch, T)
     il = pkg.InteractingLoop(eng, x0, group_sizes=sizes, max_age=W.MAX_AGE)
     B = eng.B
     dl = float(eng.dl)
@@ -222,25 +195,14 @@ def test_interacting_glue_at_scale_against_the_oracle(pkg, W, iroutes, LO):
     assert n_cut >= B * K // 4
 
 
-def _run_args(il, speed_cutoff=0):
-    loop, pre, ob, eng = il.loop, il.pre, il.obst, il.loop.eng
-    P = importlib.import_module(PKG_NAME + ".batched")._ptr
-    return (eng._ctx, eng.B, 1, P(loop.x0), P(eng.path_id), P(eng.path_len), P(eng.speed), P(eng.target_ind), P(eng.oa),
-            P(eng.od), P(eng.ox), P(eng.oy), P(eng.ov), P(eng.oyaw), P(eng.xref), P(eng.active_mask), P(eng.status),
-            P(eng.n_iter), P(eng.di_ai), P(loop.x0_spawn), P(loop.target_spawn), P(loop.age), loop.max_age, None, None, 0,
-            None, P(pre.traj_idx), P(pre.prev_len), P(pre.col_flag), P(pre.status), pre.frame_window, pre.margin, ob.n,
-            P(ob.state) if ob.n else None, P(ob.param) if ob.n else None, P(ob.get_buf) if ob.n else None, pre.n_steps,
-            speed_cutoff, eng._stream())
-
-
 def test_interacting_refusals(pkg, W, iroutes):
     """-22 with a message: too many obstacles per ego, bad group_off, no groups for this B, speed_cutoff, obstacle geometry."""
     batch, sizes = W.interacting_batch(iroutes, 2, 13, seed=1)
-    eng, x0 = _engine(pkg, W, iroutes, batch, 13)
+    eng, x0 = loop_engine(pkg, iroutes, batch, 13)
     il = pkg.InteractingLoop(eng, x0, group_sizes=sizes, obstacle_specs=W.OBSTACLE_SPECS[:2])
     lib, ctx = eng.lib, eng._ctx
-    assert lib.jsim_loop_run_interacting(*_run_args(il)) == 0
-    assert lib.jsim_loop_run_interacting(*_run_args(il, speed_cutoff=1)) == -22
+    assert lib.jsim_loop_run_interacting(ctx, eng.B, 1, *il._run_args()) == 0
+    assert lib.jsim_loop_run_interacting(ctx, eng.B, 1, *il._run_args(speed_cutoff=1)) == -22
     assert b"truncate" in lib.jsim_last_error(ctx)
 
     def groups(off):
@@ -250,13 +212,13 @@ def test_interacting_refusals(pkg, W, iroutes):
     for bad in ([0, 9, 8], [0, 0, 8], [0, 4, 7], [1, 4, 8]):
         assert groups(bad) == -22, bad
     assert groups([0, 8]) == 0                                  # two obstacles + a group of 8: 2 + 7 > 8
-    assert lib.jsim_loop_run_interacting(*_run_args(il)) == -22
+    assert lib.jsim_loop_run_interacting(ctx, eng.B, 1, *il._run_args()) == -22
     assert b"largest group" in lib.jsim_last_error(ctx)
     assert lib.jsim_loop_set_groups(ctx, eng.B, 0, None) == 0   # cleared
-    assert lib.jsim_loop_run_interacting(*_run_args(il)) == -22
+    assert lib.jsim_loop_run_interacting(ctx, eng.B, 1, *il._run_args()) == -22
     assert groups([0, 4, 8]) == 0
-    assert lib.jsim_loop_run_interacting(*_run_args(il)) == 0
+    assert lib.jsim_loop_run_interacting(ctx, eng.B, 1, *il._run_args()) == 0
     assert lib.jsim_loop_set_obstacle_geometry(ctx, 1.0, 0.0, 0.3, 1.0) == 0
-    assert lib.jsim_loop_run_interacting(*_run_args(il)) == -22
+    assert lib.jsim_loop_run_interacting(ctx, eng.B, 1, *il._run_args()) == -22
     assert b"obstacle" in lib.jsim_last_error(ctx)
     torch.cuda.synchronize()

@@ -12,7 +12,7 @@ import pytest
 import torch
 
 from conftest import PKG_NAME, load_golden
-from gpu_helpers import cu_count, iter_totals, kkt_check, variant_batches, variant_id
+from gpu_helpers import cu_count, debug_bufs, engine, iter_totals, kkt_check, oracle_batch, variant_batches, variant_id
 
 pytestmark = pytest.mark.gpu
 TS = (13, 20, 30, 40)
@@ -46,27 +46,6 @@ def _batch(size):
     return variant_batches(row, cu_count())[k]
 
 
-def _engine(pkg, routes, batch, T):
-    eng = pkg.BatchedMPC(routes, batch.path_id, dl=pkg.synth.DL, T=T, speed=batch.speed, device="cuda:0",
-                         smooth=False)
-    eng.load_state(batch.target_ind, batch.oa, batch.od, batch.path_len)
-    return eng
-
-
-def _debug_bufs(eng):
-    B, T = eng.B, eng.T
-    f = dict(dtype=torch.float64, device=eng.device)
-    return {"xbar": torch.zeros(B, 4, T + 1, **f), "ref_idx": torch.zeros(B, T + 1, dtype=torch.int64, device=eng.device),
-            "H": torch.zeros(B, 2 * T, 2 * T, **f), "g": torch.zeros(B, 2 * T, **f), "lam": torch.zeros(B, 8 * T, **f)}
-
-
-def _oracle_batch(oracle, pkg, routes, batch, T, n_threads=1, **kw):
-    p = oracle.make_params(T=T, **kw)
-    cx, cy, cyaw, off = pkg.synth.pack_paths(routes)
-    return p, oracle.mpc_step_batch(p, batch.x0, batch.path_id, batch.path_len, batch.speed, cx, cy, cyaw, off,
-                                    batch.target_ind, batch.oa, batch.od, n_threads=n_threads)
-
-
 @pytest.mark.parametrize("T", TS)
 def test_stages_vs_reference_golden(pkg, routes, T):
     """S1-S3 on the GPU against what the reference's _calc_ref_trajectory/_predict_motion returned."""
@@ -74,8 +53,8 @@ def test_stages_vs_reference_golden(pkg, routes, T):
     batch = pkg.synth.EgoBatch(x0=g["x0"], path_id=g["path_id"], path_len=g["path_len"],
                                target_ind=g["target_ind_in"], speed=np.full(len(g["x0"]), 30 / 3.6),
                                oa=g["oa"], od=g["od"])
-    eng = _engine(pkg, routes, batch, T)
-    dbg = _debug_bufs(eng)
+    eng = engine(pkg, routes, batch, T)
+    dbg = debug_bufs(eng)
     eng.solve(torch.from_numpy(batch.x0).to(eng.device), debug=dbg)
     torch.cuda.synchronize()
     st = eng.status.cpu().numpy()
@@ -104,11 +83,11 @@ def test_step_vs_oracle(pkg, oracle, routes, T, size):
     batch.path_len[7:9] = np.minimum(batch.path_len[7:9], batch.target_ind[7:9] + [2, 3])   # two / three points left
     batch.target_ind[9] = batch.path_len[9] - 1             # on the last point
     assert np.array_equal(batch.path_len[7:10] - batch.target_ind[7:10], [2, 3, 1])
-    eng = _engine(pkg, routes, batch, T)
-    dbg = _debug_bufs(eng)
+    eng = engine(pkg, routes, batch, T)
+    dbg = debug_bufs(eng)
     eng.solve(torch.from_numpy(batch.x0).to(eng.device), debug=dbg)
     torch.cuda.synchronize()
-    p, ref = _oracle_batch(oracle, pkg, routes, batch, T, n_threads=16)
+    p, ref = oracle_batch(oracle, pkg, routes, batch, T, n_threads=16)
     st = eng.status.cpu().numpy()
     assert np.array_equal(st, ref["status"])
     assert st[5] == 1 and st[6] == 1
@@ -149,8 +128,8 @@ def test_kkt_property_at_full_size(pkg, routes):
     (strictly convex => that IS the optimum), and active rows are tight."""
     for B, T in ((256, 20), (4096, 30)):
         batch = pkg.synth.make_ego_batch(routes, B, T, seed=1, truncate=(T == 30))
-        eng = _engine(pkg, routes, batch, T)
-        dbg = _debug_bufs(eng)
+        eng = engine(pkg, routes, batch, T)
+        dbg = debug_bufs(eng)
         eng.solve(torch.from_numpy(batch.x0).to(eng.device), debug=dbg)
         torch.cuda.synchronize()
         st = eng.status
@@ -294,7 +273,7 @@ def test_fused_ticks_equal_single_ticks(pkg, routes, T, size):
     B, K = _batch(size), (60 if T <= 30 else 30)
     batch = pkg.synth.make_ego_batch(routes, B, T, seed=11, near_end_frac=0.5)
     def make():
-        eng = _engine(pkg, routes, batch, T)
+        eng = engine(pkg, routes, batch, T)
         x0 = torch.from_numpy(batch.x0).to(eng.device)
         return eng, pkg.ClosedLoop(eng, x0, hist_cap=K, max_age=25, record=K)
     e1, l1 = make()
@@ -332,7 +311,7 @@ def test_helper_wavefronts_change_nothing(pkg, routes, T):
     small = pkg.synth.EgoBatch(**{k: getattr(big, k)[:B1].copy() for k in ("x0", "path_id", "path_len", "target_ind", "speed", "oa", "od")})
     out = []
     for b in (small, big):
-        eng = _engine(pkg, routes, b, T)
+        eng = engine(pkg, routes, b, T)
         loop = pkg.ClosedLoop(eng, torch.from_numpy(b.x0).to(eng.device), hist_cap=K, max_age=25)
         loop.run(K // 2); loop.run(K - K // 2)
         torch.cuda.synchronize()
@@ -342,8 +321,8 @@ def test_helper_wavefronts_change_nothing(pkg, routes, T):
     for name in ("oa", "od", "ox", "oy", "ov", "oyaw", "xref", "target_ind", "status", "n_iter", "active_mask", "di_ai"):
         assert torch.equal(getattr(e1, name), getattr(e2, name)[:B1]), name
     assert int(l1.n_respawn.item()) > 0
-    s1, s2 = _engine(pkg, routes, small, T), _engine(pkg, routes, big, T)       # one step, debug outputs included
-    d1, d2 = _debug_bufs(s1), _debug_bufs(s2)
+    s1, s2 = engine(pkg, routes, small, T), engine(pkg, routes, big, T)       # one step, debug outputs included
+    d1, d2 = debug_bufs(s1), debug_bufs(s2)
     s1.solve(torch.from_numpy(small.x0).to(s1.device), debug=d1)
     s2.solve(torch.from_numpy(big.x0).to(s2.device), debug=d2)
     torch.cuda.synchronize()
@@ -371,7 +350,7 @@ def test_garbage_states_neither_stall_nor_leak(pkg, routes, T, size):
     dirty.oa[17, :] = 1e300
     out = []
     for b in (clean, dirty):
-        eng = _engine(pkg, routes, b, T)
+        eng = engine(pkg, routes, b, T)
         x0 = torch.from_numpy(b.x0).to(eng.device)
         if pre:
             sc = pkg.ScenarioLoop(eng, x0, SCENARIO_SPECS, hist_cap=K, max_age=400)
@@ -399,14 +378,14 @@ def test_lds_kernel_and_register_kernel_agree(pkg, oracle, routes, T, monkeypatc
     B = 128 if T <= 20 else 64
     batch = pkg.synth.make_ego_batch(routes, B, T, seed=5, truncate=True, near_end_frac=0.3)
     x0 = torch.from_numpy(batch.x0).cuda()
-    e_reg = _engine(pkg, routes, batch, T)
+    e_reg = engine(pkg, routes, batch, T)
     e_reg.solve(x0)
     monkeypatch.setenv("JSIM_FORCE_LDS_KERNEL", "1")
-    e_lds = _engine(pkg, routes, batch, T)
+    e_lds = engine(pkg, routes, batch, T)
     monkeypatch.delenv("JSIM_FORCE_LDS_KERNEL")
     e_lds.solve(x0)
     torch.cuda.synchronize()
-    p, ref = _oracle_batch(oracle, pkg, routes, batch, T)
+    p, ref = oracle_batch(oracle, pkg, routes, batch, T)
     for eng in (e_reg, e_lds):
         assert np.array_equal(eng.status.cpu().numpy(), ref["status"])
         assert np.array_equal(eng.target_ind.cpu().numpy(), ref["target_ind"])
@@ -425,7 +404,7 @@ def test_iteration_totals_with_the_lds_kernel_forced(pkg, routes, kind, monkeypa
     T, B, K = 20, 97, 12
     batch = pkg.synth.make_ego_batch(routes, B, T, seed=9, truncate=True, near_end_frac=0.3)
     monkeypatch.setenv("JSIM_FORCE_LDS_KERNEL", "1")
-    engs = [_engine(pkg, routes, batch, T) for _ in range(2)]
+    engs = [engine(pkg, routes, batch, T) for _ in range(2)]
     monkeypatch.delenv("JSIM_FORCE_LDS_KERNEL")
     loops = []
     for eng in engs:
@@ -553,10 +532,10 @@ def test_generic_kernel_any_horizon(pkg, oracle, routes, T):
     n an exact multiple of the 16-column tile (T = 8, 24, 48), the largest supported T, two rows per lane (T > 32)."""
     B = 48
     batch = pkg.synth.make_ego_batch(routes, B, T, seed=100 + T, truncate=True, near_end_frac=0.3)
-    eng = _engine(pkg, routes, batch, T)
+    eng = engine(pkg, routes, batch, T)
     eng.solve(torch.from_numpy(batch.x0).to(eng.device))
     torch.cuda.synchronize()
-    p, ref = _oracle_batch(oracle, pkg, routes, batch, T)
+    p, ref = oracle_batch(oracle, pkg, routes, batch, T)
     assert np.array_equal(eng.status.cpu().numpy(), ref["status"])
     assert np.array_equal(eng.target_ind.cpu().numpy(), ref["target_ind"])
     np.testing.assert_array_equal(eng.xref.cpu().numpy(), ref["xref"])
@@ -713,7 +692,7 @@ def test_closed_loop_visited_states_against_oracle(pkg, oracle, routes, T, K, B)
     sub = pkg.synth.EgoBatch(x0=batch.x0[:B].copy(), path_id=batch.path_id[:B].copy(), path_len=batch.path_len[:B].copy(),
                              target_ind=batch.target_ind[:B].copy(), speed=batch.speed[:B].copy(), oa=batch.oa[:B].copy(),
                              od=batch.od[:B].copy())
-    eng = _engine(pkg, routes, sub, T)
+    eng = engine(pkg, routes, sub, T)
     loop = pkg.ClosedLoop(eng, torch.from_numpy(sub.x0).to(eng.device), max_age=70)
     p = oracle.make_params(T=T)
     cx, cy, cyaw, off = pkg.synth.pack_paths(routes)
@@ -848,7 +827,7 @@ def test_large_working_sets_on_the_long_horizon_kernels(pkg, oracle, routes, T, 
     eng.load_state(batch.target_ind, batch.oa, batch.od, batch.path_len)
     eng.solve(torch.from_numpy(batch.x0).to(eng.device))
     torch.cuda.synchronize()
-    p, ref = _oracle_batch(oracle, pkg, routes, batch, T, n_threads=16,
+    p, ref = oracle_batch(oracle, pkg, routes, batch, T, n_threads=16,
                            config={"MAX_ACCEL": 0.05, "MAX_DECEL": -0.05, "MAX_DSTEER": 0.4})
     st = eng.status.cpu().numpy()
     assert np.array_equal(st, ref["status"])
@@ -876,10 +855,10 @@ def test_speed_rows_in_the_working_set(pkg, oracle, routes, T, size):
     batch.x0[:, 2] = batch.speed - rng.uniform(0.0, 0.3, B)
     batch.x0[::7, 2] = batch.speed[::7]              # exactly at the limit
     batch.oa[:] = rng.uniform(0.5, 2.0, (B, T))
-    eng = _engine(pkg, routes, batch, T)
+    eng = engine(pkg, routes, batch, T)
     eng.solve(torch.from_numpy(batch.x0).to(eng.device))
     torch.cuda.synchronize()
-    _, ref = _oracle_batch(oracle, pkg, routes, batch, T, n_threads=16)
+    _, ref = oracle_batch(oracle, pkg, routes, batch, T, n_threads=16)
     st = eng.status.cpu().numpy()
     assert np.array_equal(st, ref["status"])
     ok = st == 0
@@ -911,7 +890,7 @@ def test_long_horizon_kernels_at_scale_and_deterministic(pkg, oracle, routes, T,
     batch = pkg.synth.make_ego_batch(routes, B, T, seed=21, truncate=True, near_end_frac=0.2)
     outs = []
     for rep in range(2):
-        eng = _engine(pkg, routes, batch, T)
+        eng = engine(pkg, routes, batch, T)
         eng.solve(torch.from_numpy(batch.x0).to(eng.device))
         torch.cuda.synchronize()
         outs.append({k: getattr(eng, k).clone() for k in ("oa", "od", "status", "n_iter", "active_mask", "target_ind", "ox", "oyaw")})
@@ -947,8 +926,8 @@ def test_max_iter_relinearisation_passes(pkg, oracle, routes, T):
     eng.load_state(batch.target_ind, batch.oa, batch.od, batch.path_len)
     eng.solve(torch.from_numpy(batch.x0).to(eng.device))
     torch.cuda.synchronize()
-    p, ref = _oracle_batch(oracle, pkg, routes, batch, T, config={"MAX_ITER": 3})
-    p1, ref1 = _oracle_batch(oracle, pkg, routes, batch, T)
+    p, ref = oracle_batch(oracle, pkg, routes, batch, T, config={"MAX_ITER": 3})
+    p1, ref1 = oracle_batch(oracle, pkg, routes, batch, T)
     st = eng.status.cpu().numpy()
     assert np.array_equal(st, ref["status"]) and st[3] == 1
     assert np.array_equal(eng.target_ind.cpu().numpy(), ref["target_ind"])

@@ -3,14 +3,12 @@ its own scripted vehicles equals that ego run in a plain loop whose shared obsta
 one-wave (T = 13, 20) and four-wave (T = 40) kernels and on host ticks (T = 24), with both glues; the shared-traffic special
 case, chunked fused launches, run(K) against K ticks, per-group sets of interacting egos, and the refusals."""
 import ctypes
-import dataclasses
-import importlib
 
 import numpy as np
 import pytest
 import torch
 
-from conftest import PKG_NAME
+from gpu_helpers import W, assert_state_equal, iroutes, loop_engine, loop_state, obstacle_state, sub_batch  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -26,50 +24,6 @@ SETS = [[T_INT(1, False, 25, 2.0), T_INT(-1, True, 20, 4.0)],
         []]
 
 
-@pytest.fixture(scope="module")
-def W(pkg):
-    return importlib.import_module(PKG_NAME + ".workloads")
-
-
-@pytest.fixture(scope="module")
-def iroutes(W):
-    return W.route_table(False)[0]
-
-
-def _sub(batch, idx):
-    return dataclasses.replace(batch, **{f.name: getattr(batch, f.name)[idx] for f in dataclasses.fields(batch)})
-
-
-def _engine(pkg, routes, batch, T, mode="truncate"):
-    kw = {}
-    if mode == "speed_cutoff":
-        m = pkg.mpc_with_speed
-        kw = dict(config=m.config, cv=[np.full(len(r), m.MAX_SPEED) for r in routes])
-    eng = pkg.BatchedMPC(routes, batch.path_id, dl=pkg.synth.DL, T=T, speed=batch.speed, device="cuda:0", smooth=False, **kw)
-    eng.load_state(batch.target_ind, batch.oa, batch.od, batch.path_len)
-    return eng, torch.from_numpy(batch.x0).to(eng.device)
-
-
-def _state(sc, idx=None):
-    """Every per-ego buffer of a scenario loop (rows idx), and the obstacle states."""
-    eng, loop, pre = sc.loop.eng, sc.loop, sc.pre
-    d = dict(x0=loop.x0, path_len=eng.path_len, target_ind=eng.target_ind, traj_idx=pre.traj_idx, prev_len=pre.prev_len,
-             col_flag=pre.col_flag, pre_status=pre.status, status=eng.status, oa=eng.oa, od=eng.od, di_ai=eng.di_ai,
-             age=loop.age)
-    if pre.cut is not None:
-        d["cut"] = pre.cut
-    if idx is not None:
-        d = {k: v.index_select(0, idx) for k, v in d.items()}
-    d["hist"] = loop.hist if idx is None else loop.hist.index_select(1, idx)
-    return {k: v.clone() for k, v in d.items()}
-
-
-def _assert_equal(a, b, what):
-    assert a.keys() == b.keys()
-    for k in a:
-        assert torch.equal(a[k], b[k]), (what, k)
-
-
 @pytest.mark.parametrize("mode", ("truncate", "speed_cutoff"))
 @pytest.mark.parametrize("T", (13, 20, 24, 40))
 def test_per_ego_sets_equal_plain_loops_per_set(pkg, W, iroutes, T, mode):
@@ -79,12 +33,12 @@ def test_per_ego_sets_equal_plain_loops_per_set(pkg, W, iroutes, T, mode):
     B, K = 64, 60
     batch = W.ego_batch(iroutes, B, T, rank=3)
     traffic_of = np.arange(B) % len(SETS)
-    eng, x0 = _engine(pkg, iroutes, batch, T, mode)
+    eng, x0 = loop_engine(pkg, iroutes, batch, T, mode)
     sc = pkg.ScenarioLoop(eng, x0, SETS, hist_cap=K, max_age=W.MAX_AGE, frame_window=20, mode=mode, traffic_of=traffic_of)
     plain = []
     for s, specs in enumerate(SETS):
-        sub = _sub(batch, np.flatnonzero(traffic_of == s))
-        e, x = _engine(pkg, iroutes, sub, T, mode)
+        sub = sub_batch(batch, np.flatnonzero(traffic_of == s))
+        e, x = loop_engine(pkg, iroutes, sub, T, mode)
         plain.append(pkg.ScenarioLoop(e, x, specs, hist_cap=K, max_age=W.MAX_AGE, frame_window=20, mode=mode))
     cuts = np.zeros(len(SETS), dtype=np.int64)
     tof = torch.from_numpy(traffic_of).to(eng.device)
@@ -99,9 +53,8 @@ def test_per_ego_sets_equal_plain_loops_per_set(pkg, W, iroutes, T, mode):
     _, obs_off = sc.traffic
     for s, p in enumerate(plain):
         idx = torch.from_numpy(np.flatnonzero(traffic_of == s)).to(eng.device)
-        _assert_equal(_state(sc, idx), _state(p), s)
-        assert torch.equal(sc.obst.state[obs_off[s]:obs_off[s + 1]], p.obst.state[: p.obst.n]), s
-        assert torch.equal(sc.obst.get_buf[obs_off[s]:obs_off[s + 1]], p.obst.get_buf[: p.obst.n]), s
+        assert_state_equal(loop_state(sc, idx), loop_state(p), s)
+        assert_state_equal(obstacle_state(sc, obs_off[s], obs_off[s + 1]), obstacle_state(p), s)
     assert int(sc.loop.n_respawn.item()) == sum(int(p.loop.n_respawn.item()) for p in plain)
     print(f"T = {T}, {mode}: cut ego-ticks per set {cuts.tolist()}, respawns {int(sc.loop.n_respawn.item())}")
     assert cuts[-1] == 0 and (cuts[:-1] > 0).all(), cuts
@@ -114,14 +67,15 @@ def test_one_set_for_everyone_equals_shared_obstacles(pkg, W, iroutes, T):
     batch = W.ego_batch(iroutes, B, T, rank=1)
     runs = []
     for traffic in (False, True):
-        eng, x0 = _engine(pkg, iroutes, batch, T)
+        eng, x0 = loop_engine(pkg, iroutes, batch, T)
         kw = dict(traffic_of=np.zeros(B, dtype=np.int64)) if traffic else {}
         sc = pkg.ScenarioLoop(eng, x0, [W.OBSTACLE_SPECS] if traffic else W.OBSTACLE_SPECS, hist_cap=K, max_age=W.MAX_AGE, **kw)
         sc.run(K)
         torch.cuda.synchronize()
-        runs.append((_state(sc), sc.obst.state.clone(), sc.obst.get_buf.clone(), int(sc.loop.n_respawn.item())))
-    _assert_equal(runs[0][0], runs[1][0], "shared")
-    assert torch.equal(runs[0][1], runs[1][1]) and torch.equal(runs[0][2], runs[1][2]) and runs[0][3] == runs[1][3]
+        runs.append((loop_state(sc), obstacle_state(sc), int(sc.loop.n_respawn.item())))
+    assert_state_equal(runs[0][0], runs[1][0], "shared")
+    assert_state_equal(runs[0][1], runs[1][1], "shared")
+    assert runs[0][2] == runs[1][2]
 
 
 def test_chunked_equals_unchunked_and_run_equals_ticks(pkg, W, iroutes):
@@ -132,7 +86,7 @@ def test_chunked_equals_unchunked_and_run_equals_ticks(pkg, W, iroutes):
     sets, tof = W.traffic_batch(B, seed=5, n_sets=12)
     runs = []
     for how in ("auto", "chunk7", "ticks"):
-        eng, x0 = _engine(pkg, iroutes, batch, T)
+        eng, x0 = loop_engine(pkg, iroutes, batch, T)
         sc = pkg.ScenarioLoop(eng, x0, sets, hist_cap=K, max_age=W.MAX_AGE, traffic_of=tof, chunk_ticks=7 if how == "chunk7" else 0)
         if how == "ticks":
             for _ in range(K):
@@ -140,10 +94,11 @@ def test_chunked_equals_unchunked_and_run_equals_ticks(pkg, W, iroutes):
         else:
             sc.run(K)
         torch.cuda.synchronize()
-        runs.append((_state(sc), sc.obst.state.clone(), sc.obst.get_buf.clone(), int(sc.loop.n_respawn.item())))
+        runs.append((loop_state(sc), obstacle_state(sc), int(sc.loop.n_respawn.item())))
     for r in runs[1:]:
-        _assert_equal(runs[0][0], r[0], "chunks")
-        assert torch.equal(runs[0][1], r[1]) and torch.equal(runs[0][2], r[2]) and runs[0][3] == r[3]
+        assert_state_equal(runs[0][0], r[0], "chunks")
+        assert_state_equal(runs[0][1], r[1], "chunks")
+        assert runs[0][2] == r[2]
 
 
 def test_per_group_sets_equal_groups_run_alone(pkg, W, iroutes):
@@ -153,18 +108,18 @@ def test_per_group_sets_equal_groups_run_alone(pkg, W, iroutes):
     batch, sizes = W.interacting_batch(iroutes, G, T, seed=13)
     sets = [s[:4] for s in SETS] + [[T_INT(1, True, 26, 1.0)]]       # + 3 group mates <= 8
     tog = np.arange(G) % len(sets)
-    eng, x0 = _engine(pkg, iroutes, batch, T)
+    eng, x0 = loop_engine(pkg, iroutes, batch, T)
     il = pkg.InteractingLoop(eng, x0, group_sizes=sizes, obstacle_specs=sets, hist_cap=K, max_age=W.MAX_AGE, traffic_of=tog)
     il.run(K)
     torch.cuda.synchronize()
     n_cut = 0
     for g in range(G):
         idx = np.arange(4 * g, 4 * g + 4)
-        e, x = _engine(pkg, iroutes, _sub(batch, idx), T)
+        e, x = loop_engine(pkg, iroutes, sub_batch(batch, idx), T)
         alone = pkg.InteractingLoop(e, x, group_sizes=[4], obstacle_specs=sets[tog[g]], hist_cap=K, max_age=W.MAX_AGE)
         alone.run(K)
         torch.cuda.synchronize()
-        _assert_equal(_state(il, torch.from_numpy(idx).to(eng.device)), _state(alone), g)
+        assert_state_equal(loop_state(il, torch.from_numpy(idx).to(eng.device)), loop_state(alone), g)
         o0, o1 = il.traffic[1][tog[g]], il.traffic[1][tog[g] + 1]
         assert torch.equal(il.obst.state[o0:o1], alone.obst.state[: alone.obst.n]), g
         n_cut += int(alone.pre.col_flag.sum().item())
@@ -179,7 +134,7 @@ def test_interacting_glue_with_per_group_sets_against_the_oracle(pkg, W, iroutes
     G, T, K = 64, 13, 12
     batch, sizes = W.interacting_batch(iroutes, G, T, seed=17)
     sets, tog = W.traffic_batch(G, seed=3, vehicles=2, roundabout=0.0)
-    eng, x0 = _engine(pkg, iroutes, batch, T)
+    eng, x0 = loop_engine(pkg, iroutes, batch, T)
     il = pkg.InteractingLoop(eng, x0, group_sizes=sizes, obstacle_specs=sets, max_age=W.MAX_AGE, traffic_of=tog)
     set_of, obs_off = il.traffic
     B, dl = eng.B, float(eng.dl)
@@ -211,33 +166,25 @@ def test_interacting_glue_with_per_group_sets_against_the_oracle(pkg, W, iroutes
     assert n_cut > 0 and n_scripted > 0
 
 
-def _run_args(sc, n_obs=None):
-    loop, pre, ob, eng = sc.loop, sc.pre, sc.obst, sc.loop.eng
-    P = importlib.import_module(PKG_NAME + ".batched")._ptr
-    return (eng._ctx, eng.B, 3, *loop._loop_args(), P(pre.traj_idx), P(pre.prev_len), P(pre.col_flag), P(pre.status),
-            pre.frame_window, pre.margin, ob.n if n_obs is None else n_obs, P(ob.state), P(ob.param), P(ob.get_buf), pre.n_steps,
-            0, eng._stream())
-
-
 def test_traffic_refusals_leave_the_buffers_alone(pkg, W, iroutes):
     """-22 with a message for every bad layout (set_of out of range, obs_off not from 0 / decreasing, a set of 9), a run with
     another B or total, and interacting groups with mixed sets or too many vehicles per group -- and nothing on the device
     changes: the registered layout stays, the loop buffers and obstacle states keep their values."""
     T = 13
     batch, sizes = W.interacting_batch(iroutes, 2, T, seed=1)
-    eng, x0 = _engine(pkg, iroutes, batch, T)
+    eng, x0 = loop_engine(pkg, iroutes, batch, T)
     B = eng.B
     sets = [SETS[0], SETS[2]]
     sc = pkg.ScenarioLoop(eng, x0, sets, hist_cap=4, traffic_of=np.array([0, 1] * (B // 2)))
     lib, ctx = eng.lib, eng._ctx
     p = lambda a: np.ascontiguousarray(a, dtype=np.int32).ctypes.data_as(ctypes.c_void_p)   # noqa: E731
     torch.cuda.synchronize()
-    before = (_state(sc), sc.obst.state.clone(), sc.obst.get_buf.clone())
+    before = (loop_state(sc), obstacle_state(sc))
 
     def unchanged():
         torch.cuda.synchronize()
-        _assert_equal(before[0], _state(sc), "refusal")
-        assert torch.equal(before[1], sc.obst.state) and torch.equal(before[2], sc.obst.get_buf)
+        assert_state_equal(before[0], loop_state(sc), "refusal")
+        assert_state_equal(before[1], obstacle_state(sc), "refusal")
 
     good_of, good_off = np.zeros(B), [0, 2, 4]
     for of, off, msg in (([0] * (B - 1) + [2], good_off, b"set_of"), ([0] * (B - 1) + [-1], good_off, b"set_of"),
@@ -248,29 +195,26 @@ def test_traffic_refusals_leave_the_buffers_alone(pkg, W, iroutes):
     assert lib.jsim_loop_set_traffic(ctx, B, 2, None, p(good_off), 0) == -22
     assert lib.jsim_loop_set_traffic(ctx, B, 2, p(good_of), p(good_off), -1) == -22
     # the registered layout is still the good one: a run with the right total works after all these
-    assert lib.jsim_loop_run_scenario(*_run_args(sc, n_obs=3)) == -22                 # wrong total
+    assert lib.jsim_loop_run_scenario(ctx, B, 3, *sc._run_args(n_obs=3)) == -22        # wrong total
     assert b"4 vehicles" in lib.jsim_last_error(ctx)
     unchanged()
-    args = list(_run_args(sc))
-    args[1] = B - 4                                                                    # wrong B
-    assert lib.jsim_loop_run_scenario(*args) == -22 and b"B=" in lib.jsim_last_error(ctx)
+    assert lib.jsim_loop_run_scenario(ctx, B - 4, 3, *sc._run_args()) == -22 and b"B=" in lib.jsim_last_error(ctx)   # wrong B
     unchanged()
     # interacting: a group mixing sets; a set of 6 + 3 group mates
     assert lib.jsim_loop_set_groups(ctx, B, 2, p([0, 4, 8])) == 0
-    assert lib.jsim_loop_run_interacting(*_run_args(sc)) == -22
+    assert lib.jsim_loop_run_interacting(ctx, B, 3, *sc._run_args()) == -22
     assert b"mixes traffic sets" in lib.jsim_last_error(ctx)
     unchanged()
     big = [[T_INT(1, False, 25, 1.0 + i) for i in range(6)], []]
     assert lib.jsim_loop_set_traffic(ctx, B, 2, p([0] * 4 + [1] * 4), p([0, 6, 6]), 0) == 0
-    args = list(_run_args(sc, n_obs=6))
+    args = list(sc._run_args(n_obs=6))
     obs6 = pkg.ScriptedObstacles(eng, big[0])
-    P = importlib.import_module(PKG_NAME + ".batched")._ptr
-    args[-6], args[-5], args[-4] = P(obs6.state), P(obs6.param), P(obs6.get_buf)
-    assert lib.jsim_loop_run_interacting(*args) == -22
+    args[-6], args[-5], args[-4] = (t.data_ptr() for t in (obs6.state, obs6.param, obs6.get_buf))
+    assert lib.jsim_loop_run_interacting(ctx, B, 3, *args) == -22
     assert b"group mates" in lib.jsim_last_error(ctx)
     unchanged()
     assert lib.jsim_loop_set_traffic(ctx, B, 2, p([1] * 4 + [0] * 4), p([0, 2, 4]), 0) == 0   # per-group sets: accepted
-    assert lib.jsim_loop_run_interacting(*_run_args(sc)) == 0
+    assert lib.jsim_loop_run_interacting(ctx, B, 3, *sc._run_args()) == 0
     assert lib.jsim_loop_set_traffic(ctx, B, 0, None, None, 0) == 0                   # cleared: n_obs <= 8 again
     assert lib.jsim_loop_set_groups(ctx, B, 0, None) == 0
     torch.cuda.synchronize()

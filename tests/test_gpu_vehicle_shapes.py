@@ -4,7 +4,6 @@ reference's cyclist cases through the table; a car and a cyclist in one traffic_
 (tests/shapes_numpy.py, pinned to the oracle by tests/test_vehicle_shapes_cpu.py); every ego of that batch against its plain
 loop; interacting egos beside a cyclist; refusals and clearing."""
 import ctypes
-import dataclasses
 import importlib
 
 import numpy as np
@@ -12,7 +11,8 @@ import pytest
 import torch
 
 from conftest import PKG_NAME, load_golden
-from gpu_helpers import REG_VARIANTS, cu_count, variant_batch, variant_id
+from gpu_helpers import (REG_VARIANTS, W, assert_state_equal, cu_count, iroutes, loop_engine, loop_state,  # noqa: F401
+                         obstacle_state, sub_batch, variant_batch, variant_id)
 
 pytestmark = pytest.mark.gpu
 
@@ -30,65 +30,9 @@ def with_dims(specs, dims):
 
 
 @pytest.fixture(scope="module")
-def W(pkg):
-    return importlib.import_module(PKG_NAME + ".workloads")
-
-
-@pytest.fixture(scope="module")
-def iroutes(W):
-    return W.route_table(False)[0]
-
-
-@pytest.fixture(scope="module")
 def SN(oracle):
     import shapes_numpy
     return shapes_numpy
-
-
-def _sub(batch, idx):
-    return dataclasses.replace(batch, **{f.name: getattr(batch, f.name)[idx] for f in dataclasses.fields(batch)})
-
-
-def _engine(pkg, routes, batch, T, mode="truncate"):
-    kw = {}
-    if mode == "speed_cutoff":
-        m = pkg.mpc_with_speed
-        kw = dict(config=m.config, cv=[np.full(len(r), m.MAX_SPEED) for r in routes])
-    eng = pkg.BatchedMPC(routes, batch.path_id, dl=pkg.synth.DL, T=T, speed=batch.speed, device="cuda:0", smooth=False, **kw)
-    eng.load_state(batch.target_ind, batch.oa, batch.od, batch.path_len)
-    return eng, torch.from_numpy(batch.x0).to(eng.device)
-
-
-def _state(sc, idx=None):
-    """Every per-ego buffer of a loop (rows idx), its History records, and the obstacle states."""
-    eng, loop, pre = sc.loop.eng, sc.loop, sc.pre
-    d = dict(x0=loop.x0, path_len=eng.path_len, target_ind=eng.target_ind, traj_idx=pre.traj_idx, prev_len=pre.prev_len,
-             col_flag=pre.col_flag, pre_status=pre.status, status=eng.status, oa=eng.oa, od=eng.od, di_ai=eng.di_ai,
-             age=loop.age, ox=eng.ox, oy=eng.oy, ov=eng.ov, oyaw=eng.oyaw)
-    if pre.cut is not None:
-        d["cut"] = pre.cut
-    if idx is not None:
-        d = {k: v.index_select(0, idx) for k, v in d.items()}
-    d["hist"] = loop.hist if idx is None else loop.hist.index_select(1, idx)
-    rec = sc.recorder
-    if rec is not None:
-        d["rec"] = rec.rec if idx is None else rec.rec.index_select(1, idx)
-        d["rec_flags"] = rec.flags if idx is None else rec.flags.index_select(1, idx)
-    return {k: v.clone() for k, v in d.items()}
-
-
-def _obs(sc, lo=0, hi=None):
-    hi = sc.obst.n if hi is None else hi
-    d = dict(state=sc.obst.state[lo:hi], get=sc.obst.get_buf[lo:hi])
-    if sc.recorder is not None and sc.recorder.obs is not None:
-        d["rec_obs"] = sc.recorder.obs[:, lo:hi]
-    return {k: v.clone() for k, v in d.items()}
-
-
-def _assert_equal(a, b, what):
-    assert a.keys() == b.keys()
-    for k in a:
-        assert torch.equal(a[k], b[k]), (what, k)
 
 
 def _global_geometry(sc, dims):
@@ -105,7 +49,7 @@ def _uniform_runs(pkg, W, iroutes, T, B, K, mode):
     out = {}
 
     def run(name, specs, traffic=False, ticks=False, global_dims=None):
-        eng, x0 = _engine(pkg, iroutes, batch, T, mode)
+        eng, x0 = loop_engine(pkg, iroutes, batch, T, mode)
         kw = dict(traffic_of=np.zeros(B, dtype=np.int64)) if traffic else {}
         sc = pkg.ScenarioLoop(eng, x0, [specs] if traffic else specs, hist_cap=K, max_age=W.MAX_AGE, frame_window=20, mode=mode,
                               record=K, **kw)
@@ -120,7 +64,7 @@ def _uniform_runs(pkg, W, iroutes, T, B, K, mode):
             sc.run(K)
         torch.cuda.synchronize()
         assert int(sc.pre.status.abs().sum().item()) == 0
-        out[name] = (_state(sc), _obs(sc), int(sc.pre.col_flag.sum().item()), int(sc.loop.n_respawn.item()))
+        out[name] = (loop_state(sc), obstacle_state(sc), int(sc.pre.col_flag.sum().item()), int(sc.loop.n_respawn.item()))
 
     run("none", SPECS)
     run("car_table", with_dims(SPECS, CAR))
@@ -137,8 +81,8 @@ def _check_uniform(out, what):
     for ref, names in (("none", ("car_table", "car_table_traffic", "car_table_ticks")),
                        ("bike_global", ("bike_table", "bike_table_traffic", "bike_table_ticks"))):
         for n in names:
-            _assert_equal(out[ref][0], out[n][0], (what, n))
-            _assert_equal(out[ref][1], out[n][1], (what, n))
+            assert_state_equal(out[ref][0], out[n][0], (what, n))
+            assert_state_equal(out[ref][1], out[n][1], (what, n))
             assert out[ref][2:] == out[n][2:], (what, n)
     print(what, "cut egos at the last tick / respawns: car", out["none"][2:], "cyclist", out["bike_global"][2:])
 
@@ -197,13 +141,13 @@ def test_uniform_table_pre_tick_and_interacting(pkg, W, iroutes, routes):
     batch, sizes = W.interacting_batch(iroutes, G, T, seed=13)
     runs = []
     for specs in (SPECS[:3], with_dims(SPECS[:3], CAR)):
-        eng, xs = _engine(pkg, iroutes, batch, T)
+        eng, xs = loop_engine(pkg, iroutes, batch, T)
         il = pkg.InteractingLoop(eng, xs, group_sizes=sizes, obstacle_specs=specs, hist_cap=K, max_age=W.MAX_AGE, record=K)
         il.run(K)
         torch.cuda.synchronize()
-        runs.append((_state(il), _obs(il), il.pred_egos().clone()))
-    _assert_equal(runs[0][0], runs[1][0], "interacting")
-    _assert_equal(runs[0][1], runs[1][1], "interacting")
+        runs.append((loop_state(il), obstacle_state(il), il.pred_egos().clone()))
+    assert_state_equal(runs[0][0], runs[1][0], "interacting")
+    assert_state_equal(runs[0][1], runs[1][1], "interacting")
     assert torch.equal(runs[0][2], runs[1][2])
 
 
@@ -262,7 +206,7 @@ MIXED_B, MIXED_K, MIXED_SAMPLE = 96, 50, 48       # egos, ticks, compared egos (
 def _mixed_loop(pkg, W, iroutes, T, **kw):
     batch = W.ego_batch(iroutes, MIXED_B, T, rank=3)
     traffic_of = np.arange(MIXED_B) % len(MIXED_SETS)
-    eng, x0 = _engine(pkg, iroutes, batch, T)
+    eng, x0 = loop_engine(pkg, iroutes, batch, T)
     sc = pkg.ScenarioLoop(eng, x0, MIXED_SETS, hist_cap=MIXED_K, max_age=W.MAX_AGE, frame_window=20, traffic_of=traffic_of,
                           record=MIXED_K, **kw)
     return batch, traffic_of, eng, sc
@@ -306,7 +250,7 @@ def test_mixed_traffic_against_the_restatement(pkg, W, iroutes, SN, monkeypatch,
     for s in range(len(MIXED_SETS)):
         if obs_off[s + 1] > obs_off[s]:
             egos = [b for b in sample if set_of[b] == s]
-            e2, _ = _engine(pkg, iroutes, _sub(batch, np.array(egos)), T)
+            e2, _ = loop_engine(pkg, iroutes, sub_batch(batch, np.array(egos)), T)
             side[s] = (egos, e2, pkg.PreTick(e2, frame_window=20))
     n = dict(car=0, bike=0, not_car=0, not_bike=0, ticks=0, own_car=0, own_bike=0, stored_car=0, stored_bike=0)
     worst = 0.0
@@ -387,7 +331,7 @@ def test_each_ego_of_the_mixed_batch_equals_its_plain_loop(pkg, W, iroutes, T):
     batch, traffic_of, eng, sc = _mixed_loop(pkg, W, iroutes, T)
     plain = []
     for s, specs in enumerate(MIXED_SETS):
-        e, x = _engine(pkg, iroutes, _sub(batch, np.flatnonzero(traffic_of == s)), T)
+        e, x = loop_engine(pkg, iroutes, sub_batch(batch, np.flatnonzero(traffic_of == s)), T)
         plain.append(pkg.ScenarioLoop(e, x, specs, hist_cap=MIXED_K, max_age=W.MAX_AGE, frame_window=20, record=MIXED_K))
     _, _, _, ticked = _mixed_loop(pkg, W, iroutes, T)
     sc.run(MIXED_K)
@@ -396,14 +340,14 @@ def test_each_ego_of_the_mixed_batch_equals_its_plain_loop(pkg, W, iroutes, T):
     for _ in range(MIXED_K):
         ticked.tick()              # single-tick launches: what test_mixed_traffic_against_the_restatement compares with numpy
     torch.cuda.synchronize()
-    _assert_equal(_state(sc), _state(ticked), "run(K) against K ticks")
-    _assert_equal(_obs(sc), _obs(ticked), "run(K) against K ticks")
+    assert_state_equal(loop_state(sc), loop_state(ticked), "run(K) against K ticks")
+    assert_state_equal(obstacle_state(sc), obstacle_state(ticked), "run(K) against K ticks")
     _, obs_off = sc.traffic
     for s, p in enumerate(plain):
         idx = torch.from_numpy(np.flatnonzero(traffic_of == s)).to(eng.device)
-        _assert_equal(_state(sc, idx), _state(p), s)
+        assert_state_equal(loop_state(sc, idx), loop_state(p), s)
         if p.obst.n:
-            _assert_equal(_obs(sc, obs_off[s], obs_off[s + 1]), _obs(p), s)
+            assert_state_equal(obstacle_state(sc, obs_off[s], obs_off[s + 1]), obstacle_state(p), s)
     assert int(sc.loop.n_respawn.item()) == sum(int(p.loop.n_respawn.item()) for p in plain)
 
 
@@ -416,9 +360,9 @@ def test_interacting_egos_beside_a_cyclist(pkg, W, iroutes, SN, size):
     T, G, K = 13, 24, 30
     batch4, _ = W.interacting_batch(iroutes, G, T, seed=17)
     keep = np.array([4 * g + k for g in range(G) for k in range(size)])
-    batch = _sub(batch4, keep)
+    batch = sub_batch(batch4, keep)
     specs = [_bike(T_INT(1, False, 15, None)), T_INT(-1, True, 20, 2.0)]
-    eng, x0 = _engine(pkg, iroutes, batch, T)
+    eng, x0 = loop_engine(pkg, iroutes, batch, T)
     il = pkg.InteractingLoop(eng, x0, group_sizes=[size] * G, obstacle_specs=specs, max_age=W.MAX_AGE)
     car, bike = SN.shape_of(*SN.CAR), SN.shape_of(*SN.BIKE)
     shapes = [bike, car]
@@ -460,14 +404,6 @@ def test_interacting_egos_beside_a_cyclist(pkg, W, iroutes, SN, size):
 
 
 # ---------------------------------------------------------------------------------------------------- 6. refusals and clearing
-def _run_args(sc, n_obs=None, speed_cutoff=0):
-    loop, pre, ob, eng = sc.loop, sc.pre, sc.obst, sc.loop.eng
-    P = importlib.import_module(PKG_NAME + ".batched")._ptr
-    return (eng._ctx, eng.B, 3, *loop._loop_args(), P(pre.traj_idx), P(pre.prev_len), P(pre.col_flag), P(pre.status),
-            pre.frame_window, pre.margin, ob.n if n_obs is None else n_obs, P(ob.state), P(ob.param), P(ob.get_buf), pre.n_steps,
-            speed_cutoff, eng._stream())
-
-
 def test_refusals_leave_the_context_alone_and_clearing_restores(pkg, W, iroutes):
     """Twin loops, one of which is sent every refused call first: -22 with a message for a radius / wheelbase that is not
     positive, another n_obs in the run, obstacle and prediction calls (no obstacle at all passes), speed_cutoff with interacting
@@ -482,7 +418,7 @@ def test_refusals_leave_the_context_alone_and_clearing_restores(pkg, W, iroutes)
     dp = lambda a: np.ascontiguousarray(a, dtype=np.float64).ctypes.data_as(ctypes.c_void_p)   # noqa: E731
 
     def make(specs, cls=None, **kw):
-        eng, x0 = _engine(pkg, iroutes, batch, T)
+        eng, x0 = loop_engine(pkg, iroutes, batch, T)
         sc = (cls or pkg.ScenarioLoop)(eng, x0, obstacle_specs=specs, hist_cap=K, max_age=W.MAX_AGE, **kw)
         return eng, sc
 
@@ -492,7 +428,7 @@ def test_refusals_leave_the_context_alone_and_clearing_restores(pkg, W, iroutes)
     for bad, msg in ((tab * [1, 1, 0, 1], b"radius"), (tab * [1, 1, 1, -1], b"wheelbase"), (tab * [1, 1, -1, 1], b"radius")):
         assert lib.jsim_loop_set_vehicle_shapes(ctx, 3, dp(bad)) == -22 and msg in lib.jsim_last_error(ctx)
     assert lib.jsim_loop_set_vehicle_shapes(ctx, 3, None) == -22 and lib.jsim_loop_set_vehicle_shapes(ctx, -1, dp(tab)) == -22
-    assert lib.jsim_loop_run_scenario(*_run_args(sc, n_obs=2)) == -22 and b"shape table" in lib.jsim_last_error(ctx)
+    assert lib.jsim_loop_run_scenario(ctx, eng.B, 3, *sc._run_args(n_obs=2)) == -22 and b"shape table" in lib.jsim_last_error(ctx)
     assert lib.jsim_loop_obstacles(ctx, 2, P(sc.obst.state), P(sc.obst.param), P(sc.obst.get_buf), 1, eng._stream()) == -22
     assert b"shape table" in lib.jsim_last_error(ctx)
     pred = torch.zeros(4, sc.pre.n_steps, 3, dtype=torch.float64, device=eng.device)
@@ -500,14 +436,14 @@ def test_refusals_leave_the_context_alone_and_clearing_restores(pkg, W, iroutes)
     assert b"shape table" in lib.jsim_last_error(ctx)
     assert lib.jsim_loop_predict_obstacles(ctx, 0, None, sc.pre.n_steps, None, eng._stream()) == 0     # no obstacle at all passes
     assert lib.jsim_loop_set_groups(ctx, eng.B, len(sizes), np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32).ctypes.data_as(ctypes.c_void_p)) == 0
-    assert lib.jsim_loop_run_interacting(*_run_args(sc, speed_cutoff=1)) == -22 and b"truncate glue" in lib.jsim_last_error(ctx)
-    assert lib.jsim_loop_run_interacting(*_run_args(sc, n_obs=2)) == -22 and b"shape table" in lib.jsim_last_error(ctx)
+    assert lib.jsim_loop_run_interacting(ctx, eng.B, 3, *sc._run_args(speed_cutoff=1)) == -22 and b"truncate glue" in lib.jsim_last_error(ctx)
+    assert lib.jsim_loop_run_interacting(ctx, eng.B, 3, *sc._run_args(n_obs=2)) == -22 and b"shape table" in lib.jsim_last_error(ctx)
     assert lib.jsim_loop_set_groups(ctx, eng.B, 0, None) == 0
     sc.run(K)
     twin.run(K)
     torch.cuda.synchronize()
-    _assert_equal(_state(sc), _state(twin), "after refusals")
-    _assert_equal(_obs(sc), _obs(twin), "after refusals")
+    assert_state_equal(loop_state(sc), loop_state(twin), "after refusals")
+    assert_state_equal(obstacle_state(sc), obstacle_state(twin), "after refusals")
     # n = 0: the no-table behaviour again
     eng2, cleared = make(mixed)
     assert eng2.lib.jsim_loop_set_vehicle_shapes(eng2._ctx, 0, None) == 0
@@ -515,20 +451,20 @@ def test_refusals_leave_the_context_alone_and_clearing_restores(pkg, W, iroutes)
     cleared.run(K)
     plain.run(K)
     torch.cuda.synchronize()
-    _assert_equal(_state(cleared), _state(plain), "cleared")
-    _assert_equal(_obs(cleared), _obs(plain), "cleared")
+    assert_state_equal(loop_state(cleared), loop_state(plain), "cleared")
+    assert_state_equal(obstacle_state(cleared), obstacle_state(plain), "cleared")
     # interacting egos: a global geometry without a table is still refused, with a table it runs
     eng3, il = make(SPECS[:2], cls=pkg.InteractingLoop, group_sizes=sizes)
     _global_geometry(il, BIKE)
-    assert eng3.lib.jsim_loop_run_interacting(*_run_args(il)) == -22 and b"another shape" in eng3.lib.jsim_last_error(eng3._ctx)
+    assert eng3.lib.jsim_loop_run_interacting(eng3._ctx, eng3.B, 3, *il._run_args()) == -22 and b"another shape" in eng3.lib.jsim_last_error(eng3._ctx)
     pkg.closed_loop._register_shapes(eng3, tab[:2])
-    assert eng3.lib.jsim_loop_run_interacting(*_run_args(il)) == 0
+    assert eng3.lib.jsim_loop_run_interacting(eng3._ctx, eng3.B, 3, *il._run_args()) == 0
     torch.cuda.synchronize()
     # the Python layer: ValueError before the device is touched
     for dims in (dict(L=1.0, wheelbase=2.0), dict(L=0.0), dict(width=-1.0)):
-        before = _state(sc)
+        before = loop_state(sc)
         with pytest.raises(ValueError):
             pkg.ScenarioLoop(eng, sc.loop.x0, [dict(SPECS[0], dims=dims)])
-        _assert_equal(before, _state(sc), dims)
+        assert_state_equal(before, loop_state(sc), dims)
     with pytest.raises(ValueError, match="shape table"):
         pkg.sharding.CabiGather(eng, rank=0, world=2, unique_id=b"\0" * 128)

@@ -12,9 +12,10 @@ import importlib
 import json
 import os
 import sys
-import time
 
 import torch
+
+from loop_bench import timed_run
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
@@ -26,15 +27,8 @@ def timed(routes, G, T, sizes_of, ticks, warmup):
     batch, sizes = W.interacting_batch(routes, G, T, seed=1)
     eng, x0 = W.make_engine(routes, batch, T, "cuda:0")
     il = pkg.InteractingLoop(eng, x0, group_sizes=sizes_of(sizes, eng.B), max_age=W.MAX_AGE)
-    il.run(warmup)
-    torch.cuda.synchronize()
     cut = torch.zeros((), dtype=torch.int64, device=eng.device)
-    t0 = time.perf_counter()
-    for _ in range(ticks):
-        il.tick()
-        cut += il.pre.col_flag.sum()
-    torch.cuda.synchronize()
-    dt = time.perf_counter() - t0
+    dt = timed_run(il, warmup, ticks, each_tick=lambda: cut.add_(il.pre.col_flag.sum()))
     return eng.B * ticks / dt, dt / ticks * 1e3, int(cut.item()), int((eng.status != 0).sum().item())
 
 

@@ -20,11 +20,11 @@ import importlib
 import json
 import os
 import sys
-import time
+
+from loop_bench import loop_fields, scenario_loop, summarize, timed_run
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 BIKE = dict(L=1.0, width=0.45, extra_length=0.64)     # BicycleRealDimensions, main/lib/car_dimensions.py:92-100
 CAR = dict(L=2.86, width=2.0, extra_length=0.64)      # the egos' BicycleModelDimensions
@@ -49,7 +49,6 @@ def main():
     ap.add_argument("--summarize", metavar="DIR")
     a = ap.parse_args()
     if a.summarize:
-        from bench_traffic import summarize
         summarize(a.summarize)
         return
     import torch
@@ -59,21 +58,11 @@ def main():
     T, B = a.horizon, a.egos
     for rnd in range(a.rounds):
         for way in a.ways[rnd % len(a.ways):] + a.ways[:rnd % len(a.ways)]:   # another way goes first in every round
-            batch = W.ego_batch(routes, B, T)
-            eng, x0 = W.make_engine(routes, batch, T, "cuda:0")
-            loop = pkg.ScenarioLoop(eng, x0, specs_of(way, W.OBSTACLE_SPECS), max_age=W.MAX_AGE)
-            loop.run(a.warmup)
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            loop.run(a.ticks)
-            torch.cuda.synchronize()
-            dt = time.perf_counter() - t0
-            print(json.dumps({"way": way, "round": rnd, "egos": eng.B, "T": T, "ticks": a.ticks, "vehicles": loop.obst.n,
-                              "table": None if loop.shapes is None else len(loop.shapes),
-                              "ego_steps_per_s": round(eng.B * a.ticks / dt), "ms_per_tick": round(dt / a.ticks * 1e3, 4),
-                              "cut_last_tick": int(loop.pre.col_flag.sum().item()),
-                              "failed_last_tick": int((eng.status != 0).sum().item())}), flush=True)
-            del loop, eng, x0
+            loop = scenario_loop(pkg, routes, B, T, specs_of(way, W.OBSTACLE_SPECS))
+            dt = timed_run(loop, a.warmup, a.ticks)
+            print(json.dumps({"way": way, "round": rnd, "table": None if loop.shapes is None else len(loop.shapes),
+                              **loop_fields(loop, a.ticks, dt)}), flush=True)
+            del loop
             torch.cuda.empty_cache()
 
 

@@ -15,33 +15,15 @@ The kernel-time share of the obstacle rollout and prediction comes from a profil
     python3 tools/bench_traffic.py [--egos 4096] [--ticks 60] [--warmup 10] [--ways shared per_ego per_group]
 """
 import argparse
-import csv
-import glob
 import importlib
 import json
 import os
 import sys
-import time
+
+from loop_bench import loop_fields, scenario_loop, summarize, timed_run
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
-
-
-def summarize(out_dir):
-    """Kernel time by name from rocprofv3's *kernel_stats.csv under out_dir: total, and the obstacle kernels' share."""
-    files = glob.glob(os.path.join(out_dir, "**", "*kernel_stats.csv"), recursive=True)
-    if not files:
-        raise SystemExit(f"no *kernel_stats.csv under {out_dir}")
-    for path in files:
-        rows = list(csv.DictReader(open(path)))
-        tot = sum(float(r["TotalDurationNs"]) for r in rows)
-        by = {r["Name"]: (int(r["Calls"]), float(r["TotalDurationNs"])) for r in rows}
-        obst = {n: v for n, v in by.items() if n.startswith("obstacle_")}
-        t_obst = sum(v[1] for v in obst.values())
-        print(json.dumps({"stats": os.path.relpath(path, out_dir), "kernel_ms": round(tot / 1e6, 3),
-                          "obstacle_share": round(t_obst / tot, 4) if tot else None,
-                          "kernels": {n.split("(")[0][:60]: {"calls": c, "ms": round(t / 1e6, 3), "share": round(t / tot, 4)}
-                                      for n, (c, t) in sorted(by.items(), key=lambda kv: -kv[1][1])}}), flush=True)
 
 
 def main():
@@ -56,7 +38,6 @@ def main():
     if a.summarize:
         summarize(a.summarize)
         return
-    import torch
     pkg = importlib.import_module("av-simulation-at-intersections_amd")
     W = pkg.workloads
     routes = W.route_table(False)[0]
@@ -67,24 +48,13 @@ def main():
             eng, x0 = W.make_engine(routes, batch, T, "cuda:0")
             sets, tog = W.traffic_batch(B // 4, seed=2, vehicles=4)
             loop = pkg.InteractingLoop(eng, x0, group_sizes=sizes, obstacle_specs=sets, max_age=W.MAX_AGE, traffic_of=tog)
+        elif way == "shared":
+            loop = scenario_loop(pkg, routes, B, T, W.OBSTACLE_SPECS)
         else:
-            batch = W.ego_batch(routes, B, T)
-            eng, x0 = W.make_engine(routes, batch, T, "cuda:0")
-            if way == "shared":
-                loop = pkg.ScenarioLoop(eng, x0, W.OBSTACLE_SPECS, max_age=W.MAX_AGE)
-            else:
-                sets, tof = W.traffic_batch(B, seed=2, vehicles=4)
-                loop = pkg.ScenarioLoop(eng, x0, sets, max_age=W.MAX_AGE, traffic_of=tof)
-        loop.run(a.warmup)
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        loop.run(a.ticks)
-        torch.cuda.synchronize()
-        dt = time.perf_counter() - t0
-        print(json.dumps({"way": way, "egos": eng.B, "T": T, "ticks": a.ticks, "vehicles": loop.obst.n,
-                          "ego_steps_per_s": round(eng.B * a.ticks / dt), "ms_per_tick": round(dt / a.ticks * 1e3, 4),
-                          "cut_last_tick": int(loop.pre.col_flag.sum().item()),
-                          "failed_last_tick": int((eng.status != 0).sum().item())}), flush=True)
+            sets, tof = W.traffic_batch(B, seed=2, vehicles=4)
+            loop = scenario_loop(pkg, routes, B, T, sets, traffic_of=tof)
+        dt = timed_run(loop, a.warmup, a.ticks)
+        print(json.dumps({"way": way, **loop_fields(loop, a.ticks, dt)}), flush=True)
 
 
 if __name__ == "__main__":
