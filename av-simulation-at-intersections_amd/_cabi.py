@@ -38,6 +38,7 @@ EXPORTS = (
     "jsim_loop_set_groups", "jsim_loop_predict_egos", "jsim_loop_run_interacting",
     "jsim_loop_set_traffic", "jsim_loop_set_recorder", "jsim_loop_set_vehicle_shapes",
     "jsim_comm_unique_id", "jsim_comm_init", "jsim_mpc_gather", "jsim_comm_destroy", "jsim_plan_routes",
+    "jsim_plan_routes_weighted",
 )
 
 _lib = None
@@ -132,6 +133,9 @@ def load() -> C.CDLL:
     lib.jsim_plan_routes.restype = C.c_int
     #                               dev  R    start goal box tol hp hp_off  n_obs  r_off mp_pts mp_len  n_prim n_pts cc  cc_off wh wc  max_path  outs
     lib.jsim_plan_routes.argtypes = [i32, i32, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, i32, i32, vp, vp, vp, vp, i32, i32] + [vp] * 7
+    lib.jsim_plan_routes_weighted.restype = C.c_int
+    #                                        ... as above ...                                                wh  wc form max_path cap  outs
+    lib.jsim_plan_routes_weighted.argtypes = [i32, i32, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, i32, i32] + [vp] * 7
     if lib.jsim_abi_version() != ABI_VERSION:
         raise JsimError(f"libjsim_mpc.so ABI {lib.jsim_abi_version()} != binding ABI {ABI_VERSION}")
     _lib = lib

@@ -1959,41 +1959,50 @@ extern "C" int jsim_comm_destroy(jsim_ctx *ctx)
 
 // Route planner: HOST pointers in and out -- a one-time precompute whose (M, 3) output is what
 // jsim_mpc_set_paths takes; device buffers are allocated, filled, searched (one wavefront per route) and read back inside the call.
-extern "C" int jsim_plan_routes(int device_id, int32_t n_routes, const double *start, const double *goal, const double *goal_box,
-                                const double *tol, const double *hp, const int32_t *hp_off, int32_t n_obs_total,
-                                const int32_t *route_obs_off, const double *mp_pts, const double *mp_len, int32_t n_prim,
-                                int32_t n_pts, const double *cc_pts, const int32_t *cc_off, const double *wh, const double *wc,
-                                int32_t max_path, int32_t node_cap, int32_t *status, double *cost, int32_t *n_prims, int32_t *prims,
-                                double *nodes, double *traj, int32_t *n_expanded)
+// Both entry points below end here: wh [R][5], wc [R][4] and form [R] are per-route tables; `who` names the caller in the messages.
+static int plan_routes_tables(const char *who, int device_id, int32_t n_routes, const double *start, const double *goal, const double *goal_box,
+                              const double *tol, const double *hp, const int32_t *hp_off, int32_t n_obs_total,
+                              const int32_t *route_obs_off, const double *mp_pts, const double *mp_len, int32_t n_prim,
+                              int32_t n_pts, const double *cc_pts, const int32_t *cc_off, const double *wh, const double *wc,
+                              const int32_t *form, int32_t max_path, int32_t node_cap, int32_t *status, double *cost, int32_t *n_prims,
+                              int32_t *prims, double *nodes, double *traj, int32_t *n_expanded)
 {
     if (n_routes < 0 || n_prim < 1 || n_prim > JPL_MAX_PRIM || n_pts < 2 || max_path < 1 || n_obs_total < 0 || node_cap < 64 || node_cap > (1 << 24))
-        return fail(nullptr, -22, "jsim_plan_routes: bad sizes (routes %d, primitives %d (max %d), points %d, max_path %d)", n_routes, n_prim,
+        return fail(nullptr, -22, "%s: bad sizes (routes %d, primitives %d (max %d), points %d, max_path %d)", who, n_routes, n_prim,
                     JPL_MAX_PRIM, n_pts, max_path);
     if (n_routes == 0) return 0;
-    if (!start || !goal || !goal_box || !tol || !hp_off || !route_obs_off || !mp_pts || !mp_len || !cc_pts || !cc_off || !wh || !wc ||
+    if (!start || !goal || !goal_box || !tol || !hp_off || !route_obs_off || !mp_pts || !mp_len || !cc_pts || !cc_off || !wh || !wc || !form ||
         !status || !cost || !n_prims || !prims || !nodes || !traj || !n_expanded || (n_obs_total > 0 && !hp))
-        return fail(nullptr, -22, "jsim_plan_routes: null argument");
+        return fail(nullptr, -22, "%s: null argument", who);
     // the offset tables index device arrays from inside the kernel: they must be what they claim to be
     for (int k = 0; k < n_obs_total; ++k)
-        if (hp_off[k] < 0 || hp_off[k + 1] < hp_off[k]) return fail(nullptr, -22, "jsim_plan_routes: hp_off is not non-decreasing at %d", k);
-    if (hp_off[0] != 0) return fail(nullptr, -22, "jsim_plan_routes: hp_off[0] = %d", hp_off[0]);
+        if (hp_off[k] < 0 || hp_off[k + 1] < hp_off[k]) return fail(nullptr, -22, "%s: hp_off is not non-decreasing at %d", who, k);
+    if (hp_off[0] != 0) return fail(nullptr, -22, "%s: hp_off[0] = %d", who, hp_off[0]);
     for (int k = 0; k < n_routes; ++k)
         if (route_obs_off[k] < 0 || route_obs_off[k + 1] < route_obs_off[k] || route_obs_off[k + 1] > n_obs_total)
-            return fail(nullptr, -22, "jsim_plan_routes: route_obs_off[%d..%d] = %d, %d with %d obstacles", k, k + 1, route_obs_off[k], route_obs_off[k + 1], n_obs_total);
+            return fail(nullptr, -22, "%s: route_obs_off[%d..%d] = %d, %d with %d obstacles", who, k, k + 1, route_obs_off[k], route_obs_off[k + 1], n_obs_total);
     for (int k = 0; k < n_prim; ++k)
-        if (cc_off[k] < 0 || cc_off[k + 1] < cc_off[k]) return fail(nullptr, -22, "jsim_plan_routes: cc_off is not non-decreasing at %d", k);
+        if (cc_off[k] < 0 || cc_off[k + 1] < cc_off[k]) return fail(nullptr, -22, "%s: cc_off is not non-decreasing at %d", who, k);
+    for (int k = 0; k < n_routes; ++k) {
+        if (form[k] != JPL_FORM_GENERIC && form[k] != JPL_FORM_MULTI)
+            return fail(nullptr, -22, "%s: form[%d] = %d (0: mp_search_ww_generic, 1: multi_trajectory_planner)", who, k, form[k]);
+        for (int j = 0; j < 9; ++j) {
+            const double w = j < 5 ? wh[5 * (size_t)k + j] : wc[4 * (size_t)k + j - 5];
+            if (!std::isfinite(w)) return fail(nullptr, -22, "%s: route %d: %s[%d] is not finite", who, k, j < 5 ? "wh" : "wc", j < 5 ? j : j - 5);
+        }
+    }
     int ndev = 0;
     HIP_TRY(nullptr, hipGetDeviceCount(&ndev));
-    if (device_id < 0 || device_id >= ndev) return fail(nullptr, -19, "jsim_plan_routes: device %d of %d", device_id, ndev);
+    if (device_id < 0 || device_id >= ndev) return fail(nullptr, -19, "%s: device %d of %d", who, device_id, ndev);
     DeviceGuard dev_guard(device_id);
     JSIM_GUARD_OK(nullptr);
     const int R = n_routes, cap = node_cap, seg = n_pts - 1;
     // sizes in 64 bits BEFORE anything is allocated: per route ~84 B per node slot (+ the hash table) and the output arrays
-    if (max_path > 4096 || n_pts > 4096) return fail(nullptr, -22, "jsim_plan_routes: max_path %d / points per primitive %d above 4096", max_path, n_pts);
+    if (max_path > 4096 || n_pts > 4096) return fail(nullptr, -22, "%s: max_path %d / points per primitive %d above 4096", who, max_path, n_pts);
     {
         const unsigned long long per_route = 84ull * (unsigned long long)cap * 3ull + 8ull * 3ull * (unsigned long long)max_path * (unsigned long long)seg;
         if ((unsigned long long)R * per_route > (64ull << 30))
-            return fail(nullptr, -12, "jsim_plan_routes: %d routes x node_cap %d x max_path %d would need more than 64 GiB of device memory", R, cap, max_path);
+            return fail(nullptr, -12, "%s: %d routes x node_cap %d x max_path %d would need more than 64 GiB of device memory", who, R, cap, max_path);
     }
     int hash_cap = 128;
     while (hash_cap < 2 * cap) hash_cap <<= 1;
@@ -2045,8 +2054,8 @@ extern "C" int jsim_plan_routes(int device_id, int32_t n_routes, const double *s
     PlanP P;
     memset(&P, 0, sizeof(P));
     P.n_routes = R; P.n_prim = n_prim; P.n_pts = n_pts; P.max_path = max_path; P.node_cap = cap;
-    P.wh_dist = wh[0]; P.wh_theta = wh[1]; P.wh_steer = wh[2]; P.wh_obst = wh[3]; P.wh_center = wh[4];
-    P.wc_dist = wc[0]; P.wc_steer = wc[1]; P.wc_obst = wc[2]; P.wc_center = wc[3];
+    P.wh = (const double *)put(wh, sizeof(double) * 5 * R); P.wc = (const double *)put(wc, sizeof(double) * 4 * R);
+    P.form = (const int *)put(form, sizeof(int) * R);
     P.start = (const double *)put(start, sizeof(double) * 3 * R); P.goal = (const double *)put(goal, sizeof(double) * 3 * R);
     P.goal_box = (const double *)put(goal_box, sizeof(double) * 4 * R); P.tol = (const double *)put(tol, sizeof(double) * R);
     P.hp = (const double *)put(hp, sizeof(double) * 3 * n_hp); P.hp_off = (const int *)put(hp_off, sizeof(int) * (n_obs_total + 1));
@@ -2065,10 +2074,10 @@ extern "C" int jsim_plan_routes(int device_id, int32_t n_routes, const double *s
     P.nodes = (double *)dalloc(sizeof(double) * (size_t)R * (max_path + 1) * 3);
     P.traj = (double *)dalloc(sizeof(double) * (size_t)R * max_path * seg * 3);
     if (!P.start || !P.goal || !P.goal_box || !P.tol || !P.hp || !P.hp_off || !P.route_obs_off || !P.obc || !P.mp_pts || !P.mp_len || !P.cc_pts ||
-        !P.cc_off || !P.nx || !P.ny || !P.nth || !P.ng || !P.nparent || !P.nprim || !P.htab || !P.ov_gh || !P.ov_g || !P.ov_id || !P.status || !P.n_prims || !P.n_expanded || !P.prims ||
+        !P.cc_off || !P.wh || !P.wc || !P.form || !P.nx || !P.ny || !P.nth || !P.ng || !P.nparent || !P.nprim || !P.htab || !P.ov_gh || !P.ov_g || !P.ov_id || !P.status || !P.n_prims || !P.n_expanded || !P.prims ||
         !P.cost || !P.nodes || !P.traj) {
         cleanup();
-        return fail(nullptr, -12, "jsim_plan_routes: device allocation / upload failed");
+        return fail(nullptr, -12, "%s: device allocation / upload failed", who);
     }
     hipError_t e = hipMemset(P.cost, 0, sizeof(double) * R);
     if (e == hipSuccess) e = hipMemset(P.htab, 0xff, sizeof(int) * (size_t)R * hash_cap);
@@ -2100,8 +2109,45 @@ extern "C" int jsim_plan_routes(int device_id, int32_t n_routes, const double *s
     if (e == hipSuccess) e = hipMemcpy(nodes, P.nodes, sizeof(double) * (size_t)R * (max_path + 1) * 3, hipMemcpyDeviceToHost);
     if (e == hipSuccess) e = hipMemcpy(traj, P.traj, sizeof(double) * (size_t)R * max_path * seg * 3, hipMemcpyDeviceToHost);
     cleanup();
-    if (e != hipSuccess) return fail(nullptr, -5, "jsim_plan_routes: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return fail(nullptr, -5, "%s: %s", who, hipGetErrorString(e));
     return 0;
+}
+
+// One launch-wide weight set, the generic form (mp_search_ww_generic.py): its row repeated for every route.
+extern "C" int jsim_plan_routes(int device_id, int32_t n_routes, const double *start, const double *goal, const double *goal_box,
+                                const double *tol, const double *hp, const int32_t *hp_off, int32_t n_obs_total,
+                                const int32_t *route_obs_off, const double *mp_pts, const double *mp_len, int32_t n_prim,
+                                int32_t n_pts, const double *cc_pts, const int32_t *cc_off, const double *wh, const double *wc,
+                                int32_t max_path, int32_t node_cap, int32_t *status, double *cost, int32_t *n_prims, int32_t *prims,
+                                double *nodes, double *traj, int32_t *n_expanded)
+{
+    if (n_routes > (1 << 24))   // (at >= 16 KiB of workspace per route: beyond the 64 GiB the shared part allows)
+        return fail(nullptr, -12, "jsim_plan_routes: %d routes would need more than 64 GiB of device memory", n_routes);
+    const size_t R = n_routes > 0 ? (size_t)n_routes : 0;
+    const bool tables = wh && wc;   // (a null pointer is reported by the shared part, after the sizes)
+    std::vector<double> wht(5 * R), wct(4 * R);
+    std::vector<int32_t> formt(R + 1, JPL_FORM_GENERIC);
+    for (size_t k = 0; tables && k < R; ++k) {
+        for (int j = 0; j < 5; ++j) wht[5 * k + j] = wh[j];
+        for (int j = 0; j < 4; ++j) wct[4 * k + j] = wc[j];
+    }
+    return plan_routes_tables("jsim_plan_routes", device_id, n_routes, start, goal, goal_box, tol, hp, hp_off, n_obs_total, route_obs_off, mp_pts,
+                              mp_len, n_prim, n_pts, cc_pts, cc_off, tables ? wht.data() : nullptr, tables ? wct.data() : nullptr, formt.data(),
+                              max_path, node_cap, status, cost, n_prims, prims, nodes, traj, n_expanded);
+}
+
+// Per-route weights and cost form: a weight sweep of one scenario (Planner_Sensitivity_*.py, one planner run per set) or the candidate
+// set of the multi-trajectory planner (multi_trajectory_planner.py:242-269 run_all, one A* per (e, p, o)) as ONE launch.
+extern "C" int jsim_plan_routes_weighted(int device_id, int32_t n_routes, const double *start, const double *goal, const double *goal_box,
+                                         const double *tol, const double *hp, const int32_t *hp_off, int32_t n_obs_total,
+                                         const int32_t *route_obs_off, const double *mp_pts, const double *mp_len, int32_t n_prim,
+                                         int32_t n_pts, const double *cc_pts, const int32_t *cc_off, const double *wh, const double *wc,
+                                         const int32_t *form, int32_t max_path, int32_t node_cap, int32_t *status, double *cost,
+                                         int32_t *n_prims, int32_t *prims, double *nodes, double *traj, int32_t *n_expanded)
+{
+    return plan_routes_tables("jsim_plan_routes_weighted", device_id, n_routes, start, goal, goal_box, tol, hp, hp_off, n_obs_total, route_obs_off,
+                              mp_pts, mp_len, n_prim, n_pts, cc_pts, cc_off, wh, wc, form, max_path, node_cap, status, cost, n_prims, prims,
+                              nodes, traj, n_expanded);
 }
 
 // the shape table's (thr, thr_sq) rows: check_collision_moving_bicycle's min_distance = the egos' radius + the vehicle's own

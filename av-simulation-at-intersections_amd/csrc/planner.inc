@@ -7,6 +7,10 @@
 //   :150-155 is_goal      :245-257 path_to_full_trajectory
 //   main/lib/a_star.py:31-78  AStar.run: heap of (g + h, g, node, predecessor), dict of best predecessors keyed by the exact node
 //   main/lib/obstacles.py:157-176 check_collision ; main/lib/linalg.py:4-57 ; main/lib/maths.py:4-10
+// and, per route (weights wh / wc and a cost form from tables, one row per route: a weight sweep or the candidate set of the
+// multi-trajectory planner is ONE launch), the cost terms of main/planner/multi_trajectory_planner.py:112-201 (JPL_FORM_MULTI):
+//   :185-201 distance_to_goal = e hypot + p |wrapped heading difference| + o steering proxy ; :137-141 the edge's obstacle term
+//   guarded by wc_obstacle, 1 / d for d > 0
 //
 // Most searches are small (13-208 expansions, open list <= 565 entries on the 18 reference routes), a few lane-changing routes of
 // the two-lane scenario are not (up to 23k expansions, 62k open entries -- 48 s of the reference's Python).  The open list is a
@@ -32,6 +36,8 @@
 #define JPL_MAX_HP 512    /* half-planes of one query's obstacle set */
 #define JPL_MAX_OBS 64
 #define JPL_D 64          /* arity of the open list's heap: one child per lane */
+#define JPL_FORM_GENERIC 0   /* main/lib/mp_search_ww_generic.py: heuristic :166-190, edge cost :202-243 */
+#define JPL_FORM_MULTI 1     /* main/planner/multi_trajectory_planner.py: heuristic :185-201, edge cost :112-153 */
 #define JPL_PASSES ((JPL_MAX_PRIM * JPL_MAX_CC + 63) / 64)   /* (primitive, collision point) pairs per lane */
 // One wavefront per route: what one lane writes -- to LDS or to memory -- the others see in program order, with no wait and no barrier
 // instruction (LLVM's AMDGPU memory model: a wavefront-scope fence needs no code on gfx942 / gfx950); the fence keeps the COMPILER
@@ -40,7 +46,8 @@
 
 struct PlanP {
     int n_routes, n_prim, n_pts, max_path, node_cap;
-    double wh_dist, wh_theta, wh_steer, wh_obst, wh_center, wc_dist, wc_steer, wc_obst, wc_center;
+    const double *wh, *wc;                         // [R][5] (dist, theta, steering, obstacle, center), [R][4] (dist, steering, obstacle, center)
+    const int *form;                               // [R] 0: mp_search_ww_generic.py, 1: multi_trajectory_planner.py (JPL_FORM_*)
     const double *start, *goal, *goal_box, *tol;   // [R][3], [R][3], [R][4] (x1, y1, x2, y2), [R]
     const double *hp;                              // [.][3] half-planes a x + b y + c <= 0 (inside)
     const int *hp_off;                             // per obstacle: [first, last) into hp
@@ -122,6 +129,15 @@ __global__ __launch_bounds__(64) void plan_astar_kernel(const PlanP P)
     const double gx = P.goal[3 * r], gy = P.goal[3 * r + 1], gth = P.goal[3 * r + 2];
     const double bx1 = P.goal_box[4 * r], by1 = P.goal_box[4 * r + 1], bx2 = P.goal_box[4 * r + 2], by2 = P.goal_box[4 * r + 3];
     const double tol = P.tol[r];
+    // The route's own weights and cost form (jsim_plan_routes_weighted): one row per route, the same for all its lanes -- read once,
+    // here, and marked uniform: scalar registers throughout the search, and the form a scalar branch (one side's code is run)
+    const double wh_dist = uni(P.wh[5 * r]), wh_theta = uni(P.wh[5 * r + 1]), wh_steer = uni(P.wh[5 * r + 2]), wh_obst = uni(P.wh[5 * r + 3]);
+    const double wh_center = uni(P.wh[5 * r + 4]);
+    const double wc_dist = uni(P.wc[4 * r]), wc_steer = uni(P.wc[4 * r + 1]), wc_obst = uni(P.wc[4 * r + 2]), wc_center = uni(P.wc[4 * r + 3]);
+    const bool multi = uni(P.form[r]) == JPL_FORM_MULTI;
+    // the edge's obstacle term: guarded by the HEURISTIC's weight in the generic file (sic, mp_search_ww_generic.py:230), by the
+    // edge's own in the multi-trajectory planner (multi_trajectory_planner.py:139)
+    const bool edge_obst = multi ? wc_obst != 0.0 : wh_obst != 0.0;
     const int o0 = P.route_obs_off[r], o1 = P.route_obs_off[r + 1], n_obs = o1 - o0;
     const int h0 = P.hp_off[o0], n_hp = P.hp_off[o1] - h0;
     bool bad = n_obs > JPL_MAX_OBS || n_hp > JPL_MAX_HP || NP > JPL_MAX_PRIM;
@@ -414,16 +430,17 @@ __global__ __launch_bounds__(64) void plan_astar_kernel(const PlanP P)
             if (ok) {
                 const double steer = jpl_steer_change(th, eth);
                 double obst = 0.0, center = 0.0;
-                if (P.wh_obst != 0.0) { // (sic: the heuristic's weight guards the edge's obstacle term, mp_search_ww_generic.py:230)
+                if (edge_obst) {
                     double best = INFINITY;
                     for (int e = 0; e < n_hp; ++e) {
                         const double a = hpl[3 * e], b = hpl[3 * e + 1], c = hpl[3 * e + 2];
                         best = fmin(best, fabs(a * ex + b * ey + c) / sqrt(a * a + b * b));
                     }
-                    obst = best != 0.0 ? 1.0 / best : INFINITY;
+                    if (multi) obst = best > 0.0 ? 1.0 / best : INFINITY;        // `1.0 / d if d > 0.0 else inf` (:141)
+                    else obst = best != 0.0 ? 1.0 / best : INFINITY;
                 }
-                if (P.wc_center != 0.0) center = sqrt(ex * ex + ey * ey);
-                const double edge = ((P.wc_dist * lplen + P.wc_steer * steer) + P.wc_obst * obst) + P.wc_center * center;
+                if (wc_center != 0.0) center = sqrt(ex * ex + ey * ey);
+                const double edge = ((wc_dist * lplen + wc_steer * steer) + wc_obst * obst) + wc_center * center;
                 const double ngk = g + edge;
                 // `if neighbor not in pred_dict or neighbor_g < pred_dict[neighbor][0]`
                 if (j0 >= 0) {
@@ -439,14 +456,21 @@ __global__ __launch_bounds__(64) void plan_astar_kernel(const PlanP P)
                 }
                 if (ex == x && ey == y && eth == th && !(ngk < g)) ok = 0;   // (the node itself: its dict entry is written at the end)
                 if (ok) {
-                    const double dxy = sqrt((ex - gx) * (ex - gx) + (ey - gy) * (ey - gy));
-                    const double ad = fabs(eth - gth);
-                    const double dth = fmin(ad, ad - tol / 2);
                     const double hs = jpl_steer_change(eth, gth);
-                    double hob = 0.0, hce = 0.0;
-                    if (P.wh_obst != 0.0) hob = obst;
-                    if (P.wh_center != 0.0) hce = sqrt(ex * ex + ey * ey);
-                    const double h = (((P.wh_dist * dxy + P.wh_theta * dth) + P.wh_steer * hs) + P.wh_obst * hob) + P.wh_center * hce;
+                    double h;
+                    if (multi) {    // e hypot(x - gx, y - gy) + p |((theta - gtheta) + pi) % 2 pi - pi| + o steering_change(node, goal) (:193-200)
+                        const double dxy = hypot(ex - gx, ey - gy);
+                        const double dth = fabs(jpl_pymod((eth - gth) + 3.141592653589793, 2 * 3.141592653589793) - 3.141592653589793);
+                        h = (wh_dist * dxy + wh_theta * dth) + wh_steer * hs;
+                    } else {
+                        const double dxy = sqrt((ex - gx) * (ex - gx) + (ey - gy) * (ey - gy));
+                        const double ad = fabs(eth - gth);
+                        const double dth = fmin(ad, ad - tol / 2);
+                        double hob = 0.0, hce = 0.0;
+                        if (wh_obst != 0.0) hob = obst;
+                        if (wh_center != 0.0) hce = sqrt(ex * ex + ey * ey);
+                        h = (((wh_dist * dxy + wh_theta * dth) + wh_steer * hs) + wh_obst * hob) + wh_center * hce;
+                    }
                     my_g = ngk; my_gh = ngk + h; my_x = ex; my_y = ey; my_th = eth;
                 }
             }

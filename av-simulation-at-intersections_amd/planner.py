@@ -1,6 +1,6 @@
 """Route planner on the MI355X: the reference's A* over motion primitives
 (main/lib/mp_search_ww_generic.py + main/lib/a_star.py) for a batch of route queries, one wavefront per route
-(csrc/planner.inc behind `jsim_plan_routes`).  The (M, 3) [x, y, yaw] trajectories it returns are what `MPC(cx, cy, cyaw, ...)`
+(csrc/planner.inc behind `jsim_plan_routes` / `jsim_plan_routes_weighted`).  The (M, 3) [x, y, yaw] trajectories it returns are what `MPC(cx, cy, cyaw, ...)`
 / `BatchedMPC(paths, ...)` take -- exactly the hand-over of main/scenarios/mpc_intersection.py:63-76.
 
 The motion primitives are regenerated from the reference's recipe (main/create_motion_primitives_bicycle_model.py:12-27:
@@ -23,6 +23,7 @@ MP_NAMES = ("straight", "left1", "left2", "left3", "left4", "right1", "right2", 
 MP_STEER = (0.0, 0.1, 0.2, 0.3, 0.4, -0.1, -0.2, -0.3, -0.4)     # main/create_motion_primitives_prius.py:19-29
 WH_DEFAULT = (1.0, 2.7, 15.0, 0.0, 0.0)                            # mp_search_ww_generic.py:29-31
 WC_DEFAULT = (1.0, 5.0, 0.1, 0.0)                                  # :33
+FORM_GENERIC, FORM_MULTI = 0, 1    # cost terms of main/lib/mp_search_ww_generic.py / main/planner/multi_trajectory_planner.py
 
 
 def make_motion_primitives(L: float = 2.86, v: float = 8.3, n_steps: int = 60, dt: float = 0.01):
@@ -157,15 +158,45 @@ class PlannedRoute:
     n_expanded: int
 
 
+def weight_tables(n_routes: int, wh=WH_DEFAULT, wc=WC_DEFAULT, form=FORM_GENERIC):
+    """(wh [R, 5], wc [R, 4], form [R] int32) from one row each (repeated for every route) or R rows each; raises ValueError for
+    any other shape, a form outside {0, 1} or a weight that is not finite.  No device is touched."""
+    R = int(n_routes)
+
+    def table(a, width, name):
+        a = np.asarray(a, dtype=np.float64)
+        if a.shape == (width,):
+            a = np.broadcast_to(a, (R, width))
+        if a.shape != (R, width):
+            raise ValueError(f"{name} must have shape ({width},) or ({R}, {width}) for {R} routes, got {a.shape}")
+        if not np.all(np.isfinite(a)):
+            raise ValueError(f"{name} must be finite")
+        return np.ascontiguousarray(a)
+
+    f = np.asarray(form)
+    if f.dtype.kind not in "iub" or f.shape not in ((), (R,)):
+        raise ValueError(f"form must be an integer or {R} integers (one per route), got {f.dtype} {f.shape}")
+    f = np.ascontiguousarray(np.broadcast_to(f.astype(np.int32), (R,)))
+    if not np.all((f == FORM_GENERIC) | (f == FORM_MULTI)):
+        raise ValueError(f"form must be {FORM_GENERIC} (mp_search_ww_generic) or {FORM_MULTI} (multi_trajectory_planner)")
+    return table(wh, 5, "wh"), table(wc, 4, "wc"), f
+
+
 def plan_routes(queries: Sequence[RouteQuery], L: float = 2.86, wh=WH_DEFAULT, wc=WC_DEFAULT, max_path: int = 32,
-                device: int = 0, primitives=None, node_cap: int = 1 << 17, retry_node_cap: int = 1 << 21, circles=None) -> List[PlannedRoute]:
-    """All queries in ONE launch (one wavefront per route).  Routes whose search outgrows `node_cap` nodes (status 4) are planned
-    again, together, with `retry_node_cap` (0: no second attempt).  primitives = (points [P, n, 3], total_length [P]) and
-    circles = (radius, centres [k, 2]) replace the regenerated bicycle-model set / BicycleModelDimensions' circles."""
-    out = _plan(queries, L, wh, wc, max_path, device, primitives, node_cap, circles)
+                device: int = 0, primitives=None, node_cap: int = 1 << 17, retry_node_cap: int = 1 << 21, circles=None,
+                form=FORM_GENERIC) -> List[PlannedRoute]:
+    """All queries in ONE launch (one wavefront per route).  wh (5,), wc (4,) and form hold for every route; given as (R, 5),
+    (R, 4) and (R,) they are per route -- a weight sweep is the same query R times with one row each.  form 0: the cost terms of
+    mp_search_ww_generic.py, 1: those of multi_trajectory_planner.py (wh[:3] = e, p, o).  Routes whose search outgrows `node_cap`
+    nodes (status 4) are planned again, together, each with its own rows, with `retry_node_cap` (0: no second attempt).
+    primitives = (points [P, n, 3], total_length [P]) and circles = (radius, centres [k, 2]) replace the regenerated
+    bicycle-model set / BicycleModelDimensions' circles."""
+    wh, wc, form = weight_tables(len(queries), wh, wc, form)
+    out = _plan(queries, L, wh, wc, form, max_path, device, primitives, node_cap, circles)
     again = [i for i, r in enumerate(out) if r.status == 4]
     if again and retry_node_cap > node_cap:
-        for i, r in zip(again, _plan([queries[i] for i in again], L, wh, wc, max_path, device, primitives, retry_node_cap, circles)):
+        for i, r in zip(again, _plan([queries[i] for i in again], L, wh[again], wc[again], form[again], max_path, device, primitives,
+                                     retry_node_cap, circles)):
             out[i] = r
     return out
 
@@ -176,7 +207,7 @@ class MotionPrimitiveSearch:
     .to_convex(margin) gives half-planes), car dimensions (.radius, .circle_centers), the motion primitives the CALLER holds (a
     dict name -> object with .points (n, 3) and .total_length; iteration order = expansion order, as in the reference) and the
     nine weights -- and run() -> (cost, path, trajectory) with path a list of (x, y, theta) tuples.  The search itself is
-    jsim_plan_routes on the GPU (one route = one wavefront; use plan_routes for many routes at once).  Like the reference,
+    plan_astar_kernel on the GPU (one route = one wavefront; use plan_routes for many routes at once).  Like the reference,
     run() raises Exception("No solution found.") when the open list runs empty (main/lib/a_star.py:78); debug=True (the
     reference's matplotlib trace of the expansion) is not offered."""
 
@@ -187,22 +218,8 @@ class MotionPrimitiveSearch:
         # max_path: longest path in primitives the output arrays hold (status 6 beyond); node_cap / retry_node_cap: node table of
         # the first / second attempt (status 4 beyond) -- the reference's dict and heap grow without bound, these do not
         self.max_path, self.node_cap, self.retry_node_cap = int(max_path), int(node_cap), int(retry_node_cap)
-        self._names = list(mps.keys())
-        pts = [np.asarray(mps[n].points, dtype=np.float64) for n in self._names]
-        if not pts or any(p.shape != pts[0].shape or p.ndim != 2 or p.shape[1] != 3 for p in pts):
-            raise ValueError("motion primitives must be (n, 3) arrays of one common length")
-        self._primitives = (np.stack(pts), np.array([float(mps[n].total_length) for n in self._names]))
-        self._circles = (float(car_dimensions.radius), np.asarray(car_dimensions.circle_centers, dtype=np.float64).reshape(-1, 2))
-        ga = scenario.goal_area
-        if not (hasattr(ga, "xy1") and hasattr(ga, "xy2")):
-            # the reference accepts any Obstacle with distance_to_point as goal area (main/lib/mp_search_ww_generic.py:101-103); every
-            # scenario builder it ships uses a BoxObstacle, and the kernel's goal test is the box test
-            raise ValueError(f"goal_area must be a box (.xy1 / .xy2), got {type(ga).__name__}: the GPU planner's goal test is the "
-                             "reference's BoxObstacle.distance_to_point(...) <= 0")
-        (x1, y1), (x2, y2) = ga.xy1, ga.xy2
-        self._query = RouteQuery(start=tuple(float(v) for v in scenario.start), goal=tuple(float(v) for v in scenario.goal_point),
-                                 goal_box=(float(x1), float(y1), float(x2), float(y2)), tol=float(scenario.allowed_goal_theta_difference),
-                                 obstacles=[np.asarray(o.to_convex(margin=margin), dtype=np.float64) for o in scenario.obstacles])
+        self._names, self._primitives, self._circles = _scenario_primitives(mps, car_dimensions)
+        self._query = _scenario_query(scenario, margin)
         self._wh = (wh_dist, wh_theta, wh_steering, wh_obstacle, wh_center)
         self._wc = (wc_dist, wc_steering, wc_obstacle, wc_center)
         self._device = device
@@ -215,18 +232,106 @@ class MotionPrimitiveSearch:
         r = plan_routes([self._query], wh=self._wh, wc=self._wc, primitives=self._primitives, circles=self._circles, device=self._device,
                         max_path=self.max_path, node_cap=self.node_cap, retry_node_cap=self.retry_node_cap)[0]
         self.last = r
-        if r.status == 1:
-            raise Exception("No solution found.")                    # main/lib/a_star.py:78
-        if r.status != 0:
-            raise RuntimeError(f"route planner: status {r.status} (4: node table full -- raise node_cap / retry_node_cap; 5 / 6: path "
-                               f"longer than max_path = {self.max_path} primitives)")
+        _raise_unless_found(r, self.max_path)
         path = [tuple(float(v) for v in n) for n in r.nodes]
         for a, b, k in zip(path[:-1], path[1:], r.prims):
             self._points_to_mp_names[a, b] = self._names[int(k)]
         return r.cost, path, r.trajectory
 
 
-def _plan(queries, L, wh, wc, max_path, device, primitives, node_cap, circles=None) -> List[PlannedRoute]:
+def _scenario_query(scenario, margin: float) -> RouteQuery:
+    ga = scenario.goal_area
+    if not (hasattr(ga, "xy1") and hasattr(ga, "xy2")):
+        # the reference accepts any Obstacle with distance_to_point as goal area (main/lib/mp_search_ww_generic.py:101-103); every
+        # scenario builder it ships uses a BoxObstacle, and the kernel's goal test is the box test
+        raise ValueError(f"goal_area must be a box (.xy1 / .xy2), got {type(ga).__name__}: the GPU planner's goal test is the "
+                         "reference's BoxObstacle.distance_to_point(...) <= 0")
+    (x1, y1), (x2, y2) = ga.xy1, ga.xy2
+    return RouteQuery(start=tuple(float(v) for v in scenario.start), goal=tuple(float(v) for v in scenario.goal_point),
+                      goal_box=(float(x1), float(y1), float(x2), float(y2)), tol=float(scenario.allowed_goal_theta_difference),
+                      obstacles=[np.asarray(o.to_convex(margin=margin), dtype=np.float64) for o in scenario.obstacles])
+
+
+def _scenario_primitives(mps, car_dimensions):
+    names = list(mps.keys())
+    pts = [np.asarray(mps[n].points, dtype=np.float64) for n in names]
+    if not pts or any(p.shape != pts[0].shape or p.ndim != 2 or p.shape[1] != 3 for p in pts):
+        raise ValueError("motion primitives must be (n, 3) arrays of one common length")
+    return (names, (np.stack(pts), np.array([float(mps[n].total_length) for n in names])),
+            (float(car_dimensions.radius), np.asarray(car_dimensions.circle_centers, dtype=np.float64).reshape(-1, 2)))
+
+
+def _raise_unless_found(r: PlannedRoute, max_path: int) -> None:
+    if r.status == 1:
+        raise Exception("No solution found.")                        # main/lib/a_star.py:78
+    if r.status != 0:
+        raise RuntimeError(f"route planner: status {r.status} (4: node table full -- raise node_cap / retry_node_cap; 5 / 6: path "
+                           f"longer than max_path = {max_path} primitives)")
+
+
+class MultiTrajectorySearch:
+    """Drop-in for the reference's multi-trajectory planner class (main/planner/multi_trajectory_planner.py:44-269, the class
+    main/scenarios/overtaking_cyclist_bidirectional_road.py:337 calls run_all of): the same constructor -- scenario, car
+    dimensions, the caller's motion primitives, margin, the heuristic's weights as three LISTS wh_ego / wh_policy / wh_other and
+    the four edge-cost weights -- with
+      run()      one search with the sums of the lists (:94-96, :228-240) -> (cost, path, trajectory);
+      run_all()  one search per (e, p, o), e over wh_ego, p over wh_policy, o over wh_other in that nesting (:253-267) ->
+                 [(cost, path, trajectory, e, p, o), ...] -- ALL of them in ONE launch of jsim_plan_routes_weighted (form 1: one
+                 wavefront per combination).  An empty list gives [] and the reference's message (:249-251).
+    Like the reference's loop, run_all() raises Exception("No solution found.") at the first combination, in its order, whose
+    open list runs empty.  debug=True (the expansion trace) is not offered."""
+
+    def __init__(self, scenario, car_dimensions, mps, margin: float, wh_ego=None, wh_policy=None, wh_other=None,
+                 wc_dist: float = 1.0, wc_steering: float = 5.0, wc_obstacle: float = 0.1, wc_center: float = 0.0, device: int = 0,
+                 max_path: int = 32, node_cap: int = 1 << 17, retry_node_cap: int = 1 << 21):
+        self.max_path, self.node_cap, self.retry_node_cap = int(max_path), int(node_cap), int(retry_node_cap)
+        self._names, self._primitives, self._circles = _scenario_primitives(mps, car_dimensions)
+        self._query = _scenario_query(scenario, margin)
+        self._wh_ego = wh_ego if wh_ego is not None else []
+        self._wh_policy = wh_policy if wh_policy is not None else []
+        self._wh_other = wh_other if wh_other is not None else []
+        self._sum_ego, self._sum_policy, self._sum_other = sum(self._wh_ego), sum(self._wh_policy), sum(self._wh_other)
+        self._wc = (wc_dist, wc_steering, wc_obstacle, wc_center)
+        self._device = device
+        self._points_to_mp_names = {}
+        self.last = None       # the PlannedRoutes of the last run / run_all
+
+    def combinations(self):
+        """[(e, p, o), ...] in the reference's loop order (:253-255)."""
+        return [(e, p, o) for e in self._wh_ego for p in self._wh_policy for o in self._wh_other]
+
+    def _search(self, combos):
+        wh = np.array([[e, p, o, 0.0, 0.0] for e, p, o in combos], dtype=np.float64).reshape(len(combos), 5)
+        routes = plan_routes([self._query] * len(combos), wh=wh, wc=self._wc, form=FORM_MULTI, primitives=self._primitives,
+                             circles=self._circles, device=self._device, max_path=self.max_path, node_cap=self.node_cap,
+                             retry_node_cap=self.retry_node_cap)
+        self.last = routes
+        out = []
+        for r in routes:
+            _raise_unless_found(r, self.max_path)
+            path = [tuple(float(v) for v in n) for n in r.nodes]
+            for a, b, k in zip(path[:-1], path[1:], r.prims):
+                self._points_to_mp_names[a, b] = self._names[int(k)]
+            out.append((r.cost, path, r.trajectory))
+        return out
+
+    def run(self, debug: bool = False):
+        if debug:
+            raise NotImplementedError("debug=True (the reference's expansion trace) is not offered by the GPU planner")
+        return self._search([(self._sum_ego, self._sum_policy, self._sum_other)])[0]
+
+    def run_all(self, debug: bool = False):
+        if debug:
+            raise NotImplementedError("debug=True (the reference's expansion trace) is not offered by the GPU planner")
+        if not self._wh_ego or not self._wh_policy or not self._wh_other:
+            print("One or more weight lists are empty; no solutions returned.")
+            return []
+        combos = self.combinations()
+        return [(c, path, traj, e, p, o) for (c, path, traj), (e, p, o) in zip(self._search(combos), combos)]
+
+
+def _plan(queries, L, wh, wc, form, max_path, device, primitives, node_cap, circles=None, launch_wide: bool = False) -> List[PlannedRoute]:
+    """One launch.  launch_wide: through jsim_plan_routes with row 0 for every route (tools/bench_planner_sweep.py times it)."""
     lib = _cabi.load()
     pts, length = primitives if primitives is not None else make_motion_primitives(L=L)
     radius, centres = circles if circles is not None else car_circles(L=L)
@@ -249,15 +354,23 @@ def _plan(queries, L, wh, wc, max_path, device, primitives, node_cap, circles=No
     tol = np.ascontiguousarray([q.tol for q in queries], dtype=np.float64)
     mp = np.ascontiguousarray(pts, dtype=np.float64); ml = np.ascontiguousarray(length, dtype=np.float64)
     whv = np.ascontiguousarray(wh, dtype=np.float64); wcv = np.ascontiguousarray(wc, dtype=np.float64)
+    formv = np.ascontiguousarray(form, dtype=np.int32)
+    assert whv.shape == (R, 5) and wcv.shape == (R, 4) and formv.shape == (R,)
     n_prim, n_pts = mp.shape[0], mp.shape[1]
     seg = n_pts - 1
     status = np.zeros(R, dtype=np.int32); cost = np.zeros(R); n_prims = np.zeros(R, dtype=np.int32)
     prims = np.zeros((R, max_path), dtype=np.int32); nodes = np.zeros((R, max_path + 1, 3)); traj = np.zeros((R, max_path * seg, 3))
     n_exp = np.zeros(R, dtype=np.int32)
     p = lambda a: C.c_void_p(a.ctypes.data)
-    _cabi.check(lib.jsim_plan_routes(int(device), R, p(start), p(goal), p(box), p(tol), p(hp), p(hp_off), len(hp_off) - 1, p(r_off), p(mp),
-                                     p(ml), n_prim, n_pts, p(cc_flat), p(cc_off), p(whv), p(wcv), int(max_path), int(node_cap), p(status), p(cost),
-                                     p(n_prims), p(prims), p(nodes), p(traj), p(n_exp)), None, "jsim_plan_routes")
+    if launch_wide:
+        _cabi.check(lib.jsim_plan_routes(int(device), R, p(start), p(goal), p(box), p(tol), p(hp), p(hp_off), len(hp_off) - 1, p(r_off), p(mp),
+                                         p(ml), n_prim, n_pts, p(cc_flat), p(cc_off), p(whv), p(wcv), int(max_path), int(node_cap), p(status),
+                                         p(cost), p(n_prims), p(prims), p(nodes), p(traj), p(n_exp)), None, "jsim_plan_routes")
+    else:
+        _cabi.check(lib.jsim_plan_routes_weighted(int(device), R, p(start), p(goal), p(box), p(tol), p(hp), p(hp_off), len(hp_off) - 1, p(r_off),
+                                                  p(mp), p(ml), n_prim, n_pts, p(cc_flat), p(cc_off), p(whv), p(wcv), p(formv), int(max_path),
+                                                  int(node_cap), p(status), p(cost), p(n_prims), p(prims), p(nodes), p(traj), p(n_exp)),
+                    None, "jsim_plan_routes_weighted")
     out = []
     for i in range(R):
         k = int(n_prims[i])

@@ -326,6 +326,24 @@ int jsim_plan_routes(int device_id, int32_t n_routes, const double *start, const
                      int32_t node_cap, int32_t *status, double *cost, int32_t *n_prims, int32_t *prims, double *nodes, double *traj,
                      int32_t *n_expanded);
 
+/* The same search with the weights PER ROUTE: wh [R][5], wc [R][4] and form [R] in place of the launch-wide wh [5], wc [4]; every other
+ * argument as in jsim_plan_routes, which is this call with its one row repeated and form 0.  Replaces one planner run per weight
+ * set -- main/planner/Planner_Sensitivity_TrueCost.py / Planner_Sensitivity_Heuristic.py (a MotionPrimitiveSearch per set) and
+ * main/planner/multi_trajectory_planner.py:242-269 run_all (one A* per (e, p, o) of wh_ego x wh_policy x wh_other; call site
+ * main/scenarios/overtaking_cyclist_bidirectional_road.py:337) -- by one launch: the same query repeated with one row each.
+ *   form [R]: 0 = the cost terms of main/lib/mp_search_ww_generic.py (:166-190 heuristic, :202-243 edge cost);
+ *             1 = those of main/planner/multi_trajectory_planner.py: heuristic :185-201 = wh[0] hypot(x - gx, y - gy) +
+ *                 wh[1] |((theta - gtheta) + pi) mod 2 pi - pi| + wh[2] steering_change(node, goal) (wh[3], wh[4] are not read); the
+ *                 edge's obstacle term :137-141 is guarded by wc[2] != 0 (the generic file guards it by wh[3] != 0, :230) and is
+ *                 1 / d for d > 0, inf otherwise.
+ *   -22 before any device call for a null table, a form outside {0, 1} or a weight that is not finite. */
+int jsim_plan_routes_weighted(int device_id, int32_t n_routes, const double *start, const double *goal, const double *goal_box,
+                              const double *tol, const double *hp, const int32_t *hp_off, int32_t n_obs_total,
+                              const int32_t *route_obs_off, const double *mp_pts, const double *mp_len, int32_t n_prim, int32_t n_pts,
+                              const double *cc_pts, const int32_t *cc_off, const double *wh, const double *wc, const int32_t *form,
+                              int32_t max_path, int32_t node_cap, int32_t *status, double *cost, int32_t *n_prims, int32_t *prims,
+                              double *nodes, double *traj, int32_t *n_expanded);
+
 /* ---- the job's one exchange: the final trajectory gather over RCCL / xGMI ----
  * The reference has no multi-process code at all (its only multi-ego code is the serial Python loop of
  * main/scenarios/interactive_mpc.py:119-172); egos are independent (main/lib/mpc.py:141-211), so ranks own contiguous shards
