@@ -2009,6 +2009,7 @@ static int plan_routes_tables(const char *who, int device_id, int32_t n_routes, 
     // a circle around every obstacle (the kernel's exact pruning of the collision test): vertices = the pairwise intersections of its
     // half-plane boundaries that satisfy all the others; bounded iff the largest angular gap between consecutive normals is below pi
     std::vector<double> obc((size_t)(n_obs_total > 0 ? n_obs_total : 1) * 3, 0.0);
+    std::vector<double> vx, vy;                                       // (at most 64 * 63 / 2 vertices per obstacle)
     for (int o = 0; o < n_obs_total; ++o) {
         const double *q = hp + (size_t)hp_off[o] * 3;
         const int n = hp_off[o + 1] - hp_off[o];
@@ -2021,10 +2022,12 @@ static int plan_routes_tables(const char *who, int device_id, int32_t n_routes, 
         double gap = ang[0] + 2.0 * M_PI - ang[n - 1];
         for (int i = 1; i < n; ++i) gap = std::max(gap, ang[i] - ang[i - 1]);
         if (!(gap < M_PI - 1e-9)) continue;                       // unbounded (or degenerate): no circle, never pruned
-        double sx = 0.0, sy = 0.0, vx[64 * 2], vy[64 * 2];
-        int nv = 0;
-        for (int i = 0; i < n && nv < 128; ++i)
-            for (int j = i + 1; j < n && nv < 128; ++j) {
+        // EVERY such vertex counts: rows listed more than once give the same vertex many times over (a 16-gon with each row four
+        // times: 16 x 16 of them), and a circle around only the first few of the list does not contain the obstacle
+        double sx = 0.0, sy = 0.0;
+        vx.clear(); vy.clear();
+        for (int i = 0; i < n; ++i)
+            for (int j = i + 1; j < n; ++j) {
                 const double a1 = q[3 * i], b1 = q[3 * i + 1], c1 = q[3 * i + 2], a2 = q[3 * j], b2 = q[3 * j + 1], c2 = q[3 * j + 2];
                 const double det = a1 * b2 - a2 * b1;
                 if (fabs(det) <= 1e-12 * (fabs(a1) + fabs(b1)) * (fabs(a2) + fabs(b2))) continue;
@@ -2034,9 +2037,10 @@ static int plan_routes_tables(const char *who, int device_id, int32_t n_routes, 
                     const double v = q[3 * k] * px + q[3 * k + 1] * py + q[3 * k + 2];
                     in = v <= 1e-9 * (1.0 + fabs(q[3 * k + 2]) + (fabs(q[3 * k]) + fabs(q[3 * k + 1])) * (fabs(px) + fabs(py)));
                 }
-                if (in) { vx[nv] = px; vy[nv] = py; sx += px; sy += py; ++nv; }
+                if (in) { vx.push_back(px); vy.push_back(py); sx += px; sy += py; }
             }
-        if (nv < 3) continue;                                     // (an empty or degenerate set: left to the exact test)
+        const int nv = (int)vx.size();
+        if (nv < 3) continue;                                    // (an empty or degenerate set: left to the exact test)
         const double mx = sx / nv, my = sy / nv;
         double rr = 0.0;
         for (int i = 0; i < nv; ++i) rr = std::max(rr, hypot(vx[i] - mx, vy[i] - my));

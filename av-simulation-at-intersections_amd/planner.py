@@ -24,6 +24,8 @@ MP_STEER = (0.0, 0.1, 0.2, 0.3, 0.4, -0.1, -0.2, -0.3, -0.4)     # main/create_m
 WH_DEFAULT = (1.0, 2.7, 15.0, 0.0, 0.0)                            # mp_search_ww_generic.py:29-31
 WC_DEFAULT = (1.0, 5.0, 0.1, 0.0)                                  # :33
 FORM_GENERIC, FORM_MULTI = 0, 1    # cost terms of main/lib/mp_search_ww_generic.py / main/planner/multi_trajectory_planner.py
+# the kernel's tables (csrc/planner.inc JPL_MAX_OBS, JPL_MAX_HP, JPL_MAX_PRIM, JPL_MAX_CC): a route beyond them ends with status 5
+MAX_OBSTACLES, MAX_HALFPLANES, MAX_PRIMITIVES, MAX_COLLISION_POINTS = 64, 512, 16, 16
 
 
 def make_motion_primitives(L: float = 2.86, v: float = 8.3, n_steps: int = 60, dt: float = 0.01):
@@ -264,8 +266,14 @@ def _scenario_primitives(mps, car_dimensions):
 def _raise_unless_found(r: PlannedRoute, max_path: int) -> None:
     if r.status == 1:
         raise Exception("No solution found.")                        # main/lib/a_star.py:78
+    if r.status == 5:
+        raise RuntimeError(f"route planner: status 5 -- the obstacle / primitive set is larger than the kernel's tables: at most "
+                           f"{MAX_OBSTACLES} obstacles and {MAX_HALFPLANES} half-planes per route, {MAX_PRIMITIVES} primitives, "
+                           f"{MAX_COLLISION_POINTS} collision points per primitive (for every car circle, one per circle radius of the "
+                           "primitive's length and two more: a small vehicle's circles on a 5 m primitive exceed it).  max_path "
+                           "has no part in it")
     if r.status != 0:
-        raise RuntimeError(f"route planner: status {r.status} (4: node table full -- raise node_cap / retry_node_cap; 5 / 6: path "
+        raise RuntimeError(f"route planner: status {r.status} (4: node table full -- raise node_cap / retry_node_cap; 6: path "
                            f"longer than max_path = {max_path} primitives)")
 
 
