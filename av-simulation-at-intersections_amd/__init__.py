@@ -20,3 +20,4 @@ from . import mpc_sensitivity  # noqa: F401
 from . import mpc_jerk  # noqa: F401
 from . import planner  # noqa: F401
 from . import workloads  # noqa: F401
+from . import reasons  # noqa: F401

@@ -38,7 +38,7 @@ EXPORTS = (
     "jsim_loop_set_groups", "jsim_loop_predict_egos", "jsim_loop_run_interacting",
     "jsim_loop_set_traffic", "jsim_loop_set_recorder", "jsim_loop_set_vehicle_shapes",
     "jsim_comm_unique_id", "jsim_comm_init", "jsim_mpc_gather", "jsim_comm_destroy", "jsim_plan_routes",
-    "jsim_plan_routes_weighted",
+    "jsim_plan_routes_weighted", "jsim_score_trajectories",
 )
 
 _lib = None
@@ -136,6 +136,12 @@ def load() -> C.CDLL:
     lib.jsim_plan_routes_weighted.restype = C.c_int
     #                                        ... as above ...                                                wh  wc form max_path cap  outs
     lib.jsim_plan_routes_weighted.argtypes = [i32, i32, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, i32, i32] + [vp] * 7
+    lib.jsim_score_trajectories.restype = C.c_int
+    #                                      dev  S    cand_off pt_off pts mode time_from ego cyc now par  W    w   form ideal  outs
+    lib.jsim_score_trajectories.argtypes = [i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp] + [vp] * 8
+    lib.jsim_score_trajectories.restype = C.c_int
+    #                                      dev  S    cand_off pt_off pts mode time_from ego cyc now par  W    w   form ideal  outs
+    lib.jsim_score_trajectories.argtypes = [i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp] + [vp] * 8
     if lib.jsim_abi_version() != ABI_VERSION:
         raise JsimError(f"libjsim_mpc.so ABI {lib.jsim_abi_version()} != binding ABI {ABI_VERSION}")
     _lib = lib

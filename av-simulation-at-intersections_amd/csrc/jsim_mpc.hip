@@ -2154,6 +2154,112 @@ extern "C" int jsim_plan_routes_weighted(int device_id, int32_t n_routes, const 
                               nodes, traj, n_expanded);
 }
 
+#include "reasons.inc"
+
+// Stakeholder reasons: HOST pointers in and out -- a replan is an event, not a tick; device buffers are
+// allocated, filled, scored (one workgroup per situation, one wavefront per candidate) and read back inside the call.
+extern "C" int jsim_score_trajectories(int device_id, int32_t n_sit, const int32_t *cand_off, const int32_t *pt_off, const double *pts,
+                                       const int32_t *mode, const int32_t *time_from, const double *ego, const double *cyc, const double *now,
+                                       const double *par, int32_t n_w, const double *w, const int32_t *form, const double *ideal,
+                                       int32_t *status, int32_t *n_samples, double *ct, double *avg, double *scores, int32_t *best,
+                                       double *detail, double *resampled)
+{
+    const char *who = "jsim_score_trajectories";
+    if (n_sit < 0 || n_w < 0 || n_sit > (1 << 20) || n_w > (1 << 24)) return fail(nullptr, -22, "%s: bad sizes (situations %d, weight rows %d)", who, n_sit, n_w);
+    if (n_sit == 0) return 0;
+    if (!cand_off || !pt_off || !mode || !time_from || !ego || !cyc || !now || !par || !ideal || !status || !n_samples || !ct || !avg ||
+        (n_w > 0 && (!w || !form || !scores || !best)))
+        return fail(nullptr, -22, "%s: null argument", who);
+    if (cand_off[0] != 0) return fail(nullptr, -22, "%s: cand_off[0] = %d", who, cand_off[0]);
+    for (int s = 0; s < n_sit; ++s) {
+        if (cand_off[s + 1] < cand_off[s]) return fail(nullptr, -22, "%s: cand_off decreases at %d", who, s);
+        if (cand_off[s + 1] - cand_off[s] > JSIM_MAX_CAND)
+            return fail(nullptr, -22, "%s: situation %d has %d candidates (at most %d)", who, s, cand_off[s + 1] - cand_off[s], (int)JSIM_MAX_CAND);
+    }
+    const int ctot = cand_off[n_sit];
+    if (pt_off[0] != 0) return fail(nullptr, -22, "%s: pt_off[0] = %d", who, pt_off[0]);
+    for (int c = 0; c < ctot; ++c)
+        if (pt_off[c + 1] < pt_off[c]) return fail(nullptr, -22, "%s: pt_off decreases at %d", who, c);
+    const size_t n_pts = ctot > 0 ? (size_t)pt_off[ctot] : 0;
+    if (n_pts > 0 && !pts) return fail(nullptr, -22, "%s: null argument", who);
+    for (int s = 0; s < n_sit; ++s) {
+        const int c0 = cand_off[s], C = cand_off[s + 1] - c0;
+        for (int c = 0; c < C; ++c) {
+            if (mode[c0 + c] != 0 && mode[c0 + c] != 1) return fail(nullptr, -22, "%s: mode[%d] = %d (0: planned, 1: following)", who, c0 + c, mode[c0 + c]);
+            const int d = time_from[c0 + c];
+            if (d < 0 || d >= C) return fail(nullptr, -22, "%s: time_from[%d] = %d outside its situation of %d", who, c0 + c, d, C);
+            if (time_from[c0 + d] != d) return fail(nullptr, -22, "%s: time_from[%d] = %d names a candidate that names another", who, c0 + c, d);
+        }
+    }
+    auto finite = [](const double *a, size_t n) { for (size_t k = 0; k < n; ++k) if (!std::isfinite(a[k])) return false; return true; };
+    if (!finite(pts, 3 * n_pts) || !finite(ego, 4 * (size_t)n_sit) || !finite(cyc, 6 * (size_t)n_sit) || !finite(now, 5 * (size_t)n_sit) ||
+        !finite(par, JSIM_REASON_NPAR * (size_t)n_sit) || !finite(w, 3 * (size_t)n_w) || !finite(ideal, 3))
+        return fail(nullptr, -22, "%s: a number that is not finite", who);
+    for (int s = 0; s < n_sit; ++s)
+        if (!(par[JSIM_REASON_NPAR * (size_t)s + JSIM_REASON_DT] > 0.0)) return fail(nullptr, -22, "%s: situation %d: DT <= 0", who, s);
+    for (int k = 0; k < n_w; ++k)
+        if (form[k] != 0 && form[k] != 1) return fail(nullptr, -22, "%s: form[%d] = %d (0: for_reasons, 1: with_weights)", who, k, form[k]);
+    int ndev = 0;
+    HIP_TRY(nullptr, hipGetDeviceCount(&ndev));
+    if (device_id < 0 || device_id >= ndev) return fail(nullptr, -19, "%s: device %d of %d", who, device_id, ndev);
+    DeviceGuard dev_guard(device_id);
+    JSIM_GUARD_OK(nullptr);
+    const size_t S = (size_t)n_sit, W = (size_t)n_w, Ct = (size_t)ctot;
+    if (W * (Ct + S) * 8ull > (16ull << 30)) return fail(nullptr, -12, "%s: %d weight rows x %d candidates would need more than 16 GiB", who, n_w, ctot);
+    std::vector<void *> owned;
+    auto dalloc = [&](size_t bytes) -> void * { void *q = nullptr; if (hipMalloc(&q, bytes ? bytes : 8) != hipSuccess) return nullptr; owned.push_back(q); return q; };
+    auto put = [&](const void *src, size_t bytes) -> void * {
+        void *q = dalloc(bytes);
+        if (q && bytes && hipMemcpy(q, src, bytes, hipMemcpyHostToDevice) != hipSuccess) return nullptr;
+        return q;
+    };
+    auto cleanup = [&]() { for (void *q : owned) (void)hipFree(q); };
+    ReasonP P;
+    memset(&P, 0, sizeof(P));
+    P.n_sit = n_sit; P.n_w = n_w; P.ctot = ctot;
+    P.ideal[0] = ideal[0]; P.ideal[1] = ideal[1]; P.ideal[2] = ideal[2];
+    P.cand_off = (const int *)put(cand_off, sizeof(int) * (S + 1)); P.pt_off = (const int *)put(pt_off, sizeof(int) * (Ct + 1));
+    P.pts = (const double *)put(pts, sizeof(double) * 3 * n_pts);
+    P.mode = (const int *)put(mode, sizeof(int) * Ct); P.time_from = (const int *)put(time_from, sizeof(int) * Ct);
+    P.ego = (const double *)put(ego, sizeof(double) * 4 * S); P.cyc = (const double *)put(cyc, sizeof(double) * 6 * S);
+    P.now = (const double *)put(now, sizeof(double) * 5 * S); P.par = (const double *)put(par, sizeof(double) * JSIM_REASON_NPAR * S);
+    P.w = (const double *)put(w, sizeof(double) * 3 * W); P.form = (const int *)put(form, sizeof(int) * W);
+    P.status = (int *)dalloc(sizeof(int) * Ct); P.n_samples = (int *)dalloc(sizeof(int) * Ct);
+    P.ct = (double *)dalloc(sizeof(double) * Ct); P.avg = (double *)dalloc(sizeof(double) * 4 * Ct);
+    P.scores = (double *)dalloc(sizeof(double) * W * Ct); P.best = (int *)dalloc(sizeof(int) * W * S);
+    const size_t n_detail = Ct * 5 * JSIM_MAX_RES, n_res = Ct * JSIM_MAX_RES * 3;
+    if (detail) P.detail = (double *)dalloc(sizeof(double) * n_detail);
+    if (resampled) P.resampled = (double *)dalloc(sizeof(double) * n_res);
+    if (!P.cand_off || !P.pt_off || !P.pts || !P.mode || !P.time_from || !P.ego || !P.cyc || !P.now || !P.par || !P.w || !P.form || !P.status ||
+        !P.n_samples || !P.ct || !P.avg || !P.scores || !P.best || (detail && !P.detail) || (resampled && !P.resampled)) {
+        cleanup();
+        return fail(nullptr, -12, "%s: device allocation / upload failed", who);
+    }
+    // every real output starts as NaN (all bits set): what the kernel does not write -- a candidate with a status, the rows behind a
+    // candidate's samples -- stays NaN
+    hipError_t e = hipMemset(P.ct, 0xff, sizeof(double) * Ct);
+    if (e == hipSuccess) e = hipMemset(P.avg, 0xff, sizeof(double) * 4 * Ct);
+    if (e == hipSuccess) e = hipMemset(P.scores, 0xff, sizeof(double) * W * Ct);
+    if (e == hipSuccess && P.detail) e = hipMemset(P.detail, 0xff, sizeof(double) * n_detail);
+    if (e == hipSuccess && P.resampled) e = hipMemset(P.resampled, 0xff, sizeof(double) * n_res);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(score_trajectories_kernel, dim3(n_sit), dim3(64 * JSIM_MAX_CAND), 0, 0, P);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpy(status, P.status, sizeof(int) * Ct, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(n_samples, P.n_samples, sizeof(int) * Ct, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(ct, P.ct, sizeof(double) * Ct, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(avg, P.avg, sizeof(double) * 4 * Ct, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && W) e = hipMemcpy(scores, P.scores, sizeof(double) * W * Ct, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && W) e = hipMemcpy(best, P.best, sizeof(int) * W * S, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && detail) e = hipMemcpy(detail, P.detail, sizeof(double) * n_detail, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && resampled) e = hipMemcpy(resampled, P.resampled, sizeof(double) * n_res, hipMemcpyDeviceToHost);
+    cleanup();
+    if (e != hipSuccess) return fail(nullptr, -5, "%s: %s", who, hipGetErrorString(e));
+    return 0;
+}
+
 // the shape table's (thr, thr_sq) rows: check_collision_moving_bicycle's min_distance = the egos' radius + the vehicle's own
 static int upload_shape_thresholds(jsim_ctx *ctx)
 {

@@ -344,6 +344,45 @@ int jsim_plan_routes_weighted(int device_id, int32_t n_routes, const double *sta
                               int32_t max_path, int32_t node_cap, int32_t *status, double *cost, int32_t *n_prims, int32_t *prims,
                               double *nodes, double *traj, int32_t *n_expanded);
 
+/* ---- stakeholder reasons: score the planner's candidate trajectories and pick one, every weight row in one launch ----
+ * Replaces what perform_replan does with the candidates of run_all (main/scenarios/overtaking_cyclist_bidirectional_road.py:290-407):
+ * evaluate_trajectories_for_reasons (:1233-1428, weight row form 0), evaluate_trajectories_with_weights (:1641-1864, form 1) and the
+ * loop of generate_stakeholder_weight_table (:1431-1604: the whole evaluation repeated once per weight triple), with
+ * compute_predicted_trajectory (:244-266), calculate_trajectory_completion_time (:1867-1905), lib/trajectories.py:58-86 resample_curve,
+ * lib/moving_obstacles_prediction.py:21-47 and lib/reasons_evaluation.py inside.  One workgroup per situation, one wavefront per
+ * candidate; the per-sample work is done once and only the weighted sum, the balance factor and the arg-max per weight row.
+ * HOST pointers in and out (a replan is an event, not a tick).
+ *   cand_off [n_sit + 1]: situation s owns candidates cand_off[s] .. cand_off[s + 1] - 1 (at most JSIM_MAX_CAND); Ctot = cand_off[n_sit].
+ *   pt_off [Ctot + 1], pts [.][3]: each candidate's raw (x, y, yaw) points.  mode [Ctot]: 0 = a planned candidate (resampled by the
+ *   speed the ego can reach), 1 = the following candidate (last_index=True: resampled by DT v).  time_from [Ctot]: the candidate of
+ *   the same situation, by index within it, whose completion time this one is scored with -- itself, or one that names itself (the
+ *   reference's appended following candidate reuses the time of the candidate before it, :1257-1263).
+ *   ego [n_sit][4] = x, y, yaw, v; cyc [n_sit][6] = the cyclist's get() tuple x, y, v, yaw, a, steering; now [n_sit][5] = the current
+ *   policymaker, driver and cyclist values, then time_elapsed_driver and time_passed_cyclist; par [n_sit][JSIM_REASON_NPAR] in the
+ *   order of the enum below.  w [n_w][3] = (policymaker, driver, cyclist) weights per row, form [n_w]: 0 = avg_policymaker over the
+ *   first m - 2 samples and no clamp (:1354), 1 = over m - 1 and clamped to [0, 1] (:1785, :1815).  ideal [3] = (cyclist, driver,
+ *   policymaker) ideal weights of balance_function (:1191-1231).
+ *   Out: status [Ctot] (0; 2 = the reference has no defined behaviour: fewer than 2 raw points, fewer than 3 resampled ones, a
+ *   completion time of fewer than 2 steps of DT or not finite, a resampling step that is not positive; 4 = more than JSIM_MAX_RES
+ *   resampled points, or a prediction of more than 65536 steps), n_samples [Ctot], ct [Ctot] (the completion time used),
+ *   avg [Ctot][4] = policymaker over m - 2, policymaker over m - 1, driver, cyclist; scores [n_w][Ctot]; best [n_w][n_sit] = first
+ *   arg-max by index within the situation (-1: no candidate with status 0).  A candidate with a status has NaN in ct, avg and
+ *   scores and never wins.  Optional (NULL: not wanted): detail [Ctot][5][JSIM_MAX_RES] = the policymaker, driver, cyclist_comfort,
+ *   cyclist_time and cyclist_combined arrays of detailed_scores (m - 1, m - 1, m, m, m - 1 entries, NaN behind them),
+ *   resampled [Ctot][JSIM_MAX_RES][3] (n_samples rows, NaN behind them).
+ *   -22 before any device call: a null required table, offsets that do not start at 0 or decrease, more than JSIM_MAX_CAND
+ *   candidates in a situation, a time_from outside its situation or naming a candidate that names another, a mode or form outside
+ *   {0, 1}, a number that is not finite, DT <= 0. */
+enum { JSIM_MAX_CAND = 8, JSIM_MAX_RES = 320 };
+enum { JSIM_REASON_DT = 0, JSIM_REASON_MAX_ACCEL, JSIM_REASON_MAX_SPEED, JSIM_REASON_CENTERLINE, JSIM_REASON_WIDTH,
+       JSIM_REASON_REF_D, JSIM_REASON_BUF_D, JSIM_REASON_THR_D, JSIM_REASON_REF_C, JSIM_REASON_BUF_C, JSIM_REASON_THR_C,
+       JSIM_REASON_WHEELBASE, JSIM_REASON_NPAR };
+int jsim_score_trajectories(int device_id, int32_t n_sit, const int32_t *cand_off, const int32_t *pt_off, const double *pts,
+                            const int32_t *mode, const int32_t *time_from, const double *ego, const double *cyc, const double *now,
+                            const double *par, int32_t n_w, const double *w, const int32_t *form, const double *ideal,
+                            int32_t *status, int32_t *n_samples, double *ct, double *avg, double *scores, int32_t *best,
+                            double *detail, double *resampled);
+
 /* ---- the job's one exchange: the final trajectory gather over RCCL / xGMI ----
  * The reference has no multi-process code at all (its only multi-ego code is the serial Python loop of
  * main/scenarios/interactive_mpc.py:119-172); egos are independent (main/lib/mpc.py:141-211), so ranks own contiguous shards
