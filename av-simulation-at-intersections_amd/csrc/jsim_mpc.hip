@@ -2199,6 +2199,8 @@ extern "C" int jsim_score_trajectories(int device_id, int32_t n_sit, const int32
         if (!(par[JSIM_REASON_NPAR * (size_t)s + JSIM_REASON_DT] > 0.0)) return fail(nullptr, -22, "%s: situation %d: DT <= 0", who, s);
     for (int k = 0; k < n_w; ++k)
         if (form[k] != 0 && form[k] != 1) return fail(nullptr, -22, "%s: form[%d] = %d (0: for_reasons, 1: with_weights)", who, k, form[k]);
+    for (int k = 0; k < 3; ++k)   // balance_function divides by each ideal weight (the reference raises ZeroDivisionError on a zero)
+        if (!(ideal[k] > 0.0)) return fail(nullptr, -22, "%s: ideal[%d] <= 0", who, k);
     int ndev = 0;
     HIP_TRY(nullptr, hipGetDeviceCount(&ndev));
     if (device_id < 0 || device_id >= ndev) return fail(nullptr, -19, "%s: device %d of %d", who, device_id, ndev);

@@ -34,6 +34,8 @@ def par_row(**over) -> np.ndarray:
 
 def default_layout(n_cand: int):
     """The reference's list: planned candidates, the following one last, scored with the time of the one before it."""
+    if n_cand == 0:
+        return [], []
     return [0] * (n_cand - 1) + [1], list(range(n_cand - 1)) + [max(n_cand - 2, 0)]
 
 

@@ -372,7 +372,8 @@ int jsim_plan_routes_weighted(int device_id, int32_t n_routes, const double *sta
  *   resampled [Ctot][JSIM_MAX_RES][3] (n_samples rows, NaN behind them).
  *   -22 before any device call: a null required table, offsets that do not start at 0 or decrease, more than JSIM_MAX_CAND
  *   candidates in a situation, a time_from outside its situation or naming a candidate that names another, a mode or form outside
- *   {0, 1}, a number that is not finite, DT <= 0. */
+ *   {0, 1}, a number that is not finite, DT <= 0, an ideal weight <= 0 (balance_function divides by each of them; the reference
+ *   raises ZeroDivisionError on a zero). */
 enum { JSIM_MAX_CAND = 8, JSIM_MAX_RES = 320 };
 enum { JSIM_REASON_DT = 0, JSIM_REASON_MAX_ACCEL, JSIM_REASON_MAX_SPEED, JSIM_REASON_CENTERLINE, JSIM_REASON_WIDTH,
        JSIM_REASON_REF_D, JSIM_REASON_BUF_D, JSIM_REASON_THR_D, JSIM_REASON_REF_C, JSIM_REASON_BUF_C, JSIM_REASON_THR_C,

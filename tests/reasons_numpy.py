@@ -176,6 +176,8 @@ def score_situation(cands, modes, time_from, ego, cyc, now, par=DEFAULT_PAR, wei
 
 def default_layout(C):
     """The reference's list: planned candidates, the following one last with the time of the one before it."""
+    if C == 0:
+        return [], []
     modes = [0] * (C - 1) + [1]
     time_from = list(range(C - 1)) + [C - 2 if C > 1 else 0]
     return modes, time_from

@@ -4,7 +4,10 @@ tests/golden/reasons.npz and the numpy restatement tests/reasons_numpy.py; nothi
 Bar: status, n_samples and best exact; ct, averages, scores and the five detail arrays within 1e-12 relative.  Derivation: a result
 is a mean or a sum of at most 320 O(1) terms accumulated in the reference's order, behind at most ~200 Euler steps whose sin / cos
 and the scores' exp come from another libm (a few ulp each, 2.2e-16); errors add at worst linearly: 320 x 4 ulp ~ 3e-13 for a sum
-that is then divided by its count, ~1e-14 typical -- 1e-12 leaves about 100 x headroom.  The measured maximum is printed by test_fixture_in_one_launch and recorded in DESIGN.md section 14."""
+that is then divided by its count, ~1e-14 typical -- 1e-12 leaves about 100 x headroom.  The measured maximum is printed by test_fixture_in_one_launch and recorded in DESIGN.md section 14.
+This fixture stays at 191 samples and 191 Euler steps; test_gpu_reasons_edges.py takes the same bar to the table's 320 samples and
+to 65535 Euler steps, where every cyclist with more than 200 steps has zero acceleration and steering: sin / cos are then one
+constant each, both sides add the same increment in the same order, and the step count does not enter the error."""
 import numpy as np
 import pytest
 

@@ -134,6 +134,8 @@ def test_argument_errors_without_gpu(pkg):
         refused(b"a number that is not finite", edit=_set(key, idx, v))
     refused(b"situation 1: DT <= 0", edit=_set("par", 12, 0.0))
     refused(b"situation 0: DT <= 0", edit=_set("par", 0, -0.1))
+    refused(b"ideal[0] <= 0", ideal=(0.0, 1 / 3, 1 / 3))                    # balance_function divides by each ideal weight
+    refused(b"ideal[2] <= 0", ideal=(1 / 3, 1 / 3, -0.25))
     nine = dict(sits[1], candidates=[sits[1]["candidates"][0]] * 9)
     rc, _ = RC.raw_call(pkg, [nine])
     assert rc == -22 and b"situation 0 has 9 candidates (at most 8)" in lib.jsim_last_error(None)
