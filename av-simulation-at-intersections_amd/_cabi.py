@@ -139,9 +139,6 @@ def load() -> C.CDLL:
     lib.jsim_score_trajectories.restype = C.c_int
     #                                      dev  S    cand_off pt_off pts mode time_from ego cyc now par  W    w   form ideal  outs
     lib.jsim_score_trajectories.argtypes = [i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp] + [vp] * 8
-    lib.jsim_score_trajectories.restype = C.c_int
-    #                                      dev  S    cand_off pt_off pts mode time_from ego cyc now par  W    w   form ideal  outs
-    lib.jsim_score_trajectories.argtypes = [i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp] + [vp] * 8
     if lib.jsim_abi_version() != ABI_VERSION:
         raise JsimError(f"libjsim_mpc.so ABI {lib.jsim_abi_version()} != binding ABI {ABI_VERSION}")
     _lib = lib

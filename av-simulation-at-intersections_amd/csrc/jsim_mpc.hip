@@ -1166,17 +1166,22 @@ struct PlantP {
     const double *pe; // per-ego configuration (MAX_DECEL at [14]) or NULL
 };
 
-__global__ __launch_bounds__(256) void plant_step_kernel(PlantP P, double *x0, const double *oa, const double *od,
-                                                         const int *status, double *di_ai)
+// The three helpers below are written out once more in the tails of the fused kernels (mpc_step_reg.inc, mpc_step_reg4.inc): keep them in step.
+// (di, ai) of ego b: the solve's first controls, or after a failed solve the previous steering and a full brake
+__device__ __forceinline__ void select_di_ai(const PlantP &P, int b, const int *status, const double *oa, const double *od,
+                                             double *di_ai, double &di, double &ai)
 {
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= P.B) return;
-    double di = di_ai[2 * b], ai;
+    const double max_decel = P.max_decel; // (read here: a choice between its address and the ego's row would put P into scratch)
+    di = di_ai[2 * b];
     if (status[b] == JSIM_OK) { di = od[(size_t)b * P.T]; ai = oa[(size_t)b * P.T]; }
-    else ai = P.pe ? P.pe[(size_t)b * JSIM_EGO_CFG_DOUBLES + 14] : P.max_decel;
+    else ai = P.pe ? P.pe[(size_t)b * JSIM_EGO_CFG_DOUBLES + 14] : max_decel;
     di_ai[2 * b] = di;
     di_ai[2 * b + 1] = ai;
-    double x = x0[4 * b], y = x0[4 * b + 1], v = x0[4 * b + 2], th = x0[4 * b + 3];
+}
+
+// Simulation.step
+__device__ __forceinline__ void simulation_step(const PlantP &P, double di, double ai, double &x, double &y, double &v, double &th)
+{
     double dc = (P.smax < di) ? P.smax : di;
     dc = (-P.smax > dc) ? -P.smax : dc;
     const double xd = v * cos(th), yd = v * sin(th), thd = (v / P.L) * tan(dc);
@@ -1184,6 +1189,28 @@ __global__ __launch_bounds__(256) void plant_step_kernel(PlantP P, double *x0, c
     v += ai * P.dt;
     v = (P.vmax < v) ? P.vmax : v;
     v = (P.vmin > v) ? P.vmin : v;
+}
+
+// MPC.is_goal (main/lib/mpc.py:314-330) of the state (x, y, v); the goal is the last point of the path given to MPC.__init__
+__device__ __forceinline__ bool mpc_is_goal(const double2 *pxy, const long long *poff, int path, int path_len, long long ti,
+                                            double x, double y, double v, double goal_dis, double stop_speed)
+{
+    const double2 g = pxy[poff[path + 1] - 1];
+    bool isgoal = hypot(x - g.x, y - g.y) <= goal_dis;
+    const long long df = ti - (long long)path_len;
+    if ((df < 0 ? -df : df) >= 5) isgoal = false;
+    return isgoal && fabs(v) <= stop_speed;
+}
+
+__global__ __launch_bounds__(256) void plant_step_kernel(PlantP P, double *x0, const double *oa, const double *od,
+                                                         const int *status, double *di_ai)
+{
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= P.B) return;
+    double di, ai;
+    select_di_ai(P, b, status, oa, od, di_ai, di, ai);
+    double x = x0[4 * b], y = x0[4 * b + 1], v = x0[4 * b + 2], th = x0[4 * b + 3];
+    simulation_step(P, di, ai, x, y, v, th);
     x0[4 * b] = x; x0[4 * b + 1] = y; x0[4 * b + 2] = v; x0[4 * b + 3] = th;
 }
 
@@ -1199,11 +1226,11 @@ struct RecP {
 };
 
 struct LoopP {
-    int B, T, max_age;
-    double dt, L, smax, vmax, vmin, max_decel, goal_dis, stop_speed;
+    PlantP plant;
+    int max_age;
+    double goal_dis, stop_speed;
     const double2 *pxy;
     const long long *poff;
-    const double *pe; // per-ego configuration (MAX_DECEL at [14]) or NULL
 };
 
 __global__ __launch_bounds__(256) void loop_advance_kernel(LoopP P, double *x0, double *oa, double *od,
@@ -1214,48 +1241,35 @@ __global__ __launch_bounds__(256) void loop_advance_kernel(LoopP P, double *x0, 
                                                            unsigned long long *n_respawn, RecP R)
 {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= P.B) return;
-    double di = di_ai[2 * b], ai;
-    if (status[b] == JSIM_OK) { di = od[(size_t)b * P.T]; ai = oa[(size_t)b * P.T]; }
-    else ai = P.pe ? P.pe[(size_t)b * JSIM_EGO_CFG_DOUBLES + 14] : P.max_decel;
-    di_ai[2 * b] = di;
-    di_ai[2 * b + 1] = ai;
+    const int B = P.plant.B, T = P.plant.T;
+    if (b >= B) return;
+    double di, ai;
+    select_di_ai(P.plant, b, status, oa, od, di_ai, di, ai);
     if (hist) {
         const int k = *tick; // device tick counter: bumped by a 1-thread kernel after this one (graph-replay safe)
-        if (k < hist_cap) { hist[((size_t)k * P.B + b) * 2] = di; hist[((size_t)k * P.B + b) * 2 + 1] = ai; }
+        if (k < hist_cap) { hist[((size_t)k * B + b) * 2] = di; hist[((size_t)k * B + b) * 2 + 1] = ai; }
     }
     double x = x0[4 * b], y = x0[4 * b + 1], v = x0[4 * b + 2], th = x0[4 * b + 3];
-    double dc = (P.smax < di) ? P.smax : di;
-    dc = (-P.smax > dc) ? -P.smax : dc;
-    const double xd = v * cos(th), yd = v * sin(th), thd = (v / P.L) * tan(dc);
-    x += xd * P.dt; y += yd * P.dt; th += thd * P.dt;
-    v += ai * P.dt;
-    v = (P.vmax < v) ? P.vmax : v;
-    v = (P.vmin > v) ? P.vmin : v;
-    // MPC.is_goal on the new state (main/lib/mpc.py:314-330)
-    const long long off = P.poff[path_id[b]];
-    const long long full = P.poff[path_id[b] + 1] - off;
-    const double2 g = P.pxy[off + full - 1];
+    simulation_step(P.plant, di, ai, x, y, v, th);
     const long long ti = target_ind[b];
-    bool isgoal = hypot(x - g.x, y - g.y) <= P.goal_dis;
-    long long df = ti - (long long)path_len[b];
-    if ((df < 0 ? -df : df) >= 5) isgoal = false;
-    const bool goal = isgoal && fabs(v) <= P.stop_speed, aged = age[b] + 1 >= P.max_age;
+    const bool goal = mpc_is_goal(P.pxy, P.poff, path_id[b], path_len[b], ti, x, y, v, P.goal_dis, P.stop_speed); // on the new state
+    const bool aged = age[b] + 1 >= P.max_age;
     const bool done = goal || aged;
     if (R.rec) { // the History record: state after the plant step, ahead of the respawn; the solve's ox[0], oy[0] is x0's pose
         const int k = *tick;
         if (k < R.cap) {
             const bool ok = status[b] == JSIM_OK;
-            jsim_rec_store_dev(R.rec, k, P.B, b,
+            const long long off = P.poff[path_id[b]];
+            jsim_rec_store_dev(R.rec, k, B, b,
                                ok ? jsim_xref_deviation(P.pxy[off + ti], R.pyaw[off + ti], x0[4 * b], x0[4 * b + 1]) : __builtin_nan(""));
-            jsim_rec_store(R.rec, R.flags, k, P.B, b, x, y, th, v, di, ai,
+            jsim_rec_store(R.rec, R.flags, k, B, b, x, y, th, v, di, ai,
                            (ok ? 0 : JSIM_REC_FAILED) | (goal ? JSIM_REC_GOAL : 0) | (aged ? JSIM_REC_AGE : 0));
         }
     }
     if (done) {
         x = x0_spawn[4 * b]; y = x0_spawn[4 * b + 1]; v = x0_spawn[4 * b + 2]; th = x0_spawn[4 * b + 3];
         target_ind[b] = target_spawn[b];
-        for (int t = 0; t < P.T; ++t) { oa[(size_t)b * P.T + t] = 0.0; od[(size_t)b * P.T + t] = 0.0; }
+        for (int t = 0; t < T; ++t) { oa[(size_t)b * T + t] = 0.0; od[(size_t)b * T + t] = 0.0; }
         di_ai[2 * b] = 0.0; di_ai[2 * b + 1] = 0.0;
         age[b] = 0;
         if (n_respawn) atomicAdd(n_respawn, 1ull);
@@ -1292,19 +1306,12 @@ __global__ __launch_bounds__(256) void deviation_goal_kernel(GoalP P, const doub
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= P.B) return;
     const long long off = P.poff[path_id[b]];
-    const long long full = P.poff[path_id[b] + 1] - off;
     const long long ti = target_ind[b];
     if (deviation)
         deviation[b] = jsim_xref_deviation(P.pxy[off + ti], P.pyaw[off + ti], ox[(size_t)b * (P.T + 1)], oy[(size_t)b * (P.T + 1)]);
-    if (is_goal) {
-        const double2 g = P.pxy[off + full - 1]; // goal = last point of the path given to MPC.__init__
-        const double d = hypot(x0[4 * b] - g.x, x0[4 * b + 1] - g.y);
-        bool isgoal = d <= P.goal_dis;
-        long long df = ti - (long long)path_len[b];
-        if ((df < 0 ? -df : df) >= 5) isgoal = false;
-        const bool isstop = fabs(x0[4 * b + 2]) <= P.stop_speed;
-        is_goal[b] = (isgoal && isstop) ? 1 : 0;
-    }
+    if (is_goal)
+        is_goal[b] = mpc_is_goal(P.pxy, P.poff, path_id[b], path_len[b], ti, x0[4 * b], x0[4 * b + 1], x0[4 * b + 2], P.goal_dis,
+                                 P.stop_speed) ? 1 : 0;
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -1435,6 +1442,51 @@ struct DeviceGuard {
     do {                                                                                                       \
         if (!dev_guard.ok()) return fail(ctx_, -5, "switching to the context's device failed: %s", hipGetErrorString(dev_guard.err)); \
     } while (0)
+
+// The one-shot calls (route planner, trajectory scoring) take a device id, not a context: it must name a device, and the call
+// runs on it under a DeviceGuard
+#define JSIM_ON_DEVICE_ID(who_, id_)                                                                           \
+    int ndev = 0;                                                                                             \
+    HIP_TRY(nullptr, hipGetDeviceCount(&ndev));                                                               \
+    if ((id_) < 0 || (id_) >= ndev) return fail(nullptr, -19, "%s: device %d of %d", who_, id_, ndev);       \
+    DeviceGuard dev_guard(id_);                                                                                \
+    JSIM_GUARD_OK(nullptr)
+
+// The device buffers of a one-shot call: allocated and filled inside the call, freed when it returns, whichever way.  The first
+// error is kept and turns every later step into a no-op; result() tells a failed allocation / upload from what came after.
+struct DeviceScratch {
+    std::vector<void *> owned;
+    hipError_t err = hipSuccess;
+    bool setup_failed = false; // err comes from alloc() / upload()
+    DeviceScratch() = default;
+    DeviceScratch(const DeviceScratch &) = delete;
+    DeviceScratch &operator=(const DeviceScratch &) = delete;
+    ~DeviceScratch() { for (void *q : owned) (void)hipFree(q); }
+    bool ok() const { return err == hipSuccess; }
+    template <class T> T *alloc(size_t n) // (n = 0: still a valid pointer)
+    {
+        void *q = nullptr;
+        if (!ok()) return nullptr;
+        err = hipMalloc(&q, n ? sizeof(T) * n : 8);
+        if (!ok()) { setup_failed = true; return nullptr; }
+        owned.push_back(q);
+        return (T *)q;
+    }
+    template <class T> const T *upload(const T *host, size_t n)
+    {
+        T *q = alloc<T>(n);
+        if (q && n) { err = hipMemcpy(q, host, sizeof(T) * n, hipMemcpyHostToDevice); setup_failed = !ok(); }
+        return ok() ? q : nullptr;
+    }
+    template <class T> void fill(T *dev, int byte, size_t n) { if (ok() && n) err = hipMemset(dev, byte, sizeof(T) * n); }
+    template <class T> void download(T *host, const T *dev, size_t n) { if (ok() && n) err = hipMemcpy(host, dev, sizeof(T) * n, hipMemcpyDeviceToHost); }
+    int result(const char *who) const
+    {
+        if (ok()) return 0;
+        if (setup_failed) return fail(nullptr, -12, "%s: device allocation / upload failed", who);
+        return fail(nullptr, -5, "%s: %s", who, hipGetErrorString(err));
+    }
+};
 
 extern "C" int jsim_abi_version(void) { return JSIM_ABI_VERSION; }
 
@@ -1780,6 +1832,12 @@ extern "C" int jsim_mpc_step_debug(jsim_ctx *ctx, int32_t B, const double *x0, c
     return 0;
 }
 
+static PlantP plant_p(const jsim_ctx *ctx, int B)
+{
+    const jsim_cfg &c = ctx->cfg;
+    return PlantP{B, c.T, c.dt, c.L, c.max_steer, c.max_speed, c.min_speed, c.max_decel, ctx->d_pe};
+}
+
 extern "C" int jsim_plant_step(jsim_ctx *ctx, int32_t B, double *x0, const double *oa, const double *od,
                                const int32_t *status, double *di_ai, void *stream)
 {
@@ -1789,9 +1847,8 @@ extern "C" int jsim_plant_step(jsim_ctx *ctx, int32_t B, double *x0, const doubl
     if (B < 0) return fail(ctx, -22, "jsim_plant_step: B=%d", B);
     if (B == 0) return 0;
     if (!x0 || !oa || !od || !status || !di_ai) return fail(ctx, -22, "jsim_plant_step: null device pointer");
-    const jsim_cfg &c = ctx->cfg;
-    PlantP P = {B, c.T, c.dt, c.L, c.max_steer, c.max_speed, c.min_speed, c.max_decel, ctx->d_pe};
-    hipLaunchKernelGGL(plant_step_kernel, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, P, x0, oa, od, status, di_ai);
+    hipLaunchKernelGGL(plant_step_kernel, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, plant_p(ctx, B), x0, oa, od,
+                       status, di_ai);
     HIP_TRY(ctx, hipGetLastError());
     return 0;
 }
@@ -1820,8 +1877,7 @@ extern "C" int jsim_mpc_xref_deviation_goal(jsim_ctx *ctx, int32_t B, const doub
 static void launch_advance(const jsim_ctx *ctx, int B, const StepBufs &S, const AdvanceBufs &A, hipStream_t s)
 {
     const jsim_cfg &c = ctx->cfg;
-    LoopP P = {B, c.T, A.max_age > 0 ? A.max_age : 0x7fffffff, c.dt, c.L, c.max_steer, c.max_speed, c.min_speed,
-               c.max_decel, c.goal_dis, c.stop_speed, ctx->d_pxy, ctx->d_poff, ctx->d_pe};
+    LoopP P = {plant_p(ctx, B), A.max_age > 0 ? A.max_age : 0x7fffffff, c.goal_dis, c.stop_speed, ctx->d_pxy, ctx->d_poff};
     const RecP R = {ctx->rec, ctx->rec_flags, ctx->rec_cap, ctx->d_pyaw};
     hipLaunchKernelGGL(loop_advance_kernel, dim3((B + 255) / 256), dim3(256), 0, s, P, S.x0, S.oa, S.od, S.status, A.di_ai,
                        (long long *)S.target_ind, S.path_id, S.path_len, A.x0_spawn, (const long long *)A.target_spawn, A.age,
@@ -1991,11 +2047,7 @@ static int plan_routes_tables(const char *who, int device_id, int32_t n_routes, 
             if (!std::isfinite(w)) return fail(nullptr, -22, "%s: route %d: %s[%d] is not finite", who, k, j < 5 ? "wh" : "wc", j < 5 ? j : j - 5);
         }
     }
-    int ndev = 0;
-    HIP_TRY(nullptr, hipGetDeviceCount(&ndev));
-    if (device_id < 0 || device_id >= ndev) return fail(nullptr, -19, "%s: device %d of %d", who, device_id, ndev);
-    DeviceGuard dev_guard(device_id);
-    JSIM_GUARD_OK(nullptr);
+    JSIM_ON_DEVICE_ID(who, device_id);
     const int R = n_routes, cap = node_cap, seg = n_pts - 1;
     // sizes in 64 bits BEFORE anything is allocated: per route ~84 B per node slot (+ the hash table) and the output arrays
     if (max_path > 4096 || n_pts > 4096) return fail(nullptr, -22, "%s: max_path %d / points per primitive %d above 4096", who, max_path, n_pts);
@@ -2047,52 +2099,32 @@ static int plan_routes_tables(const char *who, int device_id, int32_t n_routes, 
         c[0] = mx; c[1] = my; c[2] = rr * (1.0 + 1e-9) + 1e-9;
     }
     const size_t n_hp = (size_t)hp_off[n_obs_total], n_cc = (size_t)cc_off[n_prim];
-    std::vector<void *> owned;
-    auto dalloc = [&](size_t bytes) -> void * { void *q = nullptr; if (hipMalloc(&q, bytes ? bytes : 8) != hipSuccess) return nullptr; owned.push_back(q); return q; };
-    auto put = [&](const void *src, size_t bytes) -> void * {
-        void *q = dalloc(bytes);
-        if (q && bytes && hipMemcpy(q, src, bytes, hipMemcpyHostToDevice) != hipSuccess) return nullptr;
-        return q;
-    };
-    auto cleanup = [&]() { for (void *q : owned) (void)hipFree(q); };
+    const size_t Rn = (size_t)R * cap, n_prims_out = (size_t)R * max_path, n_nodes = (size_t)R * (max_path + 1) * 3, n_traj = n_prims_out * seg * 3;
+    DeviceScratch D;
     PlanP P;
     memset(&P, 0, sizeof(P));
-    P.n_routes = R; P.n_prim = n_prim; P.n_pts = n_pts; P.max_path = max_path; P.node_cap = cap;
-    P.wh = (const double *)put(wh, sizeof(double) * 5 * R); P.wc = (const double *)put(wc, sizeof(double) * 4 * R);
-    P.form = (const int *)put(form, sizeof(int) * R);
-    P.start = (const double *)put(start, sizeof(double) * 3 * R); P.goal = (const double *)put(goal, sizeof(double) * 3 * R);
-    P.goal_box = (const double *)put(goal_box, sizeof(double) * 4 * R); P.tol = (const double *)put(tol, sizeof(double) * R);
-    P.hp = (const double *)put(hp, sizeof(double) * 3 * n_hp); P.hp_off = (const int *)put(hp_off, sizeof(int) * (n_obs_total + 1));
-    P.route_obs_off = (const int *)put(route_obs_off, sizeof(int) * (R + 1));
-    P.obc = (const double *)put(obc.data(), sizeof(double) * obc.size());
-    P.mp_pts = (const double *)put(mp_pts, sizeof(double) * 3 * (size_t)n_prim * n_pts); P.mp_len = (const double *)put(mp_len, sizeof(double) * n_prim);
-    P.cc_pts = (const double *)put(cc_pts, sizeof(double) * 2 * n_cc); P.cc_off = (const int *)put(cc_off, sizeof(int) * (n_prim + 1));
-    P.nx = (double *)dalloc(sizeof(double) * (size_t)R * cap); P.ny = (double *)dalloc(sizeof(double) * (size_t)R * cap);
-    P.nth = (double *)dalloc(sizeof(double) * (size_t)R * cap); P.ng = (double *)dalloc(sizeof(double) * (size_t)R * cap);
-    P.nparent = (int *)dalloc(sizeof(int) * (size_t)R * cap); P.nprim = (int *)dalloc(sizeof(int) * (size_t)R * cap);
-    P.htab = (int *)dalloc(sizeof(int) * (size_t)R * hash_cap); P.hash_cap = hash_cap;
-    P.ov_gh = (double *)dalloc(sizeof(double) * (size_t)R * cap); P.ov_g = (double *)dalloc(sizeof(double) * (size_t)R * cap);
-    P.ov_id = (int *)dalloc(sizeof(int) * (size_t)R * cap);
-    P.status = (int *)dalloc(sizeof(int) * R); P.n_prims = (int *)dalloc(sizeof(int) * R); P.n_expanded = (int *)dalloc(sizeof(int) * R);
-    P.prims = (int *)dalloc(sizeof(int) * (size_t)R * max_path); P.cost = (double *)dalloc(sizeof(double) * R);
-    P.nodes = (double *)dalloc(sizeof(double) * (size_t)R * (max_path + 1) * 3);
-    P.traj = (double *)dalloc(sizeof(double) * (size_t)R * max_path * seg * 3);
-    if (!P.start || !P.goal || !P.goal_box || !P.tol || !P.hp || !P.hp_off || !P.route_obs_off || !P.obc || !P.mp_pts || !P.mp_len || !P.cc_pts ||
-        !P.cc_off || !P.wh || !P.wc || !P.form || !P.nx || !P.ny || !P.nth || !P.ng || !P.nparent || !P.nprim || !P.htab || !P.ov_gh || !P.ov_g || !P.ov_id || !P.status || !P.n_prims || !P.n_expanded || !P.prims ||
-        !P.cost || !P.nodes || !P.traj) {
-        cleanup();
-        return fail(nullptr, -12, "%s: device allocation / upload failed", who);
-    }
-    hipError_t e = hipMemset(P.cost, 0, sizeof(double) * R);
-    if (e == hipSuccess) e = hipMemset(P.htab, 0xff, sizeof(int) * (size_t)R * hash_cap);
-    if (e == hipSuccess) e = hipMemset(P.traj, 0, sizeof(double) * (size_t)R * max_path * seg * 3);
-    if (e == hipSuccess) e = hipMemset(P.nodes, 0, sizeof(double) * (size_t)R * (max_path + 1) * 3);
-    if (e == hipSuccess) e = hipMemset(P.prims, 0xff, sizeof(int) * (size_t)R * max_path);
-    if (e == hipSuccess) {
+    P.n_routes = R; P.n_prim = n_prim; P.n_pts = n_pts; P.max_path = max_path; P.node_cap = cap; P.hash_cap = hash_cap;
+    P.wh = D.upload(wh, 5 * (size_t)R); P.wc = D.upload(wc, 4 * (size_t)R); P.form = D.upload(form, R);
+    P.start = D.upload(start, 3 * (size_t)R); P.goal = D.upload(goal, 3 * (size_t)R);
+    P.goal_box = D.upload(goal_box, 4 * (size_t)R); P.tol = D.upload(tol, R);
+    P.hp = D.upload(hp, 3 * n_hp); P.hp_off = D.upload(hp_off, n_obs_total + 1); P.route_obs_off = D.upload(route_obs_off, R + 1);
+    P.obc = D.upload(obc.data(), obc.size());
+    P.mp_pts = D.upload(mp_pts, 3 * (size_t)n_prim * n_pts); P.mp_len = D.upload(mp_len, n_prim);
+    P.cc_pts = D.upload(cc_pts, 2 * n_cc); P.cc_off = D.upload(cc_off, n_prim + 1);
+    P.nx = D.alloc<double>(Rn); P.ny = D.alloc<double>(Rn); P.nth = D.alloc<double>(Rn); P.ng = D.alloc<double>(Rn);
+    P.nparent = D.alloc<int>(Rn); P.nprim = D.alloc<int>(Rn); P.htab = D.alloc<int>((size_t)R * hash_cap);
+    P.ov_gh = D.alloc<double>(Rn); P.ov_g = D.alloc<double>(Rn); P.ov_id = D.alloc<int>(Rn);
+    P.status = D.alloc<int>(R); P.n_prims = D.alloc<int>(R); P.n_expanded = D.alloc<int>(R);
+    P.prims = D.alloc<int>(n_prims_out); P.cost = D.alloc<double>(R);
+    P.nodes = D.alloc<double>(n_nodes); P.traj = D.alloc<double>(n_traj);
+    if (!D.ok()) return D.result(who);
+    D.fill(P.cost, 0, R); D.fill(P.htab, 0xff, (size_t)R * hash_cap); D.fill(P.traj, 0, n_traj); D.fill(P.nodes, 0, n_nodes);
+    D.fill(P.prims, 0xff, n_prims_out);
+    if (D.ok()) {
         hipLaunchKernelGGL(plan_astar_kernel, dim3(R), dim3(64), 0, 0, P);
-        e = hipGetLastError();
+        D.err = hipGetLastError();
     }
-    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (D.ok()) D.err = hipDeviceSynchronize();
 #ifdef JPL_STAMPS
     {
         static long long clk[64][32];
@@ -2105,16 +2137,9 @@ static int plan_routes_tables(const char *who, int device_id, int32_t n_routes, 
             }
     }
 #endif
-    if (e == hipSuccess) e = hipMemcpy(status, P.status, sizeof(int) * R, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(cost, P.cost, sizeof(double) * R, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(n_prims, P.n_prims, sizeof(int) * R, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(n_expanded, P.n_expanded, sizeof(int) * R, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(prims, P.prims, sizeof(int) * (size_t)R * max_path, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(nodes, P.nodes, sizeof(double) * (size_t)R * (max_path + 1) * 3, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(traj, P.traj, sizeof(double) * (size_t)R * max_path * seg * 3, hipMemcpyDeviceToHost);
-    cleanup();
-    if (e != hipSuccess) return fail(nullptr, -5, "%s: %s", who, hipGetErrorString(e));
-    return 0;
+    D.download(status, P.status, R); D.download(cost, P.cost, R); D.download(n_prims, P.n_prims, R); D.download(n_expanded, P.n_expanded, R);
+    D.download(prims, P.prims, n_prims_out); D.download(nodes, P.nodes, n_nodes); D.download(traj, P.traj, n_traj);
+    return D.result(who);
 }
 
 // One launch-wide weight set, the generic form (mp_search_ww_generic.py): its row repeated for every route.
@@ -2201,65 +2226,39 @@ extern "C" int jsim_score_trajectories(int device_id, int32_t n_sit, const int32
         if (form[k] != 0 && form[k] != 1) return fail(nullptr, -22, "%s: form[%d] = %d (0: for_reasons, 1: with_weights)", who, k, form[k]);
     for (int k = 0; k < 3; ++k)   // balance_function divides by each ideal weight (the reference raises ZeroDivisionError on a zero)
         if (!(ideal[k] > 0.0)) return fail(nullptr, -22, "%s: ideal[%d] <= 0", who, k);
-    int ndev = 0;
-    HIP_TRY(nullptr, hipGetDeviceCount(&ndev));
-    if (device_id < 0 || device_id >= ndev) return fail(nullptr, -19, "%s: device %d of %d", who, device_id, ndev);
-    DeviceGuard dev_guard(device_id);
-    JSIM_GUARD_OK(nullptr);
+    JSIM_ON_DEVICE_ID(who, device_id);
     const size_t S = (size_t)n_sit, W = (size_t)n_w, Ct = (size_t)ctot;
     if (W * (Ct + S) * 8ull > (16ull << 30)) return fail(nullptr, -12, "%s: %d weight rows x %d candidates would need more than 16 GiB", who, n_w, ctot);
-    std::vector<void *> owned;
-    auto dalloc = [&](size_t bytes) -> void * { void *q = nullptr; if (hipMalloc(&q, bytes ? bytes : 8) != hipSuccess) return nullptr; owned.push_back(q); return q; };
-    auto put = [&](const void *src, size_t bytes) -> void * {
-        void *q = dalloc(bytes);
-        if (q && bytes && hipMemcpy(q, src, bytes, hipMemcpyHostToDevice) != hipSuccess) return nullptr;
-        return q;
-    };
-    auto cleanup = [&]() { for (void *q : owned) (void)hipFree(q); };
+    const size_t n_detail = Ct * 5 * JSIM_MAX_RES, n_res = Ct * JSIM_MAX_RES * 3;
+    DeviceScratch D;
     ReasonP P;
     memset(&P, 0, sizeof(P));
     P.n_sit = n_sit; P.n_w = n_w; P.ctot = ctot;
     P.ideal[0] = ideal[0]; P.ideal[1] = ideal[1]; P.ideal[2] = ideal[2];
-    P.cand_off = (const int *)put(cand_off, sizeof(int) * (S + 1)); P.pt_off = (const int *)put(pt_off, sizeof(int) * (Ct + 1));
-    P.pts = (const double *)put(pts, sizeof(double) * 3 * n_pts);
-    P.mode = (const int *)put(mode, sizeof(int) * Ct); P.time_from = (const int *)put(time_from, sizeof(int) * Ct);
-    P.ego = (const double *)put(ego, sizeof(double) * 4 * S); P.cyc = (const double *)put(cyc, sizeof(double) * 6 * S);
-    P.now = (const double *)put(now, sizeof(double) * 5 * S); P.par = (const double *)put(par, sizeof(double) * JSIM_REASON_NPAR * S);
-    P.w = (const double *)put(w, sizeof(double) * 3 * W); P.form = (const int *)put(form, sizeof(int) * W);
-    P.status = (int *)dalloc(sizeof(int) * Ct); P.n_samples = (int *)dalloc(sizeof(int) * Ct);
-    P.ct = (double *)dalloc(sizeof(double) * Ct); P.avg = (double *)dalloc(sizeof(double) * 4 * Ct);
-    P.scores = (double *)dalloc(sizeof(double) * W * Ct); P.best = (int *)dalloc(sizeof(int) * W * S);
-    const size_t n_detail = Ct * 5 * JSIM_MAX_RES, n_res = Ct * JSIM_MAX_RES * 3;
-    if (detail) P.detail = (double *)dalloc(sizeof(double) * n_detail);
-    if (resampled) P.resampled = (double *)dalloc(sizeof(double) * n_res);
-    if (!P.cand_off || !P.pt_off || !P.pts || !P.mode || !P.time_from || !P.ego || !P.cyc || !P.now || !P.par || !P.w || !P.form || !P.status ||
-        !P.n_samples || !P.ct || !P.avg || !P.scores || !P.best || (detail && !P.detail) || (resampled && !P.resampled)) {
-        cleanup();
-        return fail(nullptr, -12, "%s: device allocation / upload failed", who);
-    }
+    P.cand_off = D.upload(cand_off, S + 1); P.pt_off = D.upload(pt_off, Ct + 1); P.pts = D.upload(pts, 3 * n_pts);
+    P.mode = D.upload(mode, Ct); P.time_from = D.upload(time_from, Ct);
+    P.ego = D.upload(ego, 4 * S); P.cyc = D.upload(cyc, 6 * S); P.now = D.upload(now, 5 * S); P.par = D.upload(par, JSIM_REASON_NPAR * S);
+    P.w = D.upload(w, 3 * W); P.form = D.upload(form, W);
+    P.status = D.alloc<int>(Ct); P.n_samples = D.alloc<int>(Ct); P.ct = D.alloc<double>(Ct); P.avg = D.alloc<double>(4 * Ct);
+    P.scores = D.alloc<double>(W * Ct); P.best = D.alloc<int>(W * S);
+    if (detail) P.detail = D.alloc<double>(n_detail);
+    if (resampled) P.resampled = D.alloc<double>(n_res);
+    if (!D.ok()) return D.result(who);
     // every real output starts as NaN (all bits set): what the kernel does not write -- a candidate with a status, the rows behind a
     // candidate's samples -- stays NaN
-    hipError_t e = hipMemset(P.ct, 0xff, sizeof(double) * Ct);
-    if (e == hipSuccess) e = hipMemset(P.avg, 0xff, sizeof(double) * 4 * Ct);
-    if (e == hipSuccess) e = hipMemset(P.scores, 0xff, sizeof(double) * W * Ct);
-    if (e == hipSuccess && P.detail) e = hipMemset(P.detail, 0xff, sizeof(double) * n_detail);
-    if (e == hipSuccess && P.resampled) e = hipMemset(P.resampled, 0xff, sizeof(double) * n_res);
-    if (e == hipSuccess) {
+    D.fill(P.ct, 0xff, Ct); D.fill(P.avg, 0xff, 4 * Ct); D.fill(P.scores, 0xff, W * Ct);
+    if (detail) D.fill(P.detail, 0xff, n_detail);
+    if (resampled) D.fill(P.resampled, 0xff, n_res);
+    if (D.ok()) {
         hipLaunchKernelGGL(score_trajectories_kernel, dim3(n_sit), dim3(64 * JSIM_MAX_CAND), 0, 0, P);
-        e = hipGetLastError();
+        D.err = hipGetLastError();
     }
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e == hipSuccess) e = hipMemcpy(status, P.status, sizeof(int) * Ct, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(n_samples, P.n_samples, sizeof(int) * Ct, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(ct, P.ct, sizeof(double) * Ct, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(avg, P.avg, sizeof(double) * 4 * Ct, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && W) e = hipMemcpy(scores, P.scores, sizeof(double) * W * Ct, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && W) e = hipMemcpy(best, P.best, sizeof(int) * W * S, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && detail) e = hipMemcpy(detail, P.detail, sizeof(double) * n_detail, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && resampled) e = hipMemcpy(resampled, P.resampled, sizeof(double) * n_res, hipMemcpyDeviceToHost);
-    cleanup();
-    if (e != hipSuccess) return fail(nullptr, -5, "%s: %s", who, hipGetErrorString(e));
-    return 0;
+    if (D.ok()) D.err = hipDeviceSynchronize();
+    D.download(status, P.status, Ct); D.download(n_samples, P.n_samples, Ct); D.download(ct, P.ct, Ct); D.download(avg, P.avg, 4 * Ct);
+    D.download(scores, P.scores, W * Ct); D.download(best, P.best, W * S);
+    if (detail) D.download(detail, P.detail, n_detail);
+    if (resampled) D.download(resampled, P.resampled, n_res);
+    return D.result(who);
 }
 
 // the shape table's (thr, thr_sq) rows: check_collision_moving_bicycle's min_distance = the egos' radius + the vehicle's own
@@ -2342,20 +2341,24 @@ extern "C" int jsim_loop_set_vehicle_shapes(jsim_ctx *ctx, int32_t n, const doub
 
 static const double4 *shapes_p(const jsim_ctx *ctx) { return ctx->n_shapes > 0 ? ctx->d_shapes.p : nullptr; }
 
-// obstacle_predict_kernel on n_ticks consecutive ticks' get() tuples (one block per tick)
+// obstacle_predict_kernel on n_ticks consecutive ticks' get() tuples of n_obs > 0 vehicles
 static void launch_obstacle_predict(const jsim_ctx *ctx, int n_obs, int n_steps, const double *get, double *pred, double2 *pred_cc,
                                     double4 *pred_bc, int n_ticks, hipStream_t s)
 {
     const ObsP P = {n_obs, n_steps, ctx->cfg.dt, ctx->oL, ctx->occ0, ctx->occ1, get, pred, pred_cc, pred_bc, shapes_p(ctx)};
-    hipLaunchKernelGGL(obstacle_predict_kernel, dim3(n_ticks), dim3(64), 0, s, P);
+    hipLaunchKernelGGL(obstacle_predict_kernel, dim3((n_obs + 63) / 64, n_ticks), dim3(64), 0, s, P);
 }
 
-// obstacle_predict_grid_kernel: every (tick, vehicle) of the n_obs vehicles of all traffic sets, n_ticks consecutive ticks
-static void launch_obstacle_predict_grid(const jsim_ctx *ctx, int n_obs, int n_steps, const double *get, double2 *pred_cc,
-                                         double4 *pred_bc, int n_ticks, hipStream_t s)
+// one get(), or get() + step(), of O.n_obs > 0 vehicles
+static void launch_obstacle_step(const ObsStepP &O, hipStream_t s)
 {
-    const ObsP P = {n_obs, n_steps, ctx->cfg.dt, ctx->oL, ctx->occ0, ctx->occ1, get, nullptr, pred_cc, pred_bc, shapes_p(ctx)};
-    hipLaunchKernelGGL(obstacle_predict_grid_kernel, dim3((n_obs + 63) / 64, n_ticks), dim3(64), 0, s, P);
+    hipLaunchKernelGGL(obstacle_step_kernel, dim3((O.n_obs + 63) / 64), dim3(64), 0, s, O);
+}
+
+// n_ticks ticks of them, every tick's get() tuples to get_all
+static void launch_obstacle_rollout(const ObsStepP &O, int n_ticks, double *get_all, hipStream_t s)
+{
+    hipLaunchKernelGGL(obstacle_rollout_kernel, dim3((O.n_obs + 63) / 64), dim3(64), 0, s, O, n_ticks, get_all);
 }
 
 // the registered traffic layout as the glue kernels take it (both NULL without one)
@@ -2472,8 +2475,7 @@ extern "C" int jsim_loop_obstacles(jsim_ctx *ctx, int32_t n_obs, double *state, 
     if (n_obs == 0) return 0;
     if (int rc = check_shapes(ctx, "jsim_loop_obstacles", n_obs)) return rc;
     if (!state || !param) return fail(ctx, -22, "jsim_loop_obstacles: null device pointer");
-    hipLaunchKernelGGL(obstacle_step_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream,
-                       obstacle_step_p(ctx, n_obs, do_step ? 1 : 0, state, param, get));
+    launch_obstacle_step(obstacle_step_p(ctx, n_obs, do_step ? 1 : 0, state, param, get), (hipStream_t)stream);
     HIP_TRY(ctx, hipGetLastError());
     return 0;
 }
@@ -2518,24 +2520,24 @@ static int run_host_ticks(jsim_ctx *ctx, int B, int n_ticks, const StepBufs &S, 
     PreP Q = {};
     GroupP GP = {};
     const TrafficP X = G ? traffic_p(ctx) : TrafficP{};
-    const bool grid = X.set_of != nullptr; // traffic sets: all sets' vehicles step and are predicted by the gridded kernels
-    if (grid) {
+    const bool traffic = X.set_of != nullptr; // traffic sets: the predictions of all sets' vehicles do not fit the single-tick tables
+    if (traffic) {
         HIP_TRY(ctx, ctx->d_pred_all.reserve((size_t)std::max(G->n_obs, 1) * G->n_steps * 2));
         HIP_TRY(ctx, ctx->d_bc_all.reserve(std::max(G->n_obs, 1)));
     }
+    double2 *const pred_cc = traffic ? ctx->d_pred_all : ctx->d_pred_cc;
+    double4 *const pred_bc = traffic ? ctx->d_bc_all : ctx->d_pred_bc;
     if (G) {
         Q = fill_prep(ctx, B, G->n_obs, G->n_steps, G->frame_window, G->margin);
         Q.x0 = S.x0; Q.path_id = S.path_id; Q.traj_idx = (long long *)G->traj_idx; Q.prev_path_len = G->prev_path_len;
         Q.path_len = glue_out(ctx, S, *G); Q.col_flag = G->col_flag; Q.status = G->pre_status;
-        if (grid) { Q.pred_cc = ctx->d_pred_all; Q.pred_bc = ctx->d_bc_all; }
+        Q.pred_cc = pred_cc; Q.pred_bc = pred_bc;
         const double mate_thr = 2.0 * ctx->col_radius; // check_collision_moving_cars between two egos
         GP = GroupP{ctx->d_group_of, ctx->d_group_off, ctx->d_ego_cc, ctx->d_ego_bc, G->n_obs, mate_thr, jsim_sqrt_threshold(mate_thr)};
     }
     auto obstacles = [&](int do_step) { // get(), or get() then step()
         if (G->n_obs == 0) return;
-        const ObsStepP O = obstacle_step_rec_p(ctx, G->n_obs, do_step, G->obs_state, G->obs_param, G->obs_get, A.tick);
-        if (grid) hipLaunchKernelGGL(obstacle_step_grid_kernel, dim3((G->n_obs + 63) / 64), dim3(64), 0, s, O);
-        else hipLaunchKernelGGL(obstacle_step_kernel, dim3(1), dim3(64), 0, s, O);
+        launch_obstacle_step(obstacle_step_rec_p(ctx, G->n_obs, do_step, G->obs_state, G->obs_param, G->obs_get, A.tick), s);
     };
     // every tick's iteration counts go onto the totals (jsim_mpc_iter_totals): the caller's n_iter, or the context's own
     if (int rc = prepare_iter_totals(ctx, B, s)) return rc;
@@ -2547,11 +2549,8 @@ static int run_host_ticks(jsim_ctx *ctx, int B, int n_ticks, const StepBufs &S, 
         if (G) {
             obstacles(0);
             // (traffic sets: no single-tick prediction of at most JSIM_MAX_OBS obstacles is left for jsim_loop_pre_tick)
-            ctx->pred_n_obs = grid ? 0 : G->n_obs; ctx->pred_n_steps = G->n_steps;
-            if (G->n_obs > 0) {
-                if (grid) launch_obstacle_predict_grid(ctx, G->n_obs, G->n_steps, G->obs_get, ctx->d_pred_all, ctx->d_bc_all, 1, s);
-                else launch_obstacle_predict(ctx, G->n_obs, G->n_steps, G->obs_get, nullptr, ctx->d_pred_cc, ctx->d_pred_bc, 1, s);
-            }
+            ctx->pred_n_obs = traffic ? 0 : G->n_obs; ctx->pred_n_steps = G->n_steps;
+            if (G->n_obs > 0) launch_obstacle_predict(ctx, G->n_obs, G->n_steps, G->obs_get, nullptr, pred_cc, pred_bc, 1, s);
             if (kind == Glue::interacting) {
                 launch_ego_predict(ctx, B, S.x0, A.di_ai, G->n_steps, nullptr, s);
                 hipLaunchKernelGGL(group_pre_tick_kernel, dim3(B), dim3(64), 0, s, Q, GP, X);
@@ -2650,7 +2649,7 @@ static int check_traffic(jsim_ctx *ctx, const char *fn, int B, int n_obs)
 // The whole scenario loop (main/scenarios/mpc_intersection.py:99-163) for n_ticks ticks.  With a one-wave register kernel and
 // one linearisation pass it is THREE launches: the scripted obstacles rolled forward n_ticks ticks (they do not depend on the
 // egos), their predictions for every tick, and the fused K-tick kernel with the loop glue inside each ego's tick loop.  With
-// traffic sets, the same three by the gridded obstacle kernels, per chunk of traffic_chunk_ticks ticks.
+// traffic sets, the same three per chunk of traffic_chunk_ticks ticks.
 // Otherwise the same ticks as the separate calls a host loop would make.
 extern "C" int jsim_loop_run_scenario(jsim_ctx *ctx, int32_t B, int32_t n_ticks, double *x0, const int32_t *path_id,
                                       int32_t *path_len, const double *speed, int64_t *target_ind, double *oa, double *od,
@@ -2703,14 +2702,8 @@ extern "C" int jsim_loop_run_scenario(jsim_ctx *ctx, int32_t B, int32_t n_ticks,
     for (int k0 = 0; k0 < n_ticks; k0 += chunk) {
         const int nk = std::min(chunk, n_ticks - k0);
         if (n_obs > 0) {
-            const ObsStepP O = obstacle_step_rec_p(ctx, n_obs, 1, obs_state, obs_param, nullptr, tick);
-            if (traffic) {
-                hipLaunchKernelGGL(obstacle_rollout_grid_kernel, dim3((n_obs + 63) / 64), dim3(64), 0, s, O, nk, ctx->d_get_all);
-                launch_obstacle_predict_grid(ctx, n_obs, n_steps, ctx->d_get_all, ctx->d_pred_all, ctx->d_bc_all, nk, s);
-            } else {
-                hipLaunchKernelGGL(obstacle_rollout_kernel, dim3(1), dim3(64), 0, s, O, nk, ctx->d_get_all);
-                launch_obstacle_predict(ctx, n_obs, n_steps, ctx->d_get_all, nullptr, ctx->d_pred_all, ctx->d_bc_all, nk, s);
-            }
+            launch_obstacle_rollout(obstacle_step_rec_p(ctx, n_obs, 1, obs_state, obs_param, nullptr, tick), nk, ctx->d_get_all, s);
+            launch_obstacle_predict(ctx, n_obs, n_steps, ctx->d_get_all, nullptr, ctx->d_pred_all, ctx->d_bc_all, nk, s);
             // the last get() tuples, as after nk host ticks
             HIP_TRY(ctx, hipMemcpyAsync(obs_get, ctx->d_get_all + (size_t)(nk - 1) * n_obs * 6, sizeof(double) * n_obs * 6,
                                         hipMemcpyDeviceToDevice, s));

@@ -24,14 +24,12 @@ struct ObsP {
     double2 *pred_cc;   // [n_obs][n_steps][2]  circle centres
     double4 *pred_bc;   // [n_obs] (x, y, r, -): a circle around ALL predicted circle centres of the obstacle (inflated beyond
                         // rounding): an ego whose own circles stay clear of it skips the obstacle's collision rows
-    // blockIdx.x = tick of a K-tick batch: obst, pred_cc and pred_bc advance by one tick's worth per block (pred is per call only)
+    // blockIdx.y = tick of a K-tick batch: obst, pred_cc and pred_bc advance by one tick's worth per tick (pred is per call only)
     const double4 *shape; // [n_obs] (cc0, cc1, radius, L) of each vehicle (jsim_loop_set_vehicle_shapes), NULL: L, cc0, cc1 above for all
 };
 
 // lib/moving_obstacles_prediction.py:21-47 (yaw uses the UPDATED speed), circle centres lib/trajectories.py:11-37.  Obstacle o
-// of tick t: obst, pred_cc and pred_bc advance by one tick's worth (P.n_obs obstacles) per tick, pred is per call only.  The
-// body of obstacle_predict_kernel and of its gridded counterpart obstacle_predict_grid_kernel: the same arithmetic, operation
-// for operation.
+// of tick t: obst, pred_cc and pred_bc advance by one tick's worth (P.n_obs obstacles) per tick, pred is per call only.
 __device__ __forceinline__ void obstacle_predict_one(const ObsP &P, int o, int t)
 {
     const double *ob = P.obst + (size_t)t * P.n_obs * 6;
@@ -71,17 +69,10 @@ __device__ __forceinline__ void obstacle_predict_one(const ObsP &P, int o, int t
 }
 
 #ifndef JSIM_KERNEL_TU /* (a kernel translation unit of the split build holds the register kernels only) */
-// one block per tick, one thread per obstacle (n_obs <= JSIM_MAX_OBS)
+// Grid (ceil(n_obs / 64), ticks), one thread per (tick, vehicle): one block per tick for the n_obs <= JSIM_MAX_OBS vehicles of a
+// run without traffic sets, many for the vehicles of all sets (jsim_loop_set_traffic, P.n_obs = their total).  Each thread is a
+// serial chain of n_steps fp64 sin / cos, like ego_predict_kernel: one wave per block.
 __global__ __launch_bounds__(64) void obstacle_predict_kernel(ObsP P)
-{
-    const int o = threadIdx.x;
-    if (o >= P.n_obs) return;
-    obstacle_predict_one(P, o, blockIdx.x);
-}
-
-// The vehicles of all traffic sets (jsim_loop_set_traffic), P.n_obs = their total: grid (ceil(total / 64), ticks), one thread
-// per (tick, vehicle).  Each thread is a serial chain of n_steps fp64 sin / cos, like ego_predict_kernel: one wave per block.
-__global__ __launch_bounds__(64) void obstacle_predict_grid_kernel(ObsP P)
 {
     const int o = blockIdx.x * 64 + threadIdx.x;
     if (o >= P.n_obs) return;
@@ -554,7 +545,8 @@ __global__ __launch_bounds__(64) void group_pre_tick_kernel(PreP P, GroupP G, Tr
 // Scripted obstacle vehicles of the reference scenarios (main/lib/moving_obstacles.py): MovingObstacleTIntersection (:166-232,
 // kind 0), MovingObstacleRoundabout (:28-124, kind 1) and MovingObstacleArterial (:126-164, kind 2).  State (xc, yc, theta,
 // counter) advanced by Bicycle.step with the scripted steering / start-delay rules; the `get()` tuple (x, y, v, yaw, a = 0,
-// steer) is written for the prediction kernel.  One thread per obstacle.
+// steer) is written for the prediction kernel.  One thread per obstacle over ceil(n_obs / 64) blocks: one block without traffic
+// sets (n_obs <= JSIM_MAX_OBS), many for the vehicles of all sets (P.n_obs = their total, tens of thousands).
 struct ObsStepP {
     int n_obs, do_step;
     double L;             // wheelbase of every vehicle without a shape table
@@ -650,41 +642,15 @@ __device__ __forceinline__ void obstacle_record(const ObsStepP &P, int o)
 #ifndef JSIM_KERNEL_TU /* (a kernel translation unit of the split build holds the register kernels only) */
 __global__ __launch_bounds__(64) void obstacle_step_kernel(ObsStepP P)
 {
-    const int o = threadIdx.x;
-    if (o >= P.n_obs) return;
-    obstacle_step_one(P, o);
-    obstacle_record(P, o);
-}
-#endif
-
-// n_ticks ticks of the loop's two calls per tick -- get() ahead of the prediction, then get() + step() (ScenarioLoop.tick) --
-// for scripted obstacles, which do not depend on the egos: the get() tuples of every tick go to get_all [n_ticks][n_obs][6].
-#ifndef JSIM_KERNEL_TU /* (a kernel translation unit of the split build holds the register kernels only) */
-__global__ __launch_bounds__(64) void obstacle_rollout_kernel(ObsStepP P, int n_ticks, double *get_all)
-{
-    const int o = threadIdx.x;
-    if (o >= P.n_obs) return;
-    for (int k = 0; k < n_ticks; ++k) {
-        ObsStepP Q = P;
-        Q.do_step = 0; Q.get = get_all + (size_t)k * P.n_obs * 6;
-        obstacle_step_one(Q, o);
-        Q.do_step = 1; Q.get = obstacle_rec_slot(P, k);
-        obstacle_step_one(Q, o);
-    }
-}
-
-// The gridded counterparts for the vehicles of all traffic sets (P.n_obs = their total, tens of thousands): one thread per
-// vehicle over ceil(total / 64) blocks, the same obstacle_step_one.  obstacle_step_grid_kernel is obstacle_step_kernel (one
-// get() or get() + step() per call), obstacle_rollout_grid_kernel is obstacle_rollout_kernel.
-__global__ __launch_bounds__(64) void obstacle_step_grid_kernel(ObsStepP P)
-{
     const int o = blockIdx.x * 64 + threadIdx.x;
     if (o >= P.n_obs) return;
     obstacle_step_one(P, o);
     obstacle_record(P, o);
 }
 
-__global__ __launch_bounds__(64) void obstacle_rollout_grid_kernel(ObsStepP P, int n_ticks, double *get_all)
+// n_ticks ticks of the loop's two calls per tick -- get() ahead of the prediction, then get() + step() (ScenarioLoop.tick) --
+// for scripted obstacles, which do not depend on the egos: the get() tuples of every tick go to get_all [n_ticks][n_obs][6].
+__global__ __launch_bounds__(64) void obstacle_rollout_kernel(ObsStepP P, int n_ticks, double *get_all)
 {
     const int o = blockIdx.x * 64 + threadIdx.x;
     if (o >= P.n_obs) return;
