@@ -38,7 +38,7 @@ EXPORTS = (
     "jsim_loop_set_groups", "jsim_loop_predict_egos", "jsim_loop_run_interacting",
     "jsim_loop_set_traffic", "jsim_loop_set_recorder", "jsim_loop_set_vehicle_shapes",
     "jsim_comm_unique_id", "jsim_comm_init", "jsim_mpc_gather", "jsim_comm_destroy", "jsim_plan_routes",
-    "jsim_plan_routes_weighted", "jsim_score_trajectories",
+    "jsim_plan_routes_weighted", "jsim_score_trajectories", "jsim_loop_eval_reasons",
 )
 
 _lib = None
@@ -139,6 +139,9 @@ def load() -> C.CDLL:
     lib.jsim_score_trajectories.restype = C.c_int
     #                                      dev  S    cand_off pt_off pts mode time_from ego cyc now par  W    w   form ideal  outs
     lib.jsim_score_trajectories.argtypes = [i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp] + [vp] * 8
+    lib.jsim_loop_eval_reasons.restype = C.c_int
+    #                                     ctx B    ticks rec flags n_obs obs_rec x_first x_spawn veh_of par threshold carry  outs      stream
+    lib.jsim_loop_eval_reasons.argtypes = [vp, i32, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp] + [vp] * 4 + [vp]
     if lib.jsim_abi_version() != ABI_VERSION:
         raise JsimError(f"libjsim_mpc.so ABI {lib.jsim_abi_version()} != binding ABI {ABI_VERSION}")
     _lib = lib

@@ -36,6 +36,7 @@ class Recorder:
         self._obs = torch.zeros(self.cap + 1, self.n_obs, 6, dtype=torch.float64, device=dev) if self.n_obs > 0 else None
         self.obs = self._obs[: self.cap] if self._obs is not None else None
         self.x0_first = loop.x0.clone()
+        self.traffic = eng.traffic_layout  # (set_of, obs_off) of the loop's traffic sets, or None: whose vehicle is whose
         self.superseded = False          # set when a later loop on the same engine registers its own recorder (or none)
         _register_recorder(eng, self)
 
@@ -75,6 +76,52 @@ class Recorder:
 
     def episodes(self):
         return history.episodes(self.flags[: self._n()].cpu().numpy())
+
+    def default_cyclist(self) -> np.ndarray:
+        """Each ego's moving_obstacles[0] among the recorded vehicles ([B] int32): vehicle 0 of a shared list, the first vehicle of
+        the ego's own set under a traffic layout, -1 for an ego whose set is empty."""
+        B = self.loop.eng.B
+        if self.traffic is None:
+            return np.zeros(B, dtype=np.int32)
+        set_of, obs_off = self.traffic
+        return np.where(obs_off[set_of + 1] > obs_off[set_of], obs_off[set_of], -1).astype(np.int32)
+
+    def reasons(self, par=None, threshold=0.7, cyclist=None, carry=None) -> dict:
+        """The stakeholder reasons of every recorded tick and the replan trigger (jsim_loop_eval_reasons):
+        what evaluate_reasons and reasons_evaluation of main/scenarios/overtaking_cyclist_bidirectional_road.py (:2007-2027,
+        :1907-1940) give when called in the loop, computed in one launch from the records.
+
+        par: one reasons.par_row or [B] rows (default: the reference's values with DT = the loop's sample time); threshold: one
+        number or [B] (ReasonParameters.REASONS_THRESHOLD); cyclist: the recorded vehicle that is each ego's moving_obstacles[0],
+        one index or [B], -1 = none (default: default_cyclist()); carry: [B][3] = time_elapsed_driver, time_passed_cyclist and the
+        replan tracker (0 / 1) the first recorded tick starts from (default: zeros).
+        Returns numpy arrays: policymaker, driver, cyclist, distance [n][B]; timers [n][B][2]; replan [n][B] bool; below [n][B][3]
+        bool (policymaker, driver, cyclist under the threshold); first_replan [B] (-1: none); carry [B][3] as the next tick would
+        meet it; and the par, threshold and veh_of used.  An ego without a cyclist has NaN in driver, cyclist and distance and
+        never triggers on them.  ValueError: no vehicles recorded, a bad par / threshold / carry, a cyclist index out of range."""
+        from . import reasons as _reasons
+        eng = self.loop.eng
+        B = eng.B
+        if self.obs is None:
+            raise ValueError("this recorder holds no vehicle records (a loop without scripted vehicles): there is no cyclist to evaluate")
+        par, thr, veh, car = _reasons.tick_inputs(B, self.n_obs, eng.dt, par, threshold, cyclist, carry, self.default_cyclist)
+        n = self._n()
+        dev = eng.device
+        up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(dev)
+        d_par, d_thr, d_veh, d_car = up(par, np.float64), up(thr, np.float64), up(veh, np.int32), up(car, np.float64)
+        val = torch.empty(max(n, 1), B, 4, dtype=torch.float64, device=dev)[:n]   # (no ticks yet: still valid pointers)
+        tim = torch.empty(max(n, 1), B, 2, dtype=torch.float64, device=dev)[:n]
+        trig = torch.empty(max(n, 1), B, dtype=torch.int32, device=dev)[:n]
+        first = torch.full((B,), -1, dtype=torch.int32, device=dev)
+        _cabi.check(eng.lib.jsim_loop_eval_reasons(eng._ctx, B, n, _ptr(self.rec), _ptr(self.flags), self.n_obs, _ptr(self.obs),
+                                                   _ptr(self.x0_first), _ptr(self.loop.x0_spawn), _ptr(d_veh), _ptr(d_par), _ptr(d_thr),
+                                                   _ptr(d_car), _ptr(val), _ptr(tim), _ptr(trig), _ptr(first), eng._stream()),
+                    eng._ctx, "jsim_loop_eval_reasons")
+        val, trig = val.cpu().numpy(), trig.cpu().numpy()
+        return {"policymaker": val[:, :, 0], "driver": val[:, :, 1], "cyclist": val[:, :, 2], "distance": val[:, :, 3],
+                "timers": tim.cpu().numpy(), "replan": (trig & 1) != 0, "below": ((trig[:, :, None] >> np.arange(1, 4)) & 1) != 0,
+                "first_replan": first.cpu().numpy(), "carry": d_car.cpu().numpy(), "par": np.array(par), "threshold": np.array(thr),
+                "veh_of": np.array(veh, dtype=np.int32)}
 
 
 def _register_recorder(engine: BatchedMPC, rec: Optional[Recorder]):

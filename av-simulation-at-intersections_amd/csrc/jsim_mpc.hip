@@ -2261,6 +2261,32 @@ extern "C" int jsim_score_trajectories(int device_id, int32_t n_sit, const int32
     return D.result(who);
 }
 
+#include "reasons_ticks.inc"
+
+// Stakeholder reasons per recorded tick and the replan trigger: DEVICE pointers, the recorder's buffers as
+// they are; one launch on `stream`, one wavefront per ego.
+extern "C" int jsim_loop_eval_reasons(jsim_ctx *ctx, int32_t B, int32_t n_ticks, const double *rec, const int32_t *flags, int32_t n_obs,
+                                      const double *obs_rec, const double *x_first, const double *x_spawn, const int32_t *veh_of,
+                                      const double *par, const double *threshold, double *carry, double *val, double *timers,
+                                      int32_t *trig, int32_t *first, void *stream)
+{
+    const char *const F = "jsim_loop_eval_reasons";
+    // (the argument checks come first: they need no context and no device)
+    if (B < 0 || n_ticks < 0) return fail(ctx, -22, "%s: B=%d n_ticks=%d", F, B, n_ticks);
+    if (obs_rec && n_obs < 1) return fail(ctx, -22, "%s: obs_rec given with n_obs=%d", F, n_obs);
+    if (!rec || !flags || !x_first || !x_spawn || !veh_of || !par || !threshold || !carry || !val || !timers || !trig || !first)
+        return fail(ctx, -22, "%s: null device pointer", F);
+    if (!ctx) return fail(nullptr, -22, "%s: null ctx", F);
+    if (B == 0 || n_ticks == 0) return 0;
+    DeviceGuard dev_guard(ctx->device);
+    JSIM_GUARD_OK(ctx);
+    const ReasonTickP P = {B, n_ticks, obs_rec ? n_obs : 0, rec, flags, obs_rec, x_first, x_spawn, veh_of, par, threshold,
+                           carry, val, timers, trig, first};
+    hipLaunchKernelGGL(reason_ticks_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, P);
+    HIP_TRY(ctx, hipGetLastError());
+    return 0;
+}
+
 // the shape table's (thr, thr_sq) rows: check_collision_moving_bicycle's min_distance = the egos' radius + the vehicle's own
 static int upload_shape_thresholds(jsim_ctx *ctx)
 {

@@ -2,7 +2,7 @@
 main/lib/simulation.py:50-88, and `obstacles_positions`, main/scenarios/mpc_intersection.py:95-96,159-161), rebuilt from what
 the device recorder wrote (jsim_loop_set_recorder): rec [n][B][7] = x, y, yaw, v, delta, a, xref_deviation per tick, flags
 [n][B] (FAILED / GOAL / AGE bits), obs [n][n_obs][6] = the scripted vehicles' get() tuples.  Pure numpy: the host-side half of
-the recorder, testable without a device."""
+the recorder, testable without a device.  reason_series does the same for the per-tick stakeholder reasons."""
 from __future__ import annotations
 
 from typing import List, Optional
@@ -97,3 +97,23 @@ def obstacle_positions(obs: Optional[np.ndarray], first_tick: int = 0):
 def recorded_ticks(ticks_run: int, cap: int):
     """(ticks held by a recorder of capacity cap after ticks_run ticks, whether ticks were dropped)."""
     return min(int(ticks_run), int(cap)), int(ticks_run) > int(cap)
+
+
+def reason_series(values: dict, flags: np.ndarray, dt: float):
+    """The four lists the overtaking script keeps per run (main/scenarios/overtaking_cyclist_bidirectional_road.py:54-60,
+    :2447-2451: time_values, reasons_policymaker_values, reasons_driver_values, reasons_cyclist_values), per ego and episode, from
+    the per-tick values of a recorder (Recorder.reasons: `policymaker`, `driver`, `cyclist` [n][B]) and its flags [n][B], split
+    where ego_histories splits (episode_bounds).  time_values is i * dt for tick i of the episode, as the script computes it.
+    Returns a list over egos of lists over episodes of dicts of Python float lists."""
+    f = np.asarray(flags).reshape(np.shape(flags)[0], -1)
+    names = (("reasons_policymaker_values", "policymaker"), ("reasons_driver_values", "driver"), ("reasons_cyclist_values", "cyclist"))
+    out = []
+    for b in range(f.shape[1]):
+        eps = []
+        for k0, k1, _ in episode_bounds(f[:, b]):
+            ep = {"time_values": [i * float(dt) for i in range(k1 - k0)]}
+            for key, src in names:
+                ep[key] = np.asarray(values[src], dtype=np.float64)[k0:k1, b].tolist()
+            eps.append(ep)
+        out.append(eps)
+    return out

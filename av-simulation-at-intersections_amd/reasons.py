@@ -5,7 +5,11 @@ run_all: create_following_trajectory (:410-445), evaluate_trajectories_for_reaso
 (:1641-1864), generate_stakeholder_weight_table (:1431-1604) with balance_function (:1191-1231) and compute_predicted_trajectory
 (:244-266), with the same arguments and return shapes.  Every evaluation is ONE launch of the HIP kernel, the whole weight table
 included; score_situations is the batched entry for many situations at once.  There is no CPU path: without the HIP library or a
-HIP device the calls raise."""
+HIP device the calls raise.
+
+The per-tick half of the same study -- evaluate_reasons (:2007-2027) and the replan trigger reasons_evaluation (:1907-1940) -- is
+evaluated from a loop's recorder (closed_loop.Recorder.reasons, jsim_loop_eval_reasons); tick_inputs checks
+its arguments and situation_at turns one of its ticks into a situation for score_situations."""
 from __future__ import annotations
 
 import csv
@@ -253,3 +257,54 @@ def generate_stakeholder_weight_table(trajectories_full, moving_obstacles, state
             wr.writerow(["policy_w", "driver_w", "cyclist_w", "Traj 0", "Traj 1", "Traj 2", "Traj 3", "best_traj_label"])
             wr.writerows(policy_data + driver_data + cyclist_data)
     return policy_data, driver_data, cyclist_data
+
+
+# ---- per-tick reasons of a recorded run (jsim_loop_eval_reasons): the host side of Recorder.reasons ----
+def tick_inputs(B, n_obs, dt, par=None, threshold=0.7, cyclist=None, carry=None, default_cyclist=None):
+    """Recorder.reasons' arguments as the arrays the C call takes: par [B][12], threshold [B], veh_of [B] int32, carry [B][3].
+    What the C call cannot check without a device read is refused here (ValueError): a par that is not one row or [B] rows of
+    finite numbers, DT <= 0, a threshold or carry that is not finite or of the wrong shape, a cyclist outside -1 .. n_obs - 1."""
+    par = np.asarray(par_row(dt=dt) if par is None else par, dtype=np.float64)
+    if par.ndim == 1:
+        par = np.broadcast_to(par, (B, par.size))
+    if par.shape != (B, len(PAR_NAMES)) or not np.isfinite(par).all():
+        raise ValueError(f"par must be one row or [{B}] rows of {len(PAR_NAMES)} finite numbers (reasons.par_row)")
+    if not (par[:, 0] > 0.0).all():
+        raise ValueError("par: DT must be positive")
+    thr = np.asarray(threshold, dtype=np.float64)
+    thr = np.broadcast_to(thr, (B,)) if thr.ndim == 0 else thr
+    if thr.shape != (B,) or not np.isfinite(thr).all():
+        raise ValueError(f"threshold must be one finite number or [{B}]")
+    veh = (default_cyclist() if default_cyclist is not None else np.zeros(B, dtype=np.int32)) if cyclist is None else np.asarray(cyclist)
+    veh = np.broadcast_to(veh, (B,)) if veh.ndim == 0 else veh
+    if veh.shape != (B,) or not np.issubdtype(veh.dtype, np.integer) or veh.min(initial=0) < -1 or veh.max(initial=-1) >= n_obs:
+        raise ValueError(f"cyclist must be one vehicle index or [{B}], each -1 (none) or 0..{n_obs - 1}")
+    car = np.zeros((B, 3)) if carry is None else np.asarray(carry, dtype=np.float64)
+    if car.shape != (B, 3) or not np.isfinite(car).all():
+        raise ValueError(f"carry must be [{B}][3] finite numbers")
+    return np.array(par), np.array(thr), np.array(veh, dtype=np.int32), np.array(car)
+
+
+def situation_at(recorder, b: int, k: int, candidates, reasons=None, **layout) -> dict:
+    """The situation (score_situations) of ego b at the start of recorded tick k, from a loop's recorder: `ego` (x, y, yaw, v) is the
+    state the tick started from, `cyclist` the recorded get() tuple of the ego's cyclist, `now` that tick's three values and two
+    timers, `par` the row they were evaluated with -- what perform_replan is handed when the trigger fires on tick k
+    (main/scenarios/overtaking_cyclist_bidirectional_road.py:149-161).  reasons: the dict of recorder.reasons() (evaluated with
+    its defaults when None); layout: `modes` / `time_from` of the candidates when they are not the reference's list."""
+    r = recorder.reasons() if reasons is None else reasons
+    n = r["policymaker"].shape[0]
+    if not (0 <= k < n) or not (0 <= b < r["policymaker"].shape[1]):
+        raise ValueError(f"ego {b}, tick {k}: the evaluation holds {n} ticks of {r['policymaker'].shape[1]} egos")
+    veh = int(r["veh_of"][b])
+    if veh < 0:
+        raise ValueError(f"ego {b} has no cyclist")
+    fl = int(recorder.flags[k - 1, b].item()) if k > 0 else 0
+    if k == 0 or fl & 6:                                      # (JSIM_REC_GOAL | JSIM_REC_AGE: the tick starts at the spawn state)
+        x, y, v, yaw = (recorder.x0_first if k == 0 else recorder.loop.x0_spawn)[b].cpu().numpy().tolist()
+    else:
+        x, y, yaw, v = recorder.rec[k - 1, b, :4].cpu().numpy().tolist()
+    sit = {"candidates": list(candidates), "ego": (x, y, yaw, v), "cyclist": tuple(recorder.obs[k, veh].cpu().numpy().tolist()),
+           "now": (float(r["policymaker"][k, b]), float(r["driver"][k, b]), float(r["cyclist"][k, b]), float(r["timers"][k, b, 0]),
+                   float(r["timers"][k, b, 1])), "par": np.array(r["par"][b])}
+    sit.update(layout)
+    return sit

@@ -384,6 +384,36 @@ int jsim_score_trajectories(int device_id, int32_t n_sit, const int32_t *cand_of
                             int32_t *status, int32_t *n_samples, double *ct, double *avg, double *scores, int32_t *best,
                             double *detail, double *resampled);
 
+/* ---- stakeholder reasons per recorded tick, and the replan trigger: one pass over the History recorder's buffers ----
+ * Replaces what the loop of main/scenarios/overtaking_cyclist_bidirectional_road.py does once per tick: evaluate_reasons (:127-128,
+ * :2007-2027, with evaluate_distance_to_centerline, evaluate_time_following and evaluate_distance_to_obstacle of
+ * lib/reasons_evaluation.py inside) and the replan trigger reasons_evaluation (:141-142, :1907-1940), and so the three series
+ * save_vehicle_data (:2486) writes.  Both read only the ego's (x, y) at the start of the tick, moving_obstacles[0].get()[:2] ahead of
+ * its step(), and two timers and one flag carried from the tick before: all of it is in the recorder (jsim_loop_set_recorder), so the
+ * evaluation runs after the loop, on any stretch of recorded ticks.  One wavefront per ego, 64 ticks at a time; the timers are the
+ * reference's additions (one `+ DT` per in-range tick, in order).  DEVICE pointers; one launch on `stream`.
+ *   rec [n_ticks][B][7], flags [n_ticks][B], obs_rec [n_ticks][n_obs][6] (NULL: no ego has a cyclist): the recorder's buffers.
+ *   x_first [B][4], x_spawn [B][4] (the MPC's order x, y, v, yaw): each ego's state at the start of tick 0 and its respawn state.
+ *   The ego's position at the start of tick k is x_first (k = 0), x_spawn (flags[k - 1] has JSIM_REC_GOAL or JSIM_REC_AGE: the tick
+ *   starts an episode) or rec[k - 1].  veh_of [B]: the vehicle of obs_rec that is the ego's moving_obstacles[0]; -1: none -- then
+ *   the driver and cyclist values and the distance are NaN, the timers never advance, the policymaker value is still evaluated, and
+ *   NaN never triggers.  par [B][JSIM_REASON_NPAR]: the rows of jsim_score_trajectories; DT, the centreline, the width and the six
+ *   range / threshold entries are read.  threshold [B]: ReasonParameters.REASONS_THRESHOLD (0.7 in the reference).
+ *   carry [B][3], in and out: time_elapsed_driver, time_passed_cyclist and replan_tracker (0 / 1) as the next tick meets them, so
+ *   that a long run can be evaluated in pieces (x_first is then the state the piece starts from).  An episode's first tick starts
+ *   from timers of 0 and a tracker of False, and so does the carry behind a last record that ended its episode.
+ *   Out: val [n_ticks][B][4] = policymaker, driver, cyclist, distance; timers [n_ticks][B][2] = the two timers after the tick;
+ *   trig [n_ticks][B]: bit 0 = replan_needed, bits 1-3 = policymaker / driver / cyclist below the threshold (the names the
+ *   reference logs); first [B] = the first tick with replan_needed, or -1.
+ *   Refused (-22) before any device call: B < 0, n_ticks < 0, obs_rec given with n_obs < 1, a null pointer other than obs_rec and
+ *   stream, a null ctx.  n_ticks = 0 or B = 0 returns 0 and writes nothing (carry unchanged).  A veh_of >= n_obs and a DT that is not
+ *   finite and positive would need a device read to detect: the Python surface (Recorder.reasons) refuses them with ValueError; the
+ *   kernel treats such a veh_of as -1 and otherwise computes with what it is given. */
+int jsim_loop_eval_reasons(jsim_ctx *ctx, int32_t B, int32_t n_ticks, const double *rec, const int32_t *flags, int32_t n_obs,
+                           const double *obs_rec, const double *x_first, const double *x_spawn, const int32_t *veh_of,
+                           const double *par, const double *threshold, double *carry, double *val, double *timers, int32_t *trig,
+                           int32_t *first, void *stream);
+
 /* ---- the job's one exchange: the final trajectory gather over RCCL / xGMI ----
  * The reference has no multi-process code at all (its only multi-ego code is the serial Python loop of
  * main/scenarios/interactive_mpc.py:119-172); egos are independent (main/lib/mpc.py:141-211), so ranks own contiguous shards
