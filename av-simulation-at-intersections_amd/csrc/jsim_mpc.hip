@@ -78,6 +78,7 @@ struct KP {
     double jerkw; // acceleration-state variant (main/lib/mpc_jerk.py, n = 2T + 1): jerk_penalty_weight
     const double2 *pxy;
     const double *pyaw;
+    const double4 *ptrig; // per path point {cos, sin}(yaw + pi/2), {cos, sin}(yaw): S3's weights (jsim_mpc_set_paths), or NULL (S3 evaluates them)
     const double *pcv;   // per-point speed reference of the mpc_with_speed variant, or NULL (xref[2] = 0, mpc.py:107)
     const int *cv_cut;   // [B] index from which that reference is zeroed, or NULL
     const double *pe;    // [B][JSIM_EGO_CFG_DOUBLES] per-ego weights / limits (jsim_mpc_set_ego_config), or NULL
@@ -1343,6 +1344,7 @@ struct jsim_ctx {
     int device = 0;
     DevArray<double2> d_pxy;
     DevArray<double> d_pyaw;
+    DevArray<double4> d_ptrig;     // [n_points] the path yaws' trig (path_trig_kernel); unallocated under JSIM_PATH_TRIG=0
     DevArray<long long> d_poff;
     int n_paths = 0;
     long long n_points = 0;
@@ -1534,7 +1536,7 @@ extern "C" int jsim_mpc_create(const jsim_cfg *cfg, int device_id, jsim_ctx **ou
 
 static void free_paths(jsim_ctx *c)
 {
-    c->d_pxy.release(); c->d_pyaw.release(); c->d_poff.release(); c->d_pcc.release(); c->d_pcv.release();
+    c->d_pxy.release(); c->d_pyaw.release(); c->d_ptrig.release(); c->d_poff.release(); c->d_pcc.release(); c->d_pcv.release();
     delete[] c->h_cx; delete[] c->h_cy; delete[] c->h_cyaw;
     c->h_cx = c->h_cy = c->h_cyaw = nullptr;
     c->n_paths = 0; c->n_points = 0;
@@ -1567,6 +1569,19 @@ static int upload_circle_centres(jsim_ctx *ctx)
     return 0;
 }
 
+// The trig of S3's tracking weights, once per path table instead of once per tick and lane: the same two sincos calls on the same
+// expressions as the register kernels' own (their ptrig == NULL branch), so the table holds their values bit for bit.
+__global__ __launch_bounds__(256) void path_trig_kernel(const double *pyaw, double4 *ptrig, long long n)
+{
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const double yawr = pyaw[i];
+    const double a1 = yawr + 0.5 * M_PI;
+    double c1, s1, c2, s2;
+    sincos(a1, &s1, &c1); sincos(yawr, &s2, &c2);
+    ptrig[i] = double4{c1, s1, c2, s2};
+}
+
 extern "C" int jsim_mpc_set_paths(jsim_ctx *ctx, const double *cx, const double *cy, const double *cyaw,
                                   const int64_t *path_off, int32_t n_paths)
 {
@@ -1590,6 +1605,15 @@ extern "C" int jsim_mpc_set_paths(jsim_ctx *ctx, const double *cx, const double 
     if (e == hipSuccess) e = hipMemcpy(ctx->d_pyaw, cyaw, sizeof(double) * N, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(ctx->d_poff, path_off, sizeof(long long) * (n_paths + 1), hipMemcpyHostToDevice);
     delete[] h;
+    const char *pt = getenv("JSIM_PATH_TRIG");   // "0": no table, the kernels evaluate the trig themselves (A/B and test switch)
+    if (e == hipSuccess && !(pt && pt[0] == '0')) {
+        e = ctx->d_ptrig.reserve(N);
+        if (e == hipSuccess) {
+            hipLaunchKernelGGL(path_trig_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, 0, ctx->d_pyaw.p, ctx->d_ptrig.p, N);
+            e = hipGetLastError();
+            if (e == hipSuccess) e = hipDeviceSynchronize();
+        }
+    }
     if (e != hipSuccess) { free_paths(ctx); return fail(ctx, -5, "jsim_mpc_set_paths: %s", hipGetErrorString(e)); }
     ctx->n_paths = n_paths;
     ctx->n_points = N;
@@ -1665,7 +1689,7 @@ static KP fill_kp(const jsim_ctx *ctx, int32_t B, const StepBufs &S)
     P.Re0 = c.R_end[0]; P.Re1 = c.R_end[1];
     P.dmax = c.max_dsteer * c.dt; P.amax = c.max_accel; P.amin = c.max_decel; P.smax = c.max_steer;
     P.vmax_plant = c.max_speed; P.vmin = c.min_speed; P.vref_min = c.min_ref_speed;
-    P.pxy = ctx->d_pxy; P.pyaw = ctx->d_pyaw; P.poff = ctx->d_poff;
+    P.pxy = ctx->d_pxy; P.pyaw = ctx->d_pyaw; P.ptrig = ctx->d_ptrig; P.poff = ctx->d_poff;
     P.pcv = ctx->d_pcv; P.cv_cut = ctx->cv_cut; P.pe = ctx->d_pe;
     P.x0 = S.x0; P.path_id = S.path_id; P.path_len = S.path_len; P.speed = S.speed;
     P.target_ind = (long long *)S.target_ind; P.oa = S.oa; P.od = S.od; P.ox = S.ox; P.oy = S.oy; P.ov = S.ov; P.oyaw = S.oyaw;

@@ -420,6 +420,7 @@ void mpc_step_reg_kernel(const KP Pin, const TickP K, const PreK Q)
     constexpr int PREN = PRE ? (int)((sizeof(PreScratch) + 7) / 8) : 0; // the glue's scratch lives here between two solves
     __shared__ __attribute__((aligned(16))) double HL[HLN > PREN ? HLN : PREN];
     double *const Hm = HL;
+    constexpr bool HCLR = HELP && !LCA; // the helpers clear R while the owner factors (not where the factor's columns lie on top of H)
     double *const Lc = HL + (LCA ? 0 : N * LD); // the factor's columns, unscaled (column k at Lc[k*LDC + .])
     static_assert((N * LD) % 2 == 0, "Lc stays 16-byte aligned");
     __shared__ __attribute__((aligned(16))) double gsv[2 * N]; // Givens (c, s) per column pair, identity outside a sweep
@@ -534,9 +535,23 @@ void mpc_step_reg_kernel(const KP Pin, const TickP K, const PreK Q)
 #undef JSIM_J_WAIT
 #pragma unroll
                 for (int j = 0; j < N; j += 2) *(double2 *)&Jx[lane0 * (N + 2) + j] = double2{Jr[j], Jr[j + 1]};
+            } else if (cmd == HB_JBUILD && HCLR) {
+                // helpers 2 and 3, idle in this phase: the active-set loop's zeroed R, identity rotations and zero pads.  H is dead (the
+                // owner took its rows before it posted the command) and the owner passes the phase's closing barrier before the loop.
+                for (int e = (hwave - 2) * 64 + lane0; e < N * LD; e += 128) Hm[e] = 0.0;
+                if (hwave == 2 && lane0 < N) { gsv[2 * lane0] = 1.0; gsv[2 * lane0 + 1] = 0.0; }
+                if (hwave == 3 && lane0 < 2) { drow[N + lane0] = 0.0; drow2[N + lane0] = 0.0; dzv[N + lane0] = 0.0; vzv[N + lane0] = 0.0; }
             }
             __syncthreads();
         }
+    }
+    // tan of the warm start's clamped steer, lane t: what S2 rolls out with.  Evaluated where the warm start is written (here from the
+    // loaded one, then in S5 on the new solution, whose lane 0 is also the plant step's) and carried from S5 to S2 only.
+    double wtan;
+    {
+        double dc = (P.smax < wd_t) ? P.smax : wd_t;
+        dc = (-P.smax > dc) ? -P.smax : dc;
+        wtan = tan(dc);
     }
     for (int tk = 0; tk < K.n_ticks; ++tk) {
     // WPE = 2 (256 registers): the state carried from tick to tick is the same in every lane -- say so, and it lives in scalar
@@ -571,6 +586,10 @@ void mpc_step_reg_kernel(const KP Pin, const TickP K, const PreK Q)
     int status = JSIM_OK;
     int hp = 0;            // HELP: command / barrier pairs passed in this tick (three per tick)
     bool s2_done = false;  // HELP: the rollout ran inside S1
+    // the plant step's sin / cos of the tick-start yaw are S2's lane 0 (its bth is syaw + T exact zeros, or syaw itself): kept as
+    // uniform values, not in vector registers that would live through the active-set loop
+    double p_sn = 0.0, p_cs = 0.0;
+    bool p_sc = false;     // S2 ran in this tick
     do {
     STAMP(0);
     double bx = sx, by = sy, bv = sv, bth = syaw, sn, cs;   // S2's results (declared here: HELP runs S2 inside S1)
@@ -652,6 +671,7 @@ void mpc_step_reg_kernel(const KP Pin, const TickP K, const PreK Q)
     // ------------------------------------------------------------------ S1: travel -> idx -> xref   (lane t <= T)
     const int tl_idx = lane < T ? lane : T;
     double xr, yr, yawr, vr = 0.0;
+    double4 ytr = double4{0.0, 0.0, 0.0, 0.0}; // {c1, s1, c2, s2} of S3's weights, from the path table's trig (P.ptrig)
     bool rend;
     long long ik;
     {
@@ -673,6 +693,7 @@ void mpc_step_reg_kernel(const KP Pin, const TickP K, const PreK Q)
         if (ik > M - 1) ik = M - 1;
         const double2 pr = P.pxy[off + ik];
         xr = pr.x; yr = pr.y; yawr = P.pyaw[off + ik];
+        if (P.ptrig) ytr = P.ptrig[off + ik]; // (here, not in S3: it rides the round trip of the two loads above)
         rend = (ik == M - 1);
         if (P.pcv) { // mpc_with_speed variant: xref[2] = cv[idx], cv zeroed from the ego's cut-off index on
             const int cut = (PRE && Q.speed_cutoff) ? pre_cut : (P.cv_cut ? P.cv_cut[ego] : -1);
@@ -687,6 +708,7 @@ void mpc_step_reg_kernel(const KP Pin, const TickP K, const PreK Q)
     if (!(HELP && s2_done)) {
 #include "mpc_step_reg_s2.inc"
     }
+    p_sn = rdlane(sn, 0); p_cs = rdlane(cs, 0); p_sc = true;
     if (P.dbg_xbar && lane <= T) {
         double *xb = P.dbg_xbar + (size_t)ego * 4 * (T + 1);
         xb[0 * (T + 1) + lane] = bx; xb[1 * (T + 1) + lane] = by;
@@ -700,7 +722,7 @@ void mpc_step_reg_kernel(const KP Pin, const TickP K, const PreK Q)
     }
     if (status == JSIM_INFEASIBLE) {
         if (tl) { P.oa[(size_t)ego * T + lane] = 0.0; P.od[(size_t)ego * T + lane] = 0.0; }
-        wa_t = 0.0; wd_t = 0.0; s0 = tind;
+        wa_t = 0.0; wd_t = 0.0; wtan = 0.0; s0 = tind;
         if (P.amask && lane < MW) P.amask[(size_t)ego * MW + lane] = 0u;
         if (lane == 0) {
             P.status[ego] = status;
@@ -731,9 +753,11 @@ void mpc_step_reg_kernel(const KP Pin, const TickP K, const PreK Q)
         double Qxx = 0, Qxy = 0, Qyy = 0, qv = 0, qyaw = 0;
         if (lane >= 1 && lane <= T) {
             if (!rend) {
-                const double a1 = yawr + 0.5 * M_PI;
-                double c1, s1, c2, s2;   // (sincos: one argument reduction per angle; the same values as cos() and sin() -- checked bit for bit)
-                sincos(a1, &s1, &c1); sincos(yawr, &s2, &c2);
+                double c1 = ytr.x, s1 = ytr.y, c2 = ytr.z, s2 = ytr.w;
+                if (!P.ptrig) { // no table (JSIM_PATH_TRIG=0): what path_trig_kernel evaluates, here
+                    const double a1 = yawr + 0.5 * M_PI;   // (sincos: one argument reduction per angle; the same values as cos() and sin() -- checked bit for bit)
+                    sincos(a1, &s1, &c1); sincos(yawr, &s2, &c2);
+                }
                 Qxx = (c1 * c1) * P.w_perp + (c2 * c2) * P.w_para;
                 Qxy = (c1 * s1) * P.w_perp + (c2 * s2) * P.w_para;
                 Qyy = (s1 * s1) * P.w_perp + (s2 * s2) * P.w_para;
@@ -1045,9 +1069,11 @@ void mpc_step_reg_kernel(const KP Pin, const TickP K, const PreK Q)
     // (An explicit R^-1 with r = R^-1 d1 as a lane-parallel product was measured: same cost per add, but every drop
     // then pays a second rotation sweep, which is what the slowest egos -- the ones that set the launch time -- do most.)
     double *const Rm = Hm;
-    for (int e = lane; e < N * LD; e += 64) Rm[e] = 0.0;
-    if (lane < N) { gsv[2 * lane] = 1.0; gsv[2 * lane + 1] = 0.0; } // identity rotations outside a sweep
-    if (lane < 2) { drow[N + lane] = 0.0; drow2[N + lane] = 0.0; dzv[N + lane] = 0.0; vzv[N + lane] = 0.0; }
+    if (!HCLR) { // (HCLR: helpers 2 and 3 did this beside the factorisation)
+        for (int e = lane; e < N * LD; e += 64) Rm[e] = 0.0;
+        if (lane < N) { gsv[2 * lane] = 1.0; gsv[2 * lane + 1] = 0.0; } // identity rotations outside a sweep
+        if (lane < 2) { drow[N + lane] = 0.0; drow2[N + lane] = 0.0; dzv[N + lane] = 0.0; vzv[N + lane] = 0.0; }
+    }
     LDS_SYNC();
 
     STAMP(9);
@@ -1090,11 +1116,31 @@ void mpc_step_reg_kernel(const KP Pin, const TickP K, const PreK Q)
     double iw01, iw23, w01, w23; // w = ||Jhat'n||^2 = n'H^-1 n: invariant under the orthogonal column updates of Jhat
     {
         double rn0 = 0.0, rn1 = 0.0, dn0 = 0.0, dn1 = 0.0;
+        if (HELP) {
+            // row lane + 2 straight from the rows helper 1 left in Jx (nothing writes there before the next tick's HB_JBUILD) instead
+            // of one cross-lane shuffle per column: the same operands in the same order.  Lanes without a steer-rate row read their own.
+            const double *const Jn = Jx + (cid2 >= 0 ? lane + 2 : lane) * (N + 2);
+#pragma unroll
+            for (int h = 0; h < N; h += CCH) {
+                double2 nb[CCH / 2];
+#pragma unroll
+                for (int j = h; j < h + CCH && j < N; j += 2) nb[(j - h) / 2] = *(const double2 *)&Jn[j];
+                JSIM_STAGE();
+#pragma unroll
+                for (int j = h; j < h + CCH && j < N; j += 2) {
+                    rn0 = fma(Jr[j], Jr[j], rn0); rn1 = fma(Jr[j + 1], Jr[j + 1], rn1);
+                    const double e0 = nb[(j - h) / 2].x - Jr[j], e1 = nb[(j - h) / 2].y - Jr[j + 1];
+                    dn0 = fma(e0, e0, dn0); dn1 = fma(e1, e1, dn1);
+                }
+                JSIM_STAGE();
+            }
+        } else {
 #pragma unroll
         for (int j = 0; j < N; j += 2) {
             rn0 = fma(Jr[j], Jr[j], rn0); rn1 = fma(Jr[j + 1], Jr[j + 1], rn1);
             const double e0 = __shfl_down(Jr[j], 2) - Jr[j], e1 = __shfl_down(Jr[j + 1], 2) - Jr[j + 1];
             dn0 = fma(e0, e0, dn0); dn1 = fma(e1, e1, dn1);
+        }
         }
         const double rn = rn0 + rn1;
         const double dn = (VS && lane < N && !(lane & 1)) ? spw : dn0 + dn1; // even lanes (VS): their speed row
@@ -1514,7 +1560,7 @@ void mpc_step_reg_kernel(const KP Pin, const TickP K, const PreK Q)
     // ------------------------------------------------------------------ S5: outputs
     if (status != JSIM_OK) {
         if (tl) { P.oa[(size_t)ego * T + lane] = 0.0; P.od[(size_t)ego * T + lane] = 0.0; }
-        wa_t = 0.0; wd_t = 0.0; s0 = tind;
+        wa_t = 0.0; wd_t = 0.0; wtan = 0.0; s0 = tind;
         if (P.amask && lane < MW) P.amask[(size_t)ego * MW + lane] = 0u;
         if (lane == 0) {
             P.status[ego] = status;
@@ -1558,6 +1604,11 @@ void mpc_step_reg_kernel(const KP Pin, const TickP K, const PreK Q)
         const double yy = sy + wexscan_dpp(fma(alp, vt, fma(bep, yt, ccy)), lane);
         if (tl) { P.oa[(size_t)ego * T + lane] = a; P.od[(size_t)ego * T + lane] = dl_; }
         wa_t = a; wd_t = dl_; s0 = tind; // next tick's warm start / remembered index
+        if (K.advance || tk + 1 < K.n_ticks) { // .. and its tan, for the plant step below (lane 0) and the next tick's S2
+            double dc = (P.smax < dl_) ? P.smax : dl_;
+            dc = (-P.smax > dc) ? -P.smax : dc;
+            wtan = tan(dc);
+        }
         a0n = uvec[0]; d0n = uvec[1];
         if (lane <= T) {
             const size_t o = (size_t)ego * (T + 1) + lane;
@@ -1602,8 +1653,15 @@ void mpc_step_reg_kernel(const KP Pin, const TickP K, const PreK Q)
         double dc = (P.smax < di) ? P.smax : di;
         dc = (-P.smax > dc) ? -P.smax : dc;
         double cy_, sy_;
-        sincos(syaw, &sy_, &cy_);
-        const double xd = sv * cy_, yd = sv * sy_, thd = (sv / P.L) * tan(dc);
+        if (p_sc) { // S2's own; sin keeps the sign of a zero, which the zeros added to lane 0's yaw lose
+            sy_ = syaw == 0.0 ? syaw : p_sn; cy_ = p_cs;
+        } else {    // the tick left before S2 (no path, nearest-index anomaly)
+            sincos(syaw, &sy_, &cy_);
+        }
+        double tn_;
+        if (status == JSIM_OK) tn_ = rdlane(wtan, 0); // di is this solve's delta_0: S5 has tan(dc) in lane 0
+        else tn_ = tan(dc);                           // a failed tick steers with the previous di
+        const double xd = sv * cy_, yd = sv * sy_, thd = (sv / P.L) * tn_;
         sx += xd * dt; sy += yd * dt; syaw += thd * dt;
         sv += ai * dt;
         sv = (P.vmax_plant < sv) ? P.vmax_plant : sv;
@@ -1623,7 +1681,7 @@ void mpc_step_reg_kernel(const KP Pin, const TickP K, const PreK Q)
         if (done) {
             sx = K.x0_spawn[4 * ego]; sy = K.x0_spawn[4 * ego + 1]; sv = K.x0_spawn[4 * ego + 2]; syaw = K.x0_spawn[4 * ego + 3];
             s0 = K.target_spawn[ego];
-            wa_t = 0.0; wd_t = 0.0; di_prev = 0.0; ai_last = 0.0; age = 0;
+            wa_t = 0.0; wd_t = 0.0; wtan = 0.0; di_prev = 0.0; ai_last = 0.0; age = 0;
             if (PRE) { pre_idx = 0; pre_prev = -1; } // a fresh run: no progress index, no previous truncated path
             if (tl) { P.oa[(size_t)ego * T + lane] = 0.0; P.od[(size_t)ego * T + lane] = 0.0; }
             if (lane == 0) {

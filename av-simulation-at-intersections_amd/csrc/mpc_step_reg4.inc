@@ -84,7 +84,7 @@ __global__ __launch_bounds__(256, JSIM_REG4_MINW) void mpc_step_reg4_kernel(cons
     __shared__ unsigned maskw[MW + 1];
     // what a lane would otherwise carry through the whole active-set loop in registers it does not have: the warm start of the
     // next tick (identical in the four waves: one copy) and the lane's two steepest-edge weights
-    __shared__ __attribute__((aligned(16))) double wsv[2][T];
+    __shared__ __attribute__((aligned(16))) double wsv[2][T]; // [0]: accelerations, [1]: tan of the clamped steers
     __shared__ __attribute__((aligned(16))) double iwv[2][256];
 
     const int gl0 = threadIdx.x;
@@ -134,7 +134,14 @@ __global__ __launch_bounds__(256, JSIM_REG4_MINW) void mpc_step_reg4_kernel(cons
     long long s0 = uni64(gp(Pv.target_ind)[ego]);
     double sx = gp(Pv.x0)[4 * ego + 0], sy = gp(Pv.x0)[4 * ego + 1], sv = gp(Pv.x0)[4 * ego + 2], syaw = gp(Pv.x0)[4 * ego + 3];
 #define WS_SET(a_, d_) do { if (wave == 0 && tl) { wsv[0][lane] = (a_); wsv[1][lane] = (d_); } } while (0)
-    WS_SET(gp(Pv.oa)[(size_t)ego * T + lane], gp(Pv.od)[(size_t)ego * T + lane]); // warm start, entry t; read back at S2 of every tick
+    // (the steer entries as S2 uses them: tan of the clamped steer, evaluated once where the warm start is written -- here, and in S5 on
+    //  the new solution, whose entry 0 is also the plant step's)
+#define WS_TAN(d_, out_) do { const double sm_ = Pv.smax; double dc_ = (sm_ < (d_)) ? sm_ : (d_); dc_ = (-sm_ > dc_) ? -sm_ : dc_; out_ = tan(dc_); } while (0)
+    {
+        double wt0 = 0.0;
+        if (wave == 0 && tl) { const double od0 = gp(Pv.od)[(size_t)ego * T + lane]; WS_TAN(od0, wt0); }
+        WS_SET(gp(Pv.oa)[(size_t)ego * T + lane], wt0); // warm start, entry t; read back at S2 of every tick
+    }
     __syncthreads();
     double di_prev = advance ? gp(Kv.di_ai)[2 * ego] : 0.0;
     double ai_last = advance ? gp(Kv.di_ai)[2 * ego + 1] : 0.0;
@@ -169,6 +176,9 @@ __global__ __launch_bounds__(256, JSIM_REG4_MINW) void mpc_step_reg4_kernel(cons
     }
     double a0n = 0.0, d0n = 0.0;
     int status = JSIM_OK;
+    double p_sn = 0.0, p_cs = 0.0; // the plant step's sin / cos of the tick-start yaw: S2's lane 0, as uniform values
+    bool p_sc = false;             // S2 ran in this tick
+    double p_tn = 0.0;             // .. and tan of the clamped delta_0 of this tick's solution (S5)
     do {
     STAMP2(0);
     // ------------------------------------------------------------------ S1: nearest index in direction (every wave, redundantly)
@@ -234,6 +244,7 @@ __global__ __launch_bounds__(256, JSIM_REG4_MINW) void mpc_step_reg4_kernel(cons
     // ------------------------------------------------------------------ S1: travel -> idx -> xref   (lane t <= T of each wave)
     const int tl_idx = lane < T ? lane : T;
     double xr, yr, yawr, vr = 0.0;
+    v4d ytr = v4d{0.0, 0.0, 0.0, 0.0}; // {c1, s1, c2, s2} of S3's weights, from the path table's trig (P.ptrig)
     bool rend;
     long long ik;
     {
@@ -255,6 +266,7 @@ __global__ __launch_bounds__(256, JSIM_REG4_MINW) void mpc_step_reg4_kernel(cons
         if (ik > M - 1) ik = M - 1;
         const jsim_d2v pr = ((JSIM_GAS const jsim_d2v *)Pv.pxy)[off + ik];
         xr = pr.x; yr = pr.y; yawr = gp(Pv.pyaw)[off + ik];
+        if (Pv.ptrig) ytr = ((JSIM_GAS const v4d *)Pv.ptrig)[off + ik]; // (here, not in S3: it rides the round trip of the two loads above)
         rend = (ik == M - 1);
         if (Pv.pcv) {
             const int cut = (PRE && Q.speed_cutoff) ? pre_cut : (Pv.cv_cut ? gp(Pv.cv_cut)[ego] : -1);
@@ -269,11 +281,9 @@ __global__ __launch_bounds__(256, JSIM_REG4_MINW) void mpc_step_reg4_kernel(cons
     // ------------------------------------------------------------------ S2: rollout of the warm start
     double bx = sx, by = sy, bv = sv, bth = syaw, sn, cs;
     {
-        const double smax_ = Pv.smax, vmaxp_ = Pv.vmax_plant, vmin_ = Pv.vmin;
-        const double wa_t = tl ? wsv[0][lane] : 0.0, wd_t = tl ? wsv[1][lane] : 0.0;
-        double dc = (smax_ < wd_t) ? smax_ : wd_t;
-        dc = (-smax_ > dc) ? -smax_ : dc;
-        const double tan_t = tan(dc);
+        const double vmaxp_ = Pv.vmax_plant, vmin_ = Pv.vmin;
+        const double wa_t = tl ? wsv[0][lane] : 0.0;
+        const double tan_t = tl ? wsv[1][lane] : 0.0; // tan of the clamped steer, evaluated where the warm start was written
         double vcur = sv;
 #pragma unroll
         for (int j = 0; j < T; ++j) {
@@ -300,6 +310,7 @@ __global__ __launch_bounds__(256, JSIM_REG4_MINW) void mpc_step_reg4_kernel(cons
             if (lane == j + 1) { bx = xcur; by = ycur; }
         }
     }
+    p_sn = rdlane(sn, 0); p_cs = rdlane(cs, 0); p_sc = true;
     if (wave == 0) {
         if (Pv.dbg_xbar && lane <= T) {
             double *xb = Pv.dbg_xbar + (size_t)ego * 4 * (T + 1);
@@ -352,9 +363,11 @@ __global__ __launch_bounds__(256, JSIM_REG4_MINW) void mpc_step_reg4_kernel(cons
         double Qxx = 0, Qxy = 0, Qyy = 0, qv = 0, qyaw = 0;
         if (lane >= 1 && lane <= T) {
             if (!rend) {
-                const double a1 = yawr + 0.5 * M_PI;
-                double c1, s1, c2, s2;   // (sincos: one argument reduction per angle; the same values as cos() and sin() -- checked bit for bit)
-                sincos(a1, &s1, &c1); sincos(yawr, &s2, &c2);
+                double c1 = ytr.x, s1 = ytr.y, c2 = ytr.z, s2 = ytr.w;
+                if (!Pv.ptrig) { // no table (JSIM_PATH_TRIG=0): what path_trig_kernel evaluates, here
+                    const double a1 = yawr + 0.5 * M_PI;   // (sincos: one argument reduction per angle; the same values as cos() and sin() -- checked bit for bit)
+                    sincos(a1, &s1, &c1); sincos(yawr, &s2, &c2);
+                }
                 Qxx = (c1 * c1) * Pv.w_perp + (c2 * c2) * Pv.w_para;
                 Qxy = (c1 * s1) * Pv.w_perp + (c2 * s2) * Pv.w_para;
                 Qyy = (s1 * s1) * Pv.w_perp + (s2 * s2) * Pv.w_para;
@@ -1282,7 +1295,10 @@ __global__ __launch_bounds__(256, JSIM_REG4_MINW) void mpc_step_reg4_kernel(cons
         const double xt = sx + wexscan_dpp(fma(al, vt, fma(be, yt, ccx)), lane);
         const double yy = sy + wexscan_dpp(fma(alp, vt, fma(bep, yt, ccy)), lane);
         if (wave == 0 && tl) { gp(Pv.oa)[(size_t)ego * T + lane] = a; gp(Pv.od)[(size_t)ego * T + lane] = dl_; }
-        WS_SET(a, dl_); s0 = tind;
+        double tn = 0.0; // tan of the new warm start's clamped steer: the next tick's S2, and the plant step below (entry 0)
+        if (advance || tk + 1 < n_ticks) WS_TAN(dl_, tn);
+        p_tn = rdlane(tn, 0);
+        WS_SET(a, tn); s0 = tind;
         a0n = uvec[0]; d0n = uvec[1];
         if (wave == 0 && lane <= T) {
             const size_t o = (size_t)ego * (T + 1) + lane;
@@ -1322,7 +1338,12 @@ __global__ __launch_bounds__(256, JSIM_REG4_MINW) void mpc_step_reg4_kernel(cons
         }
         double dc = (Pv.smax < di) ? Pv.smax : di;
         dc = (-Pv.smax > dc) ? -Pv.smax : dc;
-        const double xd = sv * cos(syaw), yd = sv * sin(syaw), thd = (sv / Pv.L) * tan(dc);
+        double cy_ = p_cs, sy_ = p_sn; // S2's own (lane 0's bth is syaw itself)
+        if (!p_sc) { cy_ = cos(syaw); sy_ = sin(syaw); } // the tick left before S2 (no path, nearest-index anomaly)
+        double tn_;
+        if (status == JSIM_OK) tn_ = p_tn;  // di is this solve's delta_0: S5 evaluated tan(dc)
+        else tn_ = tan(dc);                // a failed tick steers with the previous di
+        const double xd = sv * cy_, yd = sv * sy_, thd = (sv / Pv.L) * tn_;
         sx += xd * dt; sy += yd * dt; syaw += thd * dt;
         sv += ai * dt;
         sv = (Pv.vmax_plant < sv) ? Pv.vmax_plant : sv;
@@ -1370,6 +1391,7 @@ __global__ __launch_bounds__(256, JSIM_REG4_MINW) void mpc_step_reg4_kernel(cons
     }
 #undef LANE_FENCE4
 #undef WS_SET
+#undef WS_TAN
 #undef tl
 #undef SLOT_OF_ROW
 #undef SLOTMAP4

@@ -1,11 +1,9 @@
 // mpc_step_reg_s2.inc -- S2 of the one-wave register kernel: rollout of the warm start from the current state
 // (main/lib/mpc.py:115-129 _predict_motion -> lib/simulation.py:35-47).  Included by mpc_step_reg.inc where the phase runs: after S1
 // in the plain kernels, INSIDE S1 in the HELP instantiations (the owner rolls out while the helper wavefronts scan the path -- the
-// rollout does not need the index).  In: sx, sy, sv, syaw, wa_t, wd_t; out: bx, by, bv, bth (lane t: state at time t), sn, cs.
+// rollout does not need the index).  In: sx, sy, sv, syaw, wa_t, wtan (= tan of the warm start's clamped steer); out: bx, by, bv, bth (lane t: state at time t), sn, cs.
     {
-        double dc = (P.smax < wd_t) ? P.smax : wd_t;
-        dc = (-P.smax > dc) ? -P.smax : dc;
-        const double tan_t = tan(dc);
+        const double tan_t = wtan; // tan of the clamped steer, evaluated where the warm start was written
         double vcur = sv;
 #pragma unroll
         for (int j = 0; j < T; ++j) {

@@ -87,7 +87,9 @@ const char *jsim_last_error(const jsim_ctx *ctx);
 int jsim_mpc_create(const jsim_cfg *cfg, int device_id, jsim_ctx **out);
 void jsim_mpc_destroy(jsim_ctx *ctx);
 
-/* HOST pointers.  cyaw must already be smoothed (MPC.__init__ does it on the host, in place). */
+/* HOST pointers.  cyaw must already be smoothed (MPC.__init__ does it on the host, in place).  Also fills the context's table of
+ * the yaws' sin / cos (32 B per point; the register kernels read it instead of evaluating them in every tick -- same values);
+ * JSIM_PATH_TRIG=0 in the environment at the time of the call leaves it out.  Synchronises the device. */
 int jsim_mpc_set_paths(jsim_ctx *ctx, const double *cx, const double *cy, const double *cyaw,
                        const int64_t *path_off /*[n_paths+1]*/, int32_t n_paths);
 
