@@ -38,7 +38,7 @@ EXPORTS = (
     "jsim_loop_set_groups", "jsim_loop_predict_egos", "jsim_loop_run_interacting",
     "jsim_loop_set_traffic", "jsim_loop_set_recorder", "jsim_loop_set_vehicle_shapes",
     "jsim_comm_unique_id", "jsim_comm_init", "jsim_mpc_gather", "jsim_comm_destroy", "jsim_plan_routes",
-    "jsim_plan_routes_weighted", "jsim_score_trajectories", "jsim_loop_eval_reasons",
+    "jsim_plan_routes_weighted", "jsim_score_trajectories", "jsim_loop_eval_reasons", "jsim_loop_eval_conflicts",
 )
 
 _lib = None
@@ -142,6 +142,9 @@ def load() -> C.CDLL:
     lib.jsim_loop_eval_reasons.restype = C.c_int
     #                                     ctx B    ticks rec flags n_obs obs_rec x_first x_spawn veh_of par threshold carry  outs      stream
     lib.jsim_loop_eval_reasons.argtypes = [vp, i32, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp] + [vp] * 4 + [vp]
+    lib.jsim_loop_eval_conflicts.restype = C.c_int
+    #                                       ctx B    ticks rec flags n_obs obs_rec x_first x_spawn veh_range mate_range shapes ego_shape w  outs  stream
+    lib.jsim_loop_eval_conflicts.argtypes = [vp, i32, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, i32] + [vp] * 6 + [vp]
     if lib.jsim_abi_version() != ABI_VERSION:
         raise JsimError(f"libjsim_mpc.so ABI {lib.jsim_abi_version()} != binding ABI {ABI_VERSION}")
     _lib = lib

@@ -24,7 +24,7 @@ class Recorder:
     histories(b): lib.simulation.History objects, one per episode of ego b; obstacle_positions(): the scripts'
     obstacles_positions; episodes(): per-ego episode counts, lengths and ends.  These synchronise (device -> host copies)."""
 
-    def __init__(self, loop: "ClosedLoop", cap: int, n_obs: int = 0):
+    def __init__(self, loop: "ClosedLoop", cap: int, n_obs: int = 0, groups=None):
         eng = loop.eng
         if cap < 1:
             raise ValueError("record must be a positive number of ticks")
@@ -37,6 +37,7 @@ class Recorder:
         self.obs = self._obs[: self.cap] if self._obs is not None else None
         self.x0_first = loop.x0.clone()
         self.traffic = eng.traffic_layout  # (set_of, obs_off) of the loop's traffic sets, or None: whose vehicle is whose
+        self.groups = None if groups is None else np.array(groups, dtype=np.int32)   # InteractingLoop's group offsets: whose mate is who
         self.superseded = False          # set when a later loop on the same engine registers its own recorder (or none)
         _register_recorder(eng, self)
 
@@ -122,6 +123,81 @@ class Recorder:
                 "timers": tim.cpu().numpy(), "replan": (trig & 1) != 0, "below": ((trig[:, :, None] >> np.arange(1, 4)) & 1) != 0,
                 "first_replan": first.cpu().numpy(), "carry": d_car.cpu().numpy(), "par": np.array(par), "threshold": np.array(thr),
                 "veh_of": np.array(veh, dtype=np.int32)}
+
+
+    def vehicle_ranges(self) -> np.ndarray:
+        """Each ego's vehicles [lo, hi) among the recorded ones ([B][2] int32): all of a shared list, its set's slice under a traffic
+        layout (empty for an empty set or a recorder without vehicles)."""
+        B = self.loop.eng.B
+        if self.traffic is None:
+            return np.tile(np.array([0, self.n_obs], dtype=np.int32), (B, 1))
+        set_of, obs_off = self.traffic
+        return np.stack([obs_off[set_of], obs_off[set_of + 1]], axis=1).astype(np.int32)
+
+    def mate_ranges(self) -> np.ndarray:
+        """Each ego's group as a batch range [mlo, mhi) ([B][2] int32): its group of an InteractingLoop, else empty."""
+        B = self.loop.eng.B
+        if self.groups is None:
+            return np.zeros((B, 2), dtype=np.int32)
+        g = np.repeat(np.arange(len(self.groups) - 1), np.diff(self.groups))
+        return np.stack([self.groups[g], self.groups[g + 1]], axis=1).astype(np.int32)
+
+    def conflicts(self, frame_window: int = 0, shapes=None, mates=None) -> dict:
+        """Clearance and first contact of every recorded tick and episode (jsim_loop_eval_conflicts): what
+        check_collision_moving_cars / check_collision_moving_bicycle of main/lib/collision_avoidance.py (:85-166) return for an
+        episode's driven poses against the vehicles' recorded ones, computed in one launch from the records.
+
+        frame_window: the reference's frame_window, 0..20.  shapes: [n_obs][4] vehicle_shape rows (default: the loop's registered
+        table, else every vehicle has the ego's shape).  mates: [B][2] batch ranges [mlo, mhi) of each ego's group mates, itself
+        skipped (default: the groups of an InteractingLoop, else none).  An ego meets its recorded vehicles (vehicle_ranges()) and
+        then its mates, eight in all.
+        Returns numpy arrays: clear [n][B] (the smallest circle distance minus the threshold at offset 0; negative: overlap), who
+        (that vehicle's place in the ego's list), row (the first touching row of the tick's frame over all offsets, -1: none),
+        contact (row >= 0); and at the slot of an episode's first tick hit_tick (-1: no contact), hit_frame, hit_xy [n][B][2] (the
+        reference's return value; -1 / NaN elsewhere); and the frame_window, veh_range, mate_range and ego_shape used.  An ego
+        without vehicles and mates has NaN / -1 everywhere.  history.conflict_episodes splits the result into episodes.
+        ValueError: a frame_window outside 0..20, a bad shapes table, a range outside its table, more than eight vehicles."""
+        eng = self.loop.eng
+        B, n_obs = eng.B, self.n_obs
+        w = int(frame_window)
+        if w != frame_window or not 0 <= w <= 20:
+            raise ValueError(f"frame_window must be an integer in 0..20, got {frame_window!r}")
+        ego = eng.ego_shape if eng.ego_shape is not None else vehicle_shape(L=eng.L)[:3]
+        if shapes is None:
+            shapes = eng.vehicle_shapes
+        if shapes is not None:
+            shapes = np.ascontiguousarray(shapes, dtype=np.float64)
+            if shapes.shape != (n_obs, 4) or not (np.isfinite(shapes).all() and (shapes[:, 2] > 0).all()):
+                raise ValueError(f"shapes must be [n_obs = {n_obs}, 4] vehicle_shape rows with finite offsets and positive radii")
+        veh = self.vehicle_ranges()
+        mate = self.mate_ranges() if mates is None else np.ascontiguousarray(mates, dtype=np.int32)
+        if mate.shape != (B, 2):
+            raise ValueError(f"mates must be [B = {B}, 2] batch ranges, got {mate.shape}")
+        if (veh < 0).any() or (veh > n_obs).any() or (mate < 0).any() or (mate > B).any():
+            raise ValueError("a vehicle range outside [0, n_obs] or a mate range outside [0, B]")
+        me = np.arange(B)
+        count = np.maximum(veh[:, 1] - veh[:, 0], 0) + np.maximum(mate[:, 1] - mate[:, 0], 0) - ((me >= mate[:, 0]) & (me < mate[:, 1]))
+        if (count > MAX_OBS).any():
+            b = int(np.argmax(count))
+            raise ValueError(f"ego {b} would meet {int(count[b])} vehicles and mates (max {MAX_OBS})")
+        n = self._n()
+        dev = eng.device
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(dev)
+        d_veh, d_mate = up(veh), up(mate)
+        new = lambda *shape, dt: torch.empty(max(n, 1), *shape, dtype=dt, device=dev)[:n]   # (no ticks yet: still valid pointers)
+        clear, hit_xy = new(B, dt=torch.float64), new(B, 2, dt=torch.float64)
+        who, row, hit_tick, hit_frame = (new(B, dt=torch.int32) for _ in range(4))
+        ego_c = (C.c_double * 3)(*ego)
+        _cabi.check(eng.lib.jsim_loop_eval_conflicts(
+            eng._ctx, B, n, _ptr(self.rec), _ptr(self.flags), n_obs, _ptr(self.obs) if self.obs is not None else None,
+            _ptr(self.x0_first), _ptr(self.loop.x0_spawn), _ptr(d_veh), _ptr(d_mate),
+            shapes.ctypes.data_as(C.c_void_p) if shapes is not None and n_obs else None, C.cast(ego_c, C.c_void_p), w,
+            _ptr(clear), _ptr(who), _ptr(row), _ptr(hit_tick), _ptr(hit_frame), _ptr(hit_xy), eng._stream()),
+            eng._ctx, "jsim_loop_eval_conflicts")
+        row = row.cpu().numpy()
+        return {"clear": clear.cpu().numpy(), "who": who.cpu().numpy(), "row": row, "contact": row >= 0,
+                "hit_tick": hit_tick.cpu().numpy(), "hit_frame": hit_frame.cpu().numpy(), "hit_xy": hit_xy.cpu().numpy(),
+                "frame_window": w, "veh_range": veh, "mate_range": mate, "ego_shape": tuple(float(v) for v in ego)}
 
 
 def _register_recorder(engine: BatchedMPC, rec: Optional[Recorder]):
@@ -304,6 +380,7 @@ class PreTick:
         self.default_shape = (c0, c1, self.radius, float(eng.L))
         _register_shapes(eng, None)                          # an earlier loop's table on this engine does not carry over
         _cabi.check(eng.lib.jsim_loop_set_geometry(eng._ctx, c0, c1, self.radius), eng._ctx, "jsim_loop_set_geometry")
+        eng.ego_shape = (c0, c1, self.radius)
         if obstacle_dims is not None:
             oL = float(obstacle_dims["L"])
             orad, (o0, o1) = car_circles(oL, float(obstacle_dims.get("width", 2.0)), float(obstacle_dims.get("extra_length", 0.64)))
@@ -482,7 +559,7 @@ class _GlueLoop:
         if shapes is not None:
             _register_shapes(engine, shapes)
         if record:
-            self.loop.recorder = Recorder(self.loop, record, n_obs=self.obst.n)      # last: it records obst.n vehicles
+            self.loop.recorder = Recorder(self.loop, record, n_obs=self.obst.n, groups=group_off)   # last: it records obst.n vehicles
 
     def _register_groups(self):
         """Only InteractingLoop has groups."""

@@ -1364,6 +1364,7 @@ struct jsim_ctx {
     DevArray<double2> d_othr;      // [n_shapes]
     std::vector<double> h_shapes;  // host copy [n_shapes][4] (the thresholds follow jsim_loop_set_geometry)
     int n_shapes = 0;
+    DevArray<double4> d_conflict_rows; // [n_obs] (cc_front, cc_rear, thr, thr_sq) of jsim_loop_eval_conflicts' last call with a table
     DevArray<double2> d_pcc;
     DevArray<double2> d_pred_cc;
     int pred_n_obs = 0, pred_n_steps = 0;
@@ -2307,6 +2308,58 @@ extern "C" int jsim_loop_eval_reasons(jsim_ctx *ctx, int32_t B, int32_t n_ticks,
     const ReasonTickP P = {B, n_ticks, obs_rec ? n_obs : 0, rec, flags, obs_rec, x_first, x_spawn, veh_of, par, threshold,
                            carry, val, timers, trig, first};
     hipLaunchKernelGGL(reason_ticks_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, P);
+    HIP_TRY(ctx, hipGetLastError());
+    return 0;
+}
+
+#include "conflicts.inc"
+
+// Clearance and first contact per recorded tick: DEVICE pointers for the recorder's buffers, the ranges and
+// the outputs, HOST pointers for `shapes` and `ego_shape` (the thresholds are made here, on the host); one launch on `stream`, one
+// wavefront per ego.
+extern "C" int jsim_loop_eval_conflicts(jsim_ctx *ctx, int32_t B, int32_t n_ticks, const double *rec, const int32_t *flags, int32_t n_obs,
+                                        const double *obs_rec, const double *x_first, const double *x_spawn, const int32_t *veh_range,
+                                        const int32_t *mate_range, const double *shapes, const double *ego_shape, int32_t frame_window,
+                                        double *clear, int32_t *who, int32_t *row, int32_t *hit_tick, int32_t *hit_frame,
+                                        double *hit_xy, void *stream)
+{
+    const char *const F = "jsim_loop_eval_conflicts";
+    // (the argument checks come first: they need no context and no device)
+    if (B < 0 || n_ticks < 0 || n_obs < 0) return fail(ctx, -22, "%s: B=%d n_ticks=%d n_obs=%d", F, B, n_ticks, n_obs);
+    if (!obs_rec && n_obs > 0) return fail(ctx, -22, "%s: null obs_rec with n_obs=%d", F, n_obs);
+    if (frame_window < 0 || frame_window > 20) return fail(ctx, -22, "%s: frame_window=%d outside [0, 20]", F, frame_window);
+    if (!ego_shape) return fail(ctx, -22, "%s: null ego_shape", F);
+    if (!rec || !flags || !x_first || !x_spawn || !veh_range || !mate_range || !clear || !who || !row || !hit_tick || !hit_frame || !hit_xy)
+        return fail(ctx, -22, "%s: null device pointer", F);
+    const double cc_f = ego_shape[0], cc_r = ego_shape[1], r_ego = ego_shape[2];
+    if (!std::isfinite(cc_f) || !std::isfinite(cc_r)) return fail(ctx, -22, "%s: ego_shape: a circle offset that is not finite", F);
+    if (!(r_ego > 0.0) || !std::isfinite(r_ego)) return fail(ctx, -22, "%s: ego_shape: radius %g is not positive and finite", F, r_ego);
+    const bool table = shapes && n_obs > 0;
+    for (int i = 0; table && i < n_obs; ++i) {
+        const double *s = shapes + 4 * (size_t)i;
+        if (!std::isfinite(s[0]) || !std::isfinite(s[1]) || !(s[2] > 0.0) || !std::isfinite(s[2]))
+            return fail(ctx, -22, "%s: shapes row %d needs finite circle offsets and a positive, finite radius", F, i);
+    }
+    if (!ctx) return fail(nullptr, -22, "%s: null ctx", F);
+    if (B == 0 || n_ticks == 0) return 0;
+    DeviceGuard dev_guard(ctx->device);
+    JSIM_GUARD_OK(ctx);
+    if (table) {   // min_distance per vehicle: the egos' radius + its own, and the squared form the rows are compared with
+        std::vector<double4> rows((size_t)n_obs);
+        for (int i = 0; i < n_obs; ++i) {
+            const double *s = shapes + 4 * (size_t)i;
+            const double thr = r_ego + s[2];
+            rows[i] = double4{s[0], s[1], thr, jsim_sqrt_threshold(thr)};
+        }
+        HIP_TRY(ctx, hipDeviceSynchronize()); // an earlier call's launch may still read the table that is replaced
+        HIP_TRY(ctx, ctx->d_conflict_rows.reserve(n_obs));
+        HIP_TRY(ctx, hipMemcpy(ctx->d_conflict_rows, rows.data(), sizeof(double4) * n_obs, hipMemcpyHostToDevice));
+    }
+    const double thr_ee = r_ego + r_ego;
+    const ConflictP P = {B, n_ticks, n_obs, frame_window, rec, flags, n_obs > 0 ? obs_rec : nullptr, x_first, x_spawn, veh_range, mate_range,
+                         table ? ctx->d_conflict_rows.p : nullptr, cc_f, cc_r, double4{cc_f, cc_r, thr_ee, jsim_sqrt_threshold(thr_ee)},
+                         clear, who, row, hit_tick, hit_frame, hit_xy};
+    hipLaunchKernelGGL(conflict_ticks_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, P);
     HIP_TRY(ctx, hipGetLastError());
     return 0;
 }

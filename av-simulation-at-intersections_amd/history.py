@@ -2,7 +2,8 @@
 main/lib/simulation.py:50-88, and `obstacles_positions`, main/scenarios/mpc_intersection.py:95-96,159-161), rebuilt from what
 the device recorder wrote (jsim_loop_set_recorder): rec [n][B][7] = x, y, yaw, v, delta, a, xref_deviation per tick, flags
 [n][B] (FAILED / GOAL / AGE bits), obs [n][n_obs][6] = the scripted vehicles' get() tuples.  Pure numpy: the host-side half of
-the recorder, testable without a device.  reason_series does the same for the per-tick stakeholder reasons."""
+the recorder, testable without a device.  reason_series does the same for the per-tick stakeholder reasons,
+conflict_episodes for the clearance and first contact of every episode (section 17)."""
 from __future__ import annotations
 
 from typing import List, Optional
@@ -117,3 +118,42 @@ def reason_series(values: dict, flags: np.ndarray, dt: float):
             eps.append(ep)
         out.append(eps)
     return out
+
+
+def conflict_episodes(result: dict, flags: np.ndarray):
+    """The clearance and first contact of a recorder (Recorder.conflicts: `clear`, `who`, `hit_tick`, `hit_frame`, `hit_xy`) per
+    ego and episode, split where ego_histories splits (episode_bounds).  Returns a list over egos of lists over episodes of dicts:
+    contact (bool), tick (the first tick whose frame touches, -1: none), frame and xy (the reference's first_frame_idx and (x, y);
+    -1 / None), collision_xy (what check_collision_moving_cars / check_collision_moving_bicycle return for the episode: None or
+    (x, y, frame)), min_clear and min_clear_tick (the episode's smallest clearance and its first tick; NaN / -1 for an ego without
+    vehicles or an episode without a tick yet), closest_vehicle (the place in the ego's list of the vehicle that came closest)."""
+    f = np.asarray(flags).reshape(np.shape(flags)[0], -1)
+    clear, who = np.asarray(result["clear"], dtype=np.float64), np.asarray(result["who"])
+    out = []
+    for b in range(f.shape[1]):
+        eps = []
+        for k0, k1, _ in episode_bounds(f[:, b]):
+            ep = {"contact": False, "tick": -1, "frame": -1, "xy": None, "collision_xy": None, "min_clear": float("nan"),
+                  "min_clear_tick": -1, "closest_vehicle": -1}
+            if k1 > k0:
+                tick = int(result["hit_tick"][k0, b])
+                if tick >= 0:
+                    x, y = (float(v) for v in result["hit_xy"][k0, b])
+                    frame = int(result["hit_frame"][k0, b])
+                    ep.update(contact=True, tick=tick, frame=frame, xy=(x, y), collision_xy=(x, y, frame))
+                c = clear[k0:k1, b]
+                if not np.isnan(c).all():
+                    k = int(np.nanargmin(c))
+                    ep.update(min_clear=float(c[k]), min_clear_tick=k0 + k, closest_vehicle=int(who[k0 + k, b]))
+            eps.append(ep)
+        out.append(eps)
+    return out
+
+
+def threshold_crossings(series, value: float):
+    """The ticks i >= 1 with series[i] <= value < series[i - 1]: where plot_distance of
+    main/scenarios/overtaking_cyclist_bidirectional_road.py (:2390-2400) draws the line of a distance threshold.  For one ego's
+    `clear` (Recorder.conflicts) or `distance` (Recorder.reasons) series; a NaN is on neither side.  Returns an int64 array."""
+    s = np.asarray(series, dtype=np.float64).reshape(-1)
+    with np.errstate(invalid="ignore"):
+        return np.flatnonzero((s[1:] <= value) & (s[:-1] > value)) + 1

@@ -416,6 +416,41 @@ int jsim_loop_eval_reasons(jsim_ctx *ctx, int32_t B, int32_t n_ticks, const doub
                            const double *par, const double *threshold, double *carry, double *val, double *timers, int32_t *trig,
                            int32_t *first, void *stream);
 
+/* ---- clearance and first contact per recorded tick: the realised poses of a run against the vehicles it met ----
+ * Answers what main/planner/moving_obstacle_avoidance.py (:44-76) asks of whole realised trajectories with
+ * check_collision_moving_cars / check_collision_moving_bicycle (main/lib/collision_avoidance.py:85-166): did the ego touch a
+ * vehicle, when and where, and how close did it get -- per episode of every ego, from the recorder's buffers
+ * (jsim_loop_set_recorder), after the loop.  One wavefront per ego, 64 ticks at a time.  DESIGN.md section 17 is the contract.
+ *   DEVICE pointers: rec [n_ticks][B][7], flags [n_ticks][B], obs_rec [n_ticks][n_obs][6], x_first [B][4], x_spawn [B][4] exactly as
+ *   jsim_loop_eval_reasons takes them (the ego's pose at the start of tick k by the same rule, yaw included; a vehicle's pose is
+ *   entries 0, 1 and 3 of obs_rec[k]); veh_range [B][2]: the ego's vehicles [lo, hi) among the n_obs recorded ones; mate_range
+ *   [B][2]: the batch range [mlo, mhi) of its group mates, itself skipped (a mate's sample is its own start-of-tick pose); the
+ *   vehicles come first, then the mates, JSIM_MAX_OBS (8) in all; and every output.
+ *   HOST pointers: shapes [n_obs][4] = the rows of jsim_loop_set_vehicle_shapes (cc_front, cc_rear, radius, wheelbase; the wheelbase
+ *   is not read), NULL: every vehicle has the ego's shape; ego_shape [3] = cc_front, cc_rear, radius (jsim_loop_set_geometry's
+ *   values).  A vehicle's threshold is ego radius + its own radius, made here on the host together with the largest double whose
+ *   square root does not exceed it, so that a row touches exactly when sqrt(dx * dx + dy * dy) <= threshold.  Mates have the ego's
+ *   shape.  The table is copied to the device inside the call (one synchronising copy when shapes is given).
+ *   frame_window w in [0, 20]: the rows of a tick's frame are the reference's pair table, row = ((a * n_veh + i) * (2w + 1) +
+ *   (off + w)) * 2 + c (ego circle a, vehicle i, offset off, vehicle circle c), the vehicle taken at the episode's frame
+ *   clamp(f - off, 0, N - 1).
+ *   Out, per ego and tick [n_ticks][B]: clear = the minimum of dist - threshold over the rows with off = 0 (negative: overlap),
+ *   who = that row's vehicle (the lowest row on ties), row = the frame's first touching row over all offsets or -1; without
+ *   vehicles NaN / -1 / -1.  Per episode, at the slot of its first tick (every other slot -1 / -1 / NaN): hit_tick = the first
+ *   tick whose frame has a touching row or -1; hit_frame and hit_xy [n_ticks][B][2] = the reference's return value for the episode
+ *   (x, y, first_frame_idx): the ego's recorded pose at the earliest frame whose front circle touches the first touching row's
+ *   vehicle circle, or whose rear circle does when the front one never does (`np.argmax(mask) % len`); it can precede hit_tick.
+ *   Refused (-22) before any device call, jsim_last_error naming the argument: B < 0, n_ticks < 0, n_obs < 0; obs_rec NULL with
+ *   n_obs > 0; frame_window outside [0, 20]; a null pointer other than obs_rec (n_obs = 0), shapes and stream; an ego radius that is
+ *   not positive and finite, a circle offset or a shapes radius likewise; a null ctx.  n_ticks = 0 or B = 0 returns 0 and writes
+ *   nothing.  A range outside [0, n_obs] / [0, B] or a list of more than 8 would need a device read to detect: the Python surface
+ *   (Recorder.conflicts) refuses it with ValueError; the kernel clamps, so it never reads outside the tables. */
+int jsim_loop_eval_conflicts(jsim_ctx *ctx, int32_t B, int32_t n_ticks, const double *rec, const int32_t *flags, int32_t n_obs,
+                             const double *obs_rec, const double *x_first, const double *x_spawn, const int32_t *veh_range,
+                             const int32_t *mate_range, const double *shapes, const double *ego_shape, int32_t frame_window,
+                             double *clear, int32_t *who, int32_t *row, int32_t *hit_tick, int32_t *hit_frame, double *hit_xy,
+                             void *stream);
+
 /* ---- the job's one exchange: the final trajectory gather over RCCL / xGMI ----
  * The reference has no multi-process code at all (its only multi-ego code is the serial Python loop of
  * main/scenarios/interactive_mpc.py:119-172); egos are independent (main/lib/mpc.py:141-211), so ranks own contiguous shards

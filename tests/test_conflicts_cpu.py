@@ -1,0 +1,221 @@
+"""Clearance and first contact per recorded tick (jsim_loop_eval_conflicts) without a GPU: the numpy
+restatement against the reference-made fixture (tests/golden/conflicts.npz) at every window and tick count, its own rows regenerated
+bit for bit, its vectorised form against plain loops on the cases no reference function takes, the fixture's condition and events,
+the host-side pieces (history.conflict_episodes, history.threshold_crossings) and the C entry point's declaration, binding and -22
+list against the cross-compiled library."""
+import os
+import re
+
+import numpy as np
+import pytest
+
+import conflict_cases as TC
+import conflicts_numpy as CN
+from conftest import REPO
+
+
+@pytest.fixture(scope="module")
+def cs():
+    return TC.cases()
+
+
+@pytest.fixture(scope="module")
+def arrays(cs):
+    return TC.recorder_arrays(cs)
+
+
+@pytest.fixture(scope="module")
+def restated(arrays):
+    """The restatement at every (window, tick count) of the fixture."""
+    return {(w, n): TC.restate(arrays, w, n=n) for w in TC.WINDOWS for n in TC.TICK_COUNTS}
+
+
+def test_cases_are_the_stored_ones(cs):
+    g = TC.fixture()
+    assert int(g["n_cases"]) == len(cs) == 28 and g["ego"].shape == (28, TC.N, 3)
+    for b, c in enumerate(cs):
+        assert str(g["labels"][b]) == c["label"] and bool(g["restated"][b]) == c["restated"] and int(g["n_vehicles"][b]) == len(c["vehicles"])
+        assert np.array_equal(g["ego"][b], c["ego"]) and np.array_equal(g["flags"][b], c["flags"])
+        for i, v in enumerate(c["vehicles"]):
+            assert np.array_equal(g["vehicles"][b, i], v), (b, i)
+        assert bool(g["bike"][b]) == (bool(c["kinds"]) and c["kinds"][0] == "bike")
+    assert g["car_shape"].tolist() == list(TC.CAR) and g["bike_shape"].tolist() == list(TC.BIKE)
+    assert np.flatnonzero(g["restated"]).tolist() == [22, 23, 24, 25, 26, 27]
+    assert sorted({len(c["vehicles"]) for c in cs}) == [0, 1, 2, 8]
+    # every (window, tick count, case, episode) has its record: no case is left out of any comparison
+    want = sum(len(CN.episodes_of(c["flags"][:n])) for c in cs for n in TC.TICK_COUNTS) * len(TC.WINDOWS)
+    assert len(g["records"]) == want and len({tuple(r[:4]) for r in g["records"].tolist()}) == want
+
+
+def test_restatement_reproduces_the_reference(cs, restated):
+    g = TC.fixture()
+    ref_made = ~g["restated"]
+    hits = 0
+    for (w, n), mine in restated.items():
+        made, hit, tick, frame, xy = TC.expected(g, w, n)
+        assert np.array_equal(made[:, ref_made].sum(0), [len(CN.episodes_of(c["flags"][:n])) for c in np.array(cs, dtype=object)[ref_made]])
+        m = made & ref_made[None, :]
+        assert np.array_equal((mine["hit_tick"] >= 0)[m], hit[m]), (w, n)                        # None / not None
+        assert np.array_equal(mine["hit_frame"][m], frame[m]), (w, n)
+        assert np.array_equal(mine["hit_xy"][m], xy[m], equal_nan=True), (w, n)                   # exactly: a copy of a pose
+        if w == 0:
+            assert np.array_equal(mine["hit_tick"][m], tick[m]), n                                # the reference's first prefix that hits
+        else:
+            assert np.all(tick[m] == -2)
+        # what is no episode's first tick holds nothing
+        assert np.all(mine["hit_tick"][~made] == -1) and np.all(mine["hit_frame"][~made] == -1) and np.isnan(mine["hit_xy"][~made]).all()
+        hits += int(hit[m].sum())
+    assert hits == 588
+
+
+def test_restatement_made_rows_regenerate_bit_for_bit(restated):
+    g = TC.fixture()
+    rs = g["restated"]
+    for (w, n), mine in restated.items():
+        made, hit, tick, frame, xy = TC.expected(g, w, n)
+        m = made & rs[None, :]
+        assert m.any() and np.array_equal(mine["hit_tick"][m], tick[m]) and np.array_equal(mine["hit_frame"][m], frame[m]), (w, n)
+        assert np.array_equal(mine["hit_xy"][m], xy[m], equal_nan=True) and np.array_equal(hit[m], tick[m] >= 0), (w, n)
+
+
+def test_vectorised_form_equals_plain_loops_on_the_mixed_cases(cs):
+    """The cases no reference function takes -- a car and a cyclist in one list, mates -- and, to pin the loops themselves, one
+    reference-made case at each uniform end (cars only, cyclists only)."""
+    sub = [cs[0], cs[2]] + cs[22:]
+    A = TC.recorder_arrays(sub)
+    assert A["mate_range"].tolist() == [[0, 0], [1, 1], [2, 2], [3, 5], [3, 5], [5, 8], [5, 8], [5, 8]]
+    assert A["veh_range"].tolist() == [[1, 2], [2, 3], [3, 5], [5, 5], [5, 5], [5, 6], [5, 6], [5, 6]]
+    for w, n in ((0, TC.N), (1, 160), (3, 100), (20, 70)):
+        fast, slow = TC.restate(A, w, n=n), TC.restate(A, w, n=n, loops=True)
+        for k in fast:
+            assert np.array_equal(fast[k], slow[k], equal_nan=True), (w, n, k)
+        assert (fast["row"] >= 0).any()
+        if n == TC.N:
+            assert len(set(fast["who"][:, 2].tolist())) == 2                                    # the car and the cyclist both come closest
+
+
+def test_fixture_condition_holds(arrays):
+    g = TC.fixture()
+    stats = {}
+    for w in TC.WINDOWS:
+        for n in TC.TICK_COUNTS:
+            TC.restate(arrays, w, n=n, stats=stats)
+    assert stats["margin"] == float(g["margin"]) >= 1e-9
+
+
+def test_fixture_meets_the_kernel_structure(cs, restated):
+    """The events each case is named after are where the name says."""
+    full = {w: restated[(w, TC.N)] for w in TC.WINDOWS}
+    contact = lambda w, b: np.flatnonzero(full[w]["row"][:, b] >= 0).tolist()
+    first = lambda w, b, k0=0: (int(full[w]["hit_tick"][k0, b]), int(full[w]["hit_frame"][k0, b]))
+    assert contact(0, 0) and 64 < contact(0, 0)[0] < 127                                         # the crossing
+    assert contact(20, 1) == [] and contact(0, 2) != [] and np.nanmin(full[0]["clear"][:, 1]) < 0.03   # the gap above / below
+    assert contact(0, 3) == [100] and contact(1, 3) == [99, 100, 101]
+    assert contact(0, 4) == [] and contact(1, 4) == [99, 101] and first(1, 4)[0] == 99           # only through an offset
+    # case 5: no frame of the ego's front circle is within the threshold of the hit position, so the first hit of front ++ rear
+    # is in the rear half
+    c = cs[5]
+    f = first(0, 5)[0]
+    hit_pos = CN.circle_centres(c["vehicles"][0], TC.CAR[1])[f]
+    front, rear = CN.circle_centres(c["ego"], TC.CAR[0]), CN.circle_centres(c["ego"], TC.CAR[1])
+    thr = TC.CAR[2] + TC.CAR[2]
+    assert full[0]["row"][f, 5] == 3 and np.all(np.hypot(*(front - hit_pos).T) > thr) and np.hypot(*(rear - hit_pos).T)[0] <= thr
+    assert first(0, 5) == (f, 0) and f > 100
+    assert first(0, 6)[1] < first(0, 6)[0] and first(0, 8) == (62, 18) and first(1, 0)[1] < first(1, 0)[0]   # hit_frame before hit_tick
+    assert [contact(0, b) for b in range(7, 13)] == [[0], [62], [63], [64], [65], [TC.N - 1]]
+    assert [CN.episodes_of(cs[b]["flags"]) for b in (13, 14, 15)] == [[(0, k), (k + 1, TC.N - 1)] for k in (62, 63, 64)]
+    assert CN.episodes_of(cs[16]["flags"]) == [(0, 100), (101, 101), (102, TC.N - 1)] and first(0, 16, 101) == (101, 0)
+    assert CN.episodes_of(cs[17]["flags"])[:4] == [(0, 4), (5, 6), (7, 7), (8, 10)]
+    assert first(0, 17)[0] == 4 and first(3, 17)[0] == 0 and first(20, 17)[0] == 0              # the clamp brings the contact to frame 0
+    assert np.isnan(full[3]["clear"][:, 18]).all() and np.all(full[3]["who"][:, 18] == -1) and np.all(full[3]["row"][:, 18] == -1)
+    assert len(set(full[0]["who"][:, 20].tolist())) >= 6 and contact(0, 21) != []
+    # the mates see each other: the same clearance from both sides
+    assert np.array_equal(full[0]["clear"][:, 23], full[0]["clear"][:, 24]) and contact(0, 23) == contact(0, 24) != []
+    # a cut at w > 0 clamps the last frames differently: the prefix property holds at w = 0 only
+    assert np.array_equal(restated[(0, 64)]["row"], full[0]["row"][:64]) and not np.array_equal(restated[(20, 64)]["row"], full[20]["row"][:64])
+
+
+def test_conflict_episodes_and_threshold_crossings(pkg):
+    H = pkg.history
+    flags = np.zeros((6, 2), dtype=np.int32)
+    flags[2, 0], flags[5, 1] = H.GOAL, H.AGE
+    res = {"clear": np.array([[3.0, np.nan], [-0.5, np.nan], [1.0, np.nan], [2.0, np.nan], [0.25, np.nan], [0.25, np.nan]]),
+           "who": np.array([[0, -1], [1, -1], [0, -1], [1, -1], [1, -1], [0, -1]]),
+           "hit_tick": np.full((6, 2), -1), "hit_frame": np.full((6, 2), -1), "hit_xy": np.full((6, 2, 2), np.nan)}
+    res["hit_tick"][0, 0], res["hit_frame"][0, 0], res["hit_xy"][0, 0] = 1, 0, (4.0, 5.0)
+    eps = H.conflict_episodes(res, flags)
+    assert [len(e) for e in eps] == [2, 2] == [len(H.episode_bounds(flags[:, b])) for b in range(2)]
+    a, b = eps[0]
+    assert a == {"contact": True, "tick": 1, "frame": 0, "xy": (4.0, 5.0), "collision_xy": (4.0, 5.0, 0), "min_clear": -0.5,
+                 "min_clear_tick": 1, "closest_vehicle": 1}
+    assert b["contact"] is False and b["collision_xy"] is None and b["xy"] is None and (b["min_clear"], b["min_clear_tick"], b["closest_vehicle"]) == (0.25, 4, 1)
+    c, d = eps[1]                                                         # no vehicles; then an episode without a tick yet
+    assert not c["contact"] and np.isnan(c["min_clear"]) and c["min_clear_tick"] == -1 and c["closest_vehicle"] == -1
+    assert d == {**c, "min_clear": d["min_clear"]} and np.isnan(d["min_clear"])
+    assert all(isinstance(a[k], t) for k, t in (("tick", int), ("frame", int), ("min_clear", float), ("min_clear_tick", int)))
+    T = H.threshold_crossings
+    assert T([12.0, 10.0, 9.0, 10.5, 10.0, 3.0, 11.0, np.nan, 2.0], 10.0).tolist() == [1, 4]
+    assert T([5.0], 10.0).tolist() == [] and T([], 1.0).tolist() == [] and T([11.0, 9.0], 10.0).dtype == np.int64
+    assert T(res["clear"][:, 0], 0.0).tolist() == [1]
+
+
+NAMES = ("rec", "flags", "n_obs", "obs_rec", "x_first", "x_spawn", "veh_range", "mate_range", "shapes", "ego_shape", "frame_window",
+         "clear", "who", "row", "hit_tick", "hit_frame", "hit_xy")
+
+
+def test_entry_point_is_declared_and_bound(pkg):
+    hdr = open(os.path.join(REPO, "include", "jsim_mpc.h")).read()
+    m = re.search(r"\bint jsim_loop_eval_conflicts\s*\(([^;]*)\);", hdr)
+    assert m and len(m.group(1).split(",")) == 21
+    assert all(re.search(rf"\b{k}\b", m.group(1)) for k in NAMES)
+    assert "check_collision_moving_cars / check_collision_moving_bicycle (main/lib/collision_avoidance.py:85-166)" in hdr
+    assert "jsim_loop_eval_conflicts" in pkg._cabi.EXPORTS
+    lib = pkg._cabi.load()
+    assert len(lib.jsim_loop_eval_conflicts.argtypes) == 21
+    doc = open(os.path.join(REPO, "INTEGRATION.md")).read()
+    assert re.search(r"^\| `jsim_loop_eval_conflicts` \|", doc, flags=re.M)
+    assert callable(pkg.closed_loop.Recorder.conflicts) and callable(pkg.history.conflict_episodes) and callable(pkg.history.threshold_crossings)
+    src = open(os.path.join(REPO, "av-simulation-at-intersections_amd", "csrc", "jsim_mpc.hip")).read()
+    assert '#include "conflicts.inc"' in src and src.index('#include "reasons_ticks.inc"') < src.index('#include "conflicts.inc"')
+
+
+def test_argument_errors_without_gpu(pkg):
+    """The header's -22 list: from the host, before any device call (there is no device here and no context to launch on)."""
+    lib = pkg._cabi.load()
+    buf = np.zeros(64)
+    p = buf.ctypes.data                                                 # a non-null address; no refused call reads it
+    ego = np.array(TC.CAR)
+    shapes = np.array([[*TC.CAR, 2.86], [*TC.BIKE, 1.0]])
+
+    def call(B=1, n=1, ctx=None, **over):
+        a = {k: p for k in NAMES}
+        a.update(n_obs=2, frame_window=3, ego_shape=ego.ctypes.data, shapes=shapes.ctypes.data)
+        a.update(over)
+        rc = lib.jsim_loop_eval_conflicts(ctx, B, n, *[a[k] for k in NAMES], None)
+        return rc, lib.jsim_last_error(None).decode()
+
+    who = "jsim_loop_eval_conflicts: "
+    bad_ego = lambda **kw: np.array([kw.get("f", TC.CAR[0]), kw.get("r", TC.CAR[1]), kw.get("radius", TC.CAR[2])])
+    bad_row = shapes.copy()
+    bad_row[1, 2] = 0.0
+    keep = [bad_ego(radius=v) for v in (0.0, -1.0, np.inf, np.nan)] + [bad_ego(f=np.nan)]
+    for kw, msg in ((dict(B=-1), "B=-1"), (dict(n=-1), "n_ticks=-1"), (dict(n_obs=-3), "n_obs=-3"), (dict(obs_rec=None), "null obs_rec with n_obs=2"),
+                    (dict(frame_window=-1), "frame_window=-1"), (dict(frame_window=21), "frame_window=21"), (dict(ego_shape=None), "null ego_shape"),
+                    (dict(ego_shape=keep[0].ctypes.data), "ego_shape: radius 0"), (dict(ego_shape=keep[1].ctypes.data), "ego_shape: radius -1"),
+                    (dict(ego_shape=keep[2].ctypes.data), "ego_shape: radius inf"), (dict(ego_shape=keep[3].ctypes.data), "ego_shape: radius nan"),
+                    (dict(ego_shape=keep[4].ctypes.data), "ego_shape: a circle offset"), (dict(shapes=bad_row.ctypes.data), "shapes row 1")):
+        rc, err = call(**kw)
+        assert rc == -22 and err.startswith(who) and msg in err, (kw, rc, err)
+    for k in NAMES:
+        if k in ("n_obs", "obs_rec", "shapes", "ego_shape", "frame_window"):
+            continue
+        rc, err = call(**{k: None})
+        assert rc == -22 and err == who + "null device pointer", (k, rc, err)
+        rc, err = call(n=0, **{k: None})                                  # also with nothing to do
+        assert rc == -22, k
+    rc, err = call()                                                      # every argument good: the missing context is what is left
+    assert rc == -22 and err == who + "null ctx"
+    for kw in (dict(obs_rec=None, n_obs=0), dict(shapes=None), dict(frame_window=0), dict(frame_window=20), dict(n=0), dict(B=0)):
+        rc, err = call(**kw)                                              # none of these is an error of its own
+        assert rc == -22 and err == who + "null ctx", kw
+    assert not buf.any()

@@ -1,0 +1,116 @@
+#!/usr/bin/env python3
+"""The clearance and first contact of a recorded run as ONE launch (Recorder.conflicts, jsim_loop_eval_conflicts): a ScenarioLoop
+at T = 13 with config 3's four scripted vehicles, B = 256 and B = 4096 egos, 300 recorded ticks, frame_window 0 and 3.
+
+Timed: the whole Recorder.conflicts() call -- argument checks, the uploads of the two range tables, the launch, the read-back of
+clear, who, row, hit_tick, hit_frame [300][B] and hit_xy [300][B][2] -- wall ms as the median / min / max of --runs calls after
+--warmup untimed ones.  Beside it: the numpy restatement (tests/conflicts_numpy.py) on the same arrays, downloaded once outside the
+timed region, best of 3; history.conflict_episodes on the device result; the read-back of rec and obs_rec that an evaluation on
+the host would start with; and the launch alone (the entry point on buffers that stay on the device, then a synchronise, no
+read-back), which tells the kernel's share of the call from the read-back's.  Prints one JSON line and, with --out, writes it there.
+
+    python3 tools/bench_conflicts.py [--runs 9] [--warmup 2] [--ticks 300] [--out profiles/NAME.txt]
+"""
+import argparse
+import importlib
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+sys.path.insert(0, os.path.join(REPO, "tests"))
+
+
+def launch_alone(pkg, torch, r, out, w, warmup, runs):
+    """Wall ms of jsim_loop_eval_conflicts + synchronise on device buffers allocated once: the call without its read-back."""
+    eng = r.loop.eng
+    B, n, dev = eng.B, r.rec.shape[0], eng.device
+    up = lambda x: torch.from_numpy(np.ascontiguousarray(x, dtype=np.int32)).to(dev)
+    veh, mate = up(out["veh_range"]), up(out["mate_range"])
+    ego = np.array(out["ego_shape"])
+    f64 = [torch.empty(n, B, dtype=torch.float64, device=dev), torch.empty(n, B, 2, dtype=torch.float64, device=dev)]
+    i32 = [torch.empty(n, B, dtype=torch.int32, device=dev) for _ in range(4)]
+    p = lambda t: t.data_ptr()
+    ts = []
+    for run in range(warmup + runs):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        rc = eng.lib.jsim_loop_eval_conflicts(eng._ctx, B, n, p(r.rec), p(r.flags), r.n_obs, p(r.obs), p(r.x0_first), p(r.loop.x0_spawn),
+                                              p(veh), p(mate), None, ego.ctypes.data, w, p(f64[0]), *[p(t) for t in i32], p(f64[1]), None)
+        torch.cuda.synchronize()
+        if run >= warmup:
+            ts.append((time.perf_counter() - t0) * 1e3)
+        pkg._cabi.check(rc, eng._ctx, "jsim_loop_eval_conflicts")
+    return ts
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--runs", type=int, default=9)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--ticks", type=int, default=300)
+    ap.add_argument("--out")
+    a = ap.parse_args()
+    import torch
+    pkg = importlib.import_module("av-simulation-at-intersections_amd")
+    import conflicts_numpy as CN
+    W = pkg.workloads
+    routes = W.route_table(False)[0]
+    K, T = a.ticks, 13
+    res = {"ticks": K, "T": T, "runs": a.runs, "warmup": a.warmup, "vehicles": len(W.OBSTACLE_SPECS), "gpu_ms": {}, "numpy_ms": {},
+           "launch_ms": {}, "episodes_ms": {}, "readback_ms": {}, "max_clear_err": {}, "contacts": {}, "episodes": {}}
+    for B in (256, 4096):
+        eng, x0 = W.make_engine(routes, W.ego_batch(routes, B, T, rank=2), T, "cuda:0")
+        loop = pkg.ScenarioLoop(eng, x0, W.OBSTACLE_SPECS, hist_cap=K, max_age=W.MAX_AGE, record=K)
+        loop.run(K)
+        torch.cuda.synchronize()
+        r = loop.recorder
+        tr = []
+        for _ in range(3):                                              # what a host evaluation starts with
+            t0 = time.perf_counter()
+            host_rec, host_obs = r.rec.cpu().numpy(), r.obs.cpu().numpy()
+            tr.append((time.perf_counter() - t0) * 1e3)
+        res["readback_ms"][str(B)] = min(tr)
+        host = [host_rec, r.flags.cpu().numpy(), host_obs, r.x0_first.cpu().numpy(), r.loop.x0_spawn.cpu().numpy()]
+        for w in (0, 3):
+            key = f"{B}/w{w}"
+            ts = []
+            for run in range(a.warmup + a.runs):
+                t0 = time.perf_counter()
+                out = r.conflicts(frame_window=w)
+                if run >= a.warmup:
+                    ts.append((time.perf_counter() - t0) * 1e3)
+            res["gpu_ms"][key] = {"median": statistics.median(ts), "min": min(ts), "max": max(ts)}
+            res["launch_ms"][key] = statistics.median(launch_alone(pkg, torch, r, out, w, a.warmup, a.runs))
+            tn = []
+            for _ in range(3):
+                t0 = time.perf_counter()
+                ref = CN.eval_conflicts(*host, out["veh_range"], out["mate_range"], eng.vehicle_shapes, out["ego_shape"], w)
+                tn.append((time.perf_counter() - t0) * 1e3)
+            res["numpy_ms"][key] = min(tn)
+            te = []
+            for _ in range(3):
+                t0 = time.perf_counter()
+                eps = pkg.history.conflict_episodes(out, host[1])
+                te.append((time.perf_counter() - t0) * 1e3)
+            res["episodes_ms"][key] = min(te)
+            for k in ("who", "row", "hit_tick", "hit_frame"):
+                assert np.array_equal(out[k], ref[k]), (key, k)
+            assert np.array_equal(out["hit_xy"], ref["hit_xy"], equal_nan=True), key
+            res["max_clear_err"][key] = float(np.max(np.abs(out["clear"] - ref["clear"]) / np.maximum(1.0, np.abs(ref["clear"]))))
+            res["contacts"][key] = int(sum(e["contact"] for ep in eps for e in ep))
+            res["episodes"][key] = int(sum(len(ep) for ep in eps))
+    line = json.dumps(res)
+    print(line)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
