@@ -199,6 +199,58 @@ class Recorder:
                 "hit_tick": hit_tick.cpu().numpy(), "hit_frame": hit_frame.cpu().numpy(), "hit_xy": hit_xy.cpu().numpy(),
                 "frame_window": w, "veh_range": veh, "mate_range": mate, "ego_shape": tuple(float(v) for v in ego)}
 
+    def static_conflicts(self, obstacles, set_of=None, margin=None, include_hidden: bool = False) -> dict:
+        """Clearance to and contact with the scenario's static obstacles on every recorded tick (jsim_loop_eval_static, DESIGN.md
+        section 18): check_collision on Obstacle.to_convex(margin) (main/lib/obstacles.py:157-176, the planner's collision test) and
+        distance_to_point at the two collision circle centres of the poses that were driven, computed in one launch from the records.
+
+        obstacles: one set -- a scenario's obstacles list: the reference's BoxObstacle / CircleObstacle objects or the primitives of
+        planner.intersection_obstacles -- or a list of such sets (an empty list: one empty set).  set_of: the set of every ego, one
+        index or [B] (default 0).  margin: what to_convex inflates by (default: the ego radius, as the scenario scripts pass it to the
+        planner).  include_hidden: also test the hidden obstacles (the planner's lane-closing boxes).
+        Returns numpy arrays [n][B]: clear (the smallest distance_to_point(centre) - radius over the included obstacles and the two
+        centres; -radius: a centre inside an obstacle), who (that obstacle's place in its set), hit (the lowest place of a touched
+        obstacle, -1: none), contact (hit >= 0), off_tick (at the slot of an episode's first tick the episode's first touching tick
+        or -1; -1 elsewhere); and the margin, include_hidden, ego_shape and set_of used.  An ego whose set has no included obstacle
+        has NaN / -1 / -1.  history.static_episodes splits the result into episodes.
+        ValueError: an obstacle that is neither kind, a set_of outside the sets, a margin that is not finite and >= 0."""
+        from . import planner
+        eng = self.loop.eng
+        B = eng.B
+        ego = eng.ego_shape if eng.ego_shape is not None else vehicle_shape(L=eng.L)[:3]
+        margin = float(ego[2] if margin is None else margin)
+        obstacles = list(obstacles)
+        is_one = lambda o: (isinstance(o, (tuple, list)) and len(o) > 0 and isinstance(o[0], str)) or hasattr(o, "to_convex")
+        sets = [obstacles] if (not obstacles or is_one(obstacles[0])) else [list(s) for s in obstacles]
+        tables = [planner.static_obstacle_rows(s, margin) for s in sets]
+        rows = np.ascontiguousarray(np.concatenate(tables))
+        n_rows = len(rows)
+        if n_rows == 0:
+            rows = np.zeros((1, planner.STATIC_ROW))                 # (a valid pointer; no row of it is read)
+        set_off = np.concatenate([[0], np.cumsum([len(t) for t in tables])]).astype(np.int32)
+        sof = np.zeros(B, dtype=np.int64) if set_of is None else np.asarray(set_of)
+        if sof.dtype.kind not in "iu" or sof.shape not in ((), (B,)):
+            raise ValueError(f"set_of must be one integer or [B = {B}] integers, got {sof.dtype} {sof.shape}")
+        sof = np.ascontiguousarray(np.broadcast_to(sof, (B,)), dtype=np.int32)
+        if ((sof < 0) | (sof >= len(sets))).any():
+            raise ValueError(f"set_of outside [0, {len(sets)})")
+        n = self._n()
+        dev = eng.device
+        d_set = torch.from_numpy(sof).to(dev)
+        new = lambda dt: torch.empty(max(n, 1), B, dtype=dt, device=dev)[:n]   # (no ticks yet: still valid pointers)
+        clear = new(torch.float64)
+        who, hit, off_tick = (new(torch.int32) for _ in range(3))
+        ego_c = (C.c_double * 3)(*ego)
+        _cabi.check(eng.lib.jsim_loop_eval_static(
+            eng._ctx, B, n, _ptr(self.rec), _ptr(self.flags), _ptr(self.x0_first), _ptr(self.loop.x0_spawn), _ptr(d_set),
+            len(sets), set_off.ctypes.data_as(C.c_void_p), n_rows, rows.ctypes.data_as(C.c_void_p), C.cast(ego_c, C.c_void_p),
+            int(bool(include_hidden)), _ptr(clear), _ptr(who), _ptr(hit), _ptr(off_tick), eng._stream()),
+            eng._ctx, "jsim_loop_eval_static")
+        hit = hit.cpu().numpy()
+        return {"clear": clear.cpu().numpy(), "who": who.cpu().numpy(), "hit": hit, "contact": hit >= 0,
+                "off_tick": off_tick.cpu().numpy(), "margin": margin, "include_hidden": bool(include_hidden),
+                "ego_shape": tuple(float(v) for v in ego), "set_of": sof}
+
 
 def _register_recorder(engine: BatchedMPC, rec: Optional[Recorder]):
     """jsim_loop_set_recorder (None: clear).  The engine keeps the registered buffers alive; the recorder it replaces is marked

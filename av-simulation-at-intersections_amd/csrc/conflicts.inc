@@ -31,7 +31,8 @@ struct ConflictP {
 #define JCF_END (JSIM_REC_GOAL | JSIM_REC_AGE)
 
 // An ego's pose at the start of tick k: x_first, x_spawn behind a record that ended an episode, or the record before
-__device__ __forceinline__ void jcf_ego_pose(const ConflictP &P, int e, int k, double &x, double &y, double &yaw)
+// (PT: ConflictP, or StaticP of static_conflicts.inc -- the recorder's buffers under the same names)
+template <class PT> __device__ __forceinline__ void jcf_ego_pose(const PT &P, int e, int k, double &x, double &y, double &yaw)
 {
     if (k == 0) {
         const double *p = P.x_first + 4 * (size_t)e;
@@ -46,7 +47,7 @@ __device__ __forceinline__ void jcf_ego_pose(const ConflictP &P, int e, int k, d
 }
 
 // The ticks of a chunk that end an episode: the record's flag, or the last record
-__device__ __forceinline__ unsigned long long jcf_ends(const ConflictP &P, int b, int k)
+template <class PT> __device__ __forceinline__ unsigned long long jcf_ends(const PT &P, int b, int k)
 {
     return __ballot(k < P.n_ticks && (k == P.n_ticks - 1 || (P.flags[(size_t)k * P.B + b] & JCF_END) != 0));
 }

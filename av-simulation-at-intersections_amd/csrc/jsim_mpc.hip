@@ -1365,6 +1365,8 @@ struct jsim_ctx {
     std::vector<double> h_shapes;  // host copy [n_shapes][4] (the thresholds follow jsim_loop_set_geometry)
     int n_shapes = 0;
     DevArray<double4> d_conflict_rows; // [n_obs] (cc_front, cc_rear, thr, thr_sq) of jsim_loop_eval_conflicts' last call with a table
+    DevArray<double> d_static_rows;    // [n_rows][JSIM_STATIC_ROW] and
+    DevArray<int> d_static_off;        // [n_sets + 1] of jsim_loop_eval_static's last call
     DevArray<double2> d_pcc;
     DevArray<double2> d_pred_cc;
     int pred_n_obs = 0, pred_n_steps = 0;
@@ -2360,6 +2362,68 @@ extern "C" int jsim_loop_eval_conflicts(jsim_ctx *ctx, int32_t B, int32_t n_tick
                          table ? ctx->d_conflict_rows.p : nullptr, cc_f, cc_r, double4{cc_f, cc_r, thr_ee, jsim_sqrt_threshold(thr_ee)},
                          clear, who, row, hit_tick, hit_frame, hit_xy};
     hipLaunchKernelGGL(conflict_ticks_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, P);
+    HIP_TRY(ctx, hipGetLastError());
+    return 0;
+}
+
+#include "static_conflicts.inc"
+
+// Static-obstacle clearance and contact per recorded tick: DEVICE pointers for the recorder's buffers, set_of
+// and the outputs, HOST pointers for `set_off`, `rows` and `ego_shape` (checked here, copied to the device inside the call); one
+// launch on `stream`, one wavefront per ego.
+extern "C" int jsim_loop_eval_static(jsim_ctx *ctx, int32_t B, int32_t n_ticks, const double *rec, const int32_t *flags, const double *x_first,
+                                     const double *x_spawn, const int32_t *set_of, int32_t n_sets, const int32_t *set_off, int32_t n_rows,
+                                     const double *rows, const double *ego_shape, int32_t include_hidden, double *clear, int32_t *who,
+                                     int32_t *hit, int32_t *off_tick, void *stream)
+{
+    const char *const F = "jsim_loop_eval_static";
+    // (the argument checks come first: they need no context and no device)
+    if (B < 0 || n_ticks < 0 || n_sets < 0 || n_rows < 0)
+        return fail(ctx, -22, "%s: B=%d n_ticks=%d n_sets=%d n_rows=%d", F, B, n_ticks, n_sets, n_rows);
+    if (include_hidden != 0 && include_hidden != 1) return fail(ctx, -22, "%s: include_hidden=%d is neither 0 nor 1", F, include_hidden);
+    if (!ego_shape) return fail(ctx, -22, "%s: null ego_shape", F);
+    if (!set_off && n_sets > 0) return fail(ctx, -22, "%s: null set_off with n_sets=%d", F, n_sets);
+    if (!rows && (n_sets > 0 || n_rows > 0)) return fail(ctx, -22, "%s: null rows with n_sets=%d n_rows=%d", F, n_sets, n_rows);
+    if (!rec || !flags || !x_first || !x_spawn || !set_of || !clear || !who || !hit || !off_tick)
+        return fail(ctx, -22, "%s: null device pointer", F);
+    const double cc_f = ego_shape[0], cc_r = ego_shape[1], r_ego = ego_shape[2];
+    if (!std::isfinite(cc_f) || !std::isfinite(cc_r)) return fail(ctx, -22, "%s: ego_shape: a circle offset that is not finite", F);
+    if (!(r_ego > 0.0) || !std::isfinite(r_ego)) return fail(ctx, -22, "%s: ego_shape: radius %g is not positive and finite", F, r_ego);
+    if (set_off) {
+        if (set_off[0] != 0) return fail(ctx, -22, "%s: set_off[0]=%d, not 0", F, set_off[0]);
+        for (int s = 0; s < n_sets; ++s)
+            if (set_off[s + 1] < set_off[s]) return fail(ctx, -22, "%s: set_off decreases at set %d", F, s);
+    }
+    if ((set_off ? set_off[n_sets] : 0) != n_rows)
+        return fail(ctx, -22, "%s: set_off ends at %d, not at n_rows=%d", F, set_off ? set_off[n_sets] : 0, n_rows);
+    for (int i = 0; i < n_rows; ++i) {
+        const double *r = rows + JSIM_STATIC_ROW * (size_t)i;
+        if (r[0] != 0.0 && r[0] != 1.0) return fail(ctx, -22, "%s: rows[%d]: kind %g is neither 0 (box) nor 1 (circle)", F, i, r[0]);
+        if (r[1] != 0.0 && r[1] != 1.0) return fail(ctx, -22, "%s: rows[%d]: hidden %g is neither 0 nor 1", F, i, r[1]);
+        if (!(r[2] >= 1.0 && r[2] <= 8.0) || r[2] != std::floor(r[2])) return fail(ctx, -22, "%s: rows[%d]: n_hp %g outside 1..8", F, i, r[2]);
+        for (int j = 3; j < 7; ++j)
+            if (!std::isfinite(r[j])) return fail(ctx, -22, "%s: rows[%d]: geometry entry %d is not finite", F, i, j);
+        for (int j = 8; j < 8 + 3 * (int)r[2]; ++j)
+            if (!std::isfinite(r[j])) return fail(ctx, -22, "%s: rows[%d]: half-plane entry %d is not finite", F, i, j);
+        if (r[0] == 1.0 && !(r[5] > 0.0)) return fail(ctx, -22, "%s: rows[%d]: circle radius %g is not positive", F, i, r[5]);
+        if (r[0] == 0.0 && (r[3] > r[5] || r[4] > r[6])) return fail(ctx, -22, "%s: rows[%d]: box with x1 > x2 or y1 > y2", F, i);
+    }
+    if (!ctx) return fail(nullptr, -22, "%s: null ctx", F);
+    if (B == 0 || n_ticks == 0) return 0;
+    DeviceGuard dev_guard(ctx->device);
+    JSIM_GUARD_OK(ctx);
+    if (n_sets > 0) {
+        HIP_TRY(ctx, hipDeviceSynchronize()); // an earlier call's launch may still read the tables that are replaced
+        HIP_TRY(ctx, ctx->d_static_off.reserve((size_t)n_sets + 1));
+        HIP_TRY(ctx, hipMemcpy(ctx->d_static_off, set_off, sizeof(int32_t) * ((size_t)n_sets + 1), hipMemcpyHostToDevice));
+        if (n_rows > 0) {
+            HIP_TRY(ctx, ctx->d_static_rows.reserve((size_t)n_rows * JSIM_STATIC_ROW));
+            HIP_TRY(ctx, hipMemcpy(ctx->d_static_rows, rows, sizeof(double) * (size_t)n_rows * JSIM_STATIC_ROW, hipMemcpyHostToDevice));
+        }
+    }
+    const StaticP P = {B, n_ticks, n_sets, include_hidden, rec, flags, x_first, x_spawn, set_of, n_sets > 0 ? ctx->d_static_off.p : nullptr,
+                       n_rows > 0 ? ctx->d_static_rows.p : nullptr, cc_f, cc_r, r_ego, clear, who, hit, off_tick};
+    hipLaunchKernelGGL(static_ticks_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, P);
     HIP_TRY(ctx, hipGetLastError());
     return 0;
 }

@@ -3,7 +3,8 @@ main/lib/simulation.py:50-88, and `obstacles_positions`, main/scenarios/mpc_inte
 the device recorder wrote (jsim_loop_set_recorder): rec [n][B][7] = x, y, yaw, v, delta, a, xref_deviation per tick, flags
 [n][B] (FAILED / GOAL / AGE bits), obs [n][n_obs][6] = the scripted vehicles' get() tuples.  Pure numpy: the host-side half of
 the recorder, testable without a device.  reason_series does the same for the per-tick stakeholder reasons,
-conflict_episodes for the clearance and first contact of every episode (section 17)."""
+conflict_episodes for the clearance and first contact of every episode (section 17), static_episodes for the static obstacles
+(section 18)."""
 from __future__ import annotations
 
 from typing import List, Optional
@@ -145,6 +146,33 @@ def conflict_episodes(result: dict, flags: np.ndarray):
                 if not np.isnan(c).all():
                     k = int(np.nanargmin(c))
                     ep.update(min_clear=float(c[k]), min_clear_tick=k0 + k, closest_vehicle=int(who[k0 + k, b]))
+            eps.append(ep)
+        out.append(eps)
+    return out
+
+
+def static_episodes(result: dict, flags: np.ndarray):
+    """The static-obstacle clearance and contact of a recorder (Recorder.static_conflicts: `clear`, `who`, `hit`, `off_tick`) per
+    ego and episode, split where ego_histories splits (episode_bounds).  Returns a list over egos of lists over episodes of dicts:
+    contact (bool), tick (the first tick that touches an obstacle, -1: none), obstacle (the `hit` of that tick, -1), min_clear and
+    min_clear_tick (the episode's smallest clearance and its first tick; NaN / -1 for an ego without obstacles or an episode without
+    a tick yet), closest_obstacle (the place in its set of the obstacle that came closest), ticks_off (how many ticks touch)."""
+    f = np.asarray(flags).reshape(np.shape(flags)[0], -1)
+    clear, who, hit = np.asarray(result["clear"], dtype=np.float64), np.asarray(result["who"]), np.asarray(result["hit"])
+    out = []
+    for b in range(f.shape[1]):
+        eps = []
+        for k0, k1, _ in episode_bounds(f[:, b]):
+            ep = {"contact": False, "tick": -1, "obstacle": -1, "min_clear": float("nan"), "min_clear_tick": -1,
+                  "closest_obstacle": -1, "ticks_off": 0}
+            if k1 > k0:
+                tick = int(result["off_tick"][k0, b])
+                if tick >= 0:
+                    ep.update(contact=True, tick=tick, obstacle=int(hit[tick, b]), ticks_off=int((hit[k0:k1, b] >= 0).sum()))
+                c = clear[k0:k1, b]
+                if not np.isnan(c).all():
+                    k = int(np.nanargmin(c))
+                    ep.update(min_clear=float(c[k]), min_clear_tick=k0 + k, closest_obstacle=int(who[k0 + k, b]))
             eps.append(ep)
         out.append(eps)
     return out

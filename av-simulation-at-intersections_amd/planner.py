@@ -88,11 +88,9 @@ class RouteQuery:
     obstacles: List[np.ndarray]                     # half-plane sets [a, b, c], one array per obstacle (margin included)
 
 
-def intersection_query(start_pos: int, turn_indicator: int, margin: float, start_lane: int = 1, goal_lane: int = 1,
-                       number_of_lanes: int = 0) -> RouteQuery:
-    """The reference's scenarios as a route query: number_of_lanes = 0 -> main/envs/intersection.py:10-160 (one lane per
-    direction, 4 m road, 2 m island, corner radius 6); number_of_lanes >= 1 -> main/envs/intersection_multi_lanes.py:9-170
-    (lane_width 4, median 2, as mpc_intersection_multi_lane.py builds it with number_of_lanes = 2)."""
+def _intersection_scene(start_pos: int, turn_indicator: int, start_lane: int, goal_lane: int, number_of_lanes: int):
+    """(start, goal, goal box, obstacle primitives) of the reference's intersection builders: what intersection_query and
+    intersection_obstacles share."""
     pi = np.pi
     if number_of_lanes == 0:
         road, island, pav, length, corner = 4, 2, 5, 30, 6
@@ -122,20 +120,19 @@ def intersection_query(start_pos: int, turn_indicator: int, margin: float, start
     else:
         gw = (goal_w[1], goal_w[0])
     gb = (goal[0] - gw[0] / 2, goal[1] - gw[1] / 2, goal[0] + gw[0] / 2, goal[1] + gw[1] / 2)
-    m = margin
     far = length / 2 + dc
     side = half_road + pav / 2
     obs = [
-        box_halfplanes((island, length), (0, -far), m), circle_halfplanes(island / 2, (0, -dc), m),          # south median
-        box_halfplanes((island, length), (0, far), m), circle_halfplanes(island / 2, (0, dc), m),            # north median
-        box_halfplanes((length, island), (-far, 0), m), circle_halfplanes(island / 2, (-dc, 0), m),          # west median
-        box_halfplanes((length, island), (far, 0), m), circle_halfplanes(island / 2, (dc, 0), m),            # east median
-        circle_halfplanes(corner_r, (-dc, -dc), m), circle_halfplanes(corner_r, (-dc, dc), m),                # corners
-        circle_halfplanes(corner_r, (dc, dc), m), circle_halfplanes(corner_r, (dc, -dc), m),
-        box_halfplanes((pav, length), (-side, -far), m), box_halfplanes((pav, length), (side, -far), m),       # pavements: south
-        box_halfplanes((length, pav), (-far, -side), m), box_halfplanes((length, pav), (-far, side), m),       # west
-        box_halfplanes((pav, length), (-side, far), m), box_halfplanes((pav, length), (side, far), m),         # north
-        box_halfplanes((length, pav), (far, -side), m), box_halfplanes((length, pav), (far, side), m),         # east
+        ("box", (island, length), (0, -far), False), ("circle", island / 2, (0, -dc), False),          # south median
+        ("box", (island, length), (0, far), False), ("circle", island / 2, (0, dc), False),            # north median
+        ("box", (length, island), (-far, 0), False), ("circle", island / 2, (-dc, 0), False),          # west median
+        ("box", (length, island), (far, 0), False), ("circle", island / 2, (dc, 0), False),            # east median
+        ("circle", corner_r, (-dc, -dc), False), ("circle", corner_r, (-dc, dc), False),                # corners
+        ("circle", corner_r, (dc, dc), False), ("circle", corner_r, (dc, -dc), False),
+        ("box", (pav, length), (-side, -far), False), ("box", (pav, length), (side, -far), False),       # pavements: south
+        ("box", (length, pav), (-far, -side), False), ("box", (length, pav), (-far, side), False),       # west
+        ("box", (pav, length), (-side, far), False), ("box", (pav, length), (side, far), False),         # north
+        ("box", (length, pav), (far, -side), False), ("box", (length, pav), (far, side), False),         # east
     ]
     # the hidden boxes that close the oncoming lanes of the four arms (envs/intersection.py:150-208, intersection_multi_lanes.py
     # :183-213): lateral sign per (start_pos, arm W / E / S / N); the multi-lane file's east box for start_pos 4 is centred with
@@ -144,10 +141,81 @@ def intersection_query(start_pos: int, turn_indicator: int, margin: float, start
     gl_ = (road_total + island) / 2
     sign = {1: (-1, 1, -1, -1), 2: (1, 1, 1, -1), 3: (-1, 1, 1, 1), 4: (-1, -1, 1, -1)}[start_pos]
     ge = (lane_w + island) / 2 if (number_of_lanes and start_pos == 4) else gl_
-    obs += [box_halfplanes((length, road_total), (-far, sign[0] * gl_), m), box_halfplanes((length, road_total), (far, sign[1] * ge), m),
-            box_halfplanes((road_total, length), (sign[2] * gl_, -far), m), box_halfplanes((road_total, length), (sign[3] * gl_, far), m)]
+    obs += [("box", (length, road_total), (-far, sign[0] * gl_), True), ("box", (length, road_total), (far, sign[1] * ge), True),
+            ("box", (road_total, length), (sign[2] * gl_, -far), True), ("box", (road_total, length), (sign[3] * gl_, far), True)]
+    return start, goal, gb, obs
+
+
+def intersection_obstacles(start_pos: int, turn_indicator: int, start_lane: int = 1, goal_lane: int = 1,
+                           number_of_lanes: int = 0) -> list:
+    """The obstacles list of the reference's intersection scenarios (intersection_query's, in list order) as primitives:
+    ("box", xy_width, xy_center, hidden) and ("circle", radius, xy_center, hidden), the arguments of BoxObstacle / CircleObstacle
+    (main/lib/obstacles.py).  The last four are the hidden boxes that close the oncoming lanes.  static_obstacle_rows takes them."""
+    return _intersection_scene(start_pos, turn_indicator, start_lane, goal_lane, number_of_lanes)[3]
+
+
+def primitive_halfplanes(obstacle, margin: float) -> np.ndarray:
+    """to_convex(margin) of one ("box", ...) / ("circle", ...) primitive."""
+    kind, size, centre = obstacle[:3]
+    if kind == "box":
+        return box_halfplanes(size, centre, margin)
+    if kind == "circle":
+        return circle_halfplanes(size, centre, margin)
+    raise ValueError(f"an obstacle primitive is ('box', xy_width, xy_center[, hidden]) or ('circle', radius, xy_center[, hidden]), got {obstacle!r}")
+
+
+def intersection_query(start_pos: int, turn_indicator: int, margin: float, start_lane: int = 1, goal_lane: int = 1,
+                       number_of_lanes: int = 0) -> RouteQuery:
+    """The reference's scenarios as a route query: number_of_lanes = 0 -> main/envs/intersection.py:10-160 (one lane per
+    direction, 4 m road, 2 m island, corner radius 6); number_of_lanes >= 1 -> main/envs/intersection_multi_lanes.py:9-170
+    (lane_width 4, median 2, as mpc_intersection_multi_lane.py builds it with number_of_lanes = 2)."""
+    start, goal, gb, prims = _intersection_scene(start_pos, turn_indicator, start_lane, goal_lane, number_of_lanes)
     return RouteQuery(start=tuple(float(v) for v in start), goal=tuple(float(v) for v in goal), goal_box=tuple(float(v) for v in gb),
-                      tol=float(np.pi / 16), obstacles=obs)
+                      tol=float(np.pi / 16), obstacles=[primitive_halfplanes(o, margin) for o in prims])
+
+
+STATIC_ROW = 32                    # JSIM_STATIC_ROW: doubles per obstacle row of jsim_loop_eval_static (DESIGN.md section 18)
+
+
+def static_obstacle_rows(obstacles, margin: float) -> np.ndarray:
+    """[n][32] rows of jsim_loop_eval_static for one obstacle list: 0 kind (0 box, 1 circle), 1 hidden,
+    2 n_hp, 3-6 geometry (box: x1, y1, x2, y2 as BoxObstacle.__init__ computes xy1 / xy2; circle: cx, cy, r, 0), 8-31 the half-planes
+    of to_convex(margin) in the reference's row order.  An obstacle is one of the reference's objects, duck-typed (.xy1 / .xy2 or
+    .radius / .xy_center, .hidden, its own .to_convex(margin)), or a primitive ("box", xy_width, xy_center[, hidden]) /
+    ("circle", radius, xy_center[, hidden]).  ValueError: anything else, a margin that is not finite and >= 0, more than eight
+    half-planes."""
+    margin = float(margin)
+    if not (math.isfinite(margin) and margin >= 0.0):
+        raise ValueError(f"margin must be finite and >= 0, got {margin!r}")
+    obstacles = list(obstacles)
+    rows = np.zeros((len(obstacles), STATIC_ROW))
+    for r, o in zip(rows, obstacles):
+        if isinstance(o, (tuple, list)):
+            hp = primitive_halfplanes(o, margin)
+            hidden = bool(o[3]) if len(o) > 3 else False
+            if o[0] == "box":
+                (w, h), (cx, cy) = o[1], o[2]
+                kind, geom = 0, (cx - w / 2, cy - h / 2, cx + w / 2, cy + h / 2)
+            else:
+                kind, geom = 1, (o[2][0], o[2][1], o[1], 0.0)
+        elif hasattr(o, "xy1") and hasattr(o, "xy2"):
+            kind, geom, hidden, hp = 0, (*o.xy1, *o.xy2), bool(o.hidden), o.to_convex(margin)
+        elif hasattr(o, "radius") and hasattr(o, "xy_center"):
+            kind, geom, hidden, hp = 1, (*o.xy_center, o.radius, 0.0), bool(o.hidden), o.to_convex(margin)
+        else:
+            raise ValueError(f"not a box (.xy1 / .xy2), a circle (.radius / .xy_center) or a primitive tuple: {o!r}")
+        hp = np.asarray(hp, dtype=np.float64)
+        if hp.ndim != 2 or hp.shape[1] != 3 or not 1 <= hp.shape[0] <= 8:
+            raise ValueError(f"to_convex(margin) must give 1..8 half-planes [a, b, c], got shape {hp.shape}")
+        r[0], r[1], r[2], r[3:7] = kind, hidden, hp.shape[0], geom
+        r[8:8 + 3 * hp.shape[0]] = hp.reshape(-1)
+    return rows
+
+
+def scenario_obstacles(scenario) -> list:
+    """The obstacles list of a reference Scenario (main/lib/scenario.py), in list order: what static_obstacle_rows and
+    Recorder.static_conflicts take as one set."""
+    return list(scenario.obstacles)
 
 
 @dataclass

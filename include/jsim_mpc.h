@@ -451,6 +451,39 @@ int jsim_loop_eval_conflicts(jsim_ctx *ctx, int32_t B, int32_t n_ticks, const do
                              double *clear, int32_t *who, int32_t *row, int32_t *hit_tick, int32_t *hit_frame, double *hit_xy,
                              void *stream);
 
+/* ---- static-obstacle clearance and contact per recorded tick: the realised poses of a run against the scenario's obstacles ----
+ * Answers for driven poses what the reference only asks of planned ones: check_collision (main/lib/obstacles.py:157-176) on
+ * Obstacle.to_convex(margin) (:82-93 box, :134-148 circle) -- the planner's collision test, main/lib/mp_search_ww_generic.py:199-215
+ * -- and BoxObstacle / CircleObstacle.distance_to_point (main/lib/obstacles.py:95-103, :150-154), at the two collision circle
+ * centres of main/lib/trajectories.py:11-55 (car_trajectory_to_collision_point_trajectories) -- per tick and per episode of every
+ * ego, from the recorder's buffers (jsim_loop_set_recorder), after the loop.  One wavefront per ego, 64 ticks at a time.  DESIGN.md
+ * section 18 is the contract.
+ *   DEVICE pointers: rec [n_ticks][B][7], flags [n_ticks][B], x_first [B][4], x_spawn [B][4] exactly as jsim_loop_eval_conflicts
+ *   takes them (the ego's pose at the start of tick k by the same rule); set_of [B]: the ego's obstacle set; and every output.
+ *   HOST pointers: set_off [n_sets + 1]: set s is the rows [set_off[s], set_off[s + 1]), in the order of the scenario's obstacles
+ *   list (a set may be empty, its length has no cap); rows [n_rows][JSIM_STATIC_ROW]: per obstacle 0 kind (0 box, 1 circle), 1 hidden
+ *   (0 / 1), 2 n_hp (1..8), 3-6 geometry (box: x1, y1, x2, y2; circle: cx, cy, r, 0), 7 reserved, 8-31 the half-planes [8][3] =
+ *   (a, b, c) of to_convex(margin) in the reference's row order; ego_shape [3] = cc_front, cc_rear, radius (jsim_loop_set_geometry's
+ *   values).  The tables are checked on the host and copied to the device inside the call (one synchronising copy).
+ *   include_hidden 0: rows whose hidden entry is 1 are skipped, for touch and clearance alike (their indices still count).
+ *   Out, per ego and tick [n_ticks][B]: clear = the minimum over the included obstacles and the two circle centres of
+ *   distance_to_point(centre) - radius (-radius where a centre lies inside an obstacle), who = that obstacle's place in its set (the
+ *   lowest on ties), hit = the lowest place of an obstacle for which, at one of the two centres, every half-plane has
+ *   (a * x + b * y) + c <= 0 (the sum unfused, in that order), or -1; without an included obstacle NaN / -1 / -1.  Per episode, at the
+ *   slot of its first tick (every other slot -1): off_tick = the first tick of the episode with hit >= 0, or -1.
+ *   Refused (-22) before any device call, jsim_last_error naming the argument: B, n_ticks, n_sets or n_rows < 0; include_hidden not 0
+ *   or 1; a null pointer other than stream (set_off and rows may be NULL with n_sets = 0 only); an ego radius that is not positive
+ *   and finite, a circle offset that is not finite; offsets that do not start at 0, that decrease or that do not end at n_rows; a
+ *   row with a kind or hidden entry other than 0 / 1, n_hp outside 1..8, a geometry or used half-plane entry that is not finite, a
+ *   circle radius <= 0, a box with x1 > x2 or y1 > y2; a null ctx.  n_ticks = 0 or B = 0 returns 0 and writes nothing.  A set_of
+ *   outside [0, n_sets) would need a device read to detect: the kernel treats it as an empty set, and the Python surface
+ *   (Recorder.static_conflicts) refuses it with ValueError. */
+enum { JSIM_STATIC_ROW = 32 };
+int jsim_loop_eval_static(jsim_ctx *ctx, int32_t B, int32_t n_ticks, const double *rec, const int32_t *flags, const double *x_first,
+                          const double *x_spawn, const int32_t *set_of, int32_t n_sets, const int32_t *set_off, int32_t n_rows,
+                          const double *rows, const double *ego_shape, int32_t include_hidden, double *clear, int32_t *who, int32_t *hit,
+                          int32_t *off_tick, void *stream);
+
 /* ---- the job's one exchange: the final trajectory gather over RCCL / xGMI ----
  * The reference has no multi-process code at all (its only multi-ego code is the serial Python loop of
  * main/scenarios/interactive_mpc.py:119-172); egos are independent (main/lib/mpc.py:141-211), so ranks own contiguous shards
