@@ -55,14 +55,14 @@ class Recorder:
         """True once more ticks ran than the recorder holds (the later ones were dropped)."""
         return history.recorded_ticks(self.ticks_run, self.cap)[1]
 
-    def _n(self) -> int:
+    def _n(self, stacklevel: int = 3) -> int:
         if self.superseded:
             warnings.warn("a later loop on this engine replaced this recorder: its records stopped at that point",
-                          RuntimeWarning, stacklevel=3)
+                          RuntimeWarning, stacklevel=stacklevel)
         n, over = history.recorded_ticks(self.ticks_run, self.cap)
         if over:
             warnings.warn(f"the recorder holds {self.cap} ticks, {self.ticks_run} ran: the last {self.ticks_run - self.cap} are not "
-                          "recorded", RuntimeWarning, stacklevel=3)
+                          "recorded", RuntimeWarning, stacklevel=stacklevel)
         return n
 
     def histories(self, b: int):
@@ -100,13 +100,23 @@ class Recorder:
         bool (policymaker, driver, cyclist under the threshold); first_replan [B] (-1: none); carry [B][3] as the next tick would
         meet it; and the par, threshold and veh_of used.  An ego without a cyclist has NaN in driver, cyclist and distance and
         never triggers on them.  ValueError: no vehicles recorded, a bad par / threshold / carry, a cyclist index out of range."""
+        d = self._reasons_device(par, threshold, cyclist, carry)
+        val, trig = d["val"].cpu().numpy(), d["trig"].cpu().numpy()
+        return {"policymaker": val[:, :, 0], "driver": val[:, :, 1], "cyclist": val[:, :, 2], "distance": val[:, :, 3],
+                "timers": d["timers"].cpu().numpy(), "replan": (trig & 1) != 0, "below": ((trig[:, :, None] >> np.arange(1, 4)) & 1) != 0,
+                "first_replan": d["first"].cpu().numpy(), "carry": d["carry"].cpu().numpy(), "par": np.array(d["par"]),
+                "threshold": np.array(d["threshold"]), "veh_of": np.array(d["veh_of"], dtype=np.int32)}
+
+    def _reasons_device(self, par=None, threshold=0.7, cyclist=None, carry=None, n=None) -> dict:
+        """reasons() up to the launch: the outputs as device tensors (val [n][B][4], timers, trig, first, carry) and the host
+        arguments used (par, threshold, veh_of).  n: the recorded ticks, where the caller has asked for them already."""
         from . import reasons as _reasons
         eng = self.loop.eng
         B = eng.B
         if self.obs is None:
             raise ValueError("this recorder holds no vehicle records (a loop without scripted vehicles): there is no cyclist to evaluate")
         par, thr, veh, car = _reasons.tick_inputs(B, self.n_obs, eng.dt, par, threshold, cyclist, carry, self.default_cyclist)
-        n = self._n()
+        n = self._n(4) if n is None else n
         dev = eng.device
         up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(dev)
         d_par, d_thr, d_veh, d_car = up(par, np.float64), up(thr, np.float64), up(veh, np.int32), up(car, np.float64)
@@ -118,12 +128,7 @@ class Recorder:
                                                    _ptr(self.x0_first), _ptr(self.loop.x0_spawn), _ptr(d_veh), _ptr(d_par), _ptr(d_thr),
                                                    _ptr(d_car), _ptr(val), _ptr(tim), _ptr(trig), _ptr(first), eng._stream()),
                     eng._ctx, "jsim_loop_eval_reasons")
-        val, trig = val.cpu().numpy(), trig.cpu().numpy()
-        return {"policymaker": val[:, :, 0], "driver": val[:, :, 1], "cyclist": val[:, :, 2], "distance": val[:, :, 3],
-                "timers": tim.cpu().numpy(), "replan": (trig & 1) != 0, "below": ((trig[:, :, None] >> np.arange(1, 4)) & 1) != 0,
-                "first_replan": first.cpu().numpy(), "carry": d_car.cpu().numpy(), "par": np.array(par), "threshold": np.array(thr),
-                "veh_of": np.array(veh, dtype=np.int32)}
-
+        return {"val": val, "timers": tim, "trig": trig, "first": first, "carry": d_car, "par": par, "threshold": thr, "veh_of": veh}
 
     def vehicle_ranges(self) -> np.ndarray:
         """Each ego's vehicles [lo, hi) among the recorded ones ([B][2] int32): all of a shared list, its set's slice under a traffic
@@ -157,6 +162,15 @@ class Recorder:
         reference's return value; -1 / NaN elsewhere); and the frame_window, veh_range, mate_range and ego_shape used.  An ego
         without vehicles and mates has NaN / -1 everywhere.  history.conflict_episodes splits the result into episodes.
         ValueError: a frame_window outside 0..20, a bad shapes table, a range outside its table, more than eight vehicles."""
+        d = self._conflicts_device(frame_window, shapes, mates)
+        row = d["row"].cpu().numpy()
+        return {"clear": d["clear"].cpu().numpy(), "who": d["who"].cpu().numpy(), "row": row, "contact": row >= 0,
+                "hit_tick": d["hit_tick"].cpu().numpy(), "hit_frame": d["hit_frame"].cpu().numpy(), "hit_xy": d["hit_xy"].cpu().numpy(),
+                "frame_window": d["frame_window"], "veh_range": d["veh_range"], "mate_range": d["mate_range"], "ego_shape": d["ego_shape"]}
+
+    def _conflicts_device(self, frame_window: int = 0, shapes=None, mates=None, n=None) -> dict:
+        """conflicts() up to the launch: the outputs as device tensors (clear, who, row, hit_tick, hit_frame, hit_xy) and the host
+        arguments used (frame_window, veh_range, mate_range, ego_shape)."""
         eng = self.loop.eng
         B, n_obs = eng.B, self.n_obs
         w = int(frame_window)
@@ -180,7 +194,7 @@ class Recorder:
         if (count > MAX_OBS).any():
             b = int(np.argmax(count))
             raise ValueError(f"ego {b} would meet {int(count[b])} vehicles and mates (max {MAX_OBS})")
-        n = self._n()
+        n = self._n(4) if n is None else n
         dev = eng.device
         up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(dev)
         d_veh, d_mate = up(veh), up(mate)
@@ -194,9 +208,7 @@ class Recorder:
             shapes.ctypes.data_as(C.c_void_p) if shapes is not None and n_obs else None, C.cast(ego_c, C.c_void_p), w,
             _ptr(clear), _ptr(who), _ptr(row), _ptr(hit_tick), _ptr(hit_frame), _ptr(hit_xy), eng._stream()),
             eng._ctx, "jsim_loop_eval_conflicts")
-        row = row.cpu().numpy()
-        return {"clear": clear.cpu().numpy(), "who": who.cpu().numpy(), "row": row, "contact": row >= 0,
-                "hit_tick": hit_tick.cpu().numpy(), "hit_frame": hit_frame.cpu().numpy(), "hit_xy": hit_xy.cpu().numpy(),
+        return {"clear": clear, "who": who, "row": row, "hit_tick": hit_tick, "hit_frame": hit_frame, "hit_xy": hit_xy,
                 "frame_window": w, "veh_range": veh, "mate_range": mate, "ego_shape": tuple(float(v) for v in ego)}
 
     def static_conflicts(self, obstacles, set_of=None, margin=None, include_hidden: bool = False) -> dict:
@@ -214,6 +226,15 @@ class Recorder:
         or -1; -1 elsewhere); and the margin, include_hidden, ego_shape and set_of used.  An ego whose set has no included obstacle
         has NaN / -1 / -1.  history.static_episodes splits the result into episodes.
         ValueError: an obstacle that is neither kind, a set_of outside the sets, a margin that is not finite and >= 0."""
+        d = self._static_device(obstacles, set_of, margin, include_hidden)
+        hit = d["hit"].cpu().numpy()
+        return {"clear": d["clear"].cpu().numpy(), "who": d["who"].cpu().numpy(), "hit": hit, "contact": hit >= 0,
+                "off_tick": d["off_tick"].cpu().numpy(), "margin": d["margin"], "include_hidden": d["include_hidden"],
+                "ego_shape": d["ego_shape"], "set_of": d["set_of"]}
+
+    def _static_device(self, obstacles, set_of=None, margin=None, include_hidden: bool = False, n=None) -> dict:
+        """static_conflicts() up to the launch: the outputs as device tensors (clear, who, hit, off_tick) and the host arguments
+        used (margin, include_hidden, ego_shape, set_of)."""
         from . import planner
         eng = self.loop.eng
         B = eng.B
@@ -234,7 +255,7 @@ class Recorder:
         sof = np.ascontiguousarray(np.broadcast_to(sof, (B,)), dtype=np.int32)
         if ((sof < 0) | (sof >= len(sets))).any():
             raise ValueError(f"set_of outside [0, {len(sets)})")
-        n = self._n()
+        n = self._n(4) if n is None else n
         dev = eng.device
         d_set = torch.from_numpy(sof).to(dev)
         new = lambda dt: torch.empty(max(n, 1), B, dtype=dt, device=dev)[:n]   # (no ticks yet: still valid pointers)
@@ -246,10 +267,65 @@ class Recorder:
             len(sets), set_off.ctypes.data_as(C.c_void_p), n_rows, rows.ctypes.data_as(C.c_void_p), C.cast(ego_c, C.c_void_p),
             int(bool(include_hidden)), _ptr(clear), _ptr(who), _ptr(hit), _ptr(off_tick), eng._stream()),
             eng._ctx, "jsim_loop_eval_static")
-        hit = hit.cpu().numpy()
-        return {"clear": clear.cpu().numpy(), "who": who.cpu().numpy(), "hit": hit, "contact": hit >= 0,
-                "off_tick": off_tick.cpu().numpy(), "margin": margin, "include_hidden": bool(include_hidden),
+        return {"clear": clear, "who": who, "hit": hit, "off_tick": off_tick, "margin": margin, "include_hidden": bool(include_hidden),
                 "ego_shape": tuple(float(v) for v in ego), "set_of": sof}
+
+    def summary(self, conflicts=None, static=None, reasons=None) -> dict:
+        """One row per recorded episode of every ego (jsim_loop_summarise_episodes): did the ego arrive, how
+        many ticks it took, how far it drove and deviated, how close it came to a vehicle and to an obstacle, whether it touched
+        either, whether the replan trigger fired -- reduced on the device; the per-tick series are not read back.
+
+        conflicts / static / reasons: None (the group's columns stay NaN / -1 / 0), True (conflicts() / static_conflicts() /
+        reasons() with their defaults; `static` has no default for its obstacles) or a dict of that method's keyword arguments.
+        Returns numpy arrays: ep_off [B + 1] (ego b's rows are [ep_off[b], ep_off[b + 1]), in order of time) and one array [E] per
+        column of history.EP_INT and history.EP_DOUBLE (ego, k0, n, end, failed, dev_tick, veh_tick, veh_who, veh_hit_tick,
+        veh_hit_frame, st_tick, st_who, st_off_tick, st_obstacle, st_ticks_off, replan_tick; length, v_mean, v_max, a_min, a_max,
+        delta_absmax, dev_max, dev_mean, veh_clear, veh_hit_x, veh_hit_y, st_clear, pm_min, driver_min, cyclist_min, dist_min);
+        duration [E] = n * dt; dt; and under `conflicts`, `static`, `reasons` the arguments that evaluation used (None: not
+        requested).  history.episode_rows turns the result into per-ego lists of dicts.
+        ValueError: what the three methods raise, a `static` without obstacles, an argument that is none of None / True / dict."""
+        eng = self.loop.eng
+        B, dev = eng.B, eng.device
+
+        def kwargs(name, arg):
+            if arg is None or arg is True:
+                return {}
+            if not isinstance(arg, dict):
+                raise ValueError(f"{name} must be None, True or a dict of keyword arguments, got {arg!r}")
+            return dict(arg)
+
+        kw_c, kw_s, kw_r = kwargs("conflicts", conflicts), kwargs("static", static), kwargs("reasons", reasons)
+        if static is not None and "obstacles" not in kw_s:
+            raise ValueError("static needs its obstacles: static=dict(obstacles=...)")
+        n = self._n()
+        c = self._conflicts_device(n=n, **kw_c) if conflicts is not None else None
+        s = self._static_device(n=n, **kw_s) if static is not None else None
+        r = self._reasons_device(n=n, **kw_r) if reasons is not None else None
+        # the table's size, exactly: every ego's running episode and one more per end flag
+        ends = int(((self.flags[:n] & (history.GOAL | history.AGE)) != 0).sum().item()) if n else 0
+        cap = B + ends
+        ep_off = torch.empty(B + 1, dtype=torch.int64, device=dev)
+        ep_i = torch.empty(max(cap, 1), len(history.EP_INT), dtype=torch.int32, device=dev)
+        ep_d = torch.empty(max(cap, 1), len(history.EP_DOUBLE), dtype=torch.float64, device=dev)
+        group = lambda d, keys: [_ptr(d[k]) if d is not None else None for k in keys]
+        _cabi.check(eng.lib.jsim_loop_summarise_episodes(
+            eng._ctx, B, n, _ptr(self.rec), _ptr(self.flags), _ptr(self.x0_first), _ptr(self.loop.x0_spawn),
+            *group(c, ("clear", "who", "hit_tick", "hit_frame", "hit_xy")), *group(s, ("clear", "who", "hit", "off_tick")),
+            *group(r, ("val", "trig")), cap, _ptr(ep_off), _ptr(ep_i), _ptr(ep_d), eng._stream()),
+            eng._ctx, "jsim_loop_summarise_episodes")
+        off, I, D = ep_off.cpu().numpy(), ep_i[:cap].cpu().numpy(), ep_d[:cap].cpu().numpy()
+        if int(off[B]) != cap:
+            raise RuntimeError(f"the episode table has {int(off[B])} rows, {cap} were counted")
+        out = {"ep_off": off, "dt": float(eng.dt)}
+        out.update({k: np.ascontiguousarray(I[:, j]) for j, k in enumerate(history.EP_INT)})
+        out.update({k: np.ascontiguousarray(D[:, j]) for j, k in enumerate(history.EP_DOUBLE)})
+        out["duration"] = out["n"] * float(eng.dt)
+        meta = lambda d, keys: None if d is None else {k: d[k] for k in keys}
+        out["conflicts"] = meta(c, ("frame_window", "veh_range", "mate_range", "ego_shape"))
+        out["static"] = meta(s, ("margin", "include_hidden", "ego_shape", "set_of"))
+        out["reasons"] = None if r is None else {"par": np.array(r["par"]), "threshold": np.array(r["threshold"]),
+                                                 "veh_of": np.array(r["veh_of"], dtype=np.int32)}
+        return out
 
 
 def _register_recorder(engine: BatchedMPC, rec: Optional[Recorder]):

@@ -2428,6 +2428,45 @@ extern "C" int jsim_loop_eval_static(jsim_ctx *ctx, int32_t B, int32_t n_ticks, 
     return 0;
 }
 
+#include "episodes.inc"
+
+// One row per recorded episode: DEVICE pointers throughout -- the recorder's buffers, the per-tick outputs of
+// the three calls above (each group NULL or whole) and the table; three launches on `stream` (count, scan, summary).
+extern "C" int jsim_loop_summarise_episodes(jsim_ctx *ctx, int32_t B, int32_t n_ticks, const double *rec, const int32_t *flags,
+                                            const double *x_first, const double *x_spawn, const double *veh_clear, const int32_t *veh_who,
+                                            const int32_t *veh_hit_tick, const int32_t *veh_hit_frame, const double *veh_hit_xy,
+                                            const double *st_clear, const int32_t *st_who, const int32_t *st_hit,
+                                            const int32_t *st_off_tick, const double *rs_val, const int32_t *rs_trig, int32_t ep_cap,
+                                            int64_t *ep_off, int32_t *ep_i, double *ep_d, void *stream)
+{
+    const char *const F = "jsim_loop_summarise_episodes";
+    // (the argument checks come first: they need no context and no device)
+    if (B < 0 || n_ticks < 0 || ep_cap < 0) return fail(ctx, -22, "%s: B=%d n_ticks=%d ep_cap=%d", F, B, n_ticks, ep_cap);
+    const int n_veh = !!veh_clear + !!veh_who + !!veh_hit_tick + !!veh_hit_frame + !!veh_hit_xy;
+    if (n_veh != 0 && n_veh != 5)
+        return fail(ctx, -22, "%s: the veh_ group (veh_clear, veh_who, veh_hit_tick, veh_hit_frame, veh_hit_xy) is given in part", F);
+    const int n_st = !!st_clear + !!st_who + !!st_hit + !!st_off_tick;
+    if (n_st != 0 && n_st != 4) return fail(ctx, -22, "%s: the st_ group (st_clear, st_who, st_hit, st_off_tick) is given in part", F);
+    if (!rs_val != !rs_trig) return fail(ctx, -22, "%s: the rs_ group (rs_val, rs_trig) is given in part", F);
+    if (!rec || !flags || !x_first || !x_spawn || !ep_off || !ep_i || !ep_d) return fail(ctx, -22, "%s: null device pointer", F);
+    if (!ctx) return fail(nullptr, -22, "%s: null ctx", F);
+    DeviceGuard dev_guard(ctx->device);
+    JSIM_GUARD_OK(ctx);
+    const EpisodeP P = {B, n_ticks, ep_cap, rec, flags, x_first, x_spawn, veh_clear, veh_who, veh_hit_tick, veh_hit_frame, veh_hit_xy,
+                        st_clear, st_who, st_hit, st_off_tick, rs_val, rs_trig, (long long *)ep_off, ep_i, ep_d};
+    if (B > 0) {
+        hipLaunchKernelGGL(episode_count_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, P);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    hipLaunchKernelGGL(episode_scan_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, P);
+    HIP_TRY(ctx, hipGetLastError());
+    if (B > 0) {
+        hipLaunchKernelGGL(episode_summary_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, P);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    return 0;
+}
+
 // the shape table's (thr, thr_sq) rows: check_collision_moving_bicycle's min_distance = the egos' radius + the vehicle's own
 static int upload_shape_thresholds(jsim_ctx *ctx)
 {

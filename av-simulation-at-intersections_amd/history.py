@@ -4,7 +4,7 @@ the device recorder wrote (jsim_loop_set_recorder): rec [n][B][7] = x, y, yaw, v
 [n][B] (FAILED / GOAL / AGE bits), obs [n][n_obs][6] = the scripted vehicles' get() tuples.  Pure numpy: the host-side half of
 the recorder, testable without a device.  reason_series does the same for the per-tick stakeholder reasons,
 conflict_episodes for the clearance and first contact of every episode (section 17), static_episodes for the static obstacles
-(section 18)."""
+(section 18), episode_rows for the per-episode table that is reduced on the device (section 19)."""
 from __future__ import annotations
 
 from typing import List, Optional
@@ -14,6 +14,11 @@ import numpy as np
 FIELDS = ("x", "y", "yaw", "v", "delta", "a", "xref_deviation")
 FAILED, GOAL, AGE = 1, 2, 4              # JSIM_REC_* of include/jsim_mpc.h
 END_RUNNING, END_GOAL, END_AGE = 0, 1, 2  # how an episode ended (episodes())
+# the columns of the episode table (Recorder.summary), in the order of JSIM_EP_* of include/jsim_mpc.h
+EP_INT = ("ego", "k0", "n", "end", "failed", "dev_tick", "veh_tick", "veh_who", "veh_hit_tick", "veh_hit_frame", "st_tick", "st_who",
+          "st_off_tick", "st_obstacle", "st_ticks_off", "replan_tick")
+EP_DOUBLE = ("length", "v_mean", "v_max", "a_min", "a_max", "delta_absmax", "dev_max", "dev_mean", "veh_clear", "veh_hit_x",
+             "veh_hit_y", "st_clear", "pm_min", "driver_min", "cyclist_min", "dist_min")
 
 
 class History:
@@ -173,6 +178,35 @@ def static_episodes(result: dict, flags: np.ndarray):
                 if not np.isnan(c).all():
                     k = int(np.nanargmin(c))
                     ep.update(min_clear=float(c[k]), min_clear_tick=k0 + k, closest_obstacle=int(who[k0 + k, b]))
+            eps.append(ep)
+        out.append(eps)
+    return out
+
+
+def episode_rows(summary: dict):
+    """The episode table of a recorder (Recorder.summary) as a list over egos of lists over episodes (in order of time) of dicts:
+    every column of EP_INT and EP_DOUBLE under its name as a Python int / float, `duration` (n * dt) where the summary has it, and,
+    where the summary evaluated that group, under `conflicts` the dict conflict_episodes gives for the episode and under `static`
+    the one static_episodes gives (the two share key names, so each is a dict of its own)."""
+    off = np.asarray(summary["ep_off"]).reshape(-1)
+    cols = [(k, np.asarray(summary[k])) for k in EP_INT + EP_DOUBLE + (("duration",) if "duration" in summary else ())]
+    out = []
+    for b in range(off.size - 1):
+        eps = []
+        for e in range(int(off[b]), int(off[b + 1])):
+            ep = {k: (int(a[e]) if a.dtype.kind in "iu" else float(a[e])) for k, a in cols}
+            if summary.get("conflicts") is not None:
+                hit = ep["veh_hit_tick"] >= 0
+                xy = (ep["veh_hit_x"], ep["veh_hit_y"]) if hit else None
+                ep["conflicts"] = {"contact": hit, "tick": ep["veh_hit_tick"] if hit else -1, "frame": ep["veh_hit_frame"] if hit else -1,
+                                   "xy": xy, "collision_xy": (*xy, ep["veh_hit_frame"]) if hit else None, "min_clear": ep["veh_clear"],
+                                   "min_clear_tick": ep["veh_tick"], "closest_vehicle": ep["veh_who"] if ep["veh_tick"] >= 0 else -1}
+            if summary.get("static") is not None:
+                hit = ep["st_off_tick"] >= 0
+                ep["static"] = {"contact": hit, "tick": ep["st_off_tick"] if hit else -1, "obstacle": ep["st_obstacle"] if hit else -1,
+                                "min_clear": ep["st_clear"], "min_clear_tick": ep["st_tick"],
+                                "closest_obstacle": ep["st_who"] if ep["st_tick"] >= 0 else -1,
+                                "ticks_off": ep["st_ticks_off"] if hit else 0}
             eps.append(ep)
         out.append(eps)
     return out

@@ -484,6 +484,52 @@ int jsim_loop_eval_static(jsim_ctx *ctx, int32_t B, int32_t n_ticks, const doubl
                           const double *rows, const double *ego_shape, int32_t include_hidden, double *clear, int32_t *who, int32_t *hit,
                           int32_t *off_tick, void *stream);
 
+/* ---- one row per recorded episode ----
+ * What a sweep asks of every episode -- did the ego arrive, how long did it take, how far did it drive and deviate, how close did
+ * it come, did it touch, did it leave the road, did the replan trigger fire -- as a segmented reduction over the recorder's
+ * buffers (jsim_loop_set_recorder) and over the per-tick outputs of the three jsim_loop_eval_* calls, all of which stay on the
+ * device: three launches on `stream` (count, scan, summary), one wavefront per ego, 64 ticks at a time.  DESIGN.md section 19 is
+ * the contract.
+ *   DEVICE pointers, all of them.  rec [n_ticks][B][7], flags [n_ticks][B], x_first [B][4], x_spawn [B][4] exactly as the
+ *   jsim_loop_eval_* calls take them.  Three optional groups, each NULL as a whole or given as a whole: veh_clear, veh_who,
+ *   veh_hit_tick, veh_hit_frame [n_ticks][B] and veh_hit_xy [n_ticks][B][2] (jsim_loop_eval_conflicts' clear, who, hit_tick,
+ *   hit_frame, hit_xy); st_clear, st_who, st_hit, st_off_tick [n_ticks][B] (jsim_loop_eval_static's clear, who, hit, off_tick);
+ *   rs_val [n_ticks][B][4] and rs_trig [n_ticks][B] (jsim_loop_eval_reasons' val and trig).
+ *   Episodes, per ego: a record whose flag has JSIM_REC_GOAL or JSIM_REC_AGE ends one (both bits: GOAL), the next tick starts one;
+ *   the last episode is the running one and is always there, with no tick when the last record ended the one before: an ego has
+ *   (its end flags) + 1 episodes.
+ *   Out: ep_off [B + 1] (int64): the row of ego b's first episode, ep_off[B] the number of rows; rows ego-major, an ego's in
+ *   order of time; ep_i [ep_cap][JSIM_EP_NI] and ep_d [ep_cap][JSIM_EP_ND], columns by the enumerators below.  Rows at or beyond
+ *   ep_cap are not written; ep_off is complete in any case (ep_off[B] > ep_cap: the cap was too small).
+ *   Integer columns: EGO; K0, N (first tick, ticks); END (0 running, 1 goal, 2 age); FAILED (ticks with JSIM_REC_FAILED); DEV_TICK
+ *   (first tick of the largest xref_deviation); VEH_TICK (first tick of the smallest veh_clear), VEH_WHO (veh_who there),
+ *   VEH_HIT_TICK, VEH_HIT_FRAME (copied from slot K0); ST_TICK, ST_WHO (likewise for st_clear), ST_OFF_TICK (copied from slot K0),
+ *   ST_OBSTACLE (st_hit at ST_OFF_TICK; -1 when that is outside [0, n_ticks)), ST_TICKS_OFF (ticks with st_hit >= 0); REPLAN_TICK
+ *   (first tick with rs_trig & 1).
+ *   Double columns: LENGTH (the sum over the ticks of sqrt(dx * dx + dy * dy), unfused, from the start-of-tick pose -- x_first for
+ *   tick 0, x_spawn behind an end flag, else rec[k - 1] -- to rec[k]); V_MEAN, V_MAX; A_MIN, A_MAX; DELTA_ABSMAX; DEV_MAX and
+ *   DEV_MEAN (xref_deviation; the mean over the ticks whose deviation is not NaN); VEH_CLEAR (smallest), VEH_HIT_X, VEH_HIT_Y
+ *   (copied from slot K0); ST_CLEAR (smallest); PM_MIN, DRIVER_MIN, CYCLIST_MIN, DIST_MIN (minima of rs_val's entries).
+ *   Minima and maxima pass over NaN and compare numerically, their tick is the first that holds the value; nothing but NaN gives
+ *   NaN / -1; a NULL group gives NaN / -1 / 0 in its columns; an episode without a tick gives NaN / -1 / 0 in every column but
+ *   EGO, K0, N, END.  Integer columns, minima, maxima and copies are exact; the three sums are added in a fixed order that depends
+ *   on the ticks' places in their 64-tick chunks alone, so a finished episode's row does not depend on how many ticks follow it.
+ *   Refused (-22) before any device call, jsim_last_error naming the argument: B, n_ticks or ep_cap < 0; a group given in part; a
+ *   null rec, flags, x_first, x_spawn, ep_off, ep_i or ep_d; a null ctx.  n_ticks = 0 writes one running episode without a tick
+ *   per ego; B = 0 writes ep_off[0] = 0. */
+enum { JSIM_EP_EGO = 0, JSIM_EP_K0, JSIM_EP_N, JSIM_EP_END, JSIM_EP_FAILED, JSIM_EP_DEV_TICK, JSIM_EP_VEH_TICK, JSIM_EP_VEH_WHO,
+       JSIM_EP_VEH_HIT_TICK, JSIM_EP_VEH_HIT_FRAME, JSIM_EP_ST_TICK, JSIM_EP_ST_WHO, JSIM_EP_ST_OFF_TICK, JSIM_EP_ST_OBSTACLE,
+       JSIM_EP_ST_TICKS_OFF, JSIM_EP_REPLAN_TICK, JSIM_EP_NI };
+enum { JSIM_EP_LENGTH = 0, JSIM_EP_V_MEAN, JSIM_EP_V_MAX, JSIM_EP_A_MIN, JSIM_EP_A_MAX, JSIM_EP_DELTA_ABSMAX, JSIM_EP_DEV_MAX,
+       JSIM_EP_DEV_MEAN, JSIM_EP_VEH_CLEAR, JSIM_EP_VEH_HIT_X, JSIM_EP_VEH_HIT_Y, JSIM_EP_ST_CLEAR, JSIM_EP_PM_MIN,
+       JSIM_EP_DRIVER_MIN, JSIM_EP_CYCLIST_MIN, JSIM_EP_DIST_MIN, JSIM_EP_ND };
+int jsim_loop_summarise_episodes(jsim_ctx *ctx, int32_t B, int32_t n_ticks, const double *rec, const int32_t *flags,
+                                 const double *x_first, const double *x_spawn, const double *veh_clear, const int32_t *veh_who,
+                                 const int32_t *veh_hit_tick, const int32_t *veh_hit_frame, const double *veh_hit_xy,
+                                 const double *st_clear, const int32_t *st_who, const int32_t *st_hit, const int32_t *st_off_tick,
+                                 const double *rs_val, const int32_t *rs_trig, int32_t ep_cap, int64_t *ep_off, int32_t *ep_i,
+                                 double *ep_d, void *stream);
+
 /* ---- the job's one exchange: the final trajectory gather over RCCL / xGMI ----
  * The reference has no multi-process code at all (its only multi-ego code is the serial Python loop of
  * main/scenarios/interactive_mpc.py:119-172); egos are independent (main/lib/mpc.py:141-211), so ranks own contiguous shards
