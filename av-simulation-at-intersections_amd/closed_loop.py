@@ -65,6 +65,26 @@ class Recorder:
                           "recorded", RuntimeWarning, stacklevel=stacklevel)
         return n
 
+    def _buffers(self):
+        """rec, flags, x_first, x_spawn as the entry points that read the recorder take them."""
+        return _ptr(self.rec), _ptr(self.flags), _ptr(self.x0_first), _ptr(self.loop.x0_spawn)
+
+    def _new(self, n: int, *shape, dtype=torch.float64, count: Optional[int] = None):
+        """An output [n][B]...: `count` of them as a tuple, or one.  (No ticks yet: still valid pointers.)"""
+        eng = self.loop.eng
+        out = tuple(torch.empty(max(n, 1), eng.B, *shape, dtype=dtype, device=eng.device)[:n] for _ in range(count or 1))
+        return out if count else out[0]
+
+    def _ego_shape(self):
+        """(cc_front, cc_rear, radius) of the egos: the engine's registered shape, else the reference car's at its wheelbase."""
+        eng = self.loop.eng
+        return eng.ego_shape if eng.ego_shape is not None else vehicle_shape(L=eng.L)[:3]
+
+    def _call(self, name: str, *args):
+        """Entry point `name` on the engine's context and stream; a refusal raises with the library's message."""
+        eng = self.loop.eng
+        _cabi.check(getattr(eng.lib, name)(eng._ctx, *args, eng._stream()), eng._ctx, name)
+
     def histories(self, b: int):
         n = self._n()
         eng = self.loop.eng
@@ -120,14 +140,11 @@ class Recorder:
         dev = eng.device
         up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(dev)
         d_par, d_thr, d_veh, d_car = up(par, np.float64), up(thr, np.float64), up(veh, np.int32), up(car, np.float64)
-        val = torch.empty(max(n, 1), B, 4, dtype=torch.float64, device=dev)[:n]   # (no ticks yet: still valid pointers)
-        tim = torch.empty(max(n, 1), B, 2, dtype=torch.float64, device=dev)[:n]
-        trig = torch.empty(max(n, 1), B, dtype=torch.int32, device=dev)[:n]
+        val, tim, trig = self._new(n, 4), self._new(n, 2), self._new(n, dtype=torch.int32)
         first = torch.full((B,), -1, dtype=torch.int32, device=dev)
-        _cabi.check(eng.lib.jsim_loop_eval_reasons(eng._ctx, B, n, _ptr(self.rec), _ptr(self.flags), self.n_obs, _ptr(self.obs),
-                                                   _ptr(self.x0_first), _ptr(self.loop.x0_spawn), _ptr(d_veh), _ptr(d_par), _ptr(d_thr),
-                                                   _ptr(d_car), _ptr(val), _ptr(tim), _ptr(trig), _ptr(first), eng._stream()),
-                    eng._ctx, "jsim_loop_eval_reasons")
+        rec, flags, x_first, x_spawn = self._buffers()
+        self._call("jsim_loop_eval_reasons", B, n, rec, flags, self.n_obs, _ptr(self.obs), x_first, x_spawn, _ptr(d_veh), _ptr(d_par),
+                   _ptr(d_thr), _ptr(d_car), _ptr(val), _ptr(tim), _ptr(trig), _ptr(first))
         return {"val": val, "timers": tim, "trig": trig, "first": first, "carry": d_car, "par": par, "threshold": thr, "veh_of": veh}
 
     def vehicle_ranges(self) -> np.ndarray:
@@ -176,7 +193,7 @@ class Recorder:
         w = int(frame_window)
         if w != frame_window or not 0 <= w <= 20:
             raise ValueError(f"frame_window must be an integer in 0..20, got {frame_window!r}")
-        ego = eng.ego_shape if eng.ego_shape is not None else vehicle_shape(L=eng.L)[:3]
+        ego = self._ego_shape()
         if shapes is None:
             shapes = eng.vehicle_shapes
         if shapes is not None:
@@ -198,16 +215,14 @@ class Recorder:
         dev = eng.device
         up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(dev)
         d_veh, d_mate = up(veh), up(mate)
-        new = lambda *shape, dt: torch.empty(max(n, 1), *shape, dtype=dt, device=dev)[:n]   # (no ticks yet: still valid pointers)
-        clear, hit_xy = new(B, dt=torch.float64), new(B, 2, dt=torch.float64)
-        who, row, hit_tick, hit_frame = (new(B, dt=torch.int32) for _ in range(4))
+        clear, hit_xy = self._new(n), self._new(n, 2)
+        who, row, hit_tick, hit_frame = self._new(n, dtype=torch.int32, count=4)
         ego_c = (C.c_double * 3)(*ego)
-        _cabi.check(eng.lib.jsim_loop_eval_conflicts(
-            eng._ctx, B, n, _ptr(self.rec), _ptr(self.flags), n_obs, _ptr(self.obs) if self.obs is not None else None,
-            _ptr(self.x0_first), _ptr(self.loop.x0_spawn), _ptr(d_veh), _ptr(d_mate),
-            shapes.ctypes.data_as(C.c_void_p) if shapes is not None and n_obs else None, C.cast(ego_c, C.c_void_p), w,
-            _ptr(clear), _ptr(who), _ptr(row), _ptr(hit_tick), _ptr(hit_frame), _ptr(hit_xy), eng._stream()),
-            eng._ctx, "jsim_loop_eval_conflicts")
+        rec, flags, x_first, x_spawn = self._buffers()
+        self._call("jsim_loop_eval_conflicts", B, n, rec, flags, n_obs, _ptr(self.obs) if self.obs is not None else None,
+                   x_first, x_spawn, _ptr(d_veh), _ptr(d_mate),
+                   shapes.ctypes.data_as(C.c_void_p) if shapes is not None and n_obs else None, C.cast(ego_c, C.c_void_p), w,
+                   _ptr(clear), _ptr(who), _ptr(row), _ptr(hit_tick), _ptr(hit_frame), _ptr(hit_xy))
         return {"clear": clear, "who": who, "row": row, "hit_tick": hit_tick, "hit_frame": hit_frame, "hit_xy": hit_xy,
                 "frame_window": w, "veh_range": veh, "mate_range": mate, "ego_shape": tuple(float(v) for v in ego)}
 
@@ -238,7 +253,7 @@ class Recorder:
         from . import planner
         eng = self.loop.eng
         B = eng.B
-        ego = eng.ego_shape if eng.ego_shape is not None else vehicle_shape(L=eng.L)[:3]
+        ego = self._ego_shape()
         margin = float(ego[2] if margin is None else margin)
         obstacles = list(obstacles)
         is_one = lambda o: (isinstance(o, (tuple, list)) and len(o) > 0 and isinstance(o[0], str)) or hasattr(o, "to_convex")
@@ -256,17 +271,13 @@ class Recorder:
         if ((sof < 0) | (sof >= len(sets))).any():
             raise ValueError(f"set_of outside [0, {len(sets)})")
         n = self._n(4) if n is None else n
-        dev = eng.device
-        d_set = torch.from_numpy(sof).to(dev)
-        new = lambda dt: torch.empty(max(n, 1), B, dtype=dt, device=dev)[:n]   # (no ticks yet: still valid pointers)
-        clear = new(torch.float64)
-        who, hit, off_tick = (new(torch.int32) for _ in range(3))
+        d_set = torch.from_numpy(sof).to(eng.device)
+        clear = self._new(n)
+        who, hit, off_tick = self._new(n, dtype=torch.int32, count=3)
         ego_c = (C.c_double * 3)(*ego)
-        _cabi.check(eng.lib.jsim_loop_eval_static(
-            eng._ctx, B, n, _ptr(self.rec), _ptr(self.flags), _ptr(self.x0_first), _ptr(self.loop.x0_spawn), _ptr(d_set),
-            len(sets), set_off.ctypes.data_as(C.c_void_p), n_rows, rows.ctypes.data_as(C.c_void_p), C.cast(ego_c, C.c_void_p),
-            int(bool(include_hidden)), _ptr(clear), _ptr(who), _ptr(hit), _ptr(off_tick), eng._stream()),
-            eng._ctx, "jsim_loop_eval_static")
+        self._call("jsim_loop_eval_static", B, n, *self._buffers(), _ptr(d_set), len(sets), set_off.ctypes.data_as(C.c_void_p), n_rows,
+                   rows.ctypes.data_as(C.c_void_p), C.cast(ego_c, C.c_void_p), int(bool(include_hidden)),
+                   _ptr(clear), _ptr(who), _ptr(hit), _ptr(off_tick))
         return {"clear": clear, "who": who, "hit": hit, "off_tick": off_tick, "margin": margin, "include_hidden": bool(include_hidden),
                 "ego_shape": tuple(float(v) for v in ego), "set_of": sof}
 
@@ -308,11 +319,9 @@ class Recorder:
         ep_i = torch.empty(max(cap, 1), len(history.EP_INT), dtype=torch.int32, device=dev)
         ep_d = torch.empty(max(cap, 1), len(history.EP_DOUBLE), dtype=torch.float64, device=dev)
         group = lambda d, keys: [_ptr(d[k]) if d is not None else None for k in keys]
-        _cabi.check(eng.lib.jsim_loop_summarise_episodes(
-            eng._ctx, B, n, _ptr(self.rec), _ptr(self.flags), _ptr(self.x0_first), _ptr(self.loop.x0_spawn),
-            *group(c, ("clear", "who", "hit_tick", "hit_frame", "hit_xy")), *group(s, ("clear", "who", "hit", "off_tick")),
-            *group(r, ("val", "trig")), cap, _ptr(ep_off), _ptr(ep_i), _ptr(ep_d), eng._stream()),
-            eng._ctx, "jsim_loop_summarise_episodes")
+        self._call("jsim_loop_summarise_episodes", B, n, *self._buffers(),
+                   *group(c, ("clear", "who", "hit_tick", "hit_frame", "hit_xy")), *group(s, ("clear", "who", "hit", "off_tick")),
+                   *group(r, ("val", "trig")), cap, _ptr(ep_off), _ptr(ep_i), _ptr(ep_d))
         off, I, D = ep_off.cpu().numpy(), ep_i[:cap].cpu().numpy(), ep_d[:cap].cpu().numpy()
         if int(off[B]) != cap:
             raise RuntimeError(f"the episode table has {int(off[B])} rows, {cap} were counted")

@@ -1,8 +1,8 @@
 // Clearance and first contact per recorded tick (DESIGN.md section 17): what check_collision_moving_cars and
 // check_collision_moving_bicycle of main/lib/collision_avoidance.py (:85-166) answer when they are handed an episode's realised
 // poses (main/planner/moving_obstacle_avoidance.py:44-76) -- the ego's History against the vehicles' recorded get() tuples and its
-// group mates' Histories -- as one pass over the History recorder's buffers (jsim_loop_set_recorder): one wavefront per ego, ticks
-// 64 at a time, lane t owns tick k0c + t (reason_ticks_kernel's mapping).
+// group mates' Histories -- as one pass over the History recorder's buffers (jsim_loop_set_recorder), walked as recorder_walk.inc
+// says: one wavefront per ego, ticks 64 at a time, lane t owns tick k0c + t.
 //
 // Lane-parallel: the poses, the circle centres, the reference's pair table of the tick's frame (every row of it), `clear`, `who`
 // and `row`.  Per episode, in two forward sweeps of the same wavefront: sweep 1 notes at the slot of the episode's first tick the
@@ -11,12 +11,9 @@
 // the earliest at which its rear circle, touches it -- the reference's `np.argmax(mask) % len` over front ++ rear.
 
 struct ConflictP {
-    int B, n_ticks, n_obs, w;
-    const double *rec;        // [n][B][JSIM_REC_FIELDS]
-    const int *flags;         // [n][B]
+    RecorderBuf R;
+    int n_obs, w;
     const double *obs_rec;    // [n][n_obs][6] or NULL (n_obs = 0)
-    const double *x_first;    // [B][4] x, y, v, yaw at the start of tick 0
-    const double *x_spawn;    // [B][4] the respawn state
     const int *veh_range;     // [B][2] the ego's vehicles [lo, hi) among the n_obs recorded ones
     const int *mate_range;    // [B][2] the batch range [mlo, mhi) of its group mates (itself skipped)
     const double4 *shapes;    // [n_obs] (cc_front, cc_rear, thr, thr_sq) or NULL: every vehicle has the ego's shape
@@ -27,30 +24,6 @@ struct ConflictP {
     int *hit_tick, *hit_frame; // [n][B], at an episode's first slot
     double *hit_xy;           // [n][B][2]
 };
-
-#define JCF_END (JSIM_REC_GOAL | JSIM_REC_AGE)
-
-// An ego's pose at the start of tick k: x_first, x_spawn behind a record that ended an episode, or the record before
-// (PT: ConflictP, or StaticP of static_conflicts.inc -- the recorder's buffers under the same names)
-template <class PT> __device__ __forceinline__ void jcf_ego_pose(const PT &P, int e, int k, double &x, double &y, double &yaw)
-{
-    if (k == 0) {
-        const double *p = P.x_first + 4 * (size_t)e;
-        x = p[0]; y = p[1]; yaw = p[3];
-    } else if ((P.flags[(size_t)(k - 1) * P.B + e] & JCF_END) != 0) {
-        const double *p = P.x_spawn + 4 * (size_t)e;
-        x = p[0]; y = p[1]; yaw = p[3];
-    } else {
-        const double *p = P.rec + JSIM_REC_FIELDS * ((size_t)(k - 1) * P.B + e);
-        x = p[0]; y = p[1]; yaw = p[2];
-    }
-}
-
-// The ticks of a chunk that end an episode: the record's flag, or the last record
-template <class PT> __device__ __forceinline__ unsigned long long jcf_ends(const PT &P, int b, int k)
-{
-    return __ballot(k < P.n_ticks && (k == P.n_ticks - 1 || (P.flags[(size_t)k * P.B + b] & JCF_END) != 0));
-}
 
 // The ego's vehicle list: ns scripted vehicles from lo on, then nm mates from mlo on with the ego itself skipped; clamped to the
 // tables and to JSIM_MAX_OBS in total (the Python surface refuses what is clamped here)
@@ -63,10 +36,10 @@ __device__ __forceinline__ ConflictList jcf_list(const ConflictP &P, int b)
     L.lo = lo; L.ns = hi > lo ? hi - lo : 0;
     if (L.ns > JSIM_MAX_OBS) L.ns = JSIM_MAX_OBS;
     int mlo = P.mate_range[2 * b], mhi = P.mate_range[2 * b + 1];
-    mlo = mlo < 0 ? 0 : mlo; mhi = mhi > P.B ? P.B : mhi;
+    mlo = mlo < 0 ? 0 : mlo; mhi = mhi > P.R.B ? P.R.B : mhi;
     L.mlo = mlo;
-    L.skip = (b >= mlo && b < mhi) ? b : P.B;      // the batch index the enumeration steps over
-    L.nm = mhi > mlo ? mhi - mlo - (L.skip < P.B ? 1 : 0) : 0;
+    L.skip = (b >= mlo && b < mhi) ? b : P.R.B;      // the batch index the enumeration steps over
+    L.nm = mhi > mlo ? mhi - mlo - (L.skip < P.R.B ? 1 : 0) : 0;
     if (L.ns + L.nm > JSIM_MAX_OBS) L.nm = JSIM_MAX_OBS - L.ns;
     return L;
 }
@@ -84,28 +57,30 @@ __device__ __forceinline__ void jcf_vehicle_pose(const ConflictP &P, const Confl
     } else {
         int m = L.mlo + (i - L.ns);
         if (m >= L.skip) ++m;
-        jcf_ego_pose(P, m, k, x, y, yaw);
+        jrw_pose(P.R, m, k, x, y, yaw);
     }
 }
 
 __global__ __launch_bounds__(64) void conflict_ticks_kernel(const ConflictP P)
 {
-    const int lane = threadIdx.x, b = blockIdx.x, B = P.B, n = P.n_ticks, w = P.w, nw = 2 * P.w + 1;
+    const RecorderBuf &R = P.R;
+    const int lane = threadIdx.x, b = blockIdx.x, B = R.B, n = R.n_ticks, w = P.w, nw = 2 * P.w + 1;
     const ConflictList L = jcf_list(P, b);
     const int n_veh = L.ns + L.nm;
     const unsigned long long upto = ~0ull >> (63 - lane), from = ~0ull << lane;   // bits 0 .. lane, bits lane .. 63
 
     // ---- sweep 1: the frame of every tick; per episode the first touching frame's tick, vehicle and vehicle circle ----
-    unsigned long long e_prev = 0ull, e_cur = jcf_ends(P, b, lane);
+    RecChunk C = {};
+    unsigned long long e_next = jrw_end_mask(R, lane, jrw_flag(R, b, lane), true);
     int ep_k0 = 0, ep_tick = -1, ep_i = -1;
     double ep_px = NAN, ep_py = NAN;
     for (int k0c = 0; k0c < n; k0c += 64) {
         const int k = k0c + lane;
         const bool valid = k < n;
-        const int cnt = (n - k0c) < 64 ? (n - k0c) : 64;
-        const unsigned long long e_next = jcf_ends(P, b, k + 64);
-        // a tick starts an episode when the record before it ended one, and tick 0 does
-        const unsigned long long s_cur = (e_cur << 1) | (k0c == 0 ? 1ull : (e_prev >> 63));
+        // the next chunk's ends ahead of the body: the frame offsets reach into it
+        jrw_enter(C, R, k0c, e_next, true);
+        e_next = jrw_end_mask(R, k + 64, jrw_flag(R, b, k + 64), true);
+        const unsigned long long e_prev = C.e_prev, e_cur = C.e_cur, s_cur = C.s_cur;
         const unsigned long long s_prev = k0c == 0 ? 0ull : ((e_prev << 1) | 1ull);   // (bit 0: at or before the chunk's first tick)
         // the episode's own first and last tick where an offset can reach them: within the neighbouring chunks, else a bound that
         // is more than 20 ticks away in any case
@@ -117,7 +92,7 @@ __global__ __launch_bounds__(64) void conflict_ticks_kernel(const ConflictP P)
         int who = -1, crow = 0x7fffffff, row = 0x7fffffff, hi = -1;
         if (valid && n_veh > 0) {
             double ex, ey, eyaw, es, ec;
-            jcf_ego_pose(P, b, k, ex, ey, eyaw);
+            jrw_pose(R, b, k, ex, ey, eyaw);
             sincos(eyaw, &es, &ec);
             const double ecx[2] = {ex + ec * P.cc_f, ex + ec * P.cc_r}, ecy[2] = {ey + es * P.cc_f, ey + es * P.cc_r};
             for (int i = 0; i < n_veh; ++i) {
@@ -156,47 +131,39 @@ __global__ __launch_bounds__(64) void conflict_ticks_kernel(const ConflictP P)
             }
         }
         // the episodes of this chunk, one after the other (every branch is uniform: the masks are ballots)
-        for (int pos = 0; pos < cnt;) {
-            const unsigned long long rem = e_cur >> pos;
-            const int e = rem ? pos + (int)__builtin_ctzll(rem) : cnt - 1;
-            if ((s_cur >> pos) & 1ull) { ep_k0 = k0c + pos; ep_tick = -1; ep_i = -1; ep_px = NAN; ep_py = NAN; }
-            const unsigned long long h = touch & (~0ull << pos) & (~0ull >> (63 - e));
+        jrw_segments(C, [&](int pos, int e, bool starts, bool ends) {
+            if (starts) { ep_k0 = k0c + pos; ep_tick = -1; ep_i = -1; ep_px = NAN; ep_py = NAN; }
+            const unsigned long long h = touch & jrw_lanes(pos, e);
             if (ep_tick < 0 && h != 0ull) {
                 const int t = (int)__builtin_ctzll(h);
                 ep_tick = k0c + t;
                 ep_i = __shfl(hi, t); ep_px = __shfl(hpx, t); ep_py = __shfl(hpy, t);
             }
-            if (rem != 0ull && lane == 0) {    // the episode ends here: its slot, written once in this sweep
+            if (ends && lane == 0) {           // the episode ends here: its slot, written once in this sweep
                 const size_t q = (size_t)ep_k0 * B + b;
                 P.hit_tick[q] = ep_tick; P.hit_frame[q] = ep_i; P.hit_xy[2 * q] = ep_px; P.hit_xy[2 * q + 1] = ep_py;
             }
-            pos = e + 1;
-        }
-        e_prev = e_cur; e_cur = e_next;
+        });
     }
     if (n_veh == 0) return;        // every episode slot holds -1 / -1 / NaN already
     __threadfence();               // sweep 2 reads, in other lanes, what lane 0 wrote
 
     // ---- sweep 2: per episode with a touching row, the earliest frame at which each ego circle touches that vehicle circle ----
-    e_prev = 0ull; e_cur = jcf_ends(P, b, lane);
     int s_k0 = 0, s_tick = -1, bf = -1, br = -1;
     double s_px = NAN, s_py = NAN, s_thr_sq = 0.0;
     for (int k0c = 0; k0c < n; k0c += 64) {
         const int k = k0c + lane;
         const bool valid = k < n;
-        const int cnt = (n - k0c) < 64 ? (n - k0c) : 64;
-        const unsigned long long s_cur = (e_cur << 1) | (k0c == 0 ? 1ull : (e_prev >> 63));
+        jrw_enter(C, R, k0c, jrw_end_mask(R, k, jrw_flag(R, b, k), true), true);
         double fx = NAN, fy = NAN, rx = NAN, ry = NAN;
         if (valid) {
             double ex, ey, eyaw, es, ec;
-            jcf_ego_pose(P, b, k, ex, ey, eyaw);
+            jrw_pose(R, b, k, ex, ey, eyaw);
             sincos(eyaw, &es, &ec);
             fx = ex + ec * P.cc_f; fy = ey + es * P.cc_f; rx = ex + ec * P.cc_r; ry = ey + es * P.cc_r;
         }
-        for (int pos = 0; pos < cnt;) {
-            const unsigned long long rem = e_cur >> pos;
-            const int e = rem ? pos + (int)__builtin_ctzll(rem) : cnt - 1;
-            if ((s_cur >> pos) & 1ull) {
+        jrw_segments(C, [&](int pos, int e, bool starts, bool ends) {
+            if (starts) {
                 s_k0 = k0c + pos; bf = -1; br = -1;
                 const size_t q = (size_t)s_k0 * B + b;
                 s_tick = P.hit_tick[q];
@@ -214,11 +181,11 @@ __global__ __launch_bounds__(64) void conflict_ticks_kernel(const ConflictP P)
                 const unsigned long long tr = __ballot(in && drx * drx + dry * dry <= s_thr_sq);
                 if (bf < 0 && tf != 0ull) bf = k0c + (int)__builtin_ctzll(tf);
                 if (br < 0 && tr != 0ull) br = k0c + (int)__builtin_ctzll(tr);
-                if (rem != 0ull) {             // the episode ends here: front ++ rear, the first hit's index modulo the length
+                if (ends) {                    // the episode ends here: front ++ rear, the first hit's index modulo the length
                     const int fr = bf >= 0 ? bf : br;
                     if (fr >= 0) {
                         double hx, hy, hyaw;
-                        jcf_ego_pose(P, b, fr, hx, hy, hyaw);
+                        jrw_pose(R, b, fr, hx, hy, hyaw);
                         if (lane == 0) {
                             const size_t q = (size_t)s_k0 * B + b;
                             P.hit_frame[q] = fr - s_k0; P.hit_xy[2 * q] = hx; P.hit_xy[2 * q + 1] = hy;
@@ -226,8 +193,6 @@ __global__ __launch_bounds__(64) void conflict_ticks_kernel(const ConflictP P)
                     }
                 }
             }
-            pos = e + 1;
-        }
-        e_prev = e_cur; e_cur = jcf_ends(P, b, k + 64);
+        });
     }
 }

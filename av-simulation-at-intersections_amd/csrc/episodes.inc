@@ -1,9 +1,9 @@
 // One row per recorded episode (DESIGN.md section 19): the segmented reduction of the History recorder's buffers and of the per-tick
 // series of sections 16-18 over the episodes of history.episode_bounds.  Three launches: episode_count_kernel (an ego's end flags by
 // ballot and popcount), episode_scan_kernel (the exclusive prefix over the B counts, one workgroup tiling B with a carry) and
-// episode_summary_kernel: one wavefront per ego, ticks 64 at a time, lane t owns tick k0c + t (conflict_ticks_kernel's mapping).
+// episode_summary_kernel: one wavefront per ego, ticks 64 at a time, lane t owns tick k0c + t (the walk of recorder_walk.inc).
 //
-// Lane-parallel: the record, the start-of-tick pose (jcf_ego_pose), the step length and the tick's entries of the optional series.
+// Lane-parallel: the record, the start-of-tick pose (jrw_pose), the step length and the tick's entries of the optional series.
 // Per episode segment of a chunk (its lanes [pos, e], from the chunk's end-flag ballot): every sum, minimum and maximum by a
 // butterfly over the 64 lanes with the lanes outside the segment holding the operation's neutral value (0.0 / NaN), the tick of an
 // extreme value from the ballot of the lanes that hold it.  An episode open at the chunk's end is carried as wave-uniform values
@@ -11,11 +11,8 @@
 // a finished episode's row does not depend on how many ticks follow it.  A row is written once, by lane 0, with plain stores.
 
 struct EpisodeP {
-    int B, n_ticks, ep_cap;
-    const double *rec;        // [n][B][JSIM_REC_FIELDS]
-    const int *flags;         // [n][B]
-    const double *x_first;    // [B][4] x, y, v, yaw at the start of tick 0
-    const double *x_spawn;    // [B][4] the respawn state
+    RecorderBuf R;
+    int ep_cap;
     const double *veh_clear;  // [n][B] or NULL with its group (jsim_loop_eval_conflicts' outputs)
     const int *veh_who, *veh_hit_tick, *veh_hit_frame;
     const double *veh_hit_xy; // [n][B][2]
@@ -31,11 +28,11 @@ struct EpisodeP {
 // ---- launch 1: episodes per ego = its end flags + 1 (the running one), left in ep_off[b] ----
 __global__ __launch_bounds__(64) void episode_count_kernel(const EpisodeP P)
 {
-    const int lane = threadIdx.x, b = blockIdx.x, n = P.n_ticks;
+    const int lane = threadIdx.x, b = blockIdx.x, n = P.R.n_ticks;
     int ends = 0;
     for (int k0c = 0; k0c < n; k0c += 64) {
         const int k = k0c + lane;
-        ends += __popcll(__ballot(k < n && (P.flags[(size_t)k * P.B + b] & JCF_END) != 0));
+        ends += __popcll(jrw_end_mask(P.R, k, jrw_flag(P.R, b, k), false));
     }
     if (lane == 0) P.ep_off[b] = (long long)ends + 1;
 }
@@ -46,9 +43,9 @@ __global__ __launch_bounds__(1024) void episode_scan_kernel(const EpisodeP P)
     __shared__ long long wave_sum[16];
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     long long carry = 0;
-    for (int base = 0; base < P.B; base += 1024) {
+    for (int base = 0; base < P.R.B; base += 1024) {
         const int i = base + t;
-        const long long c = i < P.B ? P.ep_off[i] : 0;
+        const long long c = i < P.R.B ? P.ep_off[i] : 0;
         long long incl = c;
         for (int d = 1; d < 64; d <<= 1) {
             const long long up = __shfl_up(incl, d);
@@ -62,11 +59,11 @@ __global__ __launch_bounds__(1024) void episode_scan_kernel(const EpisodeP P)
             if (w < wave) before += s;
             total += s;
         }
-        if (i < P.B) P.ep_off[i] = carry + before + (incl - c);
+        if (i < P.R.B) P.ep_off[i] = carry + before + (incl - c);
         carry += total;
         __syncthreads();       // wave_sum is written again in the next tile
     }
-    if (t == 0) P.ep_off[P.B] = carry;
+    if (t == 0) P.ep_off[P.R.B] = carry;
 }
 
 // ---- launch 3 ----
@@ -122,7 +119,7 @@ __device__ __forceinline__ void jep_write(const EpisodeP &P, const EpisodeAcc &A
     int *I = P.ep_i + (size_t)row * JSIM_EP_NI;
     double *D = P.ep_d + (size_t)row * JSIM_EP_ND;
     const bool any = A.n > 0;
-    const size_t q = (size_t)A.k0 * P.B + b;       // the slot of the episode's first tick (read only with a tick there)
+    const size_t q = (size_t)A.k0 * P.R.B + b;       // the slot of the episode's first tick (read only with a tick there)
     I[JSIM_EP_EGO] = b; I[JSIM_EP_K0] = A.k0; I[JSIM_EP_N] = A.n; I[JSIM_EP_END] = end;
     I[JSIM_EP_FAILED] = A.failed;
     I[JSIM_EP_DEV_TICK] = A.dev.tick;
@@ -133,7 +130,7 @@ __device__ __forceinline__ void jep_write(const EpisodeP &P, const EpisodeAcc &A
     I[JSIM_EP_ST_TICK] = A.st.tick; I[JSIM_EP_ST_WHO] = A.st_who;
     const int off = (any && P.st_clear != nullptr) ? P.st_off_tick[q] : -1;
     I[JSIM_EP_ST_OFF_TICK] = off;
-    I[JSIM_EP_ST_OBSTACLE] = (off >= 0 && off < P.n_ticks) ? P.st_hit[(size_t)off * P.B + b] : -1;
+    I[JSIM_EP_ST_OBSTACLE] = (off >= 0 && off < P.R.n_ticks) ? P.st_hit[(size_t)off * P.R.B + b] : -1;
     I[JSIM_EP_ST_TICKS_OFF] = A.st_ticks_off;
     I[JSIM_EP_REPLAN_TICK] = A.replan_tick;
     D[JSIM_EP_LENGTH] = any ? A.length : NAN;
@@ -152,7 +149,8 @@ __device__ __forceinline__ void jep_write(const EpisodeP &P, const EpisodeAcc &A
 
 __global__ __launch_bounds__(64) void episode_summary_kernel(const EpisodeP P)
 {
-    const int lane = threadIdx.x, b = blockIdx.x, B = P.B, n = P.n_ticks;
+    const RecorderBuf &R = P.R;
+    const int lane = threadIdx.x, b = blockIdx.x, B = R.B, n = R.n_ticks;
     long long row = P.ep_off[b];
     EpisodeAcc A;
     jep_reset(A, 0);
@@ -166,10 +164,10 @@ __global__ __launch_bounds__(64) void episode_summary_kernel(const EpisodeP P)
         double step = 0.0, v = 0.0, a = NAN, delta = NAN, dev = NAN, v_clear = NAN, s_clear = NAN;
         double rs[4] = {NAN, NAN, NAN, NAN};
         if (valid) {
-            flag = P.flags[q];
-            const double *r = P.rec + JSIM_REC_FIELDS * q;
+            flag = R.flags[q];
+            const double *r = R.rec + JSIM_REC_FIELDS * q;
             double sx, sy, syaw;
-            jcf_ego_pose(P, b, k, sx, sy, syaw);
+            jrw_pose(R, b, k, sx, sy, syaw);
             const double dx = r[0] - sx, dy = r[1] - sy;
             step = sqrt(dx * dx + dy * dy);
             v = r[3]; delta = fabs(r[4]); a = r[5]; dev = r[6];
@@ -180,13 +178,14 @@ __global__ __launch_bounds__(64) void episode_summary_kernel(const EpisodeP P)
                 trig = P.rs_trig[q];
             }
         }
-        const unsigned long long e_cur = __ballot(valid && (flag & JCF_END) != 0);
-        // the segments of this chunk, one after the other (every branch is uniform: the masks are ballots)
+        const unsigned long long e_cur = jrw_end_mask(R, k, flag, false);
+        // the segments of this chunk, written out here and not through jrw_segments: DESIGN.md section 20 has the measurement
         for (int pos = 0; pos < cnt;) {
             const unsigned long long rem = e_cur >> pos;
             const int e = rem ? pos + (int)__builtin_ctzll(rem) : cnt - 1;
+            const bool ends = rem != 0ull;
             const bool in = lane >= pos && lane <= e;          // (e < cnt: every lane of the segment holds a tick)
-            const unsigned long long seg = (~0ull << pos) & (~0ull >> (63 - e));
+            const unsigned long long seg = jrw_lanes(pos, e);
             int at = 0;
             A.n += e - pos + 1;
             A.failed += __popcll(__ballot(in && (flag & JSIM_REC_FAILED) != 0));
@@ -212,7 +211,7 @@ __global__ __launch_bounds__(64) void episode_summary_kernel(const EpisodeP P)
                 const unsigned long long need = __ballot((trig & 1) != 0) & seg;
                 if (A.replan_tick < 0 && need != 0ull) A.replan_tick = k0c + (int)__builtin_ctzll(need);
             }
-            if (rem != 0ull) {                                  // the episode ends with lane e's record
+            if (ends) {                                         // the episode ends with lane e's record
                 const int f_end = __shfl(flag, e);
                 if (lane == 0) jep_write(P, A, b, row, (f_end & JSIM_REC_GOAL) ? 1 : 2);
                 ++row;

@@ -2288,7 +2288,40 @@ extern "C" int jsim_score_trajectories(int device_id, int32_t n_sit, const int32
     return D.result(who);
 }
 
+#include "recorder_walk.inc"
 #include "reasons_ticks.inc"
+
+// ---- what the four calls that read the History recorder share around their launches ----
+// The end of such a call's checks (they need no context and no device, so a null ctx is refused last) and the start of its device
+// work: with nothing to do (`nothing_`) it returns, else it runs on the context's device
+#define JSIM_RECORDER_CALL(nothing_)                                                                           \
+    if (!ctx) return fail(nullptr, -22, "%s: null ctx", F);                                                   \
+    if (nothing_) return 0;                                                                                   \
+    DeviceGuard dev_guard(ctx->device);                                                                        \
+    JSIM_GUARD_OK(ctx)
+
+// ego_shape = the egos' (cc_front, cc_rear, radius), a HOST pointer
+static int check_ego_shape(jsim_ctx *ctx, const char *F, const double *s)
+{
+    if (!std::isfinite(s[0]) || !std::isfinite(s[1])) return fail(ctx, -22, "%s: ego_shape: a circle offset that is not finite", F);
+    if (!(s[2] > 0.0) || !std::isfinite(s[2])) return fail(ctx, -22, "%s: ego_shape: radius %g is not positive and finite", F, s[2]);
+    return 0;
+}
+// Replace one of the context's tables with n host entries; sync = false: behind another replacement, with no launch in between
+template <class T> static int replace_table(jsim_ctx *ctx, DevArray<T> &table, const T *host, size_t n, bool sync = true)
+{
+    if (sync) HIP_TRY(ctx, hipDeviceSynchronize()); // an earlier call's launch may still read the table that is replaced
+    HIP_TRY(ctx, table.reserve(n));
+    HIP_TRY(ctx, hipMemcpy(table, host, sizeof(T) * n, hipMemcpyHostToDevice));
+    return 0;
+}
+// One wavefront per ego on `stream`
+template <class PT> static int launch_per_ego(jsim_ctx *ctx, void (*kernel)(const PT), int B, void *stream, const PT &P)
+{
+    hipLaunchKernelGGL(kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, P);
+    HIP_TRY(ctx, hipGetLastError());
+    return 0;
+}
 
 // Stakeholder reasons per recorded tick and the replan trigger: DEVICE pointers, the recorder's buffers as
 // they are; one launch on `stream`, one wavefront per ego.
@@ -2298,20 +2331,14 @@ extern "C" int jsim_loop_eval_reasons(jsim_ctx *ctx, int32_t B, int32_t n_ticks,
                                       int32_t *trig, int32_t *first, void *stream)
 {
     const char *const F = "jsim_loop_eval_reasons";
-    // (the argument checks come first: they need no context and no device)
     if (B < 0 || n_ticks < 0) return fail(ctx, -22, "%s: B=%d n_ticks=%d", F, B, n_ticks);
     if (obs_rec && n_obs < 1) return fail(ctx, -22, "%s: obs_rec given with n_obs=%d", F, n_obs);
     if (!rec || !flags || !x_first || !x_spawn || !veh_of || !par || !threshold || !carry || !val || !timers || !trig || !first)
         return fail(ctx, -22, "%s: null device pointer", F);
-    if (!ctx) return fail(nullptr, -22, "%s: null ctx", F);
-    if (B == 0 || n_ticks == 0) return 0;
-    DeviceGuard dev_guard(ctx->device);
-    JSIM_GUARD_OK(ctx);
-    const ReasonTickP P = {B, n_ticks, obs_rec ? n_obs : 0, rec, flags, obs_rec, x_first, x_spawn, veh_of, par, threshold,
+    JSIM_RECORDER_CALL(B == 0 || n_ticks == 0);
+    const ReasonTickP P = {recorder_buf(B, n_ticks, rec, flags, x_first, x_spawn), obs_rec ? n_obs : 0, obs_rec, veh_of, par, threshold,
                            carry, val, timers, trig, first};
-    hipLaunchKernelGGL(reason_ticks_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, P);
-    HIP_TRY(ctx, hipGetLastError());
-    return 0;
+    return launch_per_ego(ctx, reason_ticks_kernel, B, stream, P);
 }
 
 #include "conflicts.inc"
@@ -2326,26 +2353,21 @@ extern "C" int jsim_loop_eval_conflicts(jsim_ctx *ctx, int32_t B, int32_t n_tick
                                         double *hit_xy, void *stream)
 {
     const char *const F = "jsim_loop_eval_conflicts";
-    // (the argument checks come first: they need no context and no device)
     if (B < 0 || n_ticks < 0 || n_obs < 0) return fail(ctx, -22, "%s: B=%d n_ticks=%d n_obs=%d", F, B, n_ticks, n_obs);
     if (!obs_rec && n_obs > 0) return fail(ctx, -22, "%s: null obs_rec with n_obs=%d", F, n_obs);
     if (frame_window < 0 || frame_window > 20) return fail(ctx, -22, "%s: frame_window=%d outside [0, 20]", F, frame_window);
     if (!ego_shape) return fail(ctx, -22, "%s: null ego_shape", F);
     if (!rec || !flags || !x_first || !x_spawn || !veh_range || !mate_range || !clear || !who || !row || !hit_tick || !hit_frame || !hit_xy)
         return fail(ctx, -22, "%s: null device pointer", F);
+    if (int rc = check_ego_shape(ctx, F, ego_shape)) return rc;
     const double cc_f = ego_shape[0], cc_r = ego_shape[1], r_ego = ego_shape[2];
-    if (!std::isfinite(cc_f) || !std::isfinite(cc_r)) return fail(ctx, -22, "%s: ego_shape: a circle offset that is not finite", F);
-    if (!(r_ego > 0.0) || !std::isfinite(r_ego)) return fail(ctx, -22, "%s: ego_shape: radius %g is not positive and finite", F, r_ego);
     const bool table = shapes && n_obs > 0;
     for (int i = 0; table && i < n_obs; ++i) {
         const double *s = shapes + 4 * (size_t)i;
         if (!std::isfinite(s[0]) || !std::isfinite(s[1]) || !(s[2] > 0.0) || !std::isfinite(s[2]))
             return fail(ctx, -22, "%s: shapes row %d needs finite circle offsets and a positive, finite radius", F, i);
     }
-    if (!ctx) return fail(nullptr, -22, "%s: null ctx", F);
-    if (B == 0 || n_ticks == 0) return 0;
-    DeviceGuard dev_guard(ctx->device);
-    JSIM_GUARD_OK(ctx);
+    JSIM_RECORDER_CALL(B == 0 || n_ticks == 0);
     if (table) {   // min_distance per vehicle: the egos' radius + its own, and the squared form the rows are compared with
         std::vector<double4> rows((size_t)n_obs);
         for (int i = 0; i < n_obs; ++i) {
@@ -2353,17 +2375,13 @@ extern "C" int jsim_loop_eval_conflicts(jsim_ctx *ctx, int32_t B, int32_t n_tick
             const double thr = r_ego + s[2];
             rows[i] = double4{s[0], s[1], thr, jsim_sqrt_threshold(thr)};
         }
-        HIP_TRY(ctx, hipDeviceSynchronize()); // an earlier call's launch may still read the table that is replaced
-        HIP_TRY(ctx, ctx->d_conflict_rows.reserve(n_obs));
-        HIP_TRY(ctx, hipMemcpy(ctx->d_conflict_rows, rows.data(), sizeof(double4) * n_obs, hipMemcpyHostToDevice));
+        if (int rc = replace_table(ctx, ctx->d_conflict_rows, rows.data(), (size_t)n_obs)) return rc;
     }
     const double thr_ee = r_ego + r_ego;
-    const ConflictP P = {B, n_ticks, n_obs, frame_window, rec, flags, n_obs > 0 ? obs_rec : nullptr, x_first, x_spawn, veh_range, mate_range,
-                         table ? ctx->d_conflict_rows.p : nullptr, cc_f, cc_r, double4{cc_f, cc_r, thr_ee, jsim_sqrt_threshold(thr_ee)},
-                         clear, who, row, hit_tick, hit_frame, hit_xy};
-    hipLaunchKernelGGL(conflict_ticks_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, P);
-    HIP_TRY(ctx, hipGetLastError());
-    return 0;
+    const ConflictP P = {recorder_buf(B, n_ticks, rec, flags, x_first, x_spawn), n_obs, frame_window, n_obs > 0 ? obs_rec : nullptr,
+                         veh_range, mate_range, table ? ctx->d_conflict_rows.p : nullptr, cc_f, cc_r,
+                         double4{cc_f, cc_r, thr_ee, jsim_sqrt_threshold(thr_ee)}, clear, who, row, hit_tick, hit_frame, hit_xy};
+    return launch_per_ego(ctx, conflict_ticks_kernel, B, stream, P);
 }
 
 #include "static_conflicts.inc"
@@ -2377,7 +2395,6 @@ extern "C" int jsim_loop_eval_static(jsim_ctx *ctx, int32_t B, int32_t n_ticks, 
                                      int32_t *hit, int32_t *off_tick, void *stream)
 {
     const char *const F = "jsim_loop_eval_static";
-    // (the argument checks come first: they need no context and no device)
     if (B < 0 || n_ticks < 0 || n_sets < 0 || n_rows < 0)
         return fail(ctx, -22, "%s: B=%d n_ticks=%d n_sets=%d n_rows=%d", F, B, n_ticks, n_sets, n_rows);
     if (include_hidden != 0 && include_hidden != 1) return fail(ctx, -22, "%s: include_hidden=%d is neither 0 nor 1", F, include_hidden);
@@ -2386,9 +2403,8 @@ extern "C" int jsim_loop_eval_static(jsim_ctx *ctx, int32_t B, int32_t n_ticks, 
     if (!rows && (n_sets > 0 || n_rows > 0)) return fail(ctx, -22, "%s: null rows with n_sets=%d n_rows=%d", F, n_sets, n_rows);
     if (!rec || !flags || !x_first || !x_spawn || !set_of || !clear || !who || !hit || !off_tick)
         return fail(ctx, -22, "%s: null device pointer", F);
+    if (int rc = check_ego_shape(ctx, F, ego_shape)) return rc;
     const double cc_f = ego_shape[0], cc_r = ego_shape[1], r_ego = ego_shape[2];
-    if (!std::isfinite(cc_f) || !std::isfinite(cc_r)) return fail(ctx, -22, "%s: ego_shape: a circle offset that is not finite", F);
-    if (!(r_ego > 0.0) || !std::isfinite(r_ego)) return fail(ctx, -22, "%s: ego_shape: radius %g is not positive and finite", F, r_ego);
     if (set_off) {
         if (set_off[0] != 0) return fail(ctx, -22, "%s: set_off[0]=%d, not 0", F, set_off[0]);
         for (int s = 0; s < n_sets; ++s)
@@ -2408,24 +2424,16 @@ extern "C" int jsim_loop_eval_static(jsim_ctx *ctx, int32_t B, int32_t n_ticks, 
         if (r[0] == 1.0 && !(r[5] > 0.0)) return fail(ctx, -22, "%s: rows[%d]: circle radius %g is not positive", F, i, r[5]);
         if (r[0] == 0.0 && (r[3] > r[5] || r[4] > r[6])) return fail(ctx, -22, "%s: rows[%d]: box with x1 > x2 or y1 > y2", F, i);
     }
-    if (!ctx) return fail(nullptr, -22, "%s: null ctx", F);
-    if (B == 0 || n_ticks == 0) return 0;
-    DeviceGuard dev_guard(ctx->device);
-    JSIM_GUARD_OK(ctx);
+    JSIM_RECORDER_CALL(B == 0 || n_ticks == 0);
     if (n_sets > 0) {
-        HIP_TRY(ctx, hipDeviceSynchronize()); // an earlier call's launch may still read the tables that are replaced
-        HIP_TRY(ctx, ctx->d_static_off.reserve((size_t)n_sets + 1));
-        HIP_TRY(ctx, hipMemcpy(ctx->d_static_off, set_off, sizeof(int32_t) * ((size_t)n_sets + 1), hipMemcpyHostToDevice));
-        if (n_rows > 0) {
-            HIP_TRY(ctx, ctx->d_static_rows.reserve((size_t)n_rows * JSIM_STATIC_ROW));
-            HIP_TRY(ctx, hipMemcpy(ctx->d_static_rows, rows, sizeof(double) * (size_t)n_rows * JSIM_STATIC_ROW, hipMemcpyHostToDevice));
-        }
+        if (int rc = replace_table(ctx, ctx->d_static_off, set_off, (size_t)n_sets + 1)) return rc;
+        if (n_rows > 0)
+            if (int rc = replace_table(ctx, ctx->d_static_rows, rows, (size_t)n_rows * JSIM_STATIC_ROW, false)) return rc;
     }
-    const StaticP P = {B, n_ticks, n_sets, include_hidden, rec, flags, x_first, x_spawn, set_of, n_sets > 0 ? ctx->d_static_off.p : nullptr,
-                       n_rows > 0 ? ctx->d_static_rows.p : nullptr, cc_f, cc_r, r_ego, clear, who, hit, off_tick};
-    hipLaunchKernelGGL(static_ticks_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, P);
-    HIP_TRY(ctx, hipGetLastError());
-    return 0;
+    const StaticP P = {recorder_buf(B, n_ticks, rec, flags, x_first, x_spawn), n_sets, include_hidden, set_of,
+                       n_sets > 0 ? ctx->d_static_off.p : nullptr, n_rows > 0 ? ctx->d_static_rows.p : nullptr, cc_f, cc_r, r_ego,
+                       clear, who, hit, off_tick};
+    return launch_per_ego(ctx, static_ticks_kernel, B, stream, P);
 }
 
 #include "episodes.inc"
@@ -2440,7 +2448,6 @@ extern "C" int jsim_loop_summarise_episodes(jsim_ctx *ctx, int32_t B, int32_t n_
                                             int64_t *ep_off, int32_t *ep_i, double *ep_d, void *stream)
 {
     const char *const F = "jsim_loop_summarise_episodes";
-    // (the argument checks come first: they need no context and no device)
     if (B < 0 || n_ticks < 0 || ep_cap < 0) return fail(ctx, -22, "%s: B=%d n_ticks=%d ep_cap=%d", F, B, n_ticks, ep_cap);
     const int n_veh = !!veh_clear + !!veh_who + !!veh_hit_tick + !!veh_hit_frame + !!veh_hit_xy;
     if (n_veh != 0 && n_veh != 5)
@@ -2449,22 +2456,14 @@ extern "C" int jsim_loop_summarise_episodes(jsim_ctx *ctx, int32_t B, int32_t n_
     if (n_st != 0 && n_st != 4) return fail(ctx, -22, "%s: the st_ group (st_clear, st_who, st_hit, st_off_tick) is given in part", F);
     if (!rs_val != !rs_trig) return fail(ctx, -22, "%s: the rs_ group (rs_val, rs_trig) is given in part", F);
     if (!rec || !flags || !x_first || !x_spawn || !ep_off || !ep_i || !ep_d) return fail(ctx, -22, "%s: null device pointer", F);
-    if (!ctx) return fail(nullptr, -22, "%s: null ctx", F);
-    DeviceGuard dev_guard(ctx->device);
-    JSIM_GUARD_OK(ctx);
-    const EpisodeP P = {B, n_ticks, ep_cap, rec, flags, x_first, x_spawn, veh_clear, veh_who, veh_hit_tick, veh_hit_frame, veh_hit_xy,
+    JSIM_RECORDER_CALL(false);     // (no ego, no tick: the scan still writes the offsets)
+    const EpisodeP P = {recorder_buf(B, n_ticks, rec, flags, x_first, x_spawn), ep_cap, veh_clear, veh_who, veh_hit_tick, veh_hit_frame, veh_hit_xy,
                         st_clear, st_who, st_hit, st_off_tick, rs_val, rs_trig, (long long *)ep_off, ep_i, ep_d};
-    if (B > 0) {
-        hipLaunchKernelGGL(episode_count_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, P);
-        HIP_TRY(ctx, hipGetLastError());
-    }
+    if (B > 0)
+        if (int rc = launch_per_ego(ctx, episode_count_kernel, B, stream, P)) return rc;
     hipLaunchKernelGGL(episode_scan_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, P);
     HIP_TRY(ctx, hipGetLastError());
-    if (B > 0) {
-        hipLaunchKernelGGL(episode_summary_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, P);
-        HIP_TRY(ctx, hipGetLastError());
-    }
-    return 0;
+    return B > 0 ? launch_per_ego(ctx, episode_summary_kernel, B, stream, P) : 0;
 }
 
 // the shape table's (thr, thr_sq) rows: check_collision_moving_bicycle's min_distance = the egos' radius + the vehicle's own

@@ -1,7 +1,8 @@
 // Stakeholder reasons per recorded tick and the replan trigger (DESIGN.md section 16): what the loop of
 // main/scenarios/overtaking_cyclist_bidirectional_road.py does once per tick -- evaluate_reasons (:127-128, :2007-2027, with
 // lib/reasons_evaluation.py inside) and reasons_evaluation (:141-142, :1907-1940) -- as one pass over the History recorder's
-// buffers (jsim_loop_set_recorder): one wavefront per ego, ticks 64 at a time, lane t owns tick k0 + t.
+// buffers (jsim_loop_set_recorder), walked as recorder_walk.inc says: one wavefront per ego, ticks 64 at a time, lane t owns tick
+// k0 + t.
 //
 // Lane-parallel: the ego's position at the start of the tick, the cyclist's recorded get(), the distance, the two in-range tests,
 // the policymaker value and the distance factor.  In sequence, in the reference's order: the two timers (one `+ DT` per in-range
@@ -10,12 +11,9 @@
 // ballot, one carried bit between chunks).
 
 struct ReasonTickP {
-    int B, n_ticks, n_obs;
-    const double *rec;        // [n][B][JSIM_REC_FIELDS]
-    const int *flags;         // [n][B]
+    RecorderBuf R;
+    int n_obs;
     const double *obs_rec;    // [n][n_obs][6] or NULL (no ego has a cyclist)
-    const double *x_first;    // [B][4] x, y, v, yaw at the start of tick 0
-    const double *x_spawn;    // [B][4] the respawn state
     const int *veh_of;        // [B] the ego's cyclist among the n_obs vehicles, -1: none
     const double *par;        // [B][JSIM_REASON_NPAR]
     const double *threshold;  // [B]
@@ -42,7 +40,8 @@ __device__ __forceinline__ double jrt_seq_timer(double &run, unsigned long long 
 
 __global__ __launch_bounds__(64) void reason_ticks_kernel(const ReasonTickP P)
 {
-    const int lane = threadIdx.x, b = blockIdx.x, B = P.B, n = P.n_ticks;
+    const RecorderBuf &R = P.R;
+    const int lane = threadIdx.x, b = blockIdx.x, B = R.B, n = R.n_ticks;
     const double *par = P.par + (size_t)JSIM_REASON_NPAR * b;
     const double dt = par[JSIM_REASON_DT];
     const double half_w = par[JSIM_REASON_WIDTH] / 2, centre = par[JSIM_REASON_CENTERLINE];
@@ -56,17 +55,17 @@ __global__ __launch_bounds__(64) void reason_ticks_kernel(const ReasonTickP P)
     unsigned long long tracker = P.carry[3 * (size_t)b + 2] != 0.0 ? 1ull : 0ull;
     int first = -1;
 
+    RecChunk C = {};
     for (int k0 = 0; k0 < n; k0 += 64) {
         const int k = k0 + lane;
         const bool valid = k < n;
-        const int cnt = (n - k0) < 64 ? (n - k0) : 64;
-        // the tick starts an episode when the record before it ended one (the ego was respawned after that record)
-        const bool start = valid && k > 0 && (P.flags[(size_t)(k - 1) * B + b] & (JSIM_REC_GOAL | JSIM_REC_AGE)) != 0;
-        double ex = 0.0, ey = 0.0, dist = NAN;
+        // tick 0 starts no episode here: the carry says what it starts from
+        jrw_enter(C, R, k0, jrw_end_mask(R, k, jrw_flag(R, b, k), false), false);
+        const int cnt = C.cnt;
+        const bool start = valid && ((C.s_cur >> lane) & 1ull) != 0ull;
+        double ex = 0.0, ey = 0.0, eyaw, dist = NAN;
         if (valid) {
-            const double *e = k == 0 ? P.x_first + 4 * (size_t)b : start ? P.x_spawn + 4 * (size_t)b
-                                                                         : P.rec + JSIM_REC_FIELDS * ((size_t)(k - 1) * B + b);
-            ex = e[0]; ey = e[1];
+            jrw_pose_at(R, b, k, start, ex, ey, eyaw);
             if (has) {
                 const double *c = P.obs_rec + 6 * ((size_t)k * P.n_obs + veh);
                 const double dx = c[0] - ex, dy = c[1] - ey;
@@ -102,7 +101,7 @@ __global__ __launch_bounds__(64) void reason_ticks_kernel(const ReasonTickP P)
         }
     }
     // the carry is the state the next tick starts from: a last record that ended its episode leaves a fresh one
-    if (n > 0 && (P.flags[(size_t)(n - 1) * B + b] & (JSIM_REC_GOAL | JSIM_REC_AGE)) != 0) { t_d = 0.0; t_c = 0.0; tracker = 0ull; }
+    if (n > 0 && jrw_is_end(jrw_flag(R, b, n - 1))) { t_d = 0.0; t_c = 0.0; tracker = 0ull; }
     if (lane == 0) {
         P.carry[3 * (size_t)b] = t_d; P.carry[3 * (size_t)b + 1] = t_c; P.carry[3 * (size_t)b + 2] = tracker ? 1.0 : 0.0;
         P.first[b] = first;

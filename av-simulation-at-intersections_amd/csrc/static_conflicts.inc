@@ -1,19 +1,16 @@
 // Static-obstacle clearance and contact per recorded tick (DESIGN.md section 18): what check_collision of main/lib/obstacles.py
 // (:157-176) on Obstacle.to_convex(margin) -- the planner's collision test, main/lib/mp_search_ww_generic.py:199-215 -- and
 // BoxObstacle / CircleObstacle.distance_to_point (:95-103, :150-154) answer when they are handed the driven poses' two collision
-// circle centres (main/lib/trajectories.py:11-55), as one pass over the History recorder's buffers: one wavefront per ego, ticks 64
-// at a time, lane t owns tick k0c + t (conflict_ticks_kernel's mapping, and its start-of-tick pose and episode ends).
+// circle centres (main/lib/trajectories.py:11-55), as one pass over the History recorder's buffers, walked as recorder_walk.inc says:
+// one wavefront per ego, ticks 64 at a time, lane t owns tick k0c + t.
 //
 // Lane-parallel: the pose, one sincos, the two circle centres, `clear`, `who` and `hit`.  An obstacle row is the same for every lane
 // of the wavefront: its address depends on the ego's set and the loop counter alone, so the row is read as wave-uniform values.
 // Per episode, from ballots: the first touching tick, written at the slot of the episode's first tick by lane 0.
 
 struct StaticP {
-    int B, n_ticks, n_sets, include_hidden;
-    const double *rec;        // [n][B][JSIM_REC_FIELDS]
-    const int *flags;         // [n][B]
-    const double *x_first;    // [B][4] x, y, v, yaw at the start of tick 0
-    const double *x_spawn;    // [B][4] the respawn state
+    RecorderBuf R;
+    int n_sets, include_hidden;
     const int *set_of;        // [B] the ego's obstacle set; outside [0, n_sets): an empty set
     const int *set_off;       // [n_sets + 1] a set's rows are [set_off[s], set_off[s + 1])
     const double *rows;       // [n_rows][JSIM_STATIC_ROW]
@@ -37,25 +34,24 @@ __device__ __forceinline__ double jsf_distance(bool circle, double g0, double g1
 // this body known not to alias the table its loads are scalar loads, the row's entries wave-uniform operands.
 __device__ __forceinline__ void jsf_ticks(const StaticP &P, const double *__restrict__ rows)
 {
-    const int lane = threadIdx.x, b = blockIdx.x, B = P.B, n = P.n_ticks;
+    const RecorderBuf &R = P.R;
+    const int lane = threadIdx.x, b = blockIdx.x, B = R.B, n = R.n_ticks;
     const int s = P.set_of[b];
     int lo = 0, hi = 0;
     if (s >= 0 && s < P.n_sets) { lo = P.set_off[s]; hi = P.set_off[s + 1]; }
 
-    unsigned long long e_prev = 0ull, e_cur = jcf_ends(P, b, lane);
+    RecChunk C = {};
     int ep_k0 = 0, ep_tick = -1;
     for (int k0c = 0; k0c < n; k0c += 64) {
         const int k = k0c + lane;
         const bool valid = k < n;
-        const int cnt = (n - k0c) < 64 ? (n - k0c) : 64;
-        // a tick starts an episode when the record before it ended one, and tick 0 does
-        const unsigned long long s_cur = (e_cur << 1) | (k0c == 0 ? 1ull : (e_prev >> 63));
+        jrw_enter(C, R, k0c, jrw_end_mask(R, k, jrw_flag(R, b, k), true), true);
 
         double clear = NAN;
         int who = -1, hit = -1;
         if (valid) {
             double ex, ey, eyaw, es, ec;
-            jcf_ego_pose(P, b, k, ex, ey, eyaw);
+            jrw_pose(R, b, k, ex, ey, eyaw);
             sincos(eyaw, &es, &ec);
             const double fx = ex + ec * P.cc_f, fy = ey + es * P.cc_f, rx = ex + ec * P.cc_r, ry = ey + es * P.cc_r;
             for (int o = lo; o < hi; ++o) {
@@ -82,19 +78,15 @@ __device__ __forceinline__ void jsf_ticks(const StaticP &P, const double *__rest
         if (valid) {
             const size_t q = (size_t)k * B + b;
             P.clear[q] = clear; P.who[q] = who; P.hit[q] = hit;
-            if (!((s_cur >> lane) & 1ull)) P.off_tick[q] = -1;    // not an episode's first tick
+            if (!((C.s_cur >> lane) & 1ull)) P.off_tick[q] = -1;    // not an episode's first tick
         }
         // the episodes of this chunk, one after the other (every branch is uniform: the masks are ballots)
-        for (int pos = 0; pos < cnt;) {
-            const unsigned long long rem = e_cur >> pos;
-            const int e = rem ? pos + (int)__builtin_ctzll(rem) : cnt - 1;
-            if ((s_cur >> pos) & 1ull) { ep_k0 = k0c + pos; ep_tick = -1; }
-            const unsigned long long h = touch & (~0ull << pos) & (~0ull >> (63 - e));
+        jrw_segments(C, [&](int pos, int e, bool starts, bool ends) {
+            if (starts) { ep_k0 = k0c + pos; ep_tick = -1; }
+            const unsigned long long h = touch & jrw_lanes(pos, e);
             if (ep_tick < 0 && h != 0ull) ep_tick = k0c + (int)__builtin_ctzll(h);
-            if (rem != 0ull && lane == 0) P.off_tick[(size_t)ep_k0 * B + b] = ep_tick;   // the episode ends here: its slot, written once
-            pos = e + 1;
-        }
-        e_prev = e_cur; e_cur = jcf_ends(P, b, k + 64);
+            if (ends && lane == 0) P.off_tick[(size_t)ep_k0 * B + b] = ep_tick;   // the episode ends here: its slot, written once
+        });
     }
 }
 

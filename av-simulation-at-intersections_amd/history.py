@@ -106,24 +106,32 @@ def recorded_ticks(ticks_run: int, cap: int):
     return min(int(ticks_run), int(cap)), int(ticks_run) > int(cap)
 
 
+def _per_episode(flags: np.ndarray, make):
+    """A list over egos (flags [n][B]) of lists over an ego's episodes (episode_bounds) of make(b, k0, k1)."""
+    f = np.asarray(flags).reshape(np.shape(flags)[0], -1)
+    return [[make(b, k0, k1) for k0, k1, _ in episode_bounds(f[:, b])] for b in range(f.shape[1])]
+
+
+def _min_clear(clear: np.ndarray, who: np.ndarray, b: int, k0: int, k1: int):
+    """(the smallest clearance of ego b over ticks [k0, k1), its first tick, `who` at that tick); (NaN, -1, -1) without one."""
+    c = clear[k0:k1, b]
+    if k1 <= k0 or np.isnan(c).all():
+        return float("nan"), -1, -1
+    k = int(np.nanargmin(c))
+    return float(c[k]), k0 + k, int(who[k0 + k, b])
+
+
 def reason_series(values: dict, flags: np.ndarray, dt: float):
     """The four lists the overtaking script keeps per run (main/scenarios/overtaking_cyclist_bidirectional_road.py:54-60,
     :2447-2451: time_values, reasons_policymaker_values, reasons_driver_values, reasons_cyclist_values), per ego and episode, from
     the per-tick values of a recorder (Recorder.reasons: `policymaker`, `driver`, `cyclist` [n][B]) and its flags [n][B], split
     where ego_histories splits (episode_bounds).  time_values is i * dt for tick i of the episode, as the script computes it.
     Returns a list over egos of lists over episodes of dicts of Python float lists."""
-    f = np.asarray(flags).reshape(np.shape(flags)[0], -1)
-    names = (("reasons_policymaker_values", "policymaker"), ("reasons_driver_values", "driver"), ("reasons_cyclist_values", "cyclist"))
-    out = []
-    for b in range(f.shape[1]):
-        eps = []
-        for k0, k1, _ in episode_bounds(f[:, b]):
-            ep = {"time_values": [i * float(dt) for i in range(k1 - k0)]}
-            for key, src in names:
-                ep[key] = np.asarray(values[src], dtype=np.float64)[k0:k1, b].tolist()
-            eps.append(ep)
-        out.append(eps)
-    return out
+    series = {"reasons_" + k + "_values": np.asarray(values[k], dtype=np.float64) for k in ("policymaker", "driver", "cyclist")}
+
+    def make(b, k0, k1):
+        return {"time_values": [i * float(dt) for i in range(k1 - k0)], **{key: v[k0:k1, b].tolist() for key, v in series.items()}}
+    return _per_episode(flags, make)
 
 
 def conflict_episodes(result: dict, flags: np.ndarray):
@@ -133,27 +141,18 @@ def conflict_episodes(result: dict, flags: np.ndarray):
     -1 / None), collision_xy (what check_collision_moving_cars / check_collision_moving_bicycle return for the episode: None or
     (x, y, frame)), min_clear and min_clear_tick (the episode's smallest clearance and its first tick; NaN / -1 for an ego without
     vehicles or an episode without a tick yet), closest_vehicle (the place in the ego's list of the vehicle that came closest)."""
-    f = np.asarray(flags).reshape(np.shape(flags)[0], -1)
     clear, who = np.asarray(result["clear"], dtype=np.float64), np.asarray(result["who"])
-    out = []
-    for b in range(f.shape[1]):
-        eps = []
-        for k0, k1, _ in episode_bounds(f[:, b]):
-            ep = {"contact": False, "tick": -1, "frame": -1, "xy": None, "collision_xy": None, "min_clear": float("nan"),
-                  "min_clear_tick": -1, "closest_vehicle": -1}
-            if k1 > k0:
-                tick = int(result["hit_tick"][k0, b])
-                if tick >= 0:
-                    x, y = (float(v) for v in result["hit_xy"][k0, b])
-                    frame = int(result["hit_frame"][k0, b])
-                    ep.update(contact=True, tick=tick, frame=frame, xy=(x, y), collision_xy=(x, y, frame))
-                c = clear[k0:k1, b]
-                if not np.isnan(c).all():
-                    k = int(np.nanargmin(c))
-                    ep.update(min_clear=float(c[k]), min_clear_tick=k0 + k, closest_vehicle=int(who[k0 + k, b]))
-            eps.append(ep)
-        out.append(eps)
-    return out
+
+    def make(b, k0, k1):
+        ep = {"contact": False, "tick": -1, "frame": -1, "xy": None, "collision_xy": None}
+        tick = int(result["hit_tick"][k0, b]) if k1 > k0 else -1
+        if tick >= 0:
+            x, y = (float(v) for v in result["hit_xy"][k0, b])
+            frame = int(result["hit_frame"][k0, b])
+            ep.update(contact=True, tick=tick, frame=frame, xy=(x, y), collision_xy=(x, y, frame))
+        ep["min_clear"], ep["min_clear_tick"], ep["closest_vehicle"] = _min_clear(clear, who, b, k0, k1)
+        return ep
+    return _per_episode(flags, make)
 
 
 def static_episodes(result: dict, flags: np.ndarray):
@@ -162,25 +161,19 @@ def static_episodes(result: dict, flags: np.ndarray):
     contact (bool), tick (the first tick that touches an obstacle, -1: none), obstacle (the `hit` of that tick, -1), min_clear and
     min_clear_tick (the episode's smallest clearance and its first tick; NaN / -1 for an ego without obstacles or an episode without
     a tick yet), closest_obstacle (the place in its set of the obstacle that came closest), ticks_off (how many ticks touch)."""
-    f = np.asarray(flags).reshape(np.shape(flags)[0], -1)
     clear, who, hit = np.asarray(result["clear"], dtype=np.float64), np.asarray(result["who"]), np.asarray(result["hit"])
-    out = []
-    for b in range(f.shape[1]):
-        eps = []
-        for k0, k1, _ in episode_bounds(f[:, b]):
-            ep = {"contact": False, "tick": -1, "obstacle": -1, "min_clear": float("nan"), "min_clear_tick": -1,
-                  "closest_obstacle": -1, "ticks_off": 0}
-            if k1 > k0:
-                tick = int(result["off_tick"][k0, b])
-                if tick >= 0:
-                    ep.update(contact=True, tick=tick, obstacle=int(hit[tick, b]), ticks_off=int((hit[k0:k1, b] >= 0).sum()))
-                c = clear[k0:k1, b]
-                if not np.isnan(c).all():
-                    k = int(np.nanargmin(c))
-                    ep.update(min_clear=float(c[k]), min_clear_tick=k0 + k, closest_obstacle=int(who[k0 + k, b]))
-            eps.append(ep)
-        out.append(eps)
-    return out
+
+    def make(b, k0, k1):
+        ep = {"contact": False, "tick": -1, "obstacle": -1}
+        ticks_off = 0
+        tick = int(result["off_tick"][k0, b]) if k1 > k0 else -1
+        if tick >= 0:
+            ep.update(contact=True, tick=tick, obstacle=int(hit[tick, b]))
+            ticks_off = int((hit[k0:k1, b] >= 0).sum())
+        ep["min_clear"], ep["min_clear_tick"], ep["closest_obstacle"] = _min_clear(clear, who, b, k0, k1)
+        ep["ticks_off"] = ticks_off
+        return ep
+    return _per_episode(flags, make)
 
 
 def episode_rows(summary: dict):

@@ -10,11 +10,12 @@ import os
 import numpy as np
 
 import conflicts_numpy as CN
+import recorder_numpy as RN
+from recorder_numpy import AGE, GOAL
 
 N = 200                                              # ticks per case
 TICK_COUNTS = (1, 2, 63, 64, 65, 127, 128, 129, 200)  # every case is also evaluated cut to these lengths
 WINDOWS = (0, 1, 3, 20)
-GOAL, AGE = 2, 4
 
 
 def shape_of(L, width, extra_length=0.64):
@@ -151,25 +152,12 @@ def recorder_arrays(cs):
     (a group's scripted vehicles are its first ego's, and every ego of the group meets them)."""
     B = len(cs)
     n_obs = 1 + sum(len(c["vehicles"]) for c in cs)
-    rec, flags = np.zeros((N, B, 7)), np.zeros((N, B), dtype=np.int32)
+    A = RN.ego_arrays([c["ego"] for c in cs], [c["flags"] for c in cs], DECOY, labels=[c["label"] for c in cs])
     obs, shapes = np.zeros((N, n_obs, 6)), np.zeros((n_obs, 4))
     obs[:, 0, :2], shapes[0] = DECOY, (*CAR, 2.86)
-    x_first, x_spawn = np.zeros((B, 4)), np.full((B, 4), -DECOY)
     veh_range, mate_range = np.zeros((B, 2), dtype=np.int32), np.zeros((B, 2), dtype=np.int32)
     o = 1
     for b, c in enumerate(cs):
-        ego, fl = c["ego"], c["flags"]
-        x_first[b] = ego[0, 0], ego[0, 1], 3.0, ego[0, 2]
-        rec[:-1, b, :3] = ego[1:]
-        rec[-1, b, :3] = ego[-1] + (ego[-1] - ego[-2])
-        rec[:, b, 3] = 3.0
-        for k in np.flatnonzero(fl & (GOAL | AGE)):
-            if k + 1 < N:
-                spawn = (ego[k + 1, 0], ego[k + 1, 1], 3.0, ego[k + 1, 2])
-                assert x_spawn[b, 0] == -DECOY or tuple(x_spawn[b]) == spawn, c["label"]     # one respawn state per ego
-                x_spawn[b] = spawn
-            rec[k, b, :3] = DECOY
-        flags[:, b] = fl
         veh_range[b] = o, o + len(c["vehicles"])
         for v, kind in zip(c["vehicles"], c["kinds"]):
             obs[:, o, 0], obs[:, o, 1], obs[:, o, 2], obs[:, o, 3] = v[:, 0], v[:, 1], 1.0, v[:, 2]
@@ -182,8 +170,7 @@ def recorder_arrays(cs):
             veh_range[b] = veh_range[members[0]] if b > members[0] else veh_range[b]
         else:
             mate_range[b] = b, b                                  # none
-    return {"rec": rec, "flags": flags, "obs": obs, "x_first": x_first, "x_spawn": x_spawn, "veh_range": veh_range,
-            "mate_range": mate_range, "shapes": shapes}
+    return {**A, "obs": obs, "veh_range": veh_range, "mate_range": mate_range, "shapes": shapes}
 
 
 def restate(A, w, n=N, loops=False, stats=None):

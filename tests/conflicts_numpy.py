@@ -6,36 +6,10 @@ per tick and `hit_tick`, `hit_frame`, `hit_xy` per episode.  eval_conflicts is v
 eval_conflicts_loops states the same with one Python loop per index and is what the vectorised form is checked against."""
 import numpy as np
 
-GOAL, AGE = 2, 4                                     # JSIM_REC_GOAL, JSIM_REC_AGE
+from recorder_numpy import episodes_of, start_poses   # (the tests and the fixture generator reach them as CN.*)
+
 MAX_OBS = 8                                          # JSIM_MAX_OBS
 MAX_WINDOW = 20
-
-
-def start_poses(rec, flags, x_first, x_spawn):
-    """[n][B][3]: every ego's (x, y, yaw) at the start of every tick: x_first at tick 0, x_spawn behind a record that ended an
-    episode, else the record before (x_first / x_spawn are in the MPC's order x, y, v, yaw; a record is x, y, yaw, ...)."""
-    rec = np.asarray(rec, dtype=np.float64)
-    n, B = rec.shape[:2]
-    pose = np.empty((n, B, 3))
-    if n:
-        pose[0] = np.asarray(x_first, dtype=np.float64).reshape(B, 4)[:, [0, 1, 3]]
-        pose[1:] = rec[:-1, :, :3]
-        s = np.zeros((n, B), dtype=bool)
-        s[1:] = (np.asarray(flags).reshape(n, B)[:-1] & (GOAL | AGE)) != 0
-        pose[s] = np.broadcast_to(np.asarray(x_spawn, dtype=np.float64).reshape(B, 4)[:, [0, 1, 3]], (n, B, 3))[s]
-    return pose
-
-
-def episodes_of(flags_b):
-    """(k0, k1) inclusive of every episode of one ego that has a tick: from a start to the tick whose flag ends it, or to n - 1."""
-    f = np.asarray(flags_b).reshape(-1)
-    out, k0 = [], 0
-    for k in np.flatnonzero(f & (GOAL | AGE)):
-        out.append((k0, int(k)))
-        k0 = int(k) + 1
-    if k0 < f.size:
-        out.append((k0, f.size - 1))
-    return out
 
 
 def circle_centres(pose, cc):

@@ -14,12 +14,12 @@ import conflict_cases as TC
 import conflicts_numpy as CN
 import reason_ticks_cases as RC
 import reason_ticks_numpy as TN
+from recorder_numpy import AGE, FAILED, GOAL   # noqa: F401
 import static_cases as SC
 import static_numpy as SN
 
 N = TC.N
 TICK_COUNTS = (0, 1, 2, 63, 64, 65, 127, 128, 129, 200)
-FAILED, GOAL, AGE = 1, 2, 4
 EVENT_TICKS = (0, 62, 63, 64, 65, N - 1)               # ego b has its extreme values on EVENT_TICKS[b % 6]
 EVERY, NEVER, THREE = 28, 29, 30                       # the three egos that are no family's
 

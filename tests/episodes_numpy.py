@@ -6,12 +6,13 @@ import math
 
 import numpy as np
 
+from recorder_numpy import FAILED, start_poses
+
 EP_INT = ("ego", "k0", "n", "end", "failed", "dev_tick", "veh_tick", "veh_who", "veh_hit_tick", "veh_hit_frame", "st_tick", "st_who",
           "st_off_tick", "st_obstacle", "st_ticks_off", "replan_tick")
 EP_DOUBLE = ("length", "v_mean", "v_max", "a_min", "a_max", "delta_absmax", "dev_max", "dev_mean", "veh_clear", "veh_hit_x",
              "veh_hit_y", "st_clear", "pm_min", "driver_min", "cyclist_min", "dist_min")
 SUMS = ("length", "v_mean", "dev_mean")                # the columns with a tolerance; every other one is exact
-FAILED, GOAL, AGE = 1, 2, 4
 NAN = float("nan")
 
 
@@ -34,6 +35,7 @@ def summarise(H, rec, flags, x_first, x_spawn, veh=None, st=None, rs=None):
     rec = np.asarray(rec, dtype=np.float64)
     n, B = rec.shape[:2]
     flags = np.asarray(flags).reshape(n, B)
+    pose = start_poses(rec, flags, x_first, x_spawn)
     rows = []
     off = [0]
     for b in range(B):
@@ -44,8 +46,7 @@ def summarise(H, rec, flags, x_first, x_spawn, veh=None, st=None, rs=None):
             if k1 > k0:
                 steps = []
                 for k in range(k0, k1):
-                    s = x_first[b] if k == 0 else (x_spawn[b] if flags[k - 1, b] & (GOAL | AGE) else rec[k - 1, b])
-                    dx, dy = rec[k, b, 0] - s[0], rec[k, b, 1] - s[1]
+                    dx, dy = rec[k, b, 0] - pose[k, b, 0], rec[k, b, 1] - pose[k, b, 1]
                     steps.append(math.sqrt(dx * dx + dy * dy))
                 v, delta, a, dev = (rec[k0:k1, b, j].tolist() for j in (3, 4, 5, 6))
                 r["failed"] = sum(1 for k in range(k0, k1) if flags[k, b] & FAILED)

@@ -9,11 +9,12 @@ import os
 import numpy as np
 
 import reason_ticks_numpy as TN
+import recorder_numpy as RN
+from recorder_numpy import AGE, GOAL
 
 N = 200                                              # ticks per case
 TICK_COUNTS = (1, 2, 63, 64, 65, 127, 128, 129, 200)  # every case is also evaluated cut to these lengths
 SPLITS = (64, 37)                                    # the two-call splits of a run (restatement-made)
-GOAL, AGE = 2, 4
 X_RIGHT, X_LEFT, X_CYC = 2.0, -2.0, 2.3              # the ego's lane positions and the cyclist's
 V_CYC = 5.0 / 3.6
 FAR = 1.0e3                                          # a timer threshold that is never reached
@@ -132,29 +133,18 @@ def recorder_arrays(cs):
     away state (as the goal state would be) and tick k + 1 starts at x_spawn.  Vehicle 0 is a decoy; case b's cyclist is vehicle
     B - b (the order reversed), so that no ego's index is its own."""
     B = len(cs)
-    rec = np.zeros((N, B, 7))
-    flags = np.zeros((N, B), dtype=np.int32)
+    heading = np.full((N, 1), np.pi / 2)
+    A = RN.ego_arrays([np.hstack([c["pos"], heading]) for c in cs], [c["flags"] for c in cs], DECOY, labels=[c["label"] for c in cs])
+    A["rec"][:, :, 2] = np.pi / 2                         # (a far away state keeps its heading here)
     obs = np.zeros((N, B + 1, 6))
     obs[:, 0, :2] = DECOY
-    x_first, x_spawn = np.zeros((B, 4)), np.full((B, 4), -DECOY)
     veh = np.zeros(B, dtype=np.int32)
     for b, c in enumerate(cs):
-        pos, fl = c["pos"], c["flags"]
-        x_first[b] = pos[0, 0], pos[0, 1], 3.0, np.pi / 2
-        rec[:-1, b, :2] = pos[1:]
-        rec[-1, b, :2] = pos[-1] + (pos[-1] - pos[-2])
-        rec[:, b, 2], rec[:, b, 3] = np.pi / 2, 3.0
-        for k in np.flatnonzero(fl & (GOAL | AGE)):
-            if k + 1 < N:
-                x_spawn[b] = pos[k + 1, 0], pos[k + 1, 1], 3.0, np.pi / 2
-            rec[k, b, :2] = DECOY
-        flags[:, b] = fl
         veh[b] = B - b if c["veh"] >= 0 else -1
         obs[:, B - b, :2] = c["cyc"]
         obs[:, B - b, 2], obs[:, B - b, 3] = V_CYC, np.pi / 2
-    return {"rec": rec, "flags": flags, "obs": obs, "x_first": x_first, "x_spawn": x_spawn, "veh_of": veh,
-            "par": np.stack([c["par"] for c in cs]), "threshold": np.array([c["threshold"] for c in cs]),
-            "carry": np.stack([c["carry"] for c in cs])}
+    return {**A, "obs": obs, "veh_of": veh, "par": np.stack([c["par"] for c in cs]),
+            "threshold": np.array([c["threshold"] for c in cs]), "carry": np.stack([c["carry"] for c in cs])}
 
 
 def restate(A, n=N, carry=None, k0=0):

@@ -5,32 +5,17 @@ The lane-parallel part is vectorised over ticks and egos; the timers and the tra
 egos only), with the additions the reference makes."""
 import numpy as np
 
-GOAL, AGE = 2, 4                                     # JSIM_REC_GOAL, JSIM_REC_AGE
+from recorder_numpy import episode_starts, is_end, start_poses
+
 # columns of a parameter row (JSIM_REASON_* of include/jsim_mpc.h) that the evaluation reads
 DT, CENTRE, WIDTH, REF_D, BUF_D, THR_D, REF_C, BUF_C, THR_C = 0, 3, 4, 5, 6, 7, 8, 9, 10
 DEFAULT_PAR = np.array([0.1, 2.0, 30.0 / 3.6, 0.0, 2.0, 10.0, 2.0, 8.0, 8.0, 2.0, 5.0, 1.0])
 THRESHOLD = 0.7                                      # ReasonParameters.REASONS_THRESHOLD
 
 
-def episode_starts(flags):
-    """[n][B] bool: tick k is the first of an episode because record k - 1 ended one (never tick 0: the carry decides there)."""
-    f = np.asarray(flags).reshape(np.shape(flags)[0], -1)
-    s = np.zeros(f.shape, dtype=bool)
-    s[1:] = (f[:-1] & (GOAL | AGE)) != 0
-    return s
-
-
 def start_positions(rec, flags, x_first, x_spawn):
     """[n][B][2]: the ego's (x, y) at the start of every tick."""
-    rec = np.asarray(rec, dtype=np.float64)
-    n, B = rec.shape[:2]
-    pos = np.empty((n, B, 2))
-    if n:
-        pos[0] = np.asarray(x_first, dtype=np.float64).reshape(B, 4)[:, :2]
-        pos[1:] = rec[:-1, :, :2]
-        s = episode_starts(flags)
-        pos[s] = np.broadcast_to(np.asarray(x_spawn, dtype=np.float64).reshape(B, 4)[:, :2], (n, B, 2))[s]
-    return pos
+    return start_poses(rec, flags, x_first, x_spawn)[:, :, :2]
 
 
 def eval_ticks(rec, flags, obs, x_first, x_spawn, veh_of, par, threshold, carry=None):
@@ -88,5 +73,5 @@ def eval_ticks(rec, flags, obs, x_first, x_spawn, veh_of, par, threshold, carry=
     trig |= (lo[:, :, 0] * 2 + lo[:, :, 1] * 4 + lo[:, :, 2] * 8).astype(np.int32)
     out_carry = np.stack([t_d, t_c, tracker.astype(np.float64)], axis=1) if n else carry.copy()
     if n:
-        out_carry[(flags[n - 1] & (GOAL | AGE)) != 0] = 0.0   # the next tick starts an episode
+        out_carry[is_end(flags[n - 1])] = 0.0   # the next tick starts an episode
     return {"val": np.stack([pol, drv, cyc, dist], axis=2), "timers": timers, "trig": trig, "first": first, "carry": out_carry}

@@ -14,7 +14,7 @@ import os
 import numpy as np
 
 import conflict_cases as TC
-import conflicts_numpy as CN
+import recorder_numpy as RN
 import static_numpy as SN
 from conflict_cases import CAR, GOAL, AGE, N, blip, line, pw, respawning, still   # noqa: F401
 
@@ -132,23 +132,8 @@ DECOY = TC.DECOY
 def recorder_arrays(cs):
     """rec [N][B][7], flags [N][B], x_first, x_spawn [B][4], set_of [B] for a launch with one ego per case.  rec[k] is the pose at the
     start of tick k + 1, except where flags[k] ends the episode: there rec[k] is a far away state and tick k + 1 starts at x_spawn."""
-    B = len(cs)
-    rec, flags = np.zeros((N, B, 7)), np.zeros((N, B), dtype=np.int32)
-    x_first, x_spawn = np.zeros((B, 4)), np.full((B, 4), -DECOY)
-    for b, c in enumerate(cs):
-        ego, fl = c["ego"], c["flags"]
-        x_first[b] = ego[0, 0], ego[0, 1], 3.0, ego[0, 2]
-        rec[:-1, b, :3] = ego[1:]
-        rec[-1, b, :3] = ego[-1]
-        rec[:, b, 3] = 3.0
-        for k in np.flatnonzero(fl & (GOAL | AGE)):
-            if k + 1 < N:
-                spawn = (ego[k + 1, 0], ego[k + 1, 1], 3.0, ego[k + 1, 2])
-                assert x_spawn[b, 0] == -DECOY or tuple(x_spawn[b]) == spawn, c["label"]     # one respawn state per ego
-                x_spawn[b] = spawn
-            rec[k, b, :3] = DECOY
-        flags[:, b] = fl
-    return {"rec": rec, "flags": flags, "x_first": x_first, "x_spawn": x_spawn, "set_of": np.array([c["set"] for c in cs], dtype=np.int32)}
+    A = RN.ego_arrays([c["ego"] for c in cs], [c["flags"] for c in cs], DECOY, hold_last=True, labels=[c["label"] for c in cs])
+    return {**A, "set_of": np.array([c["set"] for c in cs], dtype=np.int32)}
 
 
 def restate(A, g, hidden, n=N, loops=False, stats=None, egos=None):
@@ -163,7 +148,7 @@ def expected_off_tick(hit, flags):
     n, B = hit.shape
     out = np.full((n, B), -1, dtype=np.int32)
     for b in range(B):
-        for k0, k1 in CN.episodes_of(flags[:n, b]):
+        for k0, k1 in RN.episodes_of(flags[:n, b]):
             for k in range(k0, k1 + 1):
                 if hit[k, b] >= 0:
                     out[k0, b] = k

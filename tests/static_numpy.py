@@ -1,12 +1,13 @@
 """Numpy restatement of the static-obstacle evaluation, written from the contract and used by the tests as
 the CPU side of jsim_loop_eval_static and by tools/bench_static.py as its baseline: from a History recorder's arrays every ego's
-pose at the start of every tick (section 17's rule: conflicts_numpy.start_poses), its two circle centres, and against the rows of
+pose at the start of every tick (recorder_numpy.start_poses), its two circle centres, and against the rows of
 its obstacle set `clear`, `who`, `hit` per tick and `off_tick` per episode.  eval_static is vectorised over ticks and over the egos
 that share a set; eval_static_loops states the same with one Python loop per index and is what the vectorised form is checked
 against."""
 import numpy as np
 
 import conflicts_numpy as CN
+import recorder_numpy as RN
 
 ROW = 32                                             # JSIM_STATIC_ROW
 
@@ -38,7 +39,7 @@ def _inputs(rec, flags, x_first, x_spawn, set_of, set_off, rows, ego_shape):
     rows = np.asarray(rows, dtype=np.float64).reshape(-1, ROW)
     set_of = np.broadcast_to(np.asarray(set_of, dtype=np.int64), (B,))
     cc_f, cc_r, radius = (float(v) for v in ego_shape)
-    pose = CN.start_poses(rec, flags, x_first, x_spawn)
+    pose = RN.start_poses(rec, flags, x_first, x_spawn)
     return n, B, flags, set_of, set_off, rows, pose, CN.circle_centres(pose, cc_f), CN.circle_centres(pose, cc_r), radius
 
 
@@ -50,7 +51,7 @@ def _empty(n, B):
 def _off_ticks(out, flags):
     n, B = flags.shape
     for b in range(B):
-        for k0, k1 in CN.episodes_of(flags[:, b]):
+        for k0, k1 in RN.episodes_of(flags[:, b]):
             t = np.flatnonzero(out["hit"][k0:k1 + 1, b] >= 0)
             if t.size:
                 out["off_tick"][k0, b] = k0 + int(t[0])
@@ -131,6 +132,6 @@ def eval_static_loops(rec, flags, x_first, x_spawn, set_of, set_off, rows, ego_s
         for k in range(n):
             if out["hit"][k, b] >= 0 and out["off_tick"][k0, b] < 0:
                 out["off_tick"][k0, b] = k
-            if flags[k, b] & (CN.GOAL | CN.AGE):
+            if RN.is_end(flags[k, b]):
                 k0 = k + 1
     return out

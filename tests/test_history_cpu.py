@@ -36,6 +36,31 @@ def test_episodes_split_at_goal_and_age(H):
     assert ep["ticks"][2].tolist() == [10] and ep["end"][2].tolist() == [H.END_RUNNING]
 
 
+def test_restated_episodes_agree_with_episode_bounds(H):
+    """recorder_numpy.episodes_of (the restatements' rule) and history.episode_bounds (the package's) are two texts of one rule:
+    on every flag series of the four case families, cut to every tick count the families are evaluated at, they give the same
+    episodes, and episode_bounds adds only the running episode without a tick."""
+    import conflict_cases as TC
+    import episode_cases as EC
+    import reason_ticks_cases as RC
+    import recorder_numpy as RN
+    import static_cases as SC
+    families = ((TC.recorder_arrays(TC.cases())["flags"], TC.TICK_COUNTS), (SC.recorder_arrays(SC.cases())["flags"], SC.TICK_COUNTS),
+                (RC.recorder_arrays(RC.cases())["flags"], RC.TICK_COUNTS), (EC.recorder_arrays()["flags"], EC.TICK_COUNTS))
+    series = ends = 0
+    for flags, counts in families:
+        for n in counts:
+            for b in range(flags.shape[1]):
+                f = flags[:n, b]
+                bounds, mine = H.episode_bounds(f), RN.episodes_of(f)
+                assert [(k0, k1 - 1) for k0, k1, _ in bounds if k1 > k0] == mine, (n, b)
+                assert all(k1 > k0 for k0, k1, _ in bounds[:-1]) and bounds[-1][2] == H.END_RUNNING and bounds[-1][1] == n, (n, b)
+                assert [e for _, _, e in bounds[:-1]] == [H.END_GOAL if f[k1] & H.GOAL else H.END_AGE for _, k1 in mine[:len(bounds) - 1]]
+                assert np.array_equal(np.flatnonzero(RN.is_end(f)), [k1 - 1 for _, k1, _ in bounds[:-1]]), (n, b)
+                series, ends = series + 1, ends + len(bounds) - 1
+    assert series == (28 + 29 + 27) * 9 + 87 * 10 and ends > 1000       # (the families are all there, and they do end episodes)
+
+
 def test_histories_spawn_entries_fields_and_time(H):
     rec, fl = _synthetic(7, 2, seed=1)
     fl[3, 1] = H.GOAL

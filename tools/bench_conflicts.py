@@ -11,19 +11,9 @@ read-back), which tells the kernel's share of the call from the read-back's.  Pr
 
     python3 tools/bench_conflicts.py [--runs 9] [--warmup 2] [--ticks 300] [--out profiles/NAME.txt]
 """
-import argparse
-import importlib
-import json
-import os
-import statistics
-import sys
-import time
-
 import numpy as np
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, REPO)
-sys.path.insert(0, os.path.join(REPO, "tests"))
+import recorder_bench as RB
 
 
 def launch_alone(pkg, torch, r, out, w, warmup, runs):
@@ -36,68 +26,32 @@ def launch_alone(pkg, torch, r, out, w, warmup, runs):
     f64 = [torch.empty(n, B, dtype=torch.float64, device=dev), torch.empty(n, B, 2, dtype=torch.float64, device=dev)]
     i32 = [torch.empty(n, B, dtype=torch.int32, device=dev) for _ in range(4)]
     p = lambda t: t.data_ptr()
-    ts = []
-    for run in range(warmup + runs):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        rc = eng.lib.jsim_loop_eval_conflicts(eng._ctx, B, n, p(r.rec), p(r.flags), r.n_obs, p(r.obs), p(r.x0_first), p(r.loop.x0_spawn),
-                                              p(veh), p(mate), None, ego.ctypes.data, w, p(f64[0]), *[p(t) for t in i32], p(f64[1]), None)
-        torch.cuda.synchronize()
-        if run >= warmup:
-            ts.append((time.perf_counter() - t0) * 1e3)
-        pkg._cabi.check(rc, eng._ctx, "jsim_loop_eval_conflicts")
-    return ts
+    call = lambda: eng.lib.jsim_loop_eval_conflicts(eng._ctx, B, n, p(r.rec), p(r.flags), r.n_obs, p(r.obs), p(r.x0_first), p(r.loop.x0_spawn),
+                                                    p(veh), p(mate), None, ego.ctypes.data, w, p(f64[0]), *[p(t) for t in i32], p(f64[1]), None)
+    return RB.launch_alone(pkg, torch, eng, "jsim_loop_eval_conflicts", call, runs, warmup)
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--runs", type=int, default=9)
-    ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--ticks", type=int, default=300)
-    ap.add_argument("--out")
-    a = ap.parse_args()
-    import torch
-    pkg = importlib.import_module("av-simulation-at-intersections_amd")
+    a = RB.arguments(runs=9, warmup=2)
+    torch, pkg = RB.setup("bench_conflicts")
     import conflicts_numpy as CN
-    W = pkg.workloads
-    routes = W.route_table(False)[0]
-    K, T = a.ticks, 13
-    res = {"ticks": K, "T": T, "runs": a.runs, "warmup": a.warmup, "vehicles": len(W.OBSTACLE_SPECS), "gpu_ms": {}, "numpy_ms": {},
-           "launch_ms": {}, "episodes_ms": {}, "readback_ms": {}, "max_clear_err": {}, "contacts": {}, "episodes": {}}
+    K = a.ticks
+    res = {"ticks": K, "T": RB.T, "runs": a.runs, "warmup": a.warmup, "vehicles": len(pkg.workloads.OBSTACLE_SPECS), "gpu_ms": {},
+           "numpy_ms": {}, "launch_ms": {}, "episodes_ms": {}, "readback_ms": {}, "max_clear_err": {}, "contacts": {}, "episodes": {}}
     for B in (256, 4096):
-        eng, x0 = W.make_engine(routes, W.ego_batch(routes, B, T, rank=2), T, "cuda:0")
-        loop = pkg.ScenarioLoop(eng, x0, W.OBSTACLE_SPECS, hist_cap=K, max_age=W.MAX_AGE, record=K)
-        loop.run(K)
-        torch.cuda.synchronize()
-        r = loop.recorder
-        tr = []
-        for _ in range(3):                                              # what a host evaluation starts with
-            t0 = time.perf_counter()
-            host_rec, host_obs = r.rec.cpu().numpy(), r.obs.cpu().numpy()
-            tr.append((time.perf_counter() - t0) * 1e3)
+        r = RB.recorded_loop(pkg, torch, B, K)
+        eng = r.loop.eng
+        tr, (host_rec, host_obs) = RB.timed(lambda: (r.rec.cpu().numpy(), r.obs.cpu().numpy()), 3)   # what a host evaluation starts with
         res["readback_ms"][str(B)] = min(tr)
         host = [host_rec, r.flags.cpu().numpy(), host_obs, r.x0_first.cpu().numpy(), r.loop.x0_spawn.cpu().numpy()]
         for w in (0, 3):
             key = f"{B}/w{w}"
-            ts = []
-            for run in range(a.warmup + a.runs):
-                t0 = time.perf_counter()
-                out = r.conflicts(frame_window=w)
-                if run >= a.warmup:
-                    ts.append((time.perf_counter() - t0) * 1e3)
-            res["gpu_ms"][key] = {"median": statistics.median(ts), "min": min(ts), "max": max(ts)}
-            res["launch_ms"][key] = statistics.median(launch_alone(pkg, torch, r, out, w, a.warmup, a.runs))
-            tn = []
-            for _ in range(3):
-                t0 = time.perf_counter()
-                ref = CN.eval_conflicts(*host, out["veh_range"], out["mate_range"], eng.vehicle_shapes, out["ego_shape"], w)
-                tn.append((time.perf_counter() - t0) * 1e3)
+            ts, out = RB.timed(lambda: r.conflicts(frame_window=w), a.runs, a.warmup)
+            res["gpu_ms"][key] = RB.stats(ts)
+            res["launch_ms"][key] = RB.stats(launch_alone(pkg, torch, r, out, w, a.warmup, a.runs))["median"]
+            tn, ref = RB.timed(lambda: CN.eval_conflicts(*host, out["veh_range"], out["mate_range"], eng.vehicle_shapes, out["ego_shape"], w), 3)
             res["numpy_ms"][key] = min(tn)
-            te = []
-            for _ in range(3):
-                t0 = time.perf_counter()
-                eps = pkg.history.conflict_episodes(out, host[1])
-                te.append((time.perf_counter() - t0) * 1e3)
+            te, eps = RB.timed(lambda: pkg.history.conflict_episodes(out, host[1]), 3)
             res["episodes_ms"][key] = min(te)
             for k in ("who", "row", "hit_tick", "hit_frame"):
                 assert np.array_equal(out[k], ref[k]), (key, k)
@@ -105,11 +59,7 @@ def main():
             res["max_clear_err"][key] = float(np.max(np.abs(out["clear"] - ref["clear"]) / np.maximum(1.0, np.abs(ref["clear"]))))
             res["contacts"][key] = int(sum(e["contact"] for ep in eps for e in ep))
             res["episodes"][key] = int(sum(len(ep) for ep in eps))
-    line = json.dumps(res)
-    print(line)
-    if a.out:
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
+    RB.emit(res, a.out)
 
 
 if __name__ == "__main__":

@@ -14,19 +14,9 @@ line and, with --out, writes it there.
 
     python3 tools/bench_static.py [--runs 30] [--warmup 3] [--ticks 300] [--out profiles/NAME.txt]
 """
-import argparse
-import importlib
-import json
-import os
-import statistics
-import sys
-import time
-
 import numpy as np
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, REPO)
-sys.path.insert(0, os.path.join(REPO, "tests"))
+import recorder_bench as RB
 
 
 def launch_alone(pkg, torch, r, out, rows, hidden, warmup, runs):
@@ -38,85 +28,43 @@ def launch_alone(pkg, torch, r, out, rows, hidden, warmup, runs):
     clear = torch.empty(n, B, dtype=torch.float64, device=dev)
     i32 = [torch.empty(n, B, dtype=torch.int32, device=dev) for _ in range(3)]
     p = lambda t: t.data_ptr()
-    ts = []
-    for run in range(warmup + runs):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        rc = eng.lib.jsim_loop_eval_static(eng._ctx, B, n, p(r.rec), p(r.flags), p(r.x0_first), p(r.loop.x0_spawn), p(sof), 1, off.ctypes.data,
-                                           len(rows), rows.ctypes.data, ego.ctypes.data, hidden, p(clear), *[p(t) for t in i32], None)
-        torch.cuda.synchronize()
-        if run >= warmup:
-            ts.append((time.perf_counter() - t0) * 1e3)
-        pkg._cabi.check(rc, eng._ctx, "jsim_loop_eval_static")
-    return ts
+    call = lambda: eng.lib.jsim_loop_eval_static(eng._ctx, B, n, p(r.rec), p(r.flags), p(r.x0_first), p(r.loop.x0_spawn), p(sof), 1,
+                                                 off.ctypes.data, len(rows), rows.ctypes.data, ego.ctypes.data, hidden, p(clear),
+                                                 *[p(t) for t in i32], None)
+    return RB.launch_alone(pkg, torch, eng, "jsim_loop_eval_static", call, runs, warmup)
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--runs", type=int, default=30)
-    ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--ticks", type=int, default=300)
-    ap.add_argument("--out")
-    a = ap.parse_args()
-    import torch
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_static needs a HIP device: a time taken without one says nothing")
-    pkg = importlib.import_module("av-simulation-at-intersections_amd")
+    a = RB.arguments(runs=30, warmup=3)
+    torch, pkg = RB.setup("bench_static")
     import static_numpy as SN
-    W = pkg.workloads
-    routes = W.route_table(False)[0]
-    K, T = a.ticks, 13
+    K = a.ticks
     obstacles = pkg.planner.intersection_obstacles(1, 1)
-    res = {"ticks": K, "T": T, "runs": a.runs, "warmup": a.warmup, "obstacles": len(obstacles), "gpu_ms": {}, "numpy_ms": {}, "launch_ms": {},
-           "episodes_ms": {}, "readback_ms": {}, "max_clear_err": {}, "mismatches": {}, "ticks_touching": {}, "episodes": {}, "output_bytes": {}}
+    res = {"ticks": K, "T": RB.T, "runs": a.runs, "warmup": a.warmup, "obstacles": len(obstacles), "gpu_ms": {}, "numpy_ms": {},
+           "launch_ms": {}, "episodes_ms": {}, "readback_ms": {}, "max_clear_err": {}, "mismatches": {}, "ticks_touching": {}, "episodes": {},
+           "output_bytes": {}}
     for B in (256, 4096):
-        eng, x0 = W.make_engine(routes, W.ego_batch(routes, B, T, rank=2), T, "cuda:0")
-        loop = pkg.ScenarioLoop(eng, x0, W.OBSTACLE_SPECS, hist_cap=K, max_age=W.MAX_AGE, record=K)
-        loop.run(K)
-        torch.cuda.synchronize()
-        r = loop.recorder
-        tr = []
-        for _ in range(3):                                              # what a host evaluation starts with
-            t0 = time.perf_counter()
-            host_rec = r.rec.cpu().numpy()
-            tr.append((time.perf_counter() - t0) * 1e3)
+        r = RB.recorded_loop(pkg, torch, B, K)
+        tr, host_rec = RB.timed(lambda: r.rec.cpu().numpy(), 3)         # what a host evaluation starts with
         res["readback_ms"][str(B)] = min(tr)
         host = [host_rec, r.flags.cpu().numpy(), r.x0_first.cpu().numpy(), r.loop.x0_spawn.cpu().numpy()]
         res["output_bytes"][str(B)] = K * B * (8 + 4 + 4 + 4)
         for hidden in (0, 1):
             key = f"{B}/hidden{hidden}"
-            ts = []
-            for run in range(a.warmup + a.runs):
-                t0 = time.perf_counter()
-                out = r.static_conflicts(obstacles, include_hidden=bool(hidden))
-                if run >= a.warmup:
-                    ts.append((time.perf_counter() - t0) * 1e3)
-            res["gpu_ms"][key] = {"median": statistics.median(ts), "min": min(ts), "max": max(ts)}
+            ts, out = RB.timed(lambda: r.static_conflicts(obstacles, include_hidden=bool(hidden)), a.runs, a.warmup)
+            res["gpu_ms"][key] = RB.stats(ts)
             rows = pkg.planner.static_obstacle_rows(obstacles, out["margin"])
-            res["launch_ms"][key] = statistics.median(launch_alone(pkg, torch, r, out, rows, hidden, a.warmup, a.runs))
-            tn = []
-            for _ in range(2):
-                t0 = time.perf_counter()
-                ref = SN.eval_static(*host, out["set_of"], [0, len(rows)], rows, out["ego_shape"], bool(hidden))
-                tn.append((time.perf_counter() - t0) * 1e3)
+            res["launch_ms"][key] = RB.stats(launch_alone(pkg, torch, r, out, rows, hidden, a.warmup, a.runs))["median"]
+            tn, ref = RB.timed(lambda: SN.eval_static(*host, out["set_of"], [0, len(rows)], rows, out["ego_shape"], bool(hidden)), 2)
             res["numpy_ms"][key] = min(tn)
-            te = []
-            for _ in range(2):
-                t0 = time.perf_counter()
-                eps = pkg.history.static_episodes(out, host[1])
-                te.append((time.perf_counter() - t0) * 1e3)
+            te, eps = RB.timed(lambda: pkg.history.static_episodes(out, host[1]), 2)
             res["episodes_ms"][key] = min(te)
             res["mismatches"][key] = {k: int((out[k] != ref[k]).sum()) for k in ("who", "hit", "off_tick")}
             res["max_clear_err"][key] = float(np.max(np.abs(out["clear"] - ref["clear"]) / np.maximum(1.0, np.abs(ref["clear"]))))
             res["ticks_touching"][key] = int(out["contact"].sum())
             res["episodes"][key] = int(sum(len(ep) for ep in eps))
-    line = json.dumps(res)
-    print(line)
-    if a.out:
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
-    if any(v for m in res["mismatches"].values() for v in m.values()) or max(res["max_clear_err"].values()) > 1e-12:
-        raise SystemExit("the device result differs from the restatement: see mismatches / max_clear_err")
+    differs = any(v for m in res["mismatches"].values() for v in m.values()) or max(res["max_clear_err"].values()) > 1e-12
+    RB.emit(res, a.out, "the device result differs from the restatement: see mismatches / max_clear_err" if differs else None)
 
 
 if __name__ == "__main__":

@@ -1,0 +1,88 @@
+"""What tools/bench_conflicts.py, bench_static.py, bench_reason_ticks.py and bench_episodes.py share: the recorded ScenarioLoop they
+evaluate, the timing of a whole call, of a restatement and of an entry point's launch alone, and the JSON line they end with."""
+import argparse
+import importlib
+import json
+import os
+import statistics
+import sys
+import time
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for _p in (os.path.join(REPO, "tests"), REPO):           # the restatements (tests/*_numpy.py) and the package
+    if _p not in sys.path:
+        sys.path.insert(0, _p)
+
+T = 13
+
+
+def arguments(runs, warmup, **more):
+    """--runs, --warmup, --ticks 300, --out and the tool's own options (name=default; an int default makes an int option)."""
+    ap = argparse.ArgumentParser()
+    for name, default in dict(runs=runs, warmup=warmup, ticks=300, **more).items():
+        ap.add_argument("--" + name.replace("_", "-"), type=type(default), default=default)
+    ap.add_argument("--out")
+    return ap.parse_args()
+
+
+def setup(tool):
+    """(torch, the package).  A time taken without a device says nothing."""
+    import torch
+    if not torch.cuda.is_available():
+        raise SystemExit(f"{tool} needs a HIP device: a time taken without one says nothing")
+    return torch, importlib.import_module("av-simulation-at-intersections_amd")
+
+
+def recorded_loop(pkg, torch, B, K, specs=None, **loop_kw):
+    """The recorder of a ScenarioLoop at T = 13 with B egos that ran and recorded K ticks; specs: its scripted vehicles (default:
+    config 3's four), or a function of the egos' start states that returns them."""
+    W = pkg.workloads
+    routes = W.route_table(False)[0]
+    eng, x0 = W.make_engine(routes, W.ego_batch(routes, B, T, rank=2), T, "cuda:0")
+    if callable(specs):
+        specs = specs(x0)
+    loop_kw.setdefault("max_age", W.MAX_AGE)
+    loop = pkg.ScenarioLoop(eng, x0, W.OBSTACLE_SPECS if specs is None else specs, hist_cap=K, record=K, **loop_kw)
+    loop.run(K)
+    torch.cuda.synchronize()
+    return loop.recorder
+
+
+def stats(ts):
+    return {"median": statistics.median(ts), "min": min(ts), "max": max(ts)}
+
+
+def timed(fn, runs, warmup=0):
+    """(wall ms of `runs` calls of fn after `warmup` untimed ones, the last call's result)."""
+    ts, out = [], None
+    for run in range(warmup + runs):
+        t0 = time.perf_counter()
+        out = fn()
+        if run >= warmup:
+            ts.append((time.perf_counter() - t0) * 1e3)
+    return ts, out
+
+
+def launch_alone(pkg, torch, eng, name, call, runs, warmup):
+    """Wall ms of entry point `name` + synchronise on buffers allocated once: the call without its read-back.  call() makes the
+    call and returns its return code."""
+    def one():
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        rc = call()
+        torch.cuda.synchronize()
+        ms = (time.perf_counter() - t0) * 1e3
+        pkg._cabi.check(rc, eng._ctx, name)
+        return ms
+    return [one() for _ in range(warmup + runs)][warmup:]
+
+
+def emit(res, out, error=None):
+    """The result as one JSON line, to --out as well; error: what ends the run behind it (a difference from the restatement)."""
+    line = json.dumps(res)
+    print(line)
+    if out:
+        with open(out, "w") as f:
+            f.write(line + "\n")
+    if error:
+        raise SystemExit(error)
