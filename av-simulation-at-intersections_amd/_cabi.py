@@ -39,7 +39,7 @@ EXPORTS = (
     "jsim_loop_set_traffic", "jsim_loop_set_recorder", "jsim_loop_set_vehicle_shapes",
     "jsim_comm_unique_id", "jsim_comm_init", "jsim_mpc_gather", "jsim_comm_destroy", "jsim_plan_routes",
     "jsim_plan_routes_weighted", "jsim_score_trajectories", "jsim_loop_eval_reasons", "jsim_loop_eval_conflicts",
-    "jsim_loop_eval_static", "jsim_loop_summarise_episodes",
+    "jsim_loop_eval_static", "jsim_loop_summarise_episodes", "jsim_loop_eval_cutoffs",
 )
 
 _lib = None
@@ -152,6 +152,9 @@ def load() -> C.CDLL:
     lib.jsim_loop_summarise_episodes.restype = C.c_int
     #                                           ctx B    ticks rec flags x_first x_spawn  veh_ (5) st_ (4) rs_ (2)  ep_cap ep_off ep_i ep_d stream
     lib.jsim_loop_summarise_episodes.argtypes = [vp, i32, i32, vp, vp, vp, vp] + [vp] * 11 + [i32, vp, vp, vp, vp]
+    lib.jsim_loop_eval_cutoffs.restype = C.c_int
+    #                                     ctx B    ticks rec flags n_obs obs_rec x_first x_spawn window margin n_steps speed interacting chunk first carry outs      stream
+    lib.jsim_loop_eval_cutoffs.argtypes = [vp, i32, i32, vp, vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp] + [vp] * 6 + [vp]
     if lib.jsim_abi_version() != ABI_VERSION:
         raise JsimError(f"libjsim_mpc.so ABI {lib.jsim_abi_version()} != binding ABI {ABI_VERSION}")
     _lib = lib

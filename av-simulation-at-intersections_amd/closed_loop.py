@@ -39,6 +39,7 @@ class Recorder:
         self.traffic = eng.traffic_layout  # (set_of, obs_off) of the loop's traffic sets, or None: whose vehicle is whose
         self.groups = None if groups is None else np.array(groups, dtype=np.int32)   # InteractingLoop's group offsets: whose mate is who
         self.superseded = False          # set when a later loop on the same engine registers its own recorder (or none)
+        self.glue = None                 # a _GlueLoop's frame_window, margin, n_steps, mode and interacting (cutoffs()); None: no glue
         _register_recorder(eng, self)
 
     def _record_obstacles(self, get: torch.Tensor):
@@ -280,6 +281,64 @@ class Recorder:
                    _ptr(clear), _ptr(who), _ptr(hit), _ptr(off_tick))
         return {"clear": clear, "who": who, "hit": hit, "off_tick": off_tick, "margin": margin, "include_hidden": bool(include_hidden),
                 "ego_shape": tuple(float(v) for v in ego), "set_of": sof}
+
+    def cutoffs(self, chunk_ticks: int = 0, carry=None) -> dict:
+        """The glue's decision on every recorded tick (jsim_loop_eval_cutoffs): what the loop ahead of MPC.step
+        found and did -- main/scenarios/mpc_intersection.py:104-143: the progress index, check_collision_moving_cars /
+        check_collision_moving_bicycle on the predicted traffic, get_cutoff_curve_by_position_idx(...) - EXTRA_CUTOFF_MARGIN -- and
+        what visualize_frame shows of it (collision_xy, the length of tmp_trajectory), computed again after the run from the records
+        by the loops' own device function: every value is the live loop's, bit for bit.
+
+        chunk_ticks: ticks per launch (0: from a 512 MiB budget of predictions).  carry: [B][3] int32 = the progress index, the
+        previous path length (-1: none) and the cut-off the first recorded tick starts from (default: the loops' own start).
+        Returns numpy arrays over the recorded ticks [n][B]: status (the glue's pre_status: 0, or the tick kept idx and cut as they
+        were), idx (the progress index after the tick's update), cut (what the loop wrote to path_len, under mode="speed_cutoff" to
+        the speed cut-off), hit (bool), first (the hit's index on the remaining path, -1: none), col_xy [n][B][2] (NaN: none); and
+        carry [B][3] as the next tick would meet it.  history.cutoff_episodes splits the result into episodes.
+        ValueError: a recorder of a ClosedLoop (it has no glue), a superseded recorder (the context's tables are no longer its
+        loop's), a bad chunk_ticks or carry."""
+        d = self._cutoffs_device(chunk_ticks, carry)
+        out = {k: d[k].cpu().numpy() for k in ("status", "idx", "cut", "first", "col_xy", "carry")}
+        out["hit"] = d["hit"].cpu().numpy() != 0
+        return out
+
+    def _cutoffs_device(self, chunk_ticks: int = 0, carry=None, n=None, first_tick: int = 0) -> dict:
+        """cutoffs() up to the launches: the outputs as device tensors (status, idx, cut, hit, first, col_xy, carry).  n: the recorded
+        ticks, where the caller has asked for them already, or fewer; first_tick: evaluate the ticks [first_tick, n) only, from the
+        carry the ticks before left (the outputs are those ticks' rows)."""
+        eng = self.loop.eng
+        B, dev = eng.B, eng.device
+        if self.glue is None:
+            raise ValueError("this recorder's loop has no glue (ClosedLoop): there is no cut-off to evaluate")
+        if self.superseded:
+            raise ValueError("a later loop on this engine replaced this recorder: the context's tables are no longer its loop's")
+        c = int(chunk_ticks)
+        if c != chunk_ticks or c < 0:
+            raise ValueError(f"chunk_ticks must be an integer >= 0, got {chunk_ticks!r}")
+        if carry is None:
+            d_car = None
+        else:
+            car = np.asarray(carry)
+            if car.shape != (B, 3) or car.dtype.kind not in "iu":
+                raise ValueError(f"carry must be [B = {B}, 3] integers, got {car.dtype} {car.shape}")
+            d_car = torch.from_numpy(np.ascontiguousarray(car, dtype=np.int32)).to(dev)
+        n = self._n(4) if n is None else n
+        k0 = int(first_tick)
+        if not 0 <= k0 <= n:
+            raise ValueError(f"first_tick must be in [0, {n}], got {first_tick!r}")
+        g = self.glue
+        if d_car is None:      # the loops' own start: what a NULL carry of the entry point stands for, as a tensor to hand back
+            full = eng.full_len
+            d_car = torch.stack([torch.zeros_like(full), torch.full_like(full, -1), full], dim=1).contiguous()
+        rows = max(n, 1)       # (no ticks yet: still valid pointers)
+        status, idx, cut, hit, first = (torch.empty(rows, B, dtype=torch.int32, device=dev) for _ in range(5))
+        col_xy = torch.empty(rows, B, 2, dtype=torch.float64, device=dev)
+        rec, flags, x_first, x_spawn = self._buffers()
+        self._call("jsim_loop_eval_cutoffs", B, n, rec, flags, self.n_obs, _ptr(self.obs) if self.obs is not None else None,
+                   x_first, x_spawn, g["frame_window"], g["margin"], g["n_steps"], int(g["mode"] == "speed_cutoff"),
+                   int(g["interacting"]), c, k0, _ptr(d_car), _ptr(status), _ptr(idx), _ptr(cut), _ptr(hit), _ptr(first), _ptr(col_xy))
+        status, idx, cut, hit, first, col_xy = (t[k0:n] for t in (status, idx, cut, hit, first, col_xy))
+        return {"status": status, "idx": idx, "cut": cut, "hit": hit, "first": first, "col_xy": col_xy, "carry": d_car}
 
     def summary(self, conflicts=None, static=None, reasons=None) -> dict:
         """One row per recorded episode of every ego (jsim_loop_summarise_episodes): did the ego arrive, how
@@ -697,6 +756,8 @@ class _GlueLoop:
             _register_shapes(engine, shapes)
         if record:
             self.loop.recorder = Recorder(self.loop, record, n_obs=self.obst.n, groups=group_off)   # last: it records obst.n vehicles
+            self.loop.recorder.glue = {"frame_window": self.pre.frame_window, "margin": self.pre.margin, "n_steps": self.pre.n_steps,
+                                       "mode": self.pre.mode, "interacting": group_off is not None}
 
     def _register_groups(self):
         """Only InteractingLoop has groups."""

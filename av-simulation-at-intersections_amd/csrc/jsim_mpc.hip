@@ -1384,6 +1384,12 @@ struct jsim_ctx {
     int rec_B = 0, rec_cap = 0, rec_n_obs = 0;
     DevArray<double2> d_ego_cc;    // [B][n_steps][2]
     DevArray<double4> d_ego_bc;    // [B]
+    // jsim_loop_eval_cutoffs: the egos' path ids as the glue last took them (caller-owned device array [B], NULL: no glue call yet),
+    // the interacting egos' tick-start states and last steering of a chunk, and the carry of a call without one
+    const int32_t *glue_path_id = nullptr;
+    int glue_B = 0;
+    DevArray<double> d_cut_x0, d_cut_di;   // [chunk][B][4], [chunk][B][2]
+    DevArray<int> d_cut_carry;             // [B][3]
     DevArray<double> d_pcv;        // speed reference per path point (mpc_with_speed variant) or NULL
     const int *cv_cut = nullptr;   // caller-owned device array [B] or NULL
     size_t lds_bytes = 0;
@@ -2620,6 +2626,7 @@ extern "C" int jsim_loop_pre_tick(jsim_ctx *ctx, int32_t B, const double *x0, co
     if (!ctx->d_pxy || !ctx->d_pcc) return fail(ctx, -22, "jsim_loop_pre_tick: paths / geometry not set");
     if (dbg_res_idx && !dbg_n_res) return fail(ctx, -22, "jsim_loop_pre_tick: dbg_res_idx needs dbg_n_res");
     if (int rc = check_shapes(ctx, "jsim_loop_pre_tick", ctx->pred_n_obs)) return rc;
+    ctx->glue_path_id = path_id; ctx->glue_B = B;
     PreP P = fill_prep(ctx, B, ctx->pred_n_obs, ctx->pred_n_steps, frame_window, margin);
     P.x0 = x0; P.path_id = path_id; P.traj_idx = (long long *)traj_idx; P.prev_path_len = prev_path_len; P.path_len = path_len;
     P.col_flag = col_flag; P.col_xy = col_xy; P.first_idx = first_idx; P.status = status;
@@ -2887,6 +2894,7 @@ extern "C" int jsim_loop_run_scenario(jsim_ctx *ctx, int32_t B, int32_t n_ticks,
     if (int rc = check_shapes(ctx, F, n_obs)) return rc;
     if (int rc = check_glue(ctx, F, G)) return rc;
     if (speed_cutoff && !ctx->cv_cut) return fail(ctx, -22, "%s: the speed-cut-off glue needs jsim_mpc_set_speed_cutoff first", F);
+    ctx->glue_path_id = path_id; ctx->glue_B = B;
     hipStream_t s = (hipStream_t)stream;
     if (!fused_ticks(ctx, &G)) return run_host_ticks(ctx, B, n_ticks, S, A, &G, Glue::scripted, s);
     // obstacles: a chunk's ticks of get() tuples, then every tick's prediction, then the chunk's fused launch; the obstacle
@@ -3025,24 +3033,10 @@ extern "C" int jsim_loop_predict_egos(jsim_ctx *ctx, int32_t B, const double *x0
     return 0;
 }
 
-// n_ticks Jacobi ticks of interacting egos (main/scenarios/interactive_mpc.py:117-190), each as separate launches
-// (run_host_ticks).  Arguments as jsim_loop_run_scenario; groups from jsim_loop_set_groups.
-extern "C" int jsim_loop_run_interacting(jsim_ctx *ctx, int32_t B, int32_t n_ticks, double *x0, const int32_t *path_id,
-                                         int32_t *path_len, const double *speed, int64_t *target_ind, double *oa, double *od,
-                                         double *ox, double *oy, double *ov, double *oyaw, double *xref, uint32_t *active_mask,
-                                         int32_t *status, int32_t *n_iter, double *di_ai, const double *x0_spawn,
-                                         const int64_t *target_spawn, int32_t *age, int32_t max_age, double *hist, int32_t *tick,
-                                         int32_t hist_cap, uint64_t *n_respawn, int64_t *traj_idx, int32_t *prev_path_len,
-                                         int32_t *col_flag, int32_t *pre_status, int32_t frame_window, int32_t margin,
-                                         int32_t n_obs, double *obs_state, const double *obs_param, double *obs_get,
-                                         int32_t n_steps, int32_t speed_cutoff, void *stream)
+// What a glue over interacting egos needs of the context: registered groups for this B, scripted vehicles of the egos' shape or
+// with a shape table, and room in the glue's obstacle table for every ego's vehicles and group mates
+static int check_groups(jsim_ctx *ctx, const char *F, int B, int n_obs, int n_steps)
 {
-    const char *const F = "jsim_loop_run_interacting";
-    if (!ctx) return fail(nullptr, -22, "%s: null ctx", F);
-    DeviceGuard dev_guard(ctx->device);
-    JSIM_GUARD_OK(ctx);
-    if (B < 0 || n_ticks < 0 || frame_window < 0 || frame_window > 32 || margin < 0) return fail(ctx, -22, "%s: bad argument", F);
-    if (speed_cutoff) return fail(ctx, -22, "%s: only the truncate glue is supported (speed_cutoff = 1)", F);
     if (ctx->have_ogeom && ctx->n_shapes == 0) // (a shape table gives the scripted vehicles their own thresholds beside the mates')
         return fail(ctx, -22, "%s: egos cannot be mixed with obstacles of another shape (jsim_loop_set_obstacle_geometry has been called)", F);
     if (ctx->n_groups == 0 || ctx->group_B != B) return fail(ctx, -22, "%s: no groups set for B=%d (jsim_loop_set_groups)", F, B);
@@ -3064,6 +3058,28 @@ extern "C" int jsim_loop_run_interacting(jsim_ctx *ctx, int32_t B, int32_t n_tic
                             JSIM_MAX_OBS);
         }
     }
+    return 0;
+}
+
+// n_ticks Jacobi ticks of interacting egos (main/scenarios/interactive_mpc.py:117-190), each as separate launches
+// (run_host_ticks).  Arguments as jsim_loop_run_scenario; groups from jsim_loop_set_groups.
+extern "C" int jsim_loop_run_interacting(jsim_ctx *ctx, int32_t B, int32_t n_ticks, double *x0, const int32_t *path_id,
+                                         int32_t *path_len, const double *speed, int64_t *target_ind, double *oa, double *od,
+                                         double *ox, double *oy, double *ov, double *oyaw, double *xref, uint32_t *active_mask,
+                                         int32_t *status, int32_t *n_iter, double *di_ai, const double *x0_spawn,
+                                         const int64_t *target_spawn, int32_t *age, int32_t max_age, double *hist, int32_t *tick,
+                                         int32_t hist_cap, uint64_t *n_respawn, int64_t *traj_idx, int32_t *prev_path_len,
+                                         int32_t *col_flag, int32_t *pre_status, int32_t frame_window, int32_t margin,
+                                         int32_t n_obs, double *obs_state, const double *obs_param, double *obs_get,
+                                         int32_t n_steps, int32_t speed_cutoff, void *stream)
+{
+    const char *const F = "jsim_loop_run_interacting";
+    if (!ctx) return fail(nullptr, -22, "%s: null ctx", F);
+    DeviceGuard dev_guard(ctx->device);
+    JSIM_GUARD_OK(ctx);
+    if (B < 0 || n_ticks < 0 || frame_window < 0 || frame_window > 32 || margin < 0) return fail(ctx, -22, "%s: bad argument", F);
+    if (speed_cutoff) return fail(ctx, -22, "%s: only the truncate glue is supported (speed_cutoff = 1)", F);
+    if (int rc = check_groups(ctx, F, B, n_obs, n_steps)) return rc;
     if (int rc = check_shapes(ctx, F, n_obs)) return rc;
     if (B == 0 || n_ticks == 0) return 0;
     const StepBufs S = {x0, path_id, path_len, speed, target_ind, oa, od, ox, oy, ov, oyaw, xref, active_mask, status, n_iter};
@@ -3074,7 +3090,97 @@ extern "C" int jsim_loop_run_interacting(jsim_ctx *ctx, int32_t B, int32_t n_tic
     if (int rc = check_advance(ctx, F, A)) return rc;
     if (int rc = check_recorder(ctx, F, B, tick, n_obs)) return rc;
     if (int rc = check_glue(ctx, F, G)) return rc;
+    ctx->glue_path_id = path_id; ctx->glue_B = B;
     if (int rc = ensure_ego_pred(ctx, B, n_steps)) return rc;
     return run_host_ticks(ctx, B, n_ticks, S, A, &G, Glue::interacting, (hipStream_t)stream);
+}
+
+#include "cutoff_ticks.inc"
+
+// The collision cut-off of every recorded tick: DEVICE pointers, the recorder's buffers as they are; per
+// chunk of ticks the vehicles' predictions, for interacting egos the mates' states and predictions, and one launch of one wavefront
+// per ego that walks the chunk's ticks in order; all on `stream`.
+extern "C" int jsim_loop_eval_cutoffs(jsim_ctx *ctx, int32_t B, int32_t n_ticks, const double *rec, const int32_t *flags, int32_t n_obs,
+                                      const double *obs_rec, const double *x_first, const double *x_spawn, int32_t frame_window,
+                                      int32_t margin, int32_t n_steps, int32_t speed_cutoff, int32_t interacting, int32_t chunk_ticks,
+                                      int32_t first_tick, int32_t *carry, int32_t *status, int32_t *idx, int32_t *cut, int32_t *hit, int32_t *first,
+                                      double *col_xy, void *stream)
+{
+    const char *const F = "jsim_loop_eval_cutoffs";
+    if (B < 0 || n_ticks < 0 || n_obs < 0) return fail(ctx, -22, "%s: B=%d n_ticks=%d n_obs=%d", F, B, n_ticks, n_obs);
+    if (margin < 0 || chunk_ticks < 0) return fail(ctx, -22, "%s: margin=%d chunk_ticks=%d", F, margin, chunk_ticks);
+    if (first_tick < 0 || first_tick > n_ticks) return fail(ctx, -22, "%s: first_tick=%d outside [0, n_ticks=%d]", F, first_tick, n_ticks);
+    if (!obs_rec && n_obs > 0) return fail(ctx, -22, "%s: null obs_rec with n_obs=%d", F, n_obs);
+    if (n_steps < 1 || n_steps > JSIM_MAX_PRED) return fail(ctx, -22, "%s: n_steps=%d outside [1, %d]", F, n_steps, JSIM_MAX_PRED);
+    if (frame_window < 0 || frame_window > 32) return fail(ctx, -22, "%s: frame_window=%d outside [0, 32]", F, frame_window);
+    if ((speed_cutoff != 0 && speed_cutoff != 1) || (interacting != 0 && interacting != 1))
+        return fail(ctx, -22, "%s: speed_cutoff=%d interacting=%d (each 0 or 1)", F, speed_cutoff, interacting);
+    if (speed_cutoff && interacting) return fail(ctx, -22, "%s: interacting egos have the truncate glue only (speed_cutoff=1)", F);
+    if (!rec || !flags || !x_first || !x_spawn || !status || !idx || !cut || !hit || !first || !col_xy)
+        return fail(ctx, -22, "%s: null device pointer", F);
+    if (!ctx) return fail(nullptr, -22, "%s: null ctx", F);
+    // the context's tables must be those of the loop that made the recording
+    if (!ctx->d_pxy || !ctx->d_pcc || !ctx->have_geom) return fail(ctx, -22, "%s: paths / geometry not set", F);
+    const bool traffic = ctx->n_sets > 0;
+    if (traffic) {
+        if (int rc = check_traffic(ctx, F, B, n_obs)) return rc;
+    } else if (n_obs > JSIM_MAX_OBS) {
+        return fail(ctx, -22, "%s: n_obs=%d (max %d without traffic sets)", F, n_obs, JSIM_MAX_OBS);
+    }
+    if (interacting)
+        if (int rc = check_groups(ctx, F, B, n_obs, n_steps)) return rc;
+    if (speed_cutoff && !ctx->cv_cut) return fail(ctx, -22, "%s: speed_cutoff=1 without a registered speed cut-off (jsim_mpc_set_speed_cutoff)", F);
+    if (int rc = check_shapes(ctx, F, n_obs)) return rc;
+    if (B == 0 || first_tick == n_ticks) return 0;
+    if (!ctx->glue_path_id || ctx->glue_B != B) // (ticks, but no run of B egos: not this context's)
+        return fail(ctx, -22, "%s: no glue call has bound the path ids of B=%d egos yet", F, B);
+    DeviceGuard dev_guard(ctx->device);
+    JSIM_GUARD_OK(ctx);
+    hipStream_t s = (hipStream_t)stream;
+    // ticks per chunk: the vehicles' predictions (as the fused run's chunks count them) and, interacting, every ego's own
+    const unsigned long long per_tick = (unsigned long long)std::max(n_obs, 1) * ((unsigned long long)n_steps * 32 + 32) +
+                                        (interacting ? (unsigned long long)B * ((unsigned long long)n_steps * 32 + 32 + 48) : 0ull);
+    unsigned long long chunk = chunk_ticks > 0 ? (unsigned long long)chunk_ticks : std::max(1ull, JSIM_TRAFFIC_BUDGET / per_tick);
+    chunk = std::min({chunk, (unsigned long long)(n_ticks - first_tick), 65535ull, std::max(1ull, (1ull << 30) / (unsigned long long)B)}); // (grid.y; rows as int)
+    const int C = (int)chunk;
+    const size_t obs_ticks = (size_t)C * std::max(n_obs, 1);
+    HIP_TRY(ctx, ctx->d_pred_all.reserve(obs_ticks * n_steps * 2));
+    HIP_TRY(ctx, ctx->d_bc_all.reserve(obs_ticks));
+    if (interacting) {
+        if (int rc = ensure_ego_pred(ctx, C * B, n_steps)) return rc;
+        HIP_TRY(ctx, ctx->d_cut_x0.reserve((size_t)C * B * 4));
+        HIP_TRY(ctx, ctx->d_cut_di.reserve((size_t)C * B * 2));
+    }
+    if (!carry) {
+        HIP_TRY(ctx, ctx->d_cut_carry.reserve((size_t)B * JSIM_CUT_CARRY));
+        hipLaunchKernelGGL(cutoff_carry_init_kernel, dim3((B + 255) / 256), dim3(256), 0, s, B, ctx->glue_path_id, ctx->d_poff.p,
+                           ctx->d_cut_carry.p);
+        carry = ctx->d_cut_carry;
+    }
+    CutoffP P;
+    memset(&P, 0, sizeof(P));
+    P.R = recorder_buf(B, n_ticks, rec, flags, x_first, x_spawn);
+    P.pre = fill_prep(ctx, B, n_obs, n_steps, frame_window, margin);
+    P.pre.path_id = ctx->glue_path_id;
+    P.X = traffic_p(ctx);
+    const double mate_thr = 2.0 * ctx->col_radius;
+    if (interacting)
+        P.G = GroupP{ctx->d_group_of, ctx->d_group_off, ctx->d_ego_cc, ctx->d_ego_bc, n_obs, mate_thr, jsim_sqrt_threshold(mate_thr)};
+    P.speed_cutoff = speed_cutoff; P.interacting = interacting;
+    P.pred_cc = ctx->d_pred_all; P.pred_bc = ctx->d_bc_all;
+    P.carry = carry; P.status = status; P.idx = idx; P.cut = cut; P.hit = hit; P.first = first; P.col_xy = col_xy;
+    for (int k0 = first_tick; k0 < n_ticks; k0 += C) {
+        const int nk = std::min(C, n_ticks - k0);
+        if (n_obs > 0)
+            launch_obstacle_predict(ctx, n_obs, n_steps, obs_rec + (size_t)k0 * n_obs * 6, nullptr, ctx->d_pred_all, ctx->d_bc_all, nk, s);
+        if (interacting) {
+            hipLaunchKernelGGL(cutoff_mate_state_kernel, dim3((unsigned)(((size_t)nk * B + 255) / 256)), dim3(256), 0, s, P.R, k0, nk,
+                               ctx->d_cut_x0.p, ctx->d_cut_di.p);
+            launch_ego_predict(ctx, nk * B, ctx->d_cut_x0, ctx->d_cut_di, n_steps, nullptr, s);
+        }
+        P.k0 = k0; P.C = nk;
+        if (int rc = launch_per_ego(ctx, cutoff_ticks_kernel, B, stream, P)) return rc;
+    }
+    return 0;
 }
 #endif /* !JSIM_KERNEL_TU */

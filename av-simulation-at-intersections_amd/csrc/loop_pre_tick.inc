@@ -493,14 +493,12 @@ struct GroupP {
 // scripted ones are its traffic set's (X), or all G.n_scripted without a layout; their thresholds are the shape table's
 // (P.othr) or P.thr, the mates' the ego / ego one.
 #ifndef JSIM_KERNEL_TU /* (a kernel translation unit of the split build holds the register kernels only) */
-__global__ __launch_bounds__(64) void group_pre_tick_kernel(PreP P, GroupP G, TrafficP X)
+// The gather, for group_pre_tick_kernel and the replay of recorded ticks (cutoff_ticks.inc): the ego's obstacles -> W.occ / W.othr
+// and their bounding circles -> bc [JSIM_MAX_OBS] (LDS); returns how many they are.  Ends behind the wavefront's fence.
+__device__ __forceinline__ int group_gather_obstacles(const PreP &P, const GroupP &G, const TrafficP &X, int ego, int lane,
+                                                      PreScratch &W, double4 *bc)
 {
-    __shared__ PreScratch W;
-    __shared__ double4 bc[JSIM_MAX_OBS];
     constexpr bool BLOCK = false;
-    const int lane = threadIdx.x;
-    const int ego = blockIdx.x;
-    if (ego >= P.B) return;
     const int g = G.group_of[ego];
     const int g0 = G.group_off[g], n_mates = G.group_off[g + 1] - g0 - 1;
     const ObsSlice sl = traffic_slice(X, ego, G.n_scripted);
@@ -522,8 +520,18 @@ __global__ __launch_bounds__(64) void group_pre_tick_kernel(PreP P, GroupP G, Tr
         W.othr[lane] = double2{G.mate_thr, G.mate_thr_sq};
     }
     JSIM_PRE_SYNC();
+    return ns + n_mates;
+}
+
+__global__ __launch_bounds__(64) void group_pre_tick_kernel(PreP P, GroupP G, TrafficP X)
+{
+    __shared__ PreScratch W;
+    __shared__ double4 bc[JSIM_MAX_OBS];
+    const int lane = threadIdx.x;
+    const int ego = blockIdx.x;
+    if (ego >= P.B) return;
     PreP Q = P;
-    Q.n_obs = ns + n_mates;
+    Q.n_obs = group_gather_obstacles(P, G, X, ego, lane, W, bc);
     const int pid = P.path_id[ego];
     const long long off = P.poff[pid];
     const int M = (int)(P.poff[pid + 1] - off);

@@ -4,7 +4,8 @@ the device recorder wrote (jsim_loop_set_recorder): rec [n][B][7] = x, y, yaw, v
 [n][B] (FAILED / GOAL / AGE bits), obs [n][n_obs][6] = the scripted vehicles' get() tuples.  Pure numpy: the host-side half of
 the recorder, testable without a device.  reason_series does the same for the per-tick stakeholder reasons,
 conflict_episodes for the clearance and first contact of every episode (section 17), static_episodes for the static obstacles
-(section 18), episode_rows for the per-episode table that is reduced on the device (section 19)."""
+(section 18), episode_rows for the per-episode table that is reduced on the device (section 19), cutoff_episodes for the glue's
+collision cut-off of every tick (section 21)."""
 from __future__ import annotations
 
 from typing import List, Optional
@@ -172,6 +173,24 @@ def static_episodes(result: dict, flags: np.ndarray):
             ticks_off = int((hit[k0:k1, b] >= 0).sum())
         ep["min_clear"], ep["min_clear_tick"], ep["closest_obstacle"] = _min_clear(clear, who, b, k0, k1)
         ep["ticks_off"] = ticks_off
+        return ep
+    return _per_episode(flags, make)
+
+
+def cutoff_episodes(result: dict, flags: np.ndarray):
+    """The collision cut-off of a recorder (Recorder.cutoffs: `status`, `idx`, `cut`, `hit`, `first`, `col_xy`) per ego and episode,
+    split where ego_histories splits (episode_bounds).  Returns a list over egos of lists over episodes of dicts: the six series of
+    the episode's ticks as numpy arrays under their names, first_cut_tick (the first tick of the run whose path was cut off, -1:
+    none), n_cut (how many of the episode's ticks were cut off) and longest_cut (the longest run of consecutive cut-off ticks within
+    the episode: a run that reaches the episode's last tick ends there, whatever the next episode starts with)."""
+    series = {k: np.asarray(result[k]) for k in ("status", "idx", "cut", "hit", "first", "col_xy")}
+
+    def make(b, k0, k1):
+        ep = {k: v[k0:k1, b] for k, v in series.items()}
+        h = ep["hit"] != 0
+        edges = np.flatnonzero(np.diff(np.concatenate([[0], h.astype(np.int8), [0]])))   # starts and ends of the runs, alternating
+        runs = edges[1::2] - edges[0::2]
+        ep.update(first_cut_tick=k0 + int(edges[0]) if runs.size else -1, n_cut=int(h.sum()), longest_cut=int(runs.max(initial=0)))
         return ep
     return _per_episode(flags, make)
 

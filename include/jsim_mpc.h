@@ -530,6 +530,50 @@ int jsim_loop_summarise_episodes(jsim_ctx *ctx, int32_t B, int32_t n_ticks, cons
                                  const double *rs_val, const int32_t *rs_trig, int32_t ep_cap, int64_t *ep_off, int32_t *ep_i,
                                  double *ep_d, void *stream);
 
+/* ---- the collision cut-off of every recorded tick: what the glue ahead of MPC.step decided, rebuilt from the recorder ----
+ * Each tick the reference's loops (main/scenarios/mpc_intersection.py:104-143, interactive_mpc.py and
+ * overtaking_cyclist_bidirectional_road.py:111-169) find the progress index, resample the remaining path, predict the traffic, run
+ * check_collision_moving_cars / check_collision_moving_bicycle and cut the path off before the predicted collision
+ * (get_cutoff_curve_by_position_idx(...) - EXTRA_CUTOFF_MARGIN); visualize_frame shows the results (collision_xy, tmp_trajectory).
+ * The fused loops compute them every tick and keep the last tick's only.  This call computes them again for every recorded tick,
+ * after the run and without touching the loops' kernels: per tick it calls the loops' own device function on the ego's tick-start
+ * state (x_first, x_spawn behind a record with JSIM_REC_GOAL / JSIM_REC_AGE, else rec[k - 1]: x, y, v, yaw), the vehicles' recorded
+ * get() tuples of the tick (predicted again) and, for interacting egos, its group mates' tick-start states and the steering of
+ * their records before (0 on tick 0 and behind a respawn; predicted again), so every value equals the live loop's bit for bit.
+ * One wavefront per ego walks the ticks in order, in chunks of chunk_ticks ticks (0: as many as a 512 MiB budget of predictions
+ * holds, the budget of the fused run's traffic chunks).  DESIGN.md section 21 is the contract.
+ *   DEVICE pointers: rec [n_ticks][B][7], flags [n_ticks][B], obs_rec [n_ticks][n_obs][6], x_first [B][4], x_spawn [B][4] exactly as
+ *   jsim_loop_eval_conflicts takes them; carry; and every output.
+ *   frame_window, margin, n_steps, speed_cutoff (0 / 1): the glue arguments of the run that was recorded (jsim_loop_run_scenario);
+ *   interacting 1: the run was jsim_loop_run_interacting's (the ego's obstacles are its vehicles, then its group mates).
+ *   Everything else is read from the context as the loops read it, so the context must still hold the recorded loop's tables: the
+ *   paths and their circle centres, the path ids of the egos as the last glue call took them (jsim_loop_run_scenario,
+ *   jsim_loop_run_interacting, jsim_loop_pre_tick; the caller's device array, which must still be alive), the geometry, the
+ *   limits of its configuration, the traffic layout, the vehicle shapes and the groups.
+ *   Out, per ego and tick [n_ticks][B] (int32): status = the glue's pre_status of the tick; idx = the progress index after the
+ *   tick's update; cut = what the loop wrote to path_len, or with speed_cutoff = 1 to the speed cut-off buffer; hit = 0 / 1; first
+ *   = the index of the hit on the remaining path (jsim_loop_pre_tick's first_idx), -1 without a hit; col_xy [n_ticks][B][2] = the
+ *   collision point, NaN without a hit.  A tick whose status is not 0 leaves idx and cut as they were and has hit = 0.
+ *   first_tick: the ticks [first_tick, n_ticks) are evaluated and their rows of the outputs written (the buffers are those of the
+ *   whole recording in any case: tick first_tick - 1's record gives the states and the steering tick first_tick starts from).
+ *   carry [B][3] (int32), in and out: the progress index, the length of the previous tick's path (-1: none) and the current
+ *   cut-off as tick first_tick meets them and as tick n_ticks would, so that a run can be evaluated in pieces.  NULL: the loops'
+ *   own start -- 0, -1 and the full path length.  These three integers are all the state the glue carries from tick to tick, so,
+ *   unlike the frame offsets of jsim_loop_eval_conflicts, a cut between any two ticks is exact.
+ *   Refused (-22) before any device call, jsim_last_error naming the argument: B, n_ticks, n_obs, margin or chunk_ticks < 0; a
+ *   first_tick outside [0, n_ticks]; obs_rec NULL with n_obs > 0; n_steps outside [1, 64]; frame_window outside [0, 32];
+ *   speed_cutoff or interacting other than 0 / 1, or both 1; a null pointer other than obs_rec (n_obs = 0), carry and stream; a
+ *   null ctx; a context without paths or geometry, or, with ticks to evaluate, without a glue call; an n_obs that is not the
+ *   registered traffic total (a B that is not the layout's), or above 8 without a layout; interacting = 1 without registered
+ *   groups for B, or with more vehicles and mates than 8; speed_cutoff = 1 without a registered speed cut-off
+ *   (jsim_mpc_set_speed_cutoff); an n_obs that is not the shape table's.  first_tick = n_ticks (so n_ticks = 0) or B = 0 returns
+ *   0 and writes nothing (carry unchanged). */
+int jsim_loop_eval_cutoffs(jsim_ctx *ctx, int32_t B, int32_t n_ticks, const double *rec, const int32_t *flags, int32_t n_obs,
+                           const double *obs_rec, const double *x_first, const double *x_spawn, int32_t frame_window, int32_t margin,
+                           int32_t n_steps, int32_t speed_cutoff, int32_t interacting, int32_t chunk_ticks, int32_t first_tick,
+                           int32_t *carry, int32_t *status, int32_t *idx, int32_t *cut, int32_t *hit, int32_t *first, double *col_xy,
+                           void *stream);
+
 /* ---- the job's one exchange: the final trajectory gather over RCCL / xGMI ----
  * The reference has no multi-process code at all (its only multi-ego code is the serial Python loop of
  * main/scenarios/interactive_mpc.py:119-172); egos are independent (main/lib/mpc.py:141-211), so ranks own contiguous shards
