@@ -119,13 +119,15 @@ class Recorder:
         replan tracker (0 / 1) the first recorded tick starts from (default: zeros).
         Returns numpy arrays: policymaker, driver, cyclist, distance [n][B]; timers [n][B][2]; replan [n][B] bool; below [n][B][3]
         bool (policymaker, driver, cyclist under the threshold); first_replan [B] (-1: none); carry [B][3] as the next tick would
-        meet it; and the par, threshold and veh_of used.  An ego without a cyclist has NaN in driver, cyclist and distance and
+        meet it; ends [n][B] bool (the records that ended an episode: history.reasons_carry_at gives the carry any tick meets);
+        and the par, threshold and veh_of used.  An ego without a cyclist has NaN in driver, cyclist and distance and
         never triggers on them.  ValueError: no vehicles recorded, a bad par / threshold / carry, a cyclist index out of range."""
         d = self._reasons_device(par, threshold, cyclist, carry)
         val, trig = d["val"].cpu().numpy(), d["trig"].cpu().numpy()
         return {"policymaker": val[:, :, 0], "driver": val[:, :, 1], "cyclist": val[:, :, 2], "distance": val[:, :, 3],
                 "timers": d["timers"].cpu().numpy(), "replan": (trig & 1) != 0, "below": ((trig[:, :, None] >> np.arange(1, 4)) & 1) != 0,
-                "first_replan": d["first"].cpu().numpy(), "carry": d["carry"].cpu().numpy(), "par": np.array(d["par"]),
+                "first_replan": d["first"].cpu().numpy(), "carry": d["carry"].cpu().numpy(),
+                "ends": (self.flags[: val.shape[0]].cpu().numpy() & (history.GOAL | history.AGE)) != 0, "par": np.array(d["par"]),
                 "threshold": np.array(d["threshold"]), "veh_of": np.array(d["veh_of"], dtype=np.int32)}
 
     def _reasons_device(self, par=None, threshold=0.7, cyclist=None, carry=None, n=None) -> dict:
@@ -339,6 +341,27 @@ class Recorder:
                    int(g["interacting"]), c, k0, _ptr(d_car), _ptr(status), _ptr(idx), _ptr(cut), _ptr(hit), _ptr(first), _ptr(col_xy))
         status, idx, cut, hit, first, col_xy = (t[k0:n] for t in (status, idx, cut, hit, first, col_xy))
         return {"status": status, "idx": idx, "cut": cut, "hit": hit, "first": first, "col_xy": col_xy, "carry": d_car}
+
+    def fork_state(self, ego, at):
+        """Where a loop forked off this recording starts (jsim_loop_fork_state): for every row r the state
+        (x, y, v, yaw) of ego ego[r] at the start of recorded tick at[r] -- at = the number of recorded ticks: after the last one --
+        by the rule the cut-off replay reads its states by, and the first tick of the episode that tick belongs to.
+
+        ego, at: one integer each or [R]; one ego may stand in several rows.  Returns x0 (a device tensor [R, 4]), k0 and
+        age = at - k0 (int32 numpy arrays [R]).  ValueError: rows that are not integers of one length, an ego outside the batch, a
+        tick outside 0 .. recorded ticks, a superseded recorder (its records stopped when the later loop was built)."""
+        eng = self.loop.eng
+        if self.superseded:
+            raise ValueError("a later loop on this engine replaced this recorder: its records stopped at that point")
+        n = self._n()
+        ego, at = history.fork_rows(eng.B, n, ego, at)
+        R = ego.size
+        x0 = torch.empty(max(R, 1), 4, dtype=torch.float64, device=eng.device)[:R]
+        k0 = torch.empty(max(R, 1), dtype=torch.int32, device=eng.device)[:R]
+        self._call("jsim_loop_fork_state", eng.B, n, *self._buffers(), R, ego.ctypes.data_as(C.c_void_p), at.ctypes.data_as(C.c_void_p),
+                   _ptr(x0), _ptr(k0))
+        k0 = k0.cpu().numpy()
+        return x0, k0, at - k0
 
     def summary(self, conflicts=None, static=None, reasons=None) -> dict:
         """One row per recorded episode of every ego (jsim_loop_summarise_episodes): did the ego arrive, how
@@ -748,6 +771,7 @@ class _GlueLoop:
         self.loop = ClosedLoop(engine, x0, hist_cap=hist_cap, max_age=max_age)
         self.pre = PreTick(engine, frame_window=frame_window, mode=mode)
         self.obst = ScriptedObstacles(engine, obstacle_specs)
+        self.specs = obstacle_specs                  # the flat list (fork() hands each row its ego's vehicles)
         self.traffic = layout
         self._register_groups()
         _register_traffic(engine, *(layout if layout else (None, None)), chunk_ticks)
@@ -818,6 +842,89 @@ class ScenarioLoop(_GlueLoop):
         if rec is not None and rec.n_obs:
             rec._record_obstacles(g)
 
+    def fork(self, ego, at, paths=None, path_id=None, speed=None, record: int = 0, max_age: Optional[int] = None,
+             chunk_ticks: int = 0, cv=None) -> "ScenarioLoop":
+        """A new ScenarioLoop on a new engine whose row r starts where ego ego[r] of this loop's recording stood at the start of
+        recorded tick at[r], on a path of its own and with a cold controller: what perform_replan of
+        main/scenarios/overtaking_cyclist_bidirectional_road.py (:394-402) does when it builds a fresh MPC on the chosen trajectory
+        and lets the same simulation and the same cyclist go on.  Rows, not egos: one ego forked at its trigger tick onto each of
+        its candidates drives them all in one batch.
+
+        paths / path_id: the new engine's route table and every row's route (paths=None: this engine's paths, path_id defaulting
+        to the ego's own); speed: per row (default: the ego's own); cv: the speed references of new paths under
+        mode="speed_cutoff" (paths=None: this engine's).  T, config, dt, dl, L, the egos' rows of a per-ego table
+        (set_ego_configs), frame_window, mode and hist_cap are this loop's; max_age too unless given.  x0 and x0_spawn are the fork
+        states (Recorder.fork_state), loop.age = at - k0, the glue starts as for a new run and the controller cold: no warm start,
+        path index 0 -- but a row that starts its ego's episode (age 0) on the ego's own route is that ego's respawn and has the
+        path index this loop respawns it with, so that it replays the episode.  Row r meets the vehicles of its ego's
+        traffic set (the whole list of a loop without sets; dims carried over) where they stood at tick at[r]
+        (jsim_loop_obstacles_at); obst.reset() returns there.  Rows of one source set and one tick share a set.
+        This loop, its engine and its recorder are left as they are.
+        ValueError: no recorder; what fork_state, BatchedMPC and traffic_layout raise; new paths without path_id."""
+        src, eng, rec = self.loop, self.loop.eng, self.recorder
+        if rec is None:
+            raise ValueError("fork needs the loop's recording (record=...)")
+        x0, k0, age = rec.fork_state(ego, at)
+        ego, at = history.fork_rows(eng.B, rec._n(), ego, at)
+        R = ego.size
+        if R < 1:
+            raise ValueError("fork needs at least one row")
+        idx = torch.from_numpy(ego.astype(np.int64)).to(eng.device)
+        own_paths = paths is None
+        if own_paths:
+            paths, cv, smooth = [p.copy() for p in eng.paths], eng.cv, False        # (unwrapped already)
+            if path_id is None:
+                path_id = eng.path_id[idx].cpu().numpy()
+        else:
+            smooth = True
+            if path_id is None:
+                raise ValueError("new paths need a path_id per row")
+        pid = np.asarray(path_id)
+        pid = np.broadcast_to(pid, (R,)) if pid.ndim == 0 else pid
+        if pid.shape != (R,):
+            raise ValueError(f"path_id must hold one route per row ({R}), got {pid.shape}")
+        spd = eng.speed[idx].cpu().numpy() if speed is None else np.asarray(speed, dtype=np.float64)
+        if spd.shape not in ((), (R,)):
+            raise ValueError(f"speed must be one number or one per row ({R}), got {spd.shape}")
+        new = BatchedMPC(paths, pid, dl=eng.dl, L=eng.L, speed=spd, dt=eng.dt, T=eng.T, config=eng.config, device=eng.device,
+                         smooth=smooth, cv=cv)
+        pe = getattr(eng, "_pe", None)
+        if pe is not None:
+            new.set_ego_configs(pe[idx])
+        # traffic: one set per (source set, tick) among the rows, the rows' own order of first appearance
+        n_src = self.obst.n
+        if self.traffic is None:
+            src_set, src_off = np.zeros(eng.B, dtype=np.int64), np.array([0, n_src])
+        else:
+            src_set, src_off = self.traffic
+        keys, tof = {}, np.empty(R, dtype=np.int32)
+        for r in range(R):
+            tof[r] = keys.setdefault((int(src_set[ego[r]]), int(at[r])), len(keys))
+        veh = [np.arange(src_off[s], src_off[s + 1]) for s, _ in keys]                # each new set's vehicles among the source's
+        sets = [[self.specs[o] for o in v] for v in veh]
+        shared = self.traffic is None and len(keys) == 1
+        fork = ScenarioLoop(new, x0, sets[0] if shared else sets, hist_cap=src.hist_cap,
+                            max_age=src.max_age if max_age is None else max_age, frame_window=self.pre.frame_window, mode=self.pre.mode,
+                            traffic_of=None if shared else tof, chunk_ticks=chunk_ticks, record=record)
+        fork.loop.age.copy_(torch.from_numpy(np.ascontiguousarray(age, dtype=np.int32)))
+        if own_paths:
+            # a row that starts its ego's episode on the ego's own route is that ego's respawn: the path index it respawns with
+            again = torch.from_numpy((age == 0) & (pid == eng.path_id[idx].cpu().numpy())).to(eng.device)
+            new.target_ind.copy_(torch.where(again, src.target_spawn[idx], new.target_ind))
+            fork.loop.target_spawn.copy_(new.target_ind)
+        if fork.obst.n:
+            pick = torch.from_numpy(np.concatenate(veh).astype(np.int64)).to(eng.device)
+            ticks = np.ascontiguousarray(np.concatenate([np.full(len(v), k, dtype=np.int32) for v, (_, k) in zip(veh, keys)]))
+            state0 = self.obst._state0[pick].contiguous()
+            wheel = None if fork.shapes is None else torch.from_numpy(np.ascontiguousarray(fork.shapes[:, 3])).to(eng.device)
+            state = torch.empty_like(state0)
+            _cabi.check(new.lib.jsim_loop_obstacles_at(new._ctx, fork.obst.n, _ptr(state0), _ptr(fork.obst.param), _ptr(wheel),
+                                                       ticks.ctypes.data_as(C.c_void_p), _ptr(state), new._stream()), new._ctx,
+                        "jsim_loop_obstacles_at")
+            fork.obst.state.copy_(state)
+            fork.obst._state0.copy_(state)
+        return fork
+
 
 MAX_GROUP = MAX_OBS    # the obstacles of an ego are the scripted ones plus its group mates
 
@@ -883,3 +990,8 @@ class InteractingLoop(_GlueLoop):
 
     def tick(self):
         self.run(1)
+
+    def fork(self, *args, **kwargs):
+        """Refused: a forked ego's group mates would have to go on with the controllers they had."""
+        raise ValueError("an InteractingLoop cannot be forked: the group mates' warm starts (oa, od) are not recorded, so their "
+                         "controllers cannot be continued from a recorded tick")

@@ -1390,6 +1390,7 @@ struct jsim_ctx {
     int glue_B = 0;
     DevArray<double> d_cut_x0, d_cut_di;   // [chunk][B][4], [chunk][B][2]
     DevArray<int> d_cut_carry;             // [B][3]
+    DevArray<int> d_fork_rows, d_fork_ticks; // [2][n_rows] (ego, at) of jsim_loop_fork_state's, [n_obs] of jsim_loop_obstacles_at's last call
     DevArray<double> d_pcv;        // speed reference per path point (mpc_with_speed variant) or NULL
     const int *cv_cut = nullptr;   // caller-owned device array [B] or NULL
     size_t lds_bytes = 0;
@@ -3181,6 +3182,49 @@ extern "C" int jsim_loop_eval_cutoffs(jsim_ctx *ctx, int32_t B, int32_t n_ticks,
         P.k0 = k0; P.C = nk;
         if (int rc = launch_per_ego(ctx, cutoff_ticks_kernel, B, stream, P)) return rc;
     }
+    return 0;
+}
+
+#include "fork.inc"
+
+// The start of a loop forked off a recorded run: row r's ego state at the start of tick at[r] of ego ego[r]
+// and the first tick of that tick's episode.  DEVICE pointers: the recorder's buffers and the two outputs; ego and at are HOST
+// arrays, checked here and copied to the context's table; one launch on `stream`, one wavefront per row.
+extern "C" int jsim_loop_fork_state(jsim_ctx *ctx, int32_t B, int32_t n_ticks, const double *rec, const int32_t *flags, const double *x_first,
+                                    const double *x_spawn, int32_t n_rows, const int32_t *ego, const int32_t *at, double *x0, int32_t *k0,
+                                    void *stream)
+{
+    const char *const F = "jsim_loop_fork_state";
+    if (B < 0 || n_ticks < 0 || n_rows < 0) return fail(ctx, -22, "%s: B=%d n_ticks=%d n_rows=%d", F, B, n_ticks, n_rows);
+    if (n_rows > 0 && (!rec || !flags || !x_first || !x_spawn || !ego || !at || !x0 || !k0)) return fail(ctx, -22, "%s: null pointer", F);
+    for (int r = 0; r < n_rows; ++r) {
+        if (ego[r] < 0 || ego[r] >= B) return fail(ctx, -22, "%s: row %d: ego=%d outside [0, B=%d)", F, r, ego[r], B);
+        if (at[r] < 0 || at[r] > n_ticks) return fail(ctx, -22, "%s: row %d: at=%d outside [0, n_ticks=%d]", F, r, at[r], n_ticks);
+    }
+    JSIM_RECORDER_CALL(n_rows == 0);
+    std::vector<int> rows((size_t)2 * n_rows);
+    std::copy(ego, ego + n_rows, rows.begin());
+    std::copy(at, at + n_rows, rows.begin() + n_rows);
+    if (int rc = replace_table(ctx, ctx->d_fork_rows, rows.data(), rows.size())) return rc;
+    const ForkStateP P = {recorder_buf(B, n_ticks, rec, flags, x_first, x_spawn), n_rows, ctx->d_fork_rows.p, ctx->d_fork_rows.p + n_rows, x0, k0};
+    return launch_per_ego(ctx, fork_state_kernel, n_rows, stream, P);
+}
+
+// The scripted vehicles at their own ticks: DEVICE pointers state0, param, wheelbase (NULL: the wheelbase
+// jsim_loop_obstacles steps with) and state; ticks is a HOST array; one launch on `stream`, one thread per vehicle.
+extern "C" int jsim_loop_obstacles_at(jsim_ctx *ctx, int32_t n_obs, const double *state0, const double *param, const double *wheelbase,
+                                      const int32_t *ticks, double *state, void *stream)
+{
+    const char *const F = "jsim_loop_obstacles_at";
+    if (n_obs < 0) return fail(ctx, -22, "%s: n_obs=%d", F, n_obs);
+    if (n_obs > 0 && (!state0 || !param || !ticks || !state)) return fail(ctx, -22, "%s: null pointer", F);
+    for (int o = 0; o < n_obs; ++o)
+        if (ticks[o] < 0) return fail(ctx, -22, "%s: vehicle %d: ticks=%d", F, o, ticks[o]);
+    JSIM_RECORDER_CALL(n_obs == 0);
+    if (int rc = replace_table(ctx, ctx->d_fork_ticks, ticks, (size_t)n_obs)) return rc;
+    const ObsAtP P = {n_obs, ctx->have_ogeom ? ctx->oL : ctx->cfg.L, state0, param, wheelbase, ctx->d_fork_ticks.p, state};
+    hipLaunchKernelGGL(obstacles_at_kernel, dim3((n_obs + 63) / 64), dim3(64), 0, (hipStream_t)stream, P);
+    HIP_TRY(ctx, hipGetLastError());
     return 0;
 }
 #endif /* !JSIM_KERNEL_TU */

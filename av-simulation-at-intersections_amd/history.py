@@ -5,7 +5,7 @@ the device recorder wrote (jsim_loop_set_recorder): rec [n][B][7] = x, y, yaw, v
 the recorder, testable without a device.  reason_series does the same for the per-tick stakeholder reasons,
 conflict_episodes for the clearance and first contact of every episode (section 17), static_episodes for the static obstacles
 (section 18), episode_rows for the per-episode table that is reduced on the device (section 19), cutoff_episodes for the glue's
-collision cut-off of every tick (section 21)."""
+collision cut-off of every tick (section 21); fork_rows, join and reasons_carry_at are the host side of a fork (section 22)."""
 from __future__ import annotations
 
 from typing import List, Optional
@@ -221,6 +221,66 @@ def episode_rows(summary: dict):
                                 "ticks_off": ep["st_ticks_off"] if hit else 0}
             eps.append(ep)
         out.append(eps)
+    return out
+
+
+def fork_rows(B: int, n: int, ego, at):
+    """The rows of a fork (Recorder.fork_state) as two int32 arrays [R]: ego and at, one integer each or
+    sequences of one length (a single one is repeated).  ValueError: not integers, not one-dimensional, lengths that differ, an ego
+    outside [0, B), a tick outside [0, n]."""
+    e, a = np.asarray(ego), np.asarray(at)
+    whole = lambda v: v.dtype.kind in "iu" or v.size == 0                            # noqa: E731  (an empty list has no type)
+    if not whole(e) or not whole(a) or e.ndim > 1 or a.ndim > 1:
+        raise ValueError(f"ego and at must be integers, one each or one-dimensional, got {e.dtype} {e.shape} and {a.dtype} {a.shape}")
+    R = a.size if e.ndim == 0 else e.size if a.ndim == 0 else max(e.size, a.size)
+    if (e.ndim and e.size != R) or (a.ndim and a.size != R):
+        raise ValueError(f"ego holds {e.size} rows, at {a.size}")
+    e, a = np.broadcast_to(e.reshape(-1), (R,)), np.broadcast_to(a.reshape(-1), (R,))
+    if R and (e.min() < 0 or e.max() >= B):
+        r = int(np.argmax((e < 0) | (e >= B)))
+        raise ValueError(f"row {r}: ego {int(e[r])} outside [0, {B})")
+    if R and (a.min() < 0 or a.max() > n):
+        r = int(np.argmax((a < 0) | (a > n)))
+        raise ValueError(f"row {r}: tick {int(a[r])} outside [0, {n}] (the recorded ticks)")
+    return np.ascontiguousarray(e, dtype=np.int32), np.ascontiguousarray(a, dtype=np.int32)
+
+
+def join(head: History, tail: History) -> History:
+    """One History of a run that was forked (ScenarioLoop.fork): `head`, the source episode's History up to and
+    including the entry for the start of the fork tick (its spawn entry and one entry per tick before the fork), then the forked
+    loop's first History `tail` without its spawn entry, which is that same state again.  t goes on by repeated `+ sample_time`, as
+    History.store counts it.  ValueError: an empty head or tail, two sample times."""
+    if len(head) < 1 or len(tail) < 1:
+        raise ValueError("join needs a head and a tail with at least their first entries")
+    if head._sample_time != tail._sample_time:
+        raise ValueError(f"the head's sample time is {head._sample_time}, the tail's {tail._sample_time}")
+    out = History(head._sample_time)
+    for h, first in ((head, 0), (tail, 1)):
+        for i in range(first, len(h)):
+            out.store(h.x[i], h.y[i], h.yaw[i], h.v[i], h.a[i], h.delta[i], h.xref_deviation[i])
+    return out
+
+
+def reasons_carry_at(result: dict, ego, at, ends=None) -> np.ndarray:
+    """The carry [R][3] that tick at[r] of ego ego[r] meets in an evaluation of the per-tick reasons (Recorder.reasons, DESIGN.md
+    section 16): the two timers as the tick before left them and the tracker = whether any value was below the threshold on the
+    tick before; zeros on tick 0 (the evaluation's own default start) and behind a record that ended an episode; at = the number
+    of evaluated ticks: the evaluation's own `carry`.  Handed to the forked loop's `recorder.reasons(carry=...)` it continues the
+    three series across the fork.  result: Recorder.reasons' dict (`timers`, `below`, `carry`, `ends`); ends: [n][B] bool, the
+    records that ended an episode, for a result without that key.  ValueError: bad rows (fork_rows), no `ends`."""
+    timers, below = np.asarray(result["timers"], dtype=np.float64), np.asarray(result["below"])
+    n, B = timers.shape[:2]
+    e, a = fork_rows(B, n, ego, at)
+    ends = result.get("ends") if ends is None else ends
+    if ends is None:
+        raise ValueError("the result holds no `ends` (the records that ended an episode): pass ends=")
+    ends = np.asarray(ends).reshape(n, B) != 0
+    out = np.zeros((e.size, 3))
+    for r, (b, k) in enumerate(zip(e.tolist(), a.tolist())):
+        if k == n:
+            out[r] = np.asarray(result["carry"], dtype=np.float64)[b]
+        elif k > 0 and not ends[k - 1, b]:
+            out[r] = (timers[k - 1, b, 0], timers[k - 1, b, 1], 1.0 if below[k - 1, b].any() else 0.0)
     return out
 
 

@@ -174,6 +174,61 @@ def intersection_query(start_pos: int, turn_indicator: int, margin: float, start
                       tol=float(np.pi / 16), obstacles=[primitive_halfplanes(o, margin) for o in prims])
 
 
+def _arterial_scene(num_lanes: int, goal_lane: int, replan, width_road: float, length: float, x_goal: float, y_goal: float,
+                    width_pavement: float, car_L: float, car_width: float, car_extra_length: float, cyclist_box_width: float):
+    """(start, goal, goal box, obstacle primitives) of the reference's arterial road: what arterial_query and arterial_obstacles
+    share.  A straight road along y of num_lanes lanes centred on x = 0, a pavement on either side; the ego starts in the middle of
+    the lane right of the centre at the road's lower end and the goal is a point, with a box of the car's bounding box around it."""
+    if num_lanes < 1:
+        raise ValueError("the road needs at least one lane")
+    if goal_lane > num_lanes:
+        raise ValueError(f"goal lane {goal_lane} of {num_lanes} lanes")
+    half = num_lanes * width_road / 2
+    start = (width_road * (num_lanes / 2 - 0.5), -length / 2, np.pi / 2)
+    goal = (x_goal, y_goal, np.pi / 2)
+    gw = (car_width, car_L + car_extra_length)
+    gb = (goal[0] - gw[0] / 2, goal[1] - gw[1] / 2, goal[0] + gw[0] / 2, goal[1] + gw[1] / 2)
+    obs = [("box", (width_pavement, length), (-half - width_pavement / 2, 0), False),                    # left pavement
+           ("box", (width_pavement, length), (half + width_pavement / 2, 0), False)]                     # right pavement
+    if replan is None:
+        obs.append(("box", (width_road, length), (-start[0], 0), False))                                 # the closed left road
+    else:
+        # the replan at the trigger: from where the AV stands, the left road open, and one box over the cyclist and everywhere its
+        # prediction takes it -- as long as the prediction's extent in y, laid from the cyclist's position onwards
+        traj = np.asarray(replan["trajectory"], dtype=np.float64)
+        if traj.ndim != 2 or traj.shape[0] < 1 or traj.shape[1] < 2:
+            raise ValueError("replan['trajectory'] is the cyclist's predicted trajectory [n][>= 2] (x, y, ...)")
+        (sx, sy), (ax, ay) = replan["spawn"], replan["av"]
+        reach = traj[-1][1] - traj[0][1]
+        start = (ax, ay, np.pi / 2)
+        obs.append(("box", (cyclist_box_width, reach), (sx, sy + reach / 2), False))
+    return start, goal, gb, obs
+
+
+_ARTERIAL = dict(width_road=4.0, length=44.0, x_goal=2.0, y_goal=22.0, width_pavement=3, car_L=2.86, car_width=2.0,
+                 car_extra_length=0.64, cyclist_box_width=1.64)
+
+
+def arterial_obstacles(num_lanes: int = 2, goal_lane: int = 1, replan=None, **constants) -> list:
+    """The obstacles list of the reference's arterial road (arterial_query's, in list order) as primitives ("box", xy_width,
+    xy_center, hidden): the two pavements and the closed left road, or with replan= the two pavements and the cyclist's box.
+    static_obstacle_rows takes them."""
+    return _arterial_scene(num_lanes, goal_lane, replan, **{**_ARTERIAL, **constants})[3]
+
+
+def arterial_query(margin: float, num_lanes: int = 2, goal_lane: int = 1, replan=None, **constants) -> RouteQuery:
+    """main/envs/arterial_multi_lanes.py's ArterialMultiLanes(num_lanes, goal_lane).create_scenario as a route query: the road of
+    the overtaking study (main/scenarios/overtaking_cyclist_bidirectional_road.py:1978-1979).  replan=dict(trajectory=the cyclist's
+    predicted trajectory [n][>= 2], spawn=(x, y) of the cyclist, av=(x, y) of the ego) is the form perform_replan asks for
+    (:318-326, is_following=False): the start moved to the ego, the left road open, a box 1.64 m wide over the cyclist's prediction.
+    constants: lib/parameters.py's ScenarioParameters and the shapes, by keyword -- width_road (WIDTH_ROAD, 4.0), length (LENGTH,
+    44.0), x_goal (X_LOC_EGO, 2.0), y_goal (Y_LOC_GOAL, 22.0), width_pavement (3), car_L / car_width / car_extra_length (the goal
+    box: BicycleModelDimensions' bounding box), cyclist_box_width (1.64).  ValueError: no lane, a goal lane beyond the lanes."""
+    start, goal, gb, prims = _arterial_scene(num_lanes, goal_lane, replan, **{**_ARTERIAL, **constants})
+    return RouteQuery(start=tuple(float(v) for v in start), goal=tuple(float(v) for v in goal), goal_box=tuple(float(v) for v in gb),
+                      tol=float(np.pi / 16), obstacles=[primitive_halfplanes(o, margin) for o in prims])
+
+
 STATIC_ROW = 32                    # JSIM_STATIC_ROW: doubles per obstacle row of jsim_loop_eval_static (DESIGN.md section 18)
 
 

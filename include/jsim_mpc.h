@@ -574,6 +574,36 @@ int jsim_loop_eval_cutoffs(jsim_ctx *ctx, int32_t B, int32_t n_ticks, const doub
                            int32_t *carry, int32_t *status, int32_t *idx, int32_t *cut, int32_t *hit, int32_t *first, double *col_xy,
                            void *stream);
 
+/* ---- Forking a recorded run: the start of a new loop at any recorded tick ----
+ * What perform_replan of main/scenarios/overtaking_cyclist_bidirectional_road.py (:394-402) has for nothing -- the same simulation and
+ * the same cyclist going on under a new MPC object -- for a run that is over: a new loop (a new context, new paths, a cold controller)
+ * whose rows start where egos of the recorded run stood at ticks of their own, meeting the scripted vehicles where they stood then.
+ *
+ * jsim_loop_fork_state: row r's state x0[r] = (x, y, v, yaw) of ego ego[r] at the start of tick at[r] -- x_first on tick 0, x_spawn
+ * behind a record with JSIM_REC_GOAL / JSIM_REC_AGE, else the record before (the rule of jsim_loop_eval_cutoffs, by the same device
+ * function) -- and k0[r], the first tick of the episode that tick belongs to: 0, or one behind the last record before at[r] with
+ * JSIM_REC_GOAL or JSIM_REC_AGE (so at[r] - k0[r] is the ego's age there).  at[r] = n_ticks is the state after the last record.  One
+ * ego may stand in any number of rows.  A pure function of the recorder's buffers; one wavefront per row.
+ *   DEVICE pointers: rec [n_ticks][B][7], flags [n_ticks][B], x_first [B][4], x_spawn [B][4] as jsim_loop_eval_cutoffs takes them,
+ *   x0 [n_rows][4], k0 [n_rows] (int32).  HOST pointers: ego [n_rows], at [n_rows].
+ *   Refused (-22) before any device call: B, n_ticks or n_rows < 0; with n_rows > 0 a null pointer other than stream, an ego outside
+ *   [0, B), an at outside [0, n_ticks]; a null ctx.  n_rows = 0 returns 0 and writes nothing.
+ *
+ * jsim_loop_obstacles_at: vehicle o's state[o] = (xc, yc, theta, counter) after ticks[o] ticks from state0[o], each tick being the
+ * loops' two calls -- get() alone, then get() + step() (jsim_loop_obstacles with do_step 0, then 1; jsim_loop_run_scenario's
+ * roll-forward) -- by the same device function, so the result is the live loop's obs_state bit for bit, the heading the roundabout
+ * rule rewrites and the start-delay counter included.  Nothing else is written.  One thread per vehicle; n_obs has no limit of 8.
+ *   DEVICE pointers: state0 [n_obs][4], param [n_obs][8] (jsim_loop_obstacles' layouts), wheelbase [n_obs] (NULL: every vehicle has the
+ *   wheelbase jsim_loop_obstacles steps with: jsim_loop_set_obstacle_geometry's, else the configuration's L), state [n_obs][4].
+ *   HOST pointer: ticks [n_obs].
+ *   Refused (-22) before any device call: n_obs < 0; with n_obs > 0 a null pointer other than wheelbase and stream, a ticks[o] < 0;
+ *   a null ctx.  n_obs = 0 returns 0 and writes nothing. */
+int jsim_loop_fork_state(jsim_ctx *ctx, int32_t B, int32_t n_ticks, const double *rec, const int32_t *flags, const double *x_first,
+                         const double *x_spawn, int32_t n_rows, const int32_t *ego, const int32_t *at, double *x0, int32_t *k0,
+                         void *stream);
+int jsim_loop_obstacles_at(jsim_ctx *ctx, int32_t n_obs, const double *state0, const double *param, const double *wheelbase,
+                           const int32_t *ticks, double *state, void *stream);
+
 /* ---- the job's one exchange: the final trajectory gather over RCCL / xGMI ----
  * The reference has no multi-process code at all (its only multi-ego code is the serial Python loop of
  * main/scenarios/interactive_mpc.py:119-172); egos are independent (main/lib/mpc.py:141-211), so ranks own contiguous shards

@@ -1,0 +1,251 @@
+"""Forking a recorded run (jsim_loop_fork_state, jsim_loop_obstacles_at) without a GPU: the numpy restatement
+(tests/fork_numpy.py) of the fork state on hand-made flag series and of the vehicles' fast-forward against the reference's own
+get() / step() sequences (tests/golden/obstacles_scripted.npz); history.join and history.reasons_carry_at; and the two entry points'
+declarations, bindings, documentation and the -22 refusals that need no context."""
+import os
+import re
+
+import numpy as np
+import pytest
+
+import fork_numpy as FN
+import reason_ticks_cases as TC
+import recorder_numpy as RN
+from conftest import REPO, load_golden
+
+GOAL, AGE, FAILED = 2, 4, 1
+STATE_NAMES = ("rec", "flags", "x_first", "x_spawn", "n_rows", "ego", "at", "x0", "k0")
+OBS_NAMES = ("state0", "param", "wheelbase", "ticks", "state")
+
+
+def recording(n, ends, seed=0):
+    """A recording of len(ends) egos over n ticks with distinct numbers everywhere: ends[b] = {tick: flag} of ego b."""
+    rng = np.random.default_rng(seed)
+    B = len(ends)
+    rec = rng.uniform(-50, 50, (n, B, 7))
+    flags = np.zeros((n, B), dtype=np.int32)
+    flags[rng.uniform(size=(n, B)) < 0.1] = FAILED                       # a failed solve ends nothing
+    for b, e in enumerate(ends):
+        for k, f in e.items():
+            flags[k, b] |= f
+    return rec, flags, rng.uniform(-50, 50, (B, 4)), rng.uniform(-50, 50, (B, 4))
+
+
+def test_fork_state_restatement_on_hand_made_flags(pkg):
+    n = 130
+    ends = [{}, {0: GOAL}, {62: AGE}, {63: GOAL}, {64: AGE}, {65: GOAL | AGE}, {n - 1: GOAL}, {10: GOAL, 63: AGE, 64: GOAL, 127: AGE, 128: GOAL},
+            {k: AGE for k in range(n)}]
+    rec, flags, x_first, x_spawn = recording(n, ends)
+    B = len(ends)
+    ego, at = np.repeat(np.arange(B), n + 1), np.tile(np.arange(n + 1), B)          # every ego at every tick 0 .. n
+    x0, k0 = FN.fork_state(rec, flags, x_first, x_spawn, ego, at)
+    x0, k0 = x0.reshape(B, n + 1, 4), k0.reshape(B, n + 1)
+    # the states: two independent statements -- recorder_numpy's poses for the ticks that have one, and the rule spelt out
+    pose = RN.start_poses(rec, flags, x_first, x_spawn)
+    assert np.array_equal(x0[:, :n, [0, 1, 3]], pose.transpose(1, 0, 2))
+    for b, e in enumerate(ends):
+        assert np.array_equal(x0[b, 0], x_first[b])
+        for k in range(1, n + 1):
+            want = x_spawn[b] if (k - 1) in e else rec[k - 1, b, [0, 1, 3, 2]]
+            assert np.array_equal(x0[b, k], want), (b, k)
+        # k0: the first tick of history.episode_bounds' episode that holds the tick (at = n: the running one)
+        bounds = pkg.history.episode_bounds(flags[:, b])
+        for k in range(n + 1):
+            want = next(a for a, z, _ in bounds if a <= k < z) if k < n else bounds[-1][0]
+            assert k0[b, k] == want, (b, k)
+    # spelt out: straight behind an end, across the 64 boundary, at 0 and at n
+    assert k0[0].tolist() == [0] * (n + 1)
+    assert k0[1, 0] == 0 and k0[1, 1] == 1 and k0[1, n] == 1
+    for b, end in ((2, 62), (3, 63), (4, 64), (5, 65)):
+        assert k0[b, end] == 0 and k0[b, end + 1] == end + 1 and k0[b, n] == end + 1 and np.array_equal(x0[b, end + 1], x_spawn[b])
+    assert k0[6, n - 1] == 0 and k0[6, n] == n and np.array_equal(x0[6, n], x_spawn[6])
+    assert [int(k0[7, k]) for k in (10, 11, 63, 64, 65, 127, 128, 129, n)] == [0, 11, 11, 64, 65, 65, 128, 129, 129]
+    assert k0[8].tolist() == list(range(n + 1))
+    # rows are rows: any order, one ego many times
+    pick = np.array([7, 7, 0, 7, 8]), np.array([129, 64, 5, 0, 17])
+    a, b = FN.fork_state(rec, flags, x_first, x_spawn, *pick)
+    assert np.array_equal(a, x0[pick]) and np.array_equal(b, k0[pick])
+
+
+def golden_specs(g):
+    t = [dict(direction=int(d), turning=bool(tn), speed=float(s), offset=None if o < 0 else float(o))
+         for d, tn, s, o in zip(g["direction"], g["turning"], g["speed"], g["offset"])]
+    r = [dict(kind="roundabout", direction=int(d), turning=bool(tn), speed=float(s), offset=None if o < 0 else float(o))
+         for d, tn, s, o in zip(g["r_direction"], g["r_turning"], g["r_speed"], g["r_offset"])]
+    a = [dict(kind="arterial", x_init=float(x), y_init=float(y), speed=float(s), initial_speed=float(v0), offset=None if o < 0 else float(o))
+         for x, y, s, v0, o in zip(g["a_x"], g["a_y"], g["a_speed"], g["a_v0"], g["a_offset"])]
+    return t, r, a
+
+
+def test_vehicle_fast_forward_reproduces_the_reference():
+    """The reference's own get() before every step(), 140 ticks of the three vehicle kinds, on every tick.  The bar is the fixture's
+    own (tests/golden/README.md: states to 1e-10; the device test of the same vectors holds the T-intersection cars to 1e-11)."""
+    g = load_golden("obstacles_scripted.npz")
+    t, r, a = golden_specs(g)
+    K = g["get"].shape[0]
+    state0, param = FN.start_states(t + r + a)
+    n = len(state0)
+    end, gets = FN.obstacles_at(state0, param, None, np.full(n, K), trace=True)
+    gets = np.array(gets).transpose(1, 0, 2)                                        # [K][n][6]
+    want = np.concatenate([g["get"], g["r_get"], g["a_get"]], axis=1)
+    assert K == 140 and gets.shape == want.shape
+    np.testing.assert_allclose(gets[:, :len(t)], want[:, :len(t)], rtol=0, atol=1e-11)
+    np.testing.assert_allclose(gets, want, rtol=0, atol=1e-10)
+    assert (gets[:, :, 5] != 0).any(axis=0).sum() >= 4                              # the turns happened
+    # a vehicle at its own tick is that tick's state of the common run: pose, and the counter = its tick
+    ticks = np.array([0, 1, 139, 64, 7, 140, 33, 100, 65, 63])[:n]
+    own = FN.obstacles_at(state0, param, None, ticks)
+    for o, k in enumerate(ticks):
+        if k < K:
+            np.testing.assert_allclose(own[o, :2], want[k, o, :2], rtol=0, atol=1e-10)
+        assert own[o, 3] == k
+        assert np.array_equal(own[o], FN.obstacles_at(state0[o:o + 1], param[o:o + 1], None, [k])[0])
+    assert np.array_equal(FN.obstacles_at(state0, param, None, np.full(n, K)), end)
+    # a wheelbase of its own turns a turning vehicle differently and leaves a straight one alone
+    short = FN.obstacles_at(state0, param, np.full(n, 1.0), np.full(n, K))
+    turning = (gets[:, :, 5] != 0).any(axis=0)
+    assert not np.array_equal(short[turning], end[turning]) and np.array_equal(short[~turning], end[~turning])
+
+
+def hist(pkg, dt, n, base=0.0):
+    h = pkg.history.History(dt)
+    for i in range(n):
+        h.store(base + i, 10 * base + i, 0.1 * i, 2.0 + i, 0.01 * i, -0.02 * i, 0.5 * i)
+    return h
+
+
+def test_history_join(pkg):
+    H = pkg.history
+    head, tail = hist(pkg, 0.2, 5), hist(pkg, 0.2, 4, base=100.0)
+    j = H.join(head, tail)
+    assert len(j) == 5 + 4 - 1
+    for f in ("x", "y", "yaw", "v", "delta", "a", "xref_deviation"):
+        assert getattr(j, f) == getattr(head, f) + getattr(tail, f)[1:], f          # the fork's spawn entry is dropped
+    t, want = 0.0, []
+    for _ in range(len(j)):
+        t = t + 0.2
+        want.append(t)
+    assert j.t == want and j.t[:5] == head.t                                         # repeated + dt, bit for bit
+    assert len(head) == 5 and len(tail) == 4                                         # the inputs are left alone
+    assert len(H.join(hist(pkg, 0.2, 1), hist(pkg, 0.2, 1))) == 1                     # a fork at the episode's start, no tick yet
+    assert len(H.join(hist(pkg, 0.2, 1), tail)) == 4
+    with pytest.raises(ValueError, match="sample time"):
+        H.join(head, hist(pkg, 0.1, 3))
+    with pytest.raises(ValueError, match="first entries"):
+        H.join(head, H.History(0.2))
+    with pytest.raises(ValueError, match="first entries"):
+        H.join(H.History(0.2), tail)
+
+
+def test_fork_rows(pkg):
+    fr = pkg.history.fork_rows
+    e, a = fr(4, 10, [3, 0, 3], [10, 0, 5])
+    assert e.dtype == a.dtype == np.int32 and e.tolist() == [3, 0, 3] and a.tolist() == [10, 0, 5]
+    assert [x.tolist() for x in fr(4, 10, 2, [1, 2])] == [[2, 2], [1, 2]] and [x.tolist() for x in fr(4, 10, [1, 2], 7)] == [[1, 2], [7, 7]]
+    assert [x.tolist() for x in fr(4, 10, 2, 3)] == [[2], [3]] and [x.size for x in fr(4, 10, [], [])] == [0, 0]
+    for ego, at, msg in (([4], [0], r"ego 4 outside \[0, 4\)"), ([-1], [0], "ego -1"), ([0], [11], r"tick 11 outside \[0, 10\]"),
+                         ([0], [-1], "tick -1"), ([0, 1], [1, 2, 3], "2 rows, at 3"), ([0.5], [1], "integers"), ([[0]], [1], "integers")):
+        with pytest.raises(ValueError, match=msg):
+            fr(4, 10, ego, at)
+
+
+def test_reasons_carry_at_is_the_carry_of_a_cut_run(pkg):
+    """The carry history.reasons_carry_at reads off a whole evaluation equals the carry the restatement hands on when the run is cut
+    at that tick -- on the cases of tests/golden/reason_ticks.npz, ends and nonzero timers included."""
+    cs = TC.cases()
+    A = TC.recorder_arrays(cs)
+    full = TC.restate(A)
+    B = len(cs)
+    result = {"timers": full["timers"], "below": ((full["trig"][:, :, None] >> np.arange(1, 4)) & 1) != 0, "carry": full["carry"],
+              "ends": RN.is_end(A["flags"])}
+    seen_end = seen_timer = seen_tracker = 0
+    for n in TC.TICK_COUNTS:
+        want = TC.restate(A, n=n)["carry"]
+        got = pkg.history.reasons_carry_at(result, np.arange(B), n)
+        assert np.array_equal(got, want), n
+        seen_end += int(RN.is_end(A["flags"][n - 1]).sum())
+        seen_timer += int((want[:, :2] > 0).any(axis=1).sum())
+        seen_tracker += int((want[:, 2] != 0).sum())
+    assert seen_end >= 1 and seen_timer >= 10 and seen_tracker >= 5
+    # rows, tick 0, and a result without `ends`
+    got = pkg.history.reasons_carry_at(result, [3, 3, 5], [64, 0, 200])
+    assert np.array_equal(got[0], TC.restate(A, n=64)["carry"][3]) and not got[1].any() and np.array_equal(got[2], full["carry"][5])
+    bare = {k: v for k, v in result.items() if k != "ends"}
+    with pytest.raises(ValueError, match="ends"):
+        pkg.history.reasons_carry_at(bare, 0, 1)
+    assert np.array_equal(pkg.history.reasons_carry_at(bare, [3], [64], ends=A["flags"] & 6), got[:1])
+    with pytest.raises(ValueError, match="tick 201"):
+        pkg.history.reasons_carry_at(result, 0, 201)
+
+
+def test_entry_points_are_declared_and_bound(pkg):
+    hdr = open(os.path.join(REPO, "include", "jsim_mpc.h")).read()
+    for fn, names in (("jsim_loop_fork_state", ("B", "n_ticks") + STATE_NAMES), ("jsim_loop_obstacles_at", ("n_obs",) + OBS_NAMES)):
+        m = re.search(r"\bint " + fn + r"\s*\(([^;]*)\);", hdr)
+        assert m, fn
+        args = [re.search(r"(\w+)$", a.strip()).group(1) for a in m.group(1).split(",")]
+        assert args == ["ctx", *names, "stream"], fn
+        assert fn in pkg._cabi.EXPORTS
+        assert len(getattr(pkg._cabi.load(), fn).argtypes) == len(args)
+        doc = open(os.path.join(REPO, "INTEGRATION.md")).read()
+        row = re.search(r"^\| `" + fn + r"` \|(.*)$", doc, flags=re.M)
+        assert row and "overtaking_cyclist_bidirectional_road.py:394-402" in row.group(1), fn
+    assert "overtaking_cyclist_bidirectional_road.py (:394-402)" in hdr and "#define JSIM_ABI_VERSION 2 " in hdr
+    CL = pkg.closed_loop
+    assert callable(CL.Recorder.fork_state) and callable(CL.ScenarioLoop.fork) and callable(pkg.history.join)
+    src = open(os.path.join(REPO, "av-simulation-at-intersections_amd", "csrc", "jsim_mpc.hip")).read()
+    tail = src[src.index('#include "fork.inc"'):]                          # inside the block the kernel translation units leave out
+    assert tail.count("#if") == 0 and tail.count("#endif") == 1 and tail.rstrip().endswith("#endif /* !JSIM_KERNEL_TU */")
+    inc = open(os.path.join(REPO, "av-simulation-at-intersections_amd", "csrc", "fork.inc")).read()
+    assert "jct_state_at(R, e, at," in inc and inc.count("obstacle_step_one(Q, o);") == 2 and "__ballot(" in inc
+
+
+def test_argument_errors_without_gpu(pkg):
+    """The header's -22 lists as far as they need no context: from the host, before any device call."""
+    lib = pkg._cabi.load()
+    buf = np.zeros(64)
+    p = buf.ctypes.data                                                    # a non-null address; no refused call reads it
+    rows = lambda *v: np.array(v, dtype=np.int32)                          # noqa: E731
+
+    def state(B=2, n=3, **over):
+        a = {k: p for k in STATE_NAMES}
+        ego, at = over.pop("ego_", rows(0, 1)), over.pop("at_", rows(0, 3))
+        a.update(n_rows=len(ego), ego=ego.ctypes.data, at=at.ctypes.data)
+        a.update(over)
+        rc = lib.jsim_loop_fork_state(None, B, n, *[a[k] for k in STATE_NAMES], None)
+        return rc, lib.jsim_last_error(None).decode()
+
+    who = "jsim_loop_fork_state: "
+    bad = [(dict(B=-1), "B=-1"), (dict(n=-1), "n_ticks=-1"), (dict(n_rows=-1), "n_rows=-1"),
+           (dict(ego_=rows(0, 2)), "row 1: ego=2 outside [0, B=2)"), (dict(ego_=rows(-1, 0)), "row 0: ego=-1 outside [0, B=2)"),
+           (dict(at_=rows(0, 4)), "row 1: at=4 outside [0, n_ticks=3]"), (dict(at_=rows(-1, 0)), "row 0: at=-1 outside [0, n_ticks=3]"),
+           (dict(B=0), "row 0: ego=0 outside [0, B=0)")]
+    for kw, msg in bad:
+        rc, err = state(**kw)
+        assert rc == -22 and err.startswith(who) and msg in err, (kw, rc, err)
+    for k in ("rec", "flags", "x_first", "x_spawn", "ego", "at", "x0", "k0"):
+        rc, err = state(**{k: None})
+        assert rc == -22 and err == who + "null pointer", (k, rc, err)
+    for kw in (dict(), dict(at_=rows(3, 3)), dict(ego_=rows(1, 1, 1), at_=rows(0, 1, 2)), dict(n_rows=0, rec=None, ego=None, x0=None), dict(n=0, at_=rows(0, 0))):
+        rc, err = state(**kw)                                              # nothing wrong but the missing context
+        assert rc == -22 and err == who + "null ctx", (kw, err)
+
+    def obst(n_obs=2, **over):
+        a = {k: p for k in OBS_NAMES}
+        ticks = over.pop("ticks_", rows(0, 5))
+        a.update(ticks=ticks.ctypes.data)
+        a.update(over)
+        rc = lib.jsim_loop_obstacles_at(None, n_obs, *[a[k] for k in OBS_NAMES], None)
+        return rc, lib.jsim_last_error(None).decode()
+
+    who = "jsim_loop_obstacles_at: "
+    for kw, msg in ((dict(n_obs=-1), "n_obs=-1"), (dict(ticks_=rows(3, -1)), "vehicle 1: ticks=-1")):
+        rc, err = obst(**kw)
+        assert rc == -22 and err.startswith(who) and msg in err, (kw, rc, err)
+    for k in ("state0", "param", "ticks", "state"):
+        rc, err = obst(**{k: None})
+        assert rc == -22 and err == who + "null pointer", (k, rc, err)
+    for kw in (dict(), dict(wheelbase=None), dict(n_obs=0, state0=None, state=None)):
+        rc, err = obst(**kw)
+        assert rc == -22 and err == who + "null ctx", (kw, err)
+    assert not buf.any()
