@@ -1100,6 +1100,18 @@ __global__ __launch_bounds__(64) void mpc_step_kernel(const KP Pin)
     STAMP(11);
 }
 
+// Both register kernels (mpc_step_reg.inc, mpc_step_reg4.inc) pass a lane's row of J through this where the add of an active-set
+// iteration rejoins the path to the drop: the drop then reads THIS value, not the one the iteration started with.  The compiler lays
+// the two branches out one behind the other (add ; join ; drop); were the drop to read the start-of-iteration row, that row would
+// stay live across the add's FMAs, their results would need a second register set, and the bottom of the loop a copy per column to
+// bring them back (compiler fact 7).  One empty asm per column: no instruction.
+template <int N>
+__device__ __forceinline__ void jsim_join_row(double (&row)[N])
+{
+#pragma unroll
+    for (int j = 0; j < N; ++j) asm volatile("" : "+v"(row[j]));
+}
+
 #include "mpc_step_reg.inc"
 #include "reg_common.inc"
 #include "mpc_step_reg4.inc"

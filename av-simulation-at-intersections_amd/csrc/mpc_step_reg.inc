@@ -1455,8 +1455,9 @@ void mpc_step_reg_kernel(const KP Pin, const TickP K, const PreK Q)
                 ++q;
                 LDS_SYNC();
                 GSTAMP(6);
-                break;
             }
+            jsim_join_row(Jr); // the drop reads the row as it stands HERE: one register set for J (jsim_mpc.hip; DESIGN.md section 5, fact 7)
+            if (full) break;
             // partial step: drop working-set position l (Givens sweep on R in LDS, same rotations on J's columns)
             {
                 const int pdrop = __builtin_amdgcn_readlane(actid, l);

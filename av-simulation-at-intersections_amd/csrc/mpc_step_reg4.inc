@@ -1108,8 +1108,9 @@ __global__ __launch_bounds__(256, JSIM_REG4_MINW) void mpc_step_reg4_kernel(cons
                 JSIM_PIN_WS(lam0, rdg0, act0); JSIM_PIN_WS(lam1, rdg1, act1); JSIM_PIN(abits);
                 GSTAMP(6);
                 ++q;
-                break; // the barrier of the next entering-row search orders the writes to R
             }
+            jsim_join_row(Jr); // the drop reads the row as it stands HERE: one register set for J (jsim_mpc.hip; DESIGN.md section 5, fact 7)
+            if (full) break; // the barrier of the next entering-row search orders the writes to R
             // partial step: drop working-set position l (Givens sweep on R in LDS by all threads, same rotations on J)
             {
                 int pdrop;
