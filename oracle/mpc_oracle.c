@@ -425,7 +425,18 @@ static double orc_ratio_trunc(double t)
 int orc_solve_qp(int n, int m, const double *H, const double *g, const double *G, const double *h,
                  const uint8_t *skip, double *u, double *lam, int32_t *n_iter_out)
 {
+    return orc_solve_qp_trace(n, m, H, g, G, h, skip, u, lam, n_iter_out, NULL);
+}
+
+/* The same solve; tr (may be NULL) receives the counts of this solve's decisions (mpc_oracle.h: orc_trace).  The counters are
+ * plain increments beside the decisions they count: no value the solve computes depends on them. */
+int orc_solve_qp_trace(int n, int m, const double *H, const double *g, const double *G, const double *h,
+                       const uint8_t *skip, double *u, double *lam, int32_t *n_iter_out, orc_trace *tr)
+{
     int status = ORC_OK;
+    orc_trace tc;
+    memset(&tc, 0, sizeof(tc));
+    tc.end = ORC_END_BEFORE_LOOP; /* until the Cholesky factor stands */
     double *Lm = (double *)malloc(sizeof(double) * n * n);
     double *J = (double *)malloc(sizeof(double) * n * n);
     double *Rm = (double *)calloc((size_t)n * n, sizeof(double));
@@ -510,9 +521,10 @@ int orc_solve_qp(int n, int m, const double *H, const double *g, const double *G
         }
         if (p < 0) break; /* optimal */
         double lplus = 0.0;
+        if (q > tc.max_q) tc.max_q = q; /* the working set at the start of an iteration */
 
         for (;;) { /* step 2 */
-            if (++iters > max_iters) { status = ORC_INFEASIBLE; goto finish; }
+            if (++iters > max_iters) { status = ORC_INFEASIBLE; tc.end = ORC_END_MAX_ITERS; goto finish; }
             /* d = J' n+,  n+ = -G_p' */
             double dd = 0.0, zn = 0.0;
             for (int j = 0; j < n; ++j) {
@@ -549,7 +561,8 @@ int orc_solve_qp(int n, int m, const double *H, const double *g, const double *G
             double t2 = dependent ? INFINITY : viol / zn;
             if (t2 < 0.0) t2 = 0.0;
 
-            if (isinf(t1) && isinf(t2)) { status = ORC_INFEASIBLE; goto finish; }
+            if (dependent) ++tc.dependent;
+            if (isinf(t1) && isinf(t2)) { status = ORC_INFEASIBLE; tc.end = ORC_END_INFEASIBLE_IN_LOOP; goto finish; }
 
             int full = (t2 <= t1);
             double t = full ? t2 : t1;
@@ -582,10 +595,15 @@ int orc_solve_qp(int n, int m, const double *H, const double *g, const double *G
                 lact[q] = lplus;
                 inact[p] = 1;
                 ++q;
+                ++tc.adds;
+                if (q > tc.max_q) tc.max_q = q;
                 break; /* back to step 1 */
             }
             /* partial step: drop working-set position l */
             {
+                ++tc.drops;
+                if (l == 0) ++tc.drops_first;
+                if (l == q - 1) ++tc.drops_last;
                 inact[act[l]] = 0;
                 for (int j = l; j + 1 < q; ++j) {
                     /* column j+1 moves to column j; rotate rows (j, j+1) to zero the subdiagonal */
@@ -617,7 +635,9 @@ int orc_solve_qp(int n, int m, const double *H, const double *g, const double *G
 finish:
     for (int k = 0; k < q; ++k) lam[act[k]] = lact[k];
     *n_iter_out = iters;
+    if (status == ORC_OK) tc.end = ORC_END_OPTIMAL;
 done:
+    if (tr) *tr = tc;
     free(Lm); free(J); free(Rm); free(d); free(z); free(r); free(w); free(lact); free(act); free(inact); free(wgt);
     return status;
 }
@@ -671,6 +691,9 @@ int orc_mpc_step_cv(const orc_params *p, double sx, double sy, double syaw, doub
     int status = ORC_OK;
     int32_t iters_total = 0;
     int64_t tind = target_ind;
+    orc_trace trace; /* summed over the passes; max_q their largest; end the last pass's */
+    memset(&trace, 0, sizeof(trace));
+    trace.end = ORC_END_BEFORE_LOOP;
 
     if (oa_in && od_in) { /* mpc.py:225-227 */
         memcpy(oa, oa_in, sizeof(double) * T);
@@ -685,8 +708,13 @@ int orc_mpc_step_cv(const orc_params *p, double sx, double sy, double syaw, doub
         status = orc_build_qp(p, xref, xbar, x0, rend, speed, H, g, G, h, skip, fresp, Sens);
         if (status != ORC_OK) break;
         int32_t iters = 0;
-        status = orc_solve_qp(n, m, H, g, G, h, skip, u, lam, &iters);
+        orc_trace tp;
+        status = orc_solve_qp_trace(n, m, H, g, G, h, skip, u, lam, &iters, &tp);
         iters_total += iters;
+        trace.adds += tp.adds; trace.drops += tp.drops; trace.drops_first += tp.drops_first;
+        trace.drops_last += tp.drops_last; trace.dependent += tp.dependent;
+        if (tp.max_q > trace.max_q) trace.max_q = tp.max_q;
+        trace.end = tp.end;
         if (status != ORC_OK) break;
         for (int t = 0; t < T; ++t) {
             oa[t] = u[2 * t];
@@ -709,6 +737,8 @@ int orc_mpc_step_cv(const orc_params *p, double sx, double sy, double syaw, doub
         }
         have_ov = 1;
     }
+    if (status != ORC_OK && trace.end == ORC_END_OPTIMAL) trace.end = ORC_END_BEFORE_LOOP; /* a later pass left before its solve */
+    if (out->trace) *out->trace = trace;
     out->status = status;
     out->n_iter = iters_total;
     out->target_ind = tind;
@@ -751,6 +781,19 @@ int orc_mpc_step_batch_cv(const orc_params *p, int32_t B, const double *x0, cons
                           double *oy, double *ov, double *oyaw, double *xref, uint32_t *active_mask,
                           int32_t *status, int32_t *n_iter, int32_t n_threads)
 {
+    return orc_mpc_step_batch_trace(p, B, x0, path_id, path_len, speed, cx, cy, cyaw, cv, cv_cut, path_off, target_ind, oa, od,
+                                    ox, oy, ov, oyaw, xref, active_mask, status, n_iter, NULL, n_threads);
+}
+
+/* orc_mpc_step_batch_cv with the trace of every ego's solve written to trace[b] (NULL: not wanted): each ego's record is
+ * written by the thread that solves that ego, nothing is shared. */
+int orc_mpc_step_batch_trace(const orc_params *p, int32_t B, const double *x0, const int32_t *path_id,
+                             const int32_t *path_len, const double *speed, const double *cx,
+                             const double *cy, const double *cyaw, const double *cv, const int32_t *cv_cut,
+                             const int64_t *path_off, int64_t *target_ind, double *oa, double *od, double *ox,
+                             double *oy, double *ov, double *oyaw, double *xref, uint32_t *active_mask,
+                             int32_t *status, int32_t *n_iter, orc_trace *trace, int32_t n_threads)
+{
     const int T = p->T, W = T + 1, MW = (8 * T + 31) / 32;
     (void)n_threads;
 #ifdef _OPENMP
@@ -769,6 +812,7 @@ int orc_mpc_step_batch_cv(const orc_params *p, int32_t B, const double *x0, cons
         o.oyaw = o.ov + W;
         o.xref = o.oyaw + W;
         o.active_mask = active_mask ? &active_mask[(size_t)b * MW] : NULL;
+        o.trace = trace ? &trace[b] : NULL;
         int st = orc_mpc_step_cv(p, x0[4 * b + 0], x0[4 * b + 1], x0[4 * b + 3], x0[4 * b + 2], cx + off,
                                  cy + off, cyaw + off, cv ? cv + off : NULL, cv_cut ? (int64_t)cv_cut[b] : -1,
                                  (int64_t)path_len[b], target_ind[b], speed[b],

@@ -141,6 +141,27 @@ int orc_build_qp(const orc_params *p, const double *xref, const double *xbar, co
 int orc_solve_qp(int n, int m, const double *H, const double *g, const double *G, const double *h,
                  const uint8_t *skip, double *u, double *lam, int32_t *n_iter);
 
+/* What one solve did, for tests that must know which paths of the iteration their inputs take (tests/active_set_cases.py): plain
+ * counts, one record per solve, filled by the thread that runs the solve. */
+enum {
+    ORC_END_OPTIMAL = 0,            /* no violated row left */
+    ORC_END_INFEASIBLE_IN_LOOP = 1, /* no step length: neither a primal step (dependent row) nor a row to drop */
+    ORC_END_MAX_ITERS = 2,          /* the iteration cap */
+    ORC_END_BEFORE_LOOP = 3         /* never reached the iteration: constant row violated, nearest-index anomaly, H not positive */
+};
+typedef struct orc_trace {
+    int32_t adds;        /* rows added to the working set (full steps) */
+    int32_t drops;       /* rows dropped (partial steps) */
+    int32_t drops_first; /* .. from working-set position 0 */
+    int32_t drops_last;  /* .. from the last position, q - 1 (no Givens sweep) */
+    int32_t dependent;   /* entering rows in the span of the working set (pure dual step) */
+    int32_t max_q;       /* largest working set, at the start of an iteration or after an add */
+    int32_t end;         /* ORC_END_* */
+    int32_t reserved_;
+} orc_trace;
+int orc_solve_qp_trace(int n, int m, const double *H, const double *g, const double *G, const double *h,
+                       const uint8_t *skip, double *u, double *lam, int32_t *n_iter, orc_trace *trace /* may be NULL */);
+
 /* active-set bitmask from multipliers: bit i set <=> lam[i] > 1e-9 * max(1, ||g||_inf) */
 void orc_active_mask(int m, int n, const double *lam, const double *g, uint32_t *mask /*ceil(m/32)*/);
 
@@ -163,6 +184,7 @@ typedef struct orc_step_out {
     int64_t target_ind;
     int32_t n_iter;
     int32_t status;
+    orc_trace *trace; /* (may be NULL) with MAX_ITER > 1: counts summed over the passes, max_q their largest, end the last pass's */
 } orc_step_out;
 
 /* One MPC.step for one ego.  state = (x, y, yaw, v) as in lib/simulation.py State;  oa_in/od_in: warm
@@ -194,6 +216,13 @@ int orc_mpc_step_batch_cv(const orc_params *p, int32_t B, const double *x0, cons
                           const int64_t *path_off, int64_t *target_ind, double *oa, double *od, double *ox,
                           double *oy, double *ov, double *oyaw, double *xref, uint32_t *active_mask,
                           int32_t *status, int32_t *n_iter, int32_t n_threads);
+
+int orc_mpc_step_batch_trace(const orc_params *p, int32_t B, const double *x0, const int32_t *path_id,
+                             const int32_t *path_len, const double *speed, const double *cx,
+                             const double *cy, const double *cyaw, const double *cv, const int32_t *cv_cut,
+                             const int64_t *path_off, int64_t *target_ind, double *oa, double *od, double *ox,
+                             double *oy, double *ov, double *oyaw, double *xref, uint32_t *active_mask,
+                             int32_t *status, int32_t *n_iter, orc_trace *trace /* [B] or NULL */, int32_t n_threads);
 
 double orc_xref_deviation(const double *cx, const double *cy, const double *cyaw, int64_t target_ind,
                           double ox0, double oy0);

@@ -50,8 +50,14 @@ class OrcStepOut(C.Structure):
         ("ov", C.c_void_p), ("oyaw", C.c_void_p), ("xref", C.c_void_p), ("xbar", C.c_void_p),
         ("idx", C.c_void_p), ("reaches_end", C.c_void_p), ("lam", C.c_void_p),
         ("active_mask", C.c_void_p), ("H", C.c_void_p), ("g", C.c_void_p),
-        ("target_ind", C.c_int64), ("n_iter", C.c_int32), ("status", C.c_int32),
+        ("target_ind", C.c_int64), ("n_iter", C.c_int32), ("status", C.c_int32), ("trace", C.c_void_p),
     ]
+
+
+# orc_trace (mpc_oracle.h): what one solve did.  A traced call returns int32 [.., 8] rows with these columns (the last is padding).
+TRACE_FIELDS = ("adds", "drops", "drops_first", "drops_last", "dependent", "max_q", "end", "reserved_")
+TRACE = {name: i for i, name in enumerate(TRACE_FIELDS)}
+END_OPTIMAL, END_INFEASIBLE_IN_LOOP, END_MAX_ITERS, END_BEFORE_LOOP = 0, 1, 2, 3
 
 
 def make_params(T: int = 13, dt: float = 0.2, dl: float = 0.083, L: float = 2.86,
@@ -138,6 +144,10 @@ def lib() -> C.CDLL:
         L.orc_mpc_step_batch.restype = C.c_int
         L.orc_mpc_step_batch_cv.argtypes = [C.POINTER(OrcParams), C.c_int32] + [C.c_void_p] * 21 + [C.c_int32]
         L.orc_mpc_step_batch_cv.restype = C.c_int
+        L.orc_mpc_step_batch_trace.argtypes = [C.POINTER(OrcParams), C.c_int32] + [C.c_void_p] * 22 + [C.c_int32]
+        L.orc_mpc_step_batch_trace.restype = C.c_int
+        L.orc_solve_qp_trace.argtypes = [C.c_int, C.c_int, dp, dp, dp, dp, bp, dp, dp, C.POINTER(C.c_int32), C.c_void_p]
+        L.orc_solve_qp_trace.restype = C.c_int
         L.orc_mpc_step_cv.argtypes = [C.POINTER(OrcParams)] + [C.c_double] * 4 + [dp, dp, dp, C.c_void_p, C.c_int64,
                                       C.c_int64, C.c_int64, C.c_double, C.c_void_p, C.c_void_p, C.POINTER(OrcStepOut)]
         L.orc_mpc_step_cv.restype = C.c_int
@@ -209,11 +219,16 @@ def build_qp(p, xref, xbar, x0, reaches_end, speed):
     return int(st), H, g, G, h, skip, fresp, Sens
 
 
-def solve_qp(H, g, G, h, skip=None):
+def solve_qp(H, g, G, h, skip=None, trace=False):
+    """trace: a fifth result, the solve's orc_trace as an int32 row (columns TRACE_FIELDS)."""
     n = g.shape[0]; m = h.shape[0]
     if skip is None:
         skip = np.zeros(m, dtype=np.uint8)
     u = np.zeros(n); lam = np.zeros(m); it = C.c_int32(0)
+    if trace:
+        tr = np.zeros(len(TRACE_FIELDS), dtype=np.int32)
+        st = lib().orc_solve_qp_trace(n, m, _c(H), _c(g), _c(G), _c(h), _c(skip, np.uint8), u, lam, C.byref(it), tr.ctypes.data)
+        return int(st), u, lam, int(it.value), tr
     st = lib().orc_solve_qp(n, m, _c(H), _c(g), _c(G), _c(h), _c(skip, np.uint8), u, lam, C.byref(it))
     return int(st), u, lam, int(it.value)
 
@@ -222,9 +237,10 @@ def active_indices_from_mask(mask_row, m):
     return [i for i in range(m) if (int(mask_row[i >> 5]) >> (i & 31)) & 1]
 
 
-def mpc_step(p, state_xyyawv, cx, cy, cyaw, target_ind, speed, oa=None, od=None, want_qp=False, cv=None, cv_cut=-1):
+def mpc_step(p, state_xyyawv, cx, cy, cyaw, target_ind, speed, oa=None, od=None, want_qp=False, cv=None, cv_cut=-1, trace=False):
     """One reference MPC.step for one ego.  state = (x, y, yaw, v) like lib.simulation.State.
-    cv / cv_cut: the mpc_with_speed variant's per-point speed reference, zeroed from index cv_cut on."""
+    cv / cv_cut: the mpc_with_speed variant's per-point speed reference, zeroed from index cv_cut on.
+    trace: res["trace"] = the step's orc_trace as an int32 row (columns TRACE_FIELDS)."""
     T = p.T; n = nvar(p); m = 8 * T
     res = {
         "oa": np.zeros(T), "od": np.zeros(T), "ox": np.zeros(T + 1), "oy": np.zeros(T + 1),
@@ -235,6 +251,8 @@ def mpc_step(p, state_xyyawv, cx, cy, cyaw, target_ind, speed, oa=None, od=None,
     }
     if want_qp:
         res["H"] = np.zeros((n, n)); res["g"] = np.zeros(n)
+    if trace:
+        res["trace"] = np.zeros(len(TRACE_FIELDS), dtype=np.int32)
     out = OrcStepOut()
     for k, v in res.items():
         setattr(out, k, v.ctypes.data)
@@ -256,9 +274,9 @@ def mpc_step(p, state_xyyawv, cx, cy, cyaw, target_ind, speed, oa=None, od=None,
 
 
 def mpc_step_batch(p, x0, path_id, path_len, speed, cx, cy, cyaw, path_off, target_ind, oa, od,
-                   n_threads=1, cv=None, cv_cut=None):
+                   n_threads=1, cv=None, cv_cut=None, trace=False):
     """Batched oracle step with the product's [B][..] layouts.  Returns a dict of fresh arrays;
-    oa/od/target_ind inputs are not modified."""
+    oa/od/target_ind inputs are not modified.  trace: out["trace"] = every ego's orc_trace, int32 [B, 8] (columns TRACE_FIELDS)."""
     B = x0.shape[0]; T = p.T; MW = (8 * T + 31) // 32
     x0 = _c(x0); path_id = _c(path_id, np.int32); path_len = _c(path_len, np.int32)
     speed = _c(speed); cx, cy, cyaw = _c(cx), _c(cy), _c(cyaw); path_off = _c(path_off, np.int64)
@@ -272,16 +290,18 @@ def mpc_step_batch(p, x0, path_id, path_len, speed, cx, cy, cyaw, path_off, targ
     ptr = lambda a: None if a is None else a.ctypes.data
     cv = _c(cv) if cv is not None else None
     cv_cut = _c(cv_cut, np.int32) if cv_cut is not None else None
-    lib().orc_mpc_step_batch_cv(C.byref(p), B, ptr(x0), ptr(path_id), ptr(path_len), ptr(speed), ptr(cx),
-                             ptr(cy), ptr(cyaw), ptr(cv), ptr(cv_cut), ptr(path_off), ptr(out["target_ind"]), ptr(out["oa"]),
-                             ptr(out["od"]), ptr(out["ox"]), ptr(out["oy"]), ptr(out["ov"]),
-                             ptr(out["oyaw"]), ptr(out["xref"]), ptr(out["active_mask"]),
-                             ptr(out["status"]), ptr(out["n_iter"]), int(n_threads))
+    if trace:
+        out["trace"] = np.zeros((B, len(TRACE_FIELDS)), dtype=np.int32)
+    lib().orc_mpc_step_batch_trace(C.byref(p), B, ptr(x0), ptr(path_id), ptr(path_len), ptr(speed), ptr(cx),
+                                   ptr(cy), ptr(cyaw), ptr(cv), ptr(cv_cut), ptr(path_off), ptr(out["target_ind"]), ptr(out["oa"]),
+                                   ptr(out["od"]), ptr(out["ox"]), ptr(out["oy"]), ptr(out["ov"]),
+                                   ptr(out["oyaw"]), ptr(out["xref"]), ptr(out["active_mask"]),
+                                   ptr(out["status"]), ptr(out["n_iter"]), ptr(out.get("trace")), int(n_threads))
     return out
 
 
 def mpc_step_batch_per_config(params_list, which, x0, path_id, path_len, speed, cx, cy, cyaw, path_off, target_ind, oa, od,
-                              n_threads=1, cv=None, cv_cut=None):
+                              n_threads=1, cv=None, cv_cut=None, trace=False):
     """mpc_step_batch for a batch whose ego b has the configuration params_list[which[b]] (the per-ego table of
     jsim_mpc_set_ego_config): one mpc_step_batch call per distinct configuration on that configuration's egos, the results
     scattered back into [B][..] arrays.  All configurations share T and NX."""
@@ -301,7 +321,7 @@ def mpc_step_batch_per_config(params_list, which, x0, path_id, path_len, speed, 
     for k in ks:
         sel = np.flatnonzero(which == k)
         r = mpc_step_batch(params_list[k], x0[sel], path_id[sel], path_len[sel], speed[sel], cx, cy, cyaw, path_off, target_ind[sel],
-                           oa[sel], od[sel], n_threads=n_threads, cv=cv, cv_cut=None if cv_cut is None else cv_cut[sel])
+                           oa[sel], od[sel], n_threads=n_threads, cv=cv, cv_cut=None if cv_cut is None else cv_cut[sel], trace=trace)
         if out is None:
             out = {name: np.zeros((B,) + a.shape[1:], dtype=a.dtype) for name, a in r.items()}
         for name, a in r.items():
