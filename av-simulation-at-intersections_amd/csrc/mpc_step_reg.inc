@@ -225,16 +225,39 @@ struct TickP {
 // The working set's lane-distributed state (position k lives in lane k: multiplier, 1 / R[k][k], canonical row id), pinned after a
 // masked write to it so that the write stays where it stands.
 #define JSIM_PIN_WS(lam_, rd_, id_) asm volatile("" : "+v"(lam_), "+v"(rd_), "+v"(id_))
+// Both halves of a 16-byte broadcast read count as used from here on (placed at the pair's first use, where its wait stands anyway):
+// a pair of which one half is dead is otherwise read as 8 bytes, and its neighbours lose their 16-byte alignment with it.
+#define JSIM_PIN_PAIR(p_) asm volatile("" : "+v"((p_).x), "+v"((p_).y))
 
 // Staged broadcast reads: the scheduling-barrier intrinsic carries no memory dependence, so plain LDS loads of later chunks
 // get clustered above it; a compiler-level memory barrier beside it keeps a software pipeline in place.
 #define JSIM_STAGE() do { asm volatile("" ::: "memory"); __builtin_amdgcn_sched_barrier(0); asm volatile("" ::: "memory"); } while (0)
+// One wait for a whole chunk of staged broadcast reads, at the chunk's first use: lgkmcnt(n) alone (gfx9 encoding: the other counters
+// at their maxima), n = the LDS operations issued AFTER the chunk (the next chunk's reads, a column's write).  The compiler otherwise
+// puts a wait in front of every FMA pair of the chunk, and a wave alone on its SIMD pays an issue slot for each, satisfied or not
+// (profiles/r20_ubench_wait_cost.txt: 4.4 ticks).  Its wait insertion sees this one and drops those of its own that it makes redundant;
+// it drops none that is still needed, so an n that is too large costs the gain, never a value.  Only where the chunk was issued a
+// stage ahead: on reads just issued one wait for all of them delays the first FMA by the whole burst (same file: 197 against 157 ticks).
+#define JSIM_CHUNK_WAIT(n) __builtin_amdgcn_s_waitcnt(0xC07F | ((n) << 8))
+__device__ __forceinline__ void jsim_chunk_wait(int n) // n: a constant once the loops around the call are unrolled
+{
+    switch (n) {
+#define JSIM_CW_CASE(i) case i: JSIM_CHUNK_WAIT(i); break;
+        JSIM_CW_CASE(0) JSIM_CW_CASE(1) JSIM_CW_CASE(2) JSIM_CW_CASE(3) JSIM_CW_CASE(4) JSIM_CW_CASE(5) JSIM_CW_CASE(6) JSIM_CW_CASE(7)
+        JSIM_CW_CASE(8) JSIM_CW_CASE(9) JSIM_CW_CASE(10) JSIM_CW_CASE(11) JSIM_CW_CASE(12) JSIM_CW_CASE(13) JSIM_CW_CASE(14)
+#undef JSIM_CW_CASE
+    default: break; // (15 and more: the counter's maximum, nothing to say)
+    }
+}
 // LDS base for constant-address reads of one phase: an opaque zero (see DESIGN.md: the compiler otherwise borrows a
 // long-lived register that happens to hold zero, spills it, and reloads it before every ds_read).
 #define JSIM_OPAQUE_ZERO(z) int z = 0; asm volatile("" : "+v"(z))
 
 #ifndef JSIM_ZY_CHUNK
 #define JSIM_ZY_CHUNK 8
+#endif
+#ifndef JSIM_CHUNK_WAITS
+#define JSIM_CHUNK_WAITS 15 /* one bit per pipeline (see CHW); 0: every wait left to the compiler (A/B builds) */
 #endif
 
 #include "loop_pre_tick.inc"
@@ -409,6 +432,12 @@ void mpc_step_reg_kernel(const KP Pin, const TickP K, const PreK Q)
     constexpr int NW = VS ? N : NR; // the lane that carries w = L^-1 g
     static_assert(NW < 64, "register path needs 2T+1 lanes (3T+2 with resident speed rows)");
     constexpr int NP = N + 2; // N is even, so every vector below stays 16-byte aligned
+    // One wait per staged chunk (JSIM_CHUNK_WAIT) where the columns are at most 40: the selection of the wait's immediate stands in
+    // the body of the column loops until they are unrolled, and with it in them the longer horizons' A, Jr and chunk buffers went to
+    // scratch (T = 25: 1072 B, T = 30: 1232 B -- the three arrays' size: their column loops were no longer unrolled in full).
+    // Bits: 1 Cholesky, 2 rows of J, 4 z/y dots, 8 Householder update.  HELP: the rows of J are helper 1's, beside the owner's
+    // factorisation and not on its path; with the waits there too, <20, false, 1, true> reserved a 20-byte stack that nothing accesses.
+    constexpr int CHW = VS ? 0 : HELP ? (JSIM_CHUNK_WAITS & ~2) : JSIM_CHUNK_WAITS;
     // Static LDS (all sizes are compile-time): addresses become instruction immediates.  With a dynamic
     // `extern __shared__` base every one of the ~1000 distinct constant offsets of the unrolled phases was
     // materialised in an SGPR, hoisted out of the tick loop and spilled.
@@ -955,6 +984,9 @@ void mpc_step_reg_kernel(const KP Pin, const TickP K, const PreK Q)
             const double tk = tmul;
             if (k + 1 < N) { // the one update the next column needs, then publish it
                 JSIM_STAGE();
+                // (even k: only .y of the pair that holds column entry k + 1 is used; left alone, that read is narrowed to 8 bytes and every
+                //  read behind it re-merged into 8-byte-aligned pairs, each with an address add of its own -- both halves count as used here)
+                if (!(k & 1)) JSIM_PIN_PAIR(cb[0][0]);
                 const double cn = ((k + 1) & 1) ? cb[0][(k + 1 - j0) / 2].y : cb[0][(k + 1 - j0) / 2].x;
                 A[k + 1] = fma(-tk, cn, A[k + 1]);
                 JSIM_PIN(A[k + 1]);
@@ -971,6 +1003,9 @@ void mpc_step_reg_kernel(const KP Pin, const TickP K, const PreK Q)
 #pragma unroll
                     for (int j = h + CCH; j < h + 2 * CCH && j < N; j += 2) cb[(c + 1) & 1][(j - h - CCH) / 2] = *(const double2 *)&LcC[k * LDC + j];
                 }
+                // behind this chunk's reads: the next chunk's; behind the first chunk's also the pivot and column k + 1 (written above).
+                // (In front of the stage boundary: behind it the scheduler moves the chunk's FMAs above the wait.)
+                if ((CHW & 1) && k + 1 < N) jsim_chunk_wait((c + 1 < nch ? ((h + 2 * CCH < N ? h + 2 * CCH : N) - (h + CCH)) / 2 : 0) + (c == 0 ? 2 : 0));
                 JSIM_STAGE();
 #pragma unroll
                 for (int j = h; j < h + CCH && j < N; j += 2) {
@@ -1333,6 +1368,8 @@ void mpc_step_reg_kernel(const KP Pin, const TickP K, const PreK Q)
                             vzb[(c + 1) & 1][(j - h - ZC) / 2] = *(const double2 *)&vzv[j];
                         }
                     }
+                    // (the first chunk was read just above: its waits stay the compiler's, one per pair as the reads come in)
+                    if ((CHW & 4) && c > 0) jsim_chunk_wait(c + 1 < NCH ? (h + 2 * ZC < N ? h + 2 * ZC : N) - (h + ZC) : 0); // behind it: the next chunk's d2 and v pairs
                     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                     for (int j = h; j < h + ZC && j < N; j += 2) {
@@ -1439,6 +1476,7 @@ void mpc_step_reg_kernel(const KP Pin, const TickP K, const PreK Q)
 #pragma unroll
                             for (int j = h + ZC; j < h + 2 * ZC && j < N; j += 2) vzb[(c + 1) & 1][(j - h - ZC) / 2] = *(const double2 *)&vzv[j];
                         }
+                        if ((CHW & 8) && c > 0) jsim_chunk_wait(c + 1 < NCH ? ((h + 2 * ZC < N ? h + 2 * ZC : N) - (h + ZC)) / 2 : 0); // (as in the dots; stage A's two cross-lane reads are in chunk 0)
                         __builtin_amdgcn_sched_barrier(0);
                         if (c == 0) JSIM_SEARCH_A()   // (same scheduling region as this chunk's FMAs)
                         if (c == CB1) JSIM_SEARCH_B1()

@@ -301,13 +301,15 @@ __global__ __launch_bounds__(256, JSIM_REG4_MINW) void mpc_step_reg4_kernel(cons
             if (lane == j + 1) bth = thcur;
         }
         sincos(bth, &sn, &cs);
-        const double ix = (bv * cs) * dt, iy = (bv * sn) * dt;
-        double xcur = sx, ycur = sy;
+        if (Pv.dbg_xbar) { // the x and y sums have one reader, the debug entry's xbar: no solve needs them
+            const double ix = (bv * cs) * dt, iy = (bv * sn) * dt;
+            double xcur = sx, ycur = sy;
 #pragma unroll
-        for (int j = 0; j < T; ++j) {
-            xcur = xcur + rdlane(ix, j);
-            ycur = ycur + rdlane(iy, j);
-            if (lane == j + 1) { bx = xcur; by = ycur; }
+            for (int j = 0; j < T; ++j) {
+                xcur = xcur + rdlane(ix, j);
+                ycur = ycur + rdlane(iy, j);
+                if (lane == j + 1) { bx = xcur; by = ycur; }
+            }
         }
     }
     p_sn = rdlane(sn, 0); p_cs = rdlane(cs, 0); p_sc = true;

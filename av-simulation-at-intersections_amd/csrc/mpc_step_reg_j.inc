@@ -44,6 +44,13 @@
                     for (int j = j1; j < j1 + CCH && j < N; j += 2) cb[pb ^ 1][(j - j1) / 2] = *(const double2 *)&LcJ[(m + 1) * LDC + j];
                     invb[(m + 1) & 1] = invJ[m + 1];
                 }
+                // one wait for the chunk in hand (and the pivot read with it): behind it are this stage's reads -- the next chunk's, or the
+                // next column's first chunk (without the pair an odd column does not use: it is never read) and its pivot
+                if ((CHW & 2) && m + c > 0) {
+                    const int j1 = (m + 1) & ~1;
+                    jsim_chunk_wait(c + 1 < nch ? ((h + 2 * CCH < N ? h + 2 * CCH : N) - (h + CCH)) / 2
+                                    : m + 1 < N ? ((j1 + CCH < N ? j1 + CCH : N) - j1) / 2 - ((m + 1) & 1) + 1 : 0);
+                }
                 JSIM_STAGE();
                 if (c == 0) {
                     const double y = Jr[m] * invb[m & 1];
@@ -52,6 +59,7 @@
                 }
 #pragma unroll
                 for (int j = h; j < h + CCH && j < N; j += 2) {
+                    if (j == m) JSIM_PIN_PAIR(cb[pb][0]);   // (even m: .x of this pair is not used -- keep the read 16 bytes wide, see JSIM_PIN_PAIR)
                     const double2 c2 = cb[pb][(j - h) / 2];
                     if (j > m) { Jr[j] = fma(-c2.x, smul, Jr[j]); JSIM_PIN(Jr[j]); }
                     if (j + 1 > m) { Jr[j + 1] = fma(-c2.y, smul, Jr[j + 1]); JSIM_PIN(Jr[j + 1]); }

@@ -1,7 +1,8 @@
 // mpc_step_reg_s2.inc -- S2 of the one-wave register kernel: rollout of the warm start from the current state
 // (main/lib/mpc.py:115-129 _predict_motion -> lib/simulation.py:35-47).  Included by mpc_step_reg.inc where the phase runs: after S1
 // in the plain kernels, INSIDE S1 in the HELP instantiations (the owner rolls out while the helper wavefronts scan the path -- the
-// rollout does not need the index).  In: sx, sy, sv, syaw, wa_t, wtan (= tan of the warm start's clamped steer); out: bx, by, bv, bth (lane t: state at time t), sn, cs.
+// rollout does not need the index).  In: sx, sy, sv, syaw, wa_t, wtan (= tan of the warm start's clamped steer); out: bv, bth (lane t: state at time t), sn, cs
+// -- and bx, by when the debug entry asks for xbar (P.dbg_xbar), their only reader.
     {
         const double tan_t = wtan; // tan of the clamped steer, evaluated where the warm start was written
         double vcur = sv;
@@ -25,6 +26,7 @@
             if (lane == j + 1) bth = thcur;
         }
         sincos(bth, &sn, &cs);
+        if (P.dbg_xbar) { // the x and y sums have one reader, the debug entry's xbar: no solve needs them
         const double ix = (bv * cs) * dt, iy = (bv * sn) * dt;
         double xcur = sx, ycur = sy;
 #pragma unroll
@@ -33,6 +35,7 @@
             ycur = ycur + rdlane(iy, j);
             if (lane == j + 1) { bx = xcur; by = ycur; }
         }
+        }
         } else {
         // Sequential sums in the reference's order, every prefix at once: the T increments sit behind T zeros in LDS and
         // lane L adds z[L], .., z[L + T - 1] to the start value -- T - L exact no-ops (+ 0.0), then inc_0, .., inc_{L-1}.
@@ -40,7 +43,7 @@
         double *const zx = tq, *const zy = tq + 2 * T;
         static_assert(4 * T <= TQ_COUNT * TP, "scratch fits the table area");
         const int li = lane <= T ? lane : T;
-        if (lane < T) { zx[lane] = 0.0; zy[lane] = 0.0; zx[T + lane] = w; }
+        if (lane < T) { zx[lane] = 0.0; zx[T + lane] = w; }
         LDS_SYNC();
         {
             double th = syaw;
@@ -49,11 +52,11 @@
             bth = th;
         }
         sincos(bth, &sn, &cs);
-        const double ix = (bv * cs) * dt, iy = (bv * sn) * dt;
-        LDS_SYNC();
-        if (lane < T) { zx[T + lane] = ix; zy[T + lane] = iy; }
-        LDS_SYNC();
-        {
+        if (P.dbg_xbar) { // the x and y sums have one reader, the debug entry's xbar: no solve needs them (nor zy's zeros)
+            const double ix = (bv * cs) * dt, iy = (bv * sn) * dt;
+            LDS_SYNC();
+            if (lane < T) { zy[lane] = 0.0; zx[T + lane] = ix; zy[T + lane] = iy; }
+            LDS_SYNC();
             double xc = sx, yc = sy;
 #pragma unroll
             for (int t = 0; t < T; ++t) { xc += zx[li + t]; yc += zy[li + t]; }

@@ -103,6 +103,26 @@ KERNEL(k_salu, int s_ = 1;, REP16(asm volatile("s_add_i32 %0, %0, 3\n s_xor_b32 
 KERNEL(k_sbranch, int s_ = 1;, REP16(asm volatile("s_cmp_eq_u32 %0, 77\n s_cbranch_scc1 1f\n s_add_i32 %0, %0, 2\n 1:\n s_nop 0" : "+s"(s_) : : "scc");); ia += s_;)
 KERNEL(k_bpermute, unsigned ad_ = ((threadIdx.x + 2) & 63) * 4;, REP16(asm volatile("ds_bpermute_b32 %0, %1, %0\n s_waitcnt lgkmcnt(0)" : "+v"(ia) : "v"(ad_));))
 KERNEL(k_rsq_f64, , REP16(asm volatile("v_rsq_f64 %0, %0" : "+v"(a));))
+// What a wait costs a lone wave (profiles/r20_ubench_wait_cost.txt): 8 broadcast reads and the 16 FMAs that consume them, once with
+// a wait in front of every FMA pair -- what the compiler emits for a staged chunk -- and once with a single wait for the chunk; then
+// the wait with nothing outstanding and s_nop 0 on their own.  (Fixed registers v[60:91]: an operand's halves cannot be named.)
+#define WC_READS "ds_read_b128 v[60:63], %8\n ds_read_b128 v[64:67], %8 offset:16\n ds_read_b128 v[68:71], %8 offset:32\n ds_read_b128 v[72:75], %8 offset:48\n" \
+                 "ds_read_b128 v[76:79], %8 offset:64\n ds_read_b128 v[80:83], %8 offset:80\n ds_read_b128 v[84:87], %8 offset:96\n ds_read_b128 v[88:91], %8 offset:112\n"
+#define WC_PAIR(w_, r0_, r1_, a0_, a1_) w_ "v_fma_f64 %" #a0_ ", v[" #r0_ "], %9, %" #a0_ "\n v_fma_f64 %" #a1_ ", v[" #r1_ "], %9, %" #a1_ "\n"
+#define WC_W(n_) "s_waitcnt lgkmcnt(" #n_ ")\n"
+#define WC_OPS : "+v"(a), "+v"(c), "+v"(d), "+v"(e), "+v"(f), "+v"(g), "+v"(h), "+v"(p_) : "v"(z_), "v"(b)                                          \
+               : "v60", "v61", "v62", "v63", "v64", "v65", "v66", "v67", "v68", "v69", "v70", "v71", "v72", "v73", "v74", "v75",  \
+                 "v76", "v77", "v78", "v79", "v80", "v81", "v82", "v83", "v84", "v85", "v86", "v87", "v88", "v89", "v90", "v91"
+KERNEL(k_wait_per_pair, double p_ = 6.0; unsigned z_ = 0;,
+       REP4(asm volatile(WC_READS WC_PAIR(WC_W(7), 60:61, 62:63, 0, 1) WC_PAIR(WC_W(6), 64:65, 66:67, 2, 3) WC_PAIR(WC_W(5), 68:69, 70:71, 4, 5)
+                         WC_PAIR(WC_W(4), 72:73, 74:75, 6, 7) WC_PAIR(WC_W(3), 76:77, 78:79, 0, 1) WC_PAIR(WC_W(2), 80:81, 82:83, 2, 3)
+                         WC_PAIR(WC_W(1), 84:85, 86:87, 4, 5) WC_PAIR(WC_W(0), 88:89, 90:91, 6, 7) WC_OPS);) a += p_;)
+KERNEL(k_wait_per_chunk, double p_ = 6.0; unsigned z_ = 0;,
+       REP4(asm volatile(WC_READS WC_PAIR(WC_W(0), 60:61, 62:63, 0, 1) WC_PAIR("", 64:65, 66:67, 2, 3) WC_PAIR("", 68:69, 70:71, 4, 5)
+                         WC_PAIR("", 72:73, 74:75, 6, 7) WC_PAIR("", 76:77, 78:79, 0, 1) WC_PAIR("", 80:81, 82:83, 2, 3)
+                         WC_PAIR("", 84:85, 86:87, 4, 5) WC_PAIR("", 88:89, 90:91, 6, 7) WC_OPS);) a += p_;)
+KERNEL(k_wait_satisfied, , REP16(asm volatile("s_waitcnt lgkmcnt(0)\n s_waitcnt lgkmcnt(0)\n s_waitcnt lgkmcnt(0)\n s_waitcnt lgkmcnt(0)");))
+KERNEL(k_snop, , REP16(asm volatile("s_nop 0\n s_nop 0\n s_nop 0\n s_nop 0");))
 typedef double v4d_ __attribute__((ext_vector_type(4)));
 #define MFMA1 acc_ = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc_, 0, 0, 0);
 KERNEL(k_mfma_f64, v4d_ acc_; acc_[0] = 0.0; acc_[1] = 0.0; acc_[2] = 0.0; acc_[3] = 0.0;, REP16(MFMA1) a += acc_[0];)
@@ -129,6 +149,8 @@ int main()
         {"s_add/s_xor dependent", k_salu, 64, "instr"}, {"s_cmp + s_cbranch (not taken) + s_add", k_sbranch, 16, "group"},
         {"ds_bpermute_b32 + wait", k_bpermute, 16, "group"}, {"v_rsq_f64 dependent", k_rsq_f64, 16, "instr"},
         {"v_mfma_f64_16x16x4 dependent", k_mfma_f64, 16, "instr"},
+        {"8 x ds_read_b128, 8 x (wait 7..0 + 2 fma_f64)", k_wait_per_pair, 4, "group"}, {"8 x ds_read_b128, 1 wait, 16 fma_f64", k_wait_per_chunk, 4, "group"},
+        {"s_waitcnt lgkmcnt(0), nothing outstanding", k_wait_satisfied, 64, "instr"}, {"s_nop 0", k_snop, 64, "instr"},
     };
     const int iters = 2000;
     for (int nb : {1, 1024}) {
