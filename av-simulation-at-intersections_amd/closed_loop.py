@@ -167,6 +167,30 @@ class Recorder:
         g = np.repeat(np.arange(len(self.groups) - 1), np.diff(self.groups))
         return np.stack([self.groups[g], self.groups[g + 1]], axis=1).astype(np.int32)
 
+    def _vehicle_lists(self, shapes=None, mates=None):
+        """What conflicts() and gaps() meet: (ego_shape, shapes [n_obs][4] or None, veh_range, mate_range), checked."""
+        eng = self.loop.eng
+        B, n_obs = eng.B, self.n_obs
+        ego = self._ego_shape()
+        if shapes is None:
+            shapes = eng.vehicle_shapes
+        if shapes is not None:
+            shapes = np.ascontiguousarray(shapes, dtype=np.float64)
+            if shapes.shape != (n_obs, 4) or not (np.isfinite(shapes).all() and (shapes[:, 2] > 0).all()):
+                raise ValueError(f"shapes must be [n_obs = {n_obs}, 4] vehicle_shape rows with finite offsets and positive radii")
+        veh = self.vehicle_ranges()
+        mate = self.mate_ranges() if mates is None else np.ascontiguousarray(mates, dtype=np.int32)
+        if mate.shape != (B, 2):
+            raise ValueError(f"mates must be [B = {B}, 2] batch ranges, got {mate.shape}")
+        if (veh < 0).any() or (veh > n_obs).any() or (mate < 0).any() or (mate > B).any():
+            raise ValueError("a vehicle range outside [0, n_obs] or a mate range outside [0, B]")
+        me = np.arange(B)
+        count = np.maximum(veh[:, 1] - veh[:, 0], 0) + np.maximum(mate[:, 1] - mate[:, 0], 0) - ((me >= mate[:, 0]) & (me < mate[:, 1]))
+        if (count > MAX_OBS).any():
+            b = int(np.argmax(count))
+            raise ValueError(f"ego {b} would meet {int(count[b])} vehicles and mates (max {MAX_OBS})")
+        return ego, shapes, veh, mate
+
     def conflicts(self, frame_window: int = 0, shapes=None, mates=None) -> dict:
         """Clearance and first contact of every recorded tick and episode (jsim_loop_eval_conflicts): what
         check_collision_moving_cars / check_collision_moving_bicycle of main/lib/collision_avoidance.py (:85-166) return for an
@@ -196,24 +220,7 @@ class Recorder:
         w = int(frame_window)
         if w != frame_window or not 0 <= w <= 20:
             raise ValueError(f"frame_window must be an integer in 0..20, got {frame_window!r}")
-        ego = self._ego_shape()
-        if shapes is None:
-            shapes = eng.vehicle_shapes
-        if shapes is not None:
-            shapes = np.ascontiguousarray(shapes, dtype=np.float64)
-            if shapes.shape != (n_obs, 4) or not (np.isfinite(shapes).all() and (shapes[:, 2] > 0).all()):
-                raise ValueError(f"shapes must be [n_obs = {n_obs}, 4] vehicle_shape rows with finite offsets and positive radii")
-        veh = self.vehicle_ranges()
-        mate = self.mate_ranges() if mates is None else np.ascontiguousarray(mates, dtype=np.int32)
-        if mate.shape != (B, 2):
-            raise ValueError(f"mates must be [B = {B}, 2] batch ranges, got {mate.shape}")
-        if (veh < 0).any() or (veh > n_obs).any() or (mate < 0).any() or (mate > B).any():
-            raise ValueError("a vehicle range outside [0, n_obs] or a mate range outside [0, B]")
-        me = np.arange(B)
-        count = np.maximum(veh[:, 1] - veh[:, 0], 0) + np.maximum(mate[:, 1] - mate[:, 0], 0) - ((me >= mate[:, 0]) & (me < mate[:, 1]))
-        if (count > MAX_OBS).any():
-            b = int(np.argmax(count))
-            raise ValueError(f"ego {b} would meet {int(count[b])} vehicles and mates (max {MAX_OBS})")
+        ego, shapes, veh, mate = self._vehicle_lists(shapes, mates)
         n = self._n(4) if n is None else n
         dev = eng.device
         up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(dev)
@@ -228,6 +235,57 @@ class Recorder:
                    _ptr(clear), _ptr(who), _ptr(row), _ptr(hit_tick), _ptr(hit_frame), _ptr(hit_xy))
         return {"clear": clear, "who": who, "row": row, "hit_tick": hit_tick, "hit_frame": hit_frame, "hit_xy": hit_xy,
                 "frame_window": w, "veh_range": veh, "mate_range": mate, "ego_shape": tuple(float(v) for v in ego)}
+
+    def gaps(self, window: int = 20, within: str = "episode", shapes=None, mates=None) -> dict:
+        """The time gap between every ego and each vehicle it meets, per recorded tick and episode (jsim_loop_eval_gaps, DESIGN.md
+        section 23): how many ticks lay between the ego occupying a place and a vehicle occupying it, and who went first -- the
+        post-encroachment time of a crossing, the time headway to a leader.  An episode's smallest gap is the least frame_window at
+        which check_collision_moving_cars / check_collision_moving_bicycle (main/lib/collision_avoidance.py:68-166) report a hit
+        on it.  One launch from the records.
+
+        window: the largest offset tried, 0..63.  within: "episode" (only vehicle ticks inside the ego's own episode count: the
+        reference's rule) or "record" (every recorded tick counts, so the vehicle that passed a spawn point just before the ego
+        respawned there is found).  shapes, mates: as for conflicts(); the list is the same, eight places in all.
+        Returns numpy arrays: off [n][B][8] int8 (per place the touching offset of smallest |off|; > 0: the vehicle was here first,
+        < 0: the ego was; -o in front of +o; history.GAP_NONE = -128: nothing within the window, or no such place), gap [n][B] (the
+        smallest |off| over the places, -1: none), who (the lowest place that has it); at the slot of an episode's first tick
+        ep_gap (the episode's smallest gap, -1: none), ep_tick (the first tick that has it), ep_who (the lowest place that has it
+        there), ep_off (its signed offset, -128: none), -1 / -1 / -1 / -128 elsewhere; and the window, within, veh_range, mate_range
+        and ego_shape used.  history.gap_episodes splits the result into episodes.
+        ValueError: a window outside 0..63, another within, and what conflicts() refuses of shapes and mates."""
+        d = self._gaps_device(window, within, shapes, mates)
+        off = d["off"].cpu().numpy()
+        gap, who = history.gap_per_tick(off)
+        return {"off": off, "gap": gap, "who": who,
+                "ep_gap": d["ep_gap"].cpu().numpy(), "ep_tick": d["ep_tick"].cpu().numpy(), "ep_who": d["ep_who"].cpu().numpy(),
+                "ep_off": d["ep_off"].cpu().numpy(), "window": d["window"], "within": d["within"], "veh_range": d["veh_range"],
+                "mate_range": d["mate_range"], "ego_shape": d["ego_shape"]}
+
+    def _gaps_device(self, window: int = 20, within: str = "episode", shapes=None, mates=None, n=None) -> dict:
+        """gaps() up to the launch: the outputs as device tensors (off, ep_gap, ep_tick, ep_who, ep_off) and the host arguments used
+        (window, within, veh_range, mate_range, ego_shape)."""
+        eng = self.loop.eng
+        B, n_obs = eng.B, self.n_obs
+        w = int(window)
+        if w != window or not 0 <= w <= history.GAP_MAX_WINDOW:
+            raise ValueError(f"window must be an integer in 0..{history.GAP_MAX_WINDOW}, got {window!r}")
+        if within not in ("episode", "record"):
+            raise ValueError(f'within must be "episode" or "record", got {within!r}')
+        ego, shapes, veh, mate = self._vehicle_lists(shapes, mates)
+        n = self._n(4) if n is None else n
+        dev = eng.device
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(dev)
+        d_veh, d_mate = up(veh), up(mate)
+        off = self._new(n, 8, dtype=torch.int8)
+        ep_gap, ep_tick, ep_who, ep_off = self._new(n, dtype=torch.int32, count=4)
+        ego_c = (C.c_double * 3)(*ego)
+        rec, flags, x_first, x_spawn = self._buffers()
+        self._call("jsim_loop_eval_gaps", B, n, rec, flags, n_obs, _ptr(self.obs) if self.obs is not None else None,
+                   x_first, x_spawn, _ptr(d_veh), _ptr(d_mate),
+                   shapes.ctypes.data_as(C.c_void_p) if shapes is not None and n_obs else None, C.cast(ego_c, C.c_void_p), w,
+                   int(within == "record"), _ptr(off), _ptr(ep_gap), _ptr(ep_tick), _ptr(ep_who), _ptr(ep_off))
+        return {"off": off, "ep_gap": ep_gap, "ep_tick": ep_tick, "ep_who": ep_who, "ep_off": ep_off, "window": w, "within": within,
+                "veh_range": veh, "mate_range": mate, "ego_shape": tuple(float(v) for v in ego)}
 
     def static_conflicts(self, obstacles, set_of=None, margin=None, include_hidden: bool = False) -> dict:
         """Clearance to and contact with the scenario's static obstacles on every recorded tick (jsim_loop_eval_static, DESIGN.md

@@ -1377,6 +1377,7 @@ struct jsim_ctx {
     std::vector<double> h_shapes;  // host copy [n_shapes][4] (the thresholds follow jsim_loop_set_geometry)
     int n_shapes = 0;
     DevArray<double4> d_conflict_rows; // [n_obs] (cc_front, cc_rear, thr, thr_sq) of jsim_loop_eval_conflicts' last call with a table
+    DevArray<double4> d_gap_rows;      // the same of jsim_loop_eval_gaps' last call with a table
     DevArray<double> d_static_rows;    // [n_rows][JSIM_STATIC_ROW] and
     DevArray<int> d_static_off;        // [n_sets + 1] of jsim_loop_eval_static's last call
     DevArray<double2> d_pcc;
@@ -2362,6 +2363,28 @@ extern "C" int jsim_loop_eval_reasons(jsim_ctx *ctx, int32_t B, int32_t n_ticks,
 
 #include "conflicts.inc"
 
+// shapes [n_obs][4] = the rows of jsim_loop_set_vehicle_shapes, a HOST pointer
+static int check_shape_rows(jsim_ctx *ctx, const char *F, int n_obs, const double *shapes)
+{
+    for (int i = 0; i < n_obs; ++i) {
+        const double *s = shapes + 4 * (size_t)i;
+        if (!std::isfinite(s[0]) || !std::isfinite(s[1]) || !(s[2] > 0.0) || !std::isfinite(s[2]))
+            return fail(ctx, -22, "%s: shapes row %d needs finite circle offsets and a positive, finite radius", F, i);
+    }
+    return 0;
+}
+// min_distance per vehicle: the egos' radius + its own, and the squared form the rows are compared with, as rows of `table`
+static int replace_conflict_rows(jsim_ctx *ctx, DevArray<double4> &table, int n_obs, const double *shapes, double r_ego)
+{
+    std::vector<double4> rows((size_t)n_obs);
+    for (int i = 0; i < n_obs; ++i) {
+        const double *s = shapes + 4 * (size_t)i;
+        const double thr = r_ego + s[2];
+        rows[i] = double4{s[0], s[1], thr, jsim_sqrt_threshold(thr)};
+    }
+    return replace_table(ctx, table, rows.data(), (size_t)n_obs);
+}
+
 // Clearance and first contact per recorded tick: DEVICE pointers for the recorder's buffers, the ranges and
 // the outputs, HOST pointers for `shapes` and `ego_shape` (the thresholds are made here, on the host); one launch on `stream`, one
 // wavefront per ego.
@@ -2381,26 +2404,57 @@ extern "C" int jsim_loop_eval_conflicts(jsim_ctx *ctx, int32_t B, int32_t n_tick
     if (int rc = check_ego_shape(ctx, F, ego_shape)) return rc;
     const double cc_f = ego_shape[0], cc_r = ego_shape[1], r_ego = ego_shape[2];
     const bool table = shapes && n_obs > 0;
-    for (int i = 0; table && i < n_obs; ++i) {
-        const double *s = shapes + 4 * (size_t)i;
-        if (!std::isfinite(s[0]) || !std::isfinite(s[1]) || !(s[2] > 0.0) || !std::isfinite(s[2]))
-            return fail(ctx, -22, "%s: shapes row %d needs finite circle offsets and a positive, finite radius", F, i);
-    }
+    if (table)
+        if (int rc = check_shape_rows(ctx, F, n_obs, shapes)) return rc;
     JSIM_RECORDER_CALL(B == 0 || n_ticks == 0);
-    if (table) {   // min_distance per vehicle: the egos' radius + its own, and the squared form the rows are compared with
-        std::vector<double4> rows((size_t)n_obs);
-        for (int i = 0; i < n_obs; ++i) {
-            const double *s = shapes + 4 * (size_t)i;
-            const double thr = r_ego + s[2];
-            rows[i] = double4{s[0], s[1], thr, jsim_sqrt_threshold(thr)};
-        }
-        if (int rc = replace_table(ctx, ctx->d_conflict_rows, rows.data(), (size_t)n_obs)) return rc;
-    }
+    if (table)
+        if (int rc = replace_conflict_rows(ctx, ctx->d_conflict_rows, n_obs, shapes, r_ego)) return rc;
     const double thr_ee = r_ego + r_ego;
     const ConflictP P = {recorder_buf(B, n_ticks, rec, flags, x_first, x_spawn), n_obs, frame_window, n_obs > 0 ? obs_rec : nullptr,
                          veh_range, mate_range, table ? ctx->d_conflict_rows.p : nullptr, cc_f, cc_r,
                          double4{cc_f, cc_r, thr_ee, jsim_sqrt_threshold(thr_ee)}, clear, who, row, hit_tick, hit_frame, hit_xy};
     return launch_per_ego(ctx, conflict_ticks_kernel, B, stream, P);
+}
+
+#include "gaps.inc"
+
+// The time gap between an ego and each vehicle per recorded tick: pointers as jsim_loop_eval_conflicts has
+// them; one launch on `stream`, one wavefront per ego, its LDS sized from the window and the longest list the tables allow.
+extern "C" int jsim_loop_eval_gaps(jsim_ctx *ctx, int32_t B, int32_t n_ticks, const double *rec, const int32_t *flags, int32_t n_obs,
+                                   const double *obs_rec, const double *x_first, const double *x_spawn, const int32_t *veh_range,
+                                   const int32_t *mate_range, const double *shapes, const double *ego_shape, int32_t window, int32_t within,
+                                   int8_t *off, int32_t *ep_gap, int32_t *ep_tick, int32_t *ep_who, int32_t *ep_off, void *stream)
+{
+    const char *const F = "jsim_loop_eval_gaps";
+    if (B < 0 || n_ticks < 0 || n_obs < 0) return fail(ctx, -22, "%s: B=%d n_ticks=%d n_obs=%d", F, B, n_ticks, n_obs);
+    if (!obs_rec && n_obs > 0) return fail(ctx, -22, "%s: null obs_rec with n_obs=%d", F, n_obs);
+    if (window < 0 || window > JSIM_GAP_MAX_WINDOW) return fail(ctx, -22, "%s: window=%d outside [0, %d]", F, window, JSIM_GAP_MAX_WINDOW);
+    if (within != 0 && within != 1) return fail(ctx, -22, "%s: within=%d is neither 0 (episode) nor 1 (record)", F, within);
+    if (!ego_shape) return fail(ctx, -22, "%s: null ego_shape", F);
+    if (!rec || !flags || !x_first || !x_spawn || !veh_range || !mate_range) return fail(ctx, -22, "%s: null device pointer", F);
+    const void *const outs[] = {off, ep_gap, ep_tick, ep_who, ep_off};
+    const char *const out_names[] = {"off", "ep_gap", "ep_tick", "ep_who", "ep_off"};
+    for (int i = 0; i < 5; ++i)
+        if (!outs[i]) return fail(ctx, -22, "%s: null output %s", F, out_names[i]);
+    if (int rc = check_ego_shape(ctx, F, ego_shape)) return rc;
+    const double cc_f = ego_shape[0], cc_r = ego_shape[1], r_ego = ego_shape[2];
+    const bool table = shapes && n_obs > 0;
+    if (table)
+        if (int rc = check_shape_rows(ctx, F, n_obs, shapes)) return rc;
+    JSIM_RECORDER_CALL(B == 0 || n_ticks == 0);
+    if (table)
+        if (int rc = replace_conflict_rows(ctx, ctx->d_gap_rows, n_obs, shapes, r_ego)) return rc;
+    const double thr_ee = r_ego + r_ego;
+    const GapP P = {{recorder_buf(B, n_ticks, rec, flags, x_first, x_spawn), n_obs, 0, n_obs > 0 ? obs_rec : nullptr, veh_range, mate_range,
+                     table ? ctx->d_gap_rows.p : nullptr, cc_f, cc_r, double4{cc_f, cc_r, thr_ee, jsim_sqrt_threshold(thr_ee)},
+                     nullptr, nullptr, nullptr, nullptr, nullptr, nullptr},
+                    window, within, reinterpret_cast<unsigned long long *>(off), ep_gap, ep_tick, ep_who, ep_off};
+    // no list is longer than the recorded vehicles plus the other egos, or than JSIM_MAX_OBS (jcf_list clamps to both)
+    const int longest = std::min<long long>(JSIM_MAX_OBS, (long long)n_obs + B - 1);
+    const size_t lds = sizeof(double2) * 2 * (size_t)std::max(longest, 1) * (size_t)(64 + 2 * window);
+    hipLaunchKernelGGL(gap_ticks_kernel, dim3(B), dim3(64), lds, (hipStream_t)stream, P);
+    HIP_TRY(ctx, hipGetLastError());
+    return 0;
 }
 
 #include "static_conflicts.inc"

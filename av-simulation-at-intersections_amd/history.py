@@ -5,7 +5,8 @@ the device recorder wrote (jsim_loop_set_recorder): rec [n][B][7] = x, y, yaw, v
 the recorder, testable without a device.  reason_series does the same for the per-tick stakeholder reasons,
 conflict_episodes for the clearance and first contact of every episode (section 17), static_episodes for the static obstacles
 (section 18), episode_rows for the per-episode table that is reduced on the device (section 19), cutoff_episodes for the glue's
-collision cut-off of every tick (section 21); fork_rows, join and reasons_carry_at are the host side of a fork (section 22)."""
+collision cut-off of every tick (section 21); fork_rows, join and reasons_carry_at are the host side of a fork (section 22);
+gap_episodes for the time gap between an ego and each vehicle (section 23)."""
 from __future__ import annotations
 
 from typing import List, Optional
@@ -20,6 +21,7 @@ EP_INT = ("ego", "k0", "n", "end", "failed", "dev_tick", "veh_tick", "veh_who", 
           "st_off_tick", "st_obstacle", "st_ticks_off", "replan_tick")
 EP_DOUBLE = ("length", "v_mean", "v_max", "a_min", "a_max", "delta_absmax", "dev_max", "dev_mean", "veh_clear", "veh_hit_x",
              "veh_hit_y", "st_clear", "pm_min", "driver_min", "cyclist_min", "dist_min")
+GAP_NONE, GAP_MAX_WINDOW = -128, 63      # JSIM_GAP_NONE, JSIM_GAP_MAX_WINDOW
 
 
 class History:
@@ -152,6 +154,45 @@ def conflict_episodes(result: dict, flags: np.ndarray):
             frame = int(result["hit_frame"][k0, b])
             ep.update(contact=True, tick=tick, frame=frame, xy=(x, y), collision_xy=(x, y, frame))
         ep["min_clear"], ep["min_clear_tick"], ep["closest_vehicle"] = _min_clear(clear, who, b, k0, k1)
+        return ep
+    return _per_episode(flags, make)
+
+
+def gap_per_tick(off: np.ndarray):
+    """(gap, who) [n][B] int32 of Recorder.gaps' `off` [n][B][8]: the smallest |offset| over an ego's places on a tick and the lowest
+    place that has it; -1 / -1 where no place has an offset (GAP_NONE)."""
+    off = np.asarray(off).astype(np.int32)
+    mag = np.where(off == GAP_NONE, GAP_MAX_WINDOW + 1, np.abs(off))
+    who = np.argmin(mag, axis=2).astype(np.int32)                          # the lowest place on ties
+    gap = np.take_along_axis(mag, who[:, :, None], axis=2)[:, :, 0]
+    none = gap > GAP_MAX_WINDOW
+    return np.where(none, -1, gap).astype(np.int32), np.where(none, -1, who).astype(np.int32)
+
+
+def gap_episodes(result: dict, flags: np.ndarray, dt: float):
+    """The time gaps of a recorder (Recorder.gaps: `off`, `ep_gap`, `ep_tick`, `ep_who`, `ep_off`) per ego and episode, split where
+    ego_histories splits (episode_bounds).  Returns a list over egos of lists over episodes of dicts: gap (the episode's smallest
+    |offset| in ticks, -1: nothing within the window), seconds (gap * dt, None without a gap), tick (the first tick that has it,
+    -1), vehicle (the lowest place in the ego's list that has it on that tick, -1), first ("vehicle": it stood in the place before
+    the ego did, "ego": the ego did, None: the same tick, or no gap) and per_vehicle: for each of the eight places (gap, offset,
+    tick) -- its own smallest |offset| over the episode's ticks, that signed offset and the first tick that has it, (-1, None, -1)
+    without one -- the table a gap-acceptance plot is drawn from."""
+    off = np.asarray(result["off"]).astype(np.int32)
+    mag = np.where(off == GAP_NONE, GAP_MAX_WINDOW + 1, np.abs(off))
+
+    def make(b, k0, k1):
+        ep = {"gap": -1, "seconds": None, "tick": -1, "vehicle": -1, "first": None, "per_vehicle": [(-1, None, -1)] * off.shape[2]}
+        if k1 <= k0:
+            return ep
+        g = int(result["ep_gap"][k0, b])
+        if g >= 0:
+            o = int(result["ep_off"][k0, b])
+            ep.update(gap=g, seconds=g * float(dt), tick=int(result["ep_tick"][k0, b]), vehicle=int(result["ep_who"][k0, b]),
+                      first="vehicle" if o > 0 else "ego" if o < 0 else None)
+        m = mag[k0:k1, b]                                                  # [ticks][places]
+        k = np.argmin(m, axis=0)                                           # the first tick of each place's smallest
+        ep["per_vehicle"] = [(int(m[k[i], i]), int(off[k0 + k[i], b, i]), k0 + int(k[i])) if m[k[i], i] <= GAP_MAX_WINDOW else (-1, None, -1)
+                             for i in range(off.shape[2])]
         return ep
     return _per_episode(flags, make)
 

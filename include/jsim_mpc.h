@@ -451,6 +451,45 @@ int jsim_loop_eval_conflicts(jsim_ctx *ctx, int32_t B, int32_t n_ticks, const do
                              double *clear, int32_t *who, int32_t *row, int32_t *hit_tick, int32_t *hit_frame, double *hit_xy,
                              void *stream);
 
+/* ---- the time gap between an ego and each vehicle per recorded tick: how close in time a pass was, and who went first ----
+ * The post-encroachment time of a realised run, in ticks: for ego b, tick k and vehicle i of its list, offset `off` touches when
+ * one of the four circle pairs of (the ego at tick k, vehicle i at tick k - off) touches.  off > 0: the vehicle stood in this place
+ * off ticks before the ego did (the vehicle went first); off < 0: the ego went first.  It is the number that
+ * check_collision_moving_cars / check_collision_moving_bicycle (main/lib/collision_avoidance.py:68-166) hold and never report: with
+ * frame_window = w they test the ego's frame f against every vehicle at the frames f - w .. f + w (_offset_trajectories_by_frames),
+ * and main/planner/moving_obstacle_avoidance.py:59-76 calls them on whole realised trajectories -- so an episode's smallest |off| is
+ * the least frame_window at which the reference's own function reports a hit on it.  From the recorder's buffers
+ * (jsim_loop_set_recorder), after the loop.  One wavefront per ego, 64 ticks at a time; the vehicles' circle centres of the ticks a
+ * chunk reaches are made once per chunk and kept in LDS.  DESIGN.md section 23 is the contract.
+ *   DEVICE pointers: rec, flags, obs_rec, x_first, x_spawn, veh_range, mate_range exactly as jsim_loop_eval_conflicts takes them (the
+ *   same poses, the same list: the vehicles of veh_range, then the mates of mate_range with the ego itself skipped, JSIM_MAX_OBS (8)
+ *   in all); and every output.  off must be 8-byte aligned (one 8-byte store per ego and tick).
+ *   HOST pointers: shapes [n_obs][4] (NULL: every vehicle has the ego's shape) and ego_shape [3] as jsim_loop_eval_conflicts takes
+ *   them; thresholds, circle centres and the comparison dx * dx + dy * dy <= thr_sq are that call's, operation for operation.
+ *   window W in [0, JSIM_GAP_MAX_WINDOW]: the offsets -W .. W are tried.  within 0 ("episode", the reference's rule): only vehicle
+ *   ticks k - off inside the ego's own episode count -- for the smallest |off| this equals the reference's clamp(f - off, 0, N - 1),
+ *   a clamped row repeating a real frame pair of no larger real offset -- so that on every tick 0 <= min_i |off_i| <= w exactly
+ *   when jsim_loop_eval_conflicts' row >= 0 at frame_window = w.  within 1 ("record"): every recorded tick 0 <= k - off < n_ticks
+ *   counts, whatever the ego's episode: a scripted vehicle's obs_rec[k - off], a mate's own start-of-tick pose, respawns included.
+ *   Out, per ego and tick: off [n_ticks][B][8] int8, byte i = the touching offset of smallest |off| of place i of the list, -o in
+ *   front of +o on a tie (the reference's row order), JSIM_GAP_NONE where nothing touches within the window and for places
+ *   i >= n_veh.  Per episode, at the slot of its first tick (the last record closes the running episode; every other slot
+ *   -1 / -1 / -1 / JSIM_GAP_NONE), [n_ticks][B] int32 each: ep_gap = the smallest |off| over the episode's ticks and vehicles or
+ *   -1, ep_tick = the first tick that has it, ep_who = the lowest place that has it on that tick, ep_off = that place's signed
+ *   offset (JSIM_GAP_NONE without one).  An ego without vehicles and mates has JSIM_GAP_NONE / -1 everywhere.
+ *   Refused (-22) before any device call, jsim_last_error naming the argument: what jsim_loop_eval_conflicts refuses (B < 0,
+ *   n_ticks < 0, n_obs < 0; obs_rec NULL with n_obs > 0; a null pointer other than obs_rec (n_obs = 0), shapes and stream; an ego
+ *   radius that is not positive and finite, a circle offset or a shapes radius likewise; a null ctx); window outside
+ *   [0, JSIM_GAP_MAX_WINDOW]; within other than 0 or 1; a null output.  n_ticks = 0 or B = 0 returns 0 and writes nothing.  A range
+ *   outside its table or a list of more than 8: the kernel clamps and the Python surface (Recorder.gaps) refuses, as for
+ *   jsim_loop_eval_conflicts. */
+#define JSIM_GAP_NONE (-128)
+#define JSIM_GAP_MAX_WINDOW 63
+int jsim_loop_eval_gaps(jsim_ctx *ctx, int32_t B, int32_t n_ticks, const double *rec, const int32_t *flags, int32_t n_obs,
+                        const double *obs_rec, const double *x_first, const double *x_spawn, const int32_t *veh_range,
+                        const int32_t *mate_range, const double *shapes, const double *ego_shape, int32_t window, int32_t within,
+                        int8_t *off, int32_t *ep_gap, int32_t *ep_tick, int32_t *ep_who, int32_t *ep_off, void *stream);
+
 /* ---- static-obstacle clearance and contact per recorded tick: the realised poses of a run against the scenario's obstacles ----
  * Answers for driven poses what the reference only asks of planned ones: check_collision (main/lib/obstacles.py:157-176) on
  * Obstacle.to_convex(margin) (:82-93 box, :134-148 circle) -- the planner's collision test, main/lib/mp_search_ww_generic.py:199-215
