@@ -50,6 +50,19 @@ class JsimError(RuntimeError):
     pass
 
 
+# per-ego status of a step / tick (include/jsim_mpc.h; 3: the ego has no path)
+STATUS_OK, STATUS_INFEASIBLE, STATUS_NEAREST_ANOMALY, STATUS_NO_PATH, STATUS_HELPER_TIMEOUT = 0, 1, 2, 3, 4
+
+
+def check_status(status, what: str) -> None:
+    """Raise on a status that is a fault of the library, not an outcome of the controller: JSIM_HELPER_TIMEOUT (a helper
+    wavefront's bounded wait ran out; that ego's tick was treated like a failed solve).  `status`: host array of per-ego status."""
+    bad = [int(b) for b in (status == STATUS_HELPER_TIMEOUT).nonzero()[0]]
+    if bad:
+        raise JsimError(f"{what}: status {STATUS_HELPER_TIMEOUT} (JSIM_HELPER_TIMEOUT) on ego(s) {bad[:8]}"
+                        f"{' ..' if len(bad) > 8 else ''}: a helper wavefront gave up waiting for a column of the factor")
+
+
 def load() -> C.CDLL:
     """Load the HIP library; raise if it is absent (no fallback path exists)."""
     global _lib

@@ -100,10 +100,13 @@ class BatchedMPC:
 
     def read_back(self) -> dict:
         """Everything the step wrote, on the host, with ONE synchronising device->host copy: a dict of numpy views
-        (target_ind, oa, od, ox, oy, ov, oyaw, xref, di_ai, active_mask, status, n_iter)."""
+        (target_ind, oa, od, ox, oy, ov, oyaw, xref, di_ai, active_mask, status, n_iter).  Raises JsimError if an ego's status is
+        JSIM_HELPER_TIMEOUT: that is a fault of the kernels, not a failed solve."""
         host = self._arena.cpu().numpy()
-        return {name: host[o:o + n].view(torch.empty((), dtype=dt).numpy().dtype).reshape(shape)
-                for name, (o, n, dt, shape) in self._arena_layout.items()}
+        out = {name: host[o:o + n].view(torch.empty((), dtype=dt).numpy().dtype).reshape(shape)
+               for name, (o, n, dt, shape) in self._arena_layout.items()}
+        _cabi.check_status(out["status"], "BatchedMPC.read_back")   # (raises JsimError on JSIM_HELPER_TIMEOUT)
+        return out
 
     # ------------------------------------------------------------------ paths
     def _upload_paths(self):

@@ -289,23 +289,27 @@ struct PreK {
 //   * J = L^-T (the forward substitutions on the rows of the augmented J) consumes the factor column by column, in the order the
 //     Cholesky factorisation produces them: helper 1 runs it BESIDE the owner's factorisation, one column behind -- it polls the
 //     pivots the owner publishes with the columns (invc) -- and hands the rows over through LDS (Jx).
-// The factorisation itself and the active-set loop are one dependent chain per column / iteration and stay with the owner; the
-// helpers sleep at a barrier.  Protocol: the owner posts a command (hb_cmd) and passes a barrier, works, passes a second barrier;
+//   * the factorisation's right half (SPLIT, where H outlives the owner's read of its rows): the chain of pivots stays one chain,
+//     but the owner carries only columns [0, NS) of it and helper 2 the rest, each with half the FMAs, reads and waits a column.
+// The active-set loop is one dependent chain per iteration and stays with the owner; the helpers sleep at a barrier.  Protocol: the owner posts a command (hb_cmd) and passes a barrier, works, passes a second barrier;
 // the helpers loop { barrier; read command; work; barrier }.  Three such pairs per tick, flushed with HB_SKIP on the owner's early
 // exits, HB_EXIT after the last tick.
 enum { HB_SKIP = 0, HB_SCAN = 1, HB_HBUILD = 2, HB_JBUILD = 3, HB_EXIT = 4 };
 
-// Helper 1 waits until the owner has published a column of the factor: 1 / sqrt(pivot) of column k, invc[k], is set to -1 before the
+// A helper waits until a column of the factor is published: 1 / sqrt(pivot) of column k, invc[k], is set to -1 before the
 // factorisation starts and written (never negative, whatever the pivot: the high word of -1.0 cannot come back) when column k and
-// everything in front of it is in LDS -- the helper polls that word; no counter has to be kept by the owner.  Written in assembly so
-// that the loop does not exist for the compiler: as a C loop inside the fully unrolled forward substitution it kept that loop from being unrolled, Jr[] became
-// dynamically indexed and was "promoted" to 100 KB of LDS.  Bounded (4M polls): a column that never arrives ends in wrong numbers
-// that the tests catch, not in a hung GPU.
-__device__ __forceinline__ void jsim_spin_published(const double *val_lds)
+// everything in front of it is in LDS -- the helper polls that word; no counter has to be kept by the publishing wave.  Written in
+// assembly so that the loop does not exist for the compiler: as a C loop inside the fully unrolled forward substitution it kept that
+// loop from being unrolled, Jr[] became dynamically indexed and was "promoted" to 100 KB of LDS.  Bounded (4M polls), so that a
+// column that never arrives cannot hang the GPU: the function returns 1 when it gave up (0: published), the helper ORs that into
+// `tmo`, posts it in hb_tmo, and the owner ends the tick with JSIM_HELPER_TIMEOUT.  A helper that has given up once polls every
+// later column once only (`tmo` in: the poll count starts at its limit).
+__device__ __forceinline__ int jsim_spin_published(const double *val_lds, int tmo)
 {
     const unsigned addr = (unsigned)(__UINTPTR_TYPE__)(__attribute__((address_space(3))) const double *)val_lds;
+    const int cnt0 = __builtin_amdgcn_readfirstlane(tmo) ? 0x3fffff : 0;
     int v, cnt, cur;
-    asm volatile("s_mov_b32 %1, 0\n"
+    asm volatile("s_mov_b32 %1, %4\n"
                  "1:\n\t"
                  "ds_read_b32 %0, %3 offset:4\n\t"
                  "s_waitcnt lgkmcnt(0)\n\t"
@@ -317,8 +321,9 @@ __device__ __forceinline__ void jsim_spin_published(const double *val_lds)
                  "s_cbranch_scc1 1b\n"
                  "2:"
                  : "=&v"(v), "=&s"(cnt), "=&s"(cur)
-                 : "v"(addr)
+                 : "v"(addr), "s"(cnt0)
                  : "memory", "scc");
+    return cur == (int)0xbff00000;
 }
 
 // tile row ROW of H = 2 S'QS -> Hm (both triangles); the operand formulas are the one-wave kernel's (S4a below)
@@ -450,6 +455,10 @@ void mpc_step_reg_kernel(const KP Pin, const TickP K, const PreK Q)
     __shared__ __attribute__((aligned(16))) double HL[HLN > PREN ? HLN : PREN];
     double *const Hm = HL;
     constexpr bool HCLR = HELP && !LCA; // the helpers clear R while the owner factors (not where the factor's columns lie on top of H)
+    // .. and where H outlives the owner's read of its rows, the factorisation is split by columns: the owner factors [0, NS), helper 2
+    // takes the right half of every row from H, applies the owner's columns to it as they are published and factors [NS, N)
+    constexpr bool SPLIT = HCLR;
+    constexpr int NS = SPLIT ? ((N / 2) & ~1) : N; // even: no 16-byte pair of a column straddles the split
     double *const Lc = HL + (LCA ? 0 : N * LD); // the factor's columns, unscaled (column k at Lc[k*LDC + .])
     static_assert((N * LD) % 2 == 0, "Lc stays 16-byte aligned");
     __shared__ __attribute__((aligned(16))) double gsv[2 * N]; // Givens (c, s) per column pair, identity outside a sweep
@@ -472,6 +481,7 @@ void mpc_step_reg_kernel(const KP Pin, const TickP K, const PreK Q)
     __shared__ unsigned maskw[MW + 1];
     // HELP: the owner's mailbox (command, scan inputs) and the helpers' answers (three nearest points per helper)
     __shared__ int hb_cmd, hb_ilen;
+    __shared__ int hb_tmo; // a helper's bounded wait for a column ran out in this tick (jsim_spin_published)
     __shared__ __attribute__((aligned(16))) double Jx[HELP ? 64 * (N + 2) : 2];   // rows of the augmented J, helper 1 -> owner
     __shared__ long long hb_s0;
     __shared__ double hb_xy[2], hb_rd[HELP ? 12 : 2];
@@ -559,17 +569,90 @@ void mpc_step_reg_kernel(const KP Pin, const TickP K, const PreK Q)
                 if (hwave == 3) { const double gi = jsim_g_own<T>(tq, lane0, dt); if (lane0 < N) gvc[lane0] = gi; }
             } else if (cmd == HB_JBUILD && hwave == 1) {
                 double Jr[N];
-#define JSIM_J_WAIT(n_) jsim_spin_published(&invc[(n_) - 1])
+                int tmo = 0;
+                // (SPLIT: the columns come faster than this wave takes them with a poll -- an LDS round trip -- in front of each: one poll
+                //  per two columns, for the odd count ahead; "n columns are published" holds at every call as before)
+#define JSIM_J_WAIT(n_) do { if (!SPLIT || (n_) == 1 || !((n_) & 1)) tmo |= jsim_spin_published(&invc[(SPLIT && (n_) + 1 <= N ? (n_) + 1 : (n_)) - 1], tmo); } while (0)
 #include "mpc_step_reg_j.inc"
 #undef JSIM_J_WAIT
 #pragma unroll
                 for (int j = 0; j < N; j += 2) *(double2 *)&Jx[lane0 * (N + 2) + j] = double2{Jr[j], Jr[j + 1]};
-            } else if (cmd == HB_JBUILD && HCLR) {
-                // helpers 2 and 3, idle in this phase: the active-set loop's zeroed R, identity rotations and zero pads.  H is dead (the
-                // owner took its rows before it posted the command) and the owner passes the phase's closing barrier before the loop.
-                for (int e = (hwave - 2) * 64 + lane0; e < N * LD; e += 128) Hm[e] = 0.0;
-                if (hwave == 2 && lane0 < N) { gsv[2 * lane0] = 1.0; gsv[2 * lane0 + 1] = 0.0; }
-                if (hwave == 3 && lane0 < 2) { drow[N + lane0] = 0.0; drow2[N + lane0] = 0.0; dzv[N + lane0] = 0.0; vzv[N + lane0] = 0.0; }
+                if (tmo && lane0 == 0) hb_tmo = 1;
+            } else if (cmd == HB_JBUILD && SPLIT && hwave == 2) {
+                // the right half of the factorisation.  The lane's row of H, columns [NS, N), with the owner's R / Rd corrections (in LDS
+                // before the owner posted the command); H is dead once every lane has its half row -- a wave's LDS operations are
+                // performed in order -- and becomes the active-set loop's zeroed R here (the owner passes the phase's closing barrier
+                // before the loop).
+                if constexpr (SPLIT) { // (discarded elsewhere: N - NS is 0 there)
+#ifdef JSIM_STAMPS /* slots 12 .. 14 of the ego's clock row: helper 2 starts, has applied the owner's columns, has factored its own */
+#define HSTAMP(i) do { if (P.dbg_clk && lane0 == 0) P.dbg_clk[(size_t)ego * 16 + (i)] = (long long)__builtin_readcyclecounter(); } while (0)
+#else
+#define HSTAMP(i) do { } while (0)
+#endif
+                HSTAMP(12);
+                double A2[N - NS];
+                {
+                    const int i = lane0 < N ? lane0 : 0;
+#pragma unroll
+                    for (int j = NS; j < N; ++j) A2[j - NS] = Hm[i * LD + j];
+                    JSIM_STAGE();
+                    for (int e = lane0; e < N * LD / 2; e += 64) *(double2 *)&Hm[2 * e] = double2{0.0, 0.0};
+                }
+                // columns k < NS, as the owner publishes them: A[j] -= (A[k] / c_k) c_j on j >= NS, with the owner's expression for the
+                // multiplier on what it published (the lane's own entry of column k, the pivot's reciprocal root).  Lanes < k read an
+                // entry nobody wrote: their rows of the factor are not used from column k on.
+                int tmo = 0;
+                {
+                    JSIM_OPAQUE_ZERO(zs_);
+                    const double *const LcS = Lc + zs_, *const invS = invc + zs_;
+                    const int i = lane0 < N ? lane0 : 0;
+                    // two columns per poll (NS is even): the pair (k, k + 1) is read once the pivot of k + 1 is there, the next pair's
+                    // poll and reads stand in front of this pair's FMAs
+                    double2 cs[2][2][(N - NS) / 2];
+                    double own[2][2], invs[2][2];
+#define JSIM_S_READ(b_, k_)                                                                                                    \
+    {                                                                                                                          \
+        tmo |= jsim_spin_published(&invc[(k_) + 1], tmo);                                                                      \
+        _Pragma("unroll") for (int c = 0; c < 2; ++c) {                                                                        \
+            _Pragma("unroll") for (int j = NS; j < N; j += 2) cs[b_][c][(j - NS) / 2] = *(const double2 *)&LcS[((k_) + c) * LDC + j]; \
+            own[b_][c] = LcS[((k_) + c) * LDC + i]; invs[b_][c] = invS[(k_) + c];                                              \
+        }                                                                                                                      \
+    }
+                    JSIM_S_READ(0, 0)
+#pragma unroll
+                    for (int k = 0; k < NS; k += 2) {
+                        if (k + 2 < NS) JSIM_S_READ(((k >> 1) + 1) & 1, k + 2)
+                        JSIM_STAGE();
+#pragma unroll
+                        for (int c = 0; c < 2; ++c) {
+                            const double tk = own[(k >> 1) & 1][c] * (invs[(k >> 1) & 1][c] * invs[(k >> 1) & 1][c]);
+#pragma unroll
+                            for (int j = NS; j < N; j += 2) {
+                                const double2 c2 = cs[(k >> 1) & 1][c][(j - NS) / 2];
+                                A2[j - NS] = fma(-tk, c2.x, A2[j - NS]); JSIM_PIN(A2[j - NS]);
+                                A2[j + 1 - NS] = fma(-tk, c2.y, A2[j + 1 - NS]); JSIM_PIN(A2[j + 1 - NS]);
+                            }
+                        }
+                        JSIM_STAGE();
+                    }
+#undef JSIM_S_READ
+                }
+                if (tmo && lane0 == 0) hb_tmo = 1;
+                HSTAMP(13);
+#define JSIM_CH_K0 NS
+#define JSIM_CH_KE N
+#define JSIM_CH_A(j_) A2[(j_) - NS]
+#include "mpc_step_reg_chol.inc"
+#undef JSIM_CH_K0
+#undef JSIM_CH_KE
+#undef JSIM_CH_A
+                HSTAMP(14);
+#undef HSTAMP
+                }
+            } else if (cmd == HB_JBUILD && HCLR && hwave == 3) {
+                // idle in this phase: the active-set loop's identity rotations and zero pads
+                if (lane0 < N) { gsv[2 * lane0] = 1.0; gsv[2 * lane0 + 1] = 0.0; }
+                if (lane0 < 2) { drow[N + lane0] = 0.0; drow2[N + lane0] = 0.0; dzv[N + lane0] = 0.0; vzv[N + lane0] = 0.0; }
             }
             __syncthreads();
         }
@@ -582,6 +665,7 @@ void mpc_step_reg_kernel(const KP Pin, const TickP K, const PreK Q)
         dc = (-P.smax > dc) ? -P.smax : dc;
         wtan = tan(dc);
     }
+    unsigned it_sum = 0; // active-set iterations of this launch's ticks, both S5 exits: added to K.work / K.iters once, in the last tick
     for (int tk = 0; tk < K.n_ticks; ++tk) {
     // WPE = 2 (256 registers): the state carried from tick to tick is the same in every lane -- say so, and it lives in scalar
     // registers (their overflow goes to single lanes of a spill VGPR, 1/64 of what a uniform value costs in a vector register)
@@ -935,13 +1019,13 @@ void mpc_step_reg_kernel(const KP Pin, const TickP K, const PreK Q)
         }
         LDS_SYNC();
 #pragma unroll
-        for (int j = 0; j < N; ++j) A[j] = Hm[i * LD + j];
+        for (int j = 0; j < NS; ++j) A[j] = Hm[i * LD + j]; // (SPLIT: the right half of the row is helper 2's)
     }
     if (P.dbg_g && lane < N) P.dbg_g[(size_t)ego * N + lane] = gi_own;
     if (P.dbg_H && lane < N) {
         double *Hd = P.dbg_H + (size_t)ego * N * N + (size_t)lane * N;
 #pragma unroll
-        for (int j = 0; j < N; ++j) Hd[j] = A[j];
+        for (int j = 0; j < N; ++j) Hd[j] = j < NS ? A[j] : Hm[lane * LD + j];
     }
     const double gmax = wmax_dpp(fabs(gi_own));
 
@@ -949,74 +1033,21 @@ void mpc_step_reg_kernel(const KP Pin, const TickP K, const PreK Q)
     STAMP(6);
     LANE_FENCE();
     // ------------------------------------------------------------------ S4b: Cholesky, right-looking, column by column through LDS
-    // Column k (entries j >= k, unscaled: c_j = A^(k)[j][k]) goes to Lc[k][.]; every lane reads it back as a broadcast
-    // vector and eliminates:  A[j] -= (A[k] / c_k) c_j ;  L[.][k] = c / sqrt(c_k).  The same columns then drive the
-    // forward substitutions below -- no row broadcasts (two v_readlane per operand), no dump of L.  Measured against the
-    // in-register version with v_readlane broadcasts: see DESIGN.md.
-    // Look-ahead of one column: as soon as column k's entry c_{k+1} has updated A[k+1], column k + 1 is written out and
-    // its pivot's reciprocal root started -- its LDS round trip and that chain then run under the rest of column k's FMAs.
-    if (HELP) { // helper 1 starts the forward substitutions beside this factorisation
+    // (the column loop: mpc_step_reg_chol.inc.)  The same columns then drive the forward substitutions below -- no row broadcasts (two
+    // v_readlane per operand), no dump of L.  Measured against the in-register version with v_readlane broadcasts: see DESIGN.md.
+    // SPLIT: the owner factors columns [0, NS) of all rows and goes to the phase's closing barrier; helper 2 has the rest.
+    if (HELP) { // helper 1 starts the forward substitutions beside this factorisation (SPLIT: helper 2 the factor's right half)
         if (lane < N) invc[lane] = -1.0;     // (invc[k] != -1: column k is published)
-        if (lane == 0) hb_cmd = HB_JBUILD;
+        if (lane == 0) { hb_tmo = 0; hb_cmd = HB_JBUILD; }
         __syncthreads();
     }
-    {
-        JSIM_OPAQUE_ZERO(zc_);
-        const double *const LcC = Lc + zc_;
-        double inv, tmul;
-        {
-            if (lane < N) Lc[lane] = A[0];
-            double ck = rdlane(A[0], 0); // the pivot travels by v_readlane: its rsqrt chain overlaps the LDS round trip
-            if (!(ck > 0.0)) ck = 1e-300;
-            inv = fast_rsqrt(ck);
-            tmul = A[0] * (inv * inv);
-        }
-#pragma unroll
-        for (int k = 0; k < N; ++k) {
-            LDS_SYNC(); // column k is in LDS
-            const int j0 = k & ~1;
-            const int nch = (N - j0 + CCH - 1) / CCH;
-            double2 cb[2][CCH / 2];
-#pragma unroll
-            for (int j = j0; j < j0 + CCH && j < N; j += 2) cb[0][(j - j0) / 2] = *(const double2 *)&LcC[k * LDC + j];
-            if (HELP) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");   // (column k is written BEFORE its pivot: helper 1 polls the pivot;
-            if (lane == k) invc[k] = inv;                                      //  a wave's LDS operations are performed in order, the compiler keeps this one)
-            const double tk = tmul;
-            if (k + 1 < N) { // the one update the next column needs, then publish it
-                JSIM_STAGE();
-                // (even k: only .y of the pair that holds column entry k + 1 is used; left alone, that read is narrowed to 8 bytes and every
-                //  read behind it re-merged into 8-byte-aligned pairs, each with an address add of its own -- both halves count as used here)
-                if (!(k & 1)) JSIM_PIN_PAIR(cb[0][0]);
-                const double cn = ((k + 1) & 1) ? cb[0][(k + 1 - j0) / 2].y : cb[0][(k + 1 - j0) / 2].x;
-                A[k + 1] = fma(-tk, cn, A[k + 1]);
-                JSIM_PIN(A[k + 1]);
-                if (lane >= k + 1 && lane < N) Lc[(k + 1) * LDC + lane] = A[k + 1];
-                double ck = rdlane(A[k + 1], k + 1);
-                if (!(ck > 0.0)) ck = 1e-300;
-                inv = fast_rsqrt(ck);
-                tmul = A[k + 1] * (inv * inv);
-            }
-#pragma unroll
-            for (int c = 0; c < nch; ++c) {
-                const int h = j0 + c * CCH;
-                if (c + 1 < nch) {
-#pragma unroll
-                    for (int j = h + CCH; j < h + 2 * CCH && j < N; j += 2) cb[(c + 1) & 1][(j - h - CCH) / 2] = *(const double2 *)&LcC[k * LDC + j];
-                }
-                // behind this chunk's reads: the next chunk's; behind the first chunk's also the pivot and column k + 1 (written above).
-                // (In front of the stage boundary: behind it the scheduler moves the chunk's FMAs above the wait.)
-                if ((CHW & 1) && k + 1 < N) jsim_chunk_wait((c + 1 < nch ? ((h + 2 * CCH < N ? h + 2 * CCH : N) - (h + CCH)) / 2 : 0) + (c == 0 ? 2 : 0));
-                JSIM_STAGE();
-#pragma unroll
-                for (int j = h; j < h + CCH && j < N; j += 2) {
-                    const double2 c2 = cb[c & 1][(j - h) / 2];
-                    if (j > k + 1) { A[j] = fma(-tk, c2.x, A[j]); JSIM_PIN(A[j]); }
-                    if (j + 1 > k + 1) { A[j + 1] = fma(-tk, c2.y, A[j + 1]); JSIM_PIN(A[j + 1]); }
-                }
-                JSIM_STAGE();
-            }
-        }
-    }
+#define JSIM_CH_K0 0
+#define JSIM_CH_KE NS
+#define JSIM_CH_A(j_) A[(j_)]
+#include "mpc_step_reg_chol.inc"
+#undef JSIM_CH_K0
+#undef JSIM_CH_KE
+#undef JSIM_CH_A
     LDS_SYNC();
 
     STAMP(7);
@@ -1033,6 +1064,14 @@ void mpc_step_reg_kernel(const KP Pin, const TickP K, const PreK Q)
     } else { // helper 1 has them (and w in wvc): one barrier, then this lane's row from LDS
         __syncthreads();
         hp = 3;
+        if (__builtin_amdgcn_readfirstlane(hb_tmo)) { // a helper gave up waiting for a column: neither the factor nor J can be trusted
+            status = JSIM_HELPER_TIMEOUT;
+            if (lane == 0) {
+                P.status[ego] = status;
+                if (P.n_iter) P.n_iter[ego] = it_base;
+            }
+            break;
+        }
 #pragma unroll
         for (int j = 0; j < N; j += 2) { const double2 v2 = *(const double2 *)&Jx[lane * (N + 2) + j]; Jr[j] = v2.x; Jr[j + 1] = v2.y; }
     }
@@ -1605,9 +1644,8 @@ void mpc_step_reg_kernel(const KP Pin, const TickP K, const PreK Q)
             P.status[ego] = status;
             P.target_ind[ego] = tind;
             if (P.n_iter) P.n_iter[ego] = it_base + iters;
-            if (K.work) K.work[ego] += (unsigned)iters;
-            if (K.iters) K.iters[ego] += (unsigned long long)iters;
         }
+        it_sum += (unsigned)iters;
         break;
     }
     if (lane < MW) maskw[lane] = 0u;
@@ -1661,9 +1699,8 @@ void mpc_step_reg_kernel(const KP Pin, const TickP K, const PreK Q)
         P.status[ego] = JSIM_OK;
         P.target_ind[ego] = tind;
         if (P.n_iter) P.n_iter[ego] = it_base + iters;
-        if (K.work) K.work[ego] += (unsigned)iters;
-        if (K.iters) K.iters[ego] += (unsigned long long)iters;
     }
+    it_sum += (unsigned)iters;
     STAMP(11);
     } while (0);
     if (HELP) // an early exit left the helpers waiting for this tick's commands
@@ -1732,6 +1769,13 @@ void mpc_step_reg_kernel(const KP Pin, const TickP K, const PreK Q)
         }
     }
     LDS_SYNC(); // LDS scratch is reused by the next tick
+    // One read-modify-write per launch and counter: in every tick's S5 each put a wait for all outstanding stores on the owner's path.
+    // (In the last tick, not behind the loop: there the two pointers stay live across the loop, and the one-wave kernels then keep
+    //  their parameters in spill lanes -- 800 v_readlane more in <15, false, 1, false> -- instead of loading them where a tick uses them.)
+    if (tk + 1 >= K.n_ticks && lane == 0) {
+        if (K.work) K.work[ego] += it_sum;
+        if (K.iters) K.iters[ego] += (unsigned long long)it_sum;
+    }
     } // tick loop
     if (HELP) {
         if (lane0 == 0) hb_cmd = HB_EXIT;

@@ -150,6 +150,7 @@ __global__ __launch_bounds__(256, JSIM_REG4_MINW) void mpc_step_reg4_kernel(cons
     double2 goal_xy = double2{0.0, 0.0};
     if (advance) { const jsim_d2v gq = ((JSIM_GAS const jsim_d2v *)Pv.pxy)[gp(Pv.poff)[pid + 1] - 1]; goal_xy = double2{uni(gq.x), uni(gq.y)}; }
 
+    unsigned it_sum = 0; // active-set iterations of this launch's ticks, both S5 exits: added to work / iters behind the loop
     for (int tk = 0; tk < n_ticks; ++tk) {
     // (the lane id is re-derived from the execution mask count instead of keeping threadIdx.x alive across the kernel)
     // (.. from an opaque all-ones mask, or the count is computed once and kept alive all the same)
@@ -1253,9 +1254,8 @@ __global__ __launch_bounds__(256, JSIM_REG4_MINW) void mpc_step_reg4_kernel(cons
             gp(Pv.status)[ego] = status;
             gp(Pv.target_ind)[ego] = tind;
             if (Pv.n_iter) gp(Pv.n_iter)[ego] = it_base + iters;
-            if (Kv.work) gp(Kv.work)[ego] += (unsigned)iters;
-            if (Kv.iters) gp(Kv.iters)[ego] += (unsigned long long)iters;
         }
+        it_sum += (unsigned)iters;
         break;
     }
     if (gl < MW) maskw[gl] = 0u;
@@ -1315,9 +1315,8 @@ __global__ __launch_bounds__(256, JSIM_REG4_MINW) void mpc_step_reg4_kernel(cons
         gp(Pv.status)[ego] = JSIM_OK;
         gp(Pv.target_ind)[ego] = tind;
         if (Pv.n_iter) gp(Pv.n_iter)[ego] = it_base + iters;
-        if (Kv.work) gp(Kv.work)[ego] += (unsigned)iters;
-            if (Kv.iters) gp(Kv.iters)[ego] += (unsigned long long)iters;
     }
+    it_sum += (unsigned)iters;
     STAMP2(11);
     } while (0);
 
@@ -1379,6 +1378,10 @@ __global__ __launch_bounds__(256, JSIM_REG4_MINW) void mpc_step_reg4_kernel(cons
     }
     BLOCK_SYNC(); // LDS scratch is reused by the next tick
     } // tick loop
+    if (gl == 0) { // one read-modify-write per launch (see mpc_step_reg.inc)
+        if (Kv.work) gp(Kv.work)[ego] += it_sum;
+        if (Kv.iters) gp(Kv.iters)[ego] += (unsigned long long)it_sum;
+    }
     if (advance && gl == 0) {
         gp(Kv.x0w)[4 * ego] = sx; gp(Kv.x0w)[4 * ego + 1] = sy; gp(Kv.x0w)[4 * ego + 2] = sv; gp(Kv.x0w)[4 * ego + 3] = syaw;
         gp(Kv.di_ai)[2 * ego] = di_prev;

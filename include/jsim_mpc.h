@@ -79,7 +79,10 @@ typedef struct jsim_cfg {
 
 typedef struct jsim_ctx jsim_ctx;
 
-enum { JSIM_OK = 0, JSIM_INFEASIBLE = 1, JSIM_NEAREST_ANOMALY = 2 };
+/* Per-ego status of a step / tick.  3: the ego has no path (path_len < 1).  JSIM_HELPER_TIMEOUT: an internal fault of the kernels with
+ * helper wavefronts -- a helper's bounded wait for a column of the factor ran out; the tick is treated like a failed solve (nothing
+ * of the controller is updated, the loops brake with MAX_DECEL), and the Python layer raises JsimError when it reads the status. */
+enum { JSIM_OK = 0, JSIM_INFEASIBLE = 1, JSIM_NEAREST_ANOMALY = 2, JSIM_HELPER_TIMEOUT = 4 };
 
 int jsim_abi_version(void);
 const char *jsim_last_error(const jsim_ctx *ctx);

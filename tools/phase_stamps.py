@@ -50,6 +50,12 @@ for tick in range(30):
     itacc = np.concatenate([itacc, eng.n_iter.cpu().numpy()[ok]])
 it = eng.n_iter.cpu().numpy()
 tot = acc.sum(axis=1)
+hc = c[ok]
+if np.all(hc[:, 12:15] > 0):   # the column-split kernels: helper 2's stamps of the last tick against the owner's (6: command posted, 7: its columns done, 8: closing barrier passed)
+    for nme, a, b in (("owner: its columns", 6, 7), ("owner: at the closing barrier", 7, 8), ("helper 2: starts after the command", 6, 12),
+                      ("helper 2: the owner's columns applied", 12, 13), ("helper 2: behind the owner's last column", 7, 13),
+                      ("helper 2: its own columns", 13, 14), ("helper 1 and the barrier behind helper 2", 14, 8)):
+        print(f"  split {nme:42s} median {np.median(hc[:, b] - hc[:, a]):8.0f} cyc")
 print(f"T={T} B={B}: total cycles/ego median {np.median(tot):.0f} (p10 {np.percentile(tot,10):.0f}, p90 {np.percentile(tot,90):.0f}); "
       f"last-tick mean n_iter {it.mean():.1f}")
 for k, nme in enumerate(names):
