@@ -11,7 +11,8 @@
 //                       (see VS below): v_t by a prefix scan over the acceleration lanes, the row formed on demand;
 //   * the entering row is published through LDS and read back as a broadcast vector (bursts of ds_read_b128 behind
 //     scheduling barriers); reductions, arg-max / arg-min use DPP (quad_perm / row_mirror) + v_readlane, not ds_bpermute;
-//   * R (strict upper triangle) lives in LDS, the back substitution runs on v_readlane broadcasts of the running solution;
+//   * R (strict upper triangle) lives in LDS, the back substitution runs on broadcasts of the running solution: the 64-bit DPP
+//     row broadcast inside the first 16-lane row (columns below 16), v_readlane from column 16 on;
 //   * PRE instantiations run the scenario loop's glue (loop_pre_tick.inc) inside the tick loop.
 
 template <int CTRL>
@@ -24,6 +25,33 @@ __device__ __forceinline__ double dpp_f64(double v) // all source lanes valid fo
 }
 template <int CTRL>
 __device__ __forceinline__ int dpp_i32(int v) { return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xf, 0xf, true); }
+
+// Two back-substitution steps on the 64-bit row broadcast (DESIGN.md section 5, fact 8).  One step is
+//     v += (lane J of the caller's 16-lane row: v) * m,   m = R[k][J] * -(1 / R[k][k])  in lane k,
+// ONE v_fmac_f64 with a DPP multiplicand (gfx90a and later; row_newbcast is the only DPP control 64-bit operations have) where the
+// v_readlane form needs two v_readlane, an s_nop and the FMA.  A DPP source must not be read in the two issue slots after the vector
+// instruction that wrote it, and the compiler's hazard pass does not look inside an asm statement, so the statement carries its own
+// padding: both steps' products stand in front of the first step (two vector instructions behind whatever wrote v last), s_nop 1 in
+// front of the second -- five slots for two steps.  r_hi, r_lo: R[k][J], R[k][J - 1].  Nothing of
+// this may be reordered or sunk into a lane-masked region (a DPP read from a lane that EXEC masks off returns 0, fact 4): volatile.
+template <int J>
+__device__ __forceinline__ void bs_step2(double &v, double r_hi, double r_lo, double rdiag)
+{
+    static_assert(J >= 1 && J < 16, "row_newbcast selects a lane of the 16-lane row");
+    double m_hi, m_lo; // (outputs of their own: tied to r_hi / r_lo, halves of one 16-byte read, each pair costs a register copy)
+    asm volatile("v_mul_f64 %1, %3, -%5\n\t"
+                 "v_mul_f64 %2, %4, -%5\n\t"
+                 "v_fmac_f64_dpp %0, %0, %1 row_newbcast:%6 row_mask:0xf bank_mask:0xf\n\t"
+                 "s_nop 1\n\t"
+                 "v_fmac_f64_dpp %0, %0, %2 row_newbcast:%7 row_mask:0xf bank_mask:0xf"
+                 : "+v"(v), "=&v"(m_hi), "=&v"(m_lo) : "v"(r_hi), "v"(r_lo), "v"(rdiag), "n"(J), "n"(J - 1));
+}
+template <int LO, int J>
+__device__ __forceinline__ void bs_steps(double &v, const double *r, double rdiag) // steps LO + J, LO + J - 1, .. LO on r[J] .. r[0] (J odd)
+{
+    bs_step2<LO + J>(v, r[J], r[J - 1], rdiag);
+    if constexpr (J > 1) bs_steps<LO, J - 2>(v, r, rdiag);
+}
 
 #define DPP_QP_1032 0xB1 /* quad_perm [1,0,3,2] */
 #define DPP_QP_2301 0x4E /* quad_perm [2,3,0,1] */
@@ -1390,6 +1418,14 @@ void mpc_step_reg_kernel(const KP Pin, const TickP K, const PreK Q)
             GSTAMP(2);
             // z = Jhat2 d2  and  y = Jhat2 v  (y only matters when the row is added)
             double z0 = 0.0, z1 = 0.0, y0 = 0.0, y1 = 0.0;
+            // The back substitution behind the dots takes its columns below BSD through the row broadcast (one 16-lane row).  One wave
+            // per SIMD: their entries of R from column BSA_LO up are read ahead, under the last chunk of the dots, the lower ones when
+            // the steps start -- that round trip passes under the upper steps.  (All sixteen ahead: ~40 more AGPR moves per tick around
+            // the loop in the headline kernel, and slower; two waves per SIMD have no registers for any: they read in place.)
+            constexpr int BSD = 16, BSA_LO = 8;
+            constexpr bool BSA = (WPE == 1);
+            const int rl = lane < N ? lane : 0; // this lane's row of R
+            double Rr[BSD];
             {
                 // chunks of ZC columns, the next chunk's broadcast reads in flight while this one's FMAs issue: the row
                 // stays in VGPRs (a 40-column burst buffer pushed half of it into AGPRs, two moves per use)
@@ -1407,8 +1443,12 @@ void mpc_step_reg_kernel(const KP Pin, const TickP K, const PreK Q)
                             vzb[(c + 1) & 1][(j - h - ZC) / 2] = *(const double2 *)&vzv[j];
                         }
                     }
+                    if (BSA && c == NCH - 1) { // in flight under this chunk's FMAs
+#pragma unroll
+                        for (int j = BSA_LO; j < BSD; ++j) Rr[j] = Rm[rl * LD + j];
+                    }
                     // (the first chunk was read just above: its waits stay the compiler's, one per pair as the reads come in)
-                    if ((CHW & 4) && c > 0) jsim_chunk_wait(c + 1 < NCH ? (h + 2 * ZC < N ? h + 2 * ZC : N) - (h + ZC) : 0); // behind it: the next chunk's d2 and v pairs
+                    if ((CHW & 4) && c > 0) jsim_chunk_wait(c + 1 < NCH ? (h + 2 * ZC < N ? h + 2 * ZC : N) - (h + ZC) : (BSA ? (BSD - BSA_LO) / 2 : 0)); // behind it: the next chunk's d2 and v pairs, or Rr (two entries a read)
                     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                     for (int j = h; j < h + ZC && j < N; j += 2) {
@@ -1423,11 +1463,20 @@ void mpc_step_reg_kernel(const KP Pin, const TickP K, const PreK Q)
             const double z = z0 + z1, y = y0 + y1;
             GSTAMP(3);
             // r = R^-1 d1 : back substitution, lane k = row k of R scaled by 1/R[k][k] at load, so one step is
-            // r_j = (lane j's running value) ; running -= Rhat[:, j] r_j  -- two v_readlane and one FMA, no masks
-            // (zeros below the diagonal / right of column q make the other lanes and steps no-ops).
+            // r_j = (lane j's running value) ; running -= Rhat[:, j] r_j  -- no masks (zeros below the diagonal / right of
+            // column q make the other lanes and steps no-ops).
+            //   * columns j >= 16 (blocks 2 and up, entered only while q > 16): two v_readlane bring r_j into a scalar pair, one FMA;
+            //   * columns j < 16, always all sixteen: ONE fused FMA whose multiplicand is the running value through the 64-bit
+            //     row broadcast (bs_step2 above) -- every 16-lane row receives its own lane j; the consumers of r_j (lanes k < j) sit
+            //     in row 0 beside lane j, the lanes of rows 1-3 hold a zero multiplier for these columns (below the diagonal, or
+            //     1/R[k][k] = 0 beyond q) and keep their value exactly, as every lane does in a step beyond q.  Same operands in the
+            //     same order j = q - 1 .. 0 as the v_readlane form: the same bits.  Their entries of R are on their way or here
+            //     (Rr, above), so no LDS round trip stands in front of them, and no branch in front of them either: the compiler
+            //     flattens a nest of q > 8k tests into a row of compare-and-branch pairs, ~40 cycles each taken or not, and eight
+            //     steps that change nothing cost 20 slots.  (Reading Rr at the top of the iteration and forming the products under
+            //     the dots' first reads was measured: 100 cycles less here, 160 more in front of the dots -- DESIGN.md section 6.)
             double rloc = dloc * rdiag;
             {
-                const int rl = lane < N ? lane : 0;
                 constexpr int NB = (N + 7) / 8;
 #define BS_BLOCK(blk)                                                                                          \
     {                                                                                                          \
@@ -1437,30 +1486,37 @@ void mpc_step_reg_kernel(const KP Pin, const TickP K, const PreK Q)
         _Pragma("unroll") for (int j = jhi; j >= jlo; --j) rloc = fma(-Rb[j - jlo], rdlane(rloc, j), rloc);    \
     }
                 // highest block first; a uniform branch costs ~40 cycles taken or not, so the tests are nested
-                static_assert(NB <= 8, "extend the block nest");
-                if (q > 0) {
-                    if (NB > 1 && q > 8) {
-                        if (NB > 2 && q > 16) {
-                            if (NB > 3 && q > 24) {
-                                if (NB > 4 && q > 32) {
-                                    if (NB > 5 && q > 40) {
-                                        if (NB > 6 && q > 48) {
-                                            if (NB > 7 && q > 56) BS_BLOCK(7 < NB ? 7 : 0)
-                                            BS_BLOCK(6 < NB ? 6 : 0)
-                                        }
-                                        BS_BLOCK(5 < NB ? 5 : 0)
-                                    }
-                                    BS_BLOCK(4 < NB ? 4 : 0)
+                static_assert(NB > 2 && NB <= 8, "extend the block nest");
+                if (q > 16) {
+                    if (NB > 3 && q > 24) {
+                        if (NB > 4 && q > 32) {
+                            if (NB > 5 && q > 40) {
+                                if (NB > 6 && q > 48) {
+                                    if (NB > 7 && q > 56) BS_BLOCK(7 < NB ? 7 : 0)
+                                    BS_BLOCK(6 < NB ? 6 : 0)
                                 }
-                                BS_BLOCK(3 < NB ? 3 : 0)
+                                BS_BLOCK(5 < NB ? 5 : 0)
                             }
-                            BS_BLOCK(2 < NB ? 2 : 0)
+                            BS_BLOCK(4 < NB ? 4 : 0)
                         }
-                        BS_BLOCK(1 < NB ? 1 : 0)
+                        BS_BLOCK(3 < NB ? 3 : 0)
                     }
-                    BS_BLOCK(0)
+                    BS_BLOCK(2)
                 }
 #undef BS_BLOCK
+                if (BSA) {
+#pragma unroll
+                    for (int j = 0; j < BSA_LO; ++j) Rr[j] = Rm[rl * LD + j];
+                    bs_steps<0, BSD - 1>(rloc, Rr, rdiag);
+                } else { // read in place, eight columns at a time
+                    double Rb[8];
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) Rb[j] = Rm[rl * LD + 8 + j];
+                    bs_steps<8, 7>(rloc, Rb, rdiag);
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) Rb[j] = Rm[rl * LD + j];
+                    bs_steps<0, 7>(rloc, Rb, rdiag);
+                }
             }
             GSTAMP(4);
             // dual ratio test: min over the working set of lam_k / r_k (r_k > 0); the step keeps its upper 57 bits and the

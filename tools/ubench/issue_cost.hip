@@ -123,6 +123,23 @@ KERNEL(k_wait_per_chunk, double p_ = 6.0; unsigned z_ = 0;,
                          WC_PAIR("", 84:85, 86:87, 4, 5) WC_PAIR("", 88:89, 90:91, 6, 7) WC_OPS);) a += p_;)
 KERNEL(k_wait_satisfied, , REP16(asm volatile("s_waitcnt lgkmcnt(0)\n s_waitcnt lgkmcnt(0)\n s_waitcnt lgkmcnt(0)\n s_waitcnt lgkmcnt(0)");))
 KERNEL(k_snop, , REP16(asm volatile("s_nop 0\n s_nop 0\n s_nop 0\n s_nop 0");))
+// One back-substitution step, as a dependent chain of 16 (profiles/r23_backsub_dpp.txt): the running value a, lane j's a as the
+// multiplicand, a multiplier per lane.  (a) the v_readlane form, compiler-generated: two v_readlane, the readlane-to-VALU padding,
+// the FMA with the scalar pair; (b) a 64-bit DPP move (row_newbcast is the only control a 64-bit operation has) and the FMA;
+// (c) the FMA with the DPP multiplicand itself -- a DPP source wants two slots behind the vector instruction that wrote it, and
+// inside an asm statement the padding is the author's; (d) (c) with the multiplier's product between the steps, one slot of
+// padding left; (e) what csrc/mpc_step_reg.inc ships: two products, a step, s_nop 1, a step.
+#define BS_A(j) a = fma(rdl(a, j), b, a);
+KERNEL(k_bs_readlane, , BS_A(15) BS_A(14) BS_A(13) BS_A(12) BS_A(11) BS_A(10) BS_A(9) BS_A(8) BS_A(7) BS_A(6) BS_A(5) BS_A(4) BS_A(3) BS_A(2) BS_A(1) BS_A(0))
+#define BS_B(j) asm volatile("s_nop 1\n v_mov_b64_dpp %1, %0 row_newbcast:" #j " row_mask:0xf bank_mask:0xf\n v_fma_f64 %0, %1, %2, %0" : "+v"(a), "=&v"(t_) : "v"(b));
+KERNEL(k_bs_dpp_mov, double t_;, BS_B(15) BS_B(14) BS_B(13) BS_B(12) BS_B(11) BS_B(10) BS_B(9) BS_B(8) BS_B(7) BS_B(6) BS_B(5) BS_B(4) BS_B(3) BS_B(2) BS_B(1) BS_B(0))
+#define BS_C(j) asm volatile("s_nop 1\n v_fmac_f64_dpp %0, %0, %1 row_newbcast:" #j " row_mask:0xf bank_mask:0xf" : "+v"(a) : "v"(b));
+KERNEL(k_bs_dpp_fused, , BS_C(15) BS_C(14) BS_C(13) BS_C(12) BS_C(11) BS_C(10) BS_C(9) BS_C(8) BS_C(7) BS_C(6) BS_C(5) BS_C(4) BS_C(3) BS_C(2) BS_C(1) BS_C(0))
+#define BS_D(j) asm volatile("v_mul_f64 %1, %2, -%3\n s_nop 0\n v_fmac_f64_dpp %0, %0, %1 row_newbcast:" #j " row_mask:0xf bank_mask:0xf" : "+v"(a), "=&v"(t_) : "v"(c), "v"(b));
+KERNEL(k_bs_dpp_fused_mul, double t_;, BS_D(15) BS_D(14) BS_D(13) BS_D(12) BS_D(11) BS_D(10) BS_D(9) BS_D(8) BS_D(7) BS_D(6) BS_D(5) BS_D(4) BS_D(3) BS_D(2) BS_D(1) BS_D(0))
+#define BS_E(j, i) asm volatile("v_mul_f64 %1, %3, -%5\n v_mul_f64 %2, %4, -%5\n v_fmac_f64_dpp %0, %0, %1 row_newbcast:" #j " row_mask:0xf bank_mask:0xf\n s_nop 1\n" \
+                                "v_fmac_f64_dpp %0, %0, %2 row_newbcast:" #i " row_mask:0xf bank_mask:0xf" : "+v"(a), "=&v"(t_), "=&v"(u_) : "v"(c), "v"(d), "v"(b));
+KERNEL(k_bs_dpp_pairs, double t_; double u_;, BS_E(15, 14) BS_E(13, 12) BS_E(11, 10) BS_E(9, 8) BS_E(7, 6) BS_E(5, 4) BS_E(3, 2) BS_E(1, 0))
 typedef double v4d_ __attribute__((ext_vector_type(4)));
 #define MFMA1 acc_ = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc_, 0, 0, 0);
 KERNEL(k_mfma_f64, v4d_ acc_; acc_[0] = 0.0; acc_[1] = 0.0; acc_[2] = 0.0; acc_[3] = 0.0;, REP16(MFMA1) a += acc_[0];)
@@ -151,6 +168,9 @@ int main()
         {"v_mfma_f64_16x16x4 dependent", k_mfma_f64, 16, "instr"},
         {"8 x ds_read_b128, 8 x (wait 7..0 + 2 fma_f64)", k_wait_per_pair, 4, "group"}, {"8 x ds_read_b128, 1 wait, 16 fma_f64", k_wait_per_chunk, 4, "group"},
         {"s_waitcnt lgkmcnt(0), nothing outstanding", k_wait_satisfied, 64, "instr"}, {"s_nop 0", k_snop, 64, "instr"},
+        {"backsubst step (a) 2 readlane + pad + fma", k_bs_readlane, 16, "step"}, {"backsubst step (b) s_nop 1 + mov_b64_dpp + fma", k_bs_dpp_mov, 16, "step"},
+        {"backsubst step (c) s_nop 1 + fmac_f64_dpp", k_bs_dpp_fused, 16, "step"}, {"backsubst step (d) mul + s_nop 0 + fmac_f64_dpp", k_bs_dpp_fused_mul, 16, "step"},
+        {"backsubst step (e) pairs: 2 mul, fmac_dpp, s_nop 1, fmac_dpp", k_bs_dpp_pairs, 16, "step"},
     };
     const int iters = 2000;
     for (int nb : {1, 1024}) {
