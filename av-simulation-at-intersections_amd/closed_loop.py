@@ -40,6 +40,7 @@ class Recorder:
         self.groups = None if groups is None else np.array(groups, dtype=np.int32)   # InteractingLoop's group offsets: whose mate is who
         self.superseded = False          # set when a later loop on the same engine registers its own recorder (or none)
         self.glue = None                 # a _GlueLoop's frame_window, margin, n_steps, mode and interacting (cutoffs()); None: no glue
+        self._tracking_table = None      # the engine's paths as tracking() takes them, made at its first call
         _register_recorder(eng, self)
 
     def _record_obstacles(self, get: torch.Tensor):
@@ -341,6 +342,64 @@ class Recorder:
                    _ptr(clear), _ptr(who), _ptr(hit), _ptr(off_tick))
         return {"clear": clear, "who": who, "hit": hit, "off_tick": off_tick, "margin": margin, "include_hidden": bool(include_hidden),
                 "ego_shape": tuple(float(v) for v in ego), "set_of": sof}
+
+    def tracking(self, paths=None, path_id=None) -> dict:
+        """Every recorded pose projected onto a path (jsim_loop_eval_tracking): how far along its route each
+        ego was on every tick, how far beside it and how far off its heading -- what plot_trajectories_comparison of
+        main/scenarios/mpc_sensitivity_analysis*.py draws against the reference trajectory -- computed in one launch from the records.
+        The pose of tick k is the record itself (History.x[k], .y[k], .yaw[k]: after the plant step).
+
+        paths: a list of (M, >= 3) arrays x, y, yaw (M >= 1; the yaw as the controller sees it: unwrapped, as engine.paths hold it),
+        default: the engine's paths (their device copy is made once and kept on the recorder); path_id: each ego's path, one index or
+        [B], default: the engine's path_id (with paths given: required unless there is one path).  Any paths will do: the original
+        route of a fork, a lane centreline.  The context's own tables are not read, so a superseded recorder gives the same result.
+        Returns numpy arrays [n][B]: idx (calc_nearest_index(state, cx, cy, 0) of main/lib/trajectories.py:89-97, relative to the
+        path), seg (the segment that holds the foot), s (arc length of the foot), d (signed lateral offset, left of the direction of
+        travel positive; |d| is the distance to the polyline), e_yaw (heading error wrapped to [-pi, pi)); -1 / NaN for a pose that
+        is not finite; at the slot of an episode's first tick ep_i [n][B][2] (history.TRK_INT: ticks, d_max_tick) and ep_d [n][B][5]
+        (history.TRK_DOUBLE: d_max, d2_mean, yaw_max, s_first, s_last), -1 / NaN elsewhere; arc (a list: the arc length at every
+        point of every path) and the path_id used.  history.tracking_episodes splits the result into episodes and gives travel
+        times between stations and the delay against free flow.
+        ValueError: a path_id out of range or of another shape, a path without a point or with fewer than three columns,
+        path entries that are not finite."""
+        d = self._tracking_device(paths, path_id)
+        out = {k: d[k].cpu().numpy() for k in ("idx", "seg", "s", "d", "e_yaw", "ep_i", "ep_d")}
+        out.update(arc=d["arc"], path_id=d["path_id"])
+        return out
+
+    def _tracking_device(self, paths=None, path_id=None, n=None) -> dict:
+        """tracking() up to the launch: the outputs as device tensors (idx, seg, s, d, e_yaw, ep_i, ep_d) and the host arguments
+        used (arc, path_id)."""
+        eng = self.loop.eng
+        B, dev = eng.B, eng.device
+        table = self._tracking_table if paths is None else None
+        if table is None:
+            table = history.path_table(eng.paths if paths is None else paths)
+            table["dev"] = [torch.from_numpy(table[k]).to(dev) for k in ("x", "y", "yaw", "off", "arc_flat")]
+            if paths is None:
+                self._tracking_table = table
+        n_paths = len(table["arc"])
+        own = paths is None and path_id is None                     # the engine's own: its path_id is on the device already
+        if path_id is None:
+            if paths is not None and n_paths != 1:
+                raise ValueError("paths of one's own need a path_id per ego")
+            pid = eng.path_id.cpu().numpy() if own else np.zeros(B, dtype=np.int32)
+        else:
+            pid = np.asarray(path_id)
+            if pid.dtype.kind not in "iu" or pid.shape not in ((), (B,)):
+                raise ValueError(f"path_id must be one integer or [B = {B}] integers, got {pid.dtype} {pid.shape}")
+            pid = np.array(np.broadcast_to(pid, (B,)), dtype=np.int32)
+        if ((pid < 0) | (pid >= n_paths)).any():
+            raise ValueError(f"path_id outside [0, {n_paths})")
+        d_pid = eng.path_id if own else torch.from_numpy(pid).to(dev)
+        n = self._n(4) if n is None else n
+        idx, seg = self._new(n, dtype=torch.int32, count=2)
+        s, d, e_yaw = self._new(n, count=3)
+        ep_i, ep_d = self._new(n, len(history.TRK_INT), dtype=torch.int32), self._new(n, len(history.TRK_DOUBLE))
+        px, py, pyaw, off, arc = table["dev"]
+        self._call("jsim_loop_eval_tracking", B, n, _ptr(self.rec), _ptr(self.flags), _ptr(d_pid), int(px.numel()), _ptr(px), _ptr(py),
+                   _ptr(pyaw), n_paths, _ptr(off), _ptr(arc), _ptr(idx), _ptr(seg), _ptr(s), _ptr(d), _ptr(e_yaw), _ptr(ep_i), _ptr(ep_d))
+        return {"idx": idx, "seg": seg, "s": s, "d": d, "e_yaw": e_yaw, "ep_i": ep_i, "ep_d": ep_d, "arc": table["arc"], "path_id": pid}
 
     def cutoffs(self, chunk_ticks: int = 0, carry=None) -> dict:
         """The glue's decision on every recorded tick (jsim_loop_eval_cutoffs): what the loop ahead of MPC.step

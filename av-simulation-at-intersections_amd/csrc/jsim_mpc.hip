@@ -2539,6 +2539,29 @@ extern "C" int jsim_loop_summarise_episodes(jsim_ctx *ctx, int32_t B, int32_t n_
     return B > 0 ? launch_per_ego(ctx, episode_summary_kernel, B, stream, P) : 0;
 }
 
+#include "tracking.inc"
+
+// Every recorded pose projected onto a path: DEVICE pointers throughout -- the recorder's buffers, path_id,
+// the call's own path table and the outputs -- with HOST counts; one launch on `stream`, one wavefront per ego.
+extern "C" int jsim_loop_eval_tracking(jsim_ctx *ctx, int32_t B, int32_t n_ticks, const double *rec, const int32_t *flags,
+                                       const int32_t *path_id, int32_t n_pts, const double *px, const double *py, const double *pyaw,
+                                       int32_t n_paths, const int64_t *path_off, const double *arc, int32_t *idx, int32_t *seg, double *s,
+                                       double *d, double *e_yaw, int32_t *ep_i, double *ep_d, void *stream)
+{
+    const char *const F = "jsim_loop_eval_tracking";
+    if (B < 0 || n_ticks < 0 || n_pts < 0 || n_paths < 0)
+        return fail(ctx, -22, "%s: B=%d n_ticks=%d n_pts=%d n_paths=%d", F, B, n_ticks, n_pts, n_paths);
+    const void *const ptrs[] = {rec, flags, path_id, px, py, pyaw, path_off, arc, idx, seg, s, d, e_yaw, ep_i, ep_d};
+    const char *const names[] = {"rec", "flags", "path_id", "px", "py", "pyaw", "path_off", "arc", "idx", "seg", "s", "d", "e_yaw", "ep_i", "ep_d"};
+    for (int i = 0; i < 15; ++i)
+        if (!ptrs[i]) return fail(ctx, -22, "%s: null pointer %s", F, names[i]);
+    if (n_paths == 0 && B > 0) return fail(ctx, -22, "%s: n_paths=0 with B=%d", F, B);
+    JSIM_RECORDER_CALL(B == 0 || n_ticks == 0);
+    const TrackP P = {B, n_ticks, rec, flags, path_id, n_pts, n_paths, px, py, pyaw, arc, (const long long *)path_off,
+                      idx, seg, s, d, e_yaw, ep_i, ep_d};
+    return launch_per_ego(ctx, tracking_ticks_kernel, B, stream, P);
+}
+
 // the shape table's (thr, thr_sq) rows: check_collision_moving_bicycle's min_distance = the egos' radius + the vehicle's own
 static int upload_shape_thresholds(jsim_ctx *ctx)
 {

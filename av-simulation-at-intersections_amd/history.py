@@ -6,7 +6,8 @@ the recorder, testable without a device.  reason_series does the same for the pe
 conflict_episodes for the clearance and first contact of every episode (section 17), static_episodes for the static obstacles
 (section 18), episode_rows for the per-episode table that is reduced on the device (section 19), cutoff_episodes for the glue's
 collision cut-off of every tick (section 21); fork_rows, join and reasons_carry_at are the host side of a fork (section 22);
-gap_episodes for the time gap between an ego and each vehicle (section 23)."""
+gap_episodes for the time gap between an ego and each vehicle (section 23); path_table and tracking_episodes for the projection of
+every recorded pose onto a path (section 24)."""
 from __future__ import annotations
 
 from typing import List, Optional
@@ -22,6 +23,9 @@ EP_INT = ("ego", "k0", "n", "end", "failed", "dev_tick", "veh_tick", "veh_who", 
 EP_DOUBLE = ("length", "v_mean", "v_max", "a_min", "a_max", "delta_absmax", "dev_max", "dev_mean", "veh_clear", "veh_hit_x",
              "veh_hit_y", "st_clear", "pm_min", "driver_min", "cyclist_min", "dist_min")
 GAP_NONE, GAP_MAX_WINDOW = -128, 63      # JSIM_GAP_NONE, JSIM_GAP_MAX_WINDOW
+# the columns of Recorder.tracking's ep_i and ep_d, in the order of the JSIM_TRK_* enumerators of include/jsim_mpc.h
+TRK_INT = ("ticks", "d_max_tick")
+TRK_DOUBLE = ("d_max", "d2_mean", "yaw_max", "s_first", "s_last")
 
 
 class History:
@@ -193,6 +197,61 @@ def gap_episodes(result: dict, flags: np.ndarray, dt: float):
         k = np.argmin(m, axis=0)                                           # the first tick of each place's smallest
         ep["per_vehicle"] = [(int(m[k[i], i]), int(off[k0 + k[i], b, i]), k0 + int(k[i])) if m[k[i], i] <= GAP_MAX_WINDOW else (-1, None, -1)
                              for i in range(off.shape[2])]
+        return ep
+    return _per_episode(flags, make)
+
+
+def path_table(paths) -> dict:
+    """A list of paths -- (M, >= 3) arrays x, y, yaw, M >= 1 -- as jsim_loop_eval_tracking takes them: x, y, yaw (all points, path
+    after path), off [n_paths + 1] (int64, as pack_paths makes it), arc (a list: the arc length at every point of each path, 0 at its
+    first, arc[i + 1] = arc[i] + sqrt(dx * dx + dy * dy) added one after the other) and arc_flat (the same, path after path).
+    ValueError: no path, a path that is not such an array, entries that are not finite."""
+    paths = [np.asarray(p, dtype=np.float64) for p in paths]
+    if not paths:
+        raise ValueError("tracking needs at least one path")
+    for i, p in enumerate(paths):
+        if p.ndim != 2 or p.shape[0] < 1 or p.shape[1] < 3:
+            raise ValueError(f"path {i} must be an (M, >= 3) array x, y, yaw with M >= 1, got shape {p.shape}")
+        if not np.isfinite(p[:, :3]).all():
+            raise ValueError(f"path {i} has entries that are not finite")
+    arc = []
+    for p in paths:
+        dx, dy = np.diff(p[:, 0]), np.diff(p[:, 1])
+        arc.append(np.concatenate([[0.0], np.cumsum(np.sqrt(dx * dx + dy * dy))]))   # (cumsum adds in order)
+    cat = np.concatenate([p[:, :3] for p in paths], axis=0)
+    off = np.concatenate([[0], np.cumsum([len(p) for p in paths])]).astype(np.int64)
+    return {"x": np.ascontiguousarray(cat[:, 0]), "y": np.ascontiguousarray(cat[:, 1]), "yaw": np.ascontiguousarray(cat[:, 2]),
+            "off": off, "arc": arc, "arc_flat": np.ascontiguousarray(np.concatenate(arc))}
+
+
+def tracking_episodes(result: dict, flags: np.ndarray, dt: float, stations=None, free_speed=None):
+    """The path tracking of a recorder (Recorder.tracking: `s`, `ep_i`, `ep_d`) per ego and episode, split where ego_histories
+    splits (episode_bounds).  Returns a list over egos of lists over episodes of dicts: k0, n (first tick, ticks), d_max (the largest
+    |d|), d_max_tick (the first tick that has it, -1), d_rms (sqrt of the mean of d * d), yaw_max (the largest |e_yaw|), s_first,
+    s_last (the arc length at the episode's first and last tick) and progress = s_last - s_first; NaN / -1 in an episode without a
+    tick.  With stations (arc lengths): t_station, a list with, per station, the seconds from the episode's first tick to its first
+    tick with s >= the station, NaN if it never is -- the travel time between two stations is the difference of two entries, the
+    rows of a time-space diagram are (k * dt, s[k]).  With free_speed (m/s): delay = n * dt - progress / free_speed, the time lost
+    against driving the same stretch at that speed.  The ticks at which |d| crosses a bound are threshold_crossings(-abs(d[:, b]),
+    -bound) for leaving it and threshold_crossings(abs(d[:, b]), bound) for returning: that function applies as it is."""
+    s = np.asarray(result["s"], dtype=np.float64)
+    ep_i, ep_d = np.asarray(result["ep_i"]), np.asarray(result["ep_d"], dtype=np.float64)
+    stations = None if stations is None else [float(v) for v in np.asarray(stations, dtype=np.float64).reshape(-1)]
+    nan = float("nan")
+
+    def make(b, k0, k1):
+        n = k1 - k0
+        ep = {"k0": k0, "n": n, "d_max": nan, "d_max_tick": -1, "d_rms": nan, "yaw_max": nan, "s_first": nan, "s_last": nan, "progress": nan}
+        if n > 0:
+            row = dict(zip(TRK_DOUBLE, ep_d[k0, b].tolist()))
+            ep.update(d_max=row["d_max"], d_max_tick=int(ep_i[k0, b, 1]), d_rms=float(np.sqrt(row["d2_mean"])), yaw_max=row["yaw_max"],
+                      s_first=row["s_first"], s_last=row["s_last"], progress=row["s_last"] - row["s_first"])
+        if stations is not None:
+            with np.errstate(invalid="ignore"):
+                reached = [np.flatnonzero(s[k0:k1, b] >= v) for v in stations]
+            ep["t_station"] = [float(r[0]) * float(dt) if r.size else nan for r in reached]
+        if free_speed is not None:
+            ep["delay"] = n * float(dt) - ep["progress"] / float(free_speed)
         return ep
     return _per_episode(flags, make)
 

@@ -493,6 +493,50 @@ int jsim_loop_eval_gaps(jsim_ctx *ctx, int32_t B, int32_t n_ticks, const double 
                         const int32_t *mate_range, const double *shapes, const double *ego_shape, int32_t window, int32_t within,
                         int8_t *off, int32_t *ep_gap, int32_t *ep_tick, int32_t *ep_who, int32_t *ep_off, void *stream);
 
+/* ---- every recorded pose projected onto a path: progress, lateral offset, heading error ----
+ * How well an ego followed the route it was given, and how far along it got and when: the question the reference answers with a
+ * picture only -- plot_trajectories_comparison(..., reference_trajectory, ...) of main/scenarios/mpc_sensitivity_analysis*.py draws
+ * the driven trajectories over the planned one.  (The recorder's xref_deviation is the controller's own number: the distance from
+ * the first predicted state to the path point at target_ind, NaN on a failed solve.)  Per tick and episode of every ego, from the
+ * recorder's buffers (jsim_loop_set_recorder), after the loop.  One wavefront per ego, 64 ticks at a time; the path's points are
+ * wave-uniform scalar loads.  DESIGN.md section 24 is the contract.
+ *   DEVICE pointers: rec [n_ticks][B][7], flags [n_ticks][B] as jsim_loop_eval_conflicts takes them; path_id [B] (int32); the path
+ *   table px, py, pyaw, arc [n_pts] and path_off [n_paths + 1] (int64, as jsim_mpc_set_paths takes it on the host: path p is the
+ *   points [path_off[p], path_off[p + 1])); and every output.  n_pts and n_paths are HOST counts.  The table is the call's own, not
+ *   the context's (the context only gives the device and jsim_last_error): the engine's paths, the source paths of
+ *   a fork, a lane centreline.  pyaw is the smoothed yaw as MPC.__init__ uploads it; arc is the arc length at every point, 0 at each
+ *   path's first, made on the host: arc[i + 1] = arc[i] + sqrt(dx * dx + dy * dy), sequentially.
+ *   The pose of tick k is rec[k] itself: x, y, yaw after the plant step (History.x[k], .y[k], .yaw[k]), not the start-of-tick pose.
+ *   Per tick [n_ticks][B], with n = the points of path path_id[b] and indices relative to the path:
+ *     idx (int32) = calc_nearest_index(state, cx, cy, 0) (main/lib/trajectories.py:89-97): the lowest i that minimises
+ *       dx * dx + dy * dy, dx = px[i] - x, dy = py[i] - y, the sum unfused (np.argmin's first occurrence).
+ *     seg (int32), t: of the segments j in {idx - 1, idx} within [0, n - 2], each from A = point j to B = point j + 1 with
+ *       u = B - A, L2 = ux * ux + uy * uy, t = 0 when L2 == 0, else ((x - Ax) * ux + (y - Ay) * uy) / L2 clamped to [0, 1], foot
+ *       A + t * u, q = rx * rx + ry * ry of the residual: the one with the smaller q, the lower on a tie.  n = 1: seg = 0, t = 0,
+ *       the foot is the point.
+ *     s (double) = arc[seg] + t * (arc[seg + 1] - arc[seg]); 0 for n = 1.
+ *     d (double) = +sqrt(q) when ux * (y - Ay) - uy * (x - Ax) >= 0 (left of the direction of travel; n = 1: always), else -sqrt(q):
+ *       |d| is the distance to the polyline, also beyond its ends.
+ *     e_yaw (double) = ((a + pi) mod 2 pi) - pi with a = yaw - (pyaw[seg] + t * (pyaw[seg + 1] - pyaw[seg])) and Python's mod (fmod,
+ *       plus 2 pi when negative).
+ *     A pose that is not finite, a path_id outside [0, n_paths) or an empty path: idx = seg = -1, s = d = e_yaw = NaN.
+ *   Per episode, at the slot of its first tick (the last record closes the running episode; every other slot -1 / NaN):
+ *     ep_i [n_ticks][B][JSIM_TRK_NI]: TICKS, D_TICK (the first tick that holds the largest |d|, -1 without one);
+ *     ep_d [n_ticks][B][JSIM_TRK_ND]: D_MAX (largest |d|), D2_MEAN (the mean of d * d over the episode's ticks that have a d, NaN
+ *     without one), YAW_MAX (largest |e_yaw|), S_FIRST, S_LAST (s at the episode's first and last tick).  Maxima pass over NaN;
+ *     the sum is added in a fixed order that depends on the ticks' places in their 64-tick chunks alone, so a finished episode's
+ *     row does not depend on how many ticks follow it.
+ *   Refused (-22) before any device call, jsim_last_error naming the argument: B, n_ticks, n_pts or n_paths < 0; a null pointer
+ *   other than stream; n_paths = 0 with B > 0; a null ctx.  n_ticks = 0 or B = 0 returns 0 and writes nothing.  A path_off or
+ *   path_id outside its table would need a device read to detect: the kernel clamps so that it never reads outside the tables,
+ *   and the Python surface (Recorder.tracking) refuses with ValueError. */
+enum { JSIM_TRK_TICKS = 0, JSIM_TRK_D_TICK, JSIM_TRK_NI };
+enum { JSIM_TRK_D_MAX = 0, JSIM_TRK_D2_MEAN, JSIM_TRK_YAW_MAX, JSIM_TRK_S_FIRST, JSIM_TRK_S_LAST, JSIM_TRK_ND };
+int jsim_loop_eval_tracking(jsim_ctx *ctx, int32_t B, int32_t n_ticks, const double *rec, const int32_t *flags, const int32_t *path_id,
+                            int32_t n_pts, const double *px, const double *py, const double *pyaw, int32_t n_paths,
+                            const int64_t *path_off, const double *arc, int32_t *idx, int32_t *seg, double *s, double *d,
+                            double *e_yaw, int32_t *ep_i, double *ep_d, void *stream);
+
 /* ---- static-obstacle clearance and contact per recorded tick: the realised poses of a run against the scenario's obstacles ----
  * Answers for driven poses what the reference only asks of planned ones: check_collision (main/lib/obstacles.py:157-176) on
  * Obstacle.to_convex(margin) (:82-93 box, :134-148 circle) -- the planner's collision test, main/lib/mp_search_ww_generic.py:199-215

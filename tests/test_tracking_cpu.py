@@ -1,0 +1,282 @@
+"""Every recorded pose projected onto a path (jsim_loop_eval_tracking) without a GPU: the numpy restatement's
+idx against the reference-made fixture (tests/golden/tracking.npz: calc_nearest_index on every pose and path of the cases), the
+cases' own condition, s / d / e_yaw against closed forms on the straight and the circular-arc path, the events each case is named
+after, history.path_table and history.tracking_episodes, the C entry point's declaration, binding and -22 list against the
+cross-compiled library, and the ValueErrors of Recorder.tracking that need no device."""
+import math
+import os
+import re
+import types
+
+import numpy as np
+import pytest
+import torch
+
+import tracking_cases as KC
+import tracking_numpy as TN
+from conftest import REPO
+
+
+@pytest.fixture(scope="module")
+def cs():
+    return KC.cases()
+
+
+@pytest.fixture(scope="module")
+def arrays(cs):
+    return KC.recorder_arrays(cs)
+
+
+@pytest.fixture(scope="module")
+def ref(arrays):
+    return KC.restate(arrays)
+
+
+def test_cases_are_the_stored_ones(cs):
+    g = KC.fixture()
+    paths = KC.paths()
+    assert int(g["n_cases"]) == len(cs) == 10 and g["ego"].shape == (10, KC.N, 3) and g["idx"].shape == (10, KC.N)
+    for b, c in enumerate(cs):
+        assert str(g["labels"][b]) == c["label"] and int(g["path"][b]) == c["path"]
+        assert np.array_equal(g["ego"][b], c["ego"], equal_nan=True) and np.array_equal(g["flags"][b], c["flags"])
+    assert [len(p) for p in paths] == [1, 2, 3, 63, 64, 65, 700, 6] == np.diff(g["path_off"]).tolist()
+    assert np.array_equal(g["points"], np.concatenate(paths))
+    assert paths[5][:, 2].max() > 2 * np.pi and np.array_equal(paths[7][2], paths[7][3])
+    assert sorted({c["path"] for c in cs}) == list(range(8)) and [c["path"] for c in cs].count(3) == 2 == [c["path"] for c in cs].count(6)
+
+
+def test_restatement_idx_is_the_references(cs, ref):
+    g = KC.fixture()
+    assert g["idx"].dtype == np.int32 and np.array_equal(ref["idx"], g["idx"].T)
+    finite = np.isfinite(g["ego"]).all(axis=2)
+    assert np.array_equal(g["idx"] >= 0, finite) and (~finite).sum() == 2
+    for n in KC.TICK_COUNTS:                                           # a pose's index does not depend on the ticks that follow
+        assert np.array_equal(KC.restate(KC.recorder_arrays(cs), n=n, egos=[1, 9])["idx"], g["idx"].T[:n, [1, 9]])
+
+
+def test_condition_holds(cs, ref):
+    assert KC.condition(cs, ref) == float(KC.fixture()["margin"]) >= KC.MARGIN
+
+
+def test_arc_lengths_and_path_table(pkg):
+    paths = KC.paths()
+    t = pkg.history.path_table(paths)
+    for p, a in zip(paths, t["arc"]):
+        assert np.array_equal(a, TN.arc_lengths(p)) and a[0] == 0.0
+    assert np.array_equal(t["arc"][3], KC.DX * np.arange(63)) and t["off"].dtype == np.int64 and t["off"].tolist() == [0, 1, 3, 6, 69, 133, 198, 898, 904]
+    assert np.array_equal(t["arc_flat"], np.concatenate(t["arc"])) and np.array_equal(t["yaw"], np.concatenate(paths)[:, 2])
+    wide = pkg.history.path_table([np.c_[paths[2], np.ones(3)]])          # further columns are passed over
+    assert np.array_equal(wide["x"], paths[2][:, 0]) and np.array_equal(wide["arc"][0], [0.0, 4.0, 8.0])
+    bad = paths[1].copy()
+    bad[1, 2] = np.nan
+    for p in ([], [np.zeros((0, 3))], [np.zeros((4, 2))], [np.zeros(3)], [bad], [paths[1], np.array([[0.0, np.inf, 0.0]])]):
+        with pytest.raises(ValueError):
+            pkg.history.path_table(p)
+
+
+def test_straight_path_in_closed_form(cs, ref):
+    """Along x at y = C: d = y - C and s = x - X0 exactly, e_yaw the pose's yaw wrapped."""
+    for b in (3, 4):
+        x, y, yaw = cs[b]["ego"].T
+        assert np.array_equal(ref["d"][:, b], y - KC.C) and np.array_equal(ref["s"][:, b], x - KC.X0)
+        near = np.floor((x - KC.X0) / KC.DX + 0.5).astype(int)
+        if b == 3:
+            near[21] = 8                                               # exactly between 8 and 9: the lower
+        assert np.array_equal(ref["idx"][:, b], near)
+        assert np.array_equal(ref["seg"][:, b], np.ceil((x - KC.X0) / KC.DX).astype(int) - 1)   # on a vertex: the lower segment
+        plain = np.abs(yaw) < 3.0
+        assert plain.sum() >= 194 and np.array_equal(ref["e_yaw"][plain, b], yaw[plain])
+    e = ref["e_yaw"][10:16, 3]
+    assert np.allclose(e[:2], [np.pi - KC.EPS, -np.pi + KC.EPS], rtol=0, atol=1e-15)             # just inside
+    assert np.allclose(e[2:4], [-np.pi + KC.EPS, np.pi - KC.EPS], rtol=0, atol=1e-15)            # across the wrap
+    assert e[4] == -np.pi == e[5] and (np.abs(ref["e_yaw"][np.isfinite(ref["e_yaw"])]) <= np.pi).all()
+
+
+def test_arc_in_closed_form(cs, ref):
+    """A pose at radius rho and angle phi about the arc's centre, against the chord j it is projected onto: d = R cos(D/2) -
+    rho cos(phi - mid), s = (j + 1/2) chord + rho sin(phi - mid), e_yaw = yaw - (j + t) D."""
+    b = 5
+    x, y, yaw = cs[b]["ego"].T
+    rho, phi = np.hypot(x, KC.R - y), np.arctan2(x, KC.R - y)
+    chord = 2 * KC.R * math.sin(KC.DTH / 2)
+    j = ref["seg"][:, b]
+    mid = (j + 0.5) * KC.DTH
+    t = (ref["s"][:, b] - j * chord) / chord
+    inside = (t > 1e-6) & (t < 1 - 1e-6)
+    assert inside.sum() > 150 and np.array_equal(j[inside], np.floor(phi[inside] / KC.DTH).astype(int))
+    assert np.allclose(ref["d"][inside, b], KC.R * math.cos(KC.DTH / 2) - rho[inside] * np.cos(phi[inside] - mid[inside]), rtol=0, atol=1e-9)
+    assert np.allclose(ref["s"][inside, b], (j[inside] + 0.5) * chord + rho[inside] * np.sin(phi[inside] - mid[inside]), rtol=0, atol=1e-9)
+    assert np.allclose(ref["e_yaw"][inside, b], yaw[inside] - (j[inside] + t[inside]) * KC.DTH, rtol=0, atol=1e-9)
+    assert (ref["d"][:60, b] > 0).all() and (ref["d"][-60:, b] < 0).all()                         # inside the arc is left of it
+    # before the first point and beyond the last: clamped, |d| the distance to the end point
+    assert ref["s"][0, b] == 0.0 and ref["s"][-1, b] == ref["arc"][4][-1] and ref["seg"][-1, b] == 62
+    last = KC.paths()[4][-1]
+    assert abs(abs(ref["d"][-1, b]) - math.hypot(x[-1] - last[0], y[-1] - last[1])) < 1e-12
+
+
+def test_cases_meet_the_kernel_structure(cs, ref):
+    """The events each case is named after are where the name says."""
+    at = lambda key, k, b: ref[key][k, b].tolist()
+    # one point
+    x, y, _ = cs[0]["ego"].T
+    assert (ref["idx"][:, 0] == 0).all() and (ref["seg"][:, 0] == 0).all() and (ref["s"][:, 0] == 0).all()
+    assert np.allclose(ref["d"][:, 0], np.hypot(x - 1.5, y + 2.25), rtol=0, atol=1e-14) and (ref["d"][:, 0] > 0).all()
+    # two points: clamped, left then right, the tie, the extension, not finite
+    assert at("s", 0, 1) == 0.0 and at("s", 199, 1) == 4.0 and at("d", 10, 1) > 0 > at("d", 190, 1)
+    assert (at("idx", 100, 1), at("seg", 100, 1), at("s", 100, 1), at("d", 100, 1)) == (0, 0, 2.0, 0.75) and at("idx", 101, 1) == 1
+    assert (at("s", 50, 1), at("d", 50, 1), at("s", 150, 1), at("d", 150, 1)) == (0.0, 1.5, 4.0, 2.0)
+    for k in (120, 121):
+        assert (at("idx", k, 1), at("seg", k, 1)) == (-1, -1) and all(math.isnan(at(key, k, 1)) for key in ("s", "d", "e_yaw"))
+    assert ref["ep_i"][0, 1].tolist() == [200, 199] and not np.isnan(ref["ep_d"][0, 1]).any()       # maxima and the mean pass over NaN
+    # the bend
+    assert [at("seg", k, 2) for k in (40, 41, 42, 43, 44)] == [0, 0, 0, 1, 0] and [at("idx", k, 2) for k in (40, 41, 42, 43, 44)] == [1] * 5
+    assert (at("d", 40, 2), at("d", 41, 2), at("d", 43, 2), at("d", 44, 2)) == (0.0, 1.0, 1.0, 1.0) and at("d", 42, 2) == -math.sqrt(2.0)
+    assert (at("s", 41, 2), at("s", 42, 2), at("s", 43, 2)) == (3.0, 4.0, 5.5)
+    assert at("e_yaw", 43, 2) == 0.5 - (np.pi / 4 + 0.375 * (np.pi / 2 - np.pi / 4))
+    # the straight path's episodes: 0..62, 63, 64, 65..199
+    assert TN.episodes_of(cs[3]["flags"]) == [(0, 62), (63, 63), (64, 64), (65, 199)]
+    assert [ref["ep_i"][k, 3].tolist() for k in (0, 63, 64, 65)] == [[63, 0], [1, 63], [1, 64], [135, 199]]
+    assert ref["ep_d"][0, 3].tolist()[0] == 100 / 64 and ref["ep_d"][65, 3, 3:].tolist() == [at("s", 65, 3), at("s", 199, 3)]
+    assert ref["ep_d"][0, 3, 2] == np.pi                                  # the largest |e_yaw| is the wrapped -pi
+    assert (at("idx", 20, 3), at("seg", 20, 3), at("idx", 21, 3), at("seg", 21, 3)) == (8, 7, 8, 8)
+    # the same largest |d| twice: the first tick stays, across two chunk carries
+    assert TN.episodes_of(cs[4]["flags"]) == [(0, 150), (151, 199)] and ref["ep_i"][0, 4].tolist() == [151, 30] and ref["ep_d"][0, 4, 0] == 2.0
+    assert at("d", 30, 4) == 2.0 and at("d", 130, 4) == -2.0 and ref["ep_i"][151, 4].tolist() == [49, 151] and ref["ep_d"][151, 4, 1] == 0.0625
+    # every tick ends an episode; none does
+    assert (ref["ep_i"][:, 5, 0] == 1).all() and np.array_equal(ref["ep_i"][:, 5, 1], np.arange(KC.N))
+    assert np.array_equal(ref["ep_d"][:, 5, 0], np.abs(ref["d"][:, 5])) and np.array_equal(ref["ep_d"][:, 5, 1], ref["d"][:, 5] ** 2)
+    assert ref["ep_i"][0, 6, 0] == 200 and (ref["ep_i"][1:, 6] == -1).all() and np.isnan(ref["ep_d"][1:, 6]).all()
+    # the spiral: the path's yaw beyond 2 pi, the pose's wrapped: the error is the small one
+    assert np.abs(ref["e_yaw"][:, 6]).max() < 0.25 and KC.paths()[5][ref["seg"][:, 6], 2].max() > 2 * np.pi
+    # the route: the last record's own end flag changes nothing; backwards the heading error is near pi
+    assert TN.episodes_of(cs[7]["flags"]) == [(0, 130), (131, 199)] and ref["ep_i"][131, 7, 0] == 69
+    assert (np.abs(ref["e_yaw"][:, 8]) > 2.5).all() and (np.diff(ref["s"][:, 8]) < 0).all() and (np.diff(ref["s"][:, 7]) > 0).all()
+    assert (ref["d"][:, 7] > 0).all() and np.abs(ref["d"][:, 7] - (0.2 * np.sin(np.arange(KC.N) / 9) + 0.25)).max() < 2e-3
+    # identical points: the lower one's index; at the path's start the segment of no length is the only candidate: t = 0
+    tied = ref["margin_idx"][:, 9] == 0.0
+    assert tied.sum() > 50 and set(ref["idx"][tied, 9].tolist()) == {0, 2} and not np.isin(ref["idx"][:, 9], (1, 3)).any()
+    start = ref["idx"][:, 9] == 0
+    assert start.sum() > 10 and (ref["seg"][start, 9] == 0).all() and (ref["s"][start, 9] == 0.0).all() and (ref["d"][start, 9] > 0).all()
+    assert np.allclose(ref["d"][start, 9], np.hypot(*cs[9]["ego"][start, :2].T), rtol=0, atol=1e-15)
+    assert (ref["seg"][ref["idx"][:, 9] == 2, 9] == 1).all()
+
+
+def test_a_cut_record_closes_the_running_episode(arrays, ref):
+    for n in KC.TICK_COUNTS:
+        cut = KC.restate(arrays, n=n, egos=[3, 4, 7])
+        for key in ("idx", "seg", "s", "d", "e_yaw"):
+            assert np.array_equal(cut[key], ref[key][:n, [3, 4, 7]], equal_nan=True), (n, key)
+        for j, b in enumerate((3, 4, 7)):
+            eps = TN.episodes_of(arrays["flags"][:n, b])
+            assert sum(k1 - k0 + 1 for k0, k1 in eps) == n
+            for k0, k1 in eps:
+                assert cut["ep_i"][k0, j, 0] == k1 - k0 + 1
+                if k1 < n - 1 or n == KC.N:                                # a finished episode's row: the long record's
+                    assert np.array_equal(cut["ep_i"][k0, j], ref["ep_i"][k0, b]) and np.array_equal(cut["ep_d"][k0, j], ref["ep_d"][k0, b])
+
+
+def test_tracking_episodes(pkg, cs, arrays, ref):
+    H = pkg.history
+    assert (H.TRK_INT, H.TRK_DOUBLE) == (("ticks", "d_max_tick"), ("d_max", "d2_mean", "yaw_max", "s_first", "s_last"))
+    assert (len(H.TRK_INT), len(H.TRK_DOUBLE)) == (TN.NI, TN.ND)
+    eps = H.tracking_episodes(ref, arrays["flags"], 0.1)
+    for b, c in enumerate(cs):
+        mine = TN.episodes_of(c["flags"])
+        assert len(eps[b]) == len(H.episode_bounds(c["flags"])) and [(e["k0"], e["n"]) for e in eps[b]][:len(mine)] == [(k0, k1 - k0 + 1) for k0, k1 in mine]
+        for e, (k0, k1) in zip(eps[b], mine):
+            row = ref["ep_d"][k0, b]
+            assert (e["d_max"], e["yaw_max"], e["s_first"], e["s_last"]) == (row[0], row[2], row[3], row[4]) and e["d_max_tick"] == ref["ep_i"][k0, b, 1]
+            assert e["d_rms"] == math.sqrt(row[1]) and e["progress"] == row[4] - row[3] and "t_station" not in e and "delay" not in e
+    # the last record of case 7 ended its episode: the running one has no tick yet
+    assert eps[7][-1] == {"k0": 200, "n": 0, "d_max_tick": -1, **{k: eps[7][-1][k] for k in ("d_max", "d_rms", "yaw_max", "s_first", "s_last", "progress")}}
+    assert all(math.isnan(eps[7][-1][k]) for k in ("d_max", "d_rms", "yaw_max", "s_first", "s_last", "progress"))
+    # a hand-made series: two episodes of one ego, stations at 1, 2.5 and 9 m, free flow at 5 m/s
+    flags = np.zeros((8, 1), dtype=np.int32)
+    flags[4, 0] = H.GOAL
+    s = np.array([0.0, 0.5, 1.0, 2.0, 3.0, 0.25, np.nan, 2.5])[:, None]
+    ep_i, ep_d = np.full((8, 1, 2), -1), np.full((8, 1, 5), np.nan)
+    ep_i[0, 0], ep_d[0, 0] = (5, 3), (0.5, 0.04, 0.1, 0.0, 3.0)
+    ep_i[5, 0], ep_d[5, 0] = (3, 5), (0.25, 0.01, 0.2, 0.25, 2.5)
+    a, b_ = H.tracking_episodes({"s": s, "ep_i": ep_i, "ep_d": ep_d}, flags, 0.2, stations=[1.0, 2.5, 9.0], free_speed=5.0)[0]
+    assert a["t_station"][:2] == [2 * 0.2, 4 * 0.2] and math.isnan(a["t_station"][2]) and a["delay"] == 5 * 0.2 - 3.0 / 5.0
+    assert math.isnan(b_["t_station"][0]) is False and b_["t_station"][:2] == [2 * 0.2, 2 * 0.2] and math.isnan(b_["t_station"][2])
+    assert b_["delay"] == 3 * 0.2 - 2.25 / 5.0 and (a["d_rms"], a["d_max_tick"], b_["k0"], b_["n"]) == (0.2, 3, 5, 3)
+    assert H.threshold_crossings(-np.abs(ref["d"][:, 4]), -1.75).tolist() == [30, 130]              # where |d| leaves a bound
+
+
+NAMES = ("rec", "flags", "path_id", "n_pts", "px", "py", "pyaw", "n_paths", "path_off", "arc", "idx", "seg", "s", "d", "e_yaw", "ep_i", "ep_d")
+POINTERS = tuple(k for k in NAMES if k not in ("n_pts", "n_paths"))
+
+
+def test_entry_point_is_declared_and_bound(pkg):
+    hdr = open(os.path.join(REPO, "include", "jsim_mpc.h")).read()
+    m = re.search(r"\bint jsim_loop_eval_tracking\s*\(([^;]*)\);", hdr)
+    assert m
+    args = [re.search(r"(\w+)$", a.strip()).group(1) for a in m.group(1).split(",")]
+    assert args == ["ctx", "B", "n_ticks", *NAMES, "stream"]
+    assert "enum { JSIM_TRK_TICKS = 0, JSIM_TRK_D_TICK, JSIM_TRK_NI };" in hdr and "#define JSIM_ABI_VERSION 2 " in hdr
+    assert "enum { JSIM_TRK_D_MAX = 0, JSIM_TRK_D2_MEAN, JSIM_TRK_YAW_MAX, JSIM_TRK_S_FIRST, JSIM_TRK_S_LAST, JSIM_TRK_ND };" in hdr
+    assert "main/lib/trajectories.py:89-97" in hdr and "plot_trajectories_comparison" in hdr and "mpc_sensitivity_analysis" in hdr
+    assert "jsim_loop_eval_tracking" in pkg._cabi.EXPORTS
+    assert len(pkg._cabi.load().jsim_loop_eval_tracking.argtypes) == len(args) == 21
+    doc = open(os.path.join(REPO, "INTEGRATION.md")).read()
+    row = re.search(r"^\| `jsim_loop_eval_tracking` \|(.*)$", doc, flags=re.M)
+    assert row and "main/lib/trajectories.py:89-97" in row.group(1) and "Recorder.tracking" in row.group(1)
+    R = pkg.closed_loop.Recorder
+    assert callable(R.tracking) and callable(R._tracking_device) and callable(pkg.history.tracking_episodes)
+    csrc = os.path.join(REPO, "av-simulation-at-intersections_amd", "csrc")
+    src = open(os.path.join(csrc, "jsim_mpc.hip")).read()
+    assert src.index("#else /* !JSIM_KERNEL_TU") < src.index('#include "episodes.inc"') < src.index('#include "tracking.inc"') < src.index('#include "fork.inc"')
+    inc = open(os.path.join(csrc, "tracking.inc")).read()
+    assert all(k in inc for k in ("jrw_segments(C,", "jrw_enter(C,", "const double *__restrict__ px", "jep_extreme(", "dx * dx + dy * dy", "d2[j] < best"))
+    assert "asm" not in inc and "atomic" not in inc and "__shared__" not in inc
+    assert "\n## 24. " in open(os.path.join(REPO, "DESIGN.md")).read()
+
+
+def test_argument_errors_without_gpu(pkg):
+    """The header's -22 list: from the host, before any device call (there is no device here and no context to launch on)."""
+    lib = pkg._cabi.load()
+    buf = np.zeros(64)
+    p = buf.ctypes.data                                                 # a non-null address; no refused call reads it
+
+    def call(B=1, n=1, ctx=None, **over):
+        a = {k: p for k in NAMES}
+        a.update(n_pts=5, n_paths=2)
+        a.update(over)
+        rc = lib.jsim_loop_eval_tracking(ctx, B, n, *[a[k] for k in NAMES], None)
+        return rc, lib.jsim_last_error(None).decode()
+
+    who = "jsim_loop_eval_tracking: "
+    for kw, msg in ((dict(B=-1), "B=-1"), (dict(n=-1), "n_ticks=-1"), (dict(n_pts=-2), "n_pts=-2"), (dict(n_paths=-1), "n_paths=-1"),
+                    (dict(n_paths=0), "n_paths=0 with B=1")):
+        rc, err = call(**kw)
+        assert rc == -22 and err.startswith(who) and msg in err, (kw, rc, err)
+    for k in POINTERS:
+        rc, err = call(**{k: None})
+        assert rc == -22 and err == who + "null pointer " + k, (k, rc, err)
+        assert call(n=0, **{k: None})[0] == -22 and call(B=0, **{k: None})[0] == -22, k   # also with nothing to do
+    rc, err = call()                                                      # every argument good: the missing context is what is left
+    assert rc == -22 and err == who + "null ctx"
+    for kw in (dict(n=0), dict(B=0), dict(B=0, n_paths=0), dict(n_pts=0)):
+        rc, err = call(**kw)                                              # none of these is an error of its own
+        assert rc == -22 and err == who + "null ctx", kw
+    assert not buf.any()
+
+
+def test_recorder_refusals_without_a_device(pkg):
+    """Recorder.tracking checks its paths and path_id before it asks for the records or the device: on a stand-in recorder whose
+    engine has three egos on the host."""
+    paths = KC.paths()
+    eng = types.SimpleNamespace(B=3, device=torch.device("cpu"), paths=paths[1:4], path_id=torch.tensor([0, 1, 2], dtype=torch.int32))
+    stand_in = types.SimpleNamespace(loop=types.SimpleNamespace(eng=eng), _tracking_table=None)
+    track = lambda **kw: pkg.closed_loop.Recorder._tracking_device(stand_in, kw.get("paths"), kw.get("path_id"))
+    bad = paths[2].copy()
+    bad[0, 0] = np.inf
+    for kw, msg in ((dict(path_id=3), "path_id outside [0, 3)"), (dict(path_id=[0, -1, 1]), "path_id outside"), (dict(path_id=[0, 1]), "path_id must be"),
+                    (dict(path_id=[0.0, 1.0, 2.0]), "path_id must be"), (dict(paths=paths[:2]), "need a path_id"),
+                    (dict(paths=paths[:2], path_id=[0, 1, 2]), "path_id outside [0, 2)"), (dict(paths=[np.zeros((0, 3))], path_id=0), "M >= 1"),
+                    (dict(paths=[], path_id=0), "at least one path"), (dict(paths=[bad], path_id=0), "not finite"),
+                    (dict(paths=[paths[1][:, :2]], path_id=0), "(M, >= 3)")):
+        with pytest.raises(ValueError, match=re.escape(msg)):
+            track(**kw)
+    assert stand_in._tracking_table is not None and len(stand_in._tracking_table["arc"]) == 3     # the engine's table is kept
