@@ -40,7 +40,7 @@ EXPORTS = (
     "jsim_comm_unique_id", "jsim_comm_init", "jsim_mpc_gather", "jsim_comm_destroy", "jsim_plan_routes",
     "jsim_plan_routes_weighted", "jsim_score_trajectories", "jsim_loop_eval_reasons", "jsim_loop_eval_conflicts",
     "jsim_loop_eval_static", "jsim_loop_summarise_episodes", "jsim_loop_eval_cutoffs", "jsim_loop_fork_state", "jsim_loop_obstacles_at",
-    "jsim_loop_eval_gaps", "jsim_loop_eval_tracking",
+    "jsim_loop_eval_gaps", "jsim_loop_eval_tracking", "jsim_loop_eval_headway",
 )
 
 _lib = None
@@ -166,6 +166,11 @@ def load() -> C.CDLL:
     lib.jsim_loop_eval_tracking.restype = C.c_int
     #                                      ctx B    ticks rec flags path_id n_pts px py pyaw n_paths path_off arc outs  stream
     lib.jsim_loop_eval_tracking.argtypes = [vp, i32, i32, vp, vp, vp, i32, vp, vp, vp, i32, vp, vp] + [vp] * 7 + [vp]
+    lib.jsim_loop_eval_headway.restype = C.c_int
+    #                                     ctx B    ticks rec flags n_obs obs_rec x_first x_spawn veh_range mate_range shapes ego_shape
+    lib.jsim_loop_eval_headway.argtypes = ([vp, i32, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp] +
+                                           # path_id n_pts px py pyaw n_paths path_off arc margin outs (8 + 3 per place) stream
+                                           [vp, i32, vp, vp, vp, i32, vp, vp, dbl] + [vp] * 11 + [vp])
     lib.jsim_loop_eval_static.restype = C.c_int
     #                                    ctx B    ticks rec flags x_first x_spawn set_of n_sets set_off n_rows rows ego_shape hidden outs  stream
     lib.jsim_loop_eval_static.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, i32, vp, i32, vp, vp, i32] + [vp] * 4 + [vp]

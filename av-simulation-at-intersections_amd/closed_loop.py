@@ -401,6 +401,86 @@ class Recorder:
                    _ptr(pyaw), n_paths, _ptr(off), _ptr(arc), _ptr(idx), _ptr(seg), _ptr(s), _ptr(d), _ptr(e_yaw), _ptr(ep_i), _ptr(ep_d))
         return {"idx": idx, "seg": seg, "s": s, "d": d, "e_yaw": e_yaw, "ep_i": ep_i, "ep_d": ep_d, "arc": table["arc"], "path_id": pid}
 
+    def headway(self, paths=None, path_id=None, shapes=None, mates=None, margin: float = 0.0, places: bool = True) -> dict:
+        """Every recorded vehicle projected onto the ego's path (jsim_loop_eval_headway): how much road lay
+        between the ego and each vehicle it meets, how fast it closed and how long until it is gone -- the distance along the road
+        that create_following_trajectory, evaluate_time_following and plot_distance of
+        main/scenarios/overtaking_cyclist_bidirectional_road.py approximate with a Euclidean range -- computed in one launch from
+        the records, everything taken at the start of each tick.
+
+        paths, path_id: as for tracking() (default: the engine's own, whose device copy is kept on the recorder).  shapes, mates:
+        as for conflicts(); the list is the same, eight places in all.  margin (>= 0): added to a vehicle's threshold (the ego's
+        radius + its own) when deciding whether it is on the path.  places=False: the three per-place arrays are neither written
+        nor read back.
+        Returns numpy arrays.  Per place [n][B][8] (places=True): gap (> 0: the vehicle is ahead by that much road, < 0: behind,
+        0: alongside), lat (its nearer circle centre's signed offset from the path, left positive), rate (its speed along the path
+        minus the ego's; an oncoming vehicle's own is negative); NaN for an empty place or a pose that is not finite.  Per tick
+        [n][B]: lead (the on-path place with the smallest gap >= 0, -1: none), lead_gap, thw (lead_gap / u_ego; inf for a standing
+        ego, 0 alongside), ttc (the smallest time to collision over the on-path places; inf: none is closing; NaN: none is on the
+        path), ttc_who, u_ego (the ego's speed along the path).  At the slot of an episode's first tick ep_i [n][B][7]
+        (history.HW_INT) and ep_d [n][B][4] (history.HW_DOUBLE), -1 / NaN elsewhere.  And arc, path_id, veh_range, mate_range,
+        ego_shape and margin as used.  An ego without vehicles and mates has -1 / NaN everywhere.  history.headway_episodes splits
+        the result into episodes.
+        ValueError: what tracking() refuses of paths and path_id, what conflicts() refuses of shapes and mates, a margin that is
+        not finite and >= 0."""
+        d = self._headway_device(paths, path_id, shapes, mates, margin, places)
+        keys = ("lead", "lead_gap", "thw", "ttc", "ttc_who", "u_ego", "ep_i", "ep_d") + (("gap", "lat", "rate") if places else ())
+        out = {k: d[k].cpu().numpy() for k in keys}
+        out.update({k: d[k] for k in ("arc", "path_id", "veh_range", "mate_range", "ego_shape", "margin")})
+        return out
+
+    def _headway_device(self, paths=None, path_id=None, shapes=None, mates=None, margin: float = 0.0, places: bool = True, n=None) -> dict:
+        """headway() up to the launch: the outputs as device tensors (lead, lead_gap, thw, ttc, ttc_who, u_ego, ep_i, ep_d and, with
+        places, gap, lat, rate) and the host arguments used (arc, path_id, veh_range, mate_range, ego_shape, margin)."""
+        eng = self.loop.eng
+        B, dev, n_obs = eng.B, eng.device, self.n_obs
+        margin = float(margin)
+        if not (math.isfinite(margin) and margin >= 0.0):
+            raise ValueError(f"margin must be finite and >= 0, got {margin!r}")
+        table = self._tracking_table if paths is None else None
+        if table is None:
+            table = history.path_table(eng.paths if paths is None else paths)
+            table["dev"] = [torch.from_numpy(table[k]).to(dev) for k in ("x", "y", "yaw", "off", "arc_flat")]
+            if paths is None:
+                self._tracking_table = table
+        n_paths = len(table["arc"])
+        own = paths is None and path_id is None                     # the engine's own: its path_id is on the device already
+        if path_id is None:
+            if paths is not None and n_paths != 1:
+                raise ValueError("paths of one's own need a path_id per ego")
+            pid = eng.path_id.cpu().numpy() if own else np.zeros(B, dtype=np.int32)
+        else:
+            pid = np.asarray(path_id)
+            if pid.dtype.kind not in "iu" or pid.shape not in ((), (B,)):
+                raise ValueError(f"path_id must be one integer or [B = {B}] integers, got {pid.dtype} {pid.shape}")
+            pid = np.array(np.broadcast_to(pid, (B,)), dtype=np.int32)
+        if ((pid < 0) | (pid >= n_paths)).any():
+            raise ValueError(f"path_id outside [0, {n_paths})")
+        ego, shapes, veh, mate = self._vehicle_lists(shapes, mates)
+        d_pid = eng.path_id if own else torch.from_numpy(pid).to(dev)
+        n = self._n(4) if n is None else n
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(dev)
+        d_veh, d_mate = up(veh), up(mate)
+        lead, ttc_who = self._new(n, dtype=torch.int32, count=2)
+        lead_gap, thw, ttc, u_ego = self._new(n, count=4)
+        ep_i, ep_d = self._new(n, len(history.HW_INT), dtype=torch.int32), self._new(n, len(history.HW_DOUBLE))
+        per_place = self._new(n, MAX_OBS, count=3) if places else (None, None, None)
+        px, py, pyaw, off, arc = table["dev"]
+        ego_c = (C.c_double * 3)(*ego)
+        rec, flags, x_first, x_spawn = self._buffers()
+        self._call("jsim_loop_eval_headway", B, n, rec, flags, n_obs, _ptr(self.obs) if self.obs is not None else None,
+                   x_first, x_spawn, _ptr(d_veh), _ptr(d_mate),
+                   shapes.ctypes.data_as(C.c_void_p) if shapes is not None and n_obs else None, C.cast(ego_c, C.c_void_p),
+                   _ptr(d_pid), int(px.numel()), _ptr(px), _ptr(py), _ptr(pyaw), n_paths, _ptr(off), _ptr(arc), margin,
+                   _ptr(lead), _ptr(lead_gap), _ptr(thw), _ptr(ttc), _ptr(ttc_who), _ptr(u_ego), _ptr(ep_i), _ptr(ep_d),
+                   *[_ptr(t) if t is not None else None for t in per_place])
+        out = {"lead": lead, "lead_gap": lead_gap, "thw": thw, "ttc": ttc, "ttc_who": ttc_who, "u_ego": u_ego, "ep_i": ep_i, "ep_d": ep_d,
+               "arc": table["arc"], "path_id": pid, "veh_range": veh, "mate_range": mate, "ego_shape": tuple(float(v) for v in ego),
+               "margin": margin}
+        if places:
+            out.update(gap=per_place[0], lat=per_place[1], rate=per_place[2])
+        return out
+
     def cutoffs(self, chunk_ticks: int = 0, carry=None) -> dict:
         """The glue's decision on every recorded tick (jsim_loop_eval_cutoffs): what the loop ahead of MPC.step
         found and did -- main/scenarios/mpc_intersection.py:104-143: the progress index, check_collision_moving_cars /

@@ -1378,6 +1378,7 @@ struct jsim_ctx {
     int n_shapes = 0;
     DevArray<double4> d_conflict_rows; // [n_obs] (cc_front, cc_rear, thr, thr_sq) of jsim_loop_eval_conflicts' last call with a table
     DevArray<double4> d_gap_rows;      // the same of jsim_loop_eval_gaps' last call with a table
+    DevArray<double4> d_headway_rows;  // [n_obs] (cc_front, cc_rear, radius, thr) of jsim_loop_eval_headway's last call with a table
     DevArray<double> d_static_rows;    // [n_rows][JSIM_STATIC_ROW] and
     DevArray<int> d_static_off;        // [n_sets + 1] of jsim_loop_eval_static's last call
     DevArray<double2> d_pcc;
@@ -2560,6 +2561,55 @@ extern "C" int jsim_loop_eval_tracking(jsim_ctx *ctx, int32_t B, int32_t n_ticks
     const TrackP P = {B, n_ticks, rec, flags, path_id, n_pts, n_paths, px, py, pyaw, arc, (const long long *)path_off,
                       idx, seg, s, d, e_yaw, ep_i, ep_d};
     return launch_per_ego(ctx, tracking_ticks_kernel, B, stream, P);
+}
+
+#include "headway.inc"
+
+// Every recorded vehicle projected onto the ego's path: DEVICE pointers for the recorder's buffers, the
+// ranges, path_id, the call's own path table and the outputs, HOST pointers for `shapes` and `ego_shape` (radii and thresholds are
+// made here, on the host) with HOST counts and margin; one launch on `stream`, one wavefront per ego.
+extern "C" int jsim_loop_eval_headway(jsim_ctx *ctx, int32_t B, int32_t n_ticks, const double *rec, const int32_t *flags, int32_t n_obs,
+                                      const double *obs_rec, const double *x_first, const double *x_spawn, const int32_t *veh_range,
+                                      const int32_t *mate_range, const double *shapes, const double *ego_shape, const int32_t *path_id,
+                                      int32_t n_pts, const double *px, const double *py, const double *pyaw, int32_t n_paths,
+                                      const int64_t *path_off, const double *arc, double margin, int32_t *lead, double *lead_gap,
+                                      double *thw, double *ttc, int32_t *ttc_who, double *u_ego, int32_t *ep_i, double *ep_d, double *gap,
+                                      double *lat, double *rate, void *stream)
+{
+    const char *const F = "jsim_loop_eval_headway";
+    if (B < 0 || n_ticks < 0 || n_obs < 0 || n_pts < 0 || n_paths < 0)
+        return fail(ctx, -22, "%s: B=%d n_ticks=%d n_obs=%d n_pts=%d n_paths=%d", F, B, n_ticks, n_obs, n_pts, n_paths);
+    if (!obs_rec && n_obs > 0) return fail(ctx, -22, "%s: null obs_rec with n_obs=%d", F, n_obs);
+    if (!(margin >= 0.0) || !std::isfinite(margin)) return fail(ctx, -22, "%s: margin %g is not finite and >= 0", F, margin);
+    const void *const ptrs[] = {rec, flags, x_first, x_spawn, veh_range, mate_range, ego_shape, path_id, px, py, pyaw, path_off, arc,
+                                lead, lead_gap, thw, ttc, ttc_who, u_ego, ep_i, ep_d};
+    const char *const names[] = {"rec", "flags", "x_first", "x_spawn", "veh_range", "mate_range", "ego_shape", "path_id", "px", "py", "pyaw",
+                                 "path_off", "arc", "lead", "lead_gap", "thw", "ttc", "ttc_who", "u_ego", "ep_i", "ep_d"};
+    for (int i = 0; i < 21; ++i)
+        if (!ptrs[i]) return fail(ctx, -22, "%s: null pointer %s", F, names[i]);
+    const int n_places = !!gap + !!lat + !!rate;
+    if (n_places != 0 && n_places != 3) return fail(ctx, -22, "%s: the per-place outputs (gap, lat, rate) are given in part", F);
+    if (n_paths == 0 && B > 0) return fail(ctx, -22, "%s: n_paths=0 with B=%d", F, B);
+    if (int rc = check_ego_shape(ctx, F, ego_shape)) return rc;
+    const double cc_f = ego_shape[0], cc_r = ego_shape[1], r_ego = ego_shape[2];
+    const bool table = shapes && n_obs > 0;
+    if (table)
+        if (int rc = check_shape_rows(ctx, F, n_obs, shapes)) return rc;
+    JSIM_RECORDER_CALL(B == 0 || n_ticks == 0);
+    if (table) {                                   // (cc_front, cc_rear, radius, thr = the egos' radius + its own: the conflicts threshold)
+        std::vector<double4> rows((size_t)n_obs);
+        for (int i = 0; i < n_obs; ++i) {
+            const double *s = shapes + 4 * (size_t)i;
+            rows[i] = double4{s[0], s[1], s[2], r_ego + s[2]};
+        }
+        if (int rc = replace_table(ctx, ctx->d_headway_rows, rows.data(), (size_t)n_obs)) return rc;
+    }
+    const HeadwayP P = {{recorder_buf(B, n_ticks, rec, flags, x_first, x_spawn), n_obs, 0, n_obs > 0 ? obs_rec : nullptr, veh_range, mate_range,
+                         table ? ctx->d_headway_rows.p : nullptr, cc_f, cc_r, double4{cc_f, cc_r, r_ego, r_ego + r_ego},
+                         nullptr, nullptr, nullptr, nullptr, nullptr, nullptr},
+                        path_id, n_pts, n_paths, px, py, pyaw, arc, (const long long *)path_off, r_ego, margin,
+                        lead, lead_gap, thw, ttc, ttc_who, u_ego, ep_i, ep_d, gap, lat, rate};
+    return launch_per_ego(ctx, headway_ticks_kernel, B, stream, P);
 }
 
 // the shape table's (thr, thr_sq) rows: check_collision_moving_bicycle's min_distance = the egos' radius + the vehicle's own

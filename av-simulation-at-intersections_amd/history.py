@@ -7,7 +7,8 @@ conflict_episodes for the clearance and first contact of every episode (section 
 (section 18), episode_rows for the per-episode table that is reduced on the device (section 19), cutoff_episodes for the glue's
 collision cut-off of every tick (section 21); fork_rows, join and reasons_carry_at are the host side of a fork (section 22);
 gap_episodes for the time gap between an ego and each vehicle (section 23); path_table and tracking_episodes for the projection of
-every recorded pose onto a path (section 24)."""
+every recorded pose onto a path (section 24); headway_episodes for the space headway, time headway and time to collision between
+an ego and the vehicles on its path (section 25)."""
 from __future__ import annotations
 
 from typing import List, Optional
@@ -26,6 +27,9 @@ GAP_NONE, GAP_MAX_WINDOW = -128, 63      # JSIM_GAP_NONE, JSIM_GAP_MAX_WINDOW
 # the columns of Recorder.tracking's ep_i and ep_d, in the order of the JSIM_TRK_* enumerators of include/jsim_mpc.h
 TRK_INT = ("ticks", "d_max_tick")
 TRK_DOUBLE = ("d_max", "d2_mean", "yaw_max", "s_first", "s_last")
+# the columns of Recorder.headway's ep_i and ep_d, in the order of the JSIM_HW_* enumerators of include/jsim_mpc.h
+HW_INT = ("ticks", "lead_ticks", "gap_tick", "gap_who", "thw_tick", "ttc_tick", "ttc_who")
+HW_DOUBLE = ("gap_min", "thw_min", "ttc_min", "thw_mean")
 
 
 class History:
@@ -252,6 +256,34 @@ def tracking_episodes(result: dict, flags: np.ndarray, dt: float, stations=None,
             ep["t_station"] = [float(r[0]) * float(dt) if r.size else nan for r in reached]
         if free_speed is not None:
             ep["delay"] = n * float(dt) - ep["progress"] / float(free_speed)
+        return ep
+    return _per_episode(flags, make)
+
+
+def headway_episodes(result: dict, flags: np.ndarray, dt: float):
+    """The headway of a recorder (Recorder.headway: `ep_i`, `ep_d`) per ego and episode, split where ego_histories splits
+    (episode_bounds).  Returns a list over egos of lists over episodes of dicts: k0, n (first tick, ticks), lead_ticks (ticks with a
+    leader on the path) and time_following = lead_ticks * dt (what evaluate_time_following of
+    main/scenarios/overtaking_cyclist_bidirectional_road.py counts within a Euclidean range); gap_min (the smallest space headway to
+    a leader, in metres), gap_tick, gap_t (the first tick that has it; seconds from the episode's first tick) and gap_who (the
+    leader's place there); thw_min, thw_tick, thw_t and thw_mean (time headway, in seconds; the mean over the ticks where it is
+    finite); ttc_min, ttc_tick, ttc_t and ttc_who (time to collision, in seconds; inf: never closing).  NaN / -1 without one and in
+    an episode without a tick."""
+    ep_i, ep_d = np.asarray(result["ep_i"]), np.asarray(result["ep_d"], dtype=np.float64)
+    nan = float("nan")
+
+    def make(b, k0, k1):
+        n = k1 - k0
+        ep = {"k0": k0, "n": n, "lead_ticks": 0, "time_following": 0.0, "gap_min": nan, "gap_tick": -1, "gap_t": nan, "gap_who": -1,
+              "thw_min": nan, "thw_tick": -1, "thw_t": nan, "thw_mean": nan, "ttc_min": nan, "ttc_tick": -1, "ttc_t": nan, "ttc_who": -1}
+        if n > 0:
+            i = dict(zip(HW_INT, (int(v) for v in ep_i[k0, b])))
+            d = dict(zip(HW_DOUBLE, ep_d[k0, b].tolist()))
+            secs = lambda tick: (tick - k0) * float(dt) if tick >= 0 else nan
+            ep.update(lead_ticks=i["lead_ticks"], time_following=i["lead_ticks"] * float(dt),
+                      gap_min=d["gap_min"], gap_tick=i["gap_tick"], gap_t=secs(i["gap_tick"]), gap_who=i["gap_who"],
+                      thw_min=d["thw_min"], thw_tick=i["thw_tick"], thw_t=secs(i["thw_tick"]), thw_mean=d["thw_mean"],
+                      ttc_min=d["ttc_min"], ttc_tick=i["ttc_tick"], ttc_t=secs(i["ttc_tick"]), ttc_who=i["ttc_who"])
         return ep
     return _per_episode(flags, make)
 

@@ -537,6 +537,65 @@ int jsim_loop_eval_tracking(jsim_ctx *ctx, int32_t B, int32_t n_ticks, const dou
                             const int64_t *path_off, const double *arc, int32_t *idx, int32_t *seg, double *s, double *d,
                             double *e_yaw, int32_t *ep_i, double *ep_d, void *stream);
 
+/* ---- every recorded vehicle projected onto the ego's path: space headway, time headway, time to collision ----
+ * How much road lay between an ego and a vehicle on the same path, and how long until it is gone: what the overtaking study
+ * (main/scenarios/overtaking_cyclist_bidirectional_road.py) approximates with a Euclidean range -- create_following_trajectory keeps
+ * a distance behind the cyclist, evaluate_time_following counts the time within a range of it, plot_distance draws that distance --
+ * none of which is a distance along the road or tells a cyclist ahead from a car in the other lane.  Per tick, place and episode of
+ * every ego, from the recorder's buffers (jsim_loop_set_recorder), after the loop.  One wavefront per ego, 64 ticks at a time; the
+ * path's points are wave-uniform scalar loads and one loaded point serves every query of a group (the ego's two circle centres, then
+ * the vehicles' four places to a pass, the rest in groups of 2 and 1).  DESIGN.md section 25 is the contract.
+ *   DEVICE pointers: rec, flags, obs_rec, x_first, x_spawn, veh_range, mate_range exactly as jsim_loop_eval_conflicts takes them (the
+ *   same list: the vehicles of veh_range, then the mates of mate_range with the ego itself skipped, JSIM_MAX_OBS (8) places in all);
+ *   path_id, px, py, pyaw, path_off, arc exactly as jsim_loop_eval_tracking takes them (the table is the call's own); and every
+ *   output.  HOST: n_obs, n_pts, n_paths, margin; shapes [n_obs][4] (NULL: every vehicle has the ego's shape) and ego_shape [3] as
+ *   jsim_loop_eval_conflicts takes them: r_e = ego_shape[2], r_i = the vehicle's radius, thr_i = r_e + r_i made here on the host.
+ *   Everything is taken at the start of tick k.  The ego's pose and speed follow the replay's rule: x_first (x, y, v, yaw) at
+ *   k = 0, x_spawn behind a record that ended an episode, else rec[k - 1] (x, y, yaw, v = entries 0, 1, 2, 3); a scripted vehicle's
+ *   are obs_rec[k] (x, y, v, yaw = entries 0, 1, 2, 3); a mate's are its own by the ego's rule.  Circle centres:
+ *   (x + cos(yaw) * cc, y + sin(yaw) * cc) for cc_front and cc_rear, the ego's with its own shape, a vehicle's with its row of shapes
+ *   (a mate, and any vehicle without a table: the ego's shape) -- jsim_loop_eval_conflicts' arithmetic, operation for operation.
+ *   Each centre is projected onto path path_id[b] as jsim_loop_eval_tracking projects a pose: idx = calc_nearest_index(state, cx,
+ *   cy, 0) (main/lib/trajectories.py:89-97: ascending, replaced on strict <), the segment of {idx - 1, idx} with the smaller residual
+ *   (the lower on a tie), the foot clamped to it; s = the foot's arc length, d = the signed offset (left positive), ref = pyaw
+ *   interpolated at the foot.  Intervals along the path: E = [min(s_front, s_rear) - r_e, max(s_front, s_rear) + r_e] of the ego,
+ *   V_i likewise with r_i.  u_e = v_e * cos(yaw_e - ref) with ref at the ego's front centre's foot; u_i the same of the vehicle.
+ *   Per place [n_ticks][B][8] (double; each of gap, lat, rate may be NULL only together: then none is written and every other
+ *   output is the same):
+ *     gap = V_i.lo - E.hi if that is > 0 (ahead), else V_i.hi - E.lo if that is < 0 (behind), else 0.0 (alongside);
+ *     lat = the d of the vehicle's centre with the smaller |d|, the front centre's on a tie;
+ *     rate = u_i - u_e (negative: the gap ahead closes);
+ *     NaN for a place nobody holds and for a vehicle pose or speed that is not finite.
+ *   A place is on the path when |lat| <= thr_i + margin.  Its ttc_i: 0 when gap == 0; gap / -rate when ahead and rate < 0;
+ *   -gap / rate when behind and rate > 0; +inf when not closing; NaN off the path, absent or not finite.
+ *   Per tick [n_ticks][B]: lead (int32) = the on-path place with the smallest gap >= 0, the lowest place on a tie, -1 without one;
+ *   lead_gap = its gap (NaN without); thw = 0 when lead_gap == 0, lead_gap / u_e when u_e > 0, else +inf (NaN without a leader);
+ *   ttc = the smallest ttc_i (NaN if every one is NaN), ttc_who (int32) = the lowest place that has it (-1); u_ego = u_e.  An ego
+ *   pose or speed that is not finite, a path_id outside [0, n_paths), an empty path or an ego without vehicles and mates: -1 / NaN
+ *   throughout, u_ego and the places included.
+ *   Per episode, at the slot of its first tick (the last record closes the running episode; every other slot -1 / NaN):
+ *     ep_i [n_ticks][B][JSIM_HW_NI]: TICKS, LEAD_TICKS (ticks with lead >= 0), GAP_TICK and GAP_WHO (the first tick that holds the
+ *     smallest lead_gap and its lead), THW_TICK (the same of thw), TTC_TICK and TTC_WHO (of ttc and its ttc_who); -1 without one;
+ *     ep_d [n_ticks][B][JSIM_HW_ND]: GAP_MIN, THW_MIN, TTC_MIN (minima pass over NaN; +inf counts), THW_MEAN (the mean of thw over
+ *     the ticks where it is finite, NaN without one; added in a fixed order that depends on the ticks' places in their 64-tick chunks
+ *     alone, so a finished episode's row does not depend on how many ticks follow it).
+ *   The nearest index is global, as in jsim_loop_eval_tracking: a route that crosses itself is not served.
+ *   Refused (-22) before any device call, jsim_last_error naming the argument: B, n_ticks, n_obs, n_pts or n_paths < 0; obs_rec
+ *   NULL with n_obs > 0; n_paths = 0 with B > 0; a null pointer other than obs_rec (n_obs = 0), shapes, stream and the three of
+ *   gap, lat, rate together; an ego radius that is not positive and finite, a circle offset or a shapes radius likewise; a margin
+ *   that is not finite and >= 0; a null ctx.  n_ticks = 0 or B = 0 returns 0 and writes nothing.  A range outside its table, a list
+ *   of more than 8, a path_id or a path_off outside its table would need a device read to detect: the kernel clamps so that it never
+ *   reads outside the tables, and the Python surface (Recorder.headway) refuses with ValueError. */
+enum { JSIM_HW_TICKS = 0, JSIM_HW_LEAD_TICKS, JSIM_HW_GAP_TICK, JSIM_HW_GAP_WHO, JSIM_HW_THW_TICK, JSIM_HW_TTC_TICK, JSIM_HW_TTC_WHO, JSIM_HW_NI };
+enum { JSIM_HW_GAP_MIN = 0, JSIM_HW_THW_MIN, JSIM_HW_TTC_MIN, JSIM_HW_THW_MEAN, JSIM_HW_ND };
+int jsim_loop_eval_headway(jsim_ctx *ctx, int32_t B, int32_t n_ticks, const double *rec, const int32_t *flags, int32_t n_obs,
+                           const double *obs_rec, const double *x_first, const double *x_spawn, const int32_t *veh_range,
+                           const int32_t *mate_range, const double *shapes, const double *ego_shape, const int32_t *path_id,
+                           int32_t n_pts, const double *px, const double *py, const double *pyaw, int32_t n_paths,
+                           const int64_t *path_off, const double *arc, double margin, int32_t *lead, double *lead_gap, double *thw,
+                           double *ttc, int32_t *ttc_who, double *u_ego, int32_t *ep_i, double *ep_d, double *gap, double *lat,
+                           double *rate, void *stream);
+
 /* ---- static-obstacle clearance and contact per recorded tick: the realised poses of a run against the scenario's obstacles ----
  * Answers for driven poses what the reference only asks of planned ones: check_collision (main/lib/obstacles.py:157-176) on
  * Obstacle.to_convex(margin) (:82-93 box, :134-148 circle) -- the planner's collision test, main/lib/mp_search_ww_generic.py:199-215

@@ -1,0 +1,236 @@
+"""Every recorded vehicle projected onto the ego's path (jsim_loop_eval_headway) without a GPU: the numpy
+restatement against the reference-made fixture (tests/golden/headway.npz: car_trajectory_to_collision_point_trajectories on every
+pose, calc_nearest_index on every circle centre), the cases' own condition, the events each case is named after,
+history.headway_episodes on a hand-made result, the C entry point's declaration, binding and -22 list against the cross-compiled
+library, and the ValueErrors of Recorder.headway that need no device."""
+import math
+import os
+import re
+import types
+
+import numpy as np
+import pytest
+import torch
+
+import headway_cases as HC
+import headway_numpy as HN
+from conftest import REPO
+
+
+@pytest.fixture(scope="module")
+def cs():
+    return HC.cases()
+
+
+@pytest.fixture(scope="module")
+def arrays(cs):
+    return HC.recorder_arrays(cs)
+
+
+@pytest.fixture(scope="module")
+def ref(arrays):
+    return HC.restate(arrays)
+
+
+def test_cases_are_the_stored_ones(cs, arrays):
+    g = HC.fixture()
+    assert int(g["n_cases"]) == len(cs) == 15 and float(g["launch_margin"]) == HC.LAUNCH_MARGIN
+    for b, c in enumerate(cs):
+        assert str(g["labels"][b]) == c["label"] and int(g["path"][b]) == c["path"] and float(g["v_ego"][b]) == c["v_ego"]
+        assert np.array_equal(g["flags"][b], c["flags"])
+    assert np.array_equal(g["veh_range"], arrays["veh_range"]) and np.array_equal(g["mate_range"], arrays["mate_range"])
+    assert [len(p) for p in HC.paths()] == [1, 2, 3, 63, 64, 65, 700, 4, 5, 8, 9] and sorted({c["path"] for c in cs}) == list(range(11))
+    places = [len(HN.vehicle_list(b, len(cs), arrays["obs"].shape[1], arrays["veh_range"], arrays["mate_range"])) for b in range(len(cs))]
+    assert places == [1, 3, 2, 1, 3, 8, 1, 1, 2, 2, 0, 1, 1, 1, 1]
+    assert HC.TICK_COUNTS == (0, 1, 63, 64, 65, 129, 200) and os.path.getsize(os.path.join(REPO, "tests", "golden", "headway.npz")) < 100_000
+
+
+def test_restatement_against_the_fixture(cs, ref):
+    g = HC.fixture()
+    # the two reference-made pieces: every circle centre's nearest index, and the centres of every fifth tick
+    assert g["idx"].dtype == np.int16 and np.array_equal(ref["idx"], np.moveaxis(g["idx"], 0, 1))
+    mine = np.moveaxis(ref["centres"][::HC.CENTRE_STRIDE], 0, 1)
+    assert np.array_equal(np.isnan(mine), np.isnan(g["centres"])) and np.nanmax(np.abs(mine - g["centres"])) <= 1e-12
+    assert (g["idx"] >= 0).sum() == 16784 and np.array_equal(g["idx"] >= 0, ~np.isnan(np.moveaxis(ref["centres"], 0, 1)[..., 0]))
+    # the restatement-made part, as stored
+    for k in ("lead", "ttc_who", "ep_i"):
+        assert np.array_equal(ref[k], np.moveaxis(g[k], 0, 1)), k
+    stored = np.moveaxis(g["ep_d"], 0, 1)
+    assert np.array_equal(np.isnan(ref["ep_d"]), np.isnan(stored)) and np.array_equal(np.isinf(ref["ep_d"]), np.isinf(stored))
+    fin = np.isfinite(stored)
+    assert np.all(np.abs(ref["ep_d"][fin] - stored[fin]) <= 1e-12 * np.maximum(1.0, np.abs(stored[fin])))
+    for n in HC.TICK_COUNTS:                                             # a tick's values do not depend on the ticks that follow
+        cut = HC.restate(HC.recorder_arrays(cs), n=n, egos=[0, 5])
+        for k in ("lead", "ttc_who", "gap", "lat", "rate", "thw", "ttc"):
+            assert np.array_equal(cut[k], ref[k][:n, [0, 5]], equal_nan=True), (n, k)
+
+
+def test_condition_holds(cs, ref):
+    assert HC.condition(cs, ref) == float(HC.fixture()["margin"]) >= HC.MARGIN
+
+
+def test_cases_meet_the_kernel_structure(cs, ref):
+    """The events each case is named after are where the name says."""
+    inf = math.inf
+    # 0: ahead, alongside from tick 61, behind from tick 154; closing at 0.75 m/s, then leaving
+    g = ref["gap"][:, 0, 0]
+    assert (g[:61] > 0).all() and (g[61:154] == 0.0).all() and (g[154:] < 0).all() and (ref["rate"][:, 0, 0] == -0.75).all()
+    assert (ref["lead"][:154, 0] == 0).all() and (ref["lead"][154:, 0] == -1).all() and np.isnan(ref["thw"][154:, 0]).all()
+    assert np.array_equal(ref["ttc"][:61, 0], g[:61] / 0.75) and (ref["ttc"][61:154, 0] == 0.0).all() and (ref["ttc"][154:, 0] == inf).all()
+    assert ref["ep_i"][0, 0].tolist() == [200, 154, 61, 0, 61, 61, 0] and ref["ep_d"][0, 0, :3].tolist() == [0.0, 0.0, 0.0]
+    # 1: episodes 0..63, 64, 65..127, 128, 129..199; the cyclist in the other lane is off the path, the oncoming car is on it
+    assert HN.TN.episodes_of(cs[1]["flags"]) == [(0, 63), (64, 64), (65, 127), (128, 128), (129, 199)]
+    assert [ref["ep_i"][k, 1, 0] for k in (0, 64, 65, 128, 129)] == [64, 1, 63, 1, 71] and (ref["ep_i"][[1, 63, 66, 127, 130], 1] == -1).all()
+    assert np.isnan(ref["ttc_i"][:, 1, 1]).all() and (ref["rate"][:, 1, 1] < -2.4).all() and (ref["rate"][:, 1, 2] == -1.5).all()
+    assert (ref["ttc_who"][:64, 1] == 2).all() and set(ref["lead"][:, 1].tolist()) == {0, 2} and ref["ep_i"][129, 1, 3] == 2
+    # 2: equal speeds: rate exactly 0, TTC inf; the same gap twice: the lower place
+    both = ~np.isnan(ref["lead_gap"][:, 2]) & (ref["gap"][:, 2, 0] > 0)
+    assert both.sum() > 150 and (ref["rate"][:, 2, :2] == 0.0).all() and (ref["ttc"][both, 2] == inf).all() and (ref["ttc_who"][both, 2] == 0).all()
+    assert np.array_equal(ref["gap"][:, 2, 0], ref["gap"][:, 2, 1]) and (ref["lead"][both, 2] == 0).all() and (ref["m_lead"][both, 2] == 0.0).all()
+    assert np.array_equal(ref["thw"][both, 2], ref["lead_gap"][both, 2]) and (ref["u_ego"][:, 2] == 1.0).all()
+    # 3: a standing ego: thw inf while the cyclist is ahead, 0 alongside; the oncoming cyclist's own speed along the path is negative
+    ahead = ref["gap"][:, 3, 0] > 0
+    assert ahead[:81].all() and not ahead[81:].any() and (ref["thw"][ahead, 3] == inf).all() and (ref["u_ego"][:, 3] == 0.0).all()
+    assert (ref["rate"][:, 3, 0] == -0.5).all() and np.array_equal(ref["ttc"][ahead, 3], ref["gap"][ahead, 3, 0] / 0.5)
+    assert ref["ep_d"][0, 3, 3] == 0.0 and ref["ep_i"][0, 3, 4] == 81     # the mean passes over inf: the finite ticks are the 0.0 alongside
+    # 4: at the threshold: off, on (exactly), on; the two on the path tie: place 1 leads
+    assert np.array_equal(ref["lat"][:, 4, :3], np.tile([HC.THR_CC + HC.EPS, HC.THR_CC, HC.THR_CC - HC.EPS], (HC.N, 1)))
+    assert np.isnan(ref["ttc_i"][:, 4, 0]).all() and not np.isnan(ref["ttc_i"][:, 4, 1:3]).any() and (ref["lead"][:, 4] == 1).all()
+    assert (ref["m_on"][:, 4, 1] == 0.0).all() and (ref["m_on"][:, 4, [0, 2]] == HC.EPS).all() and (ref["m_lead"][:, 4] == 0.0).all()
+    # 5: eight places; poses and a speed that are not finite give NaN in that place on those ticks only; vehicles beyond the end
+    nan = np.isnan(ref["gap"][:, 5])
+    assert nan.sum(axis=0).tolist() == [1, 0, 0, 6, 0, 1, 0, 0] and nan[129, 0] and nan[90:96, 3].all() and nan[100, 5]
+    assert np.array_equal(nan, np.isnan(ref["rate"][:, 5])) and np.array_equal(nan, np.isnan(ref["lat"][:, 5]))
+    last = len(HC.paths()[HC.P700]) - 1
+    assert (ref["idx"][150:, 5, 8] == last).all() and np.isnan(ref["ttc_i"][:, 5, 7]).all() and not np.isnan(ref["lead_gap"][:, 5]).any()
+    assert ref["ep_i"][0, 5, 0] == 131 and ref["ep_i"][131, 5, 0] == 69
+    # 6-7: the mates see each other; 8-9: a cyclist and a mate in one list
+    assert np.array_equal(ref["gap"][:, 6, 0], -ref["gap"][:, 7, 0]) and np.array_equal(ref["rate"][:, 6, 0], -ref["rate"][:, 7, 0])
+    assert not np.isnan(ref["gap"][:, 8:10, :2]).any() and np.isnan(ref["gap"][:, 8:10, 2:]).all() and set(ref["lead"][:, 8].tolist()) == {0, 1}
+    # 10: no vehicles
+    assert (ref["lead"][:, 10] == -1).all() and (ref["ttc_who"][:, 10] == -1).all() and np.isnan(ref["u_ego"][:, 10]).all()
+    assert np.isnan(ref["gap"][:, 10]).all() and ref["ep_i"][0, 10].tolist() == [200, 0, -1, -1, -1, -1, -1] and np.isnan(ref["ep_d"][:, 10]).all()
+    # 11: one point: every arc length is 0, so everything is alongside
+    assert (ref["gap"][:, 11, 0] == 0.0).all() and (ref["lat"][:, 11, 0] > 0).all()
+
+
+def test_headway_episodes(pkg, cs, arrays, ref):
+    H = pkg.history
+    assert H.HW_INT == ("ticks", "lead_ticks", "gap_tick", "gap_who", "thw_tick", "ttc_tick", "ttc_who") and len(H.HW_INT) == HN.NI
+    assert H.HW_DOUBLE == ("gap_min", "thw_min", "ttc_min", "thw_mean") and len(H.HW_DOUBLE) == HN.ND
+    eps = H.headway_episodes(ref, arrays["flags"], 0.125)
+    for b, c in enumerate(cs):
+        mine = HN.TN.episodes_of(c["flags"])
+        assert len(eps[b]) == len(H.episode_bounds(c["flags"])) and [(e["k0"], e["n"]) for e in eps[b]][:len(mine)] == [(k0, k1 - k0 + 1) for k0, k1 in mine]
+    e = eps[0][0]
+    assert (e["lead_ticks"], e["time_following"], e["gap_tick"], e["gap_t"], e["gap_who"], e["gap_min"]) == (154, 154 * 0.125, 61, 61 * 0.125, 0, 0.0)
+    # a hand-made result: two episodes of one ego, the second without a leader
+    flags = np.zeros((8, 1), dtype=np.int32)
+    flags[4, 0] = H.GOAL
+    ep_i, ep_d = np.full((8, 1, 7), -1), np.full((8, 1, 4), np.nan)
+    ep_i[0, 0], ep_d[0, 0] = (5, 3, 2, 1, 2, 4, 0), (1.5, 0.75, 2.25, 1.25)
+    ep_i[5, 0], ep_d[5, 0] = (3, 0, -1, -1, -1, 6, 2), (np.nan, np.nan, math.inf, np.nan)
+    a, b_ = H.headway_episodes({"ep_i": ep_i, "ep_d": ep_d}, flags, 0.2)[0]
+    assert a == {"k0": 0, "n": 5, "lead_ticks": 3, "time_following": 3 * 0.2, "gap_min": 1.5, "gap_tick": 2, "gap_t": 2 * 0.2, "gap_who": 1,
+                 "thw_min": 0.75, "thw_tick": 2, "thw_t": 2 * 0.2, "thw_mean": 1.25, "ttc_min": 2.25, "ttc_tick": 4, "ttc_t": 4 * 0.2, "ttc_who": 0}
+    assert (b_["k0"], b_["n"], b_["lead_ticks"], b_["time_following"], b_["gap_tick"], b_["ttc_min"], b_["ttc_tick"], b_["ttc_t"], b_["ttc_who"]) == \
+        (5, 3, 0, 0.0, -1, math.inf, 6, 0.2, 2)
+    assert all(math.isnan(b_[k]) for k in ("gap_min", "gap_t", "thw_min", "thw_t", "thw_mean"))
+    last = H.headway_episodes({"ep_i": ep_i[:5], "ep_d": ep_d[:5]}, flags[:5], 0.2)[0][-1]     # the last record ended an episode
+    assert (last["k0"], last["n"], last["lead_ticks"], last["gap_tick"]) == (5, 0, 0, -1) and math.isnan(last["ttc_min"])
+
+
+NAMES = ("rec", "flags", "n_obs", "obs_rec", "x_first", "x_spawn", "veh_range", "mate_range", "shapes", "ego_shape", "path_id", "n_pts", "px", "py",
+         "pyaw", "n_paths", "path_off", "arc", "margin", "lead", "lead_gap", "thw", "ttc", "ttc_who", "u_ego", "ep_i", "ep_d", "gap", "lat", "rate")
+COUNTS = ("n_obs", "n_pts", "n_paths", "margin")
+REQUIRED = tuple(k for k in NAMES if k not in COUNTS + ("obs_rec", "shapes", "gap", "lat", "rate"))
+
+
+def test_entry_point_is_declared_and_bound(pkg):
+    hdr = open(os.path.join(REPO, "include", "jsim_mpc.h")).read()
+    m = re.search(r"\bint jsim_loop_eval_headway\s*\(([^;]*)\);", hdr)
+    assert m
+    decl = [a.strip() for a in m.group(1).split(",")]
+    args = [re.search(r"(\w+)$", a).group(1) for a in decl]
+    assert args == ["ctx", "B", "n_ticks", *NAMES, "stream"]
+    assert "enum { JSIM_HW_TICKS = 0, JSIM_HW_LEAD_TICKS, JSIM_HW_GAP_TICK, JSIM_HW_GAP_WHO, JSIM_HW_THW_TICK, JSIM_HW_TTC_TICK, JSIM_HW_TTC_WHO, JSIM_HW_NI };" in hdr
+    assert "enum { JSIM_HW_GAP_MIN = 0, JSIM_HW_THW_MIN, JSIM_HW_TTC_MIN, JSIM_HW_THW_MEAN, JSIM_HW_ND };" in hdr and "#define JSIM_ABI_VERSION 2 " in hdr
+    assert "overtaking_cyclist_bidirectional_road.py" in hdr and "evaluate_time_following" in hdr and "main/lib/trajectories.py:89-97" in hdr
+    assert "jsim_loop_eval_headway" in pkg._cabi.EXPORTS
+    import ctypes as C
+    want = [C.c_void_p if "*" in a else C.c_int32 if a.startswith("int32_t ") else C.c_double for a in decl]
+    assert decl[args.index("margin")] == "double margin" and pkg._cabi.load().jsim_loop_eval_headway.argtypes == want and len(want) == 34
+    doc = open(os.path.join(REPO, "INTEGRATION.md")).read()
+    row = re.search(r"^\| `jsim_loop_eval_headway` \|(.*)$", doc, flags=re.M)
+    assert row and "Recorder.headway" in row.group(1)
+    R = pkg.closed_loop.Recorder
+    assert callable(R.headway) and callable(R._headway_device) and callable(pkg.history.headway_episodes)
+    csrc = os.path.join(REPO, "av-simulation-at-intersections_amd", "csrc")
+    src = open(os.path.join(csrc, "jsim_mpc.hip")).read()
+    assert src.index("#else /* !JSIM_KERNEL_TU") < src.index('#include "tracking.inc"') < src.index('#include "headway.inc"') < src.index('#include "fork.inc"')
+    inc = open(os.path.join(csrc, "headway.inc")).read()
+    assert all(k in inc for k in ("headway_ticks_kernel", "jrw_segments(C,", "jrw_enter(C,", "const double *__restrict__ px", "jep_extreme(", "jep_sum(",
+                                  "jtk_foot(", "jcf_list(", "dx * dx + dy * dy", "d2 < best[j]"))
+    assert "asm" not in inc and "atomic" not in inc and "__shared__" not in inc
+    assert "\n## 25. " in open(os.path.join(REPO, "DESIGN.md")).read()
+
+
+def test_argument_errors_without_gpu(pkg):
+    """The header's -22 list: from the host, before any device call (there is no device here and no context to launch on)."""
+    lib = pkg._cabi.load()
+    buf = np.zeros(64)
+    shape = np.array([2.18, 0.68, 1.4142, 2.86] * 4)                    # four good rows of shapes; its first three: a good ego_shape
+    p = buf.ctypes.data                                                  # a non-null address; no refused call reads it
+
+    def call(B=1, n=1, ctx=None, **over):
+        a = {k: p for k in NAMES}
+        a.update(n_obs=4, n_pts=5, n_paths=2, margin=0.0, shapes=shape.ctypes.data, ego_shape=shape.ctypes.data)
+        a.update(over)
+        rc = lib.jsim_loop_eval_headway(ctx, B, n, *[a[k] for k in NAMES], None)
+        return rc, lib.jsim_last_error(None).decode()
+
+    who = "jsim_loop_eval_headway: "
+    bad_row = shape.copy()
+    bad_row[4 + 2] = 0.0
+    bad_ego, odd_ego = np.array([2.18, 0.68, np.inf]), np.array([2.18, np.nan, 1.0])
+    for kw, msg in ((dict(B=-1), "B=-1"), (dict(n=-1), "n_ticks=-1"), (dict(n_obs=-1), "n_obs=-1"), (dict(n_pts=-2), "n_pts=-2"),
+                    (dict(n_paths=-1), "n_paths=-1"), (dict(n_paths=0), "n_paths=0 with B=1"), (dict(obs_rec=None), "null obs_rec with n_obs=4"),
+                    (dict(margin=-0.25), "margin -0.25"), (dict(margin=math.nan), "margin nan"), (dict(margin=math.inf), "margin inf"),
+                    (dict(gap=None), "given in part"), (dict(lat=None), "given in part"), (dict(gap=None, rate=None), "given in part"),
+                    (dict(shapes=bad_row.ctypes.data), "shapes row 1"), (dict(ego_shape=bad_ego.ctypes.data), "ego_shape: radius"),
+                    (dict(ego_shape=odd_ego.ctypes.data), "ego_shape: a circle offset")):
+        rc, err = call(**kw)
+        assert rc == -22 and err.startswith(who) and msg in err, (kw, rc, err)
+    for k in REQUIRED:
+        rc, err = call(**{k: None})
+        assert rc == -22 and err == who + "null pointer " + k, (k, rc, err)
+        assert call(n=0, **{k: None})[0] == -22 and call(B=0, **{k: None})[0] == -22, k   # also with nothing to do
+    for kw in ({}, dict(n=0), dict(B=0), dict(B=0, n_paths=0), dict(n_pts=0), dict(shapes=None), dict(n_obs=0, obs_rec=None),
+               dict(gap=None, lat=None, rate=None)):
+        rc, err = call(**kw)                                              # every argument good: the missing context is what is left
+        assert rc == -22 and err == who + "null ctx", (kw, err)
+    assert not buf.any()
+
+
+def test_recorder_refusals_without_a_device(pkg):
+    """Recorder.headway checks margin, paths, path_id, shapes and mates before it asks for the records or the device: on a stand-in
+    recorder whose engine has three egos on the host."""
+    paths = HC.paths()
+    R = pkg.closed_loop.Recorder
+    eng = types.SimpleNamespace(B=3, device=torch.device("cpu"), paths=paths[1:4], path_id=torch.tensor([0, 1, 2], dtype=torch.int32),
+                                ego_shape=HC.CAR, vehicle_shapes=None, L=2.86)
+    stand_in = types.SimpleNamespace(loop=types.SimpleNamespace(eng=eng), _tracking_table=None, n_obs=2, traffic=None, groups=None)
+    for name in ("_vehicle_lists", "_ego_shape", "vehicle_ranges", "mate_ranges"):
+        setattr(stand_in, name, types.MethodType(getattr(R, name), stand_in))
+    hw = lambda **kw: R._headway_device(stand_in, **kw)
+    bad = paths[2].copy()
+    bad[0, 0] = np.inf
+    for kw, msg in ((dict(margin=-1.0), "margin must be"), (dict(margin=math.nan), "margin must be"), (dict(margin=math.inf), "margin must be"),
+                    (dict(path_id=3), "path_id outside [0, 3)"), (dict(path_id=[0, 1]), "path_id must be"), (dict(paths=paths[:2]), "need a path_id"),
+                    (dict(paths=[np.zeros((0, 3))], path_id=0), "M >= 1"), (dict(paths=[bad], path_id=0), "not finite"),
+                    (dict(shapes=np.ones((3, 4))), "shapes must be"), (dict(shapes=-np.ones((2, 4))), "shapes must be"),
+                    (dict(mates=np.zeros((2, 2))), "mates must be"), (dict(mates=[[0, 4]] * 3), "outside [0, n_obs] or a mate range"),
+                    (dict(mates=[[-1, 2]] * 3), "outside")):
+        with pytest.raises(ValueError, match=re.escape(msg)):
+            hw(**kw)
+    assert stand_in._tracking_table is not None and len(stand_in._tracking_table["arc"]) == 3     # the engine's table is kept
