@@ -192,6 +192,19 @@ class Recorder:
             raise ValueError(f"ego {b} would meet {int(count[b])} vehicles and mates (max {MAX_OBS})")
         return ego, shapes, veh, mate
 
+    def _vehicle_args(self, shapes=None, mates=None):
+        """_vehicle_lists as conflicts, gaps and headway hand it on: (the eight arguments that follow rec and flags -- n_obs, obs_rec,
+        x_first, x_spawn, veh_range, mate_range, shapes, ego_shape --, the veh_range, mate_range and ego_shape entries of the result,
+        the arrays those pointers point into: the caller holds them until its call has returned)."""
+        dev = self.loop.eng.device
+        ego, shapes, veh, mate = self._vehicle_lists(shapes, mates)
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(dev)
+        d_veh, d_mate, ego_c = up(veh), up(mate), (C.c_double * 3)(*ego)
+        _, _, x_first, x_spawn = self._buffers()
+        args = (self.n_obs, _ptr(self.obs) if self.obs is not None else None, x_first, x_spawn, _ptr(d_veh), _ptr(d_mate),
+                shapes.ctypes.data_as(C.c_void_p) if shapes is not None and self.n_obs else None, C.cast(ego_c, C.c_void_p))
+        return args, {"veh_range": veh, "mate_range": mate, "ego_shape": tuple(float(v) for v in ego)}, (d_veh, d_mate, shapes, ego_c)
+
     def conflicts(self, frame_window: int = 0, shapes=None, mates=None) -> dict:
         """Clearance and first contact of every recorded tick and episode (jsim_loop_eval_conflicts): what
         check_collision_moving_cars / check_collision_moving_bicycle of main/lib/collision_avoidance.py (:85-166) return for an
@@ -217,25 +230,17 @@ class Recorder:
         """conflicts() up to the launch: the outputs as device tensors (clear, who, row, hit_tick, hit_frame, hit_xy) and the host
         arguments used (frame_window, veh_range, mate_range, ego_shape)."""
         eng = self.loop.eng
-        B, n_obs = eng.B, self.n_obs
         w = int(frame_window)
         if w != frame_window or not 0 <= w <= 20:
             raise ValueError(f"frame_window must be an integer in 0..20, got {frame_window!r}")
-        ego, shapes, veh, mate = self._vehicle_lists(shapes, mates)
+        veh_args, used, keep = self._vehicle_args(shapes, mates)
         n = self._n(4) if n is None else n
-        dev = eng.device
-        up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(dev)
-        d_veh, d_mate = up(veh), up(mate)
         clear, hit_xy = self._new(n), self._new(n, 2)
         who, row, hit_tick, hit_frame = self._new(n, dtype=torch.int32, count=4)
-        ego_c = (C.c_double * 3)(*ego)
-        rec, flags, x_first, x_spawn = self._buffers()
-        self._call("jsim_loop_eval_conflicts", B, n, rec, flags, n_obs, _ptr(self.obs) if self.obs is not None else None,
-                   x_first, x_spawn, _ptr(d_veh), _ptr(d_mate),
-                   shapes.ctypes.data_as(C.c_void_p) if shapes is not None and n_obs else None, C.cast(ego_c, C.c_void_p), w,
+        self._call("jsim_loop_eval_conflicts", eng.B, n, _ptr(self.rec), _ptr(self.flags), *veh_args, w,
                    _ptr(clear), _ptr(who), _ptr(row), _ptr(hit_tick), _ptr(hit_frame), _ptr(hit_xy))
         return {"clear": clear, "who": who, "row": row, "hit_tick": hit_tick, "hit_frame": hit_frame, "hit_xy": hit_xy,
-                "frame_window": w, "veh_range": veh, "mate_range": mate, "ego_shape": tuple(float(v) for v in ego)}
+                "frame_window": w, **used}
 
     def gaps(self, window: int = 20, within: str = "episode", shapes=None, mates=None) -> dict:
         """The time gap between every ego and each vehicle it meets, per recorded tick and episode (jsim_loop_eval_gaps, DESIGN.md
@@ -266,27 +271,19 @@ class Recorder:
         """gaps() up to the launch: the outputs as device tensors (off, ep_gap, ep_tick, ep_who, ep_off) and the host arguments used
         (window, within, veh_range, mate_range, ego_shape)."""
         eng = self.loop.eng
-        B, n_obs = eng.B, self.n_obs
         w = int(window)
         if w != window or not 0 <= w <= history.GAP_MAX_WINDOW:
             raise ValueError(f"window must be an integer in 0..{history.GAP_MAX_WINDOW}, got {window!r}")
         if within not in ("episode", "record"):
             raise ValueError(f'within must be "episode" or "record", got {within!r}')
-        ego, shapes, veh, mate = self._vehicle_lists(shapes, mates)
+        veh_args, used, keep = self._vehicle_args(shapes, mates)
         n = self._n(4) if n is None else n
-        dev = eng.device
-        up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(dev)
-        d_veh, d_mate = up(veh), up(mate)
         off = self._new(n, 8, dtype=torch.int8)
         ep_gap, ep_tick, ep_who, ep_off = self._new(n, dtype=torch.int32, count=4)
-        ego_c = (C.c_double * 3)(*ego)
-        rec, flags, x_first, x_spawn = self._buffers()
-        self._call("jsim_loop_eval_gaps", B, n, rec, flags, n_obs, _ptr(self.obs) if self.obs is not None else None,
-                   x_first, x_spawn, _ptr(d_veh), _ptr(d_mate),
-                   shapes.ctypes.data_as(C.c_void_p) if shapes is not None and n_obs else None, C.cast(ego_c, C.c_void_p), w,
-                   int(within == "record"), _ptr(off), _ptr(ep_gap), _ptr(ep_tick), _ptr(ep_who), _ptr(ep_off))
+        self._call("jsim_loop_eval_gaps", eng.B, n, _ptr(self.rec), _ptr(self.flags), *veh_args, w, int(within == "record"),
+                   _ptr(off), _ptr(ep_gap), _ptr(ep_tick), _ptr(ep_who), _ptr(ep_off))
         return {"off": off, "ep_gap": ep_gap, "ep_tick": ep_tick, "ep_who": ep_who, "ep_off": ep_off, "window": w, "within": within,
-                "veh_range": veh, "mate_range": mate, "ego_shape": tuple(float(v) for v in ego)}
+                **used}
 
     def static_conflicts(self, obstacles, set_of=None, margin=None, include_hidden: bool = False) -> dict:
         """Clearance to and contact with the scenario's static obstacles on every recorded tick (jsim_loop_eval_static, DESIGN.md
@@ -343,6 +340,33 @@ class Recorder:
         return {"clear": clear, "who": who, "hit": hit, "off_tick": off_tick, "margin": margin, "include_hidden": bool(include_hidden),
                 "ego_shape": tuple(float(v) for v in ego), "set_of": sof}
 
+    def _path_args(self, paths=None, path_id=None):
+        """What tracking() and headway() meet of paths and path_id, checked: (the path table on the device -- x, y, yaw, off, arc --,
+        n_paths, path_id [B] on the host, the same on the device, arc as a list)."""
+        eng = self.loop.eng
+        B, dev = eng.B, eng.device
+        table = self._tracking_table if paths is None else None
+        if table is None:
+            table = history.path_table(eng.paths if paths is None else paths)
+            table["dev"] = [torch.from_numpy(table[k]).to(dev) for k in ("x", "y", "yaw", "off", "arc_flat")]
+            if paths is None:
+                self._tracking_table = table
+        n_paths = len(table["arc"])
+        own = paths is None and path_id is None                     # the engine's own: its path_id is on the device already
+        if path_id is None:
+            if paths is not None and n_paths != 1:
+                raise ValueError("paths of one's own need a path_id per ego")
+            pid = eng.path_id.cpu().numpy() if own else np.zeros(B, dtype=np.int32)
+        else:
+            pid = np.asarray(path_id)
+            if pid.dtype.kind not in "iu" or pid.shape not in ((), (B,)):
+                raise ValueError(f"path_id must be one integer or [B = {B}] integers, got {pid.dtype} {pid.shape}")
+            pid = np.array(np.broadcast_to(pid, (B,)), dtype=np.int32)
+        if ((pid < 0) | (pid >= n_paths)).any():
+            raise ValueError(f"path_id outside [0, {n_paths})")
+        d_pid = eng.path_id if own else torch.from_numpy(pid).to(dev)
+        return table["dev"], n_paths, pid, d_pid, table["arc"]
+
     def tracking(self, paths=None, path_id=None) -> dict:
         """Every recorded pose projected onto a path (jsim_loop_eval_tracking): how far along its route each
         ego was on every tick, how far beside it and how far off its heading -- what plot_trajectories_comparison of
@@ -370,36 +394,15 @@ class Recorder:
     def _tracking_device(self, paths=None, path_id=None, n=None) -> dict:
         """tracking() up to the launch: the outputs as device tensors (idx, seg, s, d, e_yaw, ep_i, ep_d) and the host arguments
         used (arc, path_id)."""
-        eng = self.loop.eng
-        B, dev = eng.B, eng.device
-        table = self._tracking_table if paths is None else None
-        if table is None:
-            table = history.path_table(eng.paths if paths is None else paths)
-            table["dev"] = [torch.from_numpy(table[k]).to(dev) for k in ("x", "y", "yaw", "off", "arc_flat")]
-            if paths is None:
-                self._tracking_table = table
-        n_paths = len(table["arc"])
-        own = paths is None and path_id is None                     # the engine's own: its path_id is on the device already
-        if path_id is None:
-            if paths is not None and n_paths != 1:
-                raise ValueError("paths of one's own need a path_id per ego")
-            pid = eng.path_id.cpu().numpy() if own else np.zeros(B, dtype=np.int32)
-        else:
-            pid = np.asarray(path_id)
-            if pid.dtype.kind not in "iu" or pid.shape not in ((), (B,)):
-                raise ValueError(f"path_id must be one integer or [B = {B}] integers, got {pid.dtype} {pid.shape}")
-            pid = np.array(np.broadcast_to(pid, (B,)), dtype=np.int32)
-        if ((pid < 0) | (pid >= n_paths)).any():
-            raise ValueError(f"path_id outside [0, {n_paths})")
-        d_pid = eng.path_id if own else torch.from_numpy(pid).to(dev)
+        B = self.loop.eng.B
+        (px, py, pyaw, off, d_arc), n_paths, pid, d_pid, arc = self._path_args(paths, path_id)
         n = self._n(4) if n is None else n
         idx, seg = self._new(n, dtype=torch.int32, count=2)
         s, d, e_yaw = self._new(n, count=3)
         ep_i, ep_d = self._new(n, len(history.TRK_INT), dtype=torch.int32), self._new(n, len(history.TRK_DOUBLE))
-        px, py, pyaw, off, arc = table["dev"]
         self._call("jsim_loop_eval_tracking", B, n, _ptr(self.rec), _ptr(self.flags), _ptr(d_pid), int(px.numel()), _ptr(px), _ptr(py),
-                   _ptr(pyaw), n_paths, _ptr(off), _ptr(arc), _ptr(idx), _ptr(seg), _ptr(s), _ptr(d), _ptr(e_yaw), _ptr(ep_i), _ptr(ep_d))
-        return {"idx": idx, "seg": seg, "s": s, "d": d, "e_yaw": e_yaw, "ep_i": ep_i, "ep_d": ep_d, "arc": table["arc"], "path_id": pid}
+                   _ptr(pyaw), n_paths, _ptr(off), _ptr(d_arc), _ptr(idx), _ptr(seg), _ptr(s), _ptr(d), _ptr(e_yaw), _ptr(ep_i), _ptr(ep_d))
+        return {"idx": idx, "seg": seg, "s": s, "d": d, "e_yaw": e_yaw, "ep_i": ep_i, "ep_d": ep_d, "arc": arc, "path_id": pid}
 
     def headway(self, paths=None, path_id=None, shapes=None, mates=None, margin: float = 0.0, places: bool = True) -> dict:
         """Every recorded vehicle projected onto the ego's path (jsim_loop_eval_headway): how much road lay
@@ -432,51 +435,23 @@ class Recorder:
     def _headway_device(self, paths=None, path_id=None, shapes=None, mates=None, margin: float = 0.0, places: bool = True, n=None) -> dict:
         """headway() up to the launch: the outputs as device tensors (lead, lead_gap, thw, ttc, ttc_who, u_ego, ep_i, ep_d and, with
         places, gap, lat, rate) and the host arguments used (arc, path_id, veh_range, mate_range, ego_shape, margin)."""
-        eng = self.loop.eng
-        B, dev, n_obs = eng.B, eng.device, self.n_obs
+        B = self.loop.eng.B
         margin = float(margin)
         if not (math.isfinite(margin) and margin >= 0.0):
             raise ValueError(f"margin must be finite and >= 0, got {margin!r}")
-        table = self._tracking_table if paths is None else None
-        if table is None:
-            table = history.path_table(eng.paths if paths is None else paths)
-            table["dev"] = [torch.from_numpy(table[k]).to(dev) for k in ("x", "y", "yaw", "off", "arc_flat")]
-            if paths is None:
-                self._tracking_table = table
-        n_paths = len(table["arc"])
-        own = paths is None and path_id is None                     # the engine's own: its path_id is on the device already
-        if path_id is None:
-            if paths is not None and n_paths != 1:
-                raise ValueError("paths of one's own need a path_id per ego")
-            pid = eng.path_id.cpu().numpy() if own else np.zeros(B, dtype=np.int32)
-        else:
-            pid = np.asarray(path_id)
-            if pid.dtype.kind not in "iu" or pid.shape not in ((), (B,)):
-                raise ValueError(f"path_id must be one integer or [B = {B}] integers, got {pid.dtype} {pid.shape}")
-            pid = np.array(np.broadcast_to(pid, (B,)), dtype=np.int32)
-        if ((pid < 0) | (pid >= n_paths)).any():
-            raise ValueError(f"path_id outside [0, {n_paths})")
-        ego, shapes, veh, mate = self._vehicle_lists(shapes, mates)
-        d_pid = eng.path_id if own else torch.from_numpy(pid).to(dev)
+        (px, py, pyaw, off, d_arc), n_paths, pid, d_pid, arc = self._path_args(paths, path_id)
+        veh_args, used, keep = self._vehicle_args(shapes, mates)
         n = self._n(4) if n is None else n
-        up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(dev)
-        d_veh, d_mate = up(veh), up(mate)
         lead, ttc_who = self._new(n, dtype=torch.int32, count=2)
         lead_gap, thw, ttc, u_ego = self._new(n, count=4)
         ep_i, ep_d = self._new(n, len(history.HW_INT), dtype=torch.int32), self._new(n, len(history.HW_DOUBLE))
         per_place = self._new(n, MAX_OBS, count=3) if places else (None, None, None)
-        px, py, pyaw, off, arc = table["dev"]
-        ego_c = (C.c_double * 3)(*ego)
-        rec, flags, x_first, x_spawn = self._buffers()
-        self._call("jsim_loop_eval_headway", B, n, rec, flags, n_obs, _ptr(self.obs) if self.obs is not None else None,
-                   x_first, x_spawn, _ptr(d_veh), _ptr(d_mate),
-                   shapes.ctypes.data_as(C.c_void_p) if shapes is not None and n_obs else None, C.cast(ego_c, C.c_void_p),
-                   _ptr(d_pid), int(px.numel()), _ptr(px), _ptr(py), _ptr(pyaw), n_paths, _ptr(off), _ptr(arc), margin,
+        self._call("jsim_loop_eval_headway", B, n, _ptr(self.rec), _ptr(self.flags), *veh_args,
+                   _ptr(d_pid), int(px.numel()), _ptr(px), _ptr(py), _ptr(pyaw), n_paths, _ptr(off), _ptr(d_arc), margin,
                    _ptr(lead), _ptr(lead_gap), _ptr(thw), _ptr(ttc), _ptr(ttc_who), _ptr(u_ego), _ptr(ep_i), _ptr(ep_d),
                    *[_ptr(t) if t is not None else None for t in per_place])
         out = {"lead": lead, "lead_gap": lead_gap, "thw": thw, "ttc": ttc, "ttc_who": ttc_who, "u_ego": u_ego, "ep_i": ep_i, "ep_d": ep_d,
-               "arc": table["arc"], "path_id": pid, "veh_range": veh, "mate_range": mate, "ego_shape": tuple(float(v) for v in ego),
-               "margin": margin}
+               "arc": arc, "path_id": pid, **used, "margin": margin}
         if places:
             out.update(gap=per_place[0], lat=per_place[1], rate=per_place[2])
         return out

@@ -10,15 +10,23 @@
 // the vehicle's threshold through the episode as uniform values and keeps the earliest frame at which the ego's front circle, and
 // the earliest at which its rear circle, touches it -- the reference's `np.argmax(mask) % len` over front ++ rear.
 
-struct ConflictP {
+// The ego's vehicle list as every call that meets it takes it (conflicts, gaps, headway): the recorder's buffers, the recorded
+// vehicles, the ego's slice of them and of its group mates, and the shapes.  What .z and .w of a row of `shapes` and of ego_row mean
+// is the caller's: conflicts and gaps pass (thr, thr_sq), headway passes (radius, thr)
+struct VehicleListP {
     RecorderBuf R;
-    int n_obs, w;
+    int n_obs;
     const double *obs_rec;    // [n][n_obs][6] or NULL (n_obs = 0)
     const int *veh_range;     // [B][2] the ego's vehicles [lo, hi) among the n_obs recorded ones
     const int *mate_range;    // [B][2] the batch range [mlo, mhi) of its group mates (itself skipped)
-    const double4 *shapes;    // [n_obs] (cc_front, cc_rear, thr, thr_sq) or NULL: every vehicle has the ego's shape
+    const double4 *shapes;    // [n_obs] (cc_front, cc_rear, .z, .w) or NULL: every vehicle has the ego's shape
     double cc_f, cc_r;        // the ego's circle offsets
-    double4 ego_row;          // (cc_front, cc_rear, thr, thr_sq) of a vehicle with the ego's shape: a mate, or any vehicle without a table
+    double4 ego_row;          // (cc_front, cc_rear, .z, .w) of a vehicle with the ego's shape: a mate, or any vehicle without a table
+};
+
+struct ConflictP {
+    VehicleListP V;           // rows: (cc_front, cc_rear, thr, thr_sq)
+    int w;
     double *clear;            // [n][B]
     int *who, *row;           // [n][B]
     int *hit_tick, *hit_frame; // [n][B], at an episode's first slot
@@ -28,44 +36,54 @@ struct ConflictP {
 // The ego's vehicle list: ns scripted vehicles from lo on, then nm mates from mlo on with the ego itself skipped; clamped to the
 // tables and to JSIM_MAX_OBS in total (the Python surface refuses what is clamped here)
 struct ConflictList { int lo, ns, mlo, nm, skip; };
-__device__ __forceinline__ ConflictList jcf_list(const ConflictP &P, int b)
+__device__ __forceinline__ ConflictList jcf_list(const VehicleListP &V, int b)
 {
     ConflictList L;
-    int lo = P.veh_range[2 * b], hi = P.veh_range[2 * b + 1];
-    lo = lo < 0 ? 0 : lo; hi = hi > P.n_obs ? P.n_obs : hi;
+    int lo = V.veh_range[2 * b], hi = V.veh_range[2 * b + 1];
+    lo = lo < 0 ? 0 : lo; hi = hi > V.n_obs ? V.n_obs : hi;
     L.lo = lo; L.ns = hi > lo ? hi - lo : 0;
     if (L.ns > JSIM_MAX_OBS) L.ns = JSIM_MAX_OBS;
-    int mlo = P.mate_range[2 * b], mhi = P.mate_range[2 * b + 1];
-    mlo = mlo < 0 ? 0 : mlo; mhi = mhi > P.R.B ? P.R.B : mhi;
+    int mlo = V.mate_range[2 * b], mhi = V.mate_range[2 * b + 1];
+    mlo = mlo < 0 ? 0 : mlo; mhi = mhi > V.R.B ? V.R.B : mhi;
     L.mlo = mlo;
-    L.skip = (b >= mlo && b < mhi) ? b : P.R.B;      // the batch index the enumeration steps over
-    L.nm = mhi > mlo ? mhi - mlo - (L.skip < P.R.B ? 1 : 0) : 0;
+    L.skip = (b >= mlo && b < mhi) ? b : V.R.B;      // the batch index the enumeration steps over
+    L.nm = mhi > mlo ? mhi - mlo - (L.skip < V.R.B ? 1 : 0) : 0;
     if (L.ns + L.nm > JSIM_MAX_OBS) L.nm = JSIM_MAX_OBS - L.ns;
     return L;
 }
 
-// Vehicle i of the list at tick k: its pose and its row (cc_front, cc_rear, thr, thr_sq)
-__device__ __forceinline__ double4 jcf_vehicle_row(const ConflictP &P, const ConflictList &L, int i)
+// Vehicle i of the list: its row; a scripted vehicle's (i < L.ns) record of tick k, its get() tuple x, y, v, yaw, ..; the batch index
+// of the mate that holds place i >= L.ns, the ego's own stepped over; and the pose either has at the start of tick k
+__device__ __forceinline__ double4 jcf_vehicle_row(const VehicleListP &V, const ConflictList &L, int i)
 {
-    return (i < L.ns && P.shapes) ? P.shapes[L.lo + i] : P.ego_row;
+    return (i < L.ns && V.shapes) ? V.shapes[L.lo + i] : V.ego_row;
 }
-__device__ __forceinline__ void jcf_vehicle_pose(const ConflictP &P, const ConflictList &L, int i, int k, double &x, double &y, double &yaw)
+__device__ __forceinline__ const double *jcf_scripted(const VehicleListP &V, const ConflictList &L, int i, int k)
+{
+    return V.obs_rec + 6 * ((size_t)k * V.n_obs + (L.lo + i));
+}
+__device__ __forceinline__ int jcf_mate(const ConflictList &L, int i)
+{
+    int m = L.mlo + (i - L.ns);
+    if (m >= L.skip) ++m;
+    return m;
+}
+__device__ __forceinline__ void jcf_vehicle_pose(const VehicleListP &V, const ConflictList &L, int i, int k, double &x, double &y, double &yaw)
 {
     if (i < L.ns) {
-        const double *c = P.obs_rec + 6 * ((size_t)k * P.n_obs + (L.lo + i));
+        const double *c = jcf_scripted(V, L, i, k);
         x = c[0]; y = c[1]; yaw = c[3];
     } else {
-        int m = L.mlo + (i - L.ns);
-        if (m >= L.skip) ++m;
-        jrw_pose(P.R, m, k, x, y, yaw);
+        jrw_pose(V.R, jcf_mate(L, i), k, x, y, yaw);
     }
 }
 
 __global__ __launch_bounds__(64) void conflict_ticks_kernel(const ConflictP P)
 {
-    const RecorderBuf &R = P.R;
+    const VehicleListP &V = P.V;
+    const RecorderBuf &R = V.R;
     const int lane = threadIdx.x, b = blockIdx.x, B = R.B, n = R.n_ticks, w = P.w, nw = 2 * P.w + 1;
-    const ConflictList L = jcf_list(P, b);
+    const ConflictList L = jcf_list(V, b);
     const int n_veh = L.ns + L.nm;
     const unsigned long long upto = ~0ull >> (63 - lane), from = ~0ull << lane;   // bits 0 .. lane, bits lane .. 63
 
@@ -94,14 +112,14 @@ __global__ __launch_bounds__(64) void conflict_ticks_kernel(const ConflictP P)
             double ex, ey, eyaw, es, ec;
             jrw_pose(R, b, k, ex, ey, eyaw);
             sincos(eyaw, &es, &ec);
-            const double ecx[2] = {ex + ec * P.cc_f, ex + ec * P.cc_r}, ecy[2] = {ey + es * P.cc_f, ey + es * P.cc_r};
+            const double ecx[2] = {ex + ec * V.cc_f, ex + ec * V.cc_r}, ecy[2] = {ey + es * V.cc_f, ey + es * V.cc_r};
             for (int i = 0; i < n_veh; ++i) {
-                const double4 sh = jcf_vehicle_row(P, L, i);
+                const double4 sh = jcf_vehicle_row(V, L, i);
                 for (int off = -w; off <= w; ++off) {
                     int kc = k - off;
                     kc = kc < ks ? ks : kc; kc = kc > ke ? ke : kc;
                     double vx, vy, vyaw, vs, vc;
-                    jcf_vehicle_pose(P, L, i, kc, vx, vy, vyaw);
+                    jcf_vehicle_pose(V, L, i, kc, vx, vy, vyaw);
                     sincos(vyaw, &vs, &vc);
                     for (int c = 0; c < 2; ++c) {
                         const double cc = c ? sh.y : sh.x;
@@ -160,7 +178,7 @@ __global__ __launch_bounds__(64) void conflict_ticks_kernel(const ConflictP P)
             double ex, ey, eyaw, es, ec;
             jrw_pose(R, b, k, ex, ey, eyaw);
             sincos(eyaw, &es, &ec);
-            fx = ex + ec * P.cc_f; fy = ey + es * P.cc_f; rx = ex + ec * P.cc_r; ry = ey + es * P.cc_r;
+            fx = ex + ec * V.cc_f; fy = ey + es * V.cc_f; rx = ex + ec * V.cc_r; ry = ey + es * V.cc_r;
         }
         jrw_segments(C, [&](int pos, int e, bool starts, bool ends) {
             if (starts) {
@@ -171,7 +189,7 @@ __global__ __launch_bounds__(64) void conflict_ticks_kernel(const ConflictP P)
                     s_px = P.hit_xy[2 * q]; s_py = P.hit_xy[2 * q + 1];
                     int i = P.hit_frame[q];
                     i = i < 0 ? 0 : (i >= n_veh ? n_veh - 1 : i);
-                    s_thr_sq = jcf_vehicle_row(P, L, i).w;
+                    s_thr_sq = jcf_vehicle_row(V, L, i).w;
                 }
             }
             if (s_tick >= 0) {

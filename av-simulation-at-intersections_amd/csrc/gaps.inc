@@ -1,6 +1,6 @@
 // The time gap between an ego and each vehicle per recorded tick (DESIGN.md section 23): for ego b, tick k and vehicle i of its list
-// (conflicts.inc's list, shapes, thresholds and circle-centre arithmetic, operation for operation), the offset `off` of smallest
-// |off| <= W at which one of the four circle pairs of (ego at tick k, vehicle i at tick k - off) touches -- off > 0: the vehicle
+// (conflicts.inc's VehicleListP: its list, shapes, thresholds and circle-centre arithmetic, operation for operation), the offset
+// `off` of smallest |off| <= W at which one of the four circle pairs of (ego at tick k, vehicle i at tick k - off) touches -- off > 0: the vehicle
 // stood here first, off < 0: the ego did; -o in front of +o.  The least frame_window at which check_collision_moving_cars /
 // check_collision_moving_bicycle (main/lib/collision_avoidance.py:68-166) report a hit on an episode is the smallest |off| of its
 // ticks.  One pass over the History recorder's buffers, walked as recorder_walk.inc says: one wavefront per ego, ticks 64 at a time,
@@ -13,7 +13,7 @@
 // of the episode's first tick when the episode ends (the last record closes the running one, as in conflicts.inc).
 
 struct GapP {
-    ConflictP C;              // the recorder's buffers, vehicles, ranges, shapes and ego circles as conflict_ticks_kernel takes them (w and the outputs unused)
+    VehicleListP V;           // rows: (cc_front, cc_rear, thr, thr_sq), as conflict_ticks_kernel takes them
     int W, within;            // the window 0 .. JSIM_GAP_MAX_WINDOW; 0: vehicle ticks of the ego's own episode only, 1: every recorded tick
     unsigned long long *off;  // [n][B] eight int8, place i in byte i
     int *ep_gap, *ep_tick, *ep_who, *ep_off; // [n][B], at an episode's first slot
@@ -22,10 +22,10 @@ struct GapP {
 __global__ __launch_bounds__(64) void gap_ticks_kernel(const GapP G)
 {
     extern __shared__ double2 jgp_centres[];         // [2][n_veh][64 + 2W]: (x, y) of circle c of vehicle i at tick k0c - W + s
-    const ConflictP &P = G.C;
-    const RecorderBuf &R = P.R;
+    const VehicleListP &V = G.V;
+    const RecorderBuf &R = V.R;
     const int lane = threadIdx.x, b = blockIdx.x, B = R.B, n = R.n_ticks, W = G.W, span = 64 + 2 * G.W;
-    const ConflictList L = jcf_list(P, b);
+    const ConflictList L = jcf_list(V, b);
     const int n_veh = L.ns + L.nm;
     const unsigned long long upto = ~0ull >> (63 - lane), from = ~0ull << lane;   // bits 0 .. lane, bits lane .. 63
     const unsigned long long none8 = 0x8080808080808080ull;                        // JSIM_GAP_NONE in every place
@@ -52,12 +52,12 @@ __global__ __launch_bounds__(64) void gap_ticks_kernel(const GapP G)
 
         // the circle centres of the vehicle ticks this chunk can reach, once
         for (int i = 0; i < n_veh; ++i) {
-            const double4 sh = jcf_vehicle_row(P, L, i);
+            const double4 sh = jcf_vehicle_row(V, L, i);
             for (int s = lane; s < span; s += 64) {
                 const int kv = k0c - W + s;
                 if (kv >= 0 && kv < n) {
                     double vx, vy, vyaw, vs, vc;
-                    jcf_vehicle_pose(P, L, i, kv, vx, vy, vyaw);
+                    jcf_vehicle_pose(V, L, i, kv, vx, vy, vyaw);
                     sincos(vyaw, &vs, &vc);
                     jgp_centres[i * span + s] = double2{vx + vc * sh.x, vy + vs * sh.x};
                     jgp_centres[(n_veh + i) * span + s] = double2{vx + vc * sh.y, vy + vs * sh.y};
@@ -72,9 +72,9 @@ __global__ __launch_bounds__(64) void gap_ticks_kernel(const GapP G)
             double ex, ey, eyaw, es, ec;
             jrw_pose(R, b, k, ex, ey, eyaw);
             sincos(eyaw, &es, &ec);
-            const double ecx[2] = {ex + ec * P.cc_f, ex + ec * P.cc_r}, ecy[2] = {ey + es * P.cc_f, ey + es * P.cc_r};
+            const double ecx[2] = {ex + ec * V.cc_f, ex + ec * V.cc_r}, ecy[2] = {ey + es * V.cc_f, ey + es * V.cc_r};
             for (int i = 0; i < n_veh; ++i) {
-                const double thr_sq = jcf_vehicle_row(P, L, i).w;
+                const double thr_sq = jcf_vehicle_row(V, L, i).w;
                 const double2 *front = jgp_centres + i * span + (lane + W), *rear = jgp_centres + (n_veh + i) * span + (lane + W);
                 // the vehicle at tick k - off against the ego at tick k: any of the four circle pairs
                 auto touches = [&](int off) {

@@ -1,35 +1,31 @@
 // Every recorded vehicle projected onto the ego's path (DESIGN.md section 25): for ego b, tick k and place i of its vehicle list
-// (conflicts.inc's list and circle-centre arithmetic, operation for operation), the road between the two along path path_id[b] of a
-// path table that is the call's own (tracking.inc's table and projection rule): the space headway `gap` of the two circle-pair
-// intervals, the lateral offset `lat` of the vehicle's nearer centre, the closing speed `rate` along the path and the time to
-// collision; per tick the leader, its gap, the time headway and the smallest TTC.  Everything is taken at the start of tick k.  One
-// pass over the History recorder's buffers, walked as recorder_walk.inc says: one wavefront per ego, ticks 64 at a time, lane t owns
-// tick k0c + t.
+// (conflicts.inc's VehicleListP, list and circle-centre arithmetic, operation for operation), the road between the two along path
+// path_id[b] of a path table that is the call's own (path_project.inc's table, clamp, search and projection rule, the text that
+// tracking.inc runs): the space headway `gap` of the two circle-pair intervals, the lateral offset `lat` of the vehicle's nearer
+// centre, the closing speed `rate` along the path and the time to collision; per tick the leader, its gap, the time headway and the
+// smallest TTC.  Everything is taken at the start of tick k.  One pass over the History recorder's buffers, walked as
+// recorder_walk.inc says: one wavefront per ego, ticks 64 at a time, lane t owns tick k0c + t.
 //
 // The search is the hot part: a lane has 2 + 2 * n_veh query points (front and rear circle centre of the ego and of each vehicle)
-// and every one is searched over the same path.  A path point's address is the same in every lane, so px / py are read through
-// restrict-qualified pointers as scalar loads, four points to a step, and one loaded point serves every query of the group that is
-// held in registers: each query keeps its own smallest squared distance and index and replaces them on strict < in ascending order
+// and every one is searched over the same path.  A path point's address is the same in every lane, so jpp_search<Q> reads px / py
+// as scalar loads, four points to a step, and one loaded point serves every query of the group that is held in registers: each
+// query keeps its own smallest squared distance and index and replaces them on strict < in ascending order
 // (calc_nearest_index(state, cx, cy, 0) of main/lib/trajectories.py:89-97).  The groups: the ego's two centres, then the vehicles
 // JSIM_HW_GROUP = 4 places (8 queries) to a pass and the rest in groups of 2 and 1 places after the binary digits of n_veh
 // (wave-uniform), so that no pass carries an absent query: two passes over the path for four vehicles, three for eight, four at the
 // most (seven).  Eight places to a pass fit without scratch too, but at 282 VGPRs -- one wavefront per SIMD; with four the kernel
 // takes 185 and two wavefronts share a SIMD (DESIGN.md section 25).  After a search each lane gathers the at most three points around
-// each index with vector loads (jtk_foot and the segment rule of tracking.inc, restated in jhw_project).  Per episode, by butterflies
-// over the segment's lanes and a wave-uniform carry (episodes.inc), written by lane 0 at the slot of the episode's first tick when
-// the episode ends (the last record closes the running one, as in conflicts.inc).
+// each index with vector loads (jpp_project).  Per episode, by butterflies over the segment's lanes and a wave-uniform carry
+// (episodes.inc), written by lane 0 at the slot of the episode's first tick when the episode ends (the last record closes the
+// running one, as in conflicts.inc).
 
 #ifndef JSIM_HW_GROUP
 #define JSIM_HW_GROUP 4       // places to a pass: 4 or 8 (a diagnostic build's -DJSIM_HW_GROUP=8)
 #endif
 
 struct HeadwayP {
-    ConflictP C;              // the recorder's buffers, vehicles and ranges as conflict_ticks_kernel takes them; the rows of `shapes` and
-                              // ego_row are (cc_front, cc_rear, radius, thr = the ego's radius + its own) here; w and the outputs unused
-    const int *path_id;       // [B]
-    int n_pts, n_paths;
-    const double *px, *py, *pyaw, *arc; // [n_pts]
-    const long long *path_off; // [n_paths + 1]
+    VehicleListP V;           // rows: (cc_front, cc_rear, radius, thr = the ego's radius + its own)
+    PathTableP T;
     double r_ego, margin;
     int *lead;                // [n][B]
     double *lead_gap, *thw, *ttc;
@@ -52,95 +48,13 @@ __device__ __forceinline__ HwState jhw_ego_state(const RecorderBuf &R, int e, in
     const double *p = R.rec + JSIM_REC_FIELDS * ((size_t)(k - 1) * R.B + e);
     return HwState{p[0], p[1], p[2], p[3]};
 }
-__device__ __forceinline__ HwState jhw_vehicle_state(const ConflictP &P, const ConflictList &L, int i, int k)
+__device__ __forceinline__ HwState jhw_vehicle_state(const VehicleListP &V, const ConflictList &L, int i, int k)
 {
     if (i < L.ns) {
-        const double *c = P.obs_rec + 6 * ((size_t)k * P.n_obs + (L.lo + i));
+        const double *c = jcf_scripted(V, L, i, k);
         return HwState{c[0], c[1], c[3], c[2]};
     }
-    int m = L.mlo + (i - L.ns);
-    if (m >= L.skip) ++m;
-    return jhw_ego_state(P.R, m, k);
-}
-
-// Q queries against the np >= 1 points of one path: a loaded point is a wave-uniform operand of every query's distance.  The table
-// is read through the constant address space: nothing writes it while the kernel runs, its addresses are the wavefront's, and this
-// kernel has more stores (three a place) than the compiler's search for a clobbering store follows -- through the restrict-qualified
-// pointers alone, which are enough in tracking.inc, the same loads come out as vector loads of one address in every lane.
-typedef const __attribute__((address_space(4))) double *jhw_table;
-template <int Q>
-__device__ __forceinline__ void jhw_search(const double *__restrict__ px, const double *__restrict__ py, int np, const double (&x)[Q],
-                                           const double (&y)[Q], int (&best_i)[Q])
-{
-    const jhw_table qx = (jhw_table)px, qy = (jhw_table)py;
-    double best[Q];
-    {
-        const double ax = qx[0], ay = qy[0];
-#pragma unroll
-        for (int j = 0; j < Q; ++j) {
-            const double dx = ax - x[j], dy = ay - y[j];
-            best[j] = dx * dx + dy * dy;
-            best_i[j] = 0;
-        }
-    }
-    int i = 1;
-    for (; i + 4 <= np; i += 4) {
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const double ax = qx[i + u], ay = qy[i + u];
-#pragma unroll
-            for (int j = 0; j < Q; ++j) {
-                const double dx = ax - x[j], dy = ay - y[j];
-                const double d2 = dx * dx + dy * dy;
-                if (d2 < best[j]) { best[j] = d2; best_i[j] = i + u; }
-            }
-        }
-    }
-    for (; i < np; ++i) {
-        const double ax = qx[i], ay = qy[i];
-#pragma unroll
-        for (int j = 0; j < Q; ++j) {
-            const double dx = ax - x[j], dy = ay - y[j];
-            const double d2 = dx * dx + dy * dy;
-            if (d2 < best[j]) { best[j] = d2; best_i[j] = i; }
-        }
-    }
-}
-
-// The point (x, y) on the path [lo, lo + np) from its nearest index: tracking.inc's segment rule -- of the segments idx - 1 and idx
-// the one with the smaller residual, the lower on a tie, the foot clamped -- and from it the arc length, the signed offset (left
-// positive) and the path's yaw at the foot
-struct HwProj { double s, d, ref; };
-__device__ __forceinline__ HwProj jhw_project(const HeadwayP &P, const double *__restrict__ px, const double *__restrict__ py, int lo,
-                                              int np, int idx, double x, double y)
-{
-    const int ia = lo + (idx > 0 ? idx - 1 : 0), ib = lo + idx, ic = lo + (idx + 1 < np ? idx + 1 : np - 1);
-    const double bx = px[ib], by = py[ib];
-    double t = 0.0, q, cross = 0.0;
-    int other = ib, seg = 0;
-    {
-        const double rx = x - bx, ry = y - by;
-        q = rx * rx + ry * ry;                                // np = 1: the point itself
-    }
-    const bool has_a = idx >= 1, has_b = idx + 1 < np;
-    TrackFoot Fa = {}, Fb = {};
-    if (has_a) Fa = jtk_foot(px[ia], py[ia], bx, by, x, y);
-    if (has_b) Fb = jtk_foot(bx, by, px[ic], py[ic], x, y);
-    if (has_a && (!has_b || !(Fb.q < Fa.q))) {                // the lower segment on a tie
-        seg = idx - 1; t = Fa.t; q = Fa.q; other = ib;
-        cross = Fa.ux * (y - py[ia]) - Fa.uy * (x - px[ia]);
-    } else if (has_b) {
-        seg = idx; t = Fb.t; q = Fb.q; other = ic;
-        cross = Fb.ux * (y - by) - Fb.uy * (x - bx);
-    }
-    const int first = lo + seg;
-    const double a0 = P.arc[first], y0 = P.pyaw[first];
-    const double root = sqrt(q);
-    HwProj R;
-    R.s = np > 1 ? a0 + t * (P.arc[other] - a0) : 0.0;
-    R.d = cross >= 0.0 ? root : -root;
-    R.ref = np > 1 ? y0 + t * (P.pyaw[other] - y0) : y0;
-    return R;
+    return jhw_ego_state(V.R, jcf_mate(L, i), k);
 }
 
 // What a tick keeps of its places: the leader and the smallest time to collision, places in ascending order, replaced on strict <
@@ -159,23 +73,23 @@ __device__ __forceinline__ void jhw_group(const HeadwayP &P, const double *__res
     int bi[2 * VG];
 #pragma unroll
     for (int j = 0; j < VG; ++j) {
-        sh[j] = jcf_vehicle_row(P.C, L, g0 + j);
+        sh[j] = jcf_vehicle_row(P.V, L, g0 + j);
         S[j] = HwState{NAN, NAN, NAN, NAN};
-        if (live) S[j] = jhw_vehicle_state(P.C, L, g0 + j, k);
+        if (live) S[j] = jhw_vehicle_state(P.V, L, g0 + j, k);
         double vs, vc;
         sincos(S[j].yaw, &vs, &vc);
         x[2 * j] = S[j].x + vc * sh[j].x; y[2 * j] = S[j].y + vs * sh[j].x;
         x[2 * j + 1] = S[j].x + vc * sh[j].y; y[2 * j + 1] = S[j].y + vs * sh[j].y;
     }
-    jhw_search<2 * VG>(px + lo, py + lo, np, x, y, bi);
+    jpp_search<2 * VG>(px + lo, py + lo, np, x, y, bi);
 #pragma unroll
     for (int j = 0; j < VG; ++j) {
         const int i = g0 + j;
         double gap = NAN, lat = NAN, rate = NAN, ttc = NAN;
         bool on = false;
         if (live && jhw_finite(S[j])) {
-            const HwProj F = jhw_project(P, px, py, lo, np, bi[2 * j], x[2 * j], y[2 * j]);
-            const HwProj R = jhw_project(P, px, py, lo, np, bi[2 * j + 1], x[2 * j + 1], y[2 * j + 1]);
+            const PathProj F = jpp_project(P.T, px, py, lo, np, bi[2 * j], x[2 * j], y[2 * j]);
+            const PathProj R = jpp_project(P.T, px, py, lo, np, bi[2 * j + 1], x[2 * j + 1], y[2 * j + 1]);
             const double v_lo = fmin(F.s, R.s) - sh[j].z, v_hi = fmax(F.s, R.s) + sh[j].z;
             const double ahead = v_lo - e_hi, behind = v_hi - e_lo;
             gap = ahead > 0.0 ? ahead : (behind < 0.0 ? behind : 0.0);
@@ -196,21 +110,16 @@ __device__ __forceinline__ void jhw_group(const HeadwayP &P, const double *__res
     }
 }
 
-// The kernel's body.  `px`, `py` (= P.px, P.py) are restrict-qualified: a search step's address is the same in every lane, and with
-// the stores of this body known not to alias the table its loads are scalar loads, the points wave-uniform operands.
+// The kernel's body.  `px`, `py` (= P.T.px, P.T.py) are restrict-qualified: the stores of this body are known not to alias the table
+// that path_project.inc's search and gather read.
 __device__ __forceinline__ void jhw_ticks(const HeadwayP &P, const double *__restrict__ px, const double *__restrict__ py)
 {
-    const RecorderBuf &R = P.C.R;
+    const RecorderBuf &R = P.V.R;
     const int lane = threadIdx.x, b = blockIdx.x, B = R.B, n = R.n_ticks;
-    const ConflictList L = jcf_list(P.C, b);
+    const ConflictList L = jcf_list(P.V, b);
     const int n_veh = L.ns + L.nm;
-    // the ego's path, clamped to the table: [lo, lo + np)
-    const int p = P.path_id[b];
-    long long lo64 = 0, hi64 = 0;
-    if (p >= 0 && p < P.n_paths) { lo64 = P.path_off[p]; hi64 = P.path_off[p + 1]; }
-    lo64 = lo64 < 0 ? 0 : (lo64 > P.n_pts ? P.n_pts : lo64);
-    hi64 = hi64 < lo64 ? lo64 : (hi64 > P.n_pts ? P.n_pts : hi64);
-    const int lo = (int)lo64, np = (int)(hi64 - lo64);
+    const PathRange pr = jpp_path(P.T, b);
+    const int lo = pr.lo, np = pr.np;
     const bool any = n_veh > 0 && np > 0;                     // (uniform: the list and the path are the wavefront's)
 
     RecChunk C = {};
@@ -231,13 +140,13 @@ __device__ __forceinline__ void jhw_ticks(const HeadwayP &P, const double *__res
             const bool live = valid && jhw_finite(E);
             double es, ec;
             sincos(E.yaw, &es, &ec);
-            const double ex[2] = {E.x + ec * P.C.cc_f, E.x + ec * P.C.cc_r}, ey[2] = {E.y + es * P.C.cc_f, E.y + es * P.C.cc_r};
+            const double ex[2] = {E.x + ec * P.V.cc_f, E.x + ec * P.V.cc_r}, ey[2] = {E.y + es * P.V.cc_f, E.y + es * P.V.cc_r};
             int ei[2];
-            jhw_search<2>(px + lo, py + lo, np, ex, ey, ei);
+            jpp_search<2>(px + lo, py + lo, np, ex, ey, ei);
             double e_lo = NAN, e_hi = NAN;
             if (live) {
-                const HwProj F = jhw_project(P, px, py, lo, np, ei[0], ex[0], ey[0]);
-                const HwProj Rr = jhw_project(P, px, py, lo, np, ei[1], ex[1], ey[1]);
+                const PathProj F = jpp_project(P.T, px, py, lo, np, ei[0], ex[0], ey[0]);
+                const PathProj Rr = jpp_project(P.T, px, py, lo, np, ei[1], ex[1], ey[1]);
                 e_lo = fmin(F.s, Rr.s) - P.r_ego; e_hi = fmax(F.s, Rr.s) + P.r_ego;
                 u_e = E.v * cos(E.yaw - F.ref);
             }
@@ -256,10 +165,7 @@ __device__ __forceinline__ void jhw_ticks(const HeadwayP &P, const double *__res
                 for (int i = any ? n_veh : 0; i < JSIM_MAX_OBS; ++i) {
                     P.gap[JSIM_MAX_OBS * q + i] = NAN; P.lat[JSIM_MAX_OBS * q + i] = NAN; P.rate[JSIM_MAX_OBS * q + i] = NAN;
                 }
-            if (!((C.s_cur >> lane) & 1ull)) {                // not an episode's first tick: no episode outputs
-                for (int j = 0; j < JSIM_HW_NI; ++j) P.ep_i[JSIM_HW_NI * q + j] = -1;
-                for (int j = 0; j < JSIM_HW_ND; ++j) P.ep_d[JSIM_HW_ND * q + j] = NAN;
-            }
+            jrw_blank_slot(C, lane, q, P.ep_i, JSIM_HW_NI, P.ep_d, JSIM_HW_ND);
         }
         // the episodes of this chunk, one after the other (every branch is uniform: the masks are ballots, the extremes the wave's)
         jrw_segments(C, [&](int pos, int e, bool starts, bool ends) {
@@ -292,5 +198,5 @@ __device__ __forceinline__ void jhw_ticks(const HeadwayP &P, const double *__res
 
 __global__ __launch_bounds__(64) void headway_ticks_kernel(const HeadwayP P)
 {
-    jhw_ticks(P, P.px, P.py);
+    jhw_ticks(P, P.T.px, P.T.py);
 }

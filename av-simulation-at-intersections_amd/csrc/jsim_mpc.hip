@@ -2364,26 +2364,53 @@ extern "C" int jsim_loop_eval_reasons(jsim_ctx *ctx, int32_t B, int32_t n_ticks,
 
 #include "conflicts.inc"
 
-// shapes [n_obs][4] = the rows of jsim_loop_set_vehicle_shapes, a HOST pointer
-static int check_shape_rows(jsim_ctx *ctx, const char *F, int n_obs, const double *shapes)
+// ---- the vehicle-list arguments of the conflicts, gaps and headway entry points ----
+// DEVICE pointers but for shapes [n_obs][4] = the rows of jsim_loop_set_vehicle_shapes and ego_shape = the egos' (cc_front, cc_rear,
+// radius), which are HOST pointers: the device rows are made here
+struct VehicleArgs {
+    int n_obs;
+    const double *obs_rec;
+    const int *veh_range, *mate_range;
+    const double *shapes, *ego_shape;
+};
+// The checks, ahead of JSIM_RECORDER_CALL
+static int check_vehicle_list(jsim_ctx *ctx, const char *F, const VehicleArgs &A)
 {
-    for (int i = 0; i < n_obs; ++i) {
-        const double *s = shapes + 4 * (size_t)i;
+    if (!A.obs_rec && A.n_obs > 0) return fail(ctx, -22, "%s: null obs_rec with n_obs=%d", F, A.n_obs);
+    if (!A.ego_shape) return fail(ctx, -22, "%s: null ego_shape", F);
+    if (int rc = check_ego_shape(ctx, F, A.ego_shape)) return rc;
+    for (int i = 0; A.shapes && i < A.n_obs; ++i) {
+        const double *s = A.shapes + 4 * (size_t)i;
         if (!std::isfinite(s[0]) || !std::isfinite(s[1]) || !(s[2] > 0.0) || !std::isfinite(s[2]))
             return fail(ctx, -22, "%s: shapes row %d needs finite circle offsets and a positive, finite radius", F, i);
     }
     return 0;
 }
-// min_distance per vehicle: the egos' radius + its own, and the squared form the rows are compared with, as rows of `table`
-static int replace_conflict_rows(jsim_ctx *ctx, DevArray<double4> &table, int n_obs, const double *shapes, double r_ego)
+// A row of a vehicle of radius r: min_distance thr = the egos' radius + its own; (thr, thr_sq: the squared form the distances are
+// compared with) for conflicts and gaps, (radius, thr) for headway
+static double4 vehicle_row(bool radius_thr, double cc_f, double cc_r, double r, double r_ego)
 {
-    std::vector<double4> rows((size_t)n_obs);
-    for (int i = 0; i < n_obs; ++i) {
-        const double *s = shapes + 4 * (size_t)i;
-        const double thr = r_ego + s[2];
-        rows[i] = double4{s[0], s[1], thr, jsim_sqrt_threshold(thr)};
+    const double thr = r_ego + r;
+    return radius_thr ? double4{cc_f, cc_r, r, thr} : double4{cc_f, cc_r, thr, jsim_sqrt_threshold(thr)};
+}
+// The device work, behind JSIM_RECORDER_CALL: the rows of `shapes` replace `table`, the call's own (a launch of another call may
+// still read that call's table), and V is the kernel's argument
+static int upload_vehicle_list(jsim_ctx *ctx, DevArray<double4> &table, const RecorderBuf &R, const VehicleArgs &A, bool radius_thr,
+                               VehicleListP &V)
+{
+    const double *e = A.ego_shape;
+    const bool rows = A.shapes && A.n_obs > 0;
+    if (rows) {
+        std::vector<double4> host((size_t)A.n_obs);
+        for (int i = 0; i < A.n_obs; ++i) {
+            const double *s = A.shapes + 4 * (size_t)i;
+            host[i] = vehicle_row(radius_thr, s[0], s[1], s[2], e[2]);
+        }
+        if (int rc = replace_table(ctx, table, host.data(), (size_t)A.n_obs)) return rc;
     }
-    return replace_table(ctx, table, rows.data(), (size_t)n_obs);
+    V = VehicleListP{R, A.n_obs, A.n_obs > 0 ? A.obs_rec : nullptr, A.veh_range, A.mate_range, rows ? table.p : nullptr, e[0], e[1],
+                     vehicle_row(radius_thr, e[0], e[1], e[2], e[2])};
+    return 0;
 }
 
 // Clearance and first contact per recorded tick: DEVICE pointers for the recorder's buffers, the ranges and
@@ -2397,23 +2424,14 @@ extern "C" int jsim_loop_eval_conflicts(jsim_ctx *ctx, int32_t B, int32_t n_tick
 {
     const char *const F = "jsim_loop_eval_conflicts";
     if (B < 0 || n_ticks < 0 || n_obs < 0) return fail(ctx, -22, "%s: B=%d n_ticks=%d n_obs=%d", F, B, n_ticks, n_obs);
-    if (!obs_rec && n_obs > 0) return fail(ctx, -22, "%s: null obs_rec with n_obs=%d", F, n_obs);
     if (frame_window < 0 || frame_window > 20) return fail(ctx, -22, "%s: frame_window=%d outside [0, 20]", F, frame_window);
-    if (!ego_shape) return fail(ctx, -22, "%s: null ego_shape", F);
     if (!rec || !flags || !x_first || !x_spawn || !veh_range || !mate_range || !clear || !who || !row || !hit_tick || !hit_frame || !hit_xy)
         return fail(ctx, -22, "%s: null device pointer", F);
-    if (int rc = check_ego_shape(ctx, F, ego_shape)) return rc;
-    const double cc_f = ego_shape[0], cc_r = ego_shape[1], r_ego = ego_shape[2];
-    const bool table = shapes && n_obs > 0;
-    if (table)
-        if (int rc = check_shape_rows(ctx, F, n_obs, shapes)) return rc;
+    const VehicleArgs A = {n_obs, obs_rec, veh_range, mate_range, shapes, ego_shape};
+    if (int rc = check_vehicle_list(ctx, F, A)) return rc;
     JSIM_RECORDER_CALL(B == 0 || n_ticks == 0);
-    if (table)
-        if (int rc = replace_conflict_rows(ctx, ctx->d_conflict_rows, n_obs, shapes, r_ego)) return rc;
-    const double thr_ee = r_ego + r_ego;
-    const ConflictP P = {recorder_buf(B, n_ticks, rec, flags, x_first, x_spawn), n_obs, frame_window, n_obs > 0 ? obs_rec : nullptr,
-                         veh_range, mate_range, table ? ctx->d_conflict_rows.p : nullptr, cc_f, cc_r,
-                         double4{cc_f, cc_r, thr_ee, jsim_sqrt_threshold(thr_ee)}, clear, who, row, hit_tick, hit_frame, hit_xy};
+    ConflictP P = {{}, frame_window, clear, who, row, hit_tick, hit_frame, hit_xy};
+    if (int rc = upload_vehicle_list(ctx, ctx->d_conflict_rows, recorder_buf(B, n_ticks, rec, flags, x_first, x_spawn), A, false, P.V)) return rc;
     return launch_per_ego(ctx, conflict_ticks_kernel, B, stream, P);
 }
 
@@ -2428,28 +2446,18 @@ extern "C" int jsim_loop_eval_gaps(jsim_ctx *ctx, int32_t B, int32_t n_ticks, co
 {
     const char *const F = "jsim_loop_eval_gaps";
     if (B < 0 || n_ticks < 0 || n_obs < 0) return fail(ctx, -22, "%s: B=%d n_ticks=%d n_obs=%d", F, B, n_ticks, n_obs);
-    if (!obs_rec && n_obs > 0) return fail(ctx, -22, "%s: null obs_rec with n_obs=%d", F, n_obs);
     if (window < 0 || window > JSIM_GAP_MAX_WINDOW) return fail(ctx, -22, "%s: window=%d outside [0, %d]", F, window, JSIM_GAP_MAX_WINDOW);
     if (within != 0 && within != 1) return fail(ctx, -22, "%s: within=%d is neither 0 (episode) nor 1 (record)", F, within);
-    if (!ego_shape) return fail(ctx, -22, "%s: null ego_shape", F);
     if (!rec || !flags || !x_first || !x_spawn || !veh_range || !mate_range) return fail(ctx, -22, "%s: null device pointer", F);
     const void *const outs[] = {off, ep_gap, ep_tick, ep_who, ep_off};
     const char *const out_names[] = {"off", "ep_gap", "ep_tick", "ep_who", "ep_off"};
     for (int i = 0; i < 5; ++i)
         if (!outs[i]) return fail(ctx, -22, "%s: null output %s", F, out_names[i]);
-    if (int rc = check_ego_shape(ctx, F, ego_shape)) return rc;
-    const double cc_f = ego_shape[0], cc_r = ego_shape[1], r_ego = ego_shape[2];
-    const bool table = shapes && n_obs > 0;
-    if (table)
-        if (int rc = check_shape_rows(ctx, F, n_obs, shapes)) return rc;
+    const VehicleArgs A = {n_obs, obs_rec, veh_range, mate_range, shapes, ego_shape};
+    if (int rc = check_vehicle_list(ctx, F, A)) return rc;
     JSIM_RECORDER_CALL(B == 0 || n_ticks == 0);
-    if (table)
-        if (int rc = replace_conflict_rows(ctx, ctx->d_gap_rows, n_obs, shapes, r_ego)) return rc;
-    const double thr_ee = r_ego + r_ego;
-    const GapP P = {{recorder_buf(B, n_ticks, rec, flags, x_first, x_spawn), n_obs, 0, n_obs > 0 ? obs_rec : nullptr, veh_range, mate_range,
-                     table ? ctx->d_gap_rows.p : nullptr, cc_f, cc_r, double4{cc_f, cc_r, thr_ee, jsim_sqrt_threshold(thr_ee)},
-                     nullptr, nullptr, nullptr, nullptr, nullptr, nullptr},
-                    window, within, reinterpret_cast<unsigned long long *>(off), ep_gap, ep_tick, ep_who, ep_off};
+    GapP P = {{}, window, within, reinterpret_cast<unsigned long long *>(off), ep_gap, ep_tick, ep_who, ep_off};
+    if (int rc = upload_vehicle_list(ctx, ctx->d_gap_rows, recorder_buf(B, n_ticks, rec, flags, x_first, x_spawn), A, false, P.V)) return rc;
     // no list is longer than the recorded vehicles plus the other egos, or than JSIM_MAX_OBS (jcf_list clamps to both)
     const int longest = std::min<long long>(JSIM_MAX_OBS, (long long)n_obs + B - 1);
     const size_t lds = sizeof(double2) * 2 * (size_t)std::max(longest, 1) * (size_t)(64 + 2 * window);
@@ -2540,7 +2548,18 @@ extern "C" int jsim_loop_summarise_episodes(jsim_ctx *ctx, int32_t B, int32_t n_
     return B > 0 ? launch_per_ego(ctx, episode_summary_kernel, B, stream, P) : 0;
 }
 
+#include "path_project.inc"
 #include "tracking.inc"
+
+// The call's own path table as the tracking and headway entry points take it, behind their null-pointer loops: DEVICE pointers with
+// HOST counts (n_pts, n_paths >= 0 checked with the call's other counts)
+static int path_table(jsim_ctx *ctx, const char *F, int B, const int32_t *path_id, int n_pts, const double *px, const double *py,
+                      const double *pyaw, int n_paths, const int64_t *path_off, const double *arc, PathTableP &T)
+{
+    if (n_paths == 0 && B > 0) return fail(ctx, -22, "%s: n_paths=0 with B=%d", F, B);
+    T = PathTableP{path_id, n_pts, n_paths, px, py, pyaw, arc, (const long long *)path_off};
+    return 0;
+}
 
 // Every recorded pose projected onto a path: DEVICE pointers throughout -- the recorder's buffers, path_id,
 // the call's own path table and the outputs -- with HOST counts; one launch on `stream`, one wavefront per ego.
@@ -2556,10 +2575,9 @@ extern "C" int jsim_loop_eval_tracking(jsim_ctx *ctx, int32_t B, int32_t n_ticks
     const char *const names[] = {"rec", "flags", "path_id", "px", "py", "pyaw", "path_off", "arc", "idx", "seg", "s", "d", "e_yaw", "ep_i", "ep_d"};
     for (int i = 0; i < 15; ++i)
         if (!ptrs[i]) return fail(ctx, -22, "%s: null pointer %s", F, names[i]);
-    if (n_paths == 0 && B > 0) return fail(ctx, -22, "%s: n_paths=0 with B=%d", F, B);
+    TrackP P = {B, n_ticks, rec, flags, {}, idx, seg, s, d, e_yaw, ep_i, ep_d};
+    if (int rc = path_table(ctx, F, B, path_id, n_pts, px, py, pyaw, n_paths, path_off, arc, P.T)) return rc;
     JSIM_RECORDER_CALL(B == 0 || n_ticks == 0);
-    const TrackP P = {B, n_ticks, rec, flags, path_id, n_pts, n_paths, px, py, pyaw, arc, (const long long *)path_off,
-                      idx, seg, s, d, e_yaw, ep_i, ep_d};
     return launch_per_ego(ctx, tracking_ticks_kernel, B, stream, P);
 }
 
@@ -2579,7 +2597,6 @@ extern "C" int jsim_loop_eval_headway(jsim_ctx *ctx, int32_t B, int32_t n_ticks,
     const char *const F = "jsim_loop_eval_headway";
     if (B < 0 || n_ticks < 0 || n_obs < 0 || n_pts < 0 || n_paths < 0)
         return fail(ctx, -22, "%s: B=%d n_ticks=%d n_obs=%d n_pts=%d n_paths=%d", F, B, n_ticks, n_obs, n_pts, n_paths);
-    if (!obs_rec && n_obs > 0) return fail(ctx, -22, "%s: null obs_rec with n_obs=%d", F, n_obs);
     if (!(margin >= 0.0) || !std::isfinite(margin)) return fail(ctx, -22, "%s: margin %g is not finite and >= 0", F, margin);
     const void *const ptrs[] = {rec, flags, x_first, x_spawn, veh_range, mate_range, ego_shape, path_id, px, py, pyaw, path_off, arc,
                                 lead, lead_gap, thw, ttc, ttc_who, u_ego, ep_i, ep_d};
@@ -2589,26 +2606,12 @@ extern "C" int jsim_loop_eval_headway(jsim_ctx *ctx, int32_t B, int32_t n_ticks,
         if (!ptrs[i]) return fail(ctx, -22, "%s: null pointer %s", F, names[i]);
     const int n_places = !!gap + !!lat + !!rate;
     if (n_places != 0 && n_places != 3) return fail(ctx, -22, "%s: the per-place outputs (gap, lat, rate) are given in part", F);
-    if (n_paths == 0 && B > 0) return fail(ctx, -22, "%s: n_paths=0 with B=%d", F, B);
-    if (int rc = check_ego_shape(ctx, F, ego_shape)) return rc;
-    const double cc_f = ego_shape[0], cc_r = ego_shape[1], r_ego = ego_shape[2];
-    const bool table = shapes && n_obs > 0;
-    if (table)
-        if (int rc = check_shape_rows(ctx, F, n_obs, shapes)) return rc;
+    const VehicleArgs A = {n_obs, obs_rec, veh_range, mate_range, shapes, ego_shape};
+    HeadwayP P = {{}, {}, ego_shape[2], margin, lead, lead_gap, thw, ttc, ttc_who, u_ego, ep_i, ep_d, gap, lat, rate};
+    if (int rc = path_table(ctx, F, B, path_id, n_pts, px, py, pyaw, n_paths, path_off, arc, P.T)) return rc;
+    if (int rc = check_vehicle_list(ctx, F, A)) return rc;
     JSIM_RECORDER_CALL(B == 0 || n_ticks == 0);
-    if (table) {                                   // (cc_front, cc_rear, radius, thr = the egos' radius + its own: the conflicts threshold)
-        std::vector<double4> rows((size_t)n_obs);
-        for (int i = 0; i < n_obs; ++i) {
-            const double *s = shapes + 4 * (size_t)i;
-            rows[i] = double4{s[0], s[1], s[2], r_ego + s[2]};
-        }
-        if (int rc = replace_table(ctx, ctx->d_headway_rows, rows.data(), (size_t)n_obs)) return rc;
-    }
-    const HeadwayP P = {{recorder_buf(B, n_ticks, rec, flags, x_first, x_spawn), n_obs, 0, n_obs > 0 ? obs_rec : nullptr, veh_range, mate_range,
-                         table ? ctx->d_headway_rows.p : nullptr, cc_f, cc_r, double4{cc_f, cc_r, r_ego, r_ego + r_ego},
-                         nullptr, nullptr, nullptr, nullptr, nullptr, nullptr},
-                        path_id, n_pts, n_paths, px, py, pyaw, arc, (const long long *)path_off, r_ego, margin,
-                        lead, lead_gap, thw, ttc, ttc_who, u_ego, ep_i, ep_d, gap, lat, rate};
+    if (int rc = upload_vehicle_list(ctx, ctx->d_headway_rows, recorder_buf(B, n_ticks, rec, flags, x_first, x_spawn), A, true, P.V)) return rc;
     return launch_per_ego(ctx, headway_ticks_kernel, B, stream, P);
 }
 

@@ -1,6 +1,6 @@
 // How the History recorder's buffers (jsim_loop_set_recorder) are read, stated once for reason_ticks_kernel, conflict_ticks_kernel,
-// static_ticks_kernel and the episode kernels (DESIGN.md section 20).  One wavefront per ego, ticks 64 at a time, lane t owns tick
-// k0 + t.  Every mask is a ballot, so every branch on one is uniform.
+// static_ticks_kernel, the episode kernels and the per-tick kernels that came after them (DESIGN.md section 20).  One wavefront per
+// ego, ticks 64 at a time, lane t owns tick k0 + t.  Every mask is a ballot, so every branch on one is uniform.
 
 struct RecorderBuf {
     int B, n_ticks;
@@ -81,4 +81,13 @@ template <class F> __device__ __forceinline__ void jrw_segments(const RecChunk &
         body(pos, e, ((C.s_cur >> pos) & 1ull) != 0ull, rem != 0ull);
         pos = e + 1;
     }
+}
+
+// Slot q = this lane's tick of an episode table ep_i [n][B][ni], ep_d [n][B][nd]: off an episode's first tick it holds no episode
+// outputs, -1 and NaN
+__device__ __forceinline__ void jrw_blank_slot(const RecChunk &C, int lane, size_t q, int *ep_i, int ni, double *ep_d, int nd)
+{
+    if ((C.s_cur >> lane) & 1ull) return;
+    for (int j = 0; j < ni; ++j) ep_i[ni * q + j] = -1;
+    for (int j = 0; j < nd; ++j) ep_d[nd * q + j] = NAN;
 }

@@ -214,7 +214,7 @@ def test_entry_point_is_declared_and_bound(pkg):
     src = open(os.path.join(csrc, "jsim_mpc.hip")).read()
     assert src.index("#else /* !JSIM_KERNEL_TU") < src.index('#include "conflicts.inc"') < src.index('#include "gaps.inc"') < src.index('#include "fork.inc"')
     inc = open(os.path.join(csrc, "gaps.inc")).read()
-    assert all(k in inc for k in ("jcf_list(P, b)", "jcf_vehicle_row(P, L, i)", "jcf_vehicle_pose(P, L, i, kv,", "jrw_segments(C,", "extern __shared__ double2"))
+    assert all(k in inc for k in ("jcf_list(V, b)", "jcf_vehicle_row(V, L, i)", "jcf_vehicle_pose(V, L, i, kv,", "jrw_segments(C,", "extern __shared__ double2"))
     assert "asm" not in inc and "atomic" not in inc
     assert "dx * dx + dy * dy" in inc and "d2 <= thr_sq" in inc and "\n## 23. " in open(os.path.join(REPO, "DESIGN.md")).read()
 

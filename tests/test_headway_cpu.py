@@ -167,11 +167,12 @@ def test_entry_point_is_declared_and_bound(pkg):
     assert callable(R.headway) and callable(R._headway_device) and callable(pkg.history.headway_episodes)
     csrc = os.path.join(REPO, "av-simulation-at-intersections_amd", "csrc")
     src = open(os.path.join(csrc, "jsim_mpc.hip")).read()
-    assert src.index("#else /* !JSIM_KERNEL_TU") < src.index('#include "tracking.inc"') < src.index('#include "headway.inc"') < src.index('#include "fork.inc"')
-    inc = open(os.path.join(csrc, "headway.inc")).read()
+    assert src.index("#else /* !JSIM_KERNEL_TU") < src.index('#include "path_project.inc"') < src.index('#include "tracking.inc"') < src.index('#include "headway.inc"') < src.index('#include "fork.inc"')
+    inc, proj = (open(os.path.join(csrc, f)).read() for f in ("headway.inc", "path_project.inc"))
     assert all(k in inc for k in ("headway_ticks_kernel", "jrw_segments(C,", "jrw_enter(C,", "const double *__restrict__ px", "jep_extreme(", "jep_sum(",
-                                  "jtk_foot(", "jcf_list(", "dx * dx + dy * dy", "d2 < best[j]"))
-    assert "asm" not in inc and "atomic" not in inc and "__shared__" not in inc
+                                  "jcf_list(", "jpp_search<2 * VG>(", "jpp_project(P.T,"))
+    assert all(k in proj for k in ("jtk_foot(", "dx * dx + dy * dy", "d2 < best[j]"))
+    assert all("asm" not in t and "atomic" not in t and "__shared__" not in t for t in (inc, proj))
     assert "\n## 25. " in open(os.path.join(REPO, "DESIGN.md")).read()
 
 
@@ -220,7 +221,7 @@ def test_recorder_refusals_without_a_device(pkg):
     eng = types.SimpleNamespace(B=3, device=torch.device("cpu"), paths=paths[1:4], path_id=torch.tensor([0, 1, 2], dtype=torch.int32),
                                 ego_shape=HC.CAR, vehicle_shapes=None, L=2.86)
     stand_in = types.SimpleNamespace(loop=types.SimpleNamespace(eng=eng), _tracking_table=None, n_obs=2, traffic=None, groups=None)
-    for name in ("_vehicle_lists", "_ego_shape", "vehicle_ranges", "mate_ranges"):
+    for name in ("_vehicle_lists", "_ego_shape", "vehicle_ranges", "mate_ranges", "_path_args", "_vehicle_args"):
         setattr(stand_in, name, types.MethodType(getattr(R, name), stand_in))
     hw = lambda **kw: R._headway_device(stand_in, **kw)
     bad = paths[2].copy()

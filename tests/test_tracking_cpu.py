@@ -226,10 +226,11 @@ def test_entry_point_is_declared_and_bound(pkg):
     assert callable(R.tracking) and callable(R._tracking_device) and callable(pkg.history.tracking_episodes)
     csrc = os.path.join(REPO, "av-simulation-at-intersections_amd", "csrc")
     src = open(os.path.join(csrc, "jsim_mpc.hip")).read()
-    assert src.index("#else /* !JSIM_KERNEL_TU") < src.index('#include "episodes.inc"') < src.index('#include "tracking.inc"') < src.index('#include "fork.inc"')
-    inc = open(os.path.join(csrc, "tracking.inc")).read()
-    assert all(k in inc for k in ("jrw_segments(C,", "jrw_enter(C,", "const double *__restrict__ px", "jep_extreme(", "dx * dx + dy * dy", "d2[j] < best"))
-    assert "asm" not in inc and "atomic" not in inc and "__shared__" not in inc
+    assert src.index("#else /* !JSIM_KERNEL_TU") < src.index('#include "episodes.inc"') < src.index('#include "path_project.inc"') < src.index('#include "tracking.inc"') < src.index('#include "fork.inc"')
+    inc, proj = (open(os.path.join(csrc, f)).read() for f in ("tracking.inc", "path_project.inc"))
+    assert all(k in inc for k in ("jrw_segments(C,", "jrw_enter(C,", "const double *__restrict__ px", "jep_extreme(", "jpp_search<1>(", "jpp_project(P.T,"))
+    assert all(k in proj for k in ("const double *__restrict__ px", "dx * dx + dy * dy", "d2 < best[j]", "jtk_foot("))
+    assert all("asm" not in t and "atomic" not in t and "__shared__" not in t for t in (inc, proj))
     assert "\n## 24. " in open(os.path.join(REPO, "DESIGN.md")).read()
 
 
@@ -269,6 +270,7 @@ def test_recorder_refusals_without_a_device(pkg):
     paths = KC.paths()
     eng = types.SimpleNamespace(B=3, device=torch.device("cpu"), paths=paths[1:4], path_id=torch.tensor([0, 1, 2], dtype=torch.int32))
     stand_in = types.SimpleNamespace(loop=types.SimpleNamespace(eng=eng), _tracking_table=None)
+    stand_in._path_args = types.MethodType(pkg.closed_loop.Recorder._path_args, stand_in)
     track = lambda **kw: pkg.closed_loop.Recorder._tracking_device(stand_in, kw.get("paths"), kw.get("path_id"))
     bad = paths[2].copy()
     bad[0, 0] = np.inf
@@ -280,3 +282,18 @@ def test_recorder_refusals_without_a_device(pkg):
         with pytest.raises(ValueError, match=re.escape(msg)):
             track(**kw)
     assert stand_in._tracking_table is not None and len(stand_in._tracking_table["arc"]) == 3     # the engine's table is kept
+
+
+def test_vehicle_list_and_path_projection_are_stated_once():
+    """What the evaluators share is written once under csrc/: headway's own copies of the search and of the segment rule are gone, no
+    struct embeds the conflicts kernel's whole argument to get at the vehicle list, and the path clamp and the segment rule each
+    have one text."""
+    csrc = os.path.join(REPO, "av-simulation-at-intersections_amd", "csrc")
+    texts = {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc))}
+    whole = "\n".join(texts.values())
+    assert "jhw_project" not in whole and "jhw_search" not in whole
+    assert not re.search(r"\bConflictP\s+\w+\s*;", whole)                 # a member `ConflictP C;` of another struct
+    for text, home in (("lo64 < 0 ? 0", "path_project.inc"), ("the lower segment on a tie", "path_project.inc")):
+        assert whole.count(text) == 1 and text in texts[home], text
+    assert whole.count("struct VehicleListP {") == 1 and whole.count("struct PathTableP {") == 1
+    assert whole.count("m >= L.skip") + whole.count("mate >= L.skip") == 1   # the enumeration of the mates
