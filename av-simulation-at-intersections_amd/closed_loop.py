@@ -5,7 +5,6 @@ from __future__ import annotations
 
 import ctypes as C
 import math
-import warnings
 from typing import Optional
 
 import numpy as np
@@ -13,598 +12,9 @@ import torch
 
 from . import _cabi, history
 from .batched import BatchedMPC, _ptr
-
-
-class Recorder:
-    """The device History recorder of a loop (jsim_loop_set_recorder): every tick of every ego -- state after the plant step
-    (before a respawn), applied (delta, a), xref deviation, flags -- and the scripted vehicles' get() tuples, written by the loop's
-    kernels into [cap] tick slots (slot = the loop's device tick counter; ticks beyond cap are dropped).  The engine's context
-    holds one recorder: the one of the loop constructed last on it; an earlier one is marked `superseded` and warns when read.
-
-    histories(b): lib.simulation.History objects, one per episode of ego b; obstacle_positions(): the scripts'
-    obstacles_positions; episodes(): per-ego episode counts, lengths and ends.  These synchronise (device -> host copies)."""
-
-    def __init__(self, loop: "ClosedLoop", cap: int, n_obs: int = 0, groups=None):
-        eng = loop.eng
-        if cap < 1:
-            raise ValueError("record must be a positive number of ticks")
-        self.loop, self.cap, self.n_obs = loop, int(cap), int(n_obs)
-        dev = eng.device
-        self.rec = torch.zeros(self.cap, eng.B, 7, dtype=torch.float64, device=dev)
-        self.flags = torch.zeros(self.cap, eng.B, dtype=torch.int32, device=dev)
-        # one row more than registered: the slot host ticks of ScenarioLoop write beyond cap (dropped)
-        self._obs = torch.zeros(self.cap + 1, self.n_obs, 6, dtype=torch.float64, device=dev) if self.n_obs > 0 else None
-        self.obs = self._obs[: self.cap] if self._obs is not None else None
-        self.x0_first = loop.x0.clone()
-        self.traffic = eng.traffic_layout  # (set_of, obs_off) of the loop's traffic sets, or None: whose vehicle is whose
-        self.groups = None if groups is None else np.array(groups, dtype=np.int32)   # InteractingLoop's group offsets: whose mate is who
-        self.superseded = False          # set when a later loop on the same engine registers its own recorder (or none)
-        self.glue = None                 # a _GlueLoop's frame_window, margin, n_steps, mode and interacting (cutoffs()); None: no glue
-        self._tracking_table = None      # the engine's paths as tracking() takes them, made at its first call
-        _register_recorder(eng, self)
-
-    def _record_obstacles(self, get: torch.Tensor):
-        """Host ticks of ScenarioLoop: this tick's get() tuples (ahead of step()) to the slot of the tick just advanced."""
-        k = (self.loop.tick_counter.to(torch.int64) - 1).clamp_(0, self.cap)
-        self._obs.index_copy_(0, k, get.unsqueeze(0))
-
-    @property
-    def ticks_run(self) -> int:
-        return int(self.loop.tick_counter.item())
-
-    @property
-    def overflow(self) -> bool:
-        """True once more ticks ran than the recorder holds (the later ones were dropped)."""
-        return history.recorded_ticks(self.ticks_run, self.cap)[1]
-
-    def _n(self, stacklevel: int = 3) -> int:
-        if self.superseded:
-            warnings.warn("a later loop on this engine replaced this recorder: its records stopped at that point",
-                          RuntimeWarning, stacklevel=stacklevel)
-        n, over = history.recorded_ticks(self.ticks_run, self.cap)
-        if over:
-            warnings.warn(f"the recorder holds {self.cap} ticks, {self.ticks_run} ran: the last {self.ticks_run - self.cap} are not "
-                          "recorded", RuntimeWarning, stacklevel=stacklevel)
-        return n
-
-    def _buffers(self):
-        """rec, flags, x_first, x_spawn as the entry points that read the recorder take them."""
-        return _ptr(self.rec), _ptr(self.flags), _ptr(self.x0_first), _ptr(self.loop.x0_spawn)
-
-    def _new(self, n: int, *shape, dtype=torch.float64, count: Optional[int] = None):
-        """An output [n][B]...: `count` of them as a tuple, or one.  (No ticks yet: still valid pointers.)"""
-        eng = self.loop.eng
-        out = tuple(torch.empty(max(n, 1), eng.B, *shape, dtype=dtype, device=eng.device)[:n] for _ in range(count or 1))
-        return out if count else out[0]
-
-    def _ego_shape(self):
-        """(cc_front, cc_rear, radius) of the egos: the engine's registered shape, else the reference car's at its wheelbase."""
-        eng = self.loop.eng
-        return eng.ego_shape if eng.ego_shape is not None else vehicle_shape(L=eng.L)[:3]
-
-    def _call(self, name: str, *args):
-        """Entry point `name` on the engine's context and stream; a refusal raises with the library's message."""
-        eng = self.loop.eng
-        _cabi.check(getattr(eng.lib, name)(eng._ctx, *args, eng._stream()), eng._ctx, name)
-
-    def histories(self, b: int):
-        n = self._n()
-        eng = self.loop.eng
-        return history.ego_histories(self.rec[:n, b].cpu().numpy(), self.flags[:n, b].cpu().numpy(), eng.dt,
-                                     self.x0_first[b].cpu().numpy(), self.loop.x0_spawn[b].cpu().numpy())
-
-    def obstacle_positions(self):
-        n = self._n()
-        return history.obstacle_positions(self.obs[:n].cpu().numpy() if self.obs is not None else None)
-
-    def episodes(self):
-        return history.episodes(self.flags[: self._n()].cpu().numpy())
-
-    def default_cyclist(self) -> np.ndarray:
-        """Each ego's moving_obstacles[0] among the recorded vehicles ([B] int32): vehicle 0 of a shared list, the first vehicle of
-        the ego's own set under a traffic layout, -1 for an ego whose set is empty."""
-        B = self.loop.eng.B
-        if self.traffic is None:
-            return np.zeros(B, dtype=np.int32)
-        set_of, obs_off = self.traffic
-        return np.where(obs_off[set_of + 1] > obs_off[set_of], obs_off[set_of], -1).astype(np.int32)
-
-    def reasons(self, par=None, threshold=0.7, cyclist=None, carry=None) -> dict:
-        """The stakeholder reasons of every recorded tick and the replan trigger (jsim_loop_eval_reasons):
-        what evaluate_reasons and reasons_evaluation of main/scenarios/overtaking_cyclist_bidirectional_road.py (:2007-2027,
-        :1907-1940) give when called in the loop, computed in one launch from the records.
-
-        par: one reasons.par_row or [B] rows (default: the reference's values with DT = the loop's sample time); threshold: one
-        number or [B] (ReasonParameters.REASONS_THRESHOLD); cyclist: the recorded vehicle that is each ego's moving_obstacles[0],
-        one index or [B], -1 = none (default: default_cyclist()); carry: [B][3] = time_elapsed_driver, time_passed_cyclist and the
-        replan tracker (0 / 1) the first recorded tick starts from (default: zeros).
-        Returns numpy arrays: policymaker, driver, cyclist, distance [n][B]; timers [n][B][2]; replan [n][B] bool; below [n][B][3]
-        bool (policymaker, driver, cyclist under the threshold); first_replan [B] (-1: none); carry [B][3] as the next tick would
-        meet it; ends [n][B] bool (the records that ended an episode: history.reasons_carry_at gives the carry any tick meets);
-        and the par, threshold and veh_of used.  An ego without a cyclist has NaN in driver, cyclist and distance and
-        never triggers on them.  ValueError: no vehicles recorded, a bad par / threshold / carry, a cyclist index out of range."""
-        d = self._reasons_device(par, threshold, cyclist, carry)
-        val, trig = d["val"].cpu().numpy(), d["trig"].cpu().numpy()
-        return {"policymaker": val[:, :, 0], "driver": val[:, :, 1], "cyclist": val[:, :, 2], "distance": val[:, :, 3],
-                "timers": d["timers"].cpu().numpy(), "replan": (trig & 1) != 0, "below": ((trig[:, :, None] >> np.arange(1, 4)) & 1) != 0,
-                "first_replan": d["first"].cpu().numpy(), "carry": d["carry"].cpu().numpy(),
-                "ends": (self.flags[: val.shape[0]].cpu().numpy() & (history.GOAL | history.AGE)) != 0, "par": np.array(d["par"]),
-                "threshold": np.array(d["threshold"]), "veh_of": np.array(d["veh_of"], dtype=np.int32)}
-
-    def _reasons_device(self, par=None, threshold=0.7, cyclist=None, carry=None, n=None) -> dict:
-        """reasons() up to the launch: the outputs as device tensors (val [n][B][4], timers, trig, first, carry) and the host
-        arguments used (par, threshold, veh_of).  n: the recorded ticks, where the caller has asked for them already."""
-        from . import reasons as _reasons
-        eng = self.loop.eng
-        B = eng.B
-        if self.obs is None:
-            raise ValueError("this recorder holds no vehicle records (a loop without scripted vehicles): there is no cyclist to evaluate")
-        par, thr, veh, car = _reasons.tick_inputs(B, self.n_obs, eng.dt, par, threshold, cyclist, carry, self.default_cyclist)
-        n = self._n(4) if n is None else n
-        dev = eng.device
-        up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(dev)
-        d_par, d_thr, d_veh, d_car = up(par, np.float64), up(thr, np.float64), up(veh, np.int32), up(car, np.float64)
-        val, tim, trig = self._new(n, 4), self._new(n, 2), self._new(n, dtype=torch.int32)
-        first = torch.full((B,), -1, dtype=torch.int32, device=dev)
-        rec, flags, x_first, x_spawn = self._buffers()
-        self._call("jsim_loop_eval_reasons", B, n, rec, flags, self.n_obs, _ptr(self.obs), x_first, x_spawn, _ptr(d_veh), _ptr(d_par),
-                   _ptr(d_thr), _ptr(d_car), _ptr(val), _ptr(tim), _ptr(trig), _ptr(first))
-        return {"val": val, "timers": tim, "trig": trig, "first": first, "carry": d_car, "par": par, "threshold": thr, "veh_of": veh}
-
-    def vehicle_ranges(self) -> np.ndarray:
-        """Each ego's vehicles [lo, hi) among the recorded ones ([B][2] int32): all of a shared list, its set's slice under a traffic
-        layout (empty for an empty set or a recorder without vehicles)."""
-        B = self.loop.eng.B
-        if self.traffic is None:
-            return np.tile(np.array([0, self.n_obs], dtype=np.int32), (B, 1))
-        set_of, obs_off = self.traffic
-        return np.stack([obs_off[set_of], obs_off[set_of + 1]], axis=1).astype(np.int32)
-
-    def mate_ranges(self) -> np.ndarray:
-        """Each ego's group as a batch range [mlo, mhi) ([B][2] int32): its group of an InteractingLoop, else empty."""
-        B = self.loop.eng.B
-        if self.groups is None:
-            return np.zeros((B, 2), dtype=np.int32)
-        g = np.repeat(np.arange(len(self.groups) - 1), np.diff(self.groups))
-        return np.stack([self.groups[g], self.groups[g + 1]], axis=1).astype(np.int32)
-
-    def _vehicle_lists(self, shapes=None, mates=None):
-        """What conflicts() and gaps() meet: (ego_shape, shapes [n_obs][4] or None, veh_range, mate_range), checked."""
-        eng = self.loop.eng
-        B, n_obs = eng.B, self.n_obs
-        ego = self._ego_shape()
-        if shapes is None:
-            shapes = eng.vehicle_shapes
-        if shapes is not None:
-            shapes = np.ascontiguousarray(shapes, dtype=np.float64)
-            if shapes.shape != (n_obs, 4) or not (np.isfinite(shapes).all() and (shapes[:, 2] > 0).all()):
-                raise ValueError(f"shapes must be [n_obs = {n_obs}, 4] vehicle_shape rows with finite offsets and positive radii")
-        veh = self.vehicle_ranges()
-        mate = self.mate_ranges() if mates is None else np.ascontiguousarray(mates, dtype=np.int32)
-        if mate.shape != (B, 2):
-            raise ValueError(f"mates must be [B = {B}, 2] batch ranges, got {mate.shape}")
-        if (veh < 0).any() or (veh > n_obs).any() or (mate < 0).any() or (mate > B).any():
-            raise ValueError("a vehicle range outside [0, n_obs] or a mate range outside [0, B]")
-        me = np.arange(B)
-        count = np.maximum(veh[:, 1] - veh[:, 0], 0) + np.maximum(mate[:, 1] - mate[:, 0], 0) - ((me >= mate[:, 0]) & (me < mate[:, 1]))
-        if (count > MAX_OBS).any():
-            b = int(np.argmax(count))
-            raise ValueError(f"ego {b} would meet {int(count[b])} vehicles and mates (max {MAX_OBS})")
-        return ego, shapes, veh, mate
-
-    def _vehicle_args(self, shapes=None, mates=None):
-        """_vehicle_lists as conflicts, gaps and headway hand it on: (the eight arguments that follow rec and flags -- n_obs, obs_rec,
-        x_first, x_spawn, veh_range, mate_range, shapes, ego_shape --, the veh_range, mate_range and ego_shape entries of the result,
-        the arrays those pointers point into: the caller holds them until its call has returned)."""
-        dev = self.loop.eng.device
-        ego, shapes, veh, mate = self._vehicle_lists(shapes, mates)
-        up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(dev)
-        d_veh, d_mate, ego_c = up(veh), up(mate), (C.c_double * 3)(*ego)
-        _, _, x_first, x_spawn = self._buffers()
-        args = (self.n_obs, _ptr(self.obs) if self.obs is not None else None, x_first, x_spawn, _ptr(d_veh), _ptr(d_mate),
-                shapes.ctypes.data_as(C.c_void_p) if shapes is not None and self.n_obs else None, C.cast(ego_c, C.c_void_p))
-        return args, {"veh_range": veh, "mate_range": mate, "ego_shape": tuple(float(v) for v in ego)}, (d_veh, d_mate, shapes, ego_c)
-
-    def conflicts(self, frame_window: int = 0, shapes=None, mates=None) -> dict:
-        """Clearance and first contact of every recorded tick and episode (jsim_loop_eval_conflicts): what
-        check_collision_moving_cars / check_collision_moving_bicycle of main/lib/collision_avoidance.py (:85-166) return for an
-        episode's driven poses against the vehicles' recorded ones, computed in one launch from the records.
-
-        frame_window: the reference's frame_window, 0..20.  shapes: [n_obs][4] vehicle_shape rows (default: the loop's registered
-        table, else every vehicle has the ego's shape).  mates: [B][2] batch ranges [mlo, mhi) of each ego's group mates, itself
-        skipped (default: the groups of an InteractingLoop, else none).  An ego meets its recorded vehicles (vehicle_ranges()) and
-        then its mates, eight in all.
-        Returns numpy arrays: clear [n][B] (the smallest circle distance minus the threshold at offset 0; negative: overlap), who
-        (that vehicle's place in the ego's list), row (the first touching row of the tick's frame over all offsets, -1: none),
-        contact (row >= 0); and at the slot of an episode's first tick hit_tick (-1: no contact), hit_frame, hit_xy [n][B][2] (the
-        reference's return value; -1 / NaN elsewhere); and the frame_window, veh_range, mate_range and ego_shape used.  An ego
-        without vehicles and mates has NaN / -1 everywhere.  history.conflict_episodes splits the result into episodes.
-        ValueError: a frame_window outside 0..20, a bad shapes table, a range outside its table, more than eight vehicles."""
-        d = self._conflicts_device(frame_window, shapes, mates)
-        row = d["row"].cpu().numpy()
-        return {"clear": d["clear"].cpu().numpy(), "who": d["who"].cpu().numpy(), "row": row, "contact": row >= 0,
-                "hit_tick": d["hit_tick"].cpu().numpy(), "hit_frame": d["hit_frame"].cpu().numpy(), "hit_xy": d["hit_xy"].cpu().numpy(),
-                "frame_window": d["frame_window"], "veh_range": d["veh_range"], "mate_range": d["mate_range"], "ego_shape": d["ego_shape"]}
-
-    def _conflicts_device(self, frame_window: int = 0, shapes=None, mates=None, n=None) -> dict:
-        """conflicts() up to the launch: the outputs as device tensors (clear, who, row, hit_tick, hit_frame, hit_xy) and the host
-        arguments used (frame_window, veh_range, mate_range, ego_shape)."""
-        eng = self.loop.eng
-        w = int(frame_window)
-        if w != frame_window or not 0 <= w <= 20:
-            raise ValueError(f"frame_window must be an integer in 0..20, got {frame_window!r}")
-        veh_args, used, keep = self._vehicle_args(shapes, mates)
-        n = self._n(4) if n is None else n
-        clear, hit_xy = self._new(n), self._new(n, 2)
-        who, row, hit_tick, hit_frame = self._new(n, dtype=torch.int32, count=4)
-        self._call("jsim_loop_eval_conflicts", eng.B, n, _ptr(self.rec), _ptr(self.flags), *veh_args, w,
-                   _ptr(clear), _ptr(who), _ptr(row), _ptr(hit_tick), _ptr(hit_frame), _ptr(hit_xy))
-        return {"clear": clear, "who": who, "row": row, "hit_tick": hit_tick, "hit_frame": hit_frame, "hit_xy": hit_xy,
-                "frame_window": w, **used}
-
-    def gaps(self, window: int = 20, within: str = "episode", shapes=None, mates=None) -> dict:
-        """The time gap between every ego and each vehicle it meets, per recorded tick and episode (jsim_loop_eval_gaps, DESIGN.md
-        section 23): how many ticks lay between the ego occupying a place and a vehicle occupying it, and who went first -- the
-        post-encroachment time of a crossing, the time headway to a leader.  An episode's smallest gap is the least frame_window at
-        which check_collision_moving_cars / check_collision_moving_bicycle (main/lib/collision_avoidance.py:68-166) report a hit
-        on it.  One launch from the records.
-
-        window: the largest offset tried, 0..63.  within: "episode" (only vehicle ticks inside the ego's own episode count: the
-        reference's rule) or "record" (every recorded tick counts, so the vehicle that passed a spawn point just before the ego
-        respawned there is found).  shapes, mates: as for conflicts(); the list is the same, eight places in all.
-        Returns numpy arrays: off [n][B][8] int8 (per place the touching offset of smallest |off|; > 0: the vehicle was here first,
-        < 0: the ego was; -o in front of +o; history.GAP_NONE = -128: nothing within the window, or no such place), gap [n][B] (the
-        smallest |off| over the places, -1: none), who (the lowest place that has it); at the slot of an episode's first tick
-        ep_gap (the episode's smallest gap, -1: none), ep_tick (the first tick that has it), ep_who (the lowest place that has it
-        there), ep_off (its signed offset, -128: none), -1 / -1 / -1 / -128 elsewhere; and the window, within, veh_range, mate_range
-        and ego_shape used.  history.gap_episodes splits the result into episodes.
-        ValueError: a window outside 0..63, another within, and what conflicts() refuses of shapes and mates."""
-        d = self._gaps_device(window, within, shapes, mates)
-        off = d["off"].cpu().numpy()
-        gap, who = history.gap_per_tick(off)
-        return {"off": off, "gap": gap, "who": who,
-                "ep_gap": d["ep_gap"].cpu().numpy(), "ep_tick": d["ep_tick"].cpu().numpy(), "ep_who": d["ep_who"].cpu().numpy(),
-                "ep_off": d["ep_off"].cpu().numpy(), "window": d["window"], "within": d["within"], "veh_range": d["veh_range"],
-                "mate_range": d["mate_range"], "ego_shape": d["ego_shape"]}
-
-    def _gaps_device(self, window: int = 20, within: str = "episode", shapes=None, mates=None, n=None) -> dict:
-        """gaps() up to the launch: the outputs as device tensors (off, ep_gap, ep_tick, ep_who, ep_off) and the host arguments used
-        (window, within, veh_range, mate_range, ego_shape)."""
-        eng = self.loop.eng
-        w = int(window)
-        if w != window or not 0 <= w <= history.GAP_MAX_WINDOW:
-            raise ValueError(f"window must be an integer in 0..{history.GAP_MAX_WINDOW}, got {window!r}")
-        if within not in ("episode", "record"):
-            raise ValueError(f'within must be "episode" or "record", got {within!r}')
-        veh_args, used, keep = self._vehicle_args(shapes, mates)
-        n = self._n(4) if n is None else n
-        off = self._new(n, 8, dtype=torch.int8)
-        ep_gap, ep_tick, ep_who, ep_off = self._new(n, dtype=torch.int32, count=4)
-        self._call("jsim_loop_eval_gaps", eng.B, n, _ptr(self.rec), _ptr(self.flags), *veh_args, w, int(within == "record"),
-                   _ptr(off), _ptr(ep_gap), _ptr(ep_tick), _ptr(ep_who), _ptr(ep_off))
-        return {"off": off, "ep_gap": ep_gap, "ep_tick": ep_tick, "ep_who": ep_who, "ep_off": ep_off, "window": w, "within": within,
-                **used}
-
-    def static_conflicts(self, obstacles, set_of=None, margin=None, include_hidden: bool = False) -> dict:
-        """Clearance to and contact with the scenario's static obstacles on every recorded tick (jsim_loop_eval_static, DESIGN.md
-        section 18): check_collision on Obstacle.to_convex(margin) (main/lib/obstacles.py:157-176, the planner's collision test) and
-        distance_to_point at the two collision circle centres of the poses that were driven, computed in one launch from the records.
-
-        obstacles: one set -- a scenario's obstacles list: the reference's BoxObstacle / CircleObstacle objects or the primitives of
-        planner.intersection_obstacles -- or a list of such sets (an empty list: one empty set).  set_of: the set of every ego, one
-        index or [B] (default 0).  margin: what to_convex inflates by (default: the ego radius, as the scenario scripts pass it to the
-        planner).  include_hidden: also test the hidden obstacles (the planner's lane-closing boxes).
-        Returns numpy arrays [n][B]: clear (the smallest distance_to_point(centre) - radius over the included obstacles and the two
-        centres; -radius: a centre inside an obstacle), who (that obstacle's place in its set), hit (the lowest place of a touched
-        obstacle, -1: none), contact (hit >= 0), off_tick (at the slot of an episode's first tick the episode's first touching tick
-        or -1; -1 elsewhere); and the margin, include_hidden, ego_shape and set_of used.  An ego whose set has no included obstacle
-        has NaN / -1 / -1.  history.static_episodes splits the result into episodes.
-        ValueError: an obstacle that is neither kind, a set_of outside the sets, a margin that is not finite and >= 0."""
-        d = self._static_device(obstacles, set_of, margin, include_hidden)
-        hit = d["hit"].cpu().numpy()
-        return {"clear": d["clear"].cpu().numpy(), "who": d["who"].cpu().numpy(), "hit": hit, "contact": hit >= 0,
-                "off_tick": d["off_tick"].cpu().numpy(), "margin": d["margin"], "include_hidden": d["include_hidden"],
-                "ego_shape": d["ego_shape"], "set_of": d["set_of"]}
-
-    def _static_device(self, obstacles, set_of=None, margin=None, include_hidden: bool = False, n=None) -> dict:
-        """static_conflicts() up to the launch: the outputs as device tensors (clear, who, hit, off_tick) and the host arguments
-        used (margin, include_hidden, ego_shape, set_of)."""
-        from . import planner
-        eng = self.loop.eng
-        B = eng.B
-        ego = self._ego_shape()
-        margin = float(ego[2] if margin is None else margin)
-        obstacles = list(obstacles)
-        is_one = lambda o: (isinstance(o, (tuple, list)) and len(o) > 0 and isinstance(o[0], str)) or hasattr(o, "to_convex")
-        sets = [obstacles] if (not obstacles or is_one(obstacles[0])) else [list(s) for s in obstacles]
-        tables = [planner.static_obstacle_rows(s, margin) for s in sets]
-        rows = np.ascontiguousarray(np.concatenate(tables))
-        n_rows = len(rows)
-        if n_rows == 0:
-            rows = np.zeros((1, planner.STATIC_ROW))                 # (a valid pointer; no row of it is read)
-        set_off = np.concatenate([[0], np.cumsum([len(t) for t in tables])]).astype(np.int32)
-        sof = np.zeros(B, dtype=np.int64) if set_of is None else np.asarray(set_of)
-        if sof.dtype.kind not in "iu" or sof.shape not in ((), (B,)):
-            raise ValueError(f"set_of must be one integer or [B = {B}] integers, got {sof.dtype} {sof.shape}")
-        sof = np.ascontiguousarray(np.broadcast_to(sof, (B,)), dtype=np.int32)
-        if ((sof < 0) | (sof >= len(sets))).any():
-            raise ValueError(f"set_of outside [0, {len(sets)})")
-        n = self._n(4) if n is None else n
-        d_set = torch.from_numpy(sof).to(eng.device)
-        clear = self._new(n)
-        who, hit, off_tick = self._new(n, dtype=torch.int32, count=3)
-        ego_c = (C.c_double * 3)(*ego)
-        self._call("jsim_loop_eval_static", B, n, *self._buffers(), _ptr(d_set), len(sets), set_off.ctypes.data_as(C.c_void_p), n_rows,
-                   rows.ctypes.data_as(C.c_void_p), C.cast(ego_c, C.c_void_p), int(bool(include_hidden)),
-                   _ptr(clear), _ptr(who), _ptr(hit), _ptr(off_tick))
-        return {"clear": clear, "who": who, "hit": hit, "off_tick": off_tick, "margin": margin, "include_hidden": bool(include_hidden),
-                "ego_shape": tuple(float(v) for v in ego), "set_of": sof}
-
-    def _path_args(self, paths=None, path_id=None):
-        """What tracking() and headway() meet of paths and path_id, checked: (the path table on the device -- x, y, yaw, off, arc --,
-        n_paths, path_id [B] on the host, the same on the device, arc as a list)."""
-        eng = self.loop.eng
-        B, dev = eng.B, eng.device
-        table = self._tracking_table if paths is None else None
-        if table is None:
-            table = history.path_table(eng.paths if paths is None else paths)
-            table["dev"] = [torch.from_numpy(table[k]).to(dev) for k in ("x", "y", "yaw", "off", "arc_flat")]
-            if paths is None:
-                self._tracking_table = table
-        n_paths = len(table["arc"])
-        own = paths is None and path_id is None                     # the engine's own: its path_id is on the device already
-        if path_id is None:
-            if paths is not None and n_paths != 1:
-                raise ValueError("paths of one's own need a path_id per ego")
-            pid = eng.path_id.cpu().numpy() if own else np.zeros(B, dtype=np.int32)
-        else:
-            pid = np.asarray(path_id)
-            if pid.dtype.kind not in "iu" or pid.shape not in ((), (B,)):
-                raise ValueError(f"path_id must be one integer or [B = {B}] integers, got {pid.dtype} {pid.shape}")
-            pid = np.array(np.broadcast_to(pid, (B,)), dtype=np.int32)
-        if ((pid < 0) | (pid >= n_paths)).any():
-            raise ValueError(f"path_id outside [0, {n_paths})")
-        d_pid = eng.path_id if own else torch.from_numpy(pid).to(dev)
-        return table["dev"], n_paths, pid, d_pid, table["arc"]
-
-    def tracking(self, paths=None, path_id=None) -> dict:
-        """Every recorded pose projected onto a path (jsim_loop_eval_tracking): how far along its route each
-        ego was on every tick, how far beside it and how far off its heading -- what plot_trajectories_comparison of
-        main/scenarios/mpc_sensitivity_analysis*.py draws against the reference trajectory -- computed in one launch from the records.
-        The pose of tick k is the record itself (History.x[k], .y[k], .yaw[k]: after the plant step).
-
-        paths: a list of (M, >= 3) arrays x, y, yaw (M >= 1; the yaw as the controller sees it: unwrapped, as engine.paths hold it),
-        default: the engine's paths (their device copy is made once and kept on the recorder); path_id: each ego's path, one index or
-        [B], default: the engine's path_id (with paths given: required unless there is one path).  Any paths will do: the original
-        route of a fork, a lane centreline.  The context's own tables are not read, so a superseded recorder gives the same result.
-        Returns numpy arrays [n][B]: idx (calc_nearest_index(state, cx, cy, 0) of main/lib/trajectories.py:89-97, relative to the
-        path), seg (the segment that holds the foot), s (arc length of the foot), d (signed lateral offset, left of the direction of
-        travel positive; |d| is the distance to the polyline), e_yaw (heading error wrapped to [-pi, pi)); -1 / NaN for a pose that
-        is not finite; at the slot of an episode's first tick ep_i [n][B][2] (history.TRK_INT: ticks, d_max_tick) and ep_d [n][B][5]
-        (history.TRK_DOUBLE: d_max, d2_mean, yaw_max, s_first, s_last), -1 / NaN elsewhere; arc (a list: the arc length at every
-        point of every path) and the path_id used.  history.tracking_episodes splits the result into episodes and gives travel
-        times between stations and the delay against free flow.
-        ValueError: a path_id out of range or of another shape, a path without a point or with fewer than three columns,
-        path entries that are not finite."""
-        d = self._tracking_device(paths, path_id)
-        out = {k: d[k].cpu().numpy() for k in ("idx", "seg", "s", "d", "e_yaw", "ep_i", "ep_d")}
-        out.update(arc=d["arc"], path_id=d["path_id"])
-        return out
-
-    def _tracking_device(self, paths=None, path_id=None, n=None) -> dict:
-        """tracking() up to the launch: the outputs as device tensors (idx, seg, s, d, e_yaw, ep_i, ep_d) and the host arguments
-        used (arc, path_id)."""
-        B = self.loop.eng.B
-        (px, py, pyaw, off, d_arc), n_paths, pid, d_pid, arc = self._path_args(paths, path_id)
-        n = self._n(4) if n is None else n
-        idx, seg = self._new(n, dtype=torch.int32, count=2)
-        s, d, e_yaw = self._new(n, count=3)
-        ep_i, ep_d = self._new(n, len(history.TRK_INT), dtype=torch.int32), self._new(n, len(history.TRK_DOUBLE))
-        self._call("jsim_loop_eval_tracking", B, n, _ptr(self.rec), _ptr(self.flags), _ptr(d_pid), int(px.numel()), _ptr(px), _ptr(py),
-                   _ptr(pyaw), n_paths, _ptr(off), _ptr(d_arc), _ptr(idx), _ptr(seg), _ptr(s), _ptr(d), _ptr(e_yaw), _ptr(ep_i), _ptr(ep_d))
-        return {"idx": idx, "seg": seg, "s": s, "d": d, "e_yaw": e_yaw, "ep_i": ep_i, "ep_d": ep_d, "arc": arc, "path_id": pid}
-
-    def headway(self, paths=None, path_id=None, shapes=None, mates=None, margin: float = 0.0, places: bool = True) -> dict:
-        """Every recorded vehicle projected onto the ego's path (jsim_loop_eval_headway): how much road lay
-        between the ego and each vehicle it meets, how fast it closed and how long until it is gone -- the distance along the road
-        that create_following_trajectory, evaluate_time_following and plot_distance of
-        main/scenarios/overtaking_cyclist_bidirectional_road.py approximate with a Euclidean range -- computed in one launch from
-        the records, everything taken at the start of each tick.
-
-        paths, path_id: as for tracking() (default: the engine's own, whose device copy is kept on the recorder).  shapes, mates:
-        as for conflicts(); the list is the same, eight places in all.  margin (>= 0): added to a vehicle's threshold (the ego's
-        radius + its own) when deciding whether it is on the path.  places=False: the three per-place arrays are neither written
-        nor read back.
-        Returns numpy arrays.  Per place [n][B][8] (places=True): gap (> 0: the vehicle is ahead by that much road, < 0: behind,
-        0: alongside), lat (its nearer circle centre's signed offset from the path, left positive), rate (its speed along the path
-        minus the ego's; an oncoming vehicle's own is negative); NaN for an empty place or a pose that is not finite.  Per tick
-        [n][B]: lead (the on-path place with the smallest gap >= 0, -1: none), lead_gap, thw (lead_gap / u_ego; inf for a standing
-        ego, 0 alongside), ttc (the smallest time to collision over the on-path places; inf: none is closing; NaN: none is on the
-        path), ttc_who, u_ego (the ego's speed along the path).  At the slot of an episode's first tick ep_i [n][B][7]
-        (history.HW_INT) and ep_d [n][B][4] (history.HW_DOUBLE), -1 / NaN elsewhere.  And arc, path_id, veh_range, mate_range,
-        ego_shape and margin as used.  An ego without vehicles and mates has -1 / NaN everywhere.  history.headway_episodes splits
-        the result into episodes.
-        ValueError: what tracking() refuses of paths and path_id, what conflicts() refuses of shapes and mates, a margin that is
-        not finite and >= 0."""
-        d = self._headway_device(paths, path_id, shapes, mates, margin, places)
-        keys = ("lead", "lead_gap", "thw", "ttc", "ttc_who", "u_ego", "ep_i", "ep_d") + (("gap", "lat", "rate") if places else ())
-        out = {k: d[k].cpu().numpy() for k in keys}
-        out.update({k: d[k] for k in ("arc", "path_id", "veh_range", "mate_range", "ego_shape", "margin")})
-        return out
-
-    def _headway_device(self, paths=None, path_id=None, shapes=None, mates=None, margin: float = 0.0, places: bool = True, n=None) -> dict:
-        """headway() up to the launch: the outputs as device tensors (lead, lead_gap, thw, ttc, ttc_who, u_ego, ep_i, ep_d and, with
-        places, gap, lat, rate) and the host arguments used (arc, path_id, veh_range, mate_range, ego_shape, margin)."""
-        B = self.loop.eng.B
-        margin = float(margin)
-        if not (math.isfinite(margin) and margin >= 0.0):
-            raise ValueError(f"margin must be finite and >= 0, got {margin!r}")
-        (px, py, pyaw, off, d_arc), n_paths, pid, d_pid, arc = self._path_args(paths, path_id)
-        veh_args, used, keep = self._vehicle_args(shapes, mates)
-        n = self._n(4) if n is None else n
-        lead, ttc_who = self._new(n, dtype=torch.int32, count=2)
-        lead_gap, thw, ttc, u_ego = self._new(n, count=4)
-        ep_i, ep_d = self._new(n, len(history.HW_INT), dtype=torch.int32), self._new(n, len(history.HW_DOUBLE))
-        per_place = self._new(n, MAX_OBS, count=3) if places else (None, None, None)
-        self._call("jsim_loop_eval_headway", B, n, _ptr(self.rec), _ptr(self.flags), *veh_args,
-                   _ptr(d_pid), int(px.numel()), _ptr(px), _ptr(py), _ptr(pyaw), n_paths, _ptr(off), _ptr(d_arc), margin,
-                   _ptr(lead), _ptr(lead_gap), _ptr(thw), _ptr(ttc), _ptr(ttc_who), _ptr(u_ego), _ptr(ep_i), _ptr(ep_d),
-                   *[_ptr(t) if t is not None else None for t in per_place])
-        out = {"lead": lead, "lead_gap": lead_gap, "thw": thw, "ttc": ttc, "ttc_who": ttc_who, "u_ego": u_ego, "ep_i": ep_i, "ep_d": ep_d,
-               "arc": arc, "path_id": pid, **used, "margin": margin}
-        if places:
-            out.update(gap=per_place[0], lat=per_place[1], rate=per_place[2])
-        return out
-
-    def cutoffs(self, chunk_ticks: int = 0, carry=None) -> dict:
-        """The glue's decision on every recorded tick (jsim_loop_eval_cutoffs): what the loop ahead of MPC.step
-        found and did -- main/scenarios/mpc_intersection.py:104-143: the progress index, check_collision_moving_cars /
-        check_collision_moving_bicycle on the predicted traffic, get_cutoff_curve_by_position_idx(...) - EXTRA_CUTOFF_MARGIN -- and
-        what visualize_frame shows of it (collision_xy, the length of tmp_trajectory), computed again after the run from the records
-        by the loops' own device function: every value is the live loop's, bit for bit.
-
-        chunk_ticks: ticks per launch (0: from a 512 MiB budget of predictions).  carry: [B][3] int32 = the progress index, the
-        previous path length (-1: none) and the cut-off the first recorded tick starts from (default: the loops' own start).
-        Returns numpy arrays over the recorded ticks [n][B]: status (the glue's pre_status: 0, or the tick kept idx and cut as they
-        were), idx (the progress index after the tick's update), cut (what the loop wrote to path_len, under mode="speed_cutoff" to
-        the speed cut-off), hit (bool), first (the hit's index on the remaining path, -1: none), col_xy [n][B][2] (NaN: none); and
-        carry [B][3] as the next tick would meet it.  history.cutoff_episodes splits the result into episodes.
-        ValueError: a recorder of a ClosedLoop (it has no glue), a superseded recorder (the context's tables are no longer its
-        loop's), a bad chunk_ticks or carry."""
-        d = self._cutoffs_device(chunk_ticks, carry)
-        out = {k: d[k].cpu().numpy() for k in ("status", "idx", "cut", "first", "col_xy", "carry")}
-        out["hit"] = d["hit"].cpu().numpy() != 0
-        return out
-
-    def _cutoffs_device(self, chunk_ticks: int = 0, carry=None, n=None, first_tick: int = 0) -> dict:
-        """cutoffs() up to the launches: the outputs as device tensors (status, idx, cut, hit, first, col_xy, carry).  n: the recorded
-        ticks, where the caller has asked for them already, or fewer; first_tick: evaluate the ticks [first_tick, n) only, from the
-        carry the ticks before left (the outputs are those ticks' rows)."""
-        eng = self.loop.eng
-        B, dev = eng.B, eng.device
-        if self.glue is None:
-            raise ValueError("this recorder's loop has no glue (ClosedLoop): there is no cut-off to evaluate")
-        if self.superseded:
-            raise ValueError("a later loop on this engine replaced this recorder: the context's tables are no longer its loop's")
-        c = int(chunk_ticks)
-        if c != chunk_ticks or c < 0:
-            raise ValueError(f"chunk_ticks must be an integer >= 0, got {chunk_ticks!r}")
-        if carry is None:
-            d_car = None
-        else:
-            car = np.asarray(carry)
-            if car.shape != (B, 3) or car.dtype.kind not in "iu":
-                raise ValueError(f"carry must be [B = {B}, 3] integers, got {car.dtype} {car.shape}")
-            d_car = torch.from_numpy(np.ascontiguousarray(car, dtype=np.int32)).to(dev)
-        n = self._n(4) if n is None else n
-        k0 = int(first_tick)
-        if not 0 <= k0 <= n:
-            raise ValueError(f"first_tick must be in [0, {n}], got {first_tick!r}")
-        g = self.glue
-        if d_car is None:      # the loops' own start: what a NULL carry of the entry point stands for, as a tensor to hand back
-            full = eng.full_len
-            d_car = torch.stack([torch.zeros_like(full), torch.full_like(full, -1), full], dim=1).contiguous()
-        rows = max(n, 1)       # (no ticks yet: still valid pointers)
-        status, idx, cut, hit, first = (torch.empty(rows, B, dtype=torch.int32, device=dev) for _ in range(5))
-        col_xy = torch.empty(rows, B, 2, dtype=torch.float64, device=dev)
-        rec, flags, x_first, x_spawn = self._buffers()
-        self._call("jsim_loop_eval_cutoffs", B, n, rec, flags, self.n_obs, _ptr(self.obs) if self.obs is not None else None,
-                   x_first, x_spawn, g["frame_window"], g["margin"], g["n_steps"], int(g["mode"] == "speed_cutoff"),
-                   int(g["interacting"]), c, k0, _ptr(d_car), _ptr(status), _ptr(idx), _ptr(cut), _ptr(hit), _ptr(first), _ptr(col_xy))
-        status, idx, cut, hit, first, col_xy = (t[k0:n] for t in (status, idx, cut, hit, first, col_xy))
-        return {"status": status, "idx": idx, "cut": cut, "hit": hit, "first": first, "col_xy": col_xy, "carry": d_car}
-
-    def fork_state(self, ego, at):
-        """Where a loop forked off this recording starts (jsim_loop_fork_state): for every row r the state
-        (x, y, v, yaw) of ego ego[r] at the start of recorded tick at[r] -- at = the number of recorded ticks: after the last one --
-        by the rule the cut-off replay reads its states by, and the first tick of the episode that tick belongs to.
-
-        ego, at: one integer each or [R]; one ego may stand in several rows.  Returns x0 (a device tensor [R, 4]), k0 and
-        age = at - k0 (int32 numpy arrays [R]).  ValueError: rows that are not integers of one length, an ego outside the batch, a
-        tick outside 0 .. recorded ticks, a superseded recorder (its records stopped when the later loop was built)."""
-        eng = self.loop.eng
-        if self.superseded:
-            raise ValueError("a later loop on this engine replaced this recorder: its records stopped at that point")
-        n = self._n()
-        ego, at = history.fork_rows(eng.B, n, ego, at)
-        R = ego.size
-        x0 = torch.empty(max(R, 1), 4, dtype=torch.float64, device=eng.device)[:R]
-        k0 = torch.empty(max(R, 1), dtype=torch.int32, device=eng.device)[:R]
-        self._call("jsim_loop_fork_state", eng.B, n, *self._buffers(), R, ego.ctypes.data_as(C.c_void_p), at.ctypes.data_as(C.c_void_p),
-                   _ptr(x0), _ptr(k0))
-        k0 = k0.cpu().numpy()
-        return x0, k0, at - k0
-
-    def summary(self, conflicts=None, static=None, reasons=None) -> dict:
-        """One row per recorded episode of every ego (jsim_loop_summarise_episodes): did the ego arrive, how
-        many ticks it took, how far it drove and deviated, how close it came to a vehicle and to an obstacle, whether it touched
-        either, whether the replan trigger fired -- reduced on the device; the per-tick series are not read back.
-
-        conflicts / static / reasons: None (the group's columns stay NaN / -1 / 0), True (conflicts() / static_conflicts() /
-        reasons() with their defaults; `static` has no default for its obstacles) or a dict of that method's keyword arguments.
-        Returns numpy arrays: ep_off [B + 1] (ego b's rows are [ep_off[b], ep_off[b + 1]), in order of time) and one array [E] per
-        column of history.EP_INT and history.EP_DOUBLE (ego, k0, n, end, failed, dev_tick, veh_tick, veh_who, veh_hit_tick,
-        veh_hit_frame, st_tick, st_who, st_off_tick, st_obstacle, st_ticks_off, replan_tick; length, v_mean, v_max, a_min, a_max,
-        delta_absmax, dev_max, dev_mean, veh_clear, veh_hit_x, veh_hit_y, st_clear, pm_min, driver_min, cyclist_min, dist_min);
-        duration [E] = n * dt; dt; and under `conflicts`, `static`, `reasons` the arguments that evaluation used (None: not
-        requested).  history.episode_rows turns the result into per-ego lists of dicts.
-        ValueError: what the three methods raise, a `static` without obstacles, an argument that is none of None / True / dict."""
-        eng = self.loop.eng
-        B, dev = eng.B, eng.device
-
-        def kwargs(name, arg):
-            if arg is None or arg is True:
-                return {}
-            if not isinstance(arg, dict):
-                raise ValueError(f"{name} must be None, True or a dict of keyword arguments, got {arg!r}")
-            return dict(arg)
-
-        kw_c, kw_s, kw_r = kwargs("conflicts", conflicts), kwargs("static", static), kwargs("reasons", reasons)
-        if static is not None and "obstacles" not in kw_s:
-            raise ValueError("static needs its obstacles: static=dict(obstacles=...)")
-        n = self._n()
-        c = self._conflicts_device(n=n, **kw_c) if conflicts is not None else None
-        s = self._static_device(n=n, **kw_s) if static is not None else None
-        r = self._reasons_device(n=n, **kw_r) if reasons is not None else None
-        # the table's size, exactly: every ego's running episode and one more per end flag
-        ends = int(((self.flags[:n] & (history.GOAL | history.AGE)) != 0).sum().item()) if n else 0
-        cap = B + ends
-        ep_off = torch.empty(B + 1, dtype=torch.int64, device=dev)
-        ep_i = torch.empty(max(cap, 1), len(history.EP_INT), dtype=torch.int32, device=dev)
-        ep_d = torch.empty(max(cap, 1), len(history.EP_DOUBLE), dtype=torch.float64, device=dev)
-        group = lambda d, keys: [_ptr(d[k]) if d is not None else None for k in keys]
-        self._call("jsim_loop_summarise_episodes", B, n, *self._buffers(),
-                   *group(c, ("clear", "who", "hit_tick", "hit_frame", "hit_xy")), *group(s, ("clear", "who", "hit", "off_tick")),
-                   *group(r, ("val", "trig")), cap, _ptr(ep_off), _ptr(ep_i), _ptr(ep_d))
-        off, I, D = ep_off.cpu().numpy(), ep_i[:cap].cpu().numpy(), ep_d[:cap].cpu().numpy()
-        if int(off[B]) != cap:
-            raise RuntimeError(f"the episode table has {int(off[B])} rows, {cap} were counted")
-        out = {"ep_off": off, "dt": float(eng.dt)}
-        out.update({k: np.ascontiguousarray(I[:, j]) for j, k in enumerate(history.EP_INT)})
-        out.update({k: np.ascontiguousarray(D[:, j]) for j, k in enumerate(history.EP_DOUBLE)})
-        out["duration"] = out["n"] * float(eng.dt)
-        meta = lambda d, keys: None if d is None else {k: d[k] for k in keys}
-        out["conflicts"] = meta(c, ("frame_window", "veh_range", "mate_range", "ego_shape"))
-        out["static"] = meta(s, ("margin", "include_hidden", "ego_shape", "set_of"))
-        out["reasons"] = None if r is None else {"par": np.array(r["par"]), "threshold": np.array(r["threshold"]),
-                                                 "veh_of": np.array(r["veh_of"], dtype=np.int32)}
-        return out
-
-
-def _register_recorder(engine: BatchedMPC, rec: Optional[Recorder]):
-    """jsim_loop_set_recorder (None: clear).  The engine keeps the registered buffers alive; the recorder it replaces is marked
-    superseded."""
-    old = engine._recorder
-    if old is not None and old is not rec:
-        old.superseded = True
-    if rec is None:
-        _cabi.check(engine.lib.jsim_loop_set_recorder(engine._ctx, engine.B, 0, None, None, 0, None), engine._ctx,
-                    "jsim_loop_set_recorder")
-    else:
-        _cabi.check(engine.lib.jsim_loop_set_recorder(engine._ctx, engine.B, rec.cap, _ptr(rec.rec), _ptr(rec.flags), rec.n_obs,
-                                                      _ptr(rec.obs) if rec.obs is not None else None), engine._ctx,
-                    "jsim_loop_set_recorder")
-    engine._recorder = rec
+from .history import MAX_OBS
+from .recorder import Recorder, _register_recorder
+from .vehicle import car_circles, vehicle_shape
 
 
 class ClosedLoop:
@@ -683,34 +93,6 @@ class ClosedLoop:
     def replay(self):
         self._graph.replay()
         return self._graph_ticks
-
-
-def car_circles(L: float = 2.86, width: float = 2.0, extra_length: float = 0.64):
-    """Collision circles of the reference's BicycleModelDimensions (main/lib/car_dimensions.py:62-79,82-90): bounding
-    box (width, L + 0.64), radius = width / sqrt(2), two centres on the body axis at L/2 +- (length/2 - width/2) from the
-    rear axle.  Returns (radius, (front_offset, rear_offset))."""
-    length = L + extra_length
-    offset = length / 2 - width / 2
-    return width / (2 ** .5), (L / 2 + offset, L / 2 - offset)
-
-
-DIMS_KEYS = ("L", "width", "extra_length")
-
-
-def vehicle_shape(dims=None, L: float = 2.86, width: float = 2.0, extra_length: float = 0.64):
-    """One row of the shape table of jsim_loop_set_vehicle_shapes, (cc_front, cc_rear, radius, wheelbase), from the fields of
-    `obstacle_dims`: dims = dict(L=..., width=..., extra_length=...) (any missing key: the keyword's value) through car_circles.
-    Raises ValueError on an unknown key or a size that is not positive (extra_length: negative)."""
-    if dims is not None:
-        unknown = sorted(set(dims) - set(DIMS_KEYS))
-        if unknown:
-            raise ValueError(f"unknown dims key(s) {unknown}: a vehicle's dims holds {list(DIMS_KEYS)}")
-        L, width, extra_length = (float(dims.get(k, d)) for k, d in zip(DIMS_KEYS, (L, width, extra_length)))
-    if not (L > 0 and width > 0 and extra_length >= 0 and math.isfinite(L + width + extra_length)):
-        raise ValueError(f"a vehicle's L and width must be positive and its extra_length not negative (L={L}, width={width}, "
-                         f"extra_length={extra_length})")
-    radius, (c0, c1) = car_circles(L, width, extra_length)
-    return (c0, c1, radius, L)
 
 
 def shape_table(specs, default_shape):
@@ -882,9 +264,6 @@ class ScriptedObstacles:
         _cabi.check(eng.lib.jsim_loop_obstacles(eng._ctx, self.n, _ptr(self.state), _ptr(self.param), _ptr(self.get_buf),
                                                 1 if step else 0, eng._stream()), eng._ctx, "jsim_loop_obstacles")
         return self.get_buf[: self.n]
-
-
-MAX_OBS = 8            # JSIM_MAX_OBS: obstacles one ego's glue can hold (scripted vehicles, then group mates)
 
 
 def traffic_layout(B: int, sets, traffic_of, group_off=None):

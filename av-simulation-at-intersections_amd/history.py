@@ -11,7 +11,7 @@ every recorded pose onto a path (section 24); headway_episodes for the space hea
 an ego and the vehicles on its path (section 25)."""
 from __future__ import annotations
 
-from typing import List, Optional
+from typing import List, NamedTuple, Optional
 
 import numpy as np
 
@@ -30,6 +30,40 @@ TRK_DOUBLE = ("d_max", "d2_mean", "yaw_max", "s_first", "s_last")
 # the columns of Recorder.headway's ep_i and ep_d, in the order of the JSIM_HW_* enumerators of include/jsim_mpc.h
 HW_INT = ("ticks", "lead_ticks", "gap_tick", "gap_who", "thw_tick", "ttc_tick", "ttc_who")
 HW_DOUBLE = ("gap_min", "thw_min", "ttc_min", "thw_mean")
+MAX_OBS = 8            # JSIM_MAX_OBS: obstacles one ego's glue can hold (scripted vehicles, then group mates)
+
+
+class Evaluator(NamedTuple):
+    """One evaluator of the recorder: its entry point and its per-tick outputs [n][B]... as (key, numpy dtype, trailing shape), in
+    the order of the entry point's declaration in include/jsim_mpc.h; `optional`: the keys the call takes as NULL, as a whole."""
+    entry: str
+    outputs: tuple
+    optional: tuple = ()
+
+    def keys(self, skip=()):
+        return tuple(k for k, _, _ in self.outputs if k not in skip)
+
+
+_F, _I = np.float64, np.int32
+# what the Recorder allocates, hands to the entry point and reads back, what the tools time and what tests/test_recorder_outputs_cpu.py holds
+# against the header (DESIGN.md section 26).  Outputs that are not [n][B]... (first and carry of reasons, carry of cutoffs) stay with
+# their methods.
+EVALUATORS = {
+    "reasons": Evaluator("jsim_loop_eval_reasons", (("val", _F, (4,)), ("timers", _F, (2,)), ("trig", _I, ()))),
+    "conflicts": Evaluator("jsim_loop_eval_conflicts", (("clear", _F, ()), ("who", _I, ()), ("row", _I, ()), ("hit_tick", _I, ()),
+                                                        ("hit_frame", _I, ()), ("hit_xy", _F, (2,)))),
+    "gaps": Evaluator("jsim_loop_eval_gaps", (("off", np.int8, (MAX_OBS,)), ("ep_gap", _I, ()), ("ep_tick", _I, ()), ("ep_who", _I, ()),
+                                              ("ep_off", _I, ()))),
+    "static": Evaluator("jsim_loop_eval_static", (("clear", _F, ()), ("who", _I, ()), ("hit", _I, ()), ("off_tick", _I, ()))),
+    "tracking": Evaluator("jsim_loop_eval_tracking", (("idx", _I, ()), ("seg", _I, ()), ("s", _F, ()), ("d", _F, ()), ("e_yaw", _F, ()),
+                                                      ("ep_i", _I, (len(TRK_INT),)), ("ep_d", _F, (len(TRK_DOUBLE),)))),
+    "headway": Evaluator("jsim_loop_eval_headway", (("lead", _I, ()), ("lead_gap", _F, ()), ("thw", _F, ()), ("ttc", _F, ()),
+                                                    ("ttc_who", _I, ()), ("u_ego", _F, ()), ("ep_i", _I, (len(HW_INT),)),
+                                                    ("ep_d", _F, (len(HW_DOUBLE),)), ("gap", _F, (MAX_OBS,)), ("lat", _F, (MAX_OBS,)),
+                                                    ("rate", _F, (MAX_OBS,))), optional=("gap", "lat", "rate")),
+    "cutoffs": Evaluator("jsim_loop_eval_cutoffs", (("status", _I, ()), ("idx", _I, ()), ("cut", _I, ()), ("hit", _I, ()),
+                                                    ("first", _I, ()), ("col_xy", _F, (2,)))),
+}
 
 
 class History:
@@ -315,7 +349,7 @@ def cutoff_episodes(result: dict, flags: np.ndarray):
     the episode's ticks as numpy arrays under their names, first_cut_tick (the first tick of the run whose path was cut off, -1:
     none), n_cut (how many of the episode's ticks were cut off) and longest_cut (the longest run of consecutive cut-off ticks within
     the episode: a run that reaches the episode's last tick ends there, whatever the next episode starts with)."""
-    series = {k: np.asarray(result[k]) for k in ("status", "idx", "cut", "hit", "first", "col_xy")}
+    series = {k: np.asarray(result[k]) for k in EVALUATORS["cutoffs"].keys()}
 
     def make(b, k0, k1):
         ep = {k: v[k0:k1, b] for k, v in series.items()}

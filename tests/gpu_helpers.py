@@ -111,6 +111,36 @@ def assert_state_equal(a, b, what):
         assert torch.equal(a[k], b[k]), (what, k)
 
 
+# ------------------------------------------------------------------------------------------------
+# The guarded launch of the recorder's evaluators (jsim_loop_eval_*): outputs poisoned first, one row of guard slots in front of the
+# [n][B] the call may write and one behind.
+# ------------------------------------------------------------------------------------------------
+def guarded_outputs(spec, n, B, dev):
+    """(views, buffers) of the outputs `spec` -- (key, numpy dtype, trailing shape, poison: a value the output cannot take) each --:
+    buffers [n + 2][B]... filled with the poison, and their rows from 1 on -- the [n][B]... the call may write, whose pointers it
+    takes, and the guard row behind (so that n = 0 still has a pointer)."""
+    buf = {k: torch.full((n + 2, B) + tuple(shape), poison, dtype=getattr(torch, np.dtype(dt).name), device=dev) for k, dt, shape, poison in spec}
+    return {k: b[1:] for k, b in buf.items()}, buf
+
+
+def check_guarded(pkg, eng, name, spec, buf, n, rc, rc_want=0, nothing=False, what=()):
+    """Behind a call of entry point `name` on guarded_outputs' views that returned rc.  rc_want != 0 (a refusal) or `nothing` (n = 0
+    or B = 0): rc is the wanted one and every slot is still poison; returns the library's last message.  Else the call succeeded,
+    the guards are intact and no slot between is poison; returns the rows [1, n + 1) as numpy arrays."""
+    torch.cuda.synchronize()
+    poison = {k: p for k, _, _, p in spec}
+    host = {k: v.cpu().numpy() for k, v in buf.items()}
+    if rc_want != 0 or nothing:                                            # refused, or nothing to do: nothing is written
+        assert rc == rc_want, rc
+        assert all(np.all(host[k] == poison[k]) for k in poison)
+        return eng.lib.jsim_last_error(eng._ctx).decode()
+    pkg._cabi.check(rc, eng._ctx, name)
+    for k in poison:
+        assert np.all(host[k][0] == poison[k]) and np.all(host[k][n + 1] == poison[k]), ("guard", k, *what, n)
+        assert not np.any(host[k][1:n + 1] == poison[k]), ("unwritten", k, *what, n)
+    return {k: host[k][1:n + 1] for k in poison}
+
+
 def engine(pkg, routes, batch, T, **kw):
     eng = pkg.BatchedMPC(routes, batch.path_id, dl=pkg.synth.DL, T=T, speed=batch.speed, device="cuda:0", smooth=False, **kw)
     eng.load_state(batch.target_ind, batch.oa, batch.od, batch.path_len)

@@ -11,11 +11,13 @@ import torch
 
 import conflict_cases as TC
 import conflicts_numpy as CN
-from gpu_helpers import W, iroutes, loop_engine  # noqa: F401
+from gpu_helpers import W, check_guarded, guarded_outputs, iroutes, loop_engine  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 BAR = 1e-12
 KEYS = ("clear", "who", "row", "hit_tick", "hit_frame", "hit_xy")
+POISON_I, POISON_D = -85, -8.5e85                                      # values no output can take
+SPEC = [(k, np.float64, (2,) if k == "hit_xy" else (), POISON_D) if k in ("clear", "hit_xy") else (k, np.int32, (), POISON_I) for k in KEYS]
 
 
 @pytest.fixture(scope="module")
@@ -29,9 +31,9 @@ def arrays():
     return TC.recorder_arrays(TC.cases())
 
 
-def launch(pkg, eng, A, w, n=TC.N, egos=None, mates=None, fill=-7):
+def launch(pkg, eng, A, w, n=TC.N, egos=None, mates=None):
     """jsim_loop_eval_conflicts on the first n ticks of recorder arrays (egos: these egos only, in this order, with these mate
-    ranges; the vehicle table stays whole).  Returns numpy outputs; what the call does not write stays `fill`."""
+    ranges; the vehicle table stays whole), on guarded outputs (gpu_helpers.guarded_outputs).  Returns numpy outputs."""
     idx = np.arange(A["rec"].shape[1]) if egos is None else np.asarray(egos)
     B = len(idx)
     dev = eng.device
@@ -41,14 +43,11 @@ def launch(pkg, eng, A, w, n=TC.N, egos=None, mates=None, fill=-7):
     xf, xs = up(A["x_first"][idx]), up(A["x_spawn"][idx])
     veh, mate = up(A["veh_range"][idx], np.int32), up(A["mate_range"][idx] if mates is None else mates, np.int32)
     shapes, ego = np.ascontiguousarray(A["shapes"]), np.array(TC.CAR)
-    out = {k: torch.full((m, B, 2) if k == "hit_xy" else (m, B), float(fill) if k in ("clear", "hit_xy") else fill,
-                         dtype=torch.float64 if k in ("clear", "hit_xy") else torch.int32, device=dev) for k in KEYS}
+    out, buf = guarded_outputs(SPEC, n, B, dev)
     p = lambda t: t.data_ptr()
     rc = eng.lib.jsim_loop_eval_conflicts(eng._ctx, B, n, p(rec), p(flags), A["obs"].shape[1], p(obs), p(xf), p(xs), p(veh), p(mate),
                                           shapes.ctypes.data, ego.ctypes.data, w, *[p(out[k]) for k in KEYS], None)
-    pkg._cabi.check(rc, eng._ctx, "jsim_loop_eval_conflicts")
-    torch.cuda.synchronize()
-    return {k: v[:n].cpu().numpy() if n else v.cpu().numpy() for k, v in out.items()}
+    return check_guarded(pkg, eng, "jsim_loop_eval_conflicts", SPEC, buf, n, rc, nothing=n == 0)
 
 
 @pytest.fixture(scope="module")
@@ -127,9 +126,7 @@ def test_mates_see_each_other_alike(whole):
 
 
 def test_nothing_to_do_writes_nothing(pkg, eng, arrays):
-    out = launch(pkg, eng, arrays, 3, n=0)
-    for k in KEYS:
-        assert np.all(out[k] == -7), k
+    launch(pkg, eng, arrays, 3, n=0)                                   # (check_guarded: returns 0, every slot is still poison)
 
 
 # ---- loops ----

@@ -11,12 +11,13 @@ import torch
 import conflict_cases as TC
 import gap_cases as GC
 import gaps_numpy as GN
-from gpu_helpers import W, iroutes, loop_engine  # noqa: F401
+from gpu_helpers import W, check_guarded, guarded_outputs, iroutes, loop_engine  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 KEYS = ("off", "ep_gap", "ep_tick", "ep_who", "ep_off")
 ALL = ("off", "gap", "who", "ep_gap", "ep_tick", "ep_who", "ep_off")
 POISON = {"off": 85, "ep_gap": -85, "ep_tick": -85, "ep_who": -85, "ep_off": -85}   # values no output can take
+SPEC = [(k, np.int8, (8,), POISON[k]) if k == "off" else (k, np.int32, (), POISON[k]) for k in KEYS]
 
 
 @pytest.fixture(scope="module")
@@ -38,30 +39,20 @@ def device_inputs(eng, A, n):
 
 
 def launch(pkg, eng, A, window, within, n=GC.N, rc_want=0, **over):
-    """jsim_loop_eval_gaps on the first n ticks of recorder arrays.  The outputs are poisoned and have one row of guard slots in
-    front of the [n][B] the call may write and one behind: the guards must stay, and every slot between must be written.  Returns
-    numpy outputs with gap and who derived as Recorder.gaps derives them."""
+    """jsim_loop_eval_gaps on the first n ticks of recorder arrays, on guarded outputs (gpu_helpers.guarded_outputs).  Returns numpy
+    outputs with gap and who derived as Recorder.gaps derives them."""
     B = A["rec"].shape[1]
     rec, flags, obs, xf, xs, veh, mate = device_inputs(eng, A, n)
     shapes, ego = np.ascontiguousarray(A["shapes"]), np.array(GC.CAR)
-    buf = {k: torch.full((n + 2, B, 8) if k == "off" else (n + 2, B), POISON[k], dtype=torch.int8 if k == "off" else torch.int32, device=eng.device)
-           for k in KEYS}
+    views, buf = guarded_outputs(SPEC, n, B, eng.device)
     p = lambda t: t.data_ptr()
-    args = dict(B=B, n=n, n_obs=A["obs"].shape[1], window=window, within=GN.WITHIN.get(within, within), **{k: p(buf[k][1:]) for k in KEYS})
+    args = dict(B=B, n=n, n_obs=A["obs"].shape[1], window=window, within=GN.WITHIN.get(within, within), **{k: p(v) for k, v in views.items()})
     args.update(over)
     rc = eng.lib.jsim_loop_eval_gaps(eng._ctx, args["B"], args["n"], p(rec), p(flags), args["n_obs"], p(obs), p(xf), p(xs), p(veh), p(mate),
                                      shapes.ctypes.data, ego.ctypes.data, args["window"], args["within"], *[args[k] for k in KEYS], None)
-    torch.cuda.synchronize()
-    host = {k: v.cpu().numpy() for k, v in buf.items()}
-    if rc_want != 0 or args["n"] == 0 or args["B"] == 0:               # refused, or nothing to do: nothing is written
-        assert rc == rc_want, rc
-        assert all(np.all(host[k] == POISON[k]) for k in KEYS)
-        return eng.lib.jsim_last_error(eng._ctx).decode()
-    pkg._cabi.check(rc, eng._ctx, "jsim_loop_eval_gaps")
-    for k in KEYS:
-        assert np.all(host[k][0] == POISON[k]) and np.all(host[k][n + 1] == POISON[k]), ("guard", k, window, within, n)
-        assert not np.any(host[k][1:n + 1] == POISON[k]), ("unwritten", k, window, within, n)
-    out = {k: host[k][1:n + 1] for k in KEYS}
+    out = check_guarded(pkg, eng, "jsim_loop_eval_gaps", SPEC, buf, n, rc, rc_want, nothing=args["n"] == 0 or args["B"] == 0, what=(window, within))
+    if isinstance(out, str):                                           # refused, or nothing to do: the library's message
+        return out
     out["gap"], out["who"] = pkg.history.gap_per_tick(out["off"])
     return out
 

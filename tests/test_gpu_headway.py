@@ -20,7 +20,7 @@ import torch
 
 import headway_cases as HC
 import headway_numpy as HN
-from gpu_helpers import W, iroutes, loop_engine  # noqa: F401
+from gpu_helpers import W, check_guarded, guarded_outputs, iroutes, loop_engine  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 INTS = ("lead", "ttc_who", "ep_i")
@@ -30,6 +30,7 @@ DOUBLES = TICKS + ("ep_d",) + PLACES
 KEYS = ("lead", "lead_gap", "thw", "ttc", "ttc_who", "u_ego", "ep_i", "ep_d") + PLACES      # the entry point's order
 WIDTH = {"ep_i": HN.NI, "ep_d": HN.ND, "gap": 8, "lat": 8, "rate": 8}
 POISON_I, POISON_D = -85, -8.5e85                                      # values no output can take
+SPEC = [(k, np.int32 if k in INTS else np.float64, (WIDTH[k],) if k in WIDTH else (), POISON_I if k in INTS else POISON_D) for k in KEYS]
 OF_VALUE = ("thw", "ttc", "ep_d.thw_min", "ep_d.ttc_min", "ep_d.thw_mean")   # relative to the value itself
 EP_D = ("gap_min", "thw_min", "ttc_min", "thw_mean")
 SEEN = {"gap": 7.11e-15, "lat": 3.67e-15, "rate": 1.59e-15, "lead_gap": 5.11e-15, "thw": 2.47e-16, "ttc": 1.01e-15, "u_ego": 2.22e-16,
@@ -63,8 +64,7 @@ def whole(pkg, eng, arrays):
 
 def launch(pkg, eng, A, n=HC.N, egos=None, rc_want=0, places=True, margin=HC.LAUNCH_MARGIN, **over):
     """jsim_loop_eval_headway on the first n ticks of recorder arrays (egos: a subset of the cases that are nobody's mate, in that
-    order).  The outputs are poisoned and have one row of guard slots in front of the [n][B] the call may write and one behind: the
-    guards must stay, and every slot between must be written.  Returns numpy outputs."""
+    order), on guarded outputs (gpu_helpers.guarded_outputs; places=False: without the per-place ones).  Returns numpy outputs."""
     e = np.arange(A["rec"].shape[1]) if egos is None else np.asarray(egos)
     mate = A["mate_range"] if egos is None else np.zeros((len(e), 2), dtype=np.int32)
     assert egos is None or all(A["mate_range"][b, 0] == A["mate_range"][b, 1] for b in e)
@@ -72,35 +72,23 @@ def launch(pkg, eng, A, n=HC.N, egos=None, rc_want=0, places=True, margin=HC.LAU
     up = lambda a, dt=np.float64: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(dev)
     m = max(n, 1)
     t = pkg.history.path_table(A["paths"])
-    keys = [k for k in KEYS if places or k not in PLACES]
+    spec = [s for s in SPEC if places or s[0] not in PLACES]
     dv = dict(rec=up(A["rec"][:m, e]), flags=up(A["flags"][:m, e], np.int32), obs_rec=up(A["obs"][:m]), x_first=up(A["x_first"][e]),
               x_spawn=up(A["x_spawn"][e]), veh_range=up(A["veh_range"][e], np.int32), mate_range=up(mate, np.int32),
               path_id=up(A["path_id"][e], np.int32), px=up(t["x"]), py=up(t["y"]), pyaw=up(t["yaw"]), path_off=up(t["off"], np.int64),
               arc=up(t["arc_flat"]))
-    buf = {k: torch.full((n + 2, B) + ((WIDTH[k],) if k in WIDTH else ()), POISON_I if k in INTS else POISON_D,
-                         dtype=torch.int32 if k in INTS else torch.float64, device=dev) for k in keys}
+    views, buf = guarded_outputs(spec, n, B, dev)
     shapes = np.ascontiguousarray(A["shapes"], dtype=np.float64)
     ego = np.array(HC.CAR, dtype=np.float64)
     a = dict(B=B, n=n, n_obs=A["obs"].shape[1], n_pts=len(t["x"]), n_paths=len(A["paths"]), margin=margin, shapes=shapes.ctypes.data,
-             ego_shape=ego.ctypes.data, **dv, **{k: buf[k][1:] for k in keys}, **{k: None for k in PLACES if not places})
+             ego_shape=ego.ctypes.data, **dv, **views, **{k: None for k in PLACES if not places})
     a.update(over)
     p = lambda x: x.data_ptr() if isinstance(x, torch.Tensor) else x
     rc = eng.lib.jsim_loop_eval_headway(eng._ctx, a["B"], a["n"], p(a["rec"]), p(a["flags"]), a["n_obs"], p(a["obs_rec"]), p(a["x_first"]),
                                         p(a["x_spawn"]), p(a["veh_range"]), p(a["mate_range"]), a["shapes"], a["ego_shape"], p(a["path_id"]),
                                         a["n_pts"], p(a["px"]), p(a["py"]), p(a["pyaw"]), a["n_paths"], p(a["path_off"]), p(a["arc"]),
                                         a["margin"], *[p(a[k]) for k in KEYS], None)
-    torch.cuda.synchronize()
-    host = {k: v.cpu().numpy() for k, v in buf.items()}
-    poison = lambda k: POISON_I if k in INTS else POISON_D
-    if rc_want != 0 or a["n"] == 0 or a["B"] == 0:                         # refused, or nothing to do: nothing is written
-        assert rc == rc_want, rc
-        assert all(np.all(host[k] == poison(k)) for k in keys)
-        return eng.lib.jsim_last_error(eng._ctx).decode()
-    pkg._cabi.check(rc, eng._ctx, "jsim_loop_eval_headway")
-    for k in keys:
-        assert np.all(host[k][0] == poison(k)) and np.all(host[k][n + 1] == poison(k)), ("guard", k, n)
-        assert not np.any(host[k][1:n + 1] == poison(k)), ("unwritten", k, n)
-    return {k: host[k][1:n + 1] for k in keys}
+    return check_guarded(pkg, eng, "jsim_loop_eval_headway", spec, buf, n, rc, rc_want, nothing=a["n"] == 0 or a["B"] == 0)
 
 
 def relative(out, ref, of_value):

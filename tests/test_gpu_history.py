@@ -286,3 +286,18 @@ def test_graph_replay_and_overflow(pkg, W, iroutes):
     with pytest.warns(RuntimeWarning):
         hs = eager.recorder.histories(0)
     assert sum(len(h) - 1 for h in hs) == 2 * K
+
+
+def test_no_tick_recorded_yet_evaluates_to_nothing(pkg, W, iroutes):
+    """A recorder that holds no tick yet: every evaluator still hands its entry point valid pointers (an empty tensor has none),
+    the call returns and the result has no rows, of the trailing shapes of history.EVALUATORS."""
+    B = 3
+    eng, x0 = loop_engine(pkg, iroutes, W.ego_batch(iroutes, B, 13, rank=2), 13)
+    r = pkg.ScenarioLoop(eng, x0, W.OBSTACLE_SPECS[:2], record=4).recorder
+    res = {"reasons": r._reasons_device(), "conflicts": r.conflicts(), "gaps": r.gaps(), "tracking": r.tracking(), "headway": r.headway(),
+           "static": r.static_conflicts(pkg.planner.intersection_obstacles(1, 1)), "cutoffs": r.cutoffs()}
+    assert set(res) == set(pkg.history.EVALUATORS)
+    for name, out in res.items():
+        for k, _, shape in pkg.history.EVALUATORS[name].outputs:
+            assert tuple(out[k].shape) == (0, B, *shape), (name, k)
+    assert r.reasons()["first_replan"].tolist() == [-1] * B and r.gaps()["gap"].shape == (0, B)

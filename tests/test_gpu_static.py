@@ -14,11 +14,12 @@ import torch
 
 import static_cases as SC
 import static_numpy as SN
-from gpu_helpers import W, iroutes, loop_engine, sub_batch  # noqa: F401
+from gpu_helpers import W, check_guarded, guarded_outputs, iroutes, loop_engine, sub_batch  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 BAR = 1e-12
 KEYS = ("clear", "who", "hit", "off_tick")
+SPEC = [(k, np.float64, (), -8.5e85) if k == "clear" else (k, np.int32, (), -85) for k in KEYS]   # (the poison: values no output can take)
 
 
 @pytest.fixture(scope="module")
@@ -32,9 +33,9 @@ def arrays():
     return SC.recorder_arrays(SC.cases())
 
 
-def launch(pkg, eng, A, hidden, n=SC.N, egos=None, set_of=None, fill=-7):
+def launch(pkg, eng, A, hidden, n=SC.N, egos=None, set_of=None):
     """jsim_loop_eval_static on the first n ticks of recorder arrays (egos: these egos only, in this order) against the fixture's
-    tables.  Returns numpy outputs; what the call does not write stays `fill`."""
+    tables, on guarded outputs (gpu_helpers.guarded_outputs).  Returns numpy outputs."""
     g = SC.fixture()
     idx = np.arange(A["rec"].shape[1]) if egos is None else np.asarray(egos)
     B = len(idx)
@@ -45,14 +46,11 @@ def launch(pkg, eng, A, hidden, n=SC.N, egos=None, set_of=None, fill=-7):
     xf, xs = up(A["x_first"][idx]), up(A["x_spawn"][idx])
     sof = up(A["set_of"][idx] if set_of is None else set_of, np.int32)
     rows, off, ego = np.ascontiguousarray(g["rows"]), np.ascontiguousarray(g["set_off"], dtype=np.int32), np.array(SC.CAR)
-    out = {k: torch.full((m, B), float(fill) if k == "clear" else fill, dtype=torch.float64 if k == "clear" else torch.int32, device=dev)
-           for k in KEYS}
+    out, buf = guarded_outputs(SPEC, n, B, dev)
     p = lambda t: t.data_ptr()
     rc = eng.lib.jsim_loop_eval_static(eng._ctx, B, n, p(rec), p(flags), p(xf), p(xs), p(sof), len(off) - 1, off.ctypes.data, len(rows),
                                        rows.ctypes.data, ego.ctypes.data, int(hidden), *[p(out[k]) for k in KEYS], None)
-    pkg._cabi.check(rc, eng._ctx, "jsim_loop_eval_static")
-    torch.cuda.synchronize()
-    return {k: v[:n].cpu().numpy() if n else v.cpu().numpy() for k, v in out.items()}
+    return check_guarded(pkg, eng, "jsim_loop_eval_static", SPEC, buf, n, rc, nothing=n == 0)
 
 
 @pytest.fixture(scope="module")
@@ -120,9 +118,7 @@ def test_a_set_outside_the_sets_is_an_empty_set(pkg, eng, arrays):
 
 
 def test_nothing_to_do_writes_nothing(pkg, eng, arrays):
-    out = launch(pkg, eng, arrays, 1, n=0)
-    for k in KEYS:
-        assert np.all(out[k] == -7), k
+    launch(pkg, eng, arrays, 1, n=0)                                   # (check_guarded: returns 0, every slot is still poison)
 
 
 # ---- a loop: four egos, one per start position, each against its own scenario's obstacles ----

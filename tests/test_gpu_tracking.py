@@ -13,13 +13,14 @@ import torch
 
 import tracking_cases as KC
 import tracking_numpy as TN
-from gpu_helpers import W, iroutes, loop_engine  # noqa: F401
+from gpu_helpers import W, check_guarded, guarded_outputs, iroutes, loop_engine  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 INTS, DOUBLES = ("idx", "seg", "ep_i"), ("s", "d", "e_yaw", "ep_d")
 KEYS = ("idx", "seg", "s", "d", "e_yaw", "ep_i", "ep_d")
 WIDTH = {"ep_i": TN.NI, "ep_d": TN.ND}
 POISON_I, POISON_D = -85, -8.5e85                                      # values no output can take
+SPEC = [(k, np.int32 if k in INTS else np.float64, (WIDTH[k],) if k in WIDTH else (), POISON_I if k in INTS else POISON_D) for k in KEYS]
 BAR = 1e-12
 
 
@@ -41,9 +42,8 @@ def restated(arrays):
 
 
 def launch(pkg, eng, A, n=KC.N, egos=None, rc_want=0, **over):
-    """jsim_loop_eval_tracking on the first n ticks of recorder arrays (egos: a subset, in that order).  The outputs are poisoned and
-    have one row of guard slots in front of the [n][B] the call may write and one behind: the guards must stay, and every slot
-    between must be written.  Returns numpy outputs."""
+    """jsim_loop_eval_tracking on the first n ticks of recorder arrays (egos: a subset, in that order), on guarded outputs
+    (gpu_helpers.guarded_outputs).  Returns numpy outputs."""
     e = np.arange(A["rec"].shape[1]) if egos is None else np.asarray(egos)
     B, dev = len(e), eng.device
     up = lambda a, dt=np.float64: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(dev)
@@ -51,25 +51,13 @@ def launch(pkg, eng, A, n=KC.N, egos=None, rc_want=0, **over):
     t = pkg.history.path_table(A["paths"])
     rec, flags, pid = up(A["rec"][:m, e]), up(A["flags"][:m, e], np.int32), up(A["path_id"][e], np.int32)
     tab = {"px": up(t["x"]), "py": up(t["y"]), "pyaw": up(t["yaw"]), "path_off": up(t["off"], np.int64), "arc": up(t["arc_flat"])}
-    buf = {k: torch.full((n + 2, B) + ((WIDTH[k],) if k in WIDTH else ()), POISON_I if k in INTS else POISON_D,
-                         dtype=torch.int32 if k in INTS else torch.float64, device=dev) for k in KEYS}
+    views, buf = guarded_outputs(SPEC, n, B, dev)
     p = lambda x: None if x is None else x.data_ptr()
-    a = dict(B=B, n=n, rec=rec, flags=flags, path_id=pid, n_pts=len(t["x"]), n_paths=len(A["paths"]), **tab, **{k: buf[k][1:] for k in KEYS})
+    a = dict(B=B, n=n, rec=rec, flags=flags, path_id=pid, n_pts=len(t["x"]), n_paths=len(A["paths"]), **tab, **views)
     a.update(over)
     rc = eng.lib.jsim_loop_eval_tracking(eng._ctx, a["B"], a["n"], p(a["rec"]), p(a["flags"]), p(a["path_id"]), a["n_pts"], p(a["px"]), p(a["py"]),
                                          p(a["pyaw"]), a["n_paths"], p(a["path_off"]), p(a["arc"]), *[p(a[k]) for k in KEYS], None)
-    torch.cuda.synchronize()
-    host = {k: v.cpu().numpy() for k, v in buf.items()}
-    poison = lambda k: POISON_I if k in INTS else POISON_D
-    if rc_want != 0 or a["n"] == 0 or a["B"] == 0:                         # refused, or nothing to do: nothing is written
-        assert rc == rc_want, rc
-        assert all(np.all(host[k] == poison(k)) for k in KEYS)
-        return eng.lib.jsim_last_error(eng._ctx).decode()
-    pkg._cabi.check(rc, eng._ctx, "jsim_loop_eval_tracking")
-    for k in KEYS:
-        assert np.all(host[k][0] == poison(k)) and np.all(host[k][n + 1] == poison(k)), ("guard", k, n)
-        assert not np.any(host[k][1:n + 1] == poison(k)), ("unwritten", k, n)
-    return {k: host[k][1:n + 1] for k in KEYS}
+    return check_guarded(pkg, eng, "jsim_loop_eval_tracking", SPEC, buf, n, rc, rc_want, nothing=a["n"] == 0 or a["B"] == 0)
 
 
 def errors(out, ref, what):

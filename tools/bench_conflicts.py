@@ -23,11 +23,10 @@ def launch_alone(pkg, torch, r, out, w, warmup, runs):
     up = lambda x: torch.from_numpy(np.ascontiguousarray(x, dtype=np.int32)).to(dev)
     veh, mate = up(out["veh_range"]), up(out["mate_range"])
     ego = np.array(out["ego_shape"])
-    f64 = [torch.empty(n, B, dtype=torch.float64, device=dev), torch.empty(n, B, 2, dtype=torch.float64, device=dev)]
-    i32 = [torch.empty(n, B, dtype=torch.int32, device=dev) for _ in range(4)]
+    outs = r._outputs("conflicts", n)
     p = lambda t: t.data_ptr()
     call = lambda: eng.lib.jsim_loop_eval_conflicts(eng._ctx, B, n, p(r.rec), p(r.flags), r.n_obs, p(r.obs), p(r.x0_first), p(r.loop.x0_spawn),
-                                                    p(veh), p(mate), None, ego.ctypes.data, w, p(f64[0]), *[p(t) for t in i32], p(f64[1]), None)
+                                                    p(veh), p(mate), None, ego.ctypes.data, w, *[p(t) for t in outs.values()], None)
     return RB.launch_alone(pkg, torch, eng, "jsim_loop_eval_conflicts", call, runs, warmup)
 
 
@@ -53,7 +52,7 @@ def main():
             res["numpy_ms"][key] = min(tn)
             te, eps = RB.timed(lambda: pkg.history.conflict_episodes(out, host[1]), 3)
             res["episodes_ms"][key] = min(te)
-            for k in ("who", "row", "hit_tick", "hit_frame"):
+            for k in RB.output_keys(pkg, "conflicts", "i"):
                 assert np.array_equal(out[k], ref[k]), (key, k)
             assert np.array_equal(out["hit_xy"], ref["hit_xy"], equal_nan=True), key
             res["max_clear_err"][key] = float(np.max(np.abs(out["clear"] - ref["clear"]) / np.maximum(1.0, np.abs(ref["clear"]))))

@@ -33,8 +33,8 @@ def launches_alone(pkg, torch, r, obstacles, warmup, runs):
     ep_i = torch.empty(cap, len(H.EP_INT), dtype=torch.int32, device=dev)
     ep_d = torch.empty(cap, len(H.EP_DOUBLE), dtype=torch.float64, device=dev)
     p = lambda t: t.data_ptr()
-    series = [p(c[k]) for k in ("clear", "who", "hit_tick", "hit_frame", "hit_xy")] + [p(s[k]) for k in ("clear", "who", "hit", "off_tick")] + \
-             [p(q["val"]), p(q["trig"])]
+    keys = lambda name, skip=(): H.EVALUATORS[name].keys(skip)           # (the table of episodes takes no row and no timers)
+    series = [p(c[k]) for k in keys("conflicts", ("row",))] + [p(s[k]) for k in keys("static")] + [p(q[k]) for k in keys("reasons", ("timers",))]
     call = lambda: eng.lib.jsim_loop_summarise_episodes(eng._ctx, B, n, p(r.rec), p(r.flags), p(r.x0_first), p(r.loop.x0_spawn), *series, cap,
                                                         p(off), p(ep_i), p(ep_d), None)
     return RB.launch_alone(pkg, torch, eng, "jsim_loop_summarise_episodes", call, runs, warmup)

@@ -44,24 +44,23 @@ def main():
     loop = pkg.ScenarioLoop(eng, x0, W.OBSTACLE_SPECS, max_age=W.MAX_AGE, hist_cap=K, record=K)
     loop.run(K)
     torch.cuda.synchronize()
-    r, dev = loop.recorder, eng.device
+    r = loop.recorder
     host = [r.rec.cpu().numpy(), r.flags.cpu().numpy(), r.obs.cpu().numpy(), r.x0_first.cpu().numpy(), r.loop.x0_spawn.cpu().numpy()]
-    new = lambda dt, *shape: torch.empty(K, B, *shape, dtype=dt, device=dev)
     res = {"egos": B, "ticks": K, "T": T, "vehicles": len(W.OBSTACLE_SPECS), "runs": a.runs, "warmup": a.warmup, "within": "episode",
            "episodes": int(sum(r.episodes()["count"])), "launch_ms": {}, "call_ms": {}, "numpy_ms": {}, "ticks_with_a_gap": {}, "episode_gaps": {}}
     # the merged kernel at frame_window 20 on the same buffers
     ts, con = RB.timed(lambda: r.conflicts(frame_window=20), a.runs, a.warmup)
     res["conflicts_w20_call_ms"] = RB.stats(ts)
-    outs = [new(torch.float64), *[new(torch.int32) for _ in range(4)], new(torch.float64, 2)]
+    outs = r._outputs("conflicts", K).values()
     res["conflicts_w20_launch_ms"] = launch_alone(pkg, torch, r, con, "jsim_loop_eval_conflicts", (20,), outs, a.warmup, a.runs)
     for w in WINDOWS:
         ts, out = RB.timed(lambda: r.gaps(window=w), a.runs, a.warmup)
         res["call_ms"][f"w{w}"] = RB.stats(ts)
-        outs = [new(torch.int8, 8), *[new(torch.int32) for _ in range(4)]]
+        outs = r._outputs("gaps", K).values()
         res["launch_ms"][f"w{w}"] = launch_alone(pkg, torch, r, out, "jsim_loop_eval_gaps", (w, 0), outs, a.warmup, a.runs)
         tn, ref = RB.timed(lambda: GN.eval_gaps(*host, out["veh_range"], out["mate_range"], eng.vehicle_shapes, out["ego_shape"], w, 0), 1)
         res["numpy_ms"][f"w{w}"] = tn[0]
-        for k in ("off", "gap", "who", "ep_gap", "ep_tick", "ep_who", "ep_off"):
+        for k in RB.output_keys(pkg, "gaps") + ("gap", "who"):
             assert np.array_equal(out[k], ref[k]), (w, k)
         if w == 20:
             assert np.array_equal(out["gap"] >= 0, con["contact"])

@@ -21,9 +21,6 @@ import numpy as np
 import bench_tracking as BT
 import recorder_bench as RB
 
-OUTS = ("lead", "lead_gap", "thw", "ttc", "ttc_who", "u_ego", "ep_i", "ep_d")
-PLACES = ("gap", "lat", "rate")
-
 
 def launch_alone(pkg, torch, r, places, warmup, runs):
     """ms between two events around jsim_loop_eval_headway on device buffers allocated once: the call without its read-back."""
@@ -44,7 +41,7 @@ def launch_alone(pkg, torch, r, places, warmup, runs):
         rc = eng.lib.jsim_loop_eval_headway(eng._ctx, B, n, p(r.rec), p(r.flags), r.n_obs, p(r.obs), p(r.x0_first), p(r.loop.x0_spawn), p(veh),
                                             p(mate), None if shapes is None else shapes.ctypes.data, C.cast(ego, C.c_void_p), p(eng.path_id),
                                             int(px.numel()), p(px), p(py), p(pyaw), len(eng.paths), p(off), p(arc), 0.0,
-                                            *[p(d[k]) for k in OUTS], *[p(d.get(k)) for k in PLACES], eng._stream())
+                                            *[p(d.get(k)) for k in RB.output_keys(pkg, "headway")], eng._stream())   # (no places: NULL)
         t1.record()
         torch.cuda.synchronize()
         pkg._cabi.check(rc, eng._ctx, "jsim_loop_eval_headway")
@@ -86,8 +83,8 @@ def main():
         eps = pkg.history.headway_episodes(out, r.flags.cpu().numpy(), eng.dt)
         res["episodes"][key] = int(sum(len(ep) for ep in eps))
         res["lead_ticks"][key] = int((out["lead"] >= 0).sum())
-        res["mismatches"][key] = {k: int((out[k][:, :m] != ref[k]).sum()) for k in ("lead", "ttc_who", "ep_i")}
-        doubles = ("lead_gap", "thw", "ttc", "u_ego", "ep_d") + PLACES
+        res["mismatches"][key] = {k: int((out[k][:, :m] != ref[k]).sum()) for k in RB.output_keys(pkg, "headway", "i")}
+        doubles = RB.output_keys(pkg, "headway", "f")
         res["mismatches"][key]["nan_inf"] = int(sum((np.isnan(out[k][:, :m]) != np.isnan(ref[k])).sum() + (np.isinf(out[k][:, :m]) != np.isinf(ref[k])).sum()
                                                     for k in doubles))
         err = {}

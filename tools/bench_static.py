@@ -25,12 +25,11 @@ def launch_alone(pkg, torch, r, out, rows, hidden, warmup, runs):
     B, n, dev = eng.B, r.rec.shape[0], eng.device
     sof = torch.from_numpy(np.ascontiguousarray(out["set_of"], dtype=np.int32)).to(dev)
     ego, off = np.array(out["ego_shape"]), np.array([0, len(rows)], dtype=np.int32)
-    clear = torch.empty(n, B, dtype=torch.float64, device=dev)
-    i32 = [torch.empty(n, B, dtype=torch.int32, device=dev) for _ in range(3)]
+    outs = r._outputs("static", n)
     p = lambda t: t.data_ptr()
     call = lambda: eng.lib.jsim_loop_eval_static(eng._ctx, B, n, p(r.rec), p(r.flags), p(r.x0_first), p(r.loop.x0_spawn), p(sof), 1,
-                                                 off.ctypes.data, len(rows), rows.ctypes.data, ego.ctypes.data, hidden, p(clear),
-                                                 *[p(t) for t in i32], None)
+                                                 off.ctypes.data, len(rows), rows.ctypes.data, ego.ctypes.data, hidden,
+                                                 *[p(t) for t in outs.values()], None)
     return RB.launch_alone(pkg, torch, eng, "jsim_loop_eval_static", call, runs, warmup)
 
 
@@ -59,7 +58,7 @@ def main():
             res["numpy_ms"][key] = min(tn)
             te, eps = RB.timed(lambda: pkg.history.static_episodes(out, host[1]), 2)
             res["episodes_ms"][key] = min(te)
-            res["mismatches"][key] = {k: int((out[k] != ref[k]).sum()) for k in ("who", "hit", "off_tick")}
+            res["mismatches"][key] = {k: int((out[k] != ref[k]).sum()) for k in RB.output_keys(pkg, "static", "i")}
             res["max_clear_err"][key] = float(np.max(np.abs(out["clear"] - ref["clear"]) / np.maximum(1.0, np.abs(ref["clear"]))))
             res["ticks_touching"][key] = int(out["contact"].sum())
             res["episodes"][key] = int(sum(len(ep) for ep in eps))

@@ -32,7 +32,7 @@ def launch_alone(pkg, torch, r, warmup, runs):
         t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         t0.record()
         rc = eng.lib.jsim_loop_eval_tracking(eng._ctx, B, n, p(r.rec), p(r.flags), p(eng.path_id), int(px.numel()), p(px), p(py), p(pyaw),
-                                             len(eng.paths), p(off), p(arc), *[p(d[k]) for k in ("idx", "seg", "s", "d", "e_yaw", "ep_i", "ep_d")],
+                                             len(eng.paths), p(off), p(arc), *[p(d[k]) for k in RB.output_keys(pkg, "tracking")],
                                              eng._stream())
         t1.record()
         torch.cuda.synchronize()
@@ -47,6 +47,7 @@ def main():
     torch, pkg = RB.setup("bench_tracking")
     import tracking_numpy as TN
     K = a.ticks
+    ints, doubles = RB.output_keys(pkg, "tracking", "i"), RB.output_keys(pkg, "tracking", "f")
     res = {"ticks": K, "T": RB.T, "runs": a.runs, "warmup": a.warmup, "numpy_runs": a.numpy_runs, "path_points": {}, "launch_ms": {}, "call_ms": {},
            "copy_ms": {}, "numpy_ms": {}, "episodes_ms": {}, "output_bytes": {}, "episodes": {}, "max_err": {}, "mismatches": {}, "d_rms_median": {}}
     for B in ((a.egos,) if a.egos else (256, 4096)):
@@ -58,7 +59,7 @@ def main():
         res["call_ms"][key] = RB.stats(ts)
         res["launch_ms"][key] = launch_alone(pkg, torch, r, a.warmup, a.runs)
         dev = r._tracking_device()                                  # each output's device-to-host copy by itself
-        for k in ("idx", "seg", "s", "d", "e_yaw", "ep_i", "ep_d"):
+        for k in RB.output_keys(pkg, "tracking"):
             res["copy_ms"].setdefault(key, {})[k] = statistics.median(RB.timed(lambda: dev[k].cpu().numpy(), a.runs, a.warmup)[0])
         print(f"B = {B}: launch {res['launch_ms'][key]}, call {res['call_ms'][key]}; the restatement next", file=sys.stderr, flush=True)
         res["output_bytes"][key] = K * B * (4 + 4 + 8 + 8 + 8 + 4 * TN.NI + 8 * TN.ND)
@@ -69,10 +70,10 @@ def main():
         res["episodes_ms"][key] = min(te)
         res["episodes"][key] = int(sum(len(ep) for ep in eps))
         res["d_rms_median"][key] = float(np.nanmedian([e["d_rms"] for ep in eps for e in ep]))
-        res["mismatches"][key] = {k: int((out[k] != ref[k]).sum()) for k in ("idx", "seg", "ep_i")}
+        res["mismatches"][key] = {k: int((out[k] != ref[k]).sum()) for k in ints}
         with np.errstate(invalid="ignore"):
-            res["max_err"][key] = {k: float(np.nanmax(np.abs(out[k] - ref[k]) / np.maximum(1.0, np.abs(ref[k])), initial=0.0)) for k in ("s", "d", "e_yaw", "ep_d")}
-        res["mismatches"][key]["nan"] = int(sum((np.isnan(out[k]) != np.isnan(ref[k])).sum() for k in ("s", "d", "e_yaw", "ep_d")))
+            res["max_err"][key] = {k: float(np.nanmax(np.abs(out[k] - ref[k]) / np.maximum(1.0, np.abs(ref[k])), initial=0.0)) for k in doubles}
+        res["mismatches"][key]["nan"] = int(sum((np.isnan(out[k]) != np.isnan(ref[k])).sum() for k in doubles))
     differs = any(v for m in res["mismatches"].values() for v in m.values()) or max(v for m in res["max_err"].values() for v in m.values()) > 1e-12
     RB.emit(res, a.out, "the device result differs from the restatement: see mismatches / max_err" if differs else None)
 

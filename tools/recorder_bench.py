@@ -8,6 +8,8 @@ import statistics
 import sys
 import time
 
+import numpy as np
+
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for _p in (os.path.join(REPO, "tests"), REPO):           # the restatements (tests/*_numpy.py) and the package
     if _p not in sys.path:
@@ -46,6 +48,12 @@ def recorded_loop(pkg, torch, B, K, specs=None, **loop_kw):
     loop.run(K)
     torch.cuda.synchronize()
     return loop.recorder
+
+
+def output_keys(pkg, name, kind=None):
+    """The per-tick outputs of evaluator `name` in its entry point's order (history.EVALUATORS); kind "i" / "f": the integer / the
+    floating-point ones only."""
+    return tuple(k for k, dt, _ in pkg.history.EVALUATORS[name].outputs if kind is None or np.dtype(dt).kind == kind)
 
 
 def stats(ts):
