@@ -36,6 +36,7 @@ EXPORTS = (
     "jsim_mpc_set_path_speed", "jsim_mpc_set_speed_cutoff", "jsim_mpc_update_cfg", "jsim_mpc_set_ego_config", "jsim_loop_obstacles",
     "jsim_mpc_xref_deviation_goal", "jsim_loop_run_scenario",
     "jsim_loop_set_groups", "jsim_loop_predict_egos", "jsim_loop_run_interacting",
+    "jsim_loop_set_mate_prediction", "jsim_loop_predict_egos_plan",
     "jsim_loop_set_traffic", "jsim_loop_set_recorder", "jsim_loop_set_vehicle_shapes",
     "jsim_comm_unique_id", "jsim_comm_init", "jsim_mpc_gather", "jsim_comm_destroy", "jsim_plan_routes",
     "jsim_plan_routes_weighted", "jsim_score_trajectories", "jsim_loop_eval_reasons", "jsim_loop_eval_conflicts",
@@ -52,6 +53,8 @@ class JsimError(RuntimeError):
 
 # per-ego status of a step / tick (include/jsim_mpc.h; 3: the ego has no path)
 STATUS_OK, STATUS_INFEASIBLE, STATUS_NEAREST_ANOMALY, STATUS_NO_PATH, STATUS_HELPER_TIMEOUT = 0, 1, 2, 3, 4
+# how jsim_loop_run_interacting predicts an ego for its group mates (JSIM_MATE_CONSTANT, JSIM_MATE_PLAN)
+MATE_PREDICTION = {"constant": 0, "plan": 1}
 
 
 def check_status(status, what: str) -> None:
@@ -133,6 +136,10 @@ def load() -> C.CDLL:
     lib.jsim_loop_set_recorder.argtypes = [vp, i32, i32, vp, vp, i32, vp]
     lib.jsim_loop_predict_egos.restype = C.c_int
     lib.jsim_loop_predict_egos.argtypes = [vp, i32, vp, vp, i32, vp, vp]
+    lib.jsim_loop_set_mate_prediction.restype = C.c_int
+    lib.jsim_loop_set_mate_prediction.argtypes = [vp, i32]
+    lib.jsim_loop_predict_egos_plan.restype = C.c_int
+    lib.jsim_loop_predict_egos_plan.argtypes = [vp, i32, vp, vp, vp, vp, vp, i32, vp, vp]
     lib.jsim_loop_run_interacting.restype = C.c_int
     lib.jsim_loop_run_interacting.argtypes = lib.jsim_loop_run_scenario.argtypes
     lib.jsim_mpc_xref_deviation_goal.restype = C.c_int

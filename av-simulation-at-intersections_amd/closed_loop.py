@@ -332,7 +332,8 @@ class _GlueLoop:
         if record:
             self.loop.recorder = Recorder(self.loop, record, n_obs=self.obst.n, groups=group_off)   # last: it records obst.n vehicles
             self.loop.recorder.glue = {"frame_window": self.pre.frame_window, "margin": self.pre.margin, "n_steps": self.pre.n_steps,
-                                       "mode": self.pre.mode, "interacting": group_off is not None}
+                                       "mode": self.pre.mode, "interacting": group_off is not None,
+                                       "mate_prediction": getattr(self, "mate_prediction", "constant")}
 
     def _register_groups(self):
         """Only InteractingLoop has groups."""
@@ -513,13 +514,23 @@ class InteractingLoop(_GlueLoop):
     run(n_ticks): n_ticks ticks in one call (jsim_loop_run_interacting; separate launches per tick).
     traffic_of ([n_groups] set indices): every group meets its own scripted vehicles -- obstacle_specs is then a list of traffic
     sets (traffic_layout); the vehicles of a group's set + the group - 1 <= 8, per group.
-    record: ticks of the full History kept on the device (`recorder`, as ScenarioLoop's); the egos are recorded like any other."""
+    record: ticks of the full History kept on the device (`recorder`, as ScenarioLoop's); the egos are recorded like any other.
+    mate_prediction: "constant" (above), or "plan": the egos share their MPC plans -- an ego is predicted
+    by rolling the controls its controller holds at the start of the tick (eng.oa, eng.od of its last solve, from element 1 on,
+    then the last steering held at constant speed; after a failed solve the steering applied last tick at constant speed) through
+    the plant's own step, so an ego that has planned to stop in front of a conflict is predicted to stop there.  The loop
+    constructed last on an engine sets the engine's mode.  A plan-mode recording has no Recorder.cutoffs(): the plans are not
+    recorded."""
 
     _ENTRY = "jsim_loop_run_interacting"
 
     def __init__(self, engine: BatchedMPC, x0: torch.Tensor, group_off=None, obstacle_specs=(), hist_cap: int = 0,
-                 max_age: int = 0, frame_window: int = 20, group_sizes=None, traffic_of=None, record: int = 0):
-        off = self.group_off = group_offsets(engine.B, group_off, group_sizes)        # before any device work
+                 max_age: int = 0, frame_window: int = 20, group_sizes=None, traffic_of=None, record: int = 0,
+                 mate_prediction: str = "constant"):
+        if mate_prediction not in _cabi.MATE_PREDICTION:                              # before any device work
+            raise ValueError(f"mate_prediction must be one of {sorted(_cabi.MATE_PREDICTION)}, got {mate_prediction!r}")
+        self.mate_prediction = mate_prediction
+        off = self.group_off = group_offsets(engine.B, group_off, group_sizes)
         n_obs, big = len(obstacle_specs), int(np.diff(off).max())
         if traffic_of is None and n_obs + big - 1 > MAX_GROUP:
             raise ValueError(f"{n_obs} scripted obstacles + the largest group ({big}) - 1 > {MAX_GROUP}")
@@ -527,14 +538,23 @@ class InteractingLoop(_GlueLoop):
                          group_off=off)
 
     def _register_groups(self):
+        """The groups and, every time, how their egos predict each other: a later loop on the same engine has its own mode."""
         eng, off = self.loop.eng, self.group_off
         _cabi.check(eng.lib.jsim_loop_set_groups(eng._ctx, eng.B, len(off) - 1, off.ctypes.data_as(C.c_void_p)), eng._ctx,
                     "jsim_loop_set_groups")
+        _cabi.check(eng.lib.jsim_loop_set_mate_prediction(eng._ctx, _cabi.MATE_PREDICTION[self.mate_prediction]), eng._ctx,
+                    "jsim_loop_set_mate_prediction")
 
     def pred_egos(self) -> torch.Tensor:
-        """[B, n_steps, 3] (x, y, yaw): every ego's prediction from its current state, as the next tick will make it."""
+        """[B, n_steps, 3] (x, y, yaw): every ego's prediction from its current state, as the next tick will make it (under the
+        loop's mate_prediction)."""
         eng = self.loop.eng
         pred = torch.zeros(eng.B, self.pre.n_steps, 3, dtype=torch.float64, device=eng.device)
+        if self.mate_prediction == "plan":
+            _cabi.check(eng.lib.jsim_loop_predict_egos_plan(eng._ctx, eng.B, _ptr(self.loop.x0), _ptr(eng.oa), _ptr(eng.od),
+                                                            _ptr(eng.status), _ptr(eng.di_ai), self.pre.n_steps, _ptr(pred),
+                                                            eng._stream()), eng._ctx, "jsim_loop_predict_egos_plan")
+            return pred
         _cabi.check(eng.lib.jsim_loop_predict_egos(eng._ctx, eng.B, _ptr(self.loop.x0), _ptr(eng.di_ai), self.pre.n_steps,
                                                    _ptr(pred), eng._stream()), eng._ctx, "jsim_loop_predict_egos")
         return pred

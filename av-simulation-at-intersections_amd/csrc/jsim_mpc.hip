@@ -1388,6 +1388,7 @@ struct jsim_ctx {
     DevArray<int> d_group_of, d_group_off; // [group_B], [n_groups + 1]
     std::vector<int> h_group_off;          // host copy (the traffic checks of jsim_loop_run_interacting)
     int group_B = 0, n_groups = 0, group_max = 0;
+    int mate_prediction = JSIM_MATE_CONSTANT; // how jsim_loop_run_interacting predicts the group mates (jsim_loop_set_mate_prediction)
     // traffic sets (jsim_loop_set_traffic): ego -> set, set -> its vehicles in the [total] obstacle tables; host copies to validate
     DevArray<int> d_set_of, d_obs_off;     // [traffic_B], [n_sets + 1]
     std::vector<int> h_set_of, h_obs_off;
@@ -2862,6 +2863,16 @@ static int32_t *glue_out(const jsim_ctx *ctx, const StepBufs &S, const GlueBufs 
     return const_cast<int32_t *>(G.speed_cutoff ? ctx->cv_cut : S.path_len);
 }
 
+// the egos' predictions under the plan rule (JSIM_MATE_PLAN): one wavefront per ego, wheelbase and clamps as plant_p's
+static void launch_ego_plan_predict(jsim_ctx *ctx, int B, const double *x0, const double *oa, const double *od, const int32_t *status,
+                                    const double *di_ai, int n_steps, double *pred, hipStream_t s)
+{
+    const jsim_cfg &c = ctx->cfg;
+    EgoPlanP P = {B, n_steps, c.T, c.dt, c.L, c.max_steer, c.max_speed, c.min_speed, ctx->cc0, ctx->cc1, x0, oa, od, status, di_ai,
+                  pred, ctx->d_ego_cc, ctx->d_ego_bc};
+    hipLaunchKernelGGL(ego_plan_predict_kernel, dim3(B), dim3(64), 0, s, P);
+}
+
 enum class Glue { none, scripted, interacting };
 
 // n_ticks ticks as separate launches, the calls the tick() methods of closed_loop.py make.  With a glue (G): scripted obstacles
@@ -2907,7 +2918,10 @@ static int run_host_ticks(jsim_ctx *ctx, int B, int n_ticks, const StepBufs &S, 
             ctx->pred_n_obs = traffic ? 0 : G->n_obs; ctx->pred_n_steps = G->n_steps;
             if (G->n_obs > 0) launch_obstacle_predict(ctx, G->n_obs, G->n_steps, G->obs_get, nullptr, pred_cc, pred_bc, 1, s);
             if (kind == Glue::interacting) {
-                launch_ego_predict(ctx, B, S.x0, A.di_ai, G->n_steps, nullptr, s);
+                if (ctx->mate_prediction == JSIM_MATE_PLAN)
+                    launch_ego_plan_predict(ctx, B, S.x0, S.oa, S.od, S.status, A.di_ai, G->n_steps, nullptr, s);
+                else
+                    launch_ego_predict(ctx, B, S.x0, A.di_ai, G->n_steps, nullptr, s);
                 hipLaunchKernelGGL(group_pre_tick_kernel, dim3(B), dim3(64), 0, s, Q, GP, X);
             } else {
                 hipLaunchKernelGGL(loop_pre_tick_kernel, dim3(B), dim3(64), 0, s, Q, X);
@@ -3172,6 +3186,33 @@ extern "C" int jsim_loop_predict_egos(jsim_ctx *ctx, int32_t B, const double *x0
     if (!x0 || !di_ai) return fail(ctx, -22, "jsim_loop_predict_egos: null device pointer");
     if (int rc = ensure_ego_pred(ctx, B, n_steps)) return rc;
     launch_ego_predict(ctx, B, x0, di_ai, n_steps, pred, (hipStream_t)stream);
+    HIP_TRY(ctx, hipGetLastError());
+    return 0;
+}
+
+extern "C" int jsim_loop_set_mate_prediction(jsim_ctx *ctx, int32_t mode)
+{
+    if (!ctx) return fail(nullptr, -22, "jsim_loop_set_mate_prediction: null ctx");
+    if (mode != JSIM_MATE_CONSTANT && mode != JSIM_MATE_PLAN)
+        return fail(ctx, -22, "jsim_loop_set_mate_prediction: mode=%d (JSIM_MATE_CONSTANT %d or JSIM_MATE_PLAN %d)", mode,
+                    JSIM_MATE_CONSTANT, JSIM_MATE_PLAN);
+    ctx->mate_prediction = mode;
+    return 0;
+}
+
+extern "C" int jsim_loop_predict_egos_plan(jsim_ctx *ctx, int32_t B, const double *x0, const double *oa, const double *od,
+                                           const int32_t *status, const double *di_ai, int32_t n_steps, double *pred, void *stream)
+{
+    if (!ctx) return fail(nullptr, -22, "jsim_loop_predict_egos_plan: null ctx");
+    DeviceGuard dev_guard(ctx->device);
+    JSIM_GUARD_OK(ctx);
+    if (!ctx->have_geom) return fail(ctx, -22, "jsim_loop_predict_egos_plan: jsim_loop_set_geometry has not been called");
+    if (B < 0 || n_steps < 1 || n_steps > JSIM_MAX_PRED)
+        return fail(ctx, -22, "jsim_loop_predict_egos_plan: B=%d, n_steps=%d (max %d)", B, n_steps, JSIM_MAX_PRED);
+    if (B == 0) return 0;
+    if (!x0 || !oa || !od || !status || !di_ai) return fail(ctx, -22, "jsim_loop_predict_egos_plan: null device pointer");
+    if (int rc = ensure_ego_pred(ctx, B, n_steps)) return rc;
+    launch_ego_plan_predict(ctx, B, x0, oa, od, status, di_ai, n_steps, pred, (hipStream_t)stream);
     HIP_TRY(ctx, hipGetLastError());
     return 0;
 }

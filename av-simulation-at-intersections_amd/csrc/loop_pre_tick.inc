@@ -479,6 +479,97 @@ __global__ __launch_bounds__(64) void ego_predict_kernel(EgoPredP P)
 }
 #endif
 
+// ---- Egos that share their MPC plans (JSIM_MATE_PLAN, include/jsim_mpc.h, DESIGN.md section 27): ego m is predicted by rolling
+//      the controls its controller holds at the start of the tick -- oa[m][0..T-1], od[m][0..T-1] of its last solve, element 0
+//      the input it applied last tick (every kernel stores them unshifted) -- through the plant's own step (simulation_step).
+//      Input of prediction step i, with j = i + 1:  status[m] == JSIM_OK: (oa[m][j], od[m][j]) while j <= T - 1, then
+//      (0, od[m][T - 1]);  any other status: (0, the delta applied last tick) for every step.
+struct EgoPlanP {
+    int B, n_steps, T;
+    double dt, L, smax, vmax, vmin, cc0, cc1; // wheelbase and clamps: the plant's (PlantP)
+    const double *x0;    // [B][4] (x, y, v, yaw)
+    const double *oa;    // [B][T] accelerations of the last solve (zeros before the first one and after a respawn)
+    const double *od;    // [B][T] steering angles of the last solve
+    const int *status;   // [B] status of the last solve
+    const double *di_ai; // [B][2] (delta, a) applied last tick
+    double *pred;        // [B][n_steps][3] (x, y, yaw); may be NULL
+    double2 *pred_cc;    // [B][n_steps][2] circle centres
+    double4 *pred_bc;    // [B] bounding circles, as ego_predict_kernel
+};
+
+#ifndef JSIM_KERNEL_TU /* (a kernel translation unit of the split build holds the register kernels only) */
+// The running value of s += inc[0], s += inc[1], .. in step order, every lane adding the broadcast of lane i's increment to the
+// same s: lane i is left with s after step i (lanes from n on with s0).  The sums are the serial loop's, add for add.
+__device__ __forceinline__ double plan_running_sum(double s0, double inc, int n, int lane)
+{
+    double s = s0, after = s0;
+    for (int i = 0; i < n; ++i) {
+        s += rdlane(inc, i);
+        after = lane == i ? s : after;
+    }
+    return after;
+}
+
+// Grid B, one wavefront per ego, lane i owns prediction step i (n_steps <= JSIM_MAX_PRED = 64).  What costs -- tan of the
+// clamped steering, sin / cos of every heading, the circle centres -- is evaluated once per step across the lanes; what is
+// serial -- v with its clamps, then yaw, then x and y -- is a loop of fp64 adds on values broadcast with v_readlane.  cos / sin of
+// a heading serve the circle centres of its own sample and the position increment of the next step: the next lane fetches them.
+// All 64 lanes stay active to the end (the DPP reductions read every lane); lanes from n_steps on hold neutral values and
+// store nothing.  No LDS.
+__global__ __launch_bounds__(64) void ego_plan_predict_kernel(EgoPlanP P)
+{
+    const int o = blockIdx.x, lane = threadIdx.x;
+    if (o >= P.B) return;
+    const int n = P.n_steps, T = P.T;
+    const bool mine = lane < n;
+    // the input of step `lane`: every index stays inside the ego's row, for the idle lanes too
+    const int j = lane + 1, jc = j < T ? j : T - 1;
+    const bool ok = P.status[o] == JSIM_OK;
+    const double a_plan = P.oa[(size_t)o * T + jc], d_plan = P.od[(size_t)o * T + jc];
+    const double ai = (ok && j < T) ? a_plan : 0.0;
+    const double di = ok ? d_plan : P.di_ai[2 * o];
+    double dc = (P.smax < di) ? P.smax : di;
+    dc = (-P.smax > dc) ? -P.smax : dc;
+    const double tn = tan(dc);
+    const double x0 = P.x0[4 * o], y0 = P.x0[4 * o + 1], v0 = P.x0[4 * o + 2], th0 = P.x0[4 * o + 3];
+    const double c0 = cos(th0), s0 = sin(th0);
+    // v: lane i keeps the speed BEFORE step i, which both the position and the heading increment of the step use
+    double vb = v0;
+    {
+        const double adt = ai * P.dt;
+        double v = v0;
+        for (int i = 0; i < n; ++i) {
+            vb = lane == i ? v : vb;
+            v += rdlane(adt, i);
+            v = (P.vmax < v) ? P.vmax : v;
+            v = (P.vmin > v) ? P.vmin : v;
+        }
+    }
+    // yaw after the lane's step; its cos / sin, and the previous heading's from the lane below (lane 0: the start heading's)
+    const double yaw = plan_running_sum(th0, (vb / P.L) * tn * P.dt, n, lane);
+    const double c = cos(yaw), s = sin(yaw);
+    double cp = __shfl_up(c, 1), sp = __shfl_up(s, 1);
+    if (lane == 0) { cp = c0; sp = s0; }
+    const double x = plan_running_sum(x0, vb * cp * P.dt, n, lane);
+    const double y = plan_running_sum(y0, vb * sp * P.dt, n, lane);
+    const double2 q0 = double2{c * P.cc0 - s * 0.0 + x, s * P.cc0 + c * 0.0 + y};
+    const double2 q1 = double2{c * P.cc1 - s * 0.0 + x, s * P.cc1 + c * 0.0 + y};
+    if (mine) {
+        const size_t k = (size_t)o * n + lane;
+        if (P.pred) { P.pred[3 * k] = x; P.pred[3 * k + 1] = y; P.pred[3 * k + 2] = yaw; }
+        P.pred_cc[2 * k] = q0;
+        P.pred_cc[2 * k + 1] = q1;
+    }
+    // the circle around all circle centres, as ego_predict_kernel (min / max do not depend on the order)
+    const double bx0 = wmin_dpp(mine ? fmin(q0.x, q1.x) : INFINITY), bx1 = wmax_dpp(mine ? fmax(q0.x, q1.x) : -INFINITY);
+    const double by0 = wmin_dpp(mine ? fmin(q0.y, q1.y) : INFINITY), by1 = wmax_dpp(mine ? fmax(q0.y, q1.y) : -INFINITY);
+    const double mx = 0.5 * (bx0 + bx1), my = 0.5 * (by0 + by1);
+    const double dx0 = q0.x - mx, dy0 = q0.y - my, dx1 = q1.x - mx, dy1 = q1.y - my;
+    const double r = wmax_dpp(mine ? fmax(sqrt(dx0 * dx0 + dy0 * dy0), sqrt(dx1 * dx1 + dy1 * dy1)) : 0.0);
+    if (lane == 0) P.pred_bc[o] = double4{mx, my, r * (1.0 + 1e-9) + 1e-9, 0.0};
+}
+#endif
+
 struct GroupP {
     const int *group_of;     // [B] group of each ego
     const int *group_off;    // [n_groups + 1]

@@ -454,8 +454,10 @@ class Recorder:
         were), idx (the progress index after the tick's update), cut (what the loop wrote to path_len, under mode="speed_cutoff" to
         the speed cut-off), hit (bool), first (the hit's index on the remaining path, -1: none), col_xy [n][B][2] (NaN: none); and
         carry [B][3] as the next tick would meet it.  history.cutoff_episodes splits the result into episodes.
-        ValueError: a recorder of a ClosedLoop (it has no glue), a superseded recorder (the context's tables are no longer its
-        loop's), a bad chunk_ticks or carry."""
+        ValueError: a recorder of a ClosedLoop (it has no glue), a recording of an InteractingLoop with mate_prediction="plan" (the
+        replay predicts the group mates from their recorded steering, and the plans the live loop predicted them from -- every
+        ego's oa, od of the tick -- are not recorded), a superseded recorder (the context's tables are no longer its loop's), a bad
+        chunk_ticks or carry."""
         out = self._host(self._cutoffs_device(chunk_ticks, carry), history.EVALUATORS["cutoffs"].keys() + ("carry",))
         out["hit"] = out["hit"] != 0
         return out
@@ -468,6 +470,9 @@ class Recorder:
         B, dev = eng.B, eng.device
         if self.glue is None:
             raise ValueError("this recorder's loop has no glue (ClosedLoop): there is no cut-off to evaluate")
+        if self.glue.get("mate_prediction", "constant") != "constant":
+            raise ValueError("this recording is of an InteractingLoop with mate_prediction='plan': the replay predicts the group "
+                             "mates from their recorded steering, and the plans they were predicted from are not recorded")
         if self.superseded:
             raise ValueError("a later loop on this engine replaced this recorder: the context's tables are no longer its loop's")
         c = int(chunk_ticks)

@@ -244,6 +244,30 @@ int jsim_loop_run_interacting(jsim_ctx *ctx, int32_t B, int32_t n_ticks, double 
                               int32_t margin, int32_t n_obs, double *obs_state, const double *obs_param, double *obs_get,
                               int32_t n_steps, int32_t speed_cutoff, void *stream);
 
+/* ---- Interacting egos that share their MPC plans (intent sharing).  How jsim_loop_run_interacting
+ * predicts an ego for its group mates is context state: JSIM_MATE_CONSTANT (the default: jsim_loop_predict_egos' rule) or
+ * JSIM_MATE_PLAN, THE RULE: ego m at the start of a tick has the state x0[m] = (x, y, v, yaw), the controls of its last solve
+ * oa[m][0..T-1], od[m][0..T-1] as the engine holds them (element 0 is the input applied last tick; zeros before the first solve
+ * and after a respawn), that solve's status[m], and the steering applied last tick di_ai[m][0].  The input of prediction step
+ * i = 0 .. n_steps - 1 is, with j = i + 1,
+ *     status[m] == JSIM_OK:  (a, delta) = (oa[m][j], od[m][j]) while j <= T - 1, then (0, od[m][T - 1]) -- the plan's last
+ *                            steering held at constant speed; a plan longer than n_steps is not read to its end;
+ *     any other status:      (0, di_ai[m][0]) for every step.
+ *   Each step is the plant's (Simulation.step, main/lib/simulation.py:35-47, with the wheelbase and the clamps
+ *   jsim_loop_advance uses): delta clamped to +-MAX_STEER; x += v cos(yaw) dt, y += v sin(yaw) dt; yaw += (v / L) tan(delta) dt
+ *   with the speed from BEFORE the update; v += a dt, clamped to [MIN_SPEED, MAX_SPEED].  Sample i is the pose after step i (the
+ *   first lies one dt ahead); circle centres and the bounding circle are made from the samples as jsim_loop_predict_egos makes them.
+ * jsim_loop_set_mate_prediction: the mode jsim_loop_run_interacting uses from now on (nothing else reads it).  Any other value:
+ *   -22, the mode stays as it was.
+ * jsim_loop_predict_egos_plan: the counterpart of jsim_loop_predict_egos under THE RULE, T the context's.  x0 [B][4], oa and od
+ *   [B][T], status [B], di_ai [B][2] (DEVICE); pred [B][n_steps][3] = (x, y, yaw) or NULL.  Same checks: geometry set, B >= 0,
+ *   1 <= n_steps <= 64, no null pointer. */
+#define JSIM_MATE_CONSTANT 0
+#define JSIM_MATE_PLAN 1
+int jsim_loop_set_mate_prediction(jsim_ctx *ctx, int32_t mode);
+int jsim_loop_predict_egos_plan(jsim_ctx *ctx, int32_t B, const double *x0, const double *oa, const double *od,
+                                const int32_t *status, const double *di_ai, int32_t n_steps, double *pred, void *stream);
+
 /* ---- Traffic sets: each ego of a batch meets its own scripted vehicles (the reference's studies vary offsets, speeds, turning
  * and kind of the traffic: main/scenarios/mpc_intersection.py, mpc_intersection_new_ref.py, mpc_roundabout.py).
  * jsim_loop_set_traffic: set_of [B] (HOST) gives each ego its set, obs_off [n_sets + 1] (HOST) the sets' vehicles in the
