@@ -41,7 +41,7 @@ EXPORTS = (
     "jsim_comm_unique_id", "jsim_comm_init", "jsim_mpc_gather", "jsim_comm_destroy", "jsim_plan_routes",
     "jsim_plan_routes_weighted", "jsim_score_trajectories", "jsim_loop_eval_reasons", "jsim_loop_eval_conflicts",
     "jsim_loop_eval_static", "jsim_loop_summarise_episodes", "jsim_loop_eval_cutoffs", "jsim_loop_fork_state", "jsim_loop_obstacles_at",
-    "jsim_loop_eval_gaps", "jsim_loop_eval_tracking", "jsim_loop_eval_headway",
+    "jsim_loop_eval_gaps", "jsim_loop_eval_tracking", "jsim_loop_eval_headway", "jsim_loop_score_predictions",
 )
 
 _lib = None
@@ -187,6 +187,9 @@ def load() -> C.CDLL:
     lib.jsim_loop_eval_cutoffs.restype = C.c_int
     #                                     ctx B    ticks rec flags n_obs obs_rec x_first x_spawn window margin n_steps speed interacting chunk first carry outs      stream
     lib.jsim_loop_eval_cutoffs.argtypes = [vp, i32, i32, vp, vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp] + [vp] * 6 + [vp]
+    lib.jsim_loop_score_predictions.restype = C.c_int
+    #                                          ctx B    ticks rec flags n_obs obs_rec x_first x_spawn egos n_steps tol pt_i pt_d step_sum step_cnt err stream
+    lib.jsim_loop_score_predictions.argtypes = [vp, i32, i32, vp, vp, i32, vp, vp, vp, i32, i32, dbl] + [vp] * 5 + [vp]
     lib.jsim_loop_fork_state.restype = C.c_int
     #                                   ctx B    ticks rec flags x_first x_spawn n_rows ego at x0  k0  stream
     lib.jsim_loop_fork_state.argtypes = [vp, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp]

@@ -3368,6 +3368,40 @@ extern "C" int jsim_loop_eval_cutoffs(jsim_ctx *ctx, int32_t B, int32_t n_ticks,
     return 0;
 }
 
+#include "predictions.inc"
+
+// Every recorded prediction against what the vehicle then did: DEVICE pointers throughout, the recorder's
+// buffers as they are; one launch on `stream`, one wavefront per row (the recorded vehicles, then, with egos = 1, the egos).
+extern "C" int jsim_loop_score_predictions(jsim_ctx *ctx, int32_t B, int32_t n_ticks, const double *rec, const int32_t *flags, int32_t n_obs,
+                                           const double *obs_rec, const double *x_first, const double *x_spawn, int32_t egos,
+                                           int32_t n_steps, double tol, int32_t *pt_i, double *pt_d, double *step_sum, int32_t *step_cnt,
+                                           double *err, void *stream)
+{
+    const char *const F = "jsim_loop_score_predictions";
+    if (B < 0 || n_ticks < 0 || n_obs < 0) return fail(ctx, -22, "%s: B=%d n_ticks=%d n_obs=%d", F, B, n_ticks, n_obs);
+    if (n_steps < 1 || n_steps > JSIM_MAX_PRED) return fail(ctx, -22, "%s: n_steps=%d outside [1, %d]", F, n_steps, JSIM_MAX_PRED);
+    if (egos != 0 && egos != 1) return fail(ctx, -22, "%s: egos=%d (0 or 1)", F, egos);
+    if (!(tol >= 0.0) || !std::isfinite(tol)) return fail(ctx, -22, "%s: tol %g is not finite and >= 0", F, tol);
+    if (!obs_rec && n_obs > 0) return fail(ctx, -22, "%s: null obs_rec with n_obs=%d", F, n_obs);
+    const void *const ptrs[] = {rec, flags, x_first, x_spawn, pt_i, pt_d, step_sum, step_cnt};
+    const char *const names[] = {"rec", "flags", "x_first", "x_spawn", "pt_i", "pt_d", "step_sum", "step_cnt"};
+    for (int i = 0; i < 8; ++i)
+        if (!ptrs[i]) return fail(ctx, -22, "%s: null pointer %s", F, names[i]);
+    if (!ctx) return fail(nullptr, -22, "%s: null ctx", F);
+    if (ctx->n_sets > 0)
+        if (int rc = check_traffic(ctx, F, B, n_obs)) return rc;
+    if (int rc = check_shapes(ctx, F, n_obs)) return rc;
+    const long long V = (long long)n_obs + (egos ? B : 0);
+    if (V == 0 || n_ticks == 0) return 0;
+    if (V > 0x7fffffffll) return fail(ctx, -22, "%s: %lld rows", F, V);
+    DeviceGuard dev_guard(ctx->device);
+    JSIM_GUARD_OK(ctx);
+    const PredScoreP P = {recorder_buf(B, n_ticks, rec, flags, x_first, x_spawn), n_obs, egos, n_steps, ctx->cfg.dt,
+                          ctx->have_ogeom ? ctx->oL : ctx->cfg.L, ctx->cfg.L, tol, obs_rec, n_obs > 0 ? shapes_p(ctx) : nullptr,
+                          pt_i, pt_d, step_sum, step_cnt, err};
+    return launch_per_ego(ctx, prediction_score_kernel, (int)V, stream, P);
+}
+
 #include "fork.inc"
 
 // The start of a loop forked off a recorded run: row r's ego state at the start of tick at[r] of ego ego[r]

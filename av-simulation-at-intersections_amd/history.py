@@ -8,7 +8,8 @@ conflict_episodes for the clearance and first contact of every episode (section 
 collision cut-off of every tick (section 21); fork_rows, join and reasons_carry_at are the host side of a fork (section 22);
 gap_episodes for the time gap between an ego and each vehicle (section 23); path_table and tracking_episodes for the projection of
 every recorded pose onto a path (section 24); headway_episodes for the space headway, time headway and time to collision between
-an ego and the vehicles on its path (section 25)."""
+an ego and the vehicles on its path (section 25); prediction_curve and prediction_places for the error of every recorded prediction
+against what the vehicle then did (section 28)."""
 from __future__ import annotations
 
 from typing import List, NamedTuple, Optional
@@ -64,6 +65,30 @@ EVALUATORS = {
     "cutoffs": Evaluator("jsim_loop_eval_cutoffs", (("status", _I, ()), ("idx", _I, ()), ("cut", _I, ()), ("hit", _I, ()),
                                                     ("first", _I, ()), ("col_xy", _F, (2,)))),
 }
+
+
+class RowOutputs(NamedTuple):
+    """The outputs of an entry point whose rows are not the egos: (key, numpy dtype, leading axes, trailing shape) each, in the order
+    of the declaration in include/jsim_mpc.h.  Leading "tick": [n][V]..., "row": [V]...; a trailing "n_steps" is the call's n_steps;
+    `optional`: the keys the call takes as NULL."""
+    entry: str
+    outputs: tuple
+    optional: tuple = ()
+
+    def keys(self, skip=()):
+        return tuple(k for k, _, _, _ in self.outputs if k not in skip)
+
+
+# the columns of Recorder.predictions' pt_i and pt_d, in the order of the JSIM_PS_* enumerators of include/jsim_mpc.h
+PS_INT = ("n", "hold", "max_at")
+PS_DOUBLE = ("ade", "fde", "max", "lon", "lat", "yaw")
+MAX_PRED = 64          # JSIM_MAX_PRED: the longest prediction
+# jsim_loop_score_predictions' outputs (DESIGN.md section 28): rows are the recorded vehicles and then the egos, [n][V], so they stand
+# beside EVALUATORS, not in it
+PREDICTION_OUTPUTS = RowOutputs("jsim_loop_score_predictions",
+                                (("pt_i", _I, "tick", (len(PS_INT),)), ("pt_d", _F, "tick", (len(PS_DOUBLE),)),
+                                 ("step_sum", _F, "row", ("n_steps",)), ("step_cnt", _I, "row", ("n_steps",)),
+                                 ("err", _F, "tick", ("n_steps",))), optional=("err",))
 
 
 class History:
@@ -447,6 +472,47 @@ def reasons_carry_at(result: dict, ego, at, ends=None) -> np.ndarray:
             out[r] = np.asarray(result["carry"], dtype=np.float64)[b]
         elif k > 0 and not ends[k - 1, b]:
             out[r] = (timers[k - 1, b, 0], timers[k - 1, b, 1], 1.0 if below[k - 1, b].any() else 0.0)
+    return out
+
+
+def prediction_curve(result: dict, dt: float):
+    """The mean displacement error by look-ahead of a recorder's predictions (Recorder.predictions: `step_sum`, `step_cnt` [V][n_steps]):
+    (t [n_steps], mean [V][n_steps]) with t[j] = (j + 1) * dt, the time sample j lies ahead, and mean[r][j] = step_sum[r][j] /
+    step_cnt[r][j], NaN where no tick of row r scored sample j."""
+    s, c = np.asarray(result["step_sum"], dtype=np.float64), np.asarray(result["step_cnt"])
+    if s.ndim != 2 or s.shape != c.shape:
+        raise ValueError(f"step_sum and step_cnt must be [V][n_steps] alike, got {s.shape} and {c.shape}")
+    t = (np.arange(s.shape[1]) + 1) * float(dt)
+    return t, np.where(c > 0, s / np.where(c > 0, c, 1), np.nan)
+
+
+def prediction_places(result: dict, veh_range, mate_range) -> dict:
+    """The per-tick outputs of a recorder's predictions (Recorder.predictions: the columns PS_INT and PS_DOUBLE [n][V], `n_obs`,
+    `egos`) gathered per ego into the eight places of its list in Recorder.conflicts' order -- its recorded vehicles
+    [veh_range[b][0], veh_range[b][1]), then its group mates [mate_range[b][0], mate_range[b][1]) without itself -- as one array
+    [n][B][8] per column.  A place without a vehicle, a mate when the egos were not scored and a place beyond the eighth are not
+    there: -1 in the integer columns, NaN in the others.  `row` [B][8] is the row each place was taken from (-1: none)."""
+    veh, mate = np.asarray(veh_range), np.asarray(mate_range)
+    n_obs, egos = int(result["n_obs"]), bool(result["egos"])
+    if veh.ndim != 2 or veh.shape[1] != 2 or mate.shape != veh.shape:
+        raise ValueError(f"veh_range and mate_range must be [B][2] alike, got {veh.shape} and {mate.shape}")
+    B = veh.shape[0]
+    V = np.asarray(result[PS_INT[0]]).shape[1]
+    row = np.full((B, MAX_OBS), -1, dtype=np.int64)
+    for b in range(B):
+        rows = list(range(int(veh[b, 0]), int(veh[b, 1])))
+        if egos:
+            rows += [n_obs + m for m in range(int(mate[b, 0]), int(mate[b, 1])) if m != b]
+        rows = rows[:MAX_OBS]
+        if rows and (min(rows) < 0 or max(rows) >= V):
+            raise ValueError(f"ego {b}: a place outside the {V} scored rows")
+        row[b, :len(rows)] = rows
+    there = row >= 0
+    out = {"row": row.astype(np.int32)}
+    for k in PS_INT + PS_DOUBLE:
+        a = np.asarray(result[k])
+        g = a[:, np.where(there, row, 0)] if V else np.zeros((a.shape[0], B, MAX_OBS), dtype=a.dtype)   # [n][B][8]
+        out[k] = np.where(there[None], g, -1 if k in PS_INT else np.nan).astype(a.dtype)
     return out
 
 

@@ -1,6 +1,8 @@
 """The device History recorder of a closed loop and its evaluators: what the loops' kernels wrote per tick (jsim_loop_set_recorder),
 read back as the reference's History objects or evaluated on the device, one launch per question (jsim_loop_eval_*).  Each
-evaluator's per-tick outputs are stated once, in history.EVALUATORS: the Recorder allocates, passes and reads back from that table."""
+evaluator's per-tick outputs are stated once, in history.EVALUATORS: the Recorder allocates, passes and reads back from that table.
+The predictions' scores (jsim_loop_score_predictions), whose rows are the recorded vehicles and then the egos, stand beside it in
+history.PREDICTION_OUTPUTS."""
 from __future__ import annotations
 
 import ctypes as C
@@ -499,6 +501,79 @@ class Recorder:
                    x_first, x_spawn, g["frame_window"], g["margin"], g["n_steps"], int(g["mode"] == "speed_cutoff"),
                    int(g["interacting"]), c, k0, _ptr(d_car), *map(_ptr, out.values()))
         return {**self._rows(out, n, k0), "carry": d_car}
+
+    def predictions(self, n_steps=None, tol=None, egos=None, steps: bool = False) -> dict:
+        """Every recorded prediction against what the vehicle then did (jsim_loop_score_predictions): the loops
+        predict every vehicle with MovingObstaclesPrediction(x, y, v, yaw, a, steer) (main/lib/moving_obstacles_prediction.py:21-47) --
+        a constant arc for n_steps * dt seconds -- and every cut-off rests on it.  The recorded get() tuples are the exact inputs of
+        those predictions, the next ticks' tuples and the egos' records what then happened: one launch makes each prediction again in
+        registers and measures its displacement error.
+
+        n_steps: samples per prediction, 1..64 (default: the glue's, else 35).  tol: the displacement a prediction may be off while it
+        still `holds` (default: the ego radius).  egos: None scores the egos iff the loop is an InteractingLoop under
+        mate_prediction="constant" (what its mates predicted of it); True asks for it (ValueError on a plan-mode recording: the
+        plans are not recorded); "constant" scores the constant rule on any recording -- the baseline the plan rule is meant to
+        beat; False leaves the egos out (1 / 0 and numpy's booleans stand for True / False; anything else raises).  steps=True also returns every sample's error.
+        Rows: V = n_obs + (B with the egos): the recorded vehicles in the recorder's order, then the egos.  Returns numpy arrays
+        [n][V]: n (the scored samples: those whose truth is recorded, for an ego within its episode), hold (the leading samples
+        within tol), max_at (the first sample of the largest error, -1: none), ade, fde, max, lon, lat (the last scored sample's
+        error along and across the true heading; lon > 0: predicted farther ahead than the vehicle got), yaw (its heading error,
+        wrapped to [-pi, pi)); NaN where n = 0; step_sum, step_cnt [V][n_steps] (history.prediction_curve gives the mean error by
+        look-ahead); err [n][V][n_steps] with steps=True (NaN: not scored); and n_steps, tol, egos (bool), n_obs and dt as used.
+        history.prediction_places gathers an ego's eight places.
+        ValueError: an n_steps outside 1..64, a tol that is not finite and >= 0, another egos, egos=True on a plan-mode recording, a
+        superseded recorder (the context's wheelbases are no longer its loop's)."""
+        d = self._predictions_device(n_steps, tol, egos, steps)
+        h = self._host(d, history.PREDICTION_OUTPUTS.keys())
+        pt_i, pt_d = h.pop("pt_i"), h.pop("pt_d")
+        h.update({k: np.ascontiguousarray(pt_i[:, :, j]) for j, k in enumerate(history.PS_INT)})
+        h.update({k: np.ascontiguousarray(pt_d[:, :, j]) for j, k in enumerate(history.PS_DOUBLE)})
+        return h
+
+    def _predictions_device(self, n_steps=None, tol=None, egos=None, steps: bool = False, n=None) -> dict:
+        """predictions() up to the launch: the outputs as device tensors (pt_i [n][V][3], pt_d [n][V][6], step_sum, step_cnt
+        [V][n_steps] and, with steps, err [n][V][n_steps]) and the host arguments used (n_steps, tol, egos, n_obs, dt)."""
+        eng = self.loop.eng
+        B, dev = eng.B, eng.device
+        glue = self.glue or {}
+        S = glue.get("n_steps", 35) if n_steps is None else n_steps
+        if isinstance(S, (bool, np.bool_)) or not (isinstance(S, (int, float, np.integer, np.floating)) and math.isfinite(S) and int(S) == S
+                                                   and 1 <= int(S) <= history.MAX_PRED):
+            raise ValueError(f"n_steps must be an integer in 1..{history.MAX_PRED}, got {n_steps!r}")
+        S = int(S)
+        tol = float(self._ego_shape()[2] if tol is None else tol)
+        if not (math.isfinite(tol) and tol >= 0.0):
+            raise ValueError(f"tol must be finite and >= 0, got {tol!r}")
+        plan = glue.get("mate_prediction", "constant") != "constant"
+        if isinstance(egos, (np.bool_, int, np.integer)) and egos in (0, 1):     # True / False and what the entry point takes for them
+            egos = bool(egos)
+        if egos is None:
+            with_egos = bool(glue.get("interacting")) and not plan
+        elif egos is True:
+            if plan:
+                raise ValueError("this recording is of an InteractingLoop with mate_prediction='plan': its egos were predicted from "
+                                 "their plans, which are not recorded (egos='constant' scores the constant rule instead)")
+            with_egos = True
+        elif egos is False or (isinstance(egos, str) and egos == "constant"):
+            with_egos = egos is not False
+        else:
+            raise ValueError(f"egos must be None, True / False (or 1 / 0) or 'constant', got {egos!r}")
+        if self.superseded:
+            raise ValueError("a later loop on this engine replaced this recorder: the context's tables are no longer its loop's")
+        n = self._n(4) if n is None else n
+        V = self.n_obs + (B if with_egos else 0)
+        shape = {"tick": (max(n, 1), max(V, 1)), "row": (max(V, 1),)}
+        out = {k: None if (k == "err" and not steps) else
+               torch.empty(*shape[lead], *(S if s == "n_steps" else s for s in trail), dtype=_TORCH[dt], device=dev)
+               for k, dt, lead, trail in history.PREDICTION_OUTPUTS.outputs}
+        if n == 0 or V == 0:                  # (the call writes nothing: no tick has scored a sample)
+            out["step_sum"].zero_(); out["step_cnt"].zero_()
+        rec, flags, x_first, x_spawn = self._buffers()
+        self._call("jsim_loop_score_predictions", B, n, rec, flags, self.n_obs, _ptr(self.obs) if self.obs is not None else None,
+                   x_first, x_spawn, int(with_egos), S, tol, *[_ptr(t) if t is not None else None for t in out.values()])
+        cut = {"tick": lambda t: t[:n, :V], "row": lambda t: t[:V]}
+        return {**{k: cut[lead](out[k]) for k, _, lead, _ in history.PREDICTION_OUTPUTS.outputs if out[k] is not None},
+                "n_steps": S, "tol": tol, "egos": with_egos, "n_obs": self.n_obs, "dt": float(eng.dt)}
 
     def fork_state(self, ego, at):
         """Where a loop forked off this recording starts (jsim_loop_fork_state): for every row r the state

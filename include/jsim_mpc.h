@@ -773,6 +773,46 @@ int jsim_loop_fork_state(jsim_ctx *ctx, int32_t B, int32_t n_ticks, const double
 int jsim_loop_obstacles_at(jsim_ctx *ctx, int32_t n_obs, const double *state0, const double *param, const double *wheelbase,
                            const int32_t *ticks, double *state, void *stream);
 
+/* ---- every recorded prediction against what the vehicle then did ----
+ * Every cut-off of the loops rests on MovingObstaclesPrediction(x, y, v, yaw, a, steer) of main/lib/moving_obstacles_prediction.py:
+ * the vehicle held on a constant arc for n_steps * dt seconds.  After a run the recorder holds the exact input of every such
+ * prediction and what the vehicle did next; this call gives the displacement error of each, in one launch, one wavefront per row,
+ * without writing a prediction to memory.
+ *   Rows: V = n_obs + (egos ? B : 0).  Row r < n_obs is recorded vehicle r, in the recorder's order (every vehicle of every set under
+ *   a traffic layout); row n_obs + b is ego b under the constant rule (JSIM_MATE_CONSTANT).
+ *   Input of tick k.  Vehicle: obs_rec[k][r] = (x, y, v, yaw, a, steer).  Ego: (x, y, v, yaw) at the start of tick k -- x_first on tick
+ *   0, x_spawn behind a record with JSIM_REC_GOAL / JSIM_REC_AGE, else the record before, as jsim_loop_eval_cutoffs reads it --, a = 0,
+ *   steer = field 4 of record k - 1, or 0 when k = 0 or record k - 1 ended an episode: what jsim_loop_run_interacting hands the
+ *   constant rule and jsim_loop_eval_cutoffs hands it again.
+ *   Prediction: tn = tan(steer); per step  x += v * cos(yaw) * dt;  y += v * sin(yaw) * dt;  v += a * dt;  yaw += (v / L) * tn * dt
+ *   (unfused, in that order; the device function of jsim_loop_predict_obstacles, bit for bit).  dt is the context's; L is the
+ *   vehicle's row of jsim_loop_set_vehicle_shapes, else jsim_loop_set_obstacle_geometry's wheelbase, else the configuration's L; an
+ *   ego's is the configuration's L.  Sample j (from 0) is the pose after step j: (j + 1) * dt ahead.
+ *   Truth of sample j.  Vehicle: fields 0, 1, 3 of obs_rec[k + j + 1][r]; it exists iff k + j + 1 <= n_ticks - 1.  Ego: fields 0, 1, 2 of
+ *   rec[k + j][b] (the pose after that tick's plant step, before any respawn); it exists iff k + j <= ke(k), the first tick >= k whose
+ *   record has JSIM_REC_GOAL | JSIM_REC_AGE, or n_ticks - 1 without one.  m = the scored samples: min(n_steps, n_ticks - 1 - k) for a
+ *   vehicle, min(n_steps, ke - k + 1) for an ego.
+ *   Out, per tick and row, with (dx, dy) = prediction - truth and e_j = sqrt(dx * dx + dy * dy) (unfused):
+ *     pt_i [n_ticks][V][JSIM_PS_NI]: N = m; HOLD = the leading samples with e_j <= tol (m when none exceeds it); MAX_AT = the first j
+ *     of the largest e_j;
+ *     pt_d [n_ticks][V][JSIM_PS_ND]: ADE = (e_0 + e_1 + ... in step order) / m; FDE = e_(m-1); MAX; LON and LAT at sample m - 1 against
+ *     the truth heading psi: LON = dx * cos(psi) + dy * sin(psi) (> 0: predicted farther ahead than the vehicle got), LAT =
+ *     -dx * sin(psi) + dy * cos(psi); YAW = (yaw_pred - psi) wrapped to [-pi, pi) as jsim_loop_eval_tracking wraps e_yaw.
+ *     With m = 0 the row holds 0, 0, -1 and NaN.
+ *   Per row over all ticks: step_sum [V][n_steps] = the sum of e_j over the ticks that score sample j (added in a fixed order: the
+ *   same call gives the same bits), step_cnt [V][n_steps] (int32) = how many do.  err [n_ticks][V][n_steps], which may be NULL: every
+ *   e_j, NaN where a sample is not scored.
+ *   DEVICE pointers throughout, as for jsim_loop_eval_cutoffs; HOST counts, egos (0 / 1) and tol.
+ *   Refused (-22) before any device call and with nothing written: B, n_ticks or n_obs < 0; n_steps outside [1, 64]; egos other than
+ *   0 / 1; a tol that is negative or not finite; obs_rec NULL with n_obs > 0; any other null pointer but err and stream; a null ctx; an
+ *   n_obs that is not the registered traffic total (a B that is not the layout's) or not the shape table's.  V = 0 or n_ticks = 0
+ *   returns 0 and writes nothing. */
+enum { JSIM_PS_N = 0, JSIM_PS_HOLD, JSIM_PS_MAX_AT, JSIM_PS_NI };
+enum { JSIM_PS_ADE = 0, JSIM_PS_FDE, JSIM_PS_MAX, JSIM_PS_LON, JSIM_PS_LAT, JSIM_PS_YAW, JSIM_PS_ND };
+int jsim_loop_score_predictions(jsim_ctx *ctx, int32_t B, int32_t n_ticks, const double *rec, const int32_t *flags, int32_t n_obs,
+                                const double *obs_rec, const double *x_first, const double *x_spawn, int32_t egos, int32_t n_steps,
+                                double tol, int32_t *pt_i, double *pt_d, double *step_sum, int32_t *step_cnt, double *err, void *stream);
+
 /* ---- the job's one exchange: the final trajectory gather over RCCL / xGMI ----
  * The reference has no multi-process code at all (its only multi-ego code is the serial Python loop of
  * main/scenarios/interactive_mpc.py:119-172); egos are independent (main/lib/mpc.py:141-211), so ranks own contiguous shards
