@@ -42,6 +42,7 @@ EXPORTS = (
     "jsim_plan_routes_weighted", "jsim_score_trajectories", "jsim_loop_eval_reasons", "jsim_loop_eval_conflicts",
     "jsim_loop_eval_static", "jsim_loop_summarise_episodes", "jsim_loop_eval_cutoffs", "jsim_loop_fork_state", "jsim_loop_obstacles_at",
     "jsim_loop_eval_gaps", "jsim_loop_eval_tracking", "jsim_loop_eval_headway", "jsim_loop_score_predictions",
+    "jsim_loop_set_plan_recorder", "jsim_loop_score_plan_predictions", "jsim_loop_eval_cutoffs_plan",
 )
 
 _lib = None
@@ -190,6 +191,14 @@ def load() -> C.CDLL:
     lib.jsim_loop_score_predictions.restype = C.c_int
     #                                          ctx B    ticks rec flags n_obs obs_rec x_first x_spawn egos n_steps tol pt_i pt_d step_sum step_cnt err stream
     lib.jsim_loop_score_predictions.argtypes = [vp, i32, i32, vp, vp, i32, vp, vp, vp, i32, i32, dbl] + [vp] * 5 + [vp]
+    lib.jsim_loop_set_plan_recorder.restype = C.c_int
+    #                                          ctx B    cap  plan_oa plan_od plan_status
+    lib.jsim_loop_set_plan_recorder.argtypes = [vp, i32, i32, vp, vp, vp]
+    lib.jsim_loop_score_plan_predictions.restype = C.c_int
+    #                                               ctx B    ticks rec flags x_first x_spawn plan_oa plan_od plan_status n_steps tol outs     stream
+    lib.jsim_loop_score_plan_predictions.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, i32, dbl] + [vp] * 5 + [vp]
+    lib.jsim_loop_eval_cutoffs_plan.restype = C.c_int                    # jsim_loop_eval_cutoffs', the three plan pointers ahead of stream
+    lib.jsim_loop_eval_cutoffs_plan.argtypes = lib.jsim_loop_eval_cutoffs.argtypes[:-1] + [vp] * 3 + [vp]
     lib.jsim_loop_fork_state.restype = C.c_int
     #                                   ctx B    ticks rec flags x_first x_spawn n_rows ego at x0  k0  stream
     lib.jsim_loop_fork_state.argtypes = [vp, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp]

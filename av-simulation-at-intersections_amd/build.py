@@ -1,5 +1,6 @@
-"""Build libjsim_mpc.so (HIP, gfx950) in-tree with hipcc.  hipcc cross-compiles without a GPU.  Nine translation units in parallel
-(one per horizon with a register kernel + the rest of the library): a minute instead of three on eight cores."""
+"""Build libjsim_mpc.so (HIP, gfx950) in-tree with hipcc.  hipcc cross-compiles without a GPU.  Ten translation units in parallel
+(one per horizon with a register kernel + the rest of the library + the plan record's kernels, csrc/jsim_plan.hip): a minute
+instead of three on eight cores."""
 from __future__ import annotations
 
 import os
@@ -14,6 +15,7 @@ else:                                      # run as a script: python av-simulati
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(_HERE, "csrc", "jsim_mpc.hip")
+PLAN_SRC = os.path.join(_HERE, "csrc", "jsim_plan.hip")   # the plan record's kernels: a code object of their own
 INC = os.path.join(os.path.dirname(_HERE), "include")
 LIB = os.path.join(_HERE, "libjsim_mpc.so")
 
@@ -63,20 +65,21 @@ def check_isa(asm_path: str) -> None:
 
 KERNEL_TUS = tuple(sorted({row[1] for row in config.REG_VARIANTS}))   # one translation unit per horizon with a register kernel (JSIM_KERNEL_TU)
 ASM_NAME = "jsim_mpc-hip-amdgcn-amd-amdhsa-gfx950.s"
+PLAN_ASM_NAME = "jsim_plan-hip-amdgcn-amd-amdhsa-gfx950.s"
 
 
 def _build_split(hipcc: str, extra, obj_dir: str, tmp_lib: str, verbose: bool) -> None:
-    """The library from nine translation units compiled in parallel: csrc/jsim_mpc.hip once per horizon (-DJSIM_KERNEL_TU=T: that
+    """The library from ten translation units compiled in parallel: csrc/jsim_mpc.hip once per horizon (-DJSIM_KERNEL_TU=T: that
     horizon's rows of csrc/reg_variants.h, explicitly instantiated) and once for everything else (-DJSIM_SPLIT_BUILD: the same
-    kernels declared `extern template`), then one link.  Every unit's device listing goes through the ISA guard; the listings are concatenated into
+    kernels declared `extern template`), csrc/jsim_plan.hip last, then one link.  Every unit's device listing goes through the ISA guard; the listings are concatenated into
     the path the one-unit build leaves its listing at (tests and tools read that file)."""
     flags = [f for f in HIPCC_FLAGS if f != "-shared"]
-    units = [("main", ["-DJSIM_SPLIT_BUILD"])] + [(f"T{t}", [f"-DJSIM_KERNEL_TU={t}"]) for t in KERNEL_TUS]
+    units = [("main", ["-DJSIM_SPLIT_BUILD"], SRC)] + [(f"T{t}", [f"-DJSIM_KERNEL_TU={t}"], SRC) for t in KERNEL_TUS] + [("plan", [], PLAN_SRC)]
     procs = []
-    for name, defs in units:
+    for name, defs, src in units:
         d = os.path.join(obj_dir, "tu_" + name)
         os.makedirs(d, exist_ok=True)
-        cmd = [hipcc] + flags + extra + defs + ["-save-temps=obj", "-I", INC, "-c", SRC, "-o", os.path.join(d, name + ".o")]
+        cmd = [hipcc] + flags + extra + defs + ["-save-temps=obj", "-I", INC, "-c", src, "-o", os.path.join(d, name + ".o")]
         if verbose:
             print(" ".join(cmd))
         procs.append((name, d, cmd, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)))
@@ -87,11 +90,12 @@ def _build_split(hipcc: str, extra, obj_dir: str, tmp_lib: str, verbose: bool) -
             failed.append(f"--- {name}: {' '.join(cmd)}\n{out[-4000:]}")
     if failed:
         raise RuntimeError("libjsim_mpc.so: compilation failed\n" + "\n".join(failed))
+    asm = lambda name, d: os.path.join(d, PLAN_ASM_NAME if name == "plan" else ASM_NAME)
     for name, d, _, _ in procs:
-        check_isa(os.path.join(d, ASM_NAME))
+        check_isa(asm(name, d))
     with open(os.path.join(obj_dir, ASM_NAME), "w") as cat:
         for name, d, _, _ in procs:
-            cat.write(open(os.path.join(d, ASM_NAME)).read())
+            cat.write(open(asm(name, d)).read())
     link = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC"] + [os.path.join(d, name + ".o") for name, d, _, _ in procs] + ["-o", tmp_lib]
     if verbose:
         print(" ".join(link))
@@ -101,7 +105,7 @@ def _build_split(hipcc: str, extra, obj_dir: str, tmp_lib: str, verbose: bool) -
     for name, d, _, _ in procs:
         shutil.rmtree(d, ignore_errors=True)
     for f in os.listdir(obj_dir):
-        if f.startswith("jsim_mpc") and f != ASM_NAME:
+        if f.startswith(("jsim_mpc", "jsim_plan")) and f != ASM_NAME:
             os.remove(os.path.join(obj_dir, f))
 
 
@@ -115,11 +119,15 @@ def build(force: bool = False, verbose: bool = False) -> str:
         # one unit: the development builds that instantiate a subset (-DJSIM_DEV_*), or on request (JSIM_MONO_BUILD=1)
         mono = os.environ.get("JSIM_MONO_BUILD") == "1" or any(f.startswith("-DJSIM_DEV_") for f in extra)
         if mono:
-            cmd = [_hipcc()] + HIPCC_FLAGS + extra + ["-save-temps=obj", "-I", INC, SRC, "-o", tmp_lib]
+            cmd = [_hipcc()] + HIPCC_FLAGS + extra + ["-save-temps=obj", "-I", INC, SRC, PLAN_SRC, "-o", tmp_lib]
             if verbose:
                 print(" ".join(cmd))
             subprocess.check_call(cmd)
             check_isa(os.path.join(obj_dir, ASM_NAME))
+            check_isa(os.path.join(obj_dir, PLAN_ASM_NAME))
+            with open(os.path.join(obj_dir, ASM_NAME), "a") as cat:       # one listing, as the split build leaves it
+                cat.write(open(os.path.join(obj_dir, PLAN_ASM_NAME)).read())
+            os.remove(os.path.join(obj_dir, PLAN_ASM_NAME))
         else:
             _build_split(_hipcc(), extra, obj_dir, tmp_lib, verbose)
         shutil.copyfile(tmp_lib, out)

@@ -312,7 +312,7 @@ class _GlueLoop:
     owns its context's tables: ClosedLoop and PreTick clear an earlier recorder and shape table, the rest is registered here."""
 
     def __init__(self, engine: BatchedMPC, x0: torch.Tensor, obstacle_specs, hist_cap, max_age, frame_window, mode, traffic_of,
-                 chunk_ticks, record, group_off=None):
+                 chunk_ticks, record, group_off=None, record_plans=False):
         layout = None
         if traffic_of is not None:
             layout = traffic_layout(engine.B, obstacle_specs, traffic_of, group_off=group_off)   # before any device work
@@ -333,7 +333,10 @@ class _GlueLoop:
             self.loop.recorder = Recorder(self.loop, record, n_obs=self.obst.n, groups=group_off)   # last: it records obst.n vehicles
             self.loop.recorder.glue = {"frame_window": self.pre.frame_window, "margin": self.pre.margin, "n_steps": self.pre.n_steps,
                                        "mode": self.pre.mode, "interacting": group_off is not None,
-                                       "mate_prediction": getattr(self, "mate_prediction", "constant")}
+                                       "mate_prediction": getattr(self, "mate_prediction", "constant"),
+                                       "record_plans": bool(record_plans)}
+            if record_plans:
+                self.loop.recorder._record_plans()
 
     def _register_groups(self):
         """Only InteractingLoop has groups."""
@@ -519,23 +522,28 @@ class InteractingLoop(_GlueLoop):
     by rolling the controls its controller holds at the start of the tick (eng.oa, eng.od of its last solve, from element 1 on,
     then the last steering held at constant speed; after a failed solve the steering applied last tick at constant speed) through
     the plant's own step, so an ego that has planned to stop in front of a conflict is predicted to stop there.  The loop
-    constructed last on an engine sets the engine's mode.  A plan-mode recording has no Recorder.cutoffs(): the plans are not
-    recorded."""
+    constructed last on an engine sets the engine's mode.
+    record_plans (with record, under either mate_prediction): every tick's plans -- eng.oa, eng.od, eng.status as they stand at the
+    start of the tick -- are kept on the device beside the History (`recorder.plans`); the run itself is the
+    same bit for bit.  With them Recorder.cutoffs() replays a plan-mode recording and Recorder.predictions(egos="plan") scores the
+    plan rule against what each ego then did; a plan-mode recording without them has neither."""
 
     _ENTRY = "jsim_loop_run_interacting"
 
     def __init__(self, engine: BatchedMPC, x0: torch.Tensor, group_off=None, obstacle_specs=(), hist_cap: int = 0,
                  max_age: int = 0, frame_window: int = 20, group_sizes=None, traffic_of=None, record: int = 0,
-                 mate_prediction: str = "constant"):
+                 mate_prediction: str = "constant", record_plans: bool = False):
         if mate_prediction not in _cabi.MATE_PREDICTION:                              # before any device work
             raise ValueError(f"mate_prediction must be one of {sorted(_cabi.MATE_PREDICTION)}, got {mate_prediction!r}")
+        if record_plans and not record:
+            raise ValueError("record_plans needs a recorder: record must be a positive number of ticks")
         self.mate_prediction = mate_prediction
         off = self.group_off = group_offsets(engine.B, group_off, group_sizes)
         n_obs, big = len(obstacle_specs), int(np.diff(off).max())
         if traffic_of is None and n_obs + big - 1 > MAX_GROUP:
             raise ValueError(f"{n_obs} scripted obstacles + the largest group ({big}) - 1 > {MAX_GROUP}")
         super().__init__(engine, x0, obstacle_specs, hist_cap, max_age, frame_window, "truncate", traffic_of, 0, record,
-                         group_off=off)
+                         group_off=off, record_plans=record_plans)
 
     def _register_groups(self):
         """The groups and, every time, how their egos predict each other: a later loop on the same engine has its own mode."""

@@ -23,17 +23,7 @@ struct CutoffP {
     double *col_xy;           // [n][B][2]
 };
 
-// An ego's state (x, y, v, yaw) at the start of tick k: jrw_pose_at's rule with the speed
-__device__ __forceinline__ void jct_state_at(const RecorderBuf &R, int e, int k, double &x, double &y, double &v, double &yaw)
-{
-    // one pointer and one order of loads, then a choice between values: the two layouts ((x, y, v, yaw) of a state, (x, y, yaw, v) of
-    // a record) as two branches were merged by the compiler into stores to scratch at a computed place
-    const bool state = k == 0 || jrw_is_end(R.flags[(size_t)(k - 1) * R.B + e]);
-    const double *const first = R.x_first, *const spawn = R.x_spawn;
-    const double *p = state ? (k == 0 ? first : spawn) + 4 * (size_t)e : R.rec + JSIM_REC_FIELDS * ((size_t)(k - 1) * R.B + e);
-    const double q2 = p[2], q3 = p[3];
-    x = p[0]; y = p[1]; v = state ? q2 : q3; yaw = state ? q3 : q2;
-}
+// (jct_state_at, an ego's state at the start of tick k, stands in recorder_walk.inc beside jrw_pose_at, whose rule it is)
 
 // A NULL carry of the caller: the loops' own start -- progress index 0, no previous path (PreTick.__init__), the whole path
 __global__ __launch_bounds__(256) void cutoff_carry_init_kernel(int B, const int *path_id, const long long *poff, int *carry)

@@ -1397,7 +1397,10 @@ struct jsim_ctx {
     double *rec = nullptr, *rec_obs = nullptr;
     int32_t *rec_flags = nullptr;
     int rec_B = 0, rec_cap = 0, rec_n_obs = 0;
-    DevArray<double2> d_ego_cc;    // [B][n_steps][2]
+    // the plan recorder (jsim_loop_set_plan_recorder): caller-owned device buffers of the recorder's B and cap, plan_oa = NULL: none
+    double *plan_oa = nullptr, *plan_od = nullptr;
+    int32_t *plan_status = nullptr;
+    DevArray<double2> d_ego_cc;   // [B][n_steps][2]
     DevArray<double4> d_ego_bc;    // [B]
     // jsim_loop_eval_cutoffs: the egos' path ids as the glue last took them (caller-owned device array [B], NULL: no glue call yet),
     // the interacting egos' tick-start states and last steering of a chunk, and the carry of a call without one
@@ -2873,6 +2876,8 @@ static void launch_ego_plan_predict(jsim_ctx *ctx, int B, const double *x0, cons
     hipLaunchKernelGGL(ego_plan_predict_kernel, dim3(B), dim3(64), 0, s, P);
 }
 
+#include "plan_predictions.inc" // the plan recorder's and the plan scorer's parameters; their kernels are jsim_plan.hip's
+
 enum class Glue { none, scripted, interacting };
 
 // n_ticks ticks as separate launches, the calls the tick() methods of closed_loop.py make.  With a glue (G): scripted obstacles
@@ -2918,6 +2923,11 @@ static int run_host_ticks(jsim_ctx *ctx, int B, int n_ticks, const StepBufs &S, 
             ctx->pred_n_obs = traffic ? 0 : G->n_obs; ctx->pred_n_steps = G->n_steps;
             if (G->n_obs > 0) launch_obstacle_predict(ctx, G->n_obs, G->n_steps, G->obs_get, nullptr, pred_cc, pred_bc, 1, s);
             if (kind == Glue::interacting) {
+                if (ctx->plan_oa) {
+                    const PlanRecP PR = {B, ctx->cfg.T, ctx->rec_cap, A.tick, S.oa, S.od, S.status, ctx->plan_oa, ctx->plan_od,
+                                         ctx->plan_status};
+                    hipLaunchKernelGGL(plan_record_kernel, dim3((unsigned)(((size_t)B * ctx->cfg.T + 255) / 256)), dim3(256), 0, s, PR);
+                }
                 if (ctx->mate_prediction == JSIM_MATE_PLAN)
                     launch_ego_plan_predict(ctx, B, S.x0, S.oa, S.od, S.status, A.di_ai, G->n_steps, nullptr, s);
                 else
@@ -3167,9 +3177,26 @@ extern "C" int jsim_loop_set_recorder(jsim_ctx *ctx, int32_t B, int32_t cap, dou
         return fail(ctx, -22, "%s: n_obs=%d, but the traffic sets hold %d vehicles", F, n_obs, ctx->h_obs_off[ctx->n_sets]);
     ctx->rec = nullptr; ctx->rec_flags = nullptr; ctx->rec_obs = nullptr;
     ctx->rec_B = 0; ctx->rec_cap = 0; ctx->rec_n_obs = 0;
+    ctx->plan_oa = nullptr; ctx->plan_od = nullptr; ctx->plan_status = nullptr; // (a plan recorder goes with the recorder it was sized by)
     if (cap == 0) return 0;
     ctx->rec = rec; ctx->rec_flags = flags; ctx->rec_cap = cap; ctx->rec_B = B;
     if (obs_rec) { ctx->rec_obs = obs_rec; ctx->rec_n_obs = n_obs; }
+    return 0;
+}
+
+// ---- The plan recorder: jsim_loop_run_interacting keeps every tick's shared plans beside the History ----
+extern "C" int jsim_loop_set_plan_recorder(jsim_ctx *ctx, int32_t B, int32_t cap, double *plan_oa, double *plan_od, int32_t *plan_status)
+{
+    const char *const F = "jsim_loop_set_plan_recorder";
+    if (B < 0 || cap < 0) return fail(ctx, -22, "%s: B=%d cap=%d", F, B, cap);
+    if (cap > 0 && (!plan_oa || !plan_od || !plan_status)) return fail(ctx, -22, "%s: cap=%d needs the plan_oa, plan_od and plan_status buffers", F, cap);
+    if (!ctx) return fail(nullptr, -22, "%s: null ctx", F);
+    if (cap > 0 && (!ctx->rec || ctx->rec_B != B || ctx->rec_cap != cap))
+        return fail(ctx, -22, "%s: B=%d cap=%d, but the registered recorder (jsim_loop_set_recorder) has B=%d cap=%d", F, B, cap, ctx->rec_B,
+                    ctx->rec_cap);
+    ctx->plan_oa = nullptr; ctx->plan_od = nullptr; ctx->plan_status = nullptr;
+    if (cap == 0) return 0;
+    ctx->plan_oa = plan_oa; ctx->plan_od = plan_od; ctx->plan_status = plan_status;
     return 0;
 }
 
@@ -3284,13 +3311,13 @@ extern "C" int jsim_loop_run_interacting(jsim_ctx *ctx, int32_t B, int32_t n_tic
 // The collision cut-off of every recorded tick: DEVICE pointers, the recorder's buffers as they are; per
 // chunk of ticks the vehicles' predictions, for interacting egos the mates' states and predictions, and one launch of one wavefront
 // per ego that walks the chunk's ticks in order; all on `stream`.
-extern "C" int jsim_loop_eval_cutoffs(jsim_ctx *ctx, int32_t B, int32_t n_ticks, const double *rec, const int32_t *flags, int32_t n_obs,
-                                      const double *obs_rec, const double *x_first, const double *x_spawn, int32_t frame_window,
-                                      int32_t margin, int32_t n_steps, int32_t speed_cutoff, int32_t interacting, int32_t chunk_ticks,
-                                      int32_t first_tick, int32_t *carry, int32_t *status, int32_t *idx, int32_t *cut, int32_t *hit, int32_t *first,
-                                      double *col_xy, void *stream)
+// plan: the group mates are predicted under the plan rule from the recorded plans (jsim_loop_eval_cutoffs_plan), not the constant one
+static int eval_cutoffs(const char *F, bool plan, jsim_ctx *ctx, int32_t B, int32_t n_ticks, const double *rec, const int32_t *flags,
+                        int32_t n_obs, const double *obs_rec, const double *x_first, const double *x_spawn, int32_t frame_window,
+                        int32_t margin, int32_t n_steps, int32_t speed_cutoff, int32_t interacting, int32_t chunk_ticks,
+                        int32_t first_tick, int32_t *carry, int32_t *status, int32_t *idx, int32_t *cut, int32_t *hit, int32_t *first,
+                        double *col_xy, const double *plan_oa, const double *plan_od, const int32_t *plan_status, void *stream)
 {
-    const char *const F = "jsim_loop_eval_cutoffs";
     if (B < 0 || n_ticks < 0 || n_obs < 0) return fail(ctx, -22, "%s: B=%d n_ticks=%d n_obs=%d", F, B, n_ticks, n_obs);
     if (margin < 0 || chunk_ticks < 0) return fail(ctx, -22, "%s: margin=%d chunk_ticks=%d", F, margin, chunk_ticks);
     if (first_tick < 0 || first_tick > n_ticks) return fail(ctx, -22, "%s: first_tick=%d outside [0, n_ticks=%d]", F, first_tick, n_ticks);
@@ -3302,6 +3329,8 @@ extern "C" int jsim_loop_eval_cutoffs(jsim_ctx *ctx, int32_t B, int32_t n_ticks,
     if (speed_cutoff && interacting) return fail(ctx, -22, "%s: interacting egos have the truncate glue only (speed_cutoff=1)", F);
     if (!rec || !flags || !x_first || !x_spawn || !status || !idx || !cut || !hit || !first || !col_xy)
         return fail(ctx, -22, "%s: null device pointer", F);
+    if (plan && (!plan_oa || !plan_od || !plan_status)) return fail(ctx, -22, "%s: null plan_oa / plan_od / plan_status", F);
+    if (plan && !interacting) return fail(ctx, -22, "%s: interacting=0 (only interacting egos share plans)", F);
     if (!ctx) return fail(nullptr, -22, "%s: null ctx", F);
     // the context's tables must be those of the loop that made the recording
     if (!ctx->d_pxy || !ctx->d_pcc || !ctx->have_geom) return fail(ctx, -22, "%s: paths / geometry not set", F);
@@ -3360,12 +3389,41 @@ extern "C" int jsim_loop_eval_cutoffs(jsim_ctx *ctx, int32_t B, int32_t n_ticks,
         if (interacting) {
             hipLaunchKernelGGL(cutoff_mate_state_kernel, dim3((unsigned)(((size_t)nk * B + 255) / 256)), dim3(256), 0, s, P.R, k0, nk,
                                ctx->d_cut_x0.p, ctx->d_cut_di.p);
-            launch_ego_predict(ctx, nk * B, ctx->d_cut_x0, ctx->d_cut_di, n_steps, nullptr, s);
+            if (plan) // the chunk's slab of the plan record is a [nk * B][T] batch, row = tick * B + ego as the states'
+                launch_ego_plan_predict(ctx, nk * B, ctx->d_cut_x0, plan_oa + (size_t)k0 * B * ctx->cfg.T, plan_od + (size_t)k0 * B * ctx->cfg.T,
+                                        plan_status + (size_t)k0 * B, ctx->d_cut_di, n_steps, nullptr, s);
+            else
+                launch_ego_predict(ctx, nk * B, ctx->d_cut_x0, ctx->d_cut_di, n_steps, nullptr, s);
         }
         P.k0 = k0; P.C = nk;
         if (int rc = launch_per_ego(ctx, cutoff_ticks_kernel, B, stream, P)) return rc;
     }
     return 0;
+}
+
+extern "C" int jsim_loop_eval_cutoffs(jsim_ctx *ctx, int32_t B, int32_t n_ticks, const double *rec, const int32_t *flags, int32_t n_obs,
+                                      const double *obs_rec, const double *x_first, const double *x_spawn, int32_t frame_window,
+                                      int32_t margin, int32_t n_steps, int32_t speed_cutoff, int32_t interacting, int32_t chunk_ticks,
+                                      int32_t first_tick, int32_t *carry, int32_t *status, int32_t *idx, int32_t *cut, int32_t *hit, int32_t *first,
+                                      double *col_xy, void *stream)
+{
+    return eval_cutoffs("jsim_loop_eval_cutoffs", false, ctx, B, n_ticks, rec, flags, n_obs, obs_rec, x_first, x_spawn, frame_window, margin,
+                        n_steps, speed_cutoff, interacting, chunk_ticks, first_tick, carry, status, idx, cut, hit, first, col_xy, nullptr,
+                        nullptr, nullptr, stream);
+}
+
+// The same for a recording of JSIM_MATE_PLAN: the mates' predictions are made again from the plan record
+// (jsim_loop_set_plan_recorder's buffers [n_ticks][B][T], [n_ticks][B]) by ego_plan_predict_kernel, the kernel the loop ran.
+extern "C" int jsim_loop_eval_cutoffs_plan(jsim_ctx *ctx, int32_t B, int32_t n_ticks, const double *rec, const int32_t *flags, int32_t n_obs,
+                                           const double *obs_rec, const double *x_first, const double *x_spawn, int32_t frame_window,
+                                           int32_t margin, int32_t n_steps, int32_t speed_cutoff, int32_t interacting, int32_t chunk_ticks,
+                                           int32_t first_tick, int32_t *carry, int32_t *status, int32_t *idx, int32_t *cut, int32_t *hit,
+                                           int32_t *first, double *col_xy, const double *plan_oa, const double *plan_od,
+                                           const int32_t *plan_status, void *stream)
+{
+    return eval_cutoffs("jsim_loop_eval_cutoffs_plan", true, ctx, B, n_ticks, rec, flags, n_obs, obs_rec, x_first, x_spawn, frame_window,
+                        margin, n_steps, speed_cutoff, interacting, chunk_ticks, first_tick, carry, status, idx, cut, hit, first, col_xy,
+                        plan_oa, plan_od, plan_status, stream);
 }
 
 #include "predictions.inc"
@@ -3400,6 +3458,33 @@ extern "C" int jsim_loop_score_predictions(jsim_ctx *ctx, int32_t B, int32_t n_t
                           ctx->have_ogeom ? ctx->oL : ctx->cfg.L, ctx->cfg.L, tol, obs_rec, n_obs > 0 ? shapes_p(ctx) : nullptr,
                           pt_i, pt_d, step_sum, step_cnt, err};
     return launch_per_ego(ctx, prediction_score_kernel, (int)V, stream, P);
+}
+
+static_assert(JPP_SLOTS == JPS_SLOTS, "plan_predictions.inc stages prediction_score_kernel's truth slots");
+
+// Every recorded plan-rule prediction against what the ego then did: DEVICE pointers throughout, the
+// recorder's and the plan recorder's buffers as they are; one launch on `stream`, one wavefront per ego.
+extern "C" int jsim_loop_score_plan_predictions(jsim_ctx *ctx, int32_t B, int32_t n_ticks, const double *rec, const int32_t *flags,
+                                                const double *x_first, const double *x_spawn, const double *plan_oa, const double *plan_od,
+                                                const int32_t *plan_status, int32_t n_steps, double tol, int32_t *pt_i, double *pt_d,
+                                                double *step_sum, int32_t *step_cnt, double *err, void *stream)
+{
+    const char *const F = "jsim_loop_score_plan_predictions";
+    if (B < 0 || n_ticks < 0) return fail(ctx, -22, "%s: B=%d n_ticks=%d", F, B, n_ticks);
+    if (n_steps < 1 || n_steps > JSIM_MAX_PRED) return fail(ctx, -22, "%s: n_steps=%d outside [1, %d]", F, n_steps, JSIM_MAX_PRED);
+    if (!(tol >= 0.0) || !std::isfinite(tol)) return fail(ctx, -22, "%s: tol %g is not finite and >= 0", F, tol);
+    const void *const ptrs[] = {rec, flags, x_first, x_spawn, plan_oa, plan_od, plan_status, pt_i, pt_d, step_sum, step_cnt};
+    const char *const names[] = {"rec", "flags", "x_first", "x_spawn", "plan_oa", "plan_od", "plan_status", "pt_i", "pt_d", "step_sum", "step_cnt"};
+    for (int i = 0; i < 11; ++i)
+        if (!ptrs[i]) return fail(ctx, -22, "%s: null pointer %s", F, names[i]);
+    if (!ctx) return fail(nullptr, -22, "%s: null ctx", F);
+    const jsim_cfg &c = ctx->cfg; // (T <= JSIM_MAX_T, the tile's width, since jsim_mpc_create)
+    if (B == 0 || n_ticks == 0) return 0;
+    DeviceGuard dev_guard(ctx->device);
+    JSIM_GUARD_OK(ctx);
+    const PlanScoreP P = {recorder_buf(B, n_ticks, rec, flags, x_first, x_spawn), n_steps, c.T, c.dt, c.L, c.max_steer, c.max_speed,
+                          c.min_speed, tol, plan_oa, plan_od, plan_status, pt_i, pt_d, step_sum, step_cnt, err};
+    return launch_per_ego(ctx, plan_prediction_score_kernel, B, stream, P);
 }
 
 #include "fork.inc"

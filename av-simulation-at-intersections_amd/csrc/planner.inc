@@ -66,12 +66,7 @@ struct PlanP {
     double *cost, *nodes, *traj;                   // [R], [R][max_path + 1][3], [R][max_path * (n_pts - 1)][3]
 };
 
-__device__ __forceinline__ double jpl_pymod(double a, double b) // Python's float % for b > 0
-{
-    double r = fmod(a, b);
-    if (r != 0.0 && r < 0.0) r += b;
-    return r;
-}
+#include "pymod.inc" // jpl_pymod
 __device__ __forceinline__ double jpl_normalize_angle(double th) // main/lib/maths.py:4-10
 {
     th = jpl_pymod(th, 6.283185307179586);

@@ -46,6 +46,19 @@ __device__ __forceinline__ void jrw_pose(const RecorderBuf &R, int e, int k, dou
     jrw_pose_at(R, e, k, k > 0 && jrw_is_end(R.flags[(size_t)(k - 1) * R.B + e]), x, y, yaw);
 }
 
+// An ego's state (x, y, v, yaw) at the start of tick k: jrw_pose_at's rule with the speed (the cut-off replay, the fork and the
+// predictions' scores read their states by it)
+__device__ __forceinline__ void jct_state_at(const RecorderBuf &R, int e, int k, double &x, double &y, double &v, double &yaw)
+{
+    // one pointer and one order of loads, then a choice between values: the two layouts ((x, y, v, yaw) of a state, (x, y, yaw, v) of
+    // a record) as two branches were merged by the compiler into stores to scratch at a computed place
+    const bool state = k == 0 || jrw_is_end(R.flags[(size_t)(k - 1) * R.B + e]);
+    const double *const first = R.x_first, *const spawn = R.x_spawn;
+    const double *p = state ? (k == 0 ? first : spawn) + 4 * (size_t)e : R.rec + JSIM_REC_FIELDS * ((size_t)(k - 1) * R.B + e);
+    const double q2 = p[2], q3 = p[3];
+    x = p[0]; y = p[1]; v = state ? q2 : q3; yaw = state ? q3 : q2;
+}
+
 // The ticks of a chunk that start an episode: those behind an end, of this chunk or the last of the chunk before.  tick0: this is
 // the first chunk and tick 0 counts as a start (for the episode outputs it does; for the reasons the carry decides instead)
 __device__ __forceinline__ unsigned long long jrw_start_mask(unsigned long long e_prev, unsigned long long e_cur, bool tick0)

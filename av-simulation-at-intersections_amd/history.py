@@ -89,6 +89,10 @@ PREDICTION_OUTPUTS = RowOutputs("jsim_loop_score_predictions",
                                 (("pt_i", _I, "tick", (len(PS_INT),)), ("pt_d", _F, "tick", (len(PS_DOUBLE),)),
                                  ("step_sum", _F, "row", ("n_steps",)), ("step_cnt", _I, "row", ("n_steps",)),
                                  ("err", _F, "tick", ("n_steps",))), optional=("err",))
+# The plan record (jsim_loop_set_plan_recorder): (key, numpy dtype, trailing shape) of its buffers [cap][B]...,
+# in the order of the declaration; "T" is the engine's horizon.  Slot k holds eng.oa, eng.od, eng.status at the start of tick k.
+# jsim_loop_score_plan_predictions scores them into PREDICTION_OUTPUTS' columns, rows = the egos.
+PLAN_RECORD = (("plan_oa", _F, ("T",)), ("plan_od", _F, ("T",)), ("plan_status", _I, ()))
 
 
 class History:

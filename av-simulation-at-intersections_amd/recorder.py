@@ -2,7 +2,7 @@
 read back as the reference's History objects or evaluated on the device, one launch per question (jsim_loop_eval_*).  Each
 evaluator's per-tick outputs are stated once, in history.EVALUATORS: the Recorder allocates, passes and reads back from that table.
 The predictions' scores (jsim_loop_score_predictions), whose rows are the recorded vehicles and then the egos, stand beside it in
-history.PREDICTION_OUTPUTS."""
+history.PREDICTION_OUTPUTS, and so does the plan record of an InteractingLoop (jsim_loop_set_plan_recorder), history.PLAN_RECORD."""
 from __future__ import annotations
 
 import ctypes as C
@@ -26,6 +26,8 @@ class Recorder:
     (before a respawn), applied (delta, a), xref deviation, flags -- and the scripted vehicles' get() tuples, written by the loop's
     kernels into [cap] tick slots (slot = the loop's device tick counter; ticks beyond cap are dropped).  The engine's context
     holds one recorder: the one of the loop constructed last on it; an earlier one is marked `superseded` and warns when read.
+    `plans`: the plan record of InteractingLoop(record_plans=True) -- plan_oa, plan_od [cap][B][T] and plan_status [cap][B]
+    (history.PLAN_RECORD): the engine's oa, od, status at the start of every tick -- or None.
 
     histories(b): lib.simulation.History objects, one per episode of ego b; obstacle_positions(): the scripts'
     obstacles_positions; episodes(): per-ego episode counts, lengths and ends.  These synchronise (device -> host copies)."""
@@ -47,7 +49,17 @@ class Recorder:
         self.superseded = False          # set when a later loop on the same engine registers its own recorder (or none)
         self.glue = None                 # a _GlueLoop's frame_window, margin, n_steps, mode and interacting (cutoffs()); None: no glue
         self._tracking_table = None      # the engine's paths as tracking() takes them, made at its first call
+        self.plans = None                # the plan record of an InteractingLoop(record_plans=True): history.PLAN_RECORD's tensors
         _register_recorder(eng, self)
+
+    def _record_plans(self):
+        """The plan record (jsim_loop_set_plan_recorder) beside this recorder: every tick's eng.oa, eng.od and
+        eng.status as they stand at the start of the tick, [cap] slots like rec."""
+        eng = self.loop.eng
+        self.plans = {k: torch.zeros(self.cap, eng.B, *(eng.T if s == "T" else s for s in shape), dtype=_TORCH[dt], device=eng.device)
+                      for k, dt, shape in history.PLAN_RECORD}
+        _cabi.check(eng.lib.jsim_loop_set_plan_recorder(eng._ctx, eng.B, self.cap, *map(_ptr, self.plans.values())), eng._ctx,
+                    "jsim_loop_set_plan_recorder")
 
     def _record_obstacles(self, get: torch.Tensor):
         """Host ticks of ScenarioLoop: this tick's get() tuples (ahead of step()) to the slot of the tick just advanced."""
@@ -456,10 +468,12 @@ class Recorder:
         were), idx (the progress index after the tick's update), cut (what the loop wrote to path_len, under mode="speed_cutoff" to
         the speed cut-off), hit (bool), first (the hit's index on the remaining path, -1: none), col_xy [n][B][2] (NaN: none); and
         carry [B][3] as the next tick would meet it.  history.cutoff_episodes splits the result into episodes.
-        ValueError: a recorder of a ClosedLoop (it has no glue), a recording of an InteractingLoop with mate_prediction="plan" (the
-        replay predicts the group mates from their recorded steering, and the plans the live loop predicted them from -- every
-        ego's oa, od of the tick -- are not recorded), a superseded recorder (the context's tables are no longer its loop's), a bad
-        chunk_ticks or carry."""
+        A recording of an InteractingLoop with mate_prediction="plan" is replayed from its plan record (record_plans=True;
+        jsim_loop_eval_cutoffs_plan): the mates are predicted again from the plans they were predicted from.
+        ValueError: a recorder of a ClosedLoop (it has no glue), a plan-mode recording without its plans (the replay would predict
+        the group mates from their recorded steering, and the plans the live loop predicted them from -- every ego's oa, od of
+        the tick -- are not recorded), a superseded recorder (the context's tables are no longer its loop's), a bad chunk_ticks or
+        carry."""
         out = self._host(self._cutoffs_device(chunk_ticks, carry), history.EVALUATORS["cutoffs"].keys() + ("carry",))
         out["hit"] = out["hit"] != 0
         return out
@@ -472,7 +486,9 @@ class Recorder:
         B, dev = eng.B, eng.device
         if self.glue is None:
             raise ValueError("this recorder's loop has no glue (ClosedLoop): there is no cut-off to evaluate")
-        if self.glue.get("mate_prediction", "constant") != "constant":
+        plans = getattr(self, "plans", None)
+        plan = self.glue.get("mate_prediction", "constant") != "constant"
+        if plan and plans is None:
             raise ValueError("this recording is of an InteractingLoop with mate_prediction='plan': the replay predicts the group "
                              "mates from their recorded steering, and the plans they were predicted from are not recorded")
         if self.superseded:
@@ -497,9 +513,11 @@ class Recorder:
             d_car = torch.stack([torch.zeros_like(full), torch.full_like(full, -1), full], dim=1).contiguous()
         out = self._outputs("cutoffs", n)
         rec, flags, x_first, x_spawn = self._buffers()
-        self._call("jsim_loop_eval_cutoffs", B, n, rec, flags, self.n_obs, _ptr(self.obs) if self.obs is not None else None,
-                   x_first, x_spawn, g["frame_window"], g["margin"], g["n_steps"], int(g["mode"] == "speed_cutoff"),
-                   int(g["interacting"]), c, k0, _ptr(d_car), *map(_ptr, out.values()))
+        # a plan-mode recording: the same call with the plan record behind it, the mates predicted from their recorded plans
+        self._call("jsim_loop_eval_cutoffs_plan" if plan else "jsim_loop_eval_cutoffs", B, n, rec, flags, self.n_obs,
+                   _ptr(self.obs) if self.obs is not None else None, x_first, x_spawn, g["frame_window"], g["margin"], g["n_steps"],
+                   int(g["mode"] == "speed_cutoff"), int(g["interacting"]), c, k0, _ptr(d_car), *map(_ptr, out.values()),
+                   *(map(_ptr, plans.values()) if plan else ()))
         return {**self._rows(out, n, k0), "carry": d_car}
 
     def predictions(self, n_steps=None, tol=None, egos=None, steps: bool = False) -> dict:
@@ -510,19 +528,23 @@ class Recorder:
         registers and measures its displacement error.
 
         n_steps: samples per prediction, 1..64 (default: the glue's, else 35).  tol: the displacement a prediction may be off while it
-        still `holds` (default: the ego radius).  egos: None scores the egos iff the loop is an InteractingLoop under
-        mate_prediction="constant" (what its mates predicted of it); True asks for it (ValueError on a plan-mode recording: the
-        plans are not recorded); "constant" scores the constant rule on any recording -- the baseline the plan rule is meant to
-        beat; False leaves the egos out (1 / 0 and numpy's booleans stand for True / False; anything else raises).  steps=True also returns every sample's error.
+        still `holds` (default: the ego radius).  egos: None scores the egos of an InteractingLoop as its mates predicted them --
+        the constant rule under mate_prediction="constant", the plan rule under "plan" where the plans are recorded
+        (record_plans=True), no egos where they are not; True asks for it (ValueError on a plan-mode recording without its plans);
+        "constant" scores the constant rule on any recording -- the baseline the plan rule is meant to beat; "plan" scores the plan
+        rule on any recording that holds plans (jsim_loop_score_plan_predictions, DESIGN.md section 29: the egos' rows come from
+        that call, the vehicles' from the other, joined on the device; ValueError without plans); False leaves the egos out (1 / 0
+        and numpy's booleans stand for True / False; anything else raises).  steps=True also returns every sample's error.
         Rows: V = n_obs + (B with the egos): the recorded vehicles in the recorder's order, then the egos.  Returns numpy arrays
         [n][V]: n (the scored samples: those whose truth is recorded, for an ego within its episode), hold (the leading samples
         within tol), max_at (the first sample of the largest error, -1: none), ade, fde, max, lon, lat (the last scored sample's
         error along and across the true heading; lon > 0: predicted farther ahead than the vehicle got), yaw (its heading error,
         wrapped to [-pi, pi)); NaN where n = 0; step_sum, step_cnt [V][n_steps] (history.prediction_curve gives the mean error by
-        look-ahead); err [n][V][n_steps] with steps=True (NaN: not scored); and n_steps, tol, egos (bool), n_obs and dt as used.
+        look-ahead); err [n][V][n_steps] with steps=True (NaN: not scored); and n_steps, tol, egos (bool), rule ("constant" /
+        "plan" / None: how the egos' rows were predicted), n_obs and dt as used.
         history.prediction_places gathers an ego's eight places.
-        ValueError: an n_steps outside 1..64, a tol that is not finite and >= 0, another egos, egos=True on a plan-mode recording, a
-        superseded recorder (the context's wheelbases are no longer its loop's)."""
+        ValueError: an n_steps outside 1..64, a tol that is not finite and >= 0, another egos, egos=True on a plan-mode recording
+        without plans, egos="plan" on a recorder that holds none, a superseded recorder (the context's wheelbases are no longer its loop's)."""
         d = self._predictions_device(n_steps, tol, egos, steps)
         h = self._host(d, history.PREDICTION_OUTPUTS.keys())
         pt_i, pt_d = h.pop("pt_i"), h.pop("pt_d")
@@ -532,7 +554,7 @@ class Recorder:
 
     def _predictions_device(self, n_steps=None, tol=None, egos=None, steps: bool = False, n=None) -> dict:
         """predictions() up to the launch: the outputs as device tensors (pt_i [n][V][3], pt_d [n][V][6], step_sum, step_cnt
-        [V][n_steps] and, with steps, err [n][V][n_steps]) and the host arguments used (n_steps, tol, egos, n_obs, dt)."""
+        [V][n_steps] and, with steps, err [n][V][n_steps]) and the host arguments used (n_steps, tol, egos, rule, n_obs, dt)."""
         eng = self.loop.eng
         B, dev = eng.B, eng.device
         glue = self.glue or {}
@@ -545,35 +567,59 @@ class Recorder:
         if not (math.isfinite(tol) and tol >= 0.0):
             raise ValueError(f"tol must be finite and >= 0, got {tol!r}")
         plan = glue.get("mate_prediction", "constant") != "constant"
+        plans = getattr(self, "plans", None)
         if isinstance(egos, (np.bool_, int, np.integer)) and egos in (0, 1):     # True / False and what the entry point takes for them
             egos = bool(egos)
-        if egos is None:
-            with_egos = bool(glue.get("interacting")) and not plan
+        if egos is None:                      # what the mates really predicted, where the recording can tell
+            rule = None if not glue.get("interacting") or (plan and plans is None) else "plan" if plan else "constant"
         elif egos is True:
-            if plan:
+            if plan and plans is None:
                 raise ValueError("this recording is of an InteractingLoop with mate_prediction='plan': its egos were predicted from "
                                  "their plans, which are not recorded (egos='constant' scores the constant rule instead)")
-            with_egos = True
-        elif egos is False or (isinstance(egos, str) and egos == "constant"):
-            with_egos = egos is not False
+            rule = "plan" if plan else "constant"
+        elif egos is False:
+            rule = None
+        elif isinstance(egos, str) and egos == "constant":
+            rule = "constant"
+        elif isinstance(egos, str) and egos == "plan" and plans is not None:
+            rule = "plan"
+        elif isinstance(egos, str) and egos == "plan":
+            raise ValueError("egos='plan' needs the plan record of InteractingLoop(record=..., record_plans=True): this recorder "
+                             "holds no plans")
         else:
-            raise ValueError(f"egos must be None, True / False (or 1 / 0) or 'constant', got {egos!r}")
+            raise ValueError(f"egos must be None, True / False (or 1 / 0), 'constant' or 'plan', got {egos!r}")
         if self.superseded:
             raise ValueError("a later loop on this engine replaced this recorder: the context's tables are no longer its loop's")
         n = self._n(4) if n is None else n
-        V = self.n_obs + (B if with_egos else 0)
-        shape = {"tick": (max(n, 1), max(V, 1)), "row": (max(V, 1),)}
-        out = {k: None if (k == "err" and not steps) else
-               torch.empty(*shape[lead], *(S if s == "n_steps" else s for s in trail), dtype=_TORCH[dt], device=dev)
-               for k, dt, lead, trail in history.PREDICTION_OUTPUTS.outputs}
-        if n == 0 or V == 0:                  # (the call writes nothing: no tick has scored a sample)
-            out["step_sum"].zero_(); out["step_cnt"].zero_()
         rec, flags, x_first, x_spawn = self._buffers()
+
+        def outputs(V):
+            """PREDICTION_OUTPUTS' tensors for V rows and what a call takes of them."""
+            shape = {"tick": (max(n, 1), max(V, 1)), "row": (max(V, 1),)}
+            out = {k: None if (k == "err" and not steps) else
+                   torch.empty(*shape[lead], *(S if s == "n_steps" else s for s in trail), dtype=_TORCH[dt], device=dev)
+                   for k, dt, lead, trail in history.PREDICTION_OUTPUTS.outputs}
+            if n == 0 or V == 0:              # (the call writes nothing: no tick has scored a sample)
+                out["step_sum"].zero_(); out["step_cnt"].zero_()
+            return out, [_ptr(t) if t is not None else None for t in out.values()]
+
+        def rows(out, V):
+            cut = {"tick": lambda t: t[:n, :V], "row": lambda t: t[:V]}
+            return {k: cut[lead](out[k]) for k, _, lead, _ in history.PREDICTION_OUTPUTS.outputs if out[k] is not None}
+
+        # the vehicles' rows, and with them the egos' under the constant rule: the one call
+        V0 = self.n_obs + (B if rule == "constant" else 0)
+        out, ptrs = outputs(V0)
         self._call("jsim_loop_score_predictions", B, n, rec, flags, self.n_obs, _ptr(self.obs) if self.obs is not None else None,
-                   x_first, x_spawn, int(with_egos), S, tol, *[_ptr(t) if t is not None else None for t in out.values()])
-        cut = {"tick": lambda t: t[:n, :V], "row": lambda t: t[:V]}
-        return {**{k: cut[lead](out[k]) for k, _, lead, _ in history.PREDICTION_OUTPUTS.outputs if out[k] is not None},
-                "n_steps": S, "tol": tol, "egos": with_egos, "n_obs": self.n_obs, "dt": float(eng.dt)}
+                   x_first, x_spawn, int(rule == "constant"), S, tol, *ptrs)
+        res = rows(out, V0)
+        if rule == "plan":                    # the egos' rows under the plan rule, joined behind the vehicles' on the device
+            ego, ptrs = outputs(B)
+            self._call("jsim_loop_score_plan_predictions", B, n, rec, flags, x_first, x_spawn, *map(_ptr, plans.values()), S, tol, *ptrs)
+            ego = rows(ego, B)
+            axis = {k: 1 if lead == "tick" else 0 for k, _, lead, _ in history.PREDICTION_OUTPUTS.outputs}
+            res = {k: torch.cat([res[k], ego[k]], dim=axis[k]) for k in res}
+        return {**res, "n_steps": S, "tol": tol, "egos": rule is not None, "rule": rule, "n_obs": self.n_obs, "dt": float(eng.dt)}
 
     def fork_state(self, ego, at):
         """Where a loop forked off this recording starts (jsim_loop_fork_state): for every row r the state

@@ -813,6 +813,48 @@ int jsim_loop_score_predictions(jsim_ctx *ctx, int32_t B, int32_t n_ticks, const
                                 const double *obs_rec, const double *x_first, const double *x_spawn, int32_t egos, int32_t n_steps,
                                 double tol, int32_t *pt_i, double *pt_d, double *step_sum, int32_t *step_cnt, double *err, void *stream);
 
+/* ---- the shared plans of every tick: recorded, scored and replayed ----
+ * Under JSIM_MATE_PLAN an ego is predicted from the controls its controller holds, and after a run nobody could say what those were.
+ * jsim_loop_set_plan_recorder: caller-owned DEVICE buffers beside the registered recorder's, of its B and cap; cap = 0 clears.
+ *   While registered, jsim_loop_run_interacting (under either mate prediction; no other entry point) writes slot k = the device
+ *   tick counter at the start of the tick -- the slot the tick's History record goes to; slots k >= cap are dropped:
+ *   plan_oa [cap][B][T], plan_od [cap][B][T] = oa, od and plan_status [cap][B] (int32) = status as the engine holds them at the
+ *   start of the tick, before that tick's solve: what THE RULE above reads.  T is the context's.  The steering applied last tick is
+ *   not recorded: it is field 4 of record k - 1, or 0 on tick 0 and behind a record with JSIM_REC_GOAL / JSIM_REC_AGE.  A slab of C
+ *   consecutive ticks is a [C * B][T] batch for jsim_loop_predict_egos_plan, row = tick * B + ego.  The run itself is not changed.
+ *   Refused (-22), nothing changed: B < 0, cap < 0, cap > 0 with a null buffer, a null ctx, cap > 0 with a B or cap that is not the
+ *   registered recorder's (or without one).  jsim_loop_set_recorder, registering or clearing, clears the plan recorder too.
+ *
+ * jsim_loop_score_plan_predictions: jsim_loop_score_predictions for the egos under THE RULE.  Rows are the B egos.  For tick k and
+ *   ego b: the state (x, y, v, yaw) at the start of tick k as jsim_loop_score_predictions reads an ego's; ok = plan_status[k][b] ==
+ *   JSIM_OK; delta_last = field 4 of record k - 1, or 0 when k = 0 or record k - 1 ended an episode.  Step i = 0 .. n_steps - 1, with
+ *   j = i + 1:  a_i = (ok && j < T) ? plan_oa[k][b][j] : 0;  delta_i = ok ? plan_od[k][b][min(j, T - 1)] : delta_last, clamped to
+ *   +-max_steer;  vb = v;  x += vb * cos(yaw) * dt;  y += vb * sin(yaw) * dt;  yaw += (vb / L) * tan(delta_i) * dt;  v += a_i * dt;
+ *   v = max_speed < v ? max_speed : v;  v = min_speed > v ? min_speed : v  (unfused, in that order: the samples are
+ *   jsim_loop_predict_egos_plan's pred bit for bit).  T, dt, L, max_steer, max_speed and min_speed are the context's.
+ *   Truth, m and every output are jsim_loop_score_predictions' for an ego row, with V = B: pt_i [n_ticks][B][JSIM_PS_NI], pt_d
+ *   [n_ticks][B][JSIM_PS_ND], step_sum and step_cnt [B][n_steps], err [n_ticks][B][n_steps] or NULL.  One launch, one wavefront per
+ *   ego, no prediction written to memory; step_sum is added in a fixed order: the same call gives the same bits.
+ *   DEVICE pointers throughout: rec, flags, x_first, x_spawn as jsim_loop_score_predictions takes them, plan_oa, plan_od
+ *   [n_ticks][B][T] and plan_status [n_ticks][B] as the plan recorder wrote them.  HOST counts and tol.
+ *   Refused (-22) before any device call and with nothing written: B or n_ticks < 0; n_steps outside [1, 64]; a tol that is negative
+ *   or not finite; any null pointer but err and stream; a null ctx.  B = 0 or n_ticks = 0 returns 0 and writes nothing.
+ *
+ * jsim_loop_eval_cutoffs_plan: jsim_loop_eval_cutoffs for a run under JSIM_MATE_PLAN: its arguments, then plan_oa, plan_od and
+ *   plan_status as above (DEVICE, [n_ticks][B][T] and [n_ticks][B]: the buffers of the whole recording, like rec).  The group mates of
+ *   every tick are predicted again by the kernel of jsim_loop_predict_egos_plan from the tick-start states, the recorded plans and
+ *   delta_last; everything else is jsim_loop_eval_cutoffs, whose refusals hold, and: a null plan pointer; interacting = 0. */
+int jsim_loop_set_plan_recorder(jsim_ctx *ctx, int32_t B, int32_t cap, double *plan_oa, double *plan_od, int32_t *plan_status);
+int jsim_loop_score_plan_predictions(jsim_ctx *ctx, int32_t B, int32_t n_ticks, const double *rec, const int32_t *flags,
+                                     const double *x_first, const double *x_spawn, const double *plan_oa, const double *plan_od,
+                                     const int32_t *plan_status, int32_t n_steps, double tol, int32_t *pt_i, double *pt_d,
+                                     double *step_sum, int32_t *step_cnt, double *err, void *stream);
+int jsim_loop_eval_cutoffs_plan(jsim_ctx *ctx, int32_t B, int32_t n_ticks, const double *rec, const int32_t *flags, int32_t n_obs,
+                                const double *obs_rec, const double *x_first, const double *x_spawn, int32_t frame_window, int32_t margin,
+                                int32_t n_steps, int32_t speed_cutoff, int32_t interacting, int32_t chunk_ticks, int32_t first_tick,
+                                int32_t *carry, int32_t *status, int32_t *idx, int32_t *cut, int32_t *hit, int32_t *first, double *col_xy,
+                                const double *plan_oa, const double *plan_od, const int32_t *plan_status, void *stream);
+
 /* ---- the job's one exchange: the final trajectory gather over RCCL / xGMI ----
  * The reference has no multi-process code at all (its only multi-ego code is the serial Python loop of
  * main/scenarios/interactive_mpc.py:119-172); egos are independent (main/lib/mpc.py:141-211), so ranks own contiguous shards

@@ -5,11 +5,12 @@ For each horizon: ego-steps/s over `ticks` device-synchronised ticks after a war
 the same egos in singleton groups (no interaction), plus how many ego-ticks were cut by a group mate and how many egos
 re-entered.  --mate-prediction plan: the egos share their MPC plans -- another simulation with other
 solves, so its throughput is no regression figure against "constant".  --contacts: a second, untimed run of the same ticks with
-the recorder on, and the ego-ticks on which Recorder.conflicts() finds an ego in contact with a group mate.  One JSON line per
-horizon.
+the recorder on, and the ego-ticks on which Recorder.conflicts() finds an ego in contact with a group mate.  --record-plans: the
+timed interacting run keeps its History and every tick's plans on the device (record=, record_plans=True) and
+is timed beside the same run with the History alone: the cost of recording the plans per tick.  One JSON line per horizon.
 
     python tools/bench_interacting.py [--groups 1024] [--ticks 100] [--warmup 10] [--horizons 13 20]
-                                      [--mate-prediction constant|plan] [--contacts]
+                                      [--mate-prediction constant|plan] [--contacts] [--record-plans]
 """
 import argparse
 import importlib
@@ -34,8 +35,8 @@ def make_loop(routes, G, T, sizes_of, mate_prediction, **kw):
                                     **kw)
 
 
-def timed(routes, G, T, sizes_of, ticks, warmup, mate_prediction="constant"):
-    eng, il = make_loop(routes, G, T, sizes_of, mate_prediction)
+def timed(routes, G, T, sizes_of, ticks, warmup, mate_prediction="constant", **kw):
+    eng, il = make_loop(routes, G, T, sizes_of, mate_prediction, **kw)
     cut = torch.zeros((), dtype=torch.int64, device=eng.device)
     dt = timed_run(il, warmup, ticks, each_tick=lambda: cut.add_(il.pre.col_flag.sum()))
     return (eng.B * ticks / dt, dt / ticks * 1e3, int(cut.item()), int((eng.status != 0).sum().item()),
@@ -59,6 +60,7 @@ def main():
     ap.add_argument("--horizons", type=int, nargs="+", default=[13, 20])
     ap.add_argument("--mate-prediction", choices=sorted(pkg._cabi.MATE_PREDICTION), default="constant")
     ap.add_argument("--contacts", action="store_true")
+    ap.add_argument("--record-plans", action="store_true")
     a = ap.parse_args()
     routes = W.route_table(False)[0]
     for T in a.horizons:
@@ -70,6 +72,12 @@ def main():
                 "interacting_failed_solves_last_tick": r_i[3], "interacting_respawns": r_i[4],
                 "singleton_ego_steps_per_s": round(r_s[0]), "singleton_ms_per_tick": round(r_s[1], 4),
                 "singleton_cut_ego_ticks": r_s[2]}
+        if a.record_plans:
+            K = a.warmup + a.ticks
+            for key, kw in (("recorded", dict(record=K)), ("recorded_with_plans", dict(record=K, record_plans=True))):
+                r = timed(routes, a.groups, T, lambda s, B: s, a.ticks, a.warmup, a.mate_prediction, **kw)
+                line[key + "_ego_steps_per_s"], line[key + "_ms_per_tick"] = round(r[0]), round(r[1], 4)
+            line["plan_record_ms_per_tick"] = round(line["recorded_with_plans_ms_per_tick"] - line["recorded_ms_per_tick"], 4)
         if a.contacts:
             line["interacting_contact_ego_ticks"] = contacts(routes, a.groups, T, a.ticks, a.warmup, a.mate_prediction)
         print(json.dumps(line), flush=True)

@@ -21,7 +21,15 @@ The prediction launches of Recorder.cutoffs() themselves, from a kernel trace of
     rocprofv3 --kernel-trace -d OUT/NAME --output-format csv -- python3 tools/bench_predictions.py --trace-cutoffs NAME
     python3 tools/bench_predictions.py --summarize OUT
 
+--rule plan: the interacting recording made with record_plans=True, once under each mate prediction.  Per
+recording: jsim_loop_score_plan_predictions' launch alone; beside it jsim_loop_predict_egos_plan over the same ticks x B rows --
+the call that makes the same predictions and writes them to memory, on slabs of the plan record in chunks of the 512 MiB budget --,
+jsim_loop_score_predictions' launch with the egos (the constant rule, on the same recording) and the whole
+Recorder.predictions(egos="plan") call with its read-back; then both rules' mean error by look-ahead, ade, fde and mean hold time.
+`speed_bar_met`: the new launch's median is no more than the writing call's median plus that call's own min-max spread.
+
     python3 tools/bench_predictions.py [--runs 9] [--warmup 2] [--ticks 300] [--numpy-rows 16] [--only NAME] [--out profiles/NAME.txt]
+    python3 tools/bench_predictions.py --rule plan [--runs 9] [--warmup 2] [--ticks 300] [--out FILE]
 """
 import sys
 
@@ -30,7 +38,7 @@ import numpy as np
 import recorder_bench as RB
 
 
-def record(pkg, torch, name, K):
+def record(pkg, torch, name, K, **interacting_kw):
     W = pkg.workloads
     routes = W.route_table(False)[0]
     if name == "shared":
@@ -38,7 +46,7 @@ def record(pkg, torch, name, K):
     if name == "interacting":
         batch, sizes = W.interacting_batch(routes, 1024, RB.T, seed=1)
         eng, x0 = W.make_engine(routes, batch, RB.T, "cuda:0")
-        loop = pkg.InteractingLoop(eng, x0, group_sizes=sizes, max_age=W.MAX_AGE, hist_cap=K, record=K)
+        loop = pkg.InteractingLoop(eng, x0, group_sizes=sizes, max_age=W.MAX_AGE, hist_cap=K, record=K, **interacting_kw)
     else:
         sets, tof = W.traffic_batch(4096, seed=2, vehicles=4)
         eng, x0 = W.make_engine(routes, W.ego_batch(routes, 4096, RB.T), RB.T, "cuda:0")
@@ -139,11 +147,65 @@ def summarize(out_dir):
                           "kernels": {k: {"calls": c, "ms": t / 1e6} for k, (c, t) in sorted(by.items(), key=lambda kv: -kv[1][1])}}), flush=True)
 
 
+def plan_rule(pkg, torch, a):
+    """--rule plan: see the module's text."""
+    K = a.ticks
+    res = {"rule": "plan", "ticks": K, "T": RB.T, "runs": a.runs, "warmup": a.warmup, "recordings": {}}
+    p = lambda t: None if t is None else t.data_ptr()
+    for mode in ("constant", "plan"):
+        r, _ = record(pkg, torch, "interacting", K, mate_prediction=mode, record_plans=True)
+        eng = r.loop.eng
+        B, T = eng.B, eng.T
+        d = r._predictions_device(egos="plan")
+        n, S, tol = d["pt_i"].shape[0], d["n_steps"], d["tol"]
+        oa, od, st = r.plans.values()
+
+        def score_plan():
+            pkg._cabi.check(eng.lib.jsim_loop_score_plan_predictions(eng._ctx, B, n, p(r.rec), p(r.flags), p(r.x0_first), p(r.loop.x0_spawn), p(oa),
+                                                                     p(od), p(st), S, tol, p(d["pt_i"]), p(d["pt_d"]), p(d["step_sum"]),
+                                                                     p(d["step_cnt"]), None, eng._stream()), eng._ctx, "jsim_loop_score_plan_predictions")
+        rows = n * B
+        chunk = max(1, min(rows, (512 << 20) // (S * 32 + 80)))
+        x0, di = torch.zeros(chunk, 4, dtype=torch.float64, device=eng.device), torch.zeros(chunk, 2, dtype=torch.float64, device=eng.device)
+        x0[:, 2] = 5.0
+        oa_f, od_f, st_f = oa.view(-1, T), od.view(-1, T), st.view(-1)
+
+        def write_plan():
+            for lo in range(0, rows, chunk):
+                pkg._cabi.check(eng.lib.jsim_loop_predict_egos_plan(eng._ctx, min(chunk, rows - lo), p(x0), p(oa_f[lo:]), p(od_f[lo:]), p(st_f[lo:]),
+                                                                    p(di), S, None, eng._stream()), eng._ctx, "jsim_loop_predict_egos_plan")
+        new, alt = events(torch, score_plan, a.runs, a.warmup), events(torch, write_plan, a.runs, a.warmup)
+        const_launch, _ = launch_alone(pkg, torch, r, "constant", a.runs, a.warmup)
+        ts, out = RB.timed(lambda: r.predictions(egos="plan"), a.runs, a.warmup)
+        row = {"mate_prediction": mode, "B": B, "rows_per_launch": B, "predictions": rows, "n_steps": S, "tol": tol,
+               "score_plan_launch_ms": new, "predict_egos_plan_written_ms": alt, "written_chunks": -(-rows // chunk),
+               "speed_bar_ms": alt["median"] + (alt["max"] - alt["min"]), "speed_bar_met": new["median"] <= alt["median"] + (alt["max"] - alt["min"]),
+               "score_constant_launch_ms": const_launch, "call_ms": RB.stats(ts), "plan_record_bytes": int(sum(t.numel() * t.element_size() for t in r.plans.values()))}
+        for rule, o in (("plan", out), ("constant", r.predictions(egos="constant"))):
+            t, _ = pkg.history.prediction_curve(o, eng.dt)
+            with np.errstate(invalid="ignore"):
+                mean = np.nansum(o["step_sum"], axis=0) / np.maximum(o["step_cnt"].sum(axis=0), 1)
+            pick = [0, 4, 9, 14, 19, 24, 29, S - 1] if S >= 30 else list(range(S))
+            held = o["hold"] >= o["n"]                                      # within tol on every scored sample
+            row[rule] = {"t": [round(float(v), 3) for v in t[pick]], "mean_error": [float(v) for v in mean[pick]],
+                         "ade_mean": float(np.nanmean(o["ade"])), "fde_mean": float(np.nanmean(o["fde"])), "hold_mean_s": float(o["hold"].mean() * eng.dt),
+                         "held_to_the_end_share": float(held.mean()), "samples": int(o["step_cnt"].sum())}
+        res["recordings"][mode] = row
+        print(f"{mode}: {row}", file=sys.stderr, flush=True)
+        del r, d, oa, od, st, oa_f, od_f, st_f, out
+        torch.cuda.empty_cache()
+    RB.emit(res, a.out)
+
+
 def main():
-    a = RB.arguments(runs=9, warmup=2, numpy_rows=16, only="", trace_cutoffs="", summarize="")
+    a = RB.arguments(runs=9, warmup=2, numpy_rows=16, only="", trace_cutoffs="", summarize="", rule="constant")
     if a.summarize:
         return summarize(a.summarize)
     torch, pkg = RB.setup("bench_predictions")
+    if a.rule == "plan":
+        return plan_rule(pkg, torch, a)
+    if a.rule != "constant":
+        raise SystemExit(f"--rule must be constant or plan, got {a.rule!r}")
     if a.trace_cutoffs:
         return trace_cutoffs(pkg, torch, a.trace_cutoffs, a.ticks)
     import predictions_numpy as PN
