@@ -14,6 +14,7 @@ from .batched import BatchedMPC  # noqa: F401
 from .closed_loop import ClosedLoop, PreTick, ScriptedObstacles, ScenarioLoop, InteractingLoop, Recorder, car_circles  # noqa: F401
 from . import history  # noqa: F401
 from . import recorder  # noqa: F401
+from . import checkpoint  # noqa: F401
 from . import mpc  # noqa: F401
 from .mpc import MPC, MAX_ACCEL, MAX_DECEL, MPCSolutionNotFoundException  # noqa: F401
 from . import mpc_with_speed  # noqa: F401

@@ -43,7 +43,9 @@ EXPORTS = (
     "jsim_loop_eval_static", "jsim_loop_summarise_episodes", "jsim_loop_eval_cutoffs", "jsim_loop_fork_state", "jsim_loop_obstacles_at",
     "jsim_loop_eval_gaps", "jsim_loop_eval_tracking", "jsim_loop_eval_headway", "jsim_loop_score_predictions",
     "jsim_loop_set_plan_recorder", "jsim_loop_score_plan_predictions", "jsim_loop_eval_cutoffs_plan",
+    "jsim_loop_checkpoint_save", "jsim_loop_checkpoint_load",
 )
+CKPT_MAX_ARRAYS = 32   # JSIM_CKPT_MAX_ARRAYS
 
 _lib = None
 
@@ -205,6 +207,12 @@ def load() -> C.CDLL:
     lib.jsim_loop_obstacles_at.restype = C.c_int
     #                                     ctx n_obs state0 param wheelbase ticks state stream
     lib.jsim_loop_obstacles_at.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp]
+    lib.jsim_loop_checkpoint_save.restype = C.c_int
+    #                                        ctx n_arrays src dst bytes stream
+    lib.jsim_loop_checkpoint_save.argtypes = [vp, i32, vp, vp, vp, vp]
+    lib.jsim_loop_checkpoint_load.restype = C.c_int
+    #                                        ctx B    n_slots written n_rows ego slot n_fields slab dst row_bytes n_obs obs_slab n_veh veh_src veh_slot obs_state stream
+    lib.jsim_loop_checkpoint_load.argtypes = [vp, i32, i32, vp, i32, vp, vp, i32, vp, vp, vp, i32, vp, i32, vp, vp, vp, vp]
     if lib.jsim_abi_version() != ABI_VERSION:
         raise JsimError(f"libjsim_mpc.so ABI {lib.jsim_abi_version()} != binding ABI {ABI_VERSION}")
     _lib = lib

@@ -15,7 +15,7 @@ else:                                      # run as a script: python av-simulati
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(_HERE, "csrc", "jsim_mpc.hip")
-PLAN_SRC = os.path.join(_HERE, "csrc", "jsim_plan.hip")   # the plan record's kernels: a code object of their own
+PLAN_SRC = os.path.join(_HERE, "csrc", "jsim_plan.hip")   # the plan record's and the checkpoint kernels: a code object of their own (DESIGN.md sections 29, 30)
 INC = os.path.join(os.path.dirname(_HERE), "include")
 LIB = os.path.join(_HERE, "libjsim_mpc.so")
 

@@ -12,19 +12,27 @@ import torch
 
 from . import _cabi, history
 from .batched import BatchedMPC, _ptr
+from .checkpoint import Checkpointed, Checkpoints, check_every
 from .history import MAX_OBS
 from .recorder import Recorder, _register_recorder
 from .vehicle import car_circles, vehicle_shape
 
 
-class ClosedLoop:
+class ClosedLoop(Checkpointed):
     """tick(): jsim_mpc_step then jsim_loop_advance (plant, history, respawn of finished egos).
 
     hist_cap: ticks of (di, ai) history kept on the device ([hist_cap, B, 2]); max_age: safety respawn
     after that many ticks (<= 0: only MPC.is_goal ends an ego's run); record: ticks of the full History kept on the device
-    (`recorder`, a Recorder; 0: none)."""
+    (`recorder`, a Recorder; 0: none).
+    checkpoint_every=C (with record): the loop's whole live state (history.CHECKPOINT) is kept at the start of every C-th tick
+    (DESIGN.md section 30) -- run(n) is issued in pieces that end at those ticks, the results are the same bit for bit;
+    `checkpoints` lists the written slots, restore(slot) rewinds the loop, save_checkpoints / load_checkpoints carry the slabs to
+    another process.  checkpoint_slots: more slots than record // C + 1 (for a smaller C after a restore)."""
 
-    def __init__(self, engine: BatchedMPC, x0: torch.Tensor, hist_cap: int = 0, max_age: int = 0, record: int = 0):
+    def __init__(self, engine: BatchedMPC, x0: torch.Tensor, hist_cap: int = 0, max_age: int = 0, record: int = 0,
+                 checkpoint_every: Optional[int] = None, checkpoint_slots: Optional[int] = None):
+        if checkpoint_every is not None:
+            check_every(checkpoint_every, record)      # before any device work
         eng = self.eng = engine
         eng._check_x0(x0)
         self.x0 = x0
@@ -44,6 +52,8 @@ class ClosedLoop:
             _register_recorder(eng, None)            # an earlier loop's recorder on this engine stops recording
         if record:
             self.recorder = Recorder(self, record)
+        if checkpoint_every is not None:
+            self._ck = Checkpoints({"loop": self, "eng": eng}, checkpoint_every, record, checkpoint_slots)
 
     def _advance_args(self):
         """What tick() passes to jsim_loop_advance after (ctx, B)."""
@@ -54,8 +64,9 @@ class ClosedLoop:
 
     def tick(self):
         eng = self.eng
-        eng.solve(self.x0)
-        _cabi.check(eng.lib.jsim_loop_advance(eng._ctx, eng.B, *self._advance_args()), eng._ctx, "jsim_loop_advance")
+        for _ in self._pieces(1):
+            eng.solve(self.x0)
+            _cabi.check(eng.lib.jsim_loop_advance(eng._ctx, eng.B, *self._advance_args()), eng._ctx, "jsim_loop_advance")
 
     def _loop_args(self):
         """Checks x0; returns the step and advance buffers the multi-tick entry points take after (ctx, B, n_ticks)."""
@@ -70,13 +81,17 @@ class ClosedLoop:
         """n_ticks ticks in one call (jsim_mpc_run_ticks): for T = 13 / 20 a single launch in which each wavefront
         advances its own ego n_ticks times -- same results as n_ticks x tick(), without per-tick synchronisation."""
         eng = self.eng
-        _cabi.check(eng.lib.jsim_mpc_run_ticks(eng._ctx, eng.B, int(n_ticks), *self._loop_args(), eng._stream()), eng._ctx,
-                    "jsim_mpc_run_ticks")
+        for n in self._pieces(n_ticks):      # (without checkpoints: n_ticks itself)
+            _cabi.check(eng.lib.jsim_mpc_run_ticks(eng._ctx, eng.B, n, *self._loop_args(), eng._stream()), eng._ctx,
+                        "jsim_mpc_run_ticks")
 
     # ---- hipGraph: a launch-bound inner loop (two short kernels per tick) replayed without host work
     def capture(self, ticks: int):
         """Capture `ticks` consecutive ticks into one hipGraph (all pointers are fixed device buffers and the
-        history slot comes from the device tick counter, so replays continue the same simulation)."""
+        history slot comes from the device tick counter, so replays continue the same simulation).  ValueError on a loop with
+        checkpoints: a replayed graph advances ticks the host does not see."""
+        if self._ck is not None:
+            raise ValueError("a loop with checkpoints cannot be captured: a replayed graph advances ticks the host does not count")
         g = torch.cuda.CUDAGraph()
         s = torch.cuda.Stream(device=self.eng.device)
         s.wait_stream(torch.cuda.current_stream(self.eng.device))
@@ -307,12 +322,15 @@ def _register_traffic(engine: BatchedMPC, set_of, obs_off, chunk_ticks: int = 0)
     engine.traffic_layout = (set_of, obs_off)
 
 
-class _GlueLoop:
-    """What ScenarioLoop and InteractingLoop share: construction, run() and the recorder.  The loop constructed last on an engine
+class _GlueLoop(Checkpointed):
+    """What ScenarioLoop and InteractingLoop share: construction, run(), the recorder and the checkpoints (checkpoint_every,
+    checkpoint_slots: as ClosedLoop's, the glue's and the scripted vehicles' state included).  The loop constructed last on an engine
     owns its context's tables: ClosedLoop and PreTick clear an earlier recorder and shape table, the rest is registered here."""
 
     def __init__(self, engine: BatchedMPC, x0: torch.Tensor, obstacle_specs, hist_cap, max_age, frame_window, mode, traffic_of,
-                 chunk_ticks, record, group_off=None, record_plans=False):
+                 chunk_ticks, record, group_off=None, record_plans=False, checkpoint_every=None, checkpoint_slots=None):
+        if checkpoint_every is not None:
+            check_every(checkpoint_every, record)                                     # before any device work
         layout = None
         if traffic_of is not None:
             layout = traffic_layout(engine.B, obstacle_specs, traffic_of, group_off=group_off)   # before any device work
@@ -337,9 +355,67 @@ class _GlueLoop:
                                        "record_plans": bool(record_plans)}
             if record_plans:
                 self.loop.recorder._record_plans()
+        if checkpoint_every is not None:
+            self._ck = Checkpoints(self._owners(), checkpoint_every, record, checkpoint_slots)
+
+    def _owners(self) -> dict:
+        """The objects that own this loop's live state, under history.CHECKPOINT's names."""
+        return {"loop": self.loop, "eng": self.loop.eng, "pre": self.pre, "obst": self.obst}
 
     def _register_groups(self):
         """Only InteractingLoop has groups."""
+
+    # ---- what the forks share (DESIGN.md sections 22 and 30)
+    def _fork_engine(self, idx: torch.Tensor, paths, pid, speed, smooth: bool, cv, config, ego_configs) -> BatchedMPC:
+        """The new engine of a fork whose rows are this engine's egos idx: T, dt, dl, L are this engine's; speed, config and the rows
+        of the per-ego table too unless given."""
+        eng, R = self.loop.eng, int(idx.numel())
+        spd = eng.speed[idx].cpu().numpy() if speed is None else np.asarray(speed, dtype=np.float64)
+        if spd.shape not in ((), (R,)):
+            raise ValueError(f"speed must be one number or one per row ({R}), got {spd.shape}")
+        new = BatchedMPC(paths, pid, dl=eng.dl, L=eng.L, speed=spd, dt=eng.dt, T=eng.T, config=eng.config if config is None else config,
+                         device=eng.device, smooth=smooth, cv=cv)
+        pe = getattr(eng, "_pe", None)
+        if ego_configs is not None:
+            new.set_ego_configs(ego_configs)
+        elif pe is not None:
+            new.set_ego_configs(pe[idx])
+        return new
+
+    def _fork_traffic(self, set_of_row, at):
+        """The traffic of a fork: one set per (source set, tick) among the rows, in the rows' own order of first appearance.  Returns
+        (keys, tof [rows], veh: each new set's vehicles among the source's, sets: their specs, shared: one set for a loop without
+        sets -- the fork is then a loop like the source, with one shared list)."""
+        src_off = np.array([0, self.obst.n]) if self.traffic is None else self.traffic[1]
+        keys, tof = {}, np.empty(len(at), dtype=np.int32)
+        for r in range(len(at)):
+            tof[r] = keys.setdefault((int(set_of_row[r]), int(at[r])), len(keys))
+        veh = [np.arange(src_off[s], src_off[s + 1]) for s, _ in keys]
+        sets = [[self.specs[o] for o in v] for v in veh]
+        return keys, tof, veh, sets, self.traffic is None and len(keys) == 1
+
+    def _source_sets(self) -> np.ndarray:
+        """The traffic set of every ego of this loop (all 0 for a loop without sets)."""
+        return np.zeros(self.loop.eng.B, dtype=np.int64) if self.traffic is None else self.traffic[0]
+
+    def _warm_rows(self, n_units: int, unit, at):
+        """The rows of a warm fork, checked: (unit [R], at [R], slot [R]) -- every tick must be a checkpointed one."""
+        ck = self._need_ck()
+        unit, at = history.fork_rows(n_units, ck.t, unit, at)
+        if unit.size < 1:
+            raise ValueError("fork needs at least one row")
+        return unit, at, history.checkpoint_at(ck.slot_tick, at)
+
+    def _load_warm(self, fork: "_GlueLoop", ego, slot, keys, veh):
+        """Every row of `fork` continues ego ego[r] from slot slot[r], its vehicles from the slots of their ticks
+        (jsim_loop_checkpoint_load); obst.reset() returns there."""
+        ck = self._ck
+        veh_src = np.concatenate(veh) if veh else np.zeros(0, dtype=np.int64)
+        key_slot = history.checkpoint_at(ck.slot_tick, [k for _, k in keys])
+        veh_slot = np.concatenate([np.full(len(v), s) for v, s in zip(veh, key_slot)]) if veh else np.zeros(0, dtype=np.int64)
+        ck.load_into(fork._owners(), ego, slot, veh_src, veh_slot)
+        if fork.obst.n:
+            fork.obst._state0.copy_(fork.obst.state)
 
     @property
     def recorder(self) -> Optional[Recorder]:
@@ -359,7 +435,8 @@ class _GlueLoop:
         (config.ONE_WAVE_HORIZONS / FOUR_WAVE_HORIZONS) and MAX_ITER = 1: three launches -- the scripted obstacles rolled forward
         n_ticks ticks, their predictions for every tick, one fused launch of n_ticks x (glue + solve + plant) per wavefront."""
         eng, lib = self.loop.eng, self.loop.eng.lib
-        _cabi.check(getattr(lib, self._ENTRY)(eng._ctx, eng.B, int(n_ticks), *self._run_args()), eng._ctx, self._ENTRY)
+        for n in self._pieces(n_ticks):          # (without checkpoints: n_ticks itself)
+            _cabi.check(getattr(lib, self._ENTRY)(eng._ctx, eng.B, n, *self._run_args()), eng._ctx, self._ENTRY)
         self.pre.n_obs = self.obst.n
 
 
@@ -373,18 +450,26 @@ class ScenarioLoop(_GlueLoop):
     whose obstacle_specs are set traffic_of[e], bit for bit.  chunk_ticks: ticks per fused launch (0: from a 512 MiB budget).
     record: ticks of the full History kept on the device, the vehicles' get() tuples included (`recorder`; 0: none).
     A spec with dims=dict(L=..., width=..., extra_length=...) gives that vehicle its own shape (vehicle_shape): a car and a
-    cyclist in one loop, or per set.  Vehicles without dims have the ego's shape; no dims anywhere: no table is registered."""
+    cyclist in one loop, or per set.  Vehicles without dims have the ego's shape; no dims anywhere: no table is registered.
+    checkpoint_every, checkpoint_slots: as ClosedLoop's, with the glue's and the vehicles' state; such a loop
+    can be rewound (restore) and forked warm (fork(..., warm=True)): rows that continue egos from checkpointed ticks."""
 
     _ENTRY = "jsim_loop_run_scenario"
 
     def __init__(self, engine: BatchedMPC, x0: torch.Tensor, obstacle_specs, hist_cap: int = 0, max_age: int = 0,
-                 frame_window: int = 10, mode: str = "truncate", traffic_of=None, chunk_ticks: int = 0, record: int = 0):
-        super().__init__(engine, x0, obstacle_specs, hist_cap, max_age, frame_window, mode, traffic_of, chunk_ticks, record)
+                 frame_window: int = 10, mode: str = "truncate", traffic_of=None, chunk_ticks: int = 0, record: int = 0,
+                 checkpoint_every: Optional[int] = None, checkpoint_slots: Optional[int] = None):
+        super().__init__(engine, x0, obstacle_specs, hist_cap, max_age, frame_window, mode, traffic_of, chunk_ticks, record,
+                         checkpoint_every=checkpoint_every, checkpoint_slots=checkpoint_slots)
 
     def tick(self):
         if self.traffic is not None:             # the vehicles of all sets: the gridded kernels of run()
             self.run(1)
             return
+        for _ in self._pieces(1):                # (a checkpoint that is due is saved first)
+            self._host_tick()
+
+    def _host_tick(self):
         g = self.obst.get(step=False)
         self.pre.predict(g)
         self.pre.run(self.loop.x0)
@@ -398,8 +483,19 @@ class ScenarioLoop(_GlueLoop):
             rec._record_obstacles(g)
 
     def fork(self, ego, at, paths=None, path_id=None, speed=None, record: int = 0, max_age: Optional[int] = None,
-             chunk_ticks: int = 0, cv=None) -> "ScenarioLoop":
-        """A new ScenarioLoop on a new engine whose row r starts where ego ego[r] of this loop's recording stood at the start of
+             chunk_ticks: int = 0, cv=None, warm: bool = False, config=None, ego_configs=None,
+             checkpoint_every: Optional[int] = None, checkpoint_slots: Optional[int] = None) -> "ScenarioLoop":
+        """warm=True (a loop with checkpoints): every row CONTINUES ego ego[r] from the checkpoint at tick
+        at[r] -- state, age, spawn state, the controller's warm start and remembered path index, the glue's progress index, previous
+        path length and cut-off, and its traffic set's vehicles, all as they stood (jsim_loop_checkpoint_load) -- so that, with
+        nothing changed, the fork's records are the source's from that tick on, bit for bit; with another speed, max_age, config or
+        ego_configs it is the counterfactual from that tick.  at[r] must be a checkpointed tick (`checkpoints`); paths, path_id and
+        cv are refused: a warm start belongs to its path.  record, checkpoint_every, checkpoint_slots: the new loop's own.
+        config / ego_configs (either kind of fork): the new engine's configuration and per-ego table (default: this engine's, the
+        table's rows of the forked egos).
+
+        warm=False, the cold fork:
+        A new ScenarioLoop on a new engine whose row r starts where ego ego[r] of this loop's recording stood at the start of
         recorded tick at[r], on a path of its own and with a cold controller: what perform_replan of
         main/scenarios/overtaking_cyclist_bidirectional_road.py (:394-402) does when it builds a fresh MPC on the chosen trajectory
         and lets the same simulation and the same cyclist go on.  Rows, not egos: one ego forked at its trigger tick onto each of
@@ -415,8 +511,25 @@ class ScenarioLoop(_GlueLoop):
         traffic set (the whole list of a loop without sets; dims carried over) where they stood at tick at[r]
         (jsim_loop_obstacles_at); obst.reset() returns there.  Rows of one source set and one tick share a set.
         This loop, its engine and its recorder are left as they are.
-        ValueError: no recorder; what fork_state, BatchedMPC and traffic_layout raise; new paths without path_id."""
+        ValueError: no recorder; what fork_state, BatchedMPC and traffic_layout raise; new paths without path_id; warm=True without
+        checkpoints, with paths / path_id / cv, or at a tick that is not checkpointed (the message names the nearest ones)."""
         src, eng, rec = self.loop, self.loop.eng, self.recorder
+        kw = dict(hist_cap=src.hist_cap, max_age=src.max_age if max_age is None else max_age, frame_window=self.pre.frame_window,
+                  mode=self.pre.mode, chunk_ticks=chunk_ticks, record=record, checkpoint_every=checkpoint_every,
+                  checkpoint_slots=checkpoint_slots)
+        if warm:
+            if paths is not None or path_id is not None or cv is not None:
+                raise ValueError("a warm fork keeps every ego on its own path (a warm start belongs to its path): paths, path_id and "
+                                 "cv are the cold fork's")
+            ego, at, slot = self._warm_rows(eng.B, ego, at)
+            idx, sl = (torch.from_numpy(v.astype(np.int64)).to(eng.device) for v in (ego, slot))
+            new = self._fork_engine(idx, [p.copy() for p in eng.paths], eng.path_id[idx].cpu().numpy(), speed, False, eng.cv, config,
+                                    ego_configs)
+            keys, tof, veh, sets, shared = self._fork_traffic(self._source_sets()[ego], at)
+            fork = ScenarioLoop(new, self._ck.slabs["x0"][sl, idx].contiguous(), sets[0] if shared else sets,
+                                traffic_of=None if shared else tof, **kw)
+            self._load_warm(fork, ego, slot, keys, veh)
+            return fork
         if rec is None:
             raise ValueError("fork needs the loop's recording (record=...)")
         x0, k0, age = rec.fork_state(ego, at)
@@ -438,29 +551,10 @@ class ScenarioLoop(_GlueLoop):
         pid = np.broadcast_to(pid, (R,)) if pid.ndim == 0 else pid
         if pid.shape != (R,):
             raise ValueError(f"path_id must hold one route per row ({R}), got {pid.shape}")
-        spd = eng.speed[idx].cpu().numpy() if speed is None else np.asarray(speed, dtype=np.float64)
-        if spd.shape not in ((), (R,)):
-            raise ValueError(f"speed must be one number or one per row ({R}), got {spd.shape}")
-        new = BatchedMPC(paths, pid, dl=eng.dl, L=eng.L, speed=spd, dt=eng.dt, T=eng.T, config=eng.config, device=eng.device,
-                         smooth=smooth, cv=cv)
-        pe = getattr(eng, "_pe", None)
-        if pe is not None:
-            new.set_ego_configs(pe[idx])
+        new = self._fork_engine(idx, paths, pid, speed, smooth, cv, config, ego_configs)
         # traffic: one set per (source set, tick) among the rows, the rows' own order of first appearance
-        n_src = self.obst.n
-        if self.traffic is None:
-            src_set, src_off = np.zeros(eng.B, dtype=np.int64), np.array([0, n_src])
-        else:
-            src_set, src_off = self.traffic
-        keys, tof = {}, np.empty(R, dtype=np.int32)
-        for r in range(R):
-            tof[r] = keys.setdefault((int(src_set[ego[r]]), int(at[r])), len(keys))
-        veh = [np.arange(src_off[s], src_off[s + 1]) for s, _ in keys]                # each new set's vehicles among the source's
-        sets = [[self.specs[o] for o in v] for v in veh]
-        shared = self.traffic is None and len(keys) == 1
-        fork = ScenarioLoop(new, x0, sets[0] if shared else sets, hist_cap=src.hist_cap,
-                            max_age=src.max_age if max_age is None else max_age, frame_window=self.pre.frame_window, mode=self.pre.mode,
-                            traffic_of=None if shared else tof, chunk_ticks=chunk_ticks, record=record)
+        keys, tof, veh, sets, shared = self._fork_traffic(self._source_sets()[ego], at)
+        fork = ScenarioLoop(new, x0, sets[0] if shared else sets, traffic_of=None if shared else tof, **kw)
         fork.loop.age.copy_(torch.from_numpy(np.ascontiguousarray(age, dtype=np.int32)))
         if own_paths:
             # a row that starts its ego's episode on the ego's own route is that ego's respawn: the path index it respawns with
@@ -526,24 +620,29 @@ class InteractingLoop(_GlueLoop):
     record_plans (with record, under either mate_prediction): every tick's plans -- eng.oa, eng.od, eng.status as they stand at the
     start of the tick -- are kept on the device beside the History (`recorder.plans`); the run itself is the
     same bit for bit.  With them Recorder.cutoffs() replays a plan-mode recording and Recorder.predictions(egos="plan") scores the
-    plan rule against what each ego then did; a plan-mode recording without them has neither."""
+    plan rule against what each ego then did; a plan-mode recording without them has neither.
+    checkpoint_every, checkpoint_slots: as ScenarioLoop's; fork(group, at, warm=True) then continues whole
+    groups from a checkpointed tick, under this or the other mate_prediction."""
 
     _ENTRY = "jsim_loop_run_interacting"
 
     def __init__(self, engine: BatchedMPC, x0: torch.Tensor, group_off=None, obstacle_specs=(), hist_cap: int = 0,
                  max_age: int = 0, frame_window: int = 20, group_sizes=None, traffic_of=None, record: int = 0,
-                 mate_prediction: str = "constant", record_plans: bool = False):
+                 mate_prediction: str = "constant", record_plans: bool = False, checkpoint_every: Optional[int] = None,
+                 checkpoint_slots: Optional[int] = None):
         if mate_prediction not in _cabi.MATE_PREDICTION:                              # before any device work
             raise ValueError(f"mate_prediction must be one of {sorted(_cabi.MATE_PREDICTION)}, got {mate_prediction!r}")
         if record_plans and not record:
             raise ValueError("record_plans needs a recorder: record must be a positive number of ticks")
+        if checkpoint_every is not None:
+            check_every(checkpoint_every, record)
         self.mate_prediction = mate_prediction
         off = self.group_off = group_offsets(engine.B, group_off, group_sizes)
         n_obs, big = len(obstacle_specs), int(np.diff(off).max())
         if traffic_of is None and n_obs + big - 1 > MAX_GROUP:
             raise ValueError(f"{n_obs} scripted obstacles + the largest group ({big}) - 1 > {MAX_GROUP}")
         super().__init__(engine, x0, obstacle_specs, hist_cap, max_age, frame_window, "truncate", traffic_of, 0, record,
-                         group_off=off, record_plans=record_plans)
+                         group_off=off, record_plans=record_plans, checkpoint_every=checkpoint_every, checkpoint_slots=checkpoint_slots)
 
     def _register_groups(self):
         """The groups and, every time, how their egos predict each other: a later loop on the same engine has its own mode."""
@@ -570,7 +669,36 @@ class InteractingLoop(_GlueLoop):
     def tick(self):
         self.run(1)
 
-    def fork(self, *args, **kwargs):
-        """Refused: a forked ego's group mates would have to go on with the controllers they had."""
-        raise ValueError("an InteractingLoop cannot be forked: the group mates' warm starts (oa, od) are not recorded, so their "
-                         "controllers cannot be continued from a recorded tick")
+    def fork(self, group=None, at=None, warm: bool = False, mate_prediction: Optional[str] = None, record: int = 0,
+             max_age: Optional[int] = None, speed=None, config=None, ego_configs=None, record_plans: Optional[bool] = None,
+             checkpoint_every: Optional[int] = None, checkpoint_slots: Optional[int] = None, **cold) -> "InteractingLoop":
+        """A new InteractingLoop on a new engine whose rows are whole groups, continued from checkpoints: every
+        ego of group group[r] goes on from the checkpoint at tick at[r] -- the mates' controllers as they were, so that the group's
+        records are the source's from that tick on, bit for bit, until something is changed: mate_prediction (default: this
+        loop's), speed (per ego of the new batch), max_age, config, ego_configs.  The groups lie contiguously in the new batch, in the
+        rows' order; a group meets its traffic set's vehicles where they stood (rows of one source set and one tick share a set).
+        record, record_plans (default: this loop's, with record), checkpoint_every, checkpoint_slots: the new loop's own.
+        ValueError: without warm=True or on a loop without checkpoints -- a cold fork of a group is refused (section 22): the mates
+        would have to go on with the controllers they had, and the recorder does not hold them; a group outside the loop's; a tick
+        that is not checkpointed."""
+        if not warm or self._ck is None or cold:
+            raise ValueError("an InteractingLoop cannot be forked cold: the group mates' warm starts (oa, od) are not recorded, so their "
+                             "controllers cannot be continued from a recorded tick; a loop with checkpoints (checkpoint_every=...) "
+                             "forks whole groups from a checkpointed tick with warm=True")
+        src, eng, off = self.loop, self.loop.eng, self.group_off
+        group, at, _ = self._warm_rows(len(off) - 1, group, at)
+        ego = np.concatenate([np.arange(off[g], off[g + 1]) for g in group]).astype(np.int32)
+        sizes = np.diff(off)[group]
+        slot = history.checkpoint_at(self._ck.slot_tick, np.repeat(at, sizes))
+        idx, sl = (torch.from_numpy(v.astype(np.int64)).to(eng.device) for v in (ego, slot))
+        new = self._fork_engine(idx, [p.copy() for p in eng.paths], eng.path_id[idx].cpu().numpy(), speed, False, eng.cv, config, ego_configs)
+        keys, tof, veh, sets, shared = self._fork_traffic(self._source_sets()[off[group]], at)
+        if record_plans is None:
+            record_plans = bool(record) and self.recorder is not None and bool(self.recorder.glue.get("record_plans"))
+        fork = InteractingLoop(new, self._ck.slabs["x0"][sl, idx].contiguous(), group_sizes=sizes, obstacle_specs=sets[0] if shared else sets,
+                               hist_cap=src.hist_cap, max_age=src.max_age if max_age is None else max_age,
+                               frame_window=self.pre.frame_window, traffic_of=None if shared else tof, record=record,
+                               mate_prediction=self.mate_prediction if mate_prediction is None else mate_prediction,
+                               record_plans=record_plans, checkpoint_every=checkpoint_every, checkpoint_slots=checkpoint_slots)
+        self._load_warm(fork, ego, slot, keys, veh)
+        return fork

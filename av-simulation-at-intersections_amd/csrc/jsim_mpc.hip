@@ -1409,6 +1409,7 @@ struct jsim_ctx {
     DevArray<double> d_cut_x0, d_cut_di;   // [chunk][B][4], [chunk][B][2]
     DevArray<int> d_cut_carry;             // [B][3]
     DevArray<int> d_fork_rows, d_fork_ticks; // [2][n_rows] (ego, at) of jsim_loop_fork_state's, [n_obs] of jsim_loop_obstacles_at's last call
+    DevArray<int> d_ckpt_rows;     // (ego, slot) [2][n_rows], then (vehicle, slot) [2][n_veh] of jsim_loop_checkpoint_load's last call
     DevArray<double> d_pcv;        // speed reference per path point (mpc_with_speed variant) or NULL
     const int *cv_cut = nullptr;   // caller-owned device array [B] or NULL
     size_t lds_bytes = 0;
@@ -3526,6 +3527,91 @@ extern "C" int jsim_loop_obstacles_at(jsim_ctx *ctx, int32_t n_obs, const double
     if (int rc = replace_table(ctx, ctx->d_fork_ticks, ticks, (size_t)n_obs)) return rc;
     const ObsAtP P = {n_obs, ctx->have_ogeom ? ctx->oL : ctx->cfg.L, state0, param, wheelbase, ctx->d_fork_ticks.p, state};
     hipLaunchKernelGGL(obstacles_at_kernel, dim3((n_obs + 63) / 64), dim3(64), 0, (hipStream_t)stream, P);
+    HIP_TRY(ctx, hipGetLastError());
+    return 0;
+}
+
+#include "checkpoint.inc" // the checkpoint kernels' parameters; the kernels themselves are jsim_plan.hip's
+
+static bool ckpt_aligned(const void *p) { return ((uintptr_t)p & 3u) == 0; }
+
+// One slot of a loop's checkpoint slabs written, or read back: n_arrays copies of bytes[i] bytes from src[i] to
+// dst[i] in ONE launch on `stream`.  src, dst and bytes are HOST arrays of DEVICE pointers and sizes; the table travels in the
+// kernel's arguments, so the call neither allocates nor synchronises.
+extern "C" int jsim_loop_checkpoint_save(jsim_ctx *ctx, int32_t n_arrays, const void *const *src, void *const *dst, const int64_t *bytes,
+                                         void *stream)
+{
+    const char *const F = "jsim_loop_checkpoint_save";
+    if (n_arrays < 0 || n_arrays > JSIM_CKPT_MAX_ARRAYS) return fail(ctx, -22, "%s: n_arrays=%d (0..%d)", F, n_arrays, JSIM_CKPT_MAX_ARRAYS);
+    if (n_arrays > 0 && (!src || !dst || !bytes)) return fail(ctx, -22, "%s: null pointer", F);
+    long long most = 0;
+    for (int i = 0; i < n_arrays; ++i) {
+        if (!src[i] || !dst[i]) return fail(ctx, -22, "%s: array %d: null pointer", F, i);
+        if (bytes[i] < 0 || (bytes[i] & 3) || !ckpt_aligned(src[i]) || !ckpt_aligned(dst[i]))
+            return fail(ctx, -22, "%s: array %d: bytes=%lld and both pointers must be multiples of 4", F, i, (long long)bytes[i]);
+        most = std::max(most, (long long)bytes[i]);
+    }
+    JSIM_RECORDER_CALL(n_arrays == 0 || most == 0);
+    CkptCopyP P;
+    memset(&P, 0, sizeof(P));
+    P.n = n_arrays;
+    for (int i = 0; i < n_arrays; ++i) P.e[i] = CkptCopy{src[i], dst[i], (long long)bytes[i]};
+    // the largest array in 16-byte words, one per thread, up to 64 blocks; the threads stride beyond that
+    const unsigned gx = (unsigned)std::min<long long>(64, std::max<long long>(1, (most / 16 + 255) / 256));
+    hipLaunchKernelGGL(checkpoint_copy_kernel, dim3(gx, (unsigned)n_arrays), dim3(256), 0, (hipStream_t)stream, P);
+    HIP_TRY(ctx, hipGetLastError());
+    return 0;
+}
+
+// Rows of written slots gathered into a new loop's buffers.  ctx is the NEW loop's context; B, n_slots and
+// n_obs describe the slabs.  HOST arrays: written [n_slots], ego, slot [n_rows], slab, dst, row_bytes [n_fields] (DEVICE pointers
+// and sizes), veh_src, veh_slot [n_veh].  DEVICE: what slab[i] and dst[i] point to, obs_slab, obs_state.  Two launches on `stream`.
+extern "C" int jsim_loop_checkpoint_load(jsim_ctx *ctx, int32_t B, int32_t n_slots, const int32_t *written, int32_t n_rows, const int32_t *ego,
+                                         const int32_t *slot, int32_t n_fields, const void *const *slab, void *const *dst,
+                                         const int64_t *row_bytes, int32_t n_obs, const double *obs_slab, int32_t n_veh,
+                                         const int32_t *veh_src, const int32_t *veh_slot, double *obs_state, void *stream)
+{
+    const char *const F = "jsim_loop_checkpoint_load";
+    if (B < 0 || n_slots < 0 || n_rows < 0 || n_obs < 0 || n_veh < 0 || n_fields < 0 || n_fields > JSIM_CKPT_MAX_ARRAYS)
+        return fail(ctx, -22, "%s: B=%d n_slots=%d n_rows=%d n_fields=%d (max %d) n_obs=%d n_veh=%d", F, B, n_slots, n_rows, n_fields,
+                    JSIM_CKPT_MAX_ARRAYS, n_obs, n_veh);
+    if ((n_slots > 0 && !written) || (n_rows > 0 && (!ego || !slot)) || (n_fields > 0 && (!slab || !dst || !row_bytes)) ||
+        (n_veh > 0 && (!veh_src || !veh_slot || !obs_slab || !obs_state)))
+        return fail(ctx, -22, "%s: null pointer", F);
+    for (int i = 0; i < n_fields; ++i) {
+        if (!slab[i] || !dst[i]) return fail(ctx, -22, "%s: field %d: null pointer", F, i);
+        if (row_bytes[i] <= 0 || (row_bytes[i] & 3) || !ckpt_aligned(slab[i]) || !ckpt_aligned(dst[i]))
+            return fail(ctx, -22, "%s: field %d: row_bytes=%lld and both pointers must be multiples of 4", F, i, (long long)row_bytes[i]);
+    }
+    auto is_written = [&](int s) { return s >= 0 && s < n_slots && written[s] != 0; };
+    for (int r = 0; r < n_rows; ++r) {
+        if (ego[r] < 0 || ego[r] >= B) return fail(ctx, -22, "%s: row %d: ego=%d outside [0, B=%d)", F, r, ego[r], B);
+        if (!is_written(slot[r])) return fail(ctx, -22, "%s: row %d: slot=%d is not a written slot (n_slots=%d)", F, r, slot[r], n_slots);
+    }
+    for (int o = 0; o < n_veh; ++o) {
+        if (veh_src[o] < 0 || veh_src[o] >= n_obs) return fail(ctx, -22, "%s: vehicle %d: source=%d outside [0, n_obs=%d)", F, o, veh_src[o], n_obs);
+        if (!is_written(veh_slot[o])) return fail(ctx, -22, "%s: vehicle %d: slot=%d is not a written slot (n_slots=%d)", F, o, veh_slot[o], n_slots);
+    }
+    JSIM_RECORDER_CALL((n_rows == 0 || n_fields == 0) && n_veh == 0);
+    std::vector<int> rows((size_t)2 * n_rows + (size_t)2 * n_veh);
+    int *const h = rows.data();
+    std::copy(ego, ego + n_rows, h);
+    std::copy(slot, slot + n_rows, h + n_rows);
+    std::copy(veh_src, veh_src + n_veh, h + 2 * (size_t)n_rows);
+    std::copy(veh_slot, veh_slot + n_veh, h + 2 * (size_t)n_rows + n_veh);
+    if (int rc = replace_table(ctx, ctx->d_ckpt_rows, rows.data(), rows.size())) return rc;
+    const int *const d = ctx->d_ckpt_rows.p;
+    if (n_rows > 0 && n_fields > 0) {
+        CkptLoadP P;
+        memset(&P, 0, sizeof(P));
+        P.B = B; P.n_rows = n_rows; P.n_fields = n_fields; P.ego = d; P.slot = d + n_rows;
+        for (int i = 0; i < n_fields; ++i) P.f[i] = CkptField{(const char *)slab[i], (char *)dst[i], (long long)row_bytes[i]};
+        hipLaunchKernelGGL(checkpoint_load_kernel, dim3((unsigned)n_rows), dim3(64), 0, (hipStream_t)stream, P);
+    }
+    if (n_veh > 0) {
+        const CkptVehP V = {n_veh, n_obs, d + 2 * (size_t)n_rows, d + 2 * (size_t)n_rows + n_veh, obs_slab, obs_state};
+        hipLaunchKernelGGL(checkpoint_vehicles_kernel, dim3((unsigned)(((size_t)n_veh * 4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, V);
+    }
     HIP_TRY(ctx, hipGetLastError());
     return 0;
 }

@@ -1,6 +1,7 @@
 // The kernels of the plan record as a translation unit of their own: plan_record_kernel and
 // plan_prediction_score_kernel get a code object of their own, loaded when one of them is first launched, and the library's other
-// code objects are what they were before these kernels existed.  jsim_mpc.hip declares the two and launches them.
+// code objects are what they were before these kernels existed.  jsim_mpc.hip declares the two and launches them.  The checkpoint
+// kernels (checkpoint.inc) live here for the same reason.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -14,3 +15,4 @@
 
 #define JSIM_PLAN_TU 1
 #include "plan_predictions.inc"
+#include "checkpoint.inc"    // the checkpoint kernels: beside the plan record's, for the same reason

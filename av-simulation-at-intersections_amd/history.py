@@ -9,7 +9,8 @@ collision cut-off of every tick (section 21); fork_rows, join and reasons_carry_
 gap_episodes for the time gap between an ego and each vehicle (section 23); path_table and tracking_episodes for the projection of
 every recorded pose onto a path (section 24); headway_episodes for the space headway, time headway and time to collision between
 an ego and the vehicles on its path (section 25); prediction_curve and prediction_places for the error of every recorded prediction
-against what the vehicle then did (section 28)."""
+against what the vehicle then did (section 28); CHECKPOINT, checkpoint_cuts, checkpoint_at and the checkpoint file are the host
+side of a loop's checkpoints (section 30)."""
 from __future__ import annotations
 
 from typing import List, NamedTuple, Optional
@@ -93,6 +94,123 @@ PREDICTION_OUTPUTS = RowOutputs("jsim_loop_score_predictions",
 # in the order of the declaration; "T" is the engine's horizon.  Slot k holds eng.oa, eng.od, eng.status at the start of tick k.
 # jsim_loop_score_plan_predictions scores them into PREDICTION_OUTPUTS' columns, rows = the egos.
 PLAN_RECORD = (("plan_oa", _F, ("T",)), ("plan_od", _F, ("T",)), ("plan_status", _I, ()))
+
+
+class CheckpointArray(NamedTuple):
+    """One array of a loop's live state: its slab is [n_slots] + shape of dtype (`B`, `T`, `n_obs` are the loop's); the live tensor is
+    attribute `attr` of the loop's `owner` -- "loop" (ClosedLoop), "eng" (BatchedMPC), "pre" (PreTick), "obst" (ScriptedObstacles).
+    per: whose rows the leading axis counts -- "ego" (a fork gathers them row by row), "vehicle" (gathered per (source set, slot)) or
+    "loop" (one value for the whole loop: restored, never gathered; a fork starts its own)."""
+    name: str
+    dtype: type
+    shape: tuple
+    owner: str
+    attr: str
+    per: str
+
+
+_L = np.int64
+# The checkpoint record (jsim_loop_checkpoint_save / _load, DESIGN.md section 30): every buffer that a tick writes and a later tick
+# reads -- from the argument lists of the entry points (_loop_args, _run_args, _advance_args), run_host_ticks and the stores of the
+# kernels they launch.  Slot s holds them as they stand at the start of the slot's tick.  An array whose owner the loop does not have
+# (a ClosedLoop has no glue) or whose tensor is None (cv_cut without the speed cut-off glue) or empty (no vehicles) has no slab.
+# Not state: the step outputs (ox, oy, ov, oyaw, xref, active_mask, n_iter), hist, col_xy / first_idx / get_buf (written, never read
+# by a tick) and x0_first (the recorder's, written once).
+CHECKPOINT = (
+    CheckpointArray("x0", _F, ("B", 4), "loop", "x0", "ego"),
+    CheckpointArray("x0_spawn", _F, ("B", 4), "loop", "x0_spawn", "ego"),
+    CheckpointArray("target_spawn", _L, ("B",), "loop", "target_spawn", "ego"),
+    CheckpointArray("age", _I, ("B",), "loop", "age", "ego"),
+    CheckpointArray("tick_counter", _I, (1,), "loop", "tick_counter", "loop"),
+    CheckpointArray("n_respawn", _L, (1,), "loop", "n_respawn", "loop"),
+    CheckpointArray("target_ind", _L, ("B",), "eng", "target_ind", "ego"),
+    CheckpointArray("oa", _F, ("B", "T"), "eng", "oa", "ego"),
+    CheckpointArray("od", _F, ("B", "T"), "eng", "od", "ego"),
+    CheckpointArray("di_ai", _F, ("B", 2), "eng", "di_ai", "ego"),
+    CheckpointArray("status", _I, ("B",), "eng", "status", "ego"),
+    CheckpointArray("path_len", _I, ("B",), "eng", "path_len", "ego"),
+    CheckpointArray("cv_cut", _I, ("B",), "eng", "cv_cut", "ego"),
+    CheckpointArray("traj_idx", _L, ("B",), "pre", "traj_idx", "ego"),
+    CheckpointArray("prev_len", _I, ("B",), "pre", "prev_len", "ego"),
+    CheckpointArray("col_flag", _I, ("B",), "pre", "col_flag", "ego"),
+    CheckpointArray("pre_status", _I, ("B",), "pre", "status", "ego"),
+    CheckpointArray("obs_state", _F, ("n_obs", 4), "obst", "state", "vehicle"),
+)
+CHECKPOINT_MAX_ARRAYS = 32     # JSIM_CKPT_MAX_ARRAYS of include/jsim_mpc.h
+CHECKPOINT_META = ("_names", "_every", "_cap", "_slot_tick", "_kind")   # what a checkpoint file holds beside the slabs
+
+
+def checkpoint_slots(every: int, cap: int) -> int:
+    """n_slots of a loop that records cap ticks and checkpoints every `every`: the ticks 0, every, .. <= cap."""
+    return int(cap) // int(every) + 1
+
+
+def checkpoint_cuts(t0: int, n: int, every: int, cap: int):
+    """How run(n) of a loop that stands at tick t0 issues its entry point: a list of (slot, ticks) pieces, in
+    order -- `slot` is saved ahead of the piece's ticks (-1: nothing is).  A piece ends at the next multiple of `every`; tick t is
+    saved to slot t // every when t is such a multiple and t <= cap (ticks beyond cap save nothing, and are not cut).  The ticks of
+    the pieces add up to n; n = 0 gives no piece."""
+    t0, n, every, cap = int(t0), int(n), int(every), int(cap)
+    if t0 < 0 or n < 0 or every < 1 or cap < 0:
+        raise ValueError(f"checkpoint_cuts needs t0 >= 0, n >= 0, every >= 1, cap >= 0, got {t0}, {n}, {every}, {cap}")
+    out, t, end = [], t0, t0 + n
+    while t < end:
+        nxt = (t // every + 1) * every                     # the next tick that could be saved
+        stop = min(end, nxt) if nxt <= cap else end
+        out.append((t // every if (t % every == 0 and t <= cap) else -1, stop - t))
+        t = stop
+    return out
+
+
+def checkpoint_at(slot_tick, at):
+    """The slot of every tick in `at` among the written slots of a loop (slot_tick [n_slots]: the tick each slot holds, -1: not
+    written; of two slots with one tick the lower).  ValueError: a tick that is not checkpointed, naming the nearest checkpointed
+    ticks on either side."""
+    st = np.asarray(slot_tick).reshape(-1)
+    have = np.unique(st[st >= 0])
+    out = np.empty(np.size(at), dtype=np.int32)
+    for r, k in enumerate(np.asarray(at).reshape(-1).tolist()):
+        hit = np.flatnonzero(st == k)
+        if k < 0 or hit.size == 0:
+            below, above = have[have < k], have[have > k]
+            near = " and ".join(str(int(v)) for v in ([below[-1]] if below.size else []) + ([above[0]] if above.size else []))
+            raise ValueError(f"row {r}: tick {k} is not checkpointed (the nearest checkpointed ticks: {near or 'none'})")
+        out[r] = hit[0]
+    return out
+
+
+def checkpoint_file(slabs: dict, every: int, cap: int, slot_tick, kind: str) -> dict:
+    """What loop.save_checkpoints writes with numpy.savez: the slabs under their CHECKPOINT names and CHECKPOINT_META -- the names in
+    CHECKPOINT's order, `every`, `cap`, the tick every slot holds (-1: not written) and the loop's class name."""
+    names = [a.name for a in CHECKPOINT if a.name in slabs]
+    if set(names) != set(slabs):
+        raise ValueError(f"slabs that are not in history.CHECKPOINT: {sorted(set(slabs) - set(names))}")
+    d = {k: np.ascontiguousarray(slabs[k]) for k in names}
+    d.update(_names=np.array(names), _every=np.int64(every), _cap=np.int64(cap), _slot_tick=np.asarray(slot_tick, dtype=np.int64),
+             _kind=np.array(kind))
+    return d
+
+
+def read_checkpoint_file(path):
+    """(slabs, meta) of a file written by loop.save_checkpoints: the slabs as numpy arrays by name, in the file's order, and meta =
+    dict(every, cap, slot_tick, kind).  ValueError: a file without the layout names, a name CHECKPOINT does not know, a slab of
+    another dtype or with another number of slots than slot_tick."""
+    known = {a.name: a for a in CHECKPOINT}
+    with np.load(path, allow_pickle=False) as z:
+        if any(k not in z.files for k in CHECKPOINT_META):
+            raise ValueError(f"{path}: not a checkpoint file (it lacks {[k for k in CHECKPOINT_META if k not in z.files]})")
+        names = [str(v) for v in z["_names"]]
+        st = z["_slot_tick"].astype(np.int64)
+        slabs = {}
+        for k in names:
+            if k not in known or k not in z.files:
+                raise ValueError(f"{path}: array {k!r} is not in history.CHECKPOINT, or missing from the file")
+            a = z[k]
+            if a.dtype != np.dtype(known[k].dtype) or a.shape[0] != st.size or a.ndim != 1 + len(known[k].shape):
+                raise ValueError(f"{path}: array {k!r} is {a.dtype} {a.shape}; expected {np.dtype(known[k].dtype)} [{st.size}]{known[k].shape}")
+            slabs[k] = a
+        meta = {"every": int(z["_every"]), "cap": int(z["_cap"]), "slot_tick": st, "kind": str(z["_kind"])}
+    return slabs, meta
 
 
 class History:

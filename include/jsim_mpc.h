@@ -855,6 +855,38 @@ int jsim_loop_eval_cutoffs_plan(jsim_ctx *ctx, int32_t B, int32_t n_ticks, const
                                 int32_t *carry, int32_t *status, int32_t *idx, int32_t *cut, int32_t *hit, int32_t *first, double *col_xy,
                                 const double *plan_oa, const double *plan_od, const int32_t *plan_status, void *stream);
 
+/* ---- checkpoints of a running loop: rewind it, continue it elsewhere, fork it warm ----
+ * All live state of a loop sits in caller-owned DEVICE arrays; the context holds tables only.  A checkpoint is a copy of those arrays
+ * (the caller's list: closed_loop.py states it in history.CHECKPOINT) into slot s of caller-owned slabs [n_slots]..., taken between
+ * two calls of a loop entry point; no loop kernel knows of it.
+ *
+ * jsim_loop_checkpoint_save: n_arrays copies, bytes[i] bytes from src[i] to dst[i], in ONE launch on `stream` (plain vector stores, 16
+ *   bytes a thread where the pointers and the size allow it).  Saving slot s: src[i] = the live array, dst[i] = slab i + s * its slot
+ *   size; restoring it: the same call with src and dst exchanged.  The table travels in the kernel's arguments: the call neither
+ *   allocates nor synchronises, so it may stand between two fused launches on one stream.
+ *   HOST arrays src, dst [n_arrays] of DEVICE pointers and bytes [n_arrays].
+ *   Refused (-22) before any device call: n_arrays outside [0, JSIM_CKPT_MAX_ARRAYS]; with n_arrays > 0 a null array or a null entry;
+ *   a bytes[i] that is negative or no multiple of 4; a pointer that is not 4-byte aligned; a null ctx.  n_arrays = 0 returns 0.
+ *
+ * jsim_loop_checkpoint_load: rows of written slots gathered into the arrays of a NEW loop (ctx is the new loop's).  Destination row
+ *   r takes ego ego[r] of slot slot[r]: for every field i, row_bytes[i] bytes from slab[i] + (slot[r] * B + ego[r]) * row_bytes[i] to
+ *   dst[i] + r * row_bytes[i].  One wavefront per row, the lanes side by side over the row's 4-byte words (the T doubles of oa and od:
+ *   2 T lanes; a scalar: lane 0).  A second grid copies the scripted vehicles: destination vehicle o takes the 4 doubles (xc, yc,
+ *   theta, counter) of vehicle veh_src[o] of slot veh_slot[o] from obs_slab [n_slots][n_obs][4] to obs_state [n_veh][4].  One ego and
+ *   one vehicle may stand in any number of rows.  B and n_obs are the SOURCE loop's.
+ *   HOST arrays: written [n_slots] (nonzero: the slot holds a checkpoint), ego, slot [n_rows], slab, dst [n_fields] (DEVICE
+ *   pointers), row_bytes [n_fields], veh_src, veh_slot [n_veh].  DEVICE: the slabs, the destinations, obs_slab, obs_state.
+ *   Refused (-22) before any device call: a negative size; n_fields > JSIM_CKPT_MAX_ARRAYS; a null pointer that a positive size
+ *   needs; an ego outside [0, B); a slot or veh_slot outside [0, n_slots) or not written; a veh_src outside [0, n_obs); a row_bytes
+ *   that is not a positive multiple of 4, a slab or dst that is not 4-byte aligned; a null ctx.  Nothing to copy returns 0. */
+enum { JSIM_CKPT_MAX_ARRAYS = 32 };
+int jsim_loop_checkpoint_save(jsim_ctx *ctx, int32_t n_arrays, const void *const *src, void *const *dst, const int64_t *bytes,
+                              void *stream);
+int jsim_loop_checkpoint_load(jsim_ctx *ctx, int32_t B, int32_t n_slots, const int32_t *written, int32_t n_rows, const int32_t *ego,
+                              const int32_t *slot, int32_t n_fields, const void *const *slab, void *const *dst, const int64_t *row_bytes,
+                              int32_t n_obs, const double *obs_slab, int32_t n_veh, const int32_t *veh_src, const int32_t *veh_slot,
+                              double *obs_state, void *stream);
+
 /* ---- the job's one exchange: the final trajectory gather over RCCL / xGMI ----
  * The reference has no multi-process code at all (its only multi-ego code is the serial Python loop of
  * main/scenarios/interactive_mpc.py:119-172); egos are independent (main/lib/mpc.py:141-211), so ranks own contiguous shards
