@@ -142,7 +142,15 @@ int jsim_mpc_update_cfg(jsim_ctx *ctx, const jsim_cfg *cfg);
 
 /* Per-ego weights and limits: a whole sensitivity sweep (main/scenarios/mpc_sensitivity_analysis*.py run the loop once per
  * parameter set, rewriting config/mpc_config_sensitivity.json in between) as ONE batch -- ego b solves with its own row of
- * cfg, a caller-owned DEVICE array [B][JSIM_EGO_CFG_DOUBLES] in the JSON's own units:
+ * cfg, a caller-owned DEVICE array [B][JSIM_EGO_CFG_DOUBLES] in the JSON's own units.
+ * PRECONDITION: R[0] > 0 and R[1] > 0 in every row, as jsim_mpc_create / jsim_mpc_update_cfg demand of the context's R.  The
+ *   kernels factor H = L L' without a status and rely on H >= 2 min(R) I; the table lives on the device and is NOT checked.  The
+ *   study's own sweeps contain R entries of 0 (at a standstill a zero steering weight leaves H singular; DESIGN.md section 4,
+ *   "Conditioning").  What a row with an R entry of 0 gets: a pivot that is not positive is replaced by 1e-300, every loop stays
+ *   bounded, the status is 0 or 1 -- the same on every kernel of a horizon -- and a status-0 answer is optimal in value
+ *   (tests/test_gpu_conditioning.py); along a direction that costs nothing the answer is not unique, and a status of 1 makes the
+ *   ego brake like any failed solve.  A caller who wants a unique answer keeps R > 0 (1e-8 is enough for cond(H) <= 1e13 up to T = 40).
+ * The row:
  *   { w_perp, w_para, R[0], R[1], Rd[0], Rd[1], Q_v_yaw[0], Q_v_yaw[1], Qf[0..3] (unscaled; x T inside, mpc.py:28),
  *     MAX_DSTEER [rad/s], MAX_ACCEL, MAX_DECEL, reserved }.
  * Everything else (T, dt, dl, L, R_end, speed limits, goal test) stays with the context's jsim_cfg.  NULL switches back. */

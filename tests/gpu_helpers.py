@@ -274,6 +274,39 @@ def n_active(mask):
     return np.unpackbits(np.ascontiguousarray(mask).view(np.uint8), axis=1).sum(axis=1)
 
 
+def qp_constraints(T, dt, v0, speed, cfgs, min_speed, max_steer, jerk=False):
+    """(G [8T, 2T], h [B, 8T]) of the condensed QP's G u <= h in the canonical row order (include/jsim_mpc.h), u = (a_0, delta_0,
+    a_1, ...): G rows from the structure, h from each ego's start speed v0[b], speed limit speed[b] and limits cfgs[b].  The two
+    t = 0 speed rows are constants (zero rows of G).
+    jerk: the acceleration-state variant (main/lib/mpc_jerk.py), u = (u0_0, delta_0, ..., u0_{T-1}, delta_{T-1}, acc_0), G [8T, 2T + 1]:
+    the speed responds to the effective accelerations a~_s = acc_0 + u0_s + dt sum_{r<s} u0_r, v_t = v_0 + dt sum_{s<t} a~_s; the
+    acceleration rows bound u0_t itself (mpc_jerk.py keeps `u[0, :]` in those constraints)."""
+    B, n, m = len(cfgs), 2 * T + (1 if jerk else 0), 8 * T
+    G = np.zeros((m, n))
+    for t in range(T - 1):
+        G[2 * t, 2 * t + 3] = 1; G[2 * t, 2 * t + 1] = -1; G[2 * t + 1] = -G[2 * t]
+    for t in range(T + 1):
+        G[2 * T - 2 + t, 0:2 * t:2] = dt
+        if jerk:
+            G[2 * T - 2 + t, 2 * T] = dt * t
+            for r in range(t - 1):
+                G[2 * T - 2 + t, 2 * r] += dt * dt * (t - 1 - r)
+        G[3 * T - 1 + t] = -G[2 * T - 2 + t]
+    for t in range(T):
+        G[4 * T + t, 2 * t] = 1; G[5 * T + t, 2 * t] = -1
+        G[6 * T + 2 * t, 2 * t + 1] = 1; G[6 * T + 2 * t + 1, 2 * t + 1] = -1
+    col = lambda f: np.array([f(e) for e in cfgs], dtype=np.float64)[:, None]
+    v0, speed = np.asarray(v0, dtype=np.float64), np.asarray(speed, dtype=np.float64)
+    h = np.zeros((B, m))
+    h[:, :2 * T - 2] = col(lambda e: e.max_dsteer_rad * dt)
+    h[:, 2 * T - 2:3 * T - 1] = (speed - v0)[:, None]
+    h[:, 3 * T - 1:4 * T] = (v0 - min_speed)[:, None]
+    h[:, 4 * T:5 * T] = col(lambda e: e.MAX_ACCEL)
+    h[:, 5 * T:6 * T] = col(lambda e: -e.MAX_DECEL)
+    h[:, 6 * T:] = max_steer
+    return G, h
+
+
 def kkt_check(eng, batch, dbg, cfgs=None):
     """Size-independent property: the u* the kernel returned satisfies the KKT conditions of the condensed QP the kernel built
     (strictly convex => that IS the optimum), multipliers >= 0, complementary, active bits <=> positive multipliers.
@@ -285,27 +318,10 @@ def kkt_check(eng, batch, dbg, cfgs=None):
     u = torch.stack([eng.oa, eng.od], dim=2).reshape(B, 2 * T)
     lam = dbg["lam"]
     n, m = 2 * T, 8 * T
-    # G rows from the structure (canonical order), built once
-    G = torch.zeros(m, n, dtype=torch.float64, device=eng.device)
-    for t in range(T - 1):
-        G[2 * t, 2 * t + 3] = 1; G[2 * t, 2 * t + 1] = -1; G[2 * t + 1] = -G[2 * t]
-    for t in range(T + 1):
-        G[2 * T - 2 + t, 0:2 * t:2] = eng.dt
-        G[3 * T - 1 + t] = -G[2 * T - 2 + t]
-    for t in range(T):
-        G[4 * T + t, 2 * t] = 1; G[5 * T + t, 2 * t] = -1
-        G[6 * T + 2 * t, 2 * t + 1] = 1; G[6 * T + 2 * t + 1, 2 * t + 1] = -1
     c = eng.config
     per = [c] * B if cfgs is None else cfgs
-    col = lambda f: torch.tensor([f(e) for e in per], dtype=torch.float64, device=eng.device)[:, None]
-    h = torch.zeros(B, m, dtype=torch.float64, device=eng.device)
-    x0 = torch.from_numpy(batch.x0).to(eng.device)
-    h[:, :2 * T - 2] = col(lambda e: e.max_dsteer_rad * eng.dt)
-    h[:, 2 * T - 2:3 * T - 1] = (eng.speed - x0[:, 2])[:, None]
-    h[:, 3 * T - 1:4 * T] = (x0[:, 2] - c.MIN_SPEED)[:, None]
-    h[:, 4 * T:5 * T] = col(lambda e: e.MAX_ACCEL)
-    h[:, 5 * T:6 * T] = col(lambda e: -e.MAX_DECEL)
-    h[:, 6 * T:] = c.MAX_STEER_RAD
+    Gn, hn = qp_constraints(T, eng.dt, batch.x0[:, 2], eng.speed.cpu().numpy(), per, c.MIN_SPEED, c.MAX_STEER_RAD)
+    G, h = torch.from_numpy(Gn).to(eng.device), torch.from_numpy(hn).to(eng.device)
     stat = torch.einsum("bij,bj->bi", H, u) + dbg["g"] + lam @ G
     scale = dbg["g"].abs().amax(dim=1).clamp(min=1.0)
     assert float((stat.abs().amax(dim=1) / scale)[ok].max()) <= 1e-8
