@@ -2965,7 +2965,9 @@ static int launch_fused(jsim_ctx *ctx, int B, int n_ticks, const StepBufs &S, co
 {
     const jsim_cfg &c = ctx->cfg;
     KP P = fill_kp(ctx, B, S);
+#ifndef JSIM_STAMPS /* (a stamped build keeps its clock rows in the fused launch: they then hold the launch's last tick) */
     P.dbg_clk = nullptr;
+#endif
     TickP K;
     memset(&K, 0, sizeof(K));
     K.n_ticks = n_ticks; K.advance = 1; K.max_age = A.max_age > 0 ? A.max_age : 0x7fffffff; K.hist_cap = A.hist_cap;

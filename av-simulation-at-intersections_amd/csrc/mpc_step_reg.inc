@@ -322,7 +322,33 @@ struct PreK {
 // The active-set loop is one dependent chain per iteration and stays with the owner; the helpers sleep at a barrier.  Protocol: the owner posts a command (hb_cmd) and passes a barrier, works, passes a second barrier;
 // the helpers loop { barrier; read command; work; barrier }.  Three such pairs per tick, flushed with HB_SKIP on the owner's early
 // exits, HB_EXIT after the last tick.
-enum { HB_SKIP = 0, HB_SCAN = 1, HB_HBUILD = 2, HB_JBUILD = 3, HB_EXIT = 4 };
+//   * the tick boundary (NB: the glue-free kernels, DESIGN.md section 6): once the new solution stands in LDS (the top of S5) nothing of
+//     the next tick's head needs the owner any more.  HB_NEXT opens a fourth pair there, which takes the place of the next tick's
+//     HB_SCAN pair: helper 1 steps the plant, rolls the new warm start out (S2) and linearises about it (the part of S3 that needs
+//     neither the nearest index nor the reference window), helpers 2 and 3 scan from the new position -- under the owner's outputs and
+//     plant / goal / respawn tail.  The pair closes at the top of the next tick; a tick that respawned the ego throws the results away.
+enum { HB_SKIP = 0, HB_SCAN = 1, HB_HBUILD = 2, HB_JBUILD = 3, HB_EXIT = 4, HB_NEXT = 5 };
+
+// tan of the clamped steer: what the rollout S2 and the plant step turn with
+__device__ __forceinline__ double jsim_clamped_tan(double d, double smax)
+{
+    double dc = (smax < d) ? smax : d;
+    dc = (-smax > dc) ? -smax : dc;
+    return tan(dc);
+}
+// Simulation.step (main/lib/simulation.py:35-47).  cy, sy: cos / sin of the yaw; tn: tan of the clamped steer.  Only the yaw needs tn,
+// and nothing else needs the yaw: a caller that wants part of the new state passes anything for the rest and drops those results.
+// (What HB_NEXT's two waves step with; the tick's tail keeps the same operations in its own text.)
+template <class KPT> // (KP, defined by the including file; read where the text reads it)
+__device__ __forceinline__ void jsim_plant_step(double &x, double &y, double &v, double &yaw, double cy, double sy, double tn, double ai, const KPT &P,
+                                                double dt)
+{
+    const double xd = v * cy, yd = v * sy, thd = (v / P.L) * tn;
+    x += xd * dt; y += yd * dt; yaw += thd * dt;
+    v += ai * dt;
+    v = (P.vmax_plant < v) ? P.vmax_plant : v;
+    v = (P.vmin > v) ? P.vmin : v;
+}
 
 // A helper waits until a column of the factor is published: 1 / sqrt(pivot) of column k, invc[k], is set to -1 before the
 // factorisation starts and written (never negative, whatever the pivot: the high word of -1.0 cannot come back) when column k and
@@ -514,6 +540,18 @@ void mpc_step_reg_kernel(const KP Pin, const TickP K, const PreK Q)
     __shared__ long long hb_s0;
     __shared__ double hb_xy[2], hb_rd[HELP ? 12 : 2];
     __shared__ int hb_ri[HELP ? 12 : 2];
+    // NB: the tick boundary's hand-over (HB_NEXT).  Mailbox hb_st: the new speed, then the speed and yaw the step started from (the new
+    // position goes in hb_xy).  Helper 1's own: nbz S2's scratch; nbv lane-wise al, be, alp, bep, ccx, ccy, kt, FX, FY (64 each); nbs
+    // lane 0's sin and cos of the new yaw (the next plant step's); nbq (VS) the table rows it cannot write in place.
+    constexpr bool NB = HELP && !PRE;
+    __shared__ double hb_st[NB ? 3 : 1];
+    __shared__ __attribute__((aligned(16))) double nbz[NB ? 4 * T : 2];
+    __shared__ __attribute__((aligned(16))) double nbv[NB ? 9 * 64 : 2];
+    __shared__ double nbs[2];
+#ifdef JSIM_STAMPS
+    __shared__ int hb_nclk; // (not a length: helper 1's cycles in HB_NEXT, for the owner's clock row)
+#endif
+    __shared__ __attribute__((aligned(16))) double nbq[(NB && VS) ? TQN : 2];
 
     const int lane0 = HELP ? (int)(threadIdx.x & 63) : (int)threadIdx.x;
     const int hwave = HELP ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : 0;
@@ -558,12 +596,9 @@ void mpc_step_reg_kernel(const KP Pin, const TickP K, const PreK Q)
             __syncthreads();
             const int cmd = __builtin_amdgcn_readfirstlane(hb_cmd);
             if (cmd == HB_EXIT) return;
-            if (cmd == HB_SCAN) {
-                const double hx = hb_xy[0], hy = hb_xy[1];
-                const int ilen = hb_ilen;
-                const double2 *pp = P.pxy + off + hb_s0;
-                double b0 = INFINITY, b1 = INFINITY, b2 = INFINITY;
-                int i0 = 0x7fffffff, i1 = 0x7fffffff, i2 = 0x7fffffff;
+            // A helper's share of the nearest-index scan: wave W_ of ST_ / 64 takes the points 64 W_ + lane, + ST_, ..; its three nearest
+            // (nearest first, ties to the smaller index) go to slots 3 (hwave - 1) .. of hb_rd / hb_ri.  The owner's merge does not
+            // depend on how the points were dealt.
 #define HB_INSERT_PT(p_, k_)                                                                   \
     {                                                                                          \
         const double dx = (p_).x - hx, dy = (p_).y - hy;                                       \
@@ -572,24 +607,78 @@ void mpc_step_reg_kernel(const KP Pin, const TickP K, const PreK Q)
         else if (d < b1) { b2 = b1; i2 = i1; b1 = d; i1 = (k_); }                              \
         else if (d < b2) { b2 = d; i2 = (k_); }                                                \
     }
-                int k = (hwave - 1) * 64 + lane0;
-                for (; k + 576 < ilen; k += 768) {
-                    const double2 p0 = pp[k], p1 = pp[k + 192], p2 = pp[k + 384], p3 = pp[k + 576];
-                    HB_INSERT_PT(p0, k) HB_INSERT_PT(p1, k + 192) HB_INSERT_PT(p2, k + 384) HB_INSERT_PT(p3, k + 576)
+#define HB_SCAN_WAVE(ST_, W_)                                                                                          \
+    {                                                                                                                  \
+        const double hx = hb_xy[0], hy = hb_xy[1];                                                                     \
+        const int ilen = hb_ilen;                                                                                      \
+        const double2 *pp = P.pxy + off + hb_s0;                                                                       \
+        double b0 = INFINITY, b1 = INFINITY, b2 = INFINITY;                                                            \
+        int i0 = 0x7fffffff, i1 = 0x7fffffff, i2 = 0x7fffffff;                                                         \
+        int k = (W_) * 64 + lane0;                                                                                     \
+        for (; k + 3 * (ST_) < ilen; k += 4 * (ST_)) {                                                                 \
+            const double2 p0 = pp[k], p1 = pp[k + (ST_)], p2 = pp[k + 2 * (ST_)], p3 = pp[k + 3 * (ST_)];              \
+            HB_INSERT_PT(p0, k) HB_INSERT_PT(p1, k + (ST_)) HB_INSERT_PT(p2, k + 2 * (ST_)) HB_INSERT_PT(p3, k + 3 * (ST_)) \
+        }                                                                                                              \
+        for (; k < ilen; k += (ST_)) {                                                                                 \
+            const double2 p0 = pp[k];                                                                                  \
+            HB_INSERT_PT(p0, k)                                                                                        \
+        }                                                                                                              \
+        _Pragma("unroll") for (int r = 0; r < 3; ++r) {                                                                \
+            double v = b0;                                                                                             \
+            int id = i0;                                                                                               \
+            wargmin_fast(v, id);                                                                                       \
+            if (lane0 == 0) { hb_rd[(hwave - 1) * 3 + r] = v; hb_ri[(hwave - 1) * 3 + r] = id; }                       \
+            if (i0 == id) { b0 = b1; i0 = i1; b1 = b2; i1 = i2; b2 = INFINITY; i2 = 0x7fffffff; }                      \
+        }                                                                                                              \
+    }
+            if (cmd == HB_SCAN) {
+                HB_SCAN_WAVE(192, hwave - 1)
+            } else if (NB && cmd == HB_NEXT) {
+                if (hwave == 1) {
+#ifdef JSIM_STAMPS
+                    const long long ht0 = (long long)__builtin_readcyclecounter();
+#endif
+                    // the next tick's state, rollout and index-free linearisation -- the owner's own texts on the owner's operands
+                    const int lane = lane0; // (the shared texts say `lane`)
+                    double wa_t = 0.0, wd_t = 0.0;
+                    if (tl) { wa_t = uvec[2 * lane]; wd_t = uvec[2 * lane + 1]; }
+                    const double wtan = jsim_clamped_tan(wd_t, P.smax);
+                    const double sx = hb_xy[0], sy = hb_xy[1], sv = hb_st[0];
+                    double syaw = hb_st[NB ? 2 : 0];
+                    {
+                        double x_ = 0.0, y_ = 0.0, v_ = hb_st[NB ? 1 : 0]; // (the owner posted the new position and speed)
+                        jsim_plant_step(x_, y_, v_, syaw, 0.0, 0.0, rdlane(wtan, 0), 0.0, P, dt);
+                    }
+                    double bx = sx, by = sy, bv = sv, bth = syaw, sn, cs;
+                    {
+#define JSIM_S2_SCR nbz
+#include "mpc_step_reg_s2.inc"
+#undef JSIM_S2_SCR
+                    }
+                    double al = 0, be = 0, alp = 0, bep = 0, ccx = 0, ccy = 0, kt = 0;
+                    double PA, PB, PAP, PBP, FX, FY;
+                    {
+#include "mpc_step_reg_s3a.inc"
+                    }
+                    double *const rows = VS ? nbq : tq; // (VS: the solution the owner is still reading lies in the table's place)
+                    if (lane <= T + 1) {
+                        rows[TQ_PA * TP + lane] = PA; rows[TQ_PB * TP + lane] = PB; rows[TQ_PAP * TP + lane] = PAP; rows[TQ_PBP * TP + lane] = PBP;
+                        rows[TQ_KT * TP + lane] = kt;
+                    }
+                    nbv[0 * 64 + lane] = al; nbv[1 * 64 + lane] = be; nbv[2 * 64 + lane] = alp; nbv[3 * 64 + lane] = bep;
+                    nbv[4 * 64 + lane] = ccx; nbv[5 * 64 + lane] = ccy; nbv[6 * 64 + lane] = kt; nbv[7 * 64 + lane] = FX; nbv[8 * 64 + lane] = FY;
+                    if (lane == 0) { nbs[0] = sn; nbs[1] = cs; }
+                    if (lane < 3) { hb_rd[lane] = INFINITY; hb_ri[lane] = 0x7fffffff; } // (no scan of this wave's: the merge takes nine)
+                    (void)bx; (void)by;
+#ifdef JSIM_STAMPS
+                    __builtin_amdgcn_s_waitcnt(0);
+                    if (lane == 0) hb_nclk = (int)((long long)__builtin_readcyclecounter() - ht0);
+#endif
+                } else {
+                    HB_SCAN_WAVE(128, hwave - 2)
                 }
-                for (; k < ilen; k += 192) {
-                    const double2 p0 = pp[k];
-                    HB_INSERT_PT(p0, k)
-                }
+#undef HB_SCAN_WAVE
 #undef HB_INSERT_PT
-#pragma unroll
-                for (int r = 0; r < 3; ++r) {
-                    double v = b0;
-                    int id = i0;
-                    wargmin_fast(v, id);
-                    if (lane0 == 0) { hb_rd[(hwave - 1) * 3 + r] = v; hb_ri[(hwave - 1) * 3 + r] = id; }
-                    if (i0 == id) { b0 = b1; i0 = i1; b1 = b2; i1 = i2; b2 = INFINITY; i2 = 0x7fffffff; }
-                }
             } else if (cmd == HB_HBUILD) {
                 if (hwave == 1 && NTILE > 1) jsim_h_tile_row<T, 1>(tq, Hm, lane0, dt);
                 else if (hwave == 2 && NTILE > 2) jsim_h_tile_row<T, 2>(tq, Hm, lane0, dt);
@@ -693,6 +782,7 @@ void mpc_step_reg_kernel(const KP Pin, const TickP K, const PreK Q)
         dc = (-P.smax > dc) ? -P.smax : dc;
         wtan = tan(dc);
     }
+    bool nb_pending = false, nb_valid = false; // NB: an HB_NEXT pair is open; its results describe the state the next tick starts from
     unsigned it_sum = 0; // active-set iterations of this launch's ticks, both S5 exits: added to K.work / K.iters once, in the last tick
     for (int tk = 0; tk < K.n_ticks; ++tk) {
     // WPE = 2 (256 registers): the state carried from tick to tick is the same in every lane -- say so, and it lives in scalar
@@ -731,9 +821,35 @@ void mpc_step_reg_kernel(const KP Pin, const TickP K, const PreK Q)
     // uniform values, not in vector registers that would live through the active-set loop
     double p_sn = 0.0, p_cs = 0.0;
     bool p_sc = false;     // S2 ran in this tick
+#ifdef JSIM_STAMPS /* slot 15 of the ego's clock row: four stretches of the path across the tick boundary, 16 bits each -- the rollout
+                      S2 on the owner (in a tick whose head the helpers ran: helper 1's whole HB_NEXT chain instead), S5's tan, the part
+                      of S3 that needs neither the index nor the reference window, the owner's wait at HB_NEXT's closing barrier */
+    long long xclk = 0, xt0 = 0;
+#define XSTAMP0() do { __builtin_amdgcn_sched_barrier(0); xt0 = (long long)__builtin_readcyclecounter(); __builtin_amdgcn_sched_barrier(0); } while (0)
+#define XSTAMP(k) do { __builtin_amdgcn_sched_barrier(0); xclk |= (((long long)__builtin_readcyclecounter() - xt0) & 0xffff) << (16 * (k)); __builtin_amdgcn_sched_barrier(0); } while (0)
+#define XSTAMP_USE(...) asm volatile("" :: __VA_ARGS__)
+#else
+#define XSTAMP0() do { } while (0)
+#define XSTAMP(k) do { } while (0)
+#define XSTAMP_USE(...) do { } while (0)
+#endif
     do {
     STAMP(0);
     double bx = sx, by = sy, bv = sv, bth = syaw, sn, cs;   // S2's results (declared here: HELP runs S2 inside S1)
+    // NB: the previous tick opened an HB_NEXT pair -- it closes here, in front of the merge.  Its results stand unless that tick's tail
+    // respawned the ego; then this tick runs whole, as the first tick of a launch does.
+    bool nb_use = false;
+    if constexpr (NB) if (nb_pending) {
+        XSTAMP0();
+        __syncthreads();
+        XSTAMP(3);
+#ifdef JSIM_STAMPS
+        xclk |= (long long)hb_nclk & 0xffff;
+#endif
+        nb_pending = false;
+        nb_use = nb_valid;
+        if (nb_use) { hp = 1; s2_done = true; sn = nbs[0]; cs = nbs[1]; }
+    }
     // ------------------------------------------------------------------ S1: nearest index in direction
     long long tind = s0;
     {
@@ -757,14 +873,23 @@ void mpc_step_reg_kernel(const KP Pin, const TickP K, const PreK Q)
             if (HELP) {
                 // the three helper wavefronts scan (each returns its three nearest points, nearest first); this one rolls out the
                 // warm start meanwhile and then merges the nine -- the same three points, in the same order, as one wave's scan finds
+                if constexpr (NB) { if (nb_use) goto s1_scanned; } // (scanned and rolled out under the previous tick's tail)
+                {
                 if (lane == 0) { hb_xy[0] = sx; hb_xy[1] = sy; hb_s0 = s0; hb_ilen = ilen; hb_cmd = HB_SCAN; }
                 __syncthreads();
+                XSTAMP0();
                 {
+#define JSIM_S2_SCR tq
 #include "mpc_step_reg_s2.inc"
+#undef JSIM_S2_SCR
                 }
+                XSTAMP_USE("v"(bv), "v"(bth), "v"(sn), "v"(cs));
+                XSTAMP(0);
                 s2_done = true;
                 LANE_FENCE();
                 __syncthreads();
+                }
+                s1_scanned:;
                 hp = 1;
                 if (lane < 9) { b0 = hb_rd[lane]; i0 = hb_ri[lane]; }
                 (void)pp;
@@ -847,7 +972,9 @@ void mpc_step_reg_kernel(const KP Pin, const TickP K, const PreK Q)
     LANE_FENCE();
     // ------------------------------------------------------------------ S2: rollout of the warm start
     if (!(HELP && s2_done)) {
+#define JSIM_S2_SCR tq
 #include "mpc_step_reg_s2.inc"
+#undef JSIM_S2_SCR
     }
     p_sn = rdlane(sn, 0); p_cs = rdlane(cs, 0); p_sc = true;
     if (P.dbg_xbar && lane <= T) {
@@ -877,20 +1004,27 @@ void mpc_step_reg_kernel(const KP Pin, const TickP K, const PreK Q)
     LANE_FENCE();
     // ------------------------------------------------------------------ S3: linearisation coefficients (lane t < T)
     double al = 0, be = 0, alp = 0, bep = 0, ccx = 0, ccy = 0, kt = 0;
-    if (tl) {
-        al = dt * cs;
-        be = (-dt * bv) * sn;
-        alp = dt * sn;
-        bep = (dt * bv) * cs;
-        ccx = ((dt * bv) * sn) * bth;
-        ccy = ((-dt * bv) * cs) * bth;
-        kt = (dt * bv) / P.L;
-    }
+    XSTAMP0();
     {
-        const double PA = wexscan_dpp(al, lane), PB = wexscan_dpp(be, lane);
-        const double PAP = wexscan_dpp(alp, lane), PBP = wexscan_dpp(bep, lane);
-        const double FX = sx + wexscan_dpp(fma(al, sv, fma(be, syaw, ccx)), lane);
-        const double FY = sy + wexscan_dpp(fma(alp, sv, fma(bep, syaw, ccy)), lane);
+        double PA, PB, PAP, PBP, FX, FY;
+        if constexpr (NB) { // (discarded elsewhere: nothing of the hand-over is instantiated in the other kernels)
+        if (nb_use) { // helper 1 ran this part under the previous tick's tail: its rows stand in the table, the rest comes over
+            al = nbv[0 * 64 + lane]; be = nbv[1 * 64 + lane]; alp = nbv[2 * 64 + lane]; bep = nbv[3 * 64 + lane];
+            ccx = nbv[4 * 64 + lane]; ccy = nbv[5 * 64 + lane]; kt = nbv[6 * 64 + lane]; FX = nbv[7 * 64 + lane]; FY = nbv[8 * 64 + lane];
+            if (VS && lane <= T + 1) {
+                tq[TQ_PA * TP + lane] = nbq[TQ_PA * TP + lane]; tq[TQ_PB * TP + lane] = nbq[TQ_PB * TP + lane];
+                tq[TQ_PAP * TP + lane] = nbq[TQ_PAP * TP + lane]; tq[TQ_PBP * TP + lane] = nbq[TQ_PBP * TP + lane];
+                tq[TQ_KT * TP + lane] = nbq[TQ_KT * TP + lane];
+            }
+            PA = PB = PAP = PBP = 0.0;
+        } else {
+#include "mpc_step_reg_s3a.inc"
+        }
+        } else {
+#include "mpc_step_reg_s3a.inc"
+        }
+        XSTAMP_USE("v"(PA), "v"(PB), "v"(PAP), "v"(PBP), "v"(FX), "v"(FY), "v"(kt));
+        XSTAMP(2);
         double Qxx = 0, Qxy = 0, Qyy = 0, qv = 0, qyaw = 0;
         if (lane >= 1 && lane <= T) {
             if (!rend) {
@@ -911,8 +1045,9 @@ void mpc_step_reg_kernel(const KP Pin, const TickP K, const PreK Q)
         if (lane <= T + 1) {
             const int t = lane;
             const bool in = lane <= T;
-            tq[TQ_PA * TP + t] = PA; tq[TQ_PB * TP + t] = PB; tq[TQ_PAP * TP + t] = PAP; tq[TQ_PBP * TP + t] = PBP;
-            tq[TQ_KT * TP + t] = kt;
+#define JSIM_S3_ROWS() do { tq[TQ_PA * TP + t] = PA; tq[TQ_PB * TP + t] = PB; tq[TQ_PAP * TP + t] = PAP; tq[TQ_PBP * TP + t] = PBP; tq[TQ_KT * TP + t] = kt; } while (0)
+            if constexpr (NB) { if (!nb_use) JSIM_S3_ROWS(); } else JSIM_S3_ROWS();
+#undef JSIM_S3_ROWS
             tq[TQ_QXX * TP + t] = in ? Qxx : 0; tq[TQ_QXY * TP + t] = in ? Qxy : 0; tq[TQ_QYY * TP + t] = in ? Qyy : 0;
             tq[TQ_QV * TP + t] = in ? qv : 0; tq[TQ_QYAW * TP + t] = in ? qyaw : 0;
             tq[TQ_QEX * TP + t] = in ? fma(Qxx, ex, Qxy * ey) : 0;
@@ -1712,6 +1847,19 @@ void mpc_step_reg_kernel(const KP Pin, const TickP K, const PreK Q)
         if (evl) uvec[N + (lane >> 1) + 1] = vsp;
         if (lane == 0) uvec[N] = sv;
     }
+    if constexpr (NB) if (K.advance && tk + 1 < K.n_ticks && P.pass == 0 && !P.dbg_xbar) {
+        // The new solution stands in LDS: the helpers start on the next tick (HB_NEXT) under the outputs and the tail below.  The
+        // position and speed the plant step will reach need no tan; the yaw does, and helper 1 steps it from what this tick started with.
+        double nx = sx, ny = sy, nv = sv, nyaw_ = syaw;
+        jsim_plant_step(nx, ny, nv, nyaw_, p_cs, syaw == 0.0 ? syaw : p_sn, 0.0, rdlane(val, 0), P, dt);
+        const long long nlen = M - tind;
+        if (lane == 0) {
+            hb_xy[0] = nx; hb_xy[1] = ny; hb_st[0] = nv; hb_st[NB ? 1 : 0] = sv; hb_st[NB ? 2 : 0] = syaw;
+            hb_s0 = tind; hb_ilen = nlen >= 3 ? (int)nlen : 0; hb_cmd = HB_NEXT;
+        }
+        __syncthreads();
+        nb_pending = true; nb_valid = true;
+    }
     if (P.dbg_lam)
         for (int e = lane; e < 8 * T; e += 64) P.dbg_lam[(size_t)ego * 8 * T + e] = 0.0;
     LDS_SYNC();
@@ -1740,7 +1888,11 @@ void mpc_step_reg_kernel(const KP Pin, const TickP K, const PreK Q)
         if (K.advance || tk + 1 < K.n_ticks) { // .. and its tan, for the plant step below (lane 0) and the next tick's S2
             double dc = (P.smax < dl_) ? P.smax : dl_;
             dc = (-P.smax > dc) ? -P.smax : dc;
+            XSTAMP_USE("v"(dc));
+            XSTAMP0();
             wtan = tan(dc);
+            XSTAMP_USE("v"(wtan));
+            XSTAMP(1);
         }
         a0n = uvec[0]; d0n = uvec[1];
         if (lane <= T) {
@@ -1758,6 +1910,9 @@ void mpc_step_reg_kernel(const KP Pin, const TickP K, const PreK Q)
     }
     it_sum += (unsigned)iters;
     STAMP(11);
+#ifdef JSIM_STAMPS
+    if (P.dbg_clk && lane == 0) P.dbg_clk[(size_t)ego * 16 + 15] = xclk;
+#endif
     } while (0);
     if (HELP) // an early exit left the helpers waiting for this tick's commands
         for (; hp < 3; ++hp) {
@@ -1793,6 +1948,7 @@ void mpc_step_reg_kernel(const KP Pin, const TickP K, const PreK Q)
         double tn_;
         if (status == JSIM_OK) tn_ = rdlane(wtan, 0); // di is this solve's delta_0: S5 has tan(dc) in lane 0
         else tn_ = tan(dc);                           // a failed tick steers with the previous di
+        // (jsim_plant_step's operations, in the tail's own text: through the function every one-wave kernel's registers were allocated anew)
         const double xd = sv * cy_, yd = sv * sy_, thd = (sv / P.L) * tn_;
         sx += xd * dt; sy += yd * dt; syaw += thd * dt;
         sv += ai * dt;
@@ -1814,6 +1970,7 @@ void mpc_step_reg_kernel(const KP Pin, const TickP K, const PreK Q)
             sx = K.x0_spawn[4 * ego]; sy = K.x0_spawn[4 * ego + 1]; sv = K.x0_spawn[4 * ego + 2]; syaw = K.x0_spawn[4 * ego + 3];
             s0 = K.target_spawn[ego];
             wa_t = 0.0; wd_t = 0.0; wtan = 0.0; di_prev = 0.0; ai_last = 0.0; age = 0;
+            if constexpr (NB) nb_valid = false; // (NB: what the helpers prepared belongs to the state that ends here)
             if (PRE) { pre_idx = 0; pre_prev = -1; } // a fresh run: no progress index, no previous truncated path
             if (tl) { P.oa[(size_t)ego * T + lane] = 0.0; P.od[(size_t)ego * T + lane] = 0.0; }
             if (lane == 0) {

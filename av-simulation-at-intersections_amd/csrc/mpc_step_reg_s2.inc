@@ -40,7 +40,8 @@
         // Sequential sums in the reference's order, every prefix at once: the T increments sit behind T zeros in LDS and
         // lane L adds z[L], .., z[L + T - 1] to the start value -- T - L exact no-ops (+ 0.0), then inc_0, .., inc_{L-1}.
         // One ds_read with an immediate offset and one add per term (the table area is free until S3 fills it).
-        double *const zx = tq, *const zy = tq + 2 * T;
+        // (JSIM_S2_SCR: 4T doubles of the including wave's -- the owner's is the table area, free until S3 fills it)
+        double *const zx = JSIM_S2_SCR, *const zy = JSIM_S2_SCR + 2 * T;
         static_assert(4 * T <= TQ_COUNT * TP, "scratch fits the table area");
         const int li = lane <= T ? lane : T;
         if (lane < T) { zx[lane] = 0.0; zx[T + lane] = w; }

@@ -2,7 +2,9 @@
 """Diagnostic: where one mpc_step_kernel launch spends its cycles.  Builds csrc/jsim_mpc.hip with
 -DJSIM_STAMPS into a SEPARATE library (libjsim_mpc_stamps.so; the shipped library carries no stamps),
 runs the bench workload for a few ticks and prints per-phase cycle shares (median over egos).
-Never quote this build's run time -- read its shares."""
+Never quote this build's run time -- read its shares.
+usage: phase_stamps.py [T=20] [B=256] [fused=0]   (fused > 0: launches of that many fused ticks, stamped in their last tick -- the
+ticks whose head the helper wavefronts ran under the previous tick's tail)"""
 import ctypes as C
 import importlib
 import os
@@ -18,6 +20,7 @@ pkg = importlib.import_module("av-simulation-at-intersections_amd")
 
 T = int(sys.argv[1]) if len(sys.argv) > 1 else 20
 B = int(sys.argv[2]) if len(sys.argv) > 2 else 256
+FUSED = int(sys.argv[3]) if len(sys.argv) > 3 else 0   # > 0: launches of that many fused ticks, the stamps are each launch's last tick
 lib = os.environ.get("JSIM_STAMPS_LIB") or os.path.join(REPO, "av-simulation-at-intersections_amd", "libjsim_mpc_stamps.so")
 if not os.environ.get("JSIM_STAMPS_LIB"):   # (JSIM_STAMPS_LIB: a -DJSIM_STAMPS library built beforehand)
     subprocess.check_call([pkg.build._hipcc()] + pkg.build.HIPCC_FLAGS + ["-DJSIM_STAMPS", "-I", pkg.build.INC, pkg.build.SRC, "-o", lib])
@@ -40,7 +43,7 @@ names = ["S1 nearest", "S1 idx/xref", "S2 rollout", "S3 coef+scans", "S4a H mfma
 acc = np.zeros((0, 11))
 gacc = np.zeros((0, 8)); itacc = np.zeros(0)
 for tick in range(30):
-    loop.tick()
+    loop.run(FUSED) if FUSED else loop.tick()
     torch.cuda.synchronize()
     call = clk.cpu().numpy()
     c = call[:B * 16].reshape(B, 16)
@@ -56,6 +59,11 @@ if np.all(hc[:, 12:15] > 0):   # the column-split kernels: helper 2's stamps of 
                       ("helper 2: the owner's columns applied", 12, 13), ("helper 2: behind the owner's last column", 7, 13),
                       ("helper 2: its own columns", 13, 14), ("helper 1 and the barrier behind helper 2", 14, 8)):
         print(f"  split {nme:42s} median {np.median(hc[:, b] - hc[:, a]):8.0f} cyc")
+if np.any(hc[:, 15] > 0):     # the one-wave kernels: four stretches of the path across the tick boundary (slot 15, 16 bits each)
+    handed = bool(np.median((hc[:, 15] >> 48) & 0xffff) > 0)   # the helpers ran this tick's head under the previous tick's tail
+    for k, nme in enumerate(("helper 1: its whole HB_NEXT chain" if handed else "S2 rollout (HELP: inside S1 nearest)", "S5: tan of the new warm start",
+                             "S3 without index / reference window", "owner: wait at HB_NEXT's closing barrier")):
+        print(f"  boundary {nme:39s} median {np.median((hc[:, 15] >> (16 * k)) & 0xffff):8.0f} cyc")
 print(f"T={T} B={B}: total cycles/ego median {np.median(tot):.0f} (p10 {np.percentile(tot,10):.0f}, p90 {np.percentile(tot,90):.0f}); "
       f"last-tick mean n_iter {it.mean():.1f}")
 for k, nme in enumerate(names):
