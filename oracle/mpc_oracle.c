@@ -521,7 +521,8 @@ int orc_solve_qp_trace(int n, int m, const double *H, const double *g, const dou
         }
         if (p < 0) break; /* optimal */
         double lplus = 0.0;
-        if (q > tc.max_q) tc.max_q = q; /* the working set at the start of an iteration */
+        if (q > tc.max_q) tc.max_q = q;
+        if (q == n) ++tc.full_entering; /* a violated row while all n variables are bound */
 
         for (;;) { /* step 2 */
             if (++iters > max_iters) { status = ORC_INFEASIBLE; tc.end = ORC_END_MAX_ITERS; goto finish; }
@@ -712,7 +713,7 @@ int orc_mpc_step_cv(const orc_params *p, double sx, double sy, double syaw, doub
         status = orc_solve_qp_trace(n, m, H, g, G, h, skip, u, lam, &iters, &tp);
         iters_total += iters;
         trace.adds += tp.adds; trace.drops += tp.drops; trace.drops_first += tp.drops_first;
-        trace.drops_last += tp.drops_last; trace.dependent += tp.dependent;
+        trace.drops_last += tp.drops_last; trace.dependent += tp.dependent; trace.full_entering += tp.full_entering;
         if (tp.max_q > trace.max_q) trace.max_q = tp.max_q;
         trace.end = tp.end;
         if (status != ORC_OK) break;

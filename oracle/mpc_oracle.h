@@ -155,9 +155,9 @@ typedef struct orc_trace {
     int32_t drops_first; /* .. from working-set position 0 */
     int32_t drops_last;  /* .. from the last position, q - 1 (no Givens sweep) */
     int32_t dependent;   /* entering rows in the span of the working set (pure dual step) */
-    int32_t max_q;       /* largest working set, at the start of an iteration or after an add */
+    int32_t max_q;       /* the largest working set the solve held (raised after every add) */
     int32_t end;         /* ORC_END_* */
-    int32_t reserved_;
+    int32_t full_entering; /* iterations that begin with q == n and a violated row: the row is dependent by necessity */
 } orc_trace;
 int orc_solve_qp_trace(int n, int m, const double *H, const double *g, const double *G, const double *h,
                        const uint8_t *skip, double *u, double *lam, int32_t *n_iter, orc_trace *trace /* may be NULL */);

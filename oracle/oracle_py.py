@@ -54,8 +54,8 @@ class OrcStepOut(C.Structure):
     ]
 
 
-# orc_trace (mpc_oracle.h): what one solve did.  A traced call returns int32 [.., 8] rows with these columns (the last is padding).
-TRACE_FIELDS = ("adds", "drops", "drops_first", "drops_last", "dependent", "max_q", "end", "reserved_")
+# orc_trace (mpc_oracle.h): what one solve did.  A traced call returns int32 [.., 8] rows with these columns.
+TRACE_FIELDS = ("adds", "drops", "drops_first", "drops_last", "dependent", "max_q", "end", "full_entering")
 TRACE = {name: i for i, name in enumerate(TRACE_FIELDS)}
 END_OPTIMAL, END_INFEASIBLE_IN_LOOP, END_MAX_ITERS, END_BEFORE_LOOP = 0, 1, 2, 3
 

@@ -22,10 +22,20 @@ mixed_case builds one batch with all of it through the per-ego table: most egos 
 between solvable neighbours, and the v0-above-limit ego of the per-ego table tests (gpu_helpers.PLANT_FAIL, braking with -3.7),
 so that both kinds of failure sit in one launch.
 
-Two branches of the iteration are taken by no input here and by none of the suite's other families: a working set of all 2T
-variables at the start of an iteration (2T - 1 is reached), and the clamp of a negative primal step length to 0.  The oracle's
-trace shows the first; the second was counted in a scratch copy of the oracle (0 times in 2.4 million iterations of these inputs).
-Neither is chased.
+A fourth family, the full-set family (full_set_case; tests/test_full_set_cpu.py, tests/test_gpu_full_set.py), brings the working
+set to all 2T variables, which the three above cannot: with the stock weights the last acceleration moves only v_T, which costs
+nothing, so one variable always stays free and 2T - 1 is where they end.  The off-path egos at v0 = 0.1 .. 0.35 under the tight
+acceleration limits and a weight on the speed (Q_v_yaw[0] = 1, Qf[2] = 1, R = [0.01, 1e-4]) reach, on nine egos in ten:
+  * the add at position 2T - 1 (the last column of R, a Householder reflection on a trailing block of one element) and the full set
+    at termination (2T active bits) -- form "adds", MAX_DSTEER = 3000: by 2T adds and nothing else on most egos;
+  * an entering row at q = 2T -- form "drops", MAX_DSTEER = 0.4: with every variable bound a further violated row depends on the
+    working set by necessity, so the iteration is a pure dual step and a forced drop; the oracle's trace counts the iterations that
+    begin there (full_entering): 900 .. 2600 per batch of 64, not zero as a first probe of this family had it;
+  * the full set carried over the ticks of a closed loop (the later ticks start from the tick before);
+  * form "mixed": full-set rows and stock rows alternate through the per-ego table, solves of 60 .. 180 iterations beside solves of 40.
+Still taken by no input of the suite: the clamp of a negative primal step length to 0.  In exact arithmetic it cannot fire --
+viol > 0 at selection, zn > 0, and a partial step of length t1 < t2 leaves viol - t1 zn > 0 --, so it is a rounding guard, not a
+path; a scratch copy of the oracle counted it 0 times in 2.4 million iterations of the three families above.  It is not in the trace.
 """
 from dataclasses import replace
 
@@ -117,6 +127,111 @@ def mixed_case(synth, routes, base, B, T, seed=None, plant=True):
     if not plant:
         rows[ROW_A] = rows[ROW_B] = replace(base, T=T)
     return batch, [rows[k] for k in which], which
+
+
+# ------------------------------------------------------------------------------------------------
+# The full-set family: a working set of all 2T variables.
+# ------------------------------------------------------------------------------------------------
+# With the stock weights Q_v_yaw[0] = 0 and Qf[2] = 0 the last acceleration a_{T-1} moves only v_T, which costs nothing: R and Rd
+# alone hold it strictly inside its box, and one of the 2T variables stays free (2T - 1 above).  A weight on the speed sends it to
+# its bound like the others.
+FULL_WEIGHTS = dict(Q_v_yaw=[1.0, 0.5], Qf=[1.0, 1.0, 1.0, 0.5], R=[0.01, 1e-4])
+FULL_LIMITS = dict(MAX_ACCEL=0.05, MAX_DECEL=-0.05)
+FULL_DSTEER = dict(drops=0.4, adds=3000.0)    # "drops": TIGHT's steering rate -- drops and dependent rows on the way; "adds": the
+#                                               rate rows out of reach, the full set by 2T adds and nothing else
+# the start speed per horizon, and the draw.  Chosen on the oracle's evidence alone (tests/test_full_set_cpu.py prints the counts).
+FULL_V0 = {25: 0.35, 40: 0.1}                 # (at 0.25: 0 .. 4 egos of a batch reach the full set at T = 25; at T = 40 a sixth
+#                                               of a batch misses the margin of the mask comparison)
+FULL_V0_DEFAULT = 0.25
+FULL_SEED = 5
+FULL_B = dict(drops=64, adds=48, mixed=96)    # the family's egos per form; a GPU case tiles them up to its kernel's dispatch size
+FULL_MARGIN = 1000.0                          # a compared ego's multipliers exceed this many activity thresholds
+FULL_LEFT_OUT = 0.10                          # .. and at most this share of a batch is left out of the mask comparison
+
+
+def full_v0(T):
+    return FULL_V0.get(T, FULL_V0_DEFAULT)
+
+
+def full_config(base, T, form="drops"):
+    """The full-set row: tight acceleration limits, a weight on the speed, and the form's steering-rate limit."""
+    return replace(base, T=T, MAX_DSTEER=FULL_DSTEER[form], **FULL_LIMITS,
+                   **{k: list(v) for k, v in FULL_WEIGHTS.items()})
+
+
+def full_set_case(synth, routes, base, B, T, form="drops", seed=FULL_SEED, v0=None):
+    """(batch, cfgs, which) of the full-set family: the off-path tight family's egos at speed v0 (default: full_v0(T)) under
+    full_config.  form "drops" / "adds": every ego a full-set row (which = 0).  form "mixed": the even egos full-set rows of the
+    "drops" form, the odd egos the stock row `base` (which = 1) -- one launch then holds solves that end at q = 2T after a hundred
+    iterations beside solves that have long finished."""
+    batch = off_path_batch(synth, routes, B, T, seed)
+    batch.x0[:, 2] = full_v0(T) if v0 is None else v0
+    rows = (full_config(base, T, "drops" if form == "mixed" else form), replace(base, T=T))
+    which = np.zeros(B, dtype=np.int64)
+    if form == "mixed":
+        which[1::2] = 1
+    return batch, [rows[k] for k in which], which
+
+
+def full_set_stock_case(synth, routes, base, B, T, seed=FULL_SEED):
+    """The mixed batch's states with every full-set row replaced by the stock row: what a stock-row neighbour must not be able to
+    tell from the mixed batch."""
+    batch, _, which = full_set_case(synth, routes, base, B, T, "mixed", seed)
+    return batch, [replace(base, T=T)] * B, which
+
+
+def tile(batch, cfgs, which, B):
+    """The family's egos repeated cyclically up to B egos (B >= len(cfgs)): (batch, cfgs, which, first) with first[b] the ego that b
+    copies."""
+    first = np.arange(B) % len(cfgs)
+    fields = {k: np.ascontiguousarray(v[first]) for k, v in vars(batch).items()}
+    return type(batch)(**fields), [cfgs[k] for k in first], which[first], first
+
+
+def oracle_steps(oracle, routes, batch, cfgs, which):
+    """The oracle's traced step of every ego of a family batch, one ego at a time with its condensed QP: the arrays of
+    oracle.mpc_step_batch_per_config(trace=True) and beside them H [B, n, n], g [B, n], lam [B, 8T] and u [B, n] (a_0, delta_0, ..;
+    under the acceleration-state variant the free acc_0 last, recovered from the predicted speeds)."""
+    from gpu_helpers import oracle_params_list
+    ps = oracle_params_list(oracle, cfgs, which)
+    rows = []
+    for b in range(len(cfgs)):
+        p = ps[which[b]]
+        r, x0 = routes[int(batch.path_id[b])][:int(batch.path_len[b])], batch.x0[b]
+        res = oracle.mpc_step(p, (x0[0], x0[1], x0[3], x0[2]), r[:, 0], r[:, 1], r[:, 2], int(batch.target_ind[b]), float(batch.speed[b]),
+                              oa=batch.oa[b], od=batch.od[b], want_qp=True, trace=True)
+        res["u"] = np.stack([res["oa"], res["od"]], axis=1).reshape(-1)
+        if p.nx == 5:
+            res["u"] = np.concatenate([res["u"], [(res["ov"][1] - res["ov"][0]) / p.dt - res["oa"][0]]])
+        rows.append(res)
+    keys = ("oa", "od", "ox", "oy", "ov", "oyaw", "lam", "active_mask", "H", "g", "trace", "u", "status", "n_iter", "target_ind")
+    return {k: np.array([r[k] for r in rows]) for k in keys}
+
+
+def full_reached(oracle, ref, n):
+    """bool [B] from a traced oracle run: the egos whose working set reached all n variables and whose final active mask has n bits."""
+    bits = np.unpackbits(np.ascontiguousarray(ref["active_mask"]).view(np.uint8), axis=1).sum(axis=1)
+    return (ref["trace"][:, oracle.TRACE["max_q"]] == n) & (bits == n) & (ref["status"] == 0)
+
+
+def margin_ok(lam, g):
+    """The rule that admits an ego to the bit-exact mask comparison, on the oracle's multipliers alone: every multiplier of the
+    final working set that is positive exceeds FULL_MARGIN activity thresholds 1e-9 max(1, |g|_inf), so that no kernel's rounding
+    can move one across the threshold."""
+    thr = 1e-9 * max(1.0, float(np.abs(g).max()))
+    lam = np.asarray(lam)
+    return bool(np.all(lam[lam > 0.0] > FULL_MARGIN * thr))
+
+
+def compared(ref):
+    """bool [B] of an oracle_steps result: the egos that solve and pass margin_ok."""
+    return np.array([ref["status"][b] == 0 and margin_ok(ref["lam"][b], ref["g"][b]) for b in range(len(ref["status"]))])
+
+
+def active_rows(mask_row, m):
+    """The row ids of an active mask's set bits."""
+    words = np.ascontiguousarray(mask_row).view(np.uint32)
+    return [i for i in range(m) if (int(words[i >> 5]) >> (i & 31)) & 1]
 
 
 def contradiction(v0, speed, dt, T, cfg):

@@ -145,7 +145,7 @@ def test_mixed_batch_takes_the_paths(pkg, oracle, routes, gpu_cases, T):
     """For every (T, B) of the one-step GPU cases at 256 CUs: every planted A / B ego ends by the in-loop exit with at least one add
     and one drop before it; the egos with status 1 are exactly the arithmetic-contradictory ones; the off-path tight egos all
     solve; and per batch at least 20 dependent rows, a drop at position 0, a drop at the last position, a working set of 2T - 1
-    (and none of 2T: the branch no input reaches) and a solve longer than 2T.  With MAX_ITER = 3 the planted egos' traces are
+    (and none of 2T: these families end there, the full-set family of tests/test_full_set_cpu.py goes on) and a solve longer than 2T.  With MAX_ITER = 3 the planted egos' traces are
     those of one pass: they fail on the first."""
     one, _ = gpu_cases.oracle_shapes(CU)
     assert {s[0] for s in one} == set(HORIZONS)
