@@ -13,8 +13,6 @@
 // host (jsim_loop_set_geometry) -- the path is static -- so the kernel evaluates no transcendental for the ego.
 
 #define JSIM_MAX_RES 320   // kept points of a resampled ego path (<= ~150 for 720-point routes)
-#define JSIM_MAX_OBS 8
-#define JSIM_MAX_PRED 64
 
 struct ObsP {
     int n_obs, n_steps;

@@ -17,22 +17,24 @@ from typing import List, NamedTuple, Optional
 
 import numpy as np
 
+from ._header import constant as _c     # the limits and flags below are include/jsim_mpc.h's
+
 FIELDS = ("x", "y", "yaw", "v", "delta", "a", "xref_deviation")
-FAILED, GOAL, AGE = 1, 2, 4              # JSIM_REC_* of include/jsim_mpc.h
+FAILED, GOAL, AGE = _c("JSIM_REC_FAILED"), _c("JSIM_REC_GOAL"), _c("JSIM_REC_AGE")
 END_RUNNING, END_GOAL, END_AGE = 0, 1, 2  # how an episode ended (episodes())
 # the columns of the episode table (Recorder.summary), in the order of JSIM_EP_* of include/jsim_mpc.h
 EP_INT = ("ego", "k0", "n", "end", "failed", "dev_tick", "veh_tick", "veh_who", "veh_hit_tick", "veh_hit_frame", "st_tick", "st_who",
           "st_off_tick", "st_obstacle", "st_ticks_off", "replan_tick")
 EP_DOUBLE = ("length", "v_mean", "v_max", "a_min", "a_max", "delta_absmax", "dev_max", "dev_mean", "veh_clear", "veh_hit_x",
              "veh_hit_y", "st_clear", "pm_min", "driver_min", "cyclist_min", "dist_min")
-GAP_NONE, GAP_MAX_WINDOW = -128, 63      # JSIM_GAP_NONE, JSIM_GAP_MAX_WINDOW
+GAP_NONE, GAP_MAX_WINDOW = _c("JSIM_GAP_NONE"), _c("JSIM_GAP_MAX_WINDOW")
 # the columns of Recorder.tracking's ep_i and ep_d, in the order of the JSIM_TRK_* enumerators of include/jsim_mpc.h
 TRK_INT = ("ticks", "d_max_tick")
 TRK_DOUBLE = ("d_max", "d2_mean", "yaw_max", "s_first", "s_last")
 # the columns of Recorder.headway's ep_i and ep_d, in the order of the JSIM_HW_* enumerators of include/jsim_mpc.h
 HW_INT = ("ticks", "lead_ticks", "gap_tick", "gap_who", "thw_tick", "ttc_tick", "ttc_who")
 HW_DOUBLE = ("gap_min", "thw_min", "ttc_min", "thw_mean")
-MAX_OBS = 8            # JSIM_MAX_OBS: obstacles one ego's glue can hold (scripted vehicles, then group mates)
+MAX_OBS = _c("JSIM_MAX_OBS")   # obstacles one ego's glue can hold (scripted vehicles, then group mates)
 
 
 class Evaluator(NamedTuple):
@@ -83,7 +85,7 @@ class RowOutputs(NamedTuple):
 # the columns of Recorder.predictions' pt_i and pt_d, in the order of the JSIM_PS_* enumerators of include/jsim_mpc.h
 PS_INT = ("n", "hold", "max_at")
 PS_DOUBLE = ("ade", "fde", "max", "lon", "lat", "yaw")
-MAX_PRED = 64          # JSIM_MAX_PRED: the longest prediction
+MAX_PRED = _c("JSIM_MAX_PRED")   # the longest prediction
 # jsim_loop_score_predictions' outputs: rows are the recorded vehicles and then the egos, [n][V], so they stand
 # beside EVALUATORS, not in it
 PREDICTION_OUTPUTS = RowOutputs("jsim_loop_score_predictions",
@@ -136,7 +138,7 @@ CHECKPOINT = (
     CheckpointArray("pre_status", _I, ("B",), "pre", "status", "ego"),
     CheckpointArray("obs_state", _F, ("n_obs", 4), "obst", "state", "vehicle"),
 )
-CHECKPOINT_MAX_ARRAYS = 32     # JSIM_CKPT_MAX_ARRAYS of include/jsim_mpc.h
+CHECKPOINT_MAX_ARRAYS = _c("JSIM_CKPT_MAX_ARRAYS")
 CHECKPOINT_META = ("_names", "_every", "_cap", "_slot_tick", "_kind")   # what a checkpoint file holds beside the slabs
 
 

@@ -17,7 +17,7 @@ from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from . import _cabi
+from . import _cabi, _header
 
 MP_NAMES = ("straight", "left1", "left2", "left3", "left4", "right1", "right2", "right3", "right4")
 MP_STEER = (0.0, 0.1, 0.2, 0.3, 0.4, -0.1, -0.2, -0.3, -0.4)     # main/create_motion_primitives_prius.py:19-29
@@ -229,7 +229,7 @@ def arterial_query(margin: float, num_lanes: int = 2, goal_lane: int = 1, replan
                       tol=float(np.pi / 16), obstacles=[primitive_halfplanes(o, margin) for o in prims])
 
 
-STATIC_ROW = 32                    # JSIM_STATIC_ROW: doubles per obstacle row of jsim_loop_eval_static
+STATIC_ROW = _header.constant("JSIM_STATIC_ROW")   # doubles per obstacle row of jsim_loop_eval_static
 
 
 def static_obstacle_rows(obstacles, margin: float) -> np.ndarray:

@@ -18,6 +18,7 @@ import ctypes as C
 import numpy as np
 
 from . import _cabi
+from .history import AGE, GOAL
 
 MAX_CAND, MAX_RES = 8, 320
 # a situation's parameter row, in the order of the header's JSIM_REASON_* enum; the reference's values (lib/parameters.py,
@@ -299,7 +300,7 @@ def situation_at(recorder, b: int, k: int, candidates, reasons=None, **layout) -
     if veh < 0:
         raise ValueError(f"ego {b} has no cyclist")
     fl = int(recorder.flags[k - 1, b].item()) if k > 0 else 0
-    if k == 0 or fl & 6:                                      # (JSIM_REC_GOAL | JSIM_REC_AGE: the tick starts at the spawn state)
+    if k == 0 or fl & (GOAL | AGE):                           # (the tick starts at the spawn state)
         x, y, v, yaw = (recorder.x0_first if k == 0 else recorder.loop.x0_spawn)[b].cpu().numpy().tolist()
     else:
         x, y, yaw, v = recorder.rec[k - 1, b, :4].cpu().numpy().tolist()

@@ -56,6 +56,8 @@ extern "C" {
 
 #define JSIM_ABI_VERSION 2 /* 2: jsim_cfg ends with nx, reserved_, jerk_weight */
 #define JSIM_MAX_T 48 /* two (2T)x(2T+1) fp64 tiles must fit the 160 KiB LDS of one CU */
+#define JSIM_MAX_OBS 8   /* obstacles one ego's glue can hold: its scripted vehicles, then its group mates */
+#define JSIM_MAX_PRED 64 /* samples of the longest prediction (n_steps): one lane of a wavefront each */
 
 typedef struct jsim_cfg {
     int32_t T;        /* horizon; 1 <= T <= JSIM_MAX_T (stock 13) */
@@ -79,10 +81,10 @@ typedef struct jsim_cfg {
 
 typedef struct jsim_ctx jsim_ctx;
 
-/* Per-ego status of a step / tick.  3: the ego has no path (path_len < 1).  JSIM_HELPER_TIMEOUT: an internal fault of the kernels with
+/* Per-ego status of a step / tick.  JSIM_NO_PATH: the ego has no path (path_len < 1).  JSIM_HELPER_TIMEOUT: an internal fault of the kernels with
  * helper wavefronts -- a helper's bounded wait for a column of the factor ran out; the tick is treated like a failed solve (nothing
  * of the controller is updated, the loops brake with MAX_DECEL), and the Python layer raises JsimError when it reads the status. */
-enum { JSIM_OK = 0, JSIM_INFEASIBLE = 1, JSIM_NEAREST_ANOMALY = 2, JSIM_HELPER_TIMEOUT = 4 };
+enum { JSIM_OK = 0, JSIM_INFEASIBLE = 1, JSIM_NEAREST_ANOMALY = 2, JSIM_NO_PATH = 3, JSIM_HELPER_TIMEOUT = 4 };
 
 int jsim_abi_version(void);
 const char *jsim_last_error(const jsim_ctx *ctx);

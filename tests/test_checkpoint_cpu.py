@@ -192,18 +192,18 @@ def test_entry_point_refusals_without_a_context(pkg):
 
 # ---- 5. header, binding and documentation ----
 def test_header_binding_and_integration_rows(pkg):
-    hdr = open(os.path.join(REPO, "include", "jsim_mpc.h")).read()
+    hdr = pkg._header.header()
     doc = open(os.path.join(REPO, "INTEGRATION.md")).read()
     lib = pkg._cabi.load()
     for name, n_args in (("jsim_loop_checkpoint_save", 6), ("jsim_loop_checkpoint_load", 18)):
-        decl = re.search(rf"^int {name}\(([^;]*)\);", hdr, re.M)
-        assert decl and len(decl.group(1).split(",")) == n_args == len(getattr(lib, name).argtypes), name
-        assert name in pkg._cabi.EXPORTS and f"`{name}`" in doc
-        for arg in re.findall(r"(\w+)(?:,|$)", decl.group(1).replace("\n", " ")):
+        args = [arg for _, arg in hdr.functions[name].params]
+        assert len(args) == n_args == len(getattr(lib, name).argtypes), name
+        assert f"`{name}`" in doc
+        for arg in args:
             if arg not in ("ctx", "stream"):
                 assert f"`{arg}" in doc or arg in doc.split(name, 1)[1][:3000], (name, arg)
-    assert re.search(r"enum \{ JSIM_CKPT_MAX_ARRAYS = (\d+) \}", hdr).group(1) == str(pkg._cabi.CKPT_MAX_ARRAYS)
-    assert "#define JSIM_ABI_VERSION 2" in hdr or re.search(r"JSIM_ABI_VERSION\s*=?\s*2\b", hdr)
+    assert hdr.constants["JSIM_CKPT_MAX_ARRAYS"] == pkg._cabi.CKPT_MAX_ARRAYS
+    assert hdr.constants["JSIM_ABI_VERSION"] == 2
     assert lib.jsim_abi_version() == 2
     # the kernels are the plan unit's: the main unit sees their declarations only
     csrc = os.path.join(REPO, pkg.__name__, "csrc")

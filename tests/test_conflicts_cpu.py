@@ -165,11 +165,9 @@ NAMES = ("rec", "flags", "n_obs", "obs_rec", "x_first", "x_spawn", "veh_range", 
 
 def test_entry_point_is_declared_and_bound(pkg):
     hdr = open(os.path.join(REPO, "include", "jsim_mpc.h")).read()
-    m = re.search(r"\bint jsim_loop_eval_conflicts\s*\(([^;]*)\);", hdr)
-    assert m and len(m.group(1).split(",")) == 21
-    assert all(re.search(rf"\b{k}\b", m.group(1)) for k in NAMES)
+    args = [a for _, a in pkg._header.header().functions["jsim_loop_eval_conflicts"].params]
+    assert len(args) == 21 and all(k in args for k in NAMES)
     assert "check_collision_moving_cars / check_collision_moving_bicycle (main/lib/collision_avoidance.py:85-166)" in hdr
-    assert "jsim_loop_eval_conflicts" in pkg._cabi.EXPORTS
     lib = pkg._cabi.load()
     assert len(lib.jsim_loop_eval_conflicts.argtypes) == 21
     doc = open(os.path.join(REPO, "INTEGRATION.md")).read()

@@ -132,13 +132,10 @@ def test_cutoff_episodes(pkg):
 
 def test_entry_point_is_declared_and_bound(pkg):
     hdr = open(os.path.join(REPO, "include", "jsim_mpc.h")).read()
-    m = re.search(r"\bint jsim_loop_eval_cutoffs\s*\(([^;]*)\);", hdr)
-    assert m and len(m.group(1).split(",")) == 24
-    args = [a.strip() for a in m.group(1).split(",")]
-    assert [re.search(r"(\w+)$", a).group(1) for a in args] == ["ctx", "B", "n_ticks", *NAMES, "stream"]
+    args = [a for _, a in pkg._header.header().functions["jsim_loop_eval_cutoffs"].params]
+    assert len(args) == 24 and args == ["ctx", "B", "n_ticks", *NAMES, "stream"]
     for cite in ("main/scenarios/mpc_intersection.py:104-143", "overtaking_cyclist_bidirectional_road.py:111-169"):
         assert cite in hdr
-    assert "jsim_loop_eval_cutoffs" in pkg._cabi.EXPORTS
     lib = pkg._cabi.load()
     assert len(lib.jsim_loop_eval_cutoffs.argtypes) == 24
     doc = open(os.path.join(REPO, "INTEGRATION.md")).read()

@@ -226,16 +226,16 @@ GROUPS = (NAMES[4:9], NAMES[9:13], NAMES[13:15])
 
 
 def test_entry_point_is_declared_and_bound(pkg):
-    hdr = open(os.path.join(REPO, "include", "jsim_mpc.h")).read()
-    m = re.search(r"\bint jsim_loop_summarise_episodes\s*\(([^;]*)\);", hdr)
-    assert m and len(m.group(1).split(",")) == 23
-    assert all(re.search(rf"\b{k}\b", m.group(1)) for k in NAMES)
-    ints = re.search(r"enum \{ JSIM_EP_EGO = 0,([^}]*)JSIM_EP_NI \};", hdr).group(1)
-    dbls = re.search(r"enum \{ JSIM_EP_LENGTH = 0,([^}]*)JSIM_EP_ND \};", hdr).group(1)
-    assert ["ego"] + [s.strip()[8:].lower() for s in ints.split(",") if s.strip()] == list(pkg.history.EP_INT)
-    assert ["length"] + [s.strip()[8:].lower() for s in dbls.split(",") if s.strip()] == list(pkg.history.EP_DOUBLE)
-    assert "#define JSIM_ABI_VERSION 2 " in hdr
-    assert "jsim_loop_summarise_episodes" in pkg._cabi.EXPORTS
+    H = pkg._header.header()
+    args = [a for _, a in H.functions["jsim_loop_summarise_episodes"].params]
+    assert len(args) == 23 and all(k in args for k in NAMES)
+    cols = [k for k in H.constants if k.startswith("JSIM_EP_")]                    # both enums' enumerators, in the header's order
+    ints = cols[:cols.index("JSIM_EP_NI")]
+    dbls = cols[len(ints) + 1:-1]
+    assert (cols[0], cols[len(ints) + 1], cols[-1]) == ("JSIM_EP_EGO", "JSIM_EP_LENGTH", "JSIM_EP_ND")
+    assert [k[8:].lower() for k in ints] == list(pkg.history.EP_INT) and [H.constants[k] for k in ints] == list(range(len(ints)))
+    assert [k[8:].lower() for k in dbls] == list(pkg.history.EP_DOUBLE) and [H.constants[k] for k in dbls] == list(range(len(dbls)))
+    assert H.constants["JSIM_ABI_VERSION"] == 2
     lib = pkg._cabi.load()
     assert len(lib.jsim_loop_summarise_episodes.argtypes) == 23
     doc = open(os.path.join(REPO, "INTEGRATION.md")).read()

@@ -148,18 +148,15 @@ REQUIRED = tuple(k for k in NAMES if k not in COUNTS + ("obs_rec", "shapes", "ga
 
 def test_entry_point_is_declared_and_bound(pkg):
     hdr = open(os.path.join(REPO, "include", "jsim_mpc.h")).read()
-    m = re.search(r"\bint jsim_loop_eval_headway\s*\(([^;]*)\);", hdr)
-    assert m
-    decl = [a.strip() for a in m.group(1).split(",")]
-    args = [re.search(r"(\w+)$", a).group(1) for a in decl]
+    decl = pkg._header.header().functions["jsim_loop_eval_headway"].params
+    args = [a for _, a in decl]
     assert args == ["ctx", "B", "n_ticks", *NAMES, "stream"]
     assert "enum { JSIM_HW_TICKS = 0, JSIM_HW_LEAD_TICKS, JSIM_HW_GAP_TICK, JSIM_HW_GAP_WHO, JSIM_HW_THW_TICK, JSIM_HW_TTC_TICK, JSIM_HW_TTC_WHO, JSIM_HW_NI };" in hdr
     assert "enum { JSIM_HW_GAP_MIN = 0, JSIM_HW_THW_MIN, JSIM_HW_TTC_MIN, JSIM_HW_THW_MEAN, JSIM_HW_ND };" in hdr and "#define JSIM_ABI_VERSION 2 " in hdr
     assert "overtaking_cyclist_bidirectional_road.py" in hdr and "evaluate_time_following" in hdr and "main/lib/trajectories.py:89-97" in hdr
-    assert "jsim_loop_eval_headway" in pkg._cabi.EXPORTS
     import ctypes as C
-    want = [C.c_void_p if "*" in a else C.c_int32 if a.startswith("int32_t ") else C.c_double for a in decl]
-    assert decl[args.index("margin")] == "double margin" and pkg._cabi.load().jsim_loop_eval_headway.argtypes == want and len(want) == 34
+    want = [C.c_void_p if "*" in t else C.c_int32 if t == "int32_t" else C.c_double for t, _ in decl]
+    assert decl[args.index("margin")] == ("double", "margin") and pkg._cabi.load().jsim_loop_eval_headway.argtypes == want and len(want) == 34
     doc = open(os.path.join(REPO, "INTEGRATION.md")).read()
     row = re.search(r"^\| `jsim_loop_eval_headway` \|(.*)$", doc, flags=re.M)
     assert row and "Recorder.headway" in row.group(1)

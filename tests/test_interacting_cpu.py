@@ -3,7 +3,6 @@ tests/golden/make_golden_loop_interact.py replayed by the numpy glue oracle, the
 the host-side refusal of bad group layouts."""
 import ctypes
 import os
-import re
 import types
 
 import numpy as np
@@ -59,16 +58,14 @@ def test_interacting_reference_loop_replayed_by_the_oracle_glue(LO):
 
 
 def test_interacting_exports_declared_in_the_header(pkg):
-    hdr = open(os.path.join(REPO, "include", "jsim_mpc.h")).read()
+    hdr = pkg._header.header().functions
     for name in NEW_EXPORTS:
-        assert re.search(r"\bint\s+" + name + r"\s*\(", hdr), name
-        assert name in pkg._cabi.EXPORTS
+        assert hdr[name].ret == "int", name
     so = ctypes.CDLL(pkg.build.build())
     for name in NEW_EXPORTS:
         assert hasattr(so, name), name
     lib = pkg._cabi.load()
-    decl = re.search(r"int jsim_loop_run_interacting\(([^;]*)\);", hdr).group(1)
-    assert len(lib.jsim_loop_run_interacting.argtypes) == len(decl.split(",")) == len(lib.jsim_loop_run_scenario.argtypes)
+    assert len(lib.jsim_loop_run_interacting.argtypes) == len(hdr["jsim_loop_run_interacting"].params) == len(lib.jsim_loop_run_scenario.argtypes)
     assert len(lib.jsim_loop_set_groups.argtypes) == 4 and len(lib.jsim_loop_predict_egos.argtypes) == 7
     assert lib.jsim_loop_set_groups(None, 4, 1, None) == -22      # null ctx: refused before anything else
     assert lib.jsim_loop_predict_egos(None, 4, None, None, 35, None, None) == -22

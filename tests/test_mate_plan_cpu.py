@@ -4,7 +4,6 @@ against the reference's own Simulation.step (tests/golden/mate_plan.npz), the re
 (tests/golden/loop_interact_plan_T13.npz) replayed by the restatement and the oracle's glue, the two entry points against the
 header, and the refusal of an unknown mode before any device work."""
 import os
-import re
 import types
 
 import numpy as np
@@ -103,16 +102,14 @@ def test_fixtures_stay_within_the_size_of_the_interacting_one():
 
 
 def test_mate_prediction_exports_declared_in_the_header(pkg):
-    hdr = open(os.path.join(REPO, "include", "jsim_mpc.h")).read()
+    hdr = pkg._header.header()
     for name in NEW_EXPORTS:
-        assert re.search(r"\bint\s+" + name + r"\s*\(", hdr), name
-        assert name in pkg._cabi.EXPORTS
-    assert re.search(r"#define\s+JSIM_MATE_CONSTANT\s+0\b", hdr) and re.search(r"#define\s+JSIM_MATE_PLAN\s+1\b", hdr)
+        assert hdr.functions[name].ret == "int", name
+    assert hdr.constants["JSIM_MATE_CONSTANT"] == 0 and hdr.constants["JSIM_MATE_PLAN"] == 1
     assert pkg._cabi.MATE_PREDICTION == {"constant": 0, "plan": 1}
     pkg.build.build()
     lib = pkg._cabi.load()
-    decl = re.search(r"int jsim_loop_predict_egos_plan\(([^;]*)\);", hdr).group(1)
-    assert len(lib.jsim_loop_predict_egos_plan.argtypes) == len(decl.split(",")) == 10
+    assert len(lib.jsim_loop_predict_egos_plan.argtypes) == len(hdr.functions["jsim_loop_predict_egos_plan"].params) == 10
     assert len(lib.jsim_loop_set_mate_prediction.argtypes) == 2
     assert lib.jsim_loop_set_mate_prediction(None, 1) == -22                 # null ctx: refused before anything else
     assert lib.jsim_loop_predict_egos_plan(None, 4, None, None, None, None, None, 35, None, None) == -22

@@ -117,14 +117,12 @@ def test_the_references_plan_sharing_loop_scored_by_the_restatement():
 
 def test_the_exports_against_the_header_the_binding_and_the_library(pkg):
     H = pkg.history
-    hdr = open(os.path.join(REPO, "include", "jsim_mpc.h")).read()
+    hdr = pkg._header.header().functions
     pkg.build.build()
     lib = pkg._cabi.load()
     decl = {}
     for name in NEW_EXPORTS:
-        m = re.search(r"^int " + name + r"\((.*?)\);", hdr, re.S | re.M)
-        assert m and name in pkg._cabi.EXPORTS, name
-        decl[name] = [" ".join(p.split()) for p in m.group(1).split(",")]
+        decl[name] = [f"{t} {p}".replace("* ", "*") for t, p in hdr[name].params]   # `const double *rec`, `int32_t B`
         fn = getattr(lib, name)                                              # the library exports it
         assert len(fn.argtypes) == len(decl[name]), name
     names = lambda ps: [re.search(r"(\w+)$", p).group(1) for p in ps]
@@ -138,8 +136,7 @@ def test_the_exports_against_the_header_the_binding_and_the_library(pkg):
     for (k, dt, trail), p in zip(H.PLAN_RECORD, decl["jsim_loop_set_plan_recorder"][3:]):
         assert p.startswith("int32_t *" if dt == np.int32 else "double *") and trail == (() if dt == np.int32 else ("T",)), k
     # the replay is jsim_loop_eval_cutoffs' argument list plus the three plan pointers
-    old = re.search(r"^int jsim_loop_eval_cutoffs\((.*?)\);", hdr, re.S | re.M).group(1)
-    old = [" ".join(p.split()) for p in old.split(",")]
+    old = [f"{t} {p}".replace("* ", "*") for t, p in hdr["jsim_loop_eval_cutoffs"].params]
     new = decl["jsim_loop_eval_cutoffs_plan"]
     assert new[:len(old) - 1] == old[:-1] and names(new[len(old) - 1:]) == plan_keys + ["stream"]
     assert all(p.startswith("const ") for p in new[len(old) - 1:-1])

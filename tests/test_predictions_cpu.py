@@ -2,7 +2,6 @@
 the reference-made fixture, exactly; the two history helpers; the output table against the header's declaration and the binding's
 argtypes; the ValueErrors of Recorder.predictions on a stand-in recorder."""
 import os
-import re
 import types
 
 import numpy as np
@@ -88,22 +87,19 @@ def test_the_output_table_against_the_header_and_the_binding(pkg):
     H = pkg.history
     T = H.PREDICTION_OUTPUTS
     hdr = open(os.path.join(REPO, "include", "jsim_mpc.h")).read()
-    m = re.search(r"^int " + T.entry + r"\((.*?)\);", hdr, re.S | re.M)
-    params = [" ".join(p.split()) for p in m.group(1).split(",")]
-    names = [re.search(r"(\w+)$", p).group(1) for p in params]
+    params, names = map(list, zip(*pkg._header.header().functions[T.entry].params))       # the types' text, the names
     written = [nm for nm, p in zip(names[1:-1], params[1:-1]) if "*" in p and not p.startswith("const ")]
     assert written == list(T.keys()) and names[-len(written) - 1:-1] == written and (names[0], names[-1]) == ("ctx", "stream")
     for (k, dt, lead, trail), p in zip(T.outputs, params[-len(written) - 1:-1]):
         assert p.startswith("int32_t *" if dt == np.int32 else "double *") and lead in ("tick", "row"), k
-    assert T.entry in pkg._cabi.EXPORTS and len(getattr(pkg._cabi.load(), T.entry).argtypes) == len(params)
+    assert len(getattr(pkg._cabi.load(), T.entry).argtypes) == len(params)
     assert T.optional == ("err",) and T.keys(skip=T.optional) == ("pt_i", "pt_d", "step_sum", "step_cnt")
     # the columns are the enumerators, in their order
     for prefix, cols, last in (("JSIM_PS_", H.PS_INT, "NI"), ("JSIM_PS_", H.PS_DOUBLE, "ND")):
         want = ", ".join([f"{prefix}{cols[0].upper()} = 0"] + [prefix + c.upper() for c in cols[1:]] + [prefix + last])
         assert "enum { " + want + " };" in hdr, want
     assert dict((k, tr) for k, _, _, tr in T.outputs)["pt_i"] == (len(H.PS_INT),)
-    src = open(os.path.join(os.path.dirname(H.__file__), "csrc", "loop_pre_tick.inc")).read()
-    assert H.MAX_PRED == int(re.search(r"^#define JSIM_MAX_PRED (\d+)", src, re.M).group(1))
+    assert H.MAX_PRED == pkg._header.constant("JSIM_MAX_PRED") == 64
     assert tuple(H.EVALUATORS) == ("reasons", "conflicts", "gaps", "static", "tracking", "headway", "cutoffs")    # that table is left alone
     assert PN.PS_INT == H.PS_INT and PN.PS_DOUBLE == H.PS_DOUBLE
     design = open(os.path.join(REPO, "DESIGN.md")).read()

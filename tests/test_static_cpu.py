@@ -264,14 +264,11 @@ NAMES = ("rec", "flags", "x_first", "x_spawn", "set_of", "n_sets", "set_off", "n
 
 def test_entry_point_is_declared_and_bound(pkg):
     hdr = open(os.path.join(REPO, "include", "jsim_mpc.h")).read()
-    m = re.search(r"\bint jsim_loop_eval_static\s*\(([^;]*)\);", hdr)
-    assert m and len(m.group(1).split(",")) == 19
-    args = [a.strip() for a in m.group(1).split(",")]
-    assert [re.search(r"(\w+)$", a).group(1) for a in args] == ["ctx", "B", "n_ticks", *NAMES, "stream"]
-    assert "enum { JSIM_STATIC_ROW = 32 };" in hdr and pkg.planner.STATIC_ROW == SN.ROW == 32
+    args = [a for _, a in pkg._header.header().functions["jsim_loop_eval_static"].params]
+    assert len(args) == 19 and args == ["ctx", "B", "n_ticks", *NAMES, "stream"]
+    assert pkg._header.constant("JSIM_STATIC_ROW") == pkg.planner.STATIC_ROW == SN.ROW == 32
     for cite in ("main/lib/obstacles.py:157-176", "main/lib/mp_search_ww_generic.py:199-215", "main/lib/trajectories.py:11-55"):
         assert cite in hdr
-    assert "jsim_loop_eval_static" in pkg._cabi.EXPORTS
     lib = pkg._cabi.load()
     assert len(lib.jsim_loop_eval_static.argtypes) == 19
     doc = open(os.path.join(REPO, "INTEGRATION.md")).read()

@@ -210,14 +210,11 @@ POINTERS = tuple(k for k in NAMES if k not in ("n_pts", "n_paths"))
 
 def test_entry_point_is_declared_and_bound(pkg):
     hdr = open(os.path.join(REPO, "include", "jsim_mpc.h")).read()
-    m = re.search(r"\bint jsim_loop_eval_tracking\s*\(([^;]*)\);", hdr)
-    assert m
-    args = [re.search(r"(\w+)$", a.strip()).group(1) for a in m.group(1).split(",")]
+    args = [a for _, a in pkg._header.header().functions["jsim_loop_eval_tracking"].params]
     assert args == ["ctx", "B", "n_ticks", *NAMES, "stream"]
     assert "enum { JSIM_TRK_TICKS = 0, JSIM_TRK_D_TICK, JSIM_TRK_NI };" in hdr and "#define JSIM_ABI_VERSION 2 " in hdr
     assert "enum { JSIM_TRK_D_MAX = 0, JSIM_TRK_D2_MEAN, JSIM_TRK_YAW_MAX, JSIM_TRK_S_FIRST, JSIM_TRK_S_LAST, JSIM_TRK_ND };" in hdr
     assert "main/lib/trajectories.py:89-97" in hdr and "plot_trajectories_comparison" in hdr and "mpc_sensitivity_analysis" in hdr
-    assert "jsim_loop_eval_tracking" in pkg._cabi.EXPORTS
     assert len(pkg._cabi.load().jsim_loop_eval_tracking.argtypes) == len(args) == 21
     doc = open(os.path.join(REPO, "INTEGRATION.md")).read()
     row = re.search(r"^\| `jsim_loop_eval_tracking` \|(.*)$", doc, flags=re.M)

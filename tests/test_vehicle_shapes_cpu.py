@@ -7,7 +7,6 @@ uniform-table case in tests/test_gpu_vehicle_shapes.py."""
 import ctypes
 import importlib
 import os
-import re
 import types
 
 import numpy as np
@@ -138,9 +137,9 @@ def test_sharded_gather_refuses_a_shape_table(pkg):
 
 def test_vehicle_shapes_export_in_header_binding_and_library(pkg):
     hdr = open(os.path.join(REPO, "include", "jsim_mpc.h")).read()
-    assert re.search(r"\bint\s+jsim_loop_set_vehicle_shapes\s*\(jsim_ctx \*ctx, int32_t n, const double \*shapes", hdr)
+    decl = pkg._header.header().functions["jsim_loop_set_vehicle_shapes"]
+    assert decl.ret == "int" and decl.params == (("jsim_ctx *", "ctx"), ("int32_t", "n"), ("const double *", "shapes"))
     assert "collision_avoidance.py:126-165" in hdr and "moving_obstacles_prediction.py:21-47" in hdr
-    assert "jsim_loop_set_vehicle_shapes" in pkg._cabi.EXPORTS
     assert hasattr(ctypes.CDLL(pkg.build.build()), "jsim_loop_set_vehicle_shapes")
     lib = pkg._cabi.load()
     assert len(lib.jsim_loop_set_vehicle_shapes.argtypes) == 3
