@@ -12,6 +12,7 @@ from .vehicle import State, BicycleModelDimensions  # noqa: F401
 from . import _cabi  # noqa: F401
 from .batched import BatchedMPC  # noqa: F401
 from .closed_loop import ClosedLoop, PreTick, ScriptedObstacles, ScenarioLoop, InteractingLoop, Recorder, car_circles  # noqa: F401
+from .closed_loop import traffic_on_routes  # noqa: F401
 from . import history  # noqa: F401
 from . import recorder  # noqa: F401
 from . import checkpoint  # noqa: F401

@@ -58,7 +58,7 @@ class BatchedMPC:
         _cabi.check(self.lib.jsim_mpc_create(C.byref(cfg), self.dev_index, C.byref(self._ctx)), None, "jsim_mpc_create")
         self._upload_paths()
         # what the closed loop constructed last on this engine registered on the context (closed_loop._register_*)
-        self._recorder = self.traffic_layout = self.vehicle_shapes = None
+        self._recorder = self.traffic_layout = self.vehicle_shapes = self.traffic_routes = None
         self.ego_shape = None      # (cc_front, cc_rear, radius) of jsim_loop_set_geometry, once a PreTick has registered it
         # mpc_with_speed variant: per-point speed reference (one array per path), xref[2] = cv[idx]
         self.cv = None if cv is None else [np.ascontiguousarray(c, dtype=np.float64) for c in cv]

@@ -15,6 +15,7 @@ from .batched import BatchedMPC, _ptr
 from .checkpoint import Checkpointed, Checkpoints, check_every
 from .history import MAX_OBS
 from .recorder import Recorder, _register_recorder
+from .synth import pack_paths, smooth_yaw_inplace
 from .vehicle import car_circles, vehicle_shape
 
 
@@ -137,6 +138,88 @@ def _register_shapes(engine: BatchedMPC, table):
     engine.vehicle_shapes = table
 
 
+ROUTE_ENDS = {"leave": 0.0, "stop": 1.0}
+ROUTE_PARK = float(_cabi._K["JSIM_ROUTE_PARK"])     # where a route vehicle that has left stands
+
+
+def route_array(route) -> np.ndarray:
+    """A route spec's polyline as the [N, 3] float64 array (x, y, yaw) the table takes (a copy): two columns get the yaw of the
+    segment ahead (the last point the last segment's), and the yaw is made continuous (smooth_yaw).  ValueError: not [N >= 1, 2 or
+    3], or a value that is not finite."""
+    r = np.array(route, dtype=np.float64)
+    if r.ndim != 2 or r.shape[1] not in (2, 3) or r.shape[0] < 1:
+        raise ValueError(f"a route is an array [N >= 1, 3] (x, y, yaw) or [N, 2] (x, y), got {r.shape}")
+    if not np.isfinite(r).all():
+        raise ValueError("a route holds a value that is not finite")
+    if r.shape[1] == 2:
+        yaw = np.zeros(r.shape[0])
+        if r.shape[0] >= 2:
+            d = np.diff(r, axis=0)
+            yaw[:-1] = np.arctan2(d[:, 1], d[:, 0])
+            yaw[-1] = yaw[-2]
+        r = np.column_stack([r, yaw])
+    smooth_yaw_inplace(r[:, 2])
+    return np.ascontiguousarray(r)
+
+
+def route_table(specs, dt: float):
+    """The route table of a flat list of vehicle specs: (routes, rows) -- the distinct route arrays (route_array) of its
+    kind="route" specs, equal arrays shared, and each such spec's param row (route, end, speed, offset, s0, dt, 3, period_ticks)
+    of include/jsim_mpc.h's rule (None for a spec of another kind).  Needs no device.  ValueError: what route_array raises, an
+    unknown `end`, s0 < 0, speed < 0 (or either not finite), a period that is no whole number of ticks >= 1."""
+    routes, index, rows = [], {}, []
+    for i, s in enumerate(specs):
+        if s.get("kind", "t_intersection") != "route":
+            rows.append(None)
+            continue
+        r = route_array(s["route"])
+        end = s.get("end", "leave")
+        if end not in ROUTE_ENDS:
+            raise ValueError(f"vehicle {i}: end must be one of {sorted(ROUTE_ENDS)}, got {end!r}")
+        speed, s0 = float(s["speed"]), float(s.get("s0", 0.0))
+        if not (math.isfinite(speed) and speed >= 0):
+            raise ValueError(f"vehicle {i}: speed={speed} (a route vehicle never reverses)")
+        if not (math.isfinite(s0) and s0 >= 0):
+            raise ValueError(f"vehicle {i}: s0={s0} (an arc length from the route's first point)")
+        off = s.get("offset", None)
+        off = float(off) if (off is not None and off > 0) else 0.0
+        ticks = 0
+        if s.get("period") is not None:
+            ticks = int(round(float(s["period"]) / dt))
+            if ticks < 1 or abs(float(s["period"]) / dt - ticks) > 1e-9:
+                raise ValueError(f"vehicle {i}: period={s['period']} s is no whole number of ticks >= 1 of dt={dt}")
+        key = (r.shape[0], r.tobytes())
+        if key not in index:
+            index[key] = len(routes)
+            routes.append(r)
+        rows.append([float(index[key]), ROUTE_ENDS[end], speed, off, s0, float(dt), ScriptedObstacles.KINDS["route"], float(ticks)])
+    return routes, rows
+
+
+def _register_routes(engine: BatchedMPC, routes):
+    """jsim_loop_set_traffic_routes (no routes: clear the context's table, when it has one)."""
+    if not routes:
+        if engine.traffic_routes is not None:
+            _cabi.check(engine.lib.jsim_loop_set_traffic_routes(engine._ctx, 0, None, None, None, None), engine._ctx,
+                        "jsim_loop_set_traffic_routes")
+        engine.traffic_routes = None
+        return
+    x, y, yaw, off = pack_paths(routes)
+    off = np.ascontiguousarray(off, dtype=np.int32)
+    _cabi.check(engine.lib.jsim_loop_set_traffic_routes(engine._ctx, len(routes), *(a.ctypes.data_as(C.c_void_p) for a in (x, y, yaw, off))),
+                engine._ctx, "jsim_loop_set_traffic_routes")
+    engine.traffic_routes = routes
+
+
+def traffic_on_routes(routes, speed: float, headway_s: float, n: int, **spec):
+    """A stream of arrivals on every route: n kind="route" specs per route, the k-th entering k * headway_s seconds after the
+    first (offset).  routes: arrays [N, 3] or [N, 2] (typically PlannedRoute.trajectory); spec: further keys of every spec (end,
+    period, s0, dims).  Returns the flat list, route after route."""
+    if n < 0 or not headway_s >= 0:
+        raise ValueError(f"n={n}, headway_s={headway_s}")
+    return [dict(kind="route", route=r, speed=speed, offset=(k * headway_s) or None, **spec) for r in routes for k in range(int(n))]
+
+
 class PreTick:
     """The loop glue ahead of MPC.step (main/scenarios/mpc_intersection.py:104-143) for the whole batch: progress index,
     ego-path resampling, obstacle prediction, collision check, cut-off -> writes the engine's `path_len`, i.e. the batched
@@ -233,9 +316,14 @@ class ScriptedObstacles:
     """Device-resident scripted obstacle vehicles of main/lib/moving_obstacles.py.
     specs: list of dicts like the scenarios build them (main/scenarios/mpc_intersection.py:46-49):
       kind="t_intersection" (default) | "roundabout": direction=+-1, turning=bool, speed=float, offset=float|None
-      kind="arterial": x_init, y_init, speed, initial_speed, offset=float|None   (drives straight up)"""
+      kind="arterial": x_init, y_init, speed, initial_speed, offset=float|None   (drives straight up)
+      kind="route": route=array [N, 3] (x, y, yaw) or [N, 2], speed, offset=float|None, s0=0.0, end="leave"|"stop",
+        period=seconds|None -- a vehicle that follows the polyline (typically a PlannedRoute.trajectory) from arc length s0 at
+        `speed` after `offset` seconds, stops at or leaves from its end and enters again every `period` seconds
+        (include/jsim_mpc.h states the rule).  The distinct route arrays of the specs are the engine's route
+        table (`routes`), registered here; without a route spec an earlier table of the engine is cleared."""
 
-    KINDS = {"t_intersection": 0.0, "roundabout": 1.0, "arterial": 2.0}
+    KINDS = {"t_intersection": 0.0, "roundabout": 1.0, "arterial": 2.0, "route": 3.0}
 
     def __init__(self, engine: BatchedMPC, specs, dt: Optional[float] = None):
         """A spec may carry dims=dict(L=..., width=..., extra_length=...): the vehicle's own shape (vehicle_shape; `shapes`
@@ -245,11 +333,17 @@ class ScriptedObstacles:
         self.shapes = [vehicle_shape(s["dims"]) if s.get("dims") is not None else None for s in specs]
         self.eng = engine
         dt = engine.dt if dt is None else dt
-        st, pr = [], []
         for s in specs:
+            if s.get("kind", "t_intersection") not in self.KINDS:
+                raise ValueError(f"unknown obstacle kind {s.get('kind')!r}")
+        self.routes, route_rows = route_table(specs, dt)         # validates every route spec, before any device work
+        st, pr = [], []
+        for s, row in zip(specs, route_rows):
             kind = s.get("kind", "t_intersection")
-            if kind not in self.KINDS:
-                raise ValueError(f"unknown obstacle kind {kind!r}")
+            if row is not None:
+                st.append([0.0, 0.0, 0.0, 0.0])                  # (the pose slots are outputs of the first call)
+                pr.append(row)
+                continue
             off = s.get("offset", None)
             off = float(off) if (off is not None and off > 0) else 0.0
             if kind == "arterial":
@@ -268,6 +362,7 @@ class ScriptedObstacles:
         self.param = torch.tensor(pr, dtype=torch.float64, device=dev).reshape(self.n, 8)
         self.get_buf = torch.zeros(max(self.n, 1), 6, dtype=torch.float64, device=dev)
         self._state0 = self.state.clone()
+        _register_routes(engine, self.routes)
 
     def reset(self):
         """Send the vehicles in again from their start poses (asynchronous device copy on the current stream)."""
@@ -337,6 +432,10 @@ class _GlueLoop(Checkpointed):
             obstacle_specs = [sp for st in obstacle_specs for sp in st]
         obstacle_specs = list(obstacle_specs)
         shape_table(obstacle_specs, vehicle_shape())                              # validates every dims, before any device work
+        for sp in obstacle_specs:
+            if sp.get("kind", "t_intersection") not in ScriptedObstacles.KINDS:
+                raise ValueError(f"unknown obstacle kind {sp.get('kind')!r}")
+        route_table(obstacle_specs, engine.dt)                                    # and every route spec
         self.loop = ClosedLoop(engine, x0, hist_cap=hist_cap, max_age=max_age)
         self.pre = PreTick(engine, frame_window=frame_window, mode=mode)
         self.obst = ScriptedObstacles(engine, obstacle_specs)

@@ -43,6 +43,9 @@ struct ObsAtP {
     const double *wheelbase;  // [n_obs] or NULL
     const int *ticks;         // [n_obs] how many ticks each vehicle is advanced
     double *state;            // [n_obs][4] out
+    const double4 *route_pt;  // the route table as ObsStepP's (NULL: none)
+    const int *route_off;
+    int n_routes;
 };
 
 // One thread per vehicle: obstacle_rollout_kernel's body, each vehicle for its own number of ticks and with nothing written but
@@ -53,6 +56,7 @@ __global__ __launch_bounds__(64) void obstacles_at_kernel(const ObsAtP P)
     if (o >= P.n_obs) return;
     for (int j = 0; j < 4; ++j) P.state[4 * (size_t)o + j] = P.state0[4 * (size_t)o + j];
     ObsStepP Q = {P.n_obs, 0, P.wheelbase ? P.wheelbase[o] : P.L, P.state, P.param, nullptr, nullptr, nullptr, 0, nullptr};
+    Q.route_pt = P.route_pt; Q.route_off = P.route_off; Q.n_routes = P.n_routes;
     const int n = P.ticks[o];
     for (int k = 0; k < n; ++k) {
         Q.do_step = 0;

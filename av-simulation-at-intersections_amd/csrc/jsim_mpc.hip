@@ -1376,6 +1376,11 @@ struct jsim_ctx {
     DevArray<double2> d_othr;      // [n_shapes]
     std::vector<double> h_shapes;  // host copy [n_shapes][4] (the thresholds follow jsim_loop_set_geometry)
     int n_shapes = 0;
+    // route vehicles (jsim_loop_set_traffic_routes): the table as the obstacle kernels read it; n_routes = 0: none
+    DevArray<double4> d_route_pt;  // [points] (x, y, yaw, S)
+    DevArray<int> d_route_off;     // [n_routes + 1]
+    DevArray<double> d_route_in;   // [3][points] the uploaded x, y, yaw (route_arclen_kernel's input)
+    int n_routes = 0;
     DevArray<double4> d_conflict_rows; // [n_obs] (cc_front, cc_rear, thr, thr_sq) of jsim_loop_eval_conflicts' last call with a table
     DevArray<double4> d_gap_rows;      // the same of jsim_loop_eval_gaps' last call with a table
     DevArray<double4> d_headway_rows;  // [n_obs] (cc_front, cc_rear, radius, thr) of jsim_loop_eval_headway's last call with a table
@@ -2700,6 +2705,49 @@ extern "C" int jsim_loop_set_vehicle_shapes(jsim_ctx *ctx, int32_t n, const doub
 
 static const double4 *shapes_p(const jsim_ctx *ctx) { return ctx->n_shapes > 0 ? ctx->d_shapes.p : nullptr; }
 
+// ---- Route vehicles: the table of polylines that kind-3 rows of the obstacle tables follow (the rule: include/jsim_mpc.h) ----
+extern "C" int jsim_loop_set_traffic_routes(jsim_ctx *ctx, int32_t n_routes, const double *x, const double *y, const double *yaw,
+                                            const int32_t *off)
+{
+    const char *const F = "jsim_loop_set_traffic_routes";
+    if (!ctx) return fail(nullptr, -22, "%s: null ctx", F);
+    DeviceGuard dev_guard(ctx->device);
+    JSIM_GUARD_OK(ctx);
+    if (n_routes < 0) return fail(ctx, -22, "%s: n_routes=%d", F, n_routes);
+    if (n_routes == 0) {
+        HIP_TRY(ctx, hipDeviceSynchronize()); // launches in flight keep the table they were given
+        ctx->n_routes = 0;
+        return 0;
+    }
+    if (!x || !y || !yaw || !off) return fail(ctx, -22, "%s: null array", F);
+    if (off[0] != 0) return fail(ctx, -22, "%s: off[0]=%d, not 0", F, off[0]);
+    for (int r = 0; r < n_routes; ++r)
+        if (off[r + 1] < off[r]) return fail(ctx, -22, "%s: offsets decrease at route %d (%d after %d)", F, r, off[r + 1], off[r]);
+    const size_t n = (size_t)off[n_routes];
+    for (size_t i = 0; i < n; ++i)
+        if (!std::isfinite(x[i]) || !std::isfinite(y[i]) || !std::isfinite(yaw[i]))
+            return fail(ctx, -22, "%s: point %zu is not finite", F, i);
+    // (launches in flight on any stream may still read the table that is replaced: they finish first; a failed upload leaves the
+    // context without a table)
+    HIP_TRY(ctx, hipDeviceSynchronize());
+    ctx->n_routes = 0;
+    HIP_TRY(ctx, ctx->d_route_off.reserve((size_t)n_routes + 1));
+    HIP_TRY(ctx, ctx->d_route_pt.reserve(n > 0 ? n : 1));
+    HIP_TRY(ctx, ctx->d_route_in.reserve(n > 0 ? 3 * n : 1));
+    HIP_TRY(ctx, hipMemcpy(ctx->d_route_off, off, sizeof(int) * ((size_t)n_routes + 1), hipMemcpyHostToDevice));
+    if (n > 0) {
+        HIP_TRY(ctx, hipMemcpy(ctx->d_route_in.p, x, sizeof(double) * n, hipMemcpyHostToDevice));
+        HIP_TRY(ctx, hipMemcpy(ctx->d_route_in.p + n, y, sizeof(double) * n, hipMemcpyHostToDevice));
+        HIP_TRY(ctx, hipMemcpy(ctx->d_route_in.p + 2 * n, yaw, sizeof(double) * n, hipMemcpyHostToDevice));
+    }
+    hipLaunchKernelGGL(route_arclen_kernel, dim3((n_routes + 63) / 64), dim3(64), 0, (hipStream_t)0, n_routes, ctx->d_route_off.p,
+                       ctx->d_route_in.p, ctx->d_route_in.p + n, ctx->d_route_in.p + 2 * n, ctx->d_route_pt.p);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipDeviceSynchronize()); // the table is whole before any stream's next launch reads it
+    ctx->n_routes = n_routes;
+    return 0;
+}
+
 // obstacle_predict_kernel on n_ticks consecutive ticks' get() tuples of n_obs > 0 vehicles
 static void launch_obstacle_predict(const jsim_ctx *ctx, int n_obs, int n_steps, const double *get, double *pred, double2 *pred_cc,
                                     double4 *pred_bc, int n_ticks, hipStream_t s)
@@ -2729,7 +2777,8 @@ static TrafficP traffic_p(const jsim_ctx *ctx)
 
 static ObsStepP obstacle_step_p(const jsim_ctx *ctx, int n_obs, int do_step, double *state, const double *param, double *get)
 {
-    return ObsStepP{n_obs, do_step, ctx->have_ogeom ? ctx->oL : ctx->cfg.L, state, param, get, nullptr, nullptr, 0, shapes_p(ctx)};
+    return ObsStepP{n_obs, do_step, ctx->have_ogeom ? ctx->oL : ctx->cfg.L, state, param, get, nullptr, nullptr, 0, shapes_p(ctx),
+                    ctx->n_routes > 0 ? ctx->d_route_pt.p : nullptr, ctx->n_routes > 0 ? ctx->d_route_off.p : nullptr, ctx->n_routes};
 }
 
 // the same, with the recorder's obstacle tuples (when one is registered) at the slots of the device tick counter
@@ -3527,7 +3576,8 @@ extern "C" int jsim_loop_obstacles_at(jsim_ctx *ctx, int32_t n_obs, const double
         if (ticks[o] < 0) return fail(ctx, -22, "%s: vehicle %d: ticks=%d", F, o, ticks[o]);
     JSIM_RECORDER_CALL(n_obs == 0);
     if (int rc = replace_table(ctx, ctx->d_fork_ticks, ticks, (size_t)n_obs)) return rc;
-    const ObsAtP P = {n_obs, ctx->have_ogeom ? ctx->oL : ctx->cfg.L, state0, param, wheelbase, ctx->d_fork_ticks.p, state};
+    const ObsAtP P = {n_obs, ctx->have_ogeom ? ctx->oL : ctx->cfg.L, state0, param, wheelbase, ctx->d_fork_ticks.p, state,
+                      ctx->n_routes > 0 ? ctx->d_route_pt.p : nullptr, ctx->n_routes > 0 ? ctx->d_route_off.p : nullptr, ctx->n_routes};
     hipLaunchKernelGGL(obstacles_at_kernel, dim3((n_obs + 63) / 64), dim3(64), 0, (hipStream_t)stream, P);
     HIP_TRY(ctx, hipGetLastError());
     return 0;

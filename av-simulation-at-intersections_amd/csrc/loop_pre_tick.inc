@@ -638,12 +638,14 @@ __global__ __launch_bounds__(64) void group_pre_tick_kernel(PreP P, GroupP G, Tr
 #endif
 
 
+#include "traffic_routes.inc" // route vehicles (kind 3): the route table's kernel and route_pose
 
 // Scripted obstacle vehicles of the reference scenarios (main/lib/moving_obstacles.py): MovingObstacleTIntersection (:166-232,
 // kind 0), MovingObstacleRoundabout (:28-124, kind 1) and MovingObstacleArterial (:126-164, kind 2).  State (xc, yc, theta,
 // counter) advanced by Bicycle.step with the scripted steering / start-delay rules; the `get()` tuple (x, y, v, yaw, a = 0,
 // steer) is written for the prediction kernel.  One thread per obstacle over ceil(n_obs / 64) blocks: one block without traffic
 // sets (n_obs <= JSIM_MAX_OBS), many for the vehicles of all sets (P.n_obs = their total, tens of thousands).
+// Kind 3, a vehicle on a route of the table below, is not the reference's: include/jsim_mpc.h states its rule.
 struct ObsStepP {
     int n_obs, do_step;
     double L;             // wheelbase of every vehicle without a shape table
@@ -656,6 +658,10 @@ struct ObsStepP {
     const int *tick;
     int rec_cap;
     const double4 *shape; // [n_obs] (cc0, cc1, radius, L) of each vehicle (jsim_loop_set_vehicle_shapes), NULL: L above for all
+    // the route table (jsim_loop_set_traffic_routes), NULL: none -- a kind-3 row is then stepped as kind 0
+    const double4 *route_pt; // [points] (x, y, yaw, S)
+    const int *route_off;    // [n_routes + 1]
+    int n_routes;
 };
 
 __device__ __forceinline__ double obstacle_steer(double dir, double turning, double xc, double theta, double x_turn)
@@ -686,8 +692,34 @@ __device__ __forceinline__ double roundabout_steer(double dir, double turning, d
     return s;
 }
 
-__device__ __forceinline__ void obstacle_step_one(const ObsStepP &P, int o)
+// A route vehicle (kind 3; include/jsim_mpc.h states the rule): get() is the pose of the counter, step() the counter + 1 and its
+// pose; the state's pose slots are outputs
+__device__ __forceinline__ void route_vehicle_one(const ObsStepP &P, int o, int &hint)
 {
+    const double *pr = P.param + 8 * o;
+    const double L = P.shape ? P.shape[o].w : P.L;
+    double cnt = P.state[4 * o + 3], x, y, yaw, v, steer;
+    route_pose(P.route_pt, P.route_off, P.n_routes, pr, L, cnt, hint, x, y, yaw, v, steer);
+    if (P.get) {
+        P.get[6 * o] = x; P.get[6 * o + 1] = y; P.get[6 * o + 2] = v; P.get[6 * o + 3] = yaw; P.get[6 * o + 4] = 0.0;
+        P.get[6 * o + 5] = steer;
+    }
+    if (P.do_step) {
+        cnt += 1.0;
+        route_pose(P.route_pt, P.route_off, P.n_routes, pr, L, cnt, hint, x, y, yaw, v, steer);
+    }
+    P.state[4 * o] = x; P.state[4 * o + 1] = y; P.state[4 * o + 2] = yaw; P.state[4 * o + 3] = cnt;
+}
+
+// hint: a caller that steps one vehicle through many ticks carries the route vehicles' segment index here (route_segment)
+__device__ __forceinline__ void obstacle_step_one(const ObsStepP &P, int o, int *hint = nullptr)
+{
+    if (P.route_pt && (int)P.param[8 * o + 6] == 3) {
+        int h = hint ? *hint : -1;
+        route_vehicle_one(P, o, h);
+        if (hint) *hint = h;
+        return;
+    }
     double xc = P.state[4 * o], yc = P.state[4 * o + 1], th = P.state[4 * o + 2], cnt = P.state[4 * o + 3];
     const double *pr = P.param + 8 * o;
     const double dir = pr[0], turning = pr[1], speed = pr[2], offs = pr[3], x_turn = pr[4], dt = pr[5];
@@ -751,12 +783,13 @@ __global__ __launch_bounds__(64) void obstacle_rollout_kernel(ObsStepP P, int n_
 {
     const int o = blockIdx.x * 64 + threadIdx.x;
     if (o >= P.n_obs) return;
+    int hint = -1;
     for (int k = 0; k < n_ticks; ++k) {
         ObsStepP Q = P;
         Q.do_step = 0; Q.get = get_all + (size_t)k * P.n_obs * 6;
-        obstacle_step_one(Q, o);
+        obstacle_step_one(Q, o, &hint);
         Q.do_step = 1; Q.get = obstacle_rec_slot(P, k);
-        obstacle_step_one(Q, o);
+        obstacle_step_one(Q, o, &hint);
     }
 }
 #endif

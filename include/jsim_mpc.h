@@ -223,6 +223,36 @@ int jsim_loop_set_vehicle_shapes(jsim_ctx *ctx, int32_t n, const double *shapes 
  * of jsim_loop_predict_obstacles -- and, when do_step != 0, advances the state by one `step()`. */
 int jsim_loop_obstacles(jsim_ctx *ctx, int32_t n_obs, double *state, const double *param, double *get, int32_t do_step,
                         void *stream);
+/* ---- Route vehicles (kind 3): a scripted vehicle that follows any polyline at a scripted speed.  Bicycle.step
+ * (main/bicycle/main.py:28-41) is explicit Euler -- every tick a straight move of length v * dt along the heading -- so a
+ * reference vehicle played back along its own recorded poses is a special case of the rule below.
+ * jsim_loop_set_traffic_routes: the table of n_routes polylines, HOST arrays x, y, yaw [off[n_routes]] and off [n_routes + 1]
+ *   (route r owns the points off[r] .. off[r + 1] - 1).  yaw must be continuous along a route (no 2 pi jumps).  Per route the
+ *   device sums the arc length S[0] = 0, S[j] = S[j-1] + sqrt(dx^2 + dy^2) in index order in fp64.  n_routes = 0 clears the
+ *   table.  Refused (-22), the previous table kept: a null context, a negative count, offsets that do not start at 0 or
+ *   decrease, a null array with n_routes > 0, a coordinate or yaw that is not finite.  The call waits for the device to finish
+ *   what is in flight, on every stream, before the device copies are replaced.
+ * A route vehicle is a row of jsim_loop_obstacles' tables: param = (route, end, speed, offset_s, s0, dt, 3.0, period_ticks),
+ *   state = (x, y, yaw, counter).  Only the counter is read; the pose slots are outputs, rewritten on every call.
+ * The pose at a counter c (L: the vehicle's own wheelbase, as for the other kinds):
+ *   1. c' = c mod period_ticks if period_ticks >= 1, else c.
+ *   2. n0 = floor(offset_s / dt) + 1 if offset_s > 0, else 0 (kind 0's `counter > offset / dt`).
+ *   3. m = max(0, c' - n0).
+ *   4. s = s0 + m * (speed * dt).
+ *   5. s < S_end (the route's length): j = the largest index with S[j] <= s and j <= n - 2; if S[j+1] - s <= 1e-9 and
+ *      j + 1 <= n - 2, j + 1 is taken (a vehicle that lands on a vertex takes the segment ahead, whatever the rounding).
+ *      f = (s - S[j]) / (S[j+1] - S[j]) (0 on a zero-length segment); x, y, yaw = p[j] + f * (p[j+1] - p[j]);
+ *      v = speed if c' >= n0 else 0; steer = atan(L * (yaw[j+1] - yaw[j]) / (S[j+1] - S[j])) (0 on a zero-length segment).
+ *   6. s >= S_end: end = 1 ("stop") holds the last point, end = 0 ("leave") parks the vehicle at (JSIM_ROUTE_PARK,
+ *      JSIM_ROUTE_PARK, 0); v = 0 and steer = 0 either way.
+ *   7. A route of fewer than two points behaves as "stop" at its point (an empty one: at the origin).
+ *   8. The route index is clamped into the table.
+ * get() writes (x, y, v, yaw, 0, steer) of the current counter; step() is counter += 1, then the pose of the new counter.
+ * The prediction is unchanged (MovingObstaclesPrediction on the get() tuple).  A kind-3 row while no table is registered is
+ * stepped as kind 0. */
+#define JSIM_ROUTE_PARK 1000000 /* metres: where a route vehicle that has left stands, far from every road and finite */
+int jsim_loop_set_traffic_routes(jsim_ctx *ctx, int32_t n_routes, const double *x, const double *y, const double *yaw,
+                                 const int32_t *off /* host, [n_routes + 1] */);
 int jsim_loop_predict_obstacles(jsim_ctx *ctx, int32_t n_obs, const double *obst, int32_t n_steps, double *pred, void *stream);
 int jsim_loop_pre_tick(jsim_ctx *ctx, int32_t B, const double *x0, const int32_t *path_id, int64_t *traj_idx,
                        const int32_t *prev_path_len, int32_t *path_len, int32_t *col_flag, double *col_xy,

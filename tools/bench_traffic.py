@@ -5,6 +5,10 @@
              all; ScenarioLoop(traffic_of=...).run: gridded rollout + prediction, fused launches of traffic_chunk_ticks ticks)
   per_group  1024 intersections of four interacting egos (workloads.interacting_batch), each with its own set of four
              (InteractingLoop(traffic_of=...).run: host ticks)
+and with --routes two more, which differ in the vehicles' kind alone:
+  kind0      every ego its own set of four T-intersection cars
+  routes     every ego its own set of four route vehicles (kind="route") on the workload's planned routes, the k-th of a set
+             entering 2 s after the one before (closed_loop.traffic_on_routes), each entering again when the run is half over
 Prints one JSON line per way: ego-steps/s over `ticks` device-synchronised ticks after `warmup` ticks, ms per tick and the
 ego-ticks cut at the last tick.
 
@@ -13,6 +17,7 @@ The kernel-time share of the obstacle rollout and prediction comes from a profil
     python3 tools/bench_traffic.py --summarize OUT        # the share of every obstacle_* / *_pre_tick / MPC kernel
 
     python3 tools/bench_traffic.py [--egos 4096] [--ticks 60] [--warmup 10] [--ways shared per_ego per_group]
+    python3 tools/bench_traffic.py --routes [--egos 4096] [--ticks 300]      # the ways kind0 and routes
 """
 import argparse
 import importlib
@@ -30,9 +35,10 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--egos", type=int, default=4096)
     ap.add_argument("--horizon", type=int, default=30)
-    ap.add_argument("--ticks", type=int, default=60)
+    ap.add_argument("--ticks", type=int, default=None)
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--ways", nargs="+", default=["shared", "per_ego", "per_group"], choices=["shared", "per_ego", "per_group"])
+    ap.add_argument("--ways", nargs="+", default=None, choices=["shared", "per_ego", "per_group", "kind0", "routes"])
+    ap.add_argument("--routes", action="store_true", help="the ways kind0 and routes, 300 ticks unless --ticks is given")
     ap.add_argument("--summarize", metavar="DIR")
     a = ap.parse_args()
     if a.summarize:
@@ -42,7 +48,8 @@ def main():
     W = pkg.workloads
     routes = W.route_table(False)[0]
     T, B = a.horizon, a.egos
-    for way in a.ways:
+    ticks = a.ticks if a.ticks is not None else (300 if a.routes else 60)
+    for way in a.ways or (["kind0", "routes"] if a.routes else ["shared", "per_ego", "per_group"]):
         if way == "per_group":
             batch, sizes = W.interacting_batch(routes, B // 4, T, seed=1)
             eng, x0 = W.make_engine(routes, batch, T, "cuda:0")
@@ -50,11 +57,20 @@ def main():
             loop = pkg.InteractingLoop(eng, x0, group_sizes=sizes, obstacle_specs=sets, max_age=W.MAX_AGE, traffic_of=tog)
         elif way == "shared":
             loop = scenario_loop(pkg, routes, B, T, W.OBSTACLE_SPECS)
+        elif way == "kind0":
+            sets = [[dict(direction=1 if (e + k) % 2 else -1, turning=bool((e + k) % 3), speed=(15 + (e + 3 * k) % 11) / 3.6, offset=2.0 * k or None)
+                     for k in range(4)] for e in range(B)]
+            loop = scenario_loop(pkg, routes, B, T, sets, traffic_of=list(range(B)))
+        elif way == "routes":
+            dt = 0.2                                                  # the engines' tick (workloads.make_engine)
+            sets = [pkg.traffic_on_routes([routes[(e + 5) % len(routes)]], (15 + e % 11) / 3.6, 2.0, 4, period=(ticks // 2 or 1) * dt)
+                    for e in range(B)]
+            loop = scenario_loop(pkg, routes, B, T, sets, traffic_of=list(range(B)))
         else:
             sets, tof = W.traffic_batch(B, seed=2, vehicles=4)
             loop = scenario_loop(pkg, routes, B, T, sets, traffic_of=tof)
-        dt = timed_run(loop, a.warmup, a.ticks)
-        print(json.dumps({"way": way, **loop_fields(loop, a.ticks, dt)}), flush=True)
+        secs = timed_run(loop, a.warmup, ticks)
+        print(json.dumps({"way": way, **loop_fields(loop, ticks, secs), "route_points": [len(r) for r in loop.obst.routes]}), flush=True)
 
 
 if __name__ == "__main__":
