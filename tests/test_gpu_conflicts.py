@@ -12,9 +12,9 @@ import torch
 import conflict_cases as TC
 import conflicts_numpy as CN
 from gpu_helpers import W, check_guarded, guarded_outputs, iroutes, loop_engine  # noqa: F401
+from recorder_checks import conflicts_equal_restatement as assert_equals_restatement, conflicts_restate_recorder as _restate_recorder
 
 pytestmark = pytest.mark.gpu
-BAR = 1e-12
 KEYS = ("clear", "who", "row", "hit_tick", "hit_frame", "hit_xy")
 POISON_I, POISON_D = -85, -8.5e85                                      # values no output can take
 SPEC = [(k, np.float64, (2,) if k == "hit_xy" else (), POISON_D) if k in ("clear", "hit_xy") else (k, np.int32, (), POISON_I) for k in KEYS]
@@ -53,22 +53,6 @@ def launch(pkg, eng, A, w, n=TC.N, egos=None, mates=None):
 @pytest.fixture(scope="module")
 def whole(pkg, eng, arrays):
     return {w: launch(pkg, eng, arrays, w) for w in TC.WINDOWS}
-
-
-def clear_err(got, ref):
-    assert np.array_equal(np.isnan(got), np.isnan(ref))
-    ok = ~np.isnan(ref)
-    return float(np.max(np.abs(got[ok] - ref[ok]) / np.maximum(1.0, np.abs(ref[ok])))) if ok.any() else 0.0
-
-
-def assert_equals_restatement(out, ref, what):
-    for k in ("who", "row", "hit_tick", "hit_frame"):
-        assert np.array_equal(out[k], ref[k]), (what, k)
-    assert np.array_equal(out["hit_xy"], ref["hit_xy"], equal_nan=True), what
-    err = clear_err(out["clear"], ref["clear"])
-    print(f"{what}: clear against the restatement, maximum error {err:.3g}")
-    assert err <= BAR, (what, err)
-    return err
 
 
 def test_all_cases_in_one_launch(pkg, eng, arrays, whole):
@@ -142,13 +126,6 @@ def _loop(pkg, W, iroutes, traffic=False):
     if traffic:                                                     # egos 0 and 1 meet the cyclist, ego 2's set is empty
         return pkg.ScenarioLoop(eng, x0, [[cyclist], []], hist_cap=K, max_age=60, frame_window=20, traffic_of=np.array([0, 0, 1]), record=K)
     return pkg.ScenarioLoop(eng, x0, [cyclist], hist_cap=K, max_age=60, frame_window=20, record=K)
-
-
-def _restate_recorder(r, res):
-    obs = r.obs.cpu().numpy() if r.obs is not None else None
-    shapes = r.loop.eng.vehicle_shapes
-    return CN.eval_conflicts(r.rec.cpu().numpy(), r.flags.cpu().numpy(), obs, r.x0_first.cpu().numpy(), r.loop.x0_spawn.cpu().numpy(),
-                             res["veh_range"], res["mate_range"], shapes, res["ego_shape"], res["frame_window"])
 
 
 def test_scenario_loop_with_a_cyclist(pkg, W, iroutes):

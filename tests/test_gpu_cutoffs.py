@@ -10,6 +10,7 @@ import torch
 
 from conftest import load_golden
 from gpu_helpers import W, iroutes, loop_engine  # noqa: F401
+from recorder_checks import assert_replay_equals_live, assert_replay_equals_run1, live_rows, run1_rows
 
 pytestmark = pytest.mark.gpu
 
@@ -60,27 +61,9 @@ def test_interacting_reference_loop_recorded_and_replayed(pkg):
     assert np.array_equal(out["hit"], t[:, :, 8] != 0) and int(out["hit"].sum()) == int(t[:, :, 8].sum()) >= 10
 
 
-def live_rows(rows):
-    """The per-tick reads of a live loop, stacked like the replay's outputs.  A tick the glue refused keeps the loop's col_flag as it
-    was; the replay reports no hit there (the header's rule), so that is what the live series says too."""
-    d = {k: torch.stack([r[k] for r in rows]) for k in rows[0]}
-    d["hit"] = torch.where(d["status"] == 0, d["hit"], torch.zeros_like(d["hit"]))
-    return d
-
-
 def same(a, b):
     """torch.equal with NaN equal to NaN."""
     return torch.equal(a.nan_to_num(nan=-7.0), b.nan_to_num(nan=-7.0)) if a.is_floating_point() else torch.equal(a, b)
-
-
-def assert_replay_equals_live(rep, live, what, keys=("status", "idx", "cut", "hit")):
-    for k in keys:
-        assert torch.equal(rep[k], live[k].to(rep[k].dtype)), (what, k)
-    hit = rep["hit"] != 0
-    assert bool(torch.isnan(rep["col_xy"][~hit]).all()) and bool((rep["first"][~hit] == -1).all()), what
-    assert bool(torch.isfinite(rep["col_xy"][hit]).all()) and bool((rep["first"][hit] >= 0).all()), what
-    if "col_xy" in live:
-        assert torch.equal(rep["col_xy"][hit], live["col_xy"][hit]) and torch.equal(rep["first"][hit], live["first"][hit]), what
 
 
 SCENARIO = {"truncate": 13, "speed_cutoff": 20}     # mode -> horizon
@@ -165,24 +148,6 @@ def test_overflowed_recorder_replays_what_it_holds(pkg, W, iroutes):
     for k in KEYS:
         assert half[k].shape[0] == S_K // 2 and np.array_equal(half[k], full[k][: S_K // 2], equal_nan=True), k
     assert np.array_equal(half["carry"], b.recorder._cutoffs_device(n=S_K // 2)["carry"].cpu().numpy())
-
-
-def run1_rows(loop, K):
-    """K x run(1) of a loop: the live path_len, col_flag, pre_status and progress index behind every tick, and which egos the tick
-    respawned (their progress index has been reset by then)."""
-    eng, pre = loop.loop.eng, loop.pre
-    rows, resp = [], []
-    for _ in range(K):
-        loop.run(1)
-        rows.append({"status": pre.status.clone(), "idx": pre.traj_idx.clone(), "hit": pre.col_flag.clone(), "cut": eng.path_len.clone()})
-        resp.append((loop.loop.age == 0).clone())
-    torch.cuda.synchronize()
-    return live_rows(rows), torch.stack(resp)
-
-
-def assert_replay_equals_run1(rep, live, resp, what):
-    assert_replay_equals_live(rep, live, what, keys=("status", "cut", "hit"))
-    assert torch.equal(rep["idx"][~resp], live["idx"][~resp].to(torch.int32)), what
 
 
 def test_traffic_sets_and_vehicle_shapes(pkg, W, iroutes):

@@ -12,10 +12,10 @@ import conflict_cases as TC
 import gap_cases as GC
 import gaps_numpy as GN
 from gpu_helpers import W, check_guarded, guarded_outputs, iroutes, loop_engine  # noqa: F401
+from recorder_checks import GAPS_ALL as ALL, gaps_assert_same as assert_same, gaps_check_recorder as check_recorder  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 KEYS = ("off", "ep_gap", "ep_tick", "ep_who", "ep_off")
-ALL = ("off", "gap", "who", "ep_gap", "ep_tick", "ep_who", "ep_off")
 POISON = {"off": 85, "ep_gap": -85, "ep_tick": -85, "ep_who": -85, "ep_off": -85}   # values no output can take
 SPEC = [(k, np.int8, (8,), POISON[k]) if k == "off" else (k, np.int32, (), POISON[k]) for k in KEYS]
 
@@ -55,11 +55,6 @@ def launch(pkg, eng, A, window, within, n=GC.N, rc_want=0, **over):
         return out
     out["gap"], out["who"] = pkg.history.gap_per_tick(out["off"])
     return out
-
-
-def assert_same(out, ref, what):
-    for k in ALL:
-        assert out[k].dtype == ref[k].dtype and np.array_equal(out[k], ref[k]), (what, k)
 
 
 @pytest.mark.parametrize("rule", GC.RULES)
@@ -115,37 +110,6 @@ def test_a_gap_within_w_is_the_merged_kernels_contact(pkg, eng, arrays, which):
 # ---- live recorders ----
 CYCLIST = dict(L=1.0, width=0.45, extra_length=0.64)
 T = 13
-
-
-def restate_recorder(r, res):
-    obs = r.obs.cpu().numpy() if r.obs is not None else None
-    n = res["off"].shape[0]
-    return GN.eval_gaps(r.rec[:n].cpu().numpy(), r.flags[:n].cpu().numpy(), None if obs is None else obs[:n], r.x0_first.cpu().numpy(),
-                        r.loop.x0_spawn.cpu().numpy(), res["veh_range"], res["mate_range"], r.loop.eng.vehicle_shapes, res["ego_shape"],
-                        res["window"], GN.WITHIN[res["within"]])
-
-
-def check_recorder(pkg, r, n, what):
-    """Both rules at windows 20 and 63 against the restatement on the recorder's own arrays, the equivalence with conflicts(), and
-    gap_episodes' split."""
-    flags = r.flags[:n].cpu().numpy()
-    found = {}
-    for rule in GC.RULES:
-        for w in (20, 63):
-            res = r.gaps(window=w, within=rule)
-            assert res["off"].shape == (n, r.loop.eng.B, 8) and res["off"].dtype == np.int8 and (res["window"], res["within"]) == (w, rule)
-            assert_same(res, restate_recorder(r, res), (what, rule, w))
-            eps = pkg.history.gap_episodes(res, flags, r.loop.eng.dt)
-            assert [len(e) for e in eps] == r.episodes()["count"].tolist()
-            found[rule, w] = [e["gap"] for ep in eps for e in ep]
-    wide = r.gaps(window=20)
-    assert wide["within"] == "episode"
-    for w in (0, 1, 3, 20):
-        contact = r.conflicts(frame_window=w)["contact"]
-        assert np.array_equal((wide["gap"] >= 0) & (wide["gap"] <= w), contact), (what, w)
-        assert np.array_equal(r.gaps(window=w)["gap"] >= 0, contact), (what, w)
-    print(f"{what}: episode gaps at window 63 {found['episode', 63]}; under the record rule {found['record', 63]}")
-    return found
 
 
 def test_scenario_loop_with_traffic_sets(pkg, W, iroutes):

@@ -21,22 +21,13 @@ import torch
 import headway_cases as HC
 import headway_numpy as HN
 from gpu_helpers import W, check_guarded, guarded_outputs, iroutes, loop_engine  # noqa: F401
+from recorder_checks import HEADWAY_BARS as BARS, HEADWAY_INTS as INTS, HEADWAY_KEYS as KEYS, HEADWAY_PLACES as PLACES, HEADWAY_TICKS as TICKS
+from recorder_checks import headway_check_recorder as check_recorder, headway_errors as errors, headway_same_bits as same_bits
 
 pytestmark = pytest.mark.gpu
-INTS = ("lead", "ttc_who", "ep_i")
-PLACES = ("gap", "lat", "rate")
-TICKS = ("lead_gap", "thw", "ttc", "u_ego")
-DOUBLES = TICKS + ("ep_d",) + PLACES
-KEYS = ("lead", "lead_gap", "thw", "ttc", "ttc_who", "u_ego", "ep_i", "ep_d") + PLACES      # the entry point's order
 WIDTH = {"ep_i": HN.NI, "ep_d": HN.ND, "gap": 8, "lat": 8, "rate": 8}
 POISON_I, POISON_D = -85, -8.5e85                                      # values no output can take
 SPEC = [(k, np.int32 if k in INTS else np.float64, (WIDTH[k],) if k in WIDTH else (), POISON_I if k in INTS else POISON_D) for k in KEYS]
-OF_VALUE = ("thw", "ttc", "ep_d.thw_min", "ep_d.ttc_min", "ep_d.thw_mean")   # relative to the value itself
-EP_D = ("gap_min", "thw_min", "ttc_min", "thw_mean")
-SEEN = {"gap": 7.11e-15, "lat": 3.67e-15, "rate": 1.59e-15, "lead_gap": 5.11e-15, "thw": 2.47e-16, "ttc": 1.01e-15, "u_ego": 2.22e-16,
-        "ep_d.gap_min": 0.0, "ep_d.thw_min": 0.0, "ep_d.ttc_min": 0.0, "ep_d.thw_mean": 2.39e-16}    # the first run's largest errors, rounded up
-CAP = 1e-12
-BARS = {k: min(4.0 * v, CAP) for k, v in SEEN.items()}
 FREE = [b for b, c in enumerate(HC.cases()) if c["group"] is None]      # the cases that are nobody's mate: any sub-batch of them stands alone
 
 
@@ -89,41 +80,6 @@ def launch(pkg, eng, A, n=HC.N, egos=None, rc_want=0, places=True, margin=HC.LAU
                                         a["n_pts"], p(a["px"]), p(a["py"]), p(a["pyaw"]), a["n_paths"], p(a["path_off"]), p(a["arc"]),
                                         a["margin"], *[p(a[k]) for k in KEYS], None)
     return check_guarded(pkg, eng, "jsim_loop_eval_headway", spec, buf, n, rc, rc_want, nothing=a["n"] == 0 or a["B"] == 0)
-
-
-def relative(out, ref, of_value):
-    """|device - restatement| relative to max(1, |restatement|), or to the value itself; inf and NaN must sit in the same slots."""
-    assert out.shape == ref.shape and np.array_equal(np.isnan(out), np.isnan(ref)) and np.array_equal(np.isinf(out), np.isinf(ref))
-    fin = np.isfinite(ref)
-    assert np.array_equal(out[~fin & ~np.isnan(ref)], ref[~fin & ~np.isnan(ref)])     # the sign of an inf
-    scale = np.abs(ref[fin]) if of_value else np.maximum(1.0, np.abs(ref[fin]))
-    err = np.abs(out[fin] - ref[fin])
-    assert np.all(err[scale == 0.0] == 0.0)                               # (a 0.0 is exact on both sides)
-    return float((err[scale > 0.0] / scale[scale > 0.0]).max(initial=0.0))
-
-
-def errors(out, ref, what, worst=None, keys=DOUBLES):
-    """Integers exact; inf and NaN where the restatement has them; prints the largest relative error per double output (ep_d by
-    column), then asserts each within its bar.  `worst` collects the largest over several calls."""
-    seen = {}
-    for k in INTS:
-        assert out[k].dtype == np.int32 and np.array_equal(out[k], ref[k]), (what, k, np.argwhere(out[k] != ref[k])[:5])
-    for k in keys:
-        if k == "ep_d":
-            seen.update({f"ep_d.{name}": relative(out[k][..., j], ref[k][..., j], f"ep_d.{name}" in OF_VALUE) for j, name in enumerate(EP_D)})
-        else:
-            seen[k] = relative(out[k], ref[k], k in OF_VALUE)
-    print(f"{what}: largest relative error {seen}")
-    if worst is not None:
-        for k, v in seen.items():
-            worst[k] = max(worst.get(k, 0.0), v)
-    assert all(v <= BARS[k] for k, v in seen.items()), (what, {k: v for k, v in seen.items() if v > BARS[k]})
-    return seen
-
-
-def same_bits(a, b, what, keys=KEYS):
-    for k in keys:
-        assert a[k].dtype == b[k].dtype and a[k].tobytes() == b[k].tobytes(), (what, k)
 
 
 def test_all_cases_in_one_launch(pkg, eng, arrays, restated, whole):
@@ -215,33 +171,6 @@ def test_two_mates_see_each_other_antisymmetrically(arrays, whole):
 
 # ---- live recorders ----
 T = 13
-
-
-def restate_recorder(r, res, paths):
-    n = res["lead"].shape[0]
-    obs = r.obs.cpu().numpy() if r.obs is not None else None
-    return HN.eval_headway(r.rec[:n].cpu().numpy(), r.flags[:n].cpu().numpy(), None if obs is None else obs[:n], r.x0_first.cpu().numpy(),
-                           r.loop.x0_spawn.cpu().numpy(), res["veh_range"], res["mate_range"], r.loop.eng.vehicle_shapes, res["ego_shape"],
-                           res["path_id"], paths, res["margin"])
-
-
-def check_recorder(pkg, r, n, what, worst, paths=None, path_id=None, margin=0.0):
-    """headway() against the restatement on the recorder's own arrays, places=False, and headway_episodes' split."""
-    eng = r.loop.eng
-    res = r.headway(paths=paths, path_id=path_id, margin=margin)
-    assert res["lead"].shape == (n, eng.B) and res["gap"].shape == (n, eng.B, 8) and res["ep_i"].shape == (n, eng.B, 7) and res["ep_d"].shape == (n, eng.B, 4)
-    assert res["margin"] == margin
-    ref = restate_recorder(r, res, eng.paths if paths is None else paths)
-    errors(res, ref, what, worst)
-    bare = r.headway(paths=paths, path_id=path_id, margin=margin, places=False)
-    assert not any(k in bare for k in PLACES)
-    same_bits(bare, res, what, keys=[k for k in KEYS if k not in PLACES])
-    eps = pkg.history.headway_episodes(res, r.flags[:n].cpu().numpy(), eng.dt)
-    assert [len(e) for e in eps] == r.episodes()["count"].tolist()
-    assert all(e["time_following"] == e["lead_ticks"] * eng.dt for ep in eps for e in ep)
-    print(f"{what}: per ego (ticks, lead ticks, smallest gap, smallest thw, smallest ttc) of the first episode "
-          f"{[(e[0]['n'], e[0]['lead_ticks'], round(e[0]['gap_min'], 3), round(e[0]['thw_min'], 3), round(e[0]['ttc_min'], 3)) for e in eps]}")
-    return res
 
 
 def test_scenario_loop_its_fork_and_an_interacting_loop(pkg, W, iroutes):

@@ -14,14 +14,13 @@ import torch
 import tracking_cases as KC
 import tracking_numpy as TN
 from gpu_helpers import W, check_guarded, guarded_outputs, iroutes, loop_engine  # noqa: F401
+from recorder_checks import TRACKING_INTS as INTS, tracking_check_recorder as check_recorder, tracking_errors as errors
 
 pytestmark = pytest.mark.gpu
-INTS, DOUBLES = ("idx", "seg", "ep_i"), ("s", "d", "e_yaw", "ep_d")
 KEYS = ("idx", "seg", "s", "d", "e_yaw", "ep_i", "ep_d")
 WIDTH = {"ep_i": TN.NI, "ep_d": TN.ND}
 POISON_I, POISON_D = -85, -8.5e85                                      # values no output can take
 SPEC = [(k, np.int32 if k in INTS else np.float64, (WIDTH[k],) if k in WIDTH else (), POISON_I if k in INTS else POISON_D) for k in KEYS]
-BAR = 1e-12
 
 
 @pytest.fixture(scope="module")
@@ -58,25 +57,6 @@ def launch(pkg, eng, A, n=KC.N, egos=None, rc_want=0, **over):
     rc = eng.lib.jsim_loop_eval_tracking(eng._ctx, a["B"], a["n"], p(a["rec"]), p(a["flags"]), p(a["path_id"]), a["n_pts"], p(a["px"]), p(a["py"]),
                                          p(a["pyaw"]), a["n_paths"], p(a["path_off"]), p(a["arc"]), *[p(a[k]) for k in KEYS], None)
     return check_guarded(pkg, eng, "jsim_loop_eval_tracking", SPEC, buf, n, rc, rc_want, nothing=a["n"] == 0 or a["B"] == 0)
-
-
-def errors(out, ref, what):
-    """Integers exact, NaN where the restatement has NaN; returns the largest |device - restatement| / max(1, |restatement|) per
-    double output (ep_d by column), after asserting it is within the bar."""
-    worst = {}
-    for k in INTS:
-        assert out[k].dtype == np.int32 and np.array_equal(out[k], ref[k]), (what, k)
-    for k in DOUBLES:
-        assert out[k].shape == ref[k].shape and np.array_equal(np.isnan(out[k]), np.isnan(ref[k])), (what, k)
-        with np.errstate(invalid="ignore"):
-            rel = np.nan_to_num(np.abs(out[k] - ref[k]) / np.maximum(1.0, np.abs(ref[k])), nan=0.0)
-        if k == "ep_d":
-            worst.update({f"ep_d.{name}": float(rel[..., j].max(initial=0.0)) for j, name in enumerate(("d_max", "d2_mean", "yaw_max", "s_first", "s_last"))})
-        else:
-            worst[k] = float(rel.max(initial=0.0))
-    print(f"{what}: largest relative error {worst}")
-    assert max(worst.values()) <= BAR, (what, worst)
-    return worst
 
 
 def same_bits(a, b, what):
@@ -138,29 +118,6 @@ def test_sub_batches_and_single_egos_are_bit_identical(pkg, eng, arrays):
 
 # ---- live recorders ----
 T = 13
-
-
-def restate_recorder(r, n, paths, path_id):
-    return TN.eval_tracking(r.rec[:n].cpu().numpy(), r.flags[:n].cpu().numpy(), path_id, paths)
-
-
-def check_recorder(pkg, r, n, what, paths=None, path_id=None):
-    """tracking() against the restatement on the recorder's own arrays, and tracking_episodes' split."""
-    eng = r.loop.eng
-    res = r.tracking(paths=paths, path_id=path_id)
-    assert res["idx"].shape == (n, eng.B) and res["ep_i"].shape == (n, eng.B, 2) and res["ep_d"].shape == (n, eng.B, 5)
-    use_paths = eng.paths if paths is None else paths
-    own = eng.path_id.cpu().numpy() if paths is None else np.zeros(eng.B, dtype=np.int32)
-    assert np.array_equal(res["path_id"], own if path_id is None else np.broadcast_to(path_id, (eng.B,)))
-    ref = restate_recorder(r, n, use_paths, res["path_id"])
-    errors(res, ref, what)
-    assert len(res["arc"]) == len(use_paths) and all(np.array_equal(a, b) for a, b in zip(res["arc"], ref["arc"]))
-    assert (res["idx"] >= 0).all() and np.isfinite(res["d"]).all()
-    eps = pkg.history.tracking_episodes(res, r.flags[:n].cpu().numpy(), eng.dt, stations=[1.0, 5.0], free_speed=float(eng.speed.max()))
-    assert [len(e) for e in eps] == r.episodes()["count"].tolist()
-    print(f"{what}: path ids {res['path_id'].tolist()}, per ego (ticks, d_max, d_rms, progress, delay) of the first episode "
-          f"{[(e[0]['n'], round(e[0]['d_max'], 3), round(e[0]['d_rms'], 3), round(e[0]['progress'], 2), round(e[0]['delay'], 2)) for e in eps]}")
-    return res
 
 
 def shifted(route, d):

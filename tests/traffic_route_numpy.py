@@ -113,7 +113,7 @@ def stepped(route, n_ticks, end, speed, offset, s0, dt, period, L):
     for _ in range(n_ticks):
         moving = c >= n0
         if route.shape[0] < 2:
-            p = route[0]
+            p = route[0] if route.shape[0] == 1 else np.zeros(3)           # 7 (an empty route: at the origin)
             g = [p[0], p[1], 0.0, p[2], 0.0, 0.0]
         elif s < S[-1]:
             j = 0
